@@ -10,10 +10,18 @@ tracks ITS sequences as one batch with gradslam_amd.slam.PointFusion(odom="gradi
 serves all sequences of the rank at once (workgroup -> sequence), which is how one GPU is filled -- one 640x480
 sequence alone is a chain of ~50 dependent launches.  A step = one frame of every sequence through the
 whole hot path: back-projection / normals, target selection, 20 gradLM point-to-plane ICP iterations (40 exact 1-NN
-searches), projective association, fuse + append.  Frames are resident in HBM before the timed region.  Total work
+searches), projective association, fuse + append.  Frames are resident in HBM before the timed region: up to 64 per
+sequence (and in every --full run) generated on the host by synthetic.make_sequence, beyond that on the device by
+make_sequences_on_device (same scene and camera path, its own seeded holes and colours).  Total work
 is fixed (B sequences x K frames) as N grows: "scaling": "strong".  value = B * K / max-over-ranks time.
 
-The JSON line also carries
+A plain run does only what the headline needs: generate the frames, warm up, time exactly K steps, gather the result
+(N > 1) and print the JSON line (with ms_per_step = milliseconds of one timed step).
+  --dump-outputs DIR   also write what the timed path returned to its caller after its last step as DIR/<name>.npy
+                       (see dump_outputs; the inputs are seeded, so the same arguments give the same inputs)
+  --full               also run everything else below (each still switchable off with its --no-* option):
+
+The JSON line of a --full run also carries
   roofline      the dominant kernel (fused exact grid 1-NN + Gauss-Newton linearisation, batched over the
                 sequences): algorithmic bytes / its mean launch duration, measured with HIP events on the launch
                 stream inside the library in a second pass over the SAME frames from the same map state (event
@@ -23,7 +31,9 @@ The JSON line also carries
                 timed on this machine's host cores in the same run on a bounded sample of the same workload, rank 0,
                 N = 1 only, with the CPU oracle (the C port, oracle/) as a second field; parity of the timed GPU poses
                 against both and against the committed reference goldens (ate_vs_reference_live_m, ate_vs_oracle_m,
-                ate_vs_reference_golden).
+                ate_vs_reference_golden);
+  secondary     the other BASELINE configurations (secondary_measurements);
+  segments      (--workload c5) ms per frame of consecutive stretches of the timed region against the map size.
 """
 import argparse
 import ctypes
@@ -56,11 +66,16 @@ def parse():
     ap.add_argument("--workload", default="c4", choices=["c4", "c5"],
                     help="c4: B x 640x480 PointFusion (BASELINE configs[1]/[3]); c5: one 1296x968 sequence, growing map")
     ap.add_argument("--weak", action="store_true", help="weak scaling: --batch sequences PER GPU (8 N in total by default)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (configs 2, 3 and 5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the poses and a seeded sample of the maps of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline pass, the CPU baseline, the parity checks against the reference, the "
+                         "secondary configurations and (c5) the per-segment timings; off: the headline alone")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary measurements (configs 2, 3 and 5)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-frames", type=int, default=6,
                     help="timed frames of the CPU baseline sample (reference and oracle port: ~10 + ~13 s of CPU work at the default)")
-    ap.add_argument("--no-roofline-pass", action="store_true")
+    ap.add_argument("--no-roofline-pass", action="store_true", help="--full: skip the roofline pass")
     return ap.parse_args()
 
 
@@ -82,6 +97,17 @@ def spawn_ranks(args):
     sys.stdout.write(out)
     sys.stdout.flush()
     sys.exit(max(rcs))
+
+
+def host_workers():
+    """host cores this process may use: its CPU affinity, capped by OMP_NUM_THREADS where the environment sets it (a
+    shared host can grant fewer cores than it has; more workers than cores only slow the generation down)"""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    cap = os.environ.get("OMP_NUM_THREADS", "")
+    return max(1, min(n, int(cap))) if cap.isdigit() and int(cap) > 0 else n
 
 
 def _make(a):
@@ -114,7 +140,7 @@ def make_sequences(seeds, L, Hh, Ww, chunk=None):
                 if k in ("LD_PRELOAD", "HSA_TOOLS_LIB", "HSA_TOOLS_REPORT_LOAD_FAILURE") or k.startswith(("ROCP", "ROCPROF", "ROCTX")):
                     scrub[k] = os.environ.pop(k)
         try:
-            pool = mp.get_context("spawn" if profiled else "fork").Pool(min(len(jobs), os.cpu_count() or 1, 96))
+            pool = mp.get_context("spawn" if profiled else "fork").Pool(min(len(jobs), host_workers(), 96))
             try:
                 parts = pool.map(_make, jobs)
             finally:
@@ -136,6 +162,62 @@ def frames_on_device(gs, seqs, device):
     poses = st("poses")
     poses[:, 1:] = poses[:, :1]  # only the first pose is given; the rest is recovered by ICP
     return gs.RGBDImages(st("colors"), st("depths"), st("intrinsics"), poses)
+
+
+HOST_FRAMES_MAX = 64   # frames per sequence up to which a plain run generates them on the host (make_sequences)
+
+
+def scene_depth_torch(x_w, y_w):
+    """synthetic._scene_depth_at ("wave", the benchmark scene) on torch tensors"""
+    import torch
+    return 2.0 + 0.3 * torch.sin(3.0 * x_w + 0.4) * torch.cos(2.5 * y_w) + 0.2 * x_w
+
+
+def make_sequences_on_device(gs, seeds, L, Hh, Ww, device, hole_frac=0.05, chunk=16):
+    """A long plain run's frames, generated on the device: the scene and camera path of synthetic.make_sequence
+    (the same fixed-point ray cast, in float64, once per distinct point of the back-and-forth path), with the holes
+    and colours drawn from a torch generator seeded by the sequence's seed.  On the host the ray cast costs ~0.3 s per
+    640x480 frame, minutes for a few thousand frames.  Returns (RGBDImages with only the first pose given, per-sequence
+    dicts holding the ground-truth poses)."""
+    import torch
+    from gradslam_amd.datasets import synthetic
+    f64 = dict(dtype=torch.float64, device=device)
+    K = synthetic.tum_intrinsics(Hh, Ww)
+    v, u = torch.meshgrid(torch.arange(Hh, **f64), torch.arange(Ww, **f64), indexing="ij")
+    rx = (u - float(K[0, 2])) / float(K[0, 0])
+    ry = (v - float(K[1, 2])) / float(K[1, 1])
+    B = len(seeds)
+    gt = np.stack([synthetic.gt_pose(s) for s in range(L)])                      # (L, 4, 4), as make_sequence
+    path = [synthetic.path_parameter(s) for s in range(L)]
+    uniq = sorted(set(path))
+    phase = torch.tensor([0.1 * s for s in seeds], **f64).view(B, 1, 1, 1)
+    geo = torch.empty((B, len(uniq), Hh, Ww), dtype=torch.float32, device=device)
+    for c0 in range(0, len(uniq), chunk):
+        T = torch.from_numpy(np.stack([synthetic.gt_pose(p) for p in uniq[c0:c0 + chunk]]).astype(np.float64)).to(device)
+        R = [[T[:, i, j].view(1, -1, 1, 1) for j in range(3)] for i in range(3)]
+        t = [T[:, i, 3].view(1, -1, 1, 1) for i in range(3)]
+        d = torch.full((B, T.shape[0], Hh, Ww), 2.0, **f64)
+        for _ in range(30):   # the fixed point of make_sequence: world z of the ray point = the height field
+            x, y = rx * d, ry * d
+            pw = [x * R[i][0] + y * R[i][1] + d * R[i][2] + t[i] for i in range(3)]
+            d = d + (scene_depth_torch(pw[0] + phase, pw[1]) - pw[2]) / R[2][2]
+        geo[:, c0:c0 + T.shape[0]] = d.float()
+    del d, x, y, pw
+    index = torch.tensor([uniq.index(p) for p in path], device=device)
+    depth = torch.empty((B, L, Hh, Ww, 1), dtype=torch.float32, device=device)
+    color = torch.empty((B, L, Hh, Ww, 3), dtype=torch.float32, device=device)
+    for b, sd in enumerate(seeds):
+        g = torch.Generator(device=device)
+        g.manual_seed(int(sd))
+        for f0 in range(0, L, chunk):
+            f1 = min(f0 + chunk, L)
+            holes = torch.rand((f1 - f0, Hh, Ww), generator=g, device=device) < hole_frac
+            depth[b, f0:f1, ..., 0] = geo[b].index_select(0, index[f0:f1]).masked_fill_(holes, 0.0)
+        torch.rand((L, Hh, Ww, 3), generator=g, device=device, out=color[b]).mul_(255.0)
+    del geo
+    Kd = torch.from_numpy(K[None]).to(device).expand(B, 1, 4, 4).contiguous()
+    poses = torch.from_numpy(gt[:1]).to(device).expand(B, L, 4, 4).contiguous()   # only the first pose is given
+    return gs.RGBDImages(color, depth, Kd, poses), [{"poses": gt} for _ in seeds]
 
 
 def run_steps(slam, pc, frames, prev, first, last, poses_out=None, after_step=None, events=None):
@@ -491,6 +573,41 @@ def secondary_measurements(gs, args, frames, device, barrier, Wm, K):
     return out
 
 
+DUMP_MAX_ROWS = 1 << 19   # sampled map rows in all: 4 attributes (10 floats) + the row index = 22 MB at most
+
+
+def dump_outputs(out_dir, poses, maps, seed=0):
+    """--dump-outputs: what PointFusion.step handed its caller, after the last timed step, as out_dir/<name>.npy.
+      poses.npy         (B, 4, 4) f32     the pose the last timed step returned for each sequence
+      trajectory.npy    (B, L, 4, 4) f32  the poses of every step (warm-up included)
+      map_counts.npy    (B,) f64          surfels in each sequence's map
+      map_rows.npy      (R, 2) f64        (sequence, row) of each sampled surfel: a fixed seeded sample of at most
+                                          DUMP_MAX_ROWS / B rows of every map (all of them when the map is smaller)
+      map_points.npy, map_normals.npy, map_colors.npy, map_features.npy   (R, 3 / 3 / 3 / F) f32 of those rows
+    All sequences of the run, in sequence order (gathered to rank 0 when N > 1)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(out_dir, name + ".npy"), a)  # noqa: E731
+    poses = poses.detach().float().cpu().numpy()
+    save("poses", poses[:, -1])
+    save("trajectory", poses)
+    counts = [int(p.shape[0]) for p in maps.points_list]
+    save("map_counts", np.asarray(counts, np.float64))
+    per_seq = DUMP_MAX_ROWS // max(len(counts), 1)
+    rows = []
+    for b, n in enumerate(counts):
+        idx = np.arange(n) if n <= per_seq else np.sort(np.random.default_rng([seed, b]).choice(n, per_seq, replace=False))
+        rows.append(idx)
+    save("map_rows", np.concatenate([np.stack([np.full(len(r), b), r], 1) for b, r in enumerate(rows)]).astype(np.float64)
+         if rows else np.zeros((0, 2)))
+    for k in ("points", "normals", "colors", "features"):
+        lst = getattr(maps, k + "_list")
+        if lst is None or not len(lst):
+            continue
+        parts = [t.index_select(0, torch.from_numpy(r).to(t.device)).float().cpu().numpy() for t, r in zip(lst, rows)]
+        save("map_" + k, np.concatenate(parts))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -526,8 +643,11 @@ def main():
     L = Wm + K
     mine = multigpu.shard_sequences(args.batch, world, rank)
     assert mine, "more GPUs than sequences"
-    seqs = make_sequences(mine, L, Hh, Ww)
-    frames = frames_on_device(gs, seqs, device)
+    if L <= HOST_FRAMES_MAX or args.full:   # the host generator: the goldens' inputs, what --full compares against
+        seqs = make_sequences(mine, L, Hh, Ww)
+        frames = frames_on_device(gs, seqs, device)
+    else:
+        frames, seqs = make_sequences_on_device(gs, mine, L, Hh, Ww, device)
     B_local = len(mine)
     slam = gs.slam.PointFusion(odom=args.odom, device=device)
     lib = _C.lib()
@@ -546,7 +666,7 @@ def main():
     gc.freeze()
 
     # ---------------- warm-up (untimed: map init + first ICP frames, allocator, kernels), then exactly K timed steps
-    run = timed_steps(gs, slam, frames, Wm, K, device, barrier, seg_every=25 if args.workload == "c5" else 0)
+    run = timed_steps(gs, slam, frames, Wm, K, device, barrier, seg_every=25 if args.workload == "c5" and args.full else 0)
     pc, elapsed_local, t_enq = run["pc"], run["elapsed"], run["t_enq"]
     elapsed = elapsed_local
     if world > 1:
@@ -555,7 +675,7 @@ def main():
         elapsed = float(t.item())
     n_map = [int(p.shape[0]) for p in pc.points_list]
     poses_local = run["poses"]  # (B_local, L, 4, 4) recovered trajectories of this rank's sequences
-    ate_gt = max(ate_np(poses_local[b].cpu().numpy(), seqs[b]["poses"]) for b in range(B_local))
+    ate_gt = max(ate_np(poses_local[b].cpu().numpy(), seqs[b]["poses"]) for b in range(B_local)) if args.full else None
 
     # ---------------- the only exchange step: final pose (+ map) gather over RCCL
     barrier()
@@ -575,6 +695,8 @@ def main():
     poses_sha = sha(all_poses)
     poses_sha_by_sequence = [sha(all_poses[b:b + 1]) for b in range(all_poses.shape[0])]
     n_map_all = [int(p.shape[0]) for p in all_maps.points_list] if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, all_poses, all_maps)
     # what every rank saw: its own clock around the K steps, its sequences, the fingerprint of its poses
     props = torch.cuda.get_device_properties(device)
     mine_info = {"rank": rank, "sequences": mine, "elapsed_s": elapsed_local, "ms_per_step": elapsed_local / K * 1e3,
@@ -597,7 +719,7 @@ def main():
 
     # ---------------- roofline pass: same frames from the same map state, HIP events inside the library
     roofline, roofline_hbm = None, None
-    if not args.no_roofline_pass and rank == 0:
+    if args.full and not args.no_roofline_pass and rank == 0:
         # a second pass over the same frames, from scratch (nothing of it exists while the timed region runs: a map
         # snapshot taken before the timed region cost it a few per cent): warm-up frames unprofiled, then the K steps
         pc2, prev2 = run_steps(slam, gs.Pointclouds(device=device), frames, None, 0, Wm)
@@ -714,7 +836,7 @@ def main():
                                 "step / wall time of a step / 8 TB/s"}
 
     cpu, ate_oracle, ate_ref, ate_refs = None, None, None, {}
-    if (Hh, Ww) == (480, 640) and args.odom == "gradicp" and L <= 64:
+    if args.full and (Hh, Ww) == (480, 640) and args.odom == "gradicp" and L <= 64:
         # the REAL reference's poses (oracle/make_golden_640.py) for every sequence of this rank that has a golden: seed 0
         # over 60 frames (pf640_l60.npz), seeds 1..7 over 25 frames -- the goldens cover the TIMED window of the default
         # run (frames 5 .. 24), and the record says for every sequence how many warm-up and how many timed frames it
@@ -734,7 +856,7 @@ def main():
         if rank == 0 and "0" in ate_refs:
             ate_ref = dict(ate_refs["0"], source=ate_refs["0"]["source"] + " (unmodified gradslam PointFusion on the same sequence)")
     ate_ref_live = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         port, op = cpu_baseline(seqs[0], args.cpu_frames, args.odom)
         ate_oracle = ate_np(poses_local[0, :op.shape[0]].cpu().numpy(), op)
         # gradslam's own CPU path, timed here and now; the oracle port stays next to it as a second field
@@ -750,7 +872,7 @@ def main():
 
     seg_out = run["segments"]
     second = None
-    if rank == 0 and world == 1 and not args.no_secondary and args.workload == "c4" and (Hh, Ww) == (480, 640):
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and args.workload == "c4" and (Hh, Ww) == (480, 640):
         second = secondary_measurements(gs, args, frames, device, barrier, Wm, K)
     if rank == 0:
         value = args.batch * K / elapsed
