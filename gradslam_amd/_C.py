@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("GRADSLAM_HIP_LIB") or os.path.join(_HERE, "csrc", "li
 if os.environ.get("GRADSLAM_HIP_LIB"):   # (a bench line must not come from an experimental build unnoticed)
     import warnings
     warnings.warn("GRADSLAM_HIP_LIB overrides the product library: %s" % LIB_PATH, RuntimeWarning)
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _lib = None
 
@@ -133,6 +133,7 @@ _PROTOS = {
     "gs_lie_small_f32": [_i32, _vp, _vp, _vp],
     "gs_localize_far_stats_i64": [_vp, _i32, _i32, _i32, _i64, C.POINTER(C.c_int64), _vp],
     "gs_localize_list_stats_i64": [_vp, _i32, _i32, _i32, _i64, C.POINTER(C.c_int64), _vp],
+    "gs_localize_solve_stats_i64": [_vp, _i32, _i32, _i32, _i64, C.POINTER(C.c_int64), _vp],
     "gs_pointfusion_step_batch_f32": [C.POINTER(StepSeq), _i32, _i32, _i32, _i32, C.POINTER(IcpParams), _f, _f, _f, _i32, _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,

@@ -13,7 +13,7 @@
 
 #include "../../include/gradslam_hip.h"
 
-#define GS_ABI_VERSION 2
+#define GS_ABI_VERSION 3
 
 // sequences per launch of the batched (multi-sequence) kernels; larger batches run in chunks of this size
 constexpr int GS_MAX_BATCH = 8;

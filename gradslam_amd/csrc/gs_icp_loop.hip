@@ -278,6 +278,7 @@ struct IcpHalfLists {
   float4* lq;
   uint32_t* ls;
   int* lstat;
+  unsigned* weak_n;   // (list-building launch with GRADSLAM_HIP_ICP_WEAK_ROOM) weak lists flagged: a word of the sync record
 };
 
 // flags of an entry of the block's list of left-over queries (hard_q)
@@ -646,6 +647,13 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
         }
       }
       if (win >= 0 || (lane == 0 && key == ~0ull)) bslot_s[slot] = win;  // one writer: the winning lane
+      if (build_all && weak_room > 0.0f) {
+        // (diagnostics, gs_localize_solve_stats_i64: weak lists, one atomic per wave by its first active lane)
+        const unsigned long long wm = __ballot(weak && lane == 0);
+        if (wm && __builtin_amdgcn_mbcnt_hi((unsigned)(__builtin_amdgcn_read_exec() >> 32),
+                                            __builtin_amdgcn_mbcnt_lo((unsigned)__builtin_amdgcn_read_exec(), 0u)) == 0u)
+          atomicAdd(ql.weak_n, (unsigned)__popcll(wm));
+      }
       if (lane == 0) {
         if (FULL) {  // the transformed cloud of this iteration
           src_out[3 * s] = qx;
@@ -929,6 +937,11 @@ __global__ void __launch_bounds__(FS_BLOCK, 6) gs_icp_half_batch_kernel(const Ic
 
 #include "gs_icp_persist.h"
 
+// the persistent solve's sync record lives in the padding behind the one row of large solves (icp_carve: rowred)
+constexpr int ICP_ROWRED_DOUBLES = 32;
+static_assert(sizeof(double) * ICP_ROWRED_DOUBLES >= sizeof(double) * LIN_NV + sizeof(unsigned) * PS_WORDS,
+              "the sync record does not fit behind rowred + LIN_NV");
+
 static size_t icp_rows(int64_t n_src) { return (size_t)gs_ceil_div(n_src, FS_QPB); }  // >= ceil(n_src / LIN_BLOCK)
 
 // Launch geometry of a half-iteration: lanes per query G, blocks per sequence nb and row units per block upb.
@@ -1200,7 +1213,7 @@ static IcpScratch icp_carve(void* scratch, int64_t n_src) {
   char* p = reinterpret_cast<char*>(scratch);
   IcpScratch s;
   s.state = reinterpret_cast<GsIcpState*>(p); p += gs_align(sizeof(GsIcpState));
-  s.rowred = reinterpret_cast<double*>(p); p += gs_align(sizeof(double) * 32);
+  s.rowred = reinterpret_cast<double*>(p); p += gs_align(sizeof(double) * ICP_ROWRED_DOUBLES);
   s.best = reinterpret_cast<unsigned long long*>(p); p += gs_align(8 * (size_t)n_src);
   s.srcA = reinterpret_cast<float*>(p); p += gs_align(12 * (size_t)n_src);
   s.srcB = reinterpret_cast<float*>(p); p += gs_align(12 * (size_t)n_src);
@@ -1224,7 +1237,7 @@ static bool icp_grid_enabled() {
 
 extern "C" int64_t gs_icp_scratch_bytes(int64_t n_src, int64_t n_tgt) {
   if (n_src < 1) n_src = 1;
-  return (int64_t)(gs_align(sizeof(GsIcpState)) + gs_align(sizeof(double) * 32) + gs_align(8 * (size_t)n_src) + 2 * gs_align(12 * (size_t)n_src) +
+  return (int64_t)(gs_align(sizeof(GsIcpState)) + gs_align(sizeof(double) * ICP_ROWRED_DOUBLES) + gs_align(8 * (size_t)n_src) + 2 * gs_align(12 * (size_t)n_src) +
                    2 * gs_align(sizeof(double) * LIN_NV * icp_rows(n_src)) + gs_knn_grid_scratch_bytes(n_src, n_tgt) +
                    4096);
 }
@@ -1304,7 +1317,7 @@ static int icp_run(const float* src, int64_t n_src, const float* tgt, const floa
     IcpHalfBatch hb;
     hb.B = 1;
     hb.weak_room = 0.0f;
-    hb.l[0] = IcpHalfLists{nullptr, nullptr, nullptr};
+    hb.l[0] = IcpHalfLists{nullptr, nullptr, nullptr, nullptr};
     hb.w[0] = IcpHalfWide{nullptr, nullptr};
     for (int it = 0; it < prm->numiters; ++it) {
       float* cur = cloud(it);
@@ -1518,7 +1531,8 @@ struct IcpFinishBatch {
   GsIcpState* st[GS_MAX_BATCH];
   const float* compose16[GS_MAX_BATCH];
   float* out_T16[GS_MAX_BATCH];
-  const unsigned* sync[GS_MAX_BATCH];   // sync record of a persistent solve (NULL: none): a raised error word = NaN pose
+  unsigned* sync[GS_MAX_BATCH];   // sync record of a persistent solve (NULL: none): anything but a complete run = NaN pose
+  int nb, h0;                     // (persistent solve) blocks per sequence, first half-iteration it served
 };
 __global__ void __launch_bounds__(FS_BLOCK) gs_icp_finish_batch_kernel(const IcpFinishBatch fb, GsCount n_src_c, int buf,
                                                                        gs_icp_params prm) {
@@ -1533,8 +1547,16 @@ __global__ void __launch_bounds__(FS_BLOCK) gs_icp_finish_batch_kernel(const Icp
   icp_update_math((float)e1, sm, prm, it < GS_ICP_MAX_ITERS ? st->trace + 12 * it : nullptr);
   st->s[buf ^ 1] = sm;
   icp_write_result(sm, fb.compose16[b], fb.out_T16[b]);
-  if (fb.sync[b] && fb.sync[b][PS_ERROR] != 0u)   // a block of the persistent solve gave up waiting (gs_icp_persist.h): fail loudly
-    for (int i = 0; i < 16; ++i) fb.out_T16[b][i] = __builtin_nanf("");
+  // The persistent solve (gs_icp_persist.h) counts as run only if no block gave up waiting (error word), every one of its
+  // nb blocks arrived at every half-iteration it served, and its XCD handed out at least nb tickets: an XCD that got no
+  // block at all raises no error, and its partial rows and state are those of the launch before -- fail loudly instead.
+  if (unsigned* sy = fb.sync[b]) {
+    const unsigned arrived = sy[PS_ARRIVED], want = (unsigned)fb.nb * (unsigned)(2 * prm.numiters - fb.h0);
+    if (!(sy[PS_ERROR] == 0u && arrived == want && sy[PS_TICKET] >= (unsigned)fb.nb))
+      for (int i = 0; i < 16; ++i) fb.out_T16[b][i] = __builtin_nanf("");
+    sy[PS_NB] = (unsigned)fb.nb;   // (diagnostics: gs_localize_solve_stats_i64)
+    sy[PS_H0] = (unsigned)fb.h0;
+  }
 }
 
 static int64_t loc_lattice(int H, int W, int ds) { return (int64_t)((H + ds - 1) / ds) * ((W + ds - 1) / ds); }
@@ -1695,6 +1717,22 @@ static LocCarve loc_carve(const gs_localize_seq& q, int64_t n_lat) {
   return c;
 }
 
+// The persistent solve puts a sequence's blocks on ONE XCD of PS_CUS_PER_XCD CUs (gs_icp_persist.h): only a whole gfx950
+// device qualifies (a partitioned one shows fewer CUs).  Asked once per device.
+static bool ps_device_fits() {
+  constexpr int MAX_DEV = 64;
+  static signed char fits[MAX_DEV] = {};   // 0: not asked yet, 1: yes, -1: no
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return false;
+  if (fits[dev] == 0) {
+    hipDeviceProp_t p;
+    const bool ok = hipGetDeviceProperties(&p, dev) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0 &&
+                    p.multiProcessorCount == (int)(GS_XCDS * PS_CUS_PER_XCD);
+    fits[dev] = ok ? 1 : -1;
+  }
+  return fits[dev] == 1;
+}
+
 // grid_cleared: the caller has zeroed the first gs_knn_grid_clear_bytes() bytes of every sequence's grid scratch
 // (loc_carve().gm.g) on the stream already
 static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int ds, const gs_icp_params* prm,
@@ -1840,7 +1878,7 @@ static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int 
   const int ps_nb = (int)gs_ceil_div((int64_t)icp_rows(n_lat), ps_upb > 0 ? ps_upb : 1);
   bool persist_on = persist_env == 1 && ord_lists == 1 && !far_on && B <= (int)GS_XCDS && ps_upb <= PS_UPB &&
                     prm->numiters > lists_from + 1 && !getenv("GRADSLAM_HIP_ICP_TIMELINE") &&
-                    !getenv("GRADSLAM_HIP_ICP_LANES");
+                    !getenv("GRADSLAM_HIP_ICP_LANES") && ps_device_fits();
   for (int b = 0; b < B && persist_on; ++b) persist_on = gm[b].sorted_n != nullptr;
   const IcpHalfPlan plan = icp_half_plan(n_lat, B, far_on ? 4 : (persist_on ? 2 : 8));
   // (a block reads the lists of ONE group of row units: solves whose blocks walk several groups keep none)
@@ -1873,7 +1911,7 @@ static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int 
   // persistent kernel keeps the four nearest of a list in registers and falls back on the other four, lane by lane, before
   // anything is re-searched (gs_icp_persist.h).  (Measured with 4-entry lists and a later start, GRADSLAM_HIP_ICP_PERSIST_FROM
   // = 2 / 5 / 7 / 9 / 12: 7 924 / 7 857 / 7 872 / 7 816 / 7 763 frames/s against 7 623 without -- the earliest start won.)
-  int ps_it0 = prm->numiters;
+  int ps_it0 = prm->numiters, ps_h0 = 0;
   if (persist_on) {
     ps_it0 = lists_from + 1;
     if (ps_it0 >= prm->numiters) { persist_on = false; ps_it0 = prm->numiters; }
@@ -1889,7 +1927,8 @@ static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int 
                            &sc[b].state->s[h & 1], &sc[b].state->s[(h + 1) & 1], sc[b].state->trace, nullptr, nullptr,
                            nullptr, fm[b].cq, fm[b].c, fm[b].idx, fm[b].n};
       hb.w[b] = wide_on ? IcpHalfWide{wm[b].cq, wm[b].c} : IcpHalfWide{nullptr, nullptr};
-      hb.l[b] = lists_on ? IcpHalfLists{lm[b].lq, lm[b].ls, lm[b].stat} : IcpHalfLists{nullptr, nullptr, nullptr};
+      hb.l[b] = lists_on ? IcpHalfLists{lm[b].lq, lm[b].ls, lm[b].stat, lb.s[b].sync + PS_WEAK}
+                         : IcpHalfLists{nullptr, nullptr, nullptr, nullptr};
     }
     // lists: built behind the look-ahead search of iteration lists_from, tried from then on
     icp_half_launch<true>(plan, hb, n_src_c, prm, it, 0, st, lists_on && it > lists_from ? 2 : 0);
@@ -1927,7 +1966,7 @@ static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int 
     pb.B = B;
     pb.nb = ps_nb;
     pb.upb = ps_upb;
-    pb.h0 = h;
+    pb.h0 = ps_h0 = h;
     pb.tl_h = 0;
     pb.timeline = nullptr;
     for (int b = 0; b < B; ++b) {
@@ -1983,6 +2022,8 @@ static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int 
     GsProf prof(GS_PROF_SOLVE, 1.0, st);
     IcpFinishBatch fb;
     fb.B = B;
+    fb.nb = persist_on ? ps_nb : 0;
+    fb.h0 = persist_on ? ps_h0 : 0;
     for (int b = 0; b < B; ++b) {
       fb.partials_in[b] = sc[b].partials[(h + 1) & 1];
       fb.st[b] = sc[b].state;
@@ -2082,6 +2123,24 @@ extern "C" int gs_localize_list_stats_i64(const void* scratch, int H, int W, int
   GS_HIP(hipMemcpyAsync(h, lm.stat, sizeof(h), hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   for (int i = 0; i < 3 * GL_STAT_LAUNCHES; ++i) out192_host[i] = h[i];
+  return GS_OK;
+}
+
+extern "C" int gs_localize_solve_stats_i64(const void* scratch, int H, int W, int ds, int64_t map_rows, int64_t* out8_host,
+                                           void* stream) {
+  GS_REQUIRE(scratch && out8_host && H > 0 && W > 0 && ds > 0 && map_rows > 0, "bad arguments");
+  const int64_t n_lat = loc_lattice(H, W, ds);
+  gs_localize_seq q;
+  memset(&q, 0, sizeof(q));
+  q.scratch = const_cast<void*>(scratch);
+  q.map.capacity = map_rows; q.map.n_bound = map_rows;
+  const LocCarve cv = loc_carve(q, n_lat);
+  unsigned h[PS_WORDS];
+  hipStream_t st = gs_stream(stream);
+  GS_HIP(hipMemcpyAsync(h, cv.sc.rowred + LIN_NV, sizeof(h), hipMemcpyDeviceToHost, st));   // (the sync record: LocSeq::sync)
+  GS_HIP(hipStreamSynchronize(st));
+  static_assert(PS_WORDS == 8, "out8");
+  for (int i = 0; i < PS_WORDS; ++i) out8_host[i] = h[i];
   return GS_OK;
 }
 

@@ -40,8 +40,10 @@ constexpr int PS_CUS_PER_XCD = 32;             // the grid is 8 x this
 constexpr unsigned PS_SPIN_LIMIT = 1u << 22;   // polls before a block gives up (~ seconds)
 static_assert(PS_NQ <= PS_BLOCK - GS_WAVE && 2 * PS_UPB <= PS_BLOCK / GS_WAVE && PS_LM <= GL_SLOTS && PS_LM == 2 * gl_k<2>(), "block shape");
 
-// words of a sequence's sync record (zeroed by the prep launch of the frame)
-enum { PS_TICKET = 0, PS_ARRIVED = 1, PS_ERROR = 2, PS_WORDS = 8 };
+// words of a sequence's sync record (zeroed by the prep launch of every solve, persistent or not): ticket / arrival /
+// error words of the persistent solve; weak lists the list-building launch flagged (GRADSLAM_HIP_ICP_WEAK_ROOM); the block
+// count and first half-iteration the persistent solve was launched with (written by the finish launch; 0 / 0: it was not)
+enum { PS_TICKET = 0, PS_ARRIVED = 1, PS_ERROR = 2, PS_WEAK = 3, PS_NB = 4, PS_H0 = 5, PS_WORDS = 8 };
 
 struct IcpPersistSeq {
   const float* src_in;       // the cloud behind the first half of iteration it0 - 1 (read once)
@@ -76,12 +78,12 @@ GS_DEV unsigned ps_load_u32_sc1(const unsigned* p) {
   asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
   return v;
 }
-GS_DEV unsigned ps_atomic_inc_ret(unsigned* p) {
+GS_DEV unsigned ps_l2_inc_ret(unsigned* p) {
   unsigned v, one = 1u;
   asm volatile("global_atomic_add %0, %1, %2, off sc0\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p), "v"(one) : "memory");
   return v;
 }
-GS_DEV void ps_atomic_inc(unsigned* p) {
+GS_DEV void ps_l2_inc(unsigned* p) {
   unsigned one = 1u;
   asm volatile("global_atomic_add %0, %1, off" : : "v"(p), "v"(one) : "memory");
 }
@@ -707,7 +709,7 @@ GS_DEV void ps_half(const IcpPersistSeq& q, IcpPersistShared& L, PsRegs& r, cons
   // ---- arrive: the rows of this block are in the L2 before the counter says so
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   gs_barrier_lds();
-  if (threadIdx.x == 0) ps_atomic_inc(q.sync + PS_ARRIVED);
+  if (threadIdx.x == 0) ps_l2_inc(q.sync + PS_ARRIVED);
   PS_STAMP(5);
 }
 
@@ -721,7 +723,7 @@ __global__ void __launch_bounds__(PS_BLOCK) gs_icp_persist_kernel(const IcpPersi
   if ((int)xcc >= pb.B) return;              // sequence b lives on XCD b
   const IcpPersistSeq& q = pb.s[xcc];
   if (threadIdx.x == 0) {
-    L.ctl[0] = (int)ps_atomic_inc_ret(q.sync + PS_TICKET);
+    L.ctl[0] = (int)ps_l2_inc_ret(q.sync + PS_TICKET);
     L.ctl[1] = 0;
     L.q = q;
     L.g = *q.gp;

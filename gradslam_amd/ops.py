@@ -777,6 +777,20 @@ def localize_list_stats(device, b, H, W, ds, capacity):
     return v[:64], v[64:128], v[128:]
 
 
+def localize_solve_stats(device, b, H, W, ds, capacity):
+    """Diagnostics of the sync record of the last localisation of sequence b on `device` (gs_localize_solve_stats_i64):
+    dict(ticket, arrived, error, weak, nb, h0).  ticket / arrived / error: the persistent solve's words (arrived =
+    nb x (2 numiters - h0) when it ran to its end); nb / h0: its blocks per sequence and first half-iteration (0 / 0: the
+    solve ran without it); weak: lists the list-building launch flagged as weak (GRADSLAM_HIP_ICP_WEAK_ROOM > 0)."""
+    L = lib()
+    scratch = Workspace.get(device).bytes("localize%d" % b, L.gs_localize_scratch_bytes(H, W, int(ds), int(capacity)))
+    import ctypes
+    out = (ctypes.c_int64 * 8)()
+    check(L.gs_localize_solve_stats_i64(scratch.data_ptr(), H, W, int(ds), int(capacity), out, stream(device)),
+          "gs_localize_solve_stats_i64")
+    return dict(zip(("ticket", "arrived", "error", "weak", "nb", "h0"), (int(x) for x in out[:6])))
+
+
 def update_map_fusion_batch_(maps, vertex, normal, depth, rgb, alpha, poses, K, dist_th, dot_th, renorm_all=True,
                              out=None):
     """update_map_fusion of all sequences of a batch, in place on their capacity-backed buffers

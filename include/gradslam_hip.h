@@ -489,6 +489,15 @@ GS_API int gs_localize_far_stats_i64(const void* scratch, int H, int W, int ds, 
  * launches before the lists start (GRADSLAM_HIP_ICP_LISTS_FROM).  out_host holds 192 values. */
 GS_API int gs_localize_list_stats_i64(const void* scratch, int H, int W, int ds, int64_t map_rows, int64_t* out192_host,
                                       void* stream);
+/* Diagnostics of the sync record of the last solve a scratch was used for (ABI v3; tests, tools; synchronises the
+ * stream; arguments as gs_localize_far_stats_i64): out8[0] = tickets the persistent solve's blocks took, out8[1] = their
+ * arrivals (nb per half-iteration served: nb x (2 numiters - h0) for a complete run), out8[2] = its error word (a block
+ * gave up waiting), out8[3] = source points whose list the list-building launch flagged as weak (counted only with
+ * GRADSLAM_HIP_ICP_WEAK_ROOM > 0), out8[4] = nb, the persistent solve's blocks per sequence, out8[5] = h0, the first
+ * half-iteration it served, out8[6..7] = 0.  out8[0], [1], [2], [4], [5] are 0 when the solve ran without the
+ * persistent launch. */
+GS_API int gs_localize_solve_stats_i64(const void* scratch, int H, int W, int ds, int64_t map_rows, int64_t* out8_host,
+                                       void* stream);
 
 /* update_map_fusion (slam/fusionutils.py:761-789) for B sequences: gs_update_map_fusion_dc_f32 per sequence, 4
  * launches for the whole batch.  scratch: gs_update_map_scratch_bytes(map.n_bound, H, W) per sequence. */

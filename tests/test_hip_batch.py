@@ -732,7 +732,7 @@ st = lambda k: torch.from_numpy(np.stack([s[k] for s in seqs])).cuda()
 poses = st("poses"); poses[:, 1:] = poses[:, :1]
 frames = gs.RGBDImages(st("colors"), st("depths"), st("intrinsics"), poses)
 slam = gs.slam.PointFusion(odom="gradicp", device="cuda")
-pc, prev, rec, stats = gs.Pointclouds(device="cuda"), None, [], []
+pc, prev, rec, stats, sstats = gs.Pointclouds(device="cuda"), None, [], [], []
 for i in range(L):
     live = frames[:, i]
     pc, p = slam.step(pc, live, prev, inplace=True)
@@ -740,8 +740,11 @@ for i in range(L):
     rec.append(p[:, 0].cpu().numpy())
     if i >= 1:
         stats.append([ops.localize_list_stats(torch.device("cuda", 0), b, H, W, 4, pc._buf["points"][b].shape[0]) for b in range(B)])
+        sstats.append([ops.localize_solve_stats(torch.device("cuda", 0), b, H, W, 4, pc._buf["points"][b].shape[0]) for b in range(B)])
 np.savez(sys.argv[1], poses=np.stack(rec), n=np.array([int(x.shape[0]) for x in pc.points_list]),
-         pts=np.concatenate([x.cpu().numpy() for x in pc.points_list]), stats=np.array(stats))
+         pts=np.concatenate([x.cpu().numpy() for x in pc.points_list]), stats=np.array(stats),
+         ps_nb=np.array([[d["nb"] for d in f] for f in sstats]), ps_h0=np.array([[d["h0"] for d in f] for f in sstats]),
+         ps_arrived=np.array([[d["arrived"] for d in f] for f in sstats]), ps_error=np.array([[d["error"] for d in f] for f in sstats]))
 """
 
 
@@ -841,7 +844,10 @@ def test_persistent_xcd_solve_leaves_results_identical(tmp_path, B, first):
     one L2 atomic per half-iteration, readers bypass their L1; source points, lists and listed targets stay in registers /
     LDS across the half-iterations).  Every sum keeps its order and every search its arithmetic, so the bits must be those
     of the launch-per-half-iteration path: poses, surfel counts, points -- at 8 / 1 / 3 sequences per GPU, the last on
-    frames 85 .. 88 of the camera path, where points without a provable list (cube scans, wide lists, block passes) exist."""
+    frames 85 .. 88 of the camera path, where points without a provable list (cube scans, wide lists, block passes) exist.
+    And the persistent kernel must really have run (it falls back to the launches without a word, e.g. under
+    GRADSLAM_HIP_ICP_LANES or GRADSLAM_HIP_ICP_TIMELINE, popped here): in every solve its nb blocks arrived at each of
+    the 2 numiters - h0 half-iterations it served (ops.localize_solve_stats)."""
     import os
     import subprocess
     import sys
@@ -849,10 +855,16 @@ def test_persistent_xcd_solve_leaves_results_identical(tmp_path, B, first):
     outs = []
     for on in ("1", "0"):
         out = str(tmp_path / ("persist%s.npz" % on))
+        env = dict(os.environ, GRADSLAM_HIP_ICP_PERSIST=on)
+        env.pop("GRADSLAM_HIP_ICP_LANES", None)
+        env.pop("GRADSLAM_HIP_ICP_TIMELINE", None)
         subprocess.run([sys.executable, "-c", _LIST_SCRIPT % repo, out, str(B), "480", "640", str(first)], check=True, timeout=900,
-                       env=dict(os.environ, GRADSLAM_HIP_ICP_PERSIST=on))
+                       env=env)
         outs.append(np.load(out))
     a, b = outs
+    assert (a["ps_nb"] > 0).all() and not a["ps_error"].any(), (a["ps_nb"], a["ps_error"])   # (20 iterations per solve)
+    assert np.array_equal(a["ps_arrived"], a["ps_nb"] * (2 * 20 - a["ps_h0"])), (a["ps_arrived"], a["ps_nb"], a["ps_h0"])
+    assert not b["ps_nb"].any()
     assert np.isfinite(a["poses"]).all()                         # (a block that gives up waiting leaves a NaN pose)
     assert np.array_equal(a["poses"].view(np.int32), b["poses"].view(np.int32))
     assert np.array_equal(a["n"], b["n"])

@@ -446,3 +446,22 @@ def test_pointfusion_640x480_sixty_frames_oracle_vs_reference():
     np.testing.assert_allclose(rp[:c], g["poses"][:c], rtol=0, atol=1e-4)
     assert max(d["per_frame"][:c]) <= 300, d
     assert a <= 6e-3 and np.abs(rp - g["poses"]).max() <= 1.2e-2, a
+
+
+@pytest.mark.parametrize("scene,b", [("ragged2", 0), ("ragged2", 1), ("hard3", 0)])
+def test_engine_matrix_fixtures_reproduce(scene, b):
+    """The oracle records of the ICP engine matrix (tests/golden/engine_<scene>_oracle.npz, oracle/make_golden_engine.py)
+    are what the oracle computes now, bit for bit: a stale fixture would hold the GPU tests to the wrong numbers.  Both
+    sequences of the ragged lattice and the first of the hard frames (~15 s of CPU)."""
+    from oracle import make_golden_engine as mge
+    g = np.load(mge.golden_path(scene))
+    c = mge.SCENES[scene]
+    assert (int(g["H"]), int(g["W"]), int(g["L"]), int(g["first"])) == (c["H"], c["W"], c["L"], c["first"])
+    assert g["seeds"].tolist() == c["seeds"]
+    r = mge.run_one(scene, b)
+    assert r["depth_sum"] == float(g["depth_sum"][b])
+    assert np.array_equal(r["poses"].view(np.int32), g["poses"][b].view(np.int32))
+    assert np.array_equal(r["counts"], g["counts"][b])
+    assert np.array_equal(r["sum_points"], g["sum_points"][b])
+    assert np.array_equal(r["sample_idx"], g["sample_idx"][b])
+    assert np.array_equal(r["sample_points"].view(np.int32), g["sample_points"][b].view(np.int32))
