@@ -56,6 +56,13 @@ class StepSeq(C.Structure):
                 ("upd_scratch", C.c_void_p)]
 
 
+class RenderSeq(C.Structure):
+    """gs_render_seq: one map and its L views for gs_render_map_dc_f32."""
+    _fields_ = [("map", MapView), ("poses16", C.c_void_p), ("K16", C.c_void_p), ("depth", C.c_void_p),
+                ("color", C.c_void_p), ("normal", C.c_void_p), ("confidence", C.c_void_p), ("index", C.c_void_p),
+                ("scratch", C.c_void_p)]
+
+
 # name -> argtypes (return type is int unless listed in _RESTYPE)
 _PROTOS = {
     "gs_abi_version": [],
@@ -135,10 +142,13 @@ _PROTOS = {
     "gs_localize_list_stats_i64": [_vp, _i32, _i32, _i32, _i64, C.POINTER(C.c_int64), _vp],
     "gs_localize_solve_stats_i64": [_vp, _i32, _i32, _i32, _i64, C.POINTER(C.c_int64), _vp],
     "gs_pointfusion_step_batch_f32": [C.POINTER(StepSeq), _i32, _i32, _i32, _i32, C.POINTER(IcpParams), _f, _f, _f, _i32, _vp],
+    "gs_render_scratch_bytes": [_i32, _i32, _i32],
+    "gs_render_map_dc_f32": [C.POINTER(RenderSeq), _i32, _i32, _i32, _i32, _i32, _f, _i32, _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,
             "gs_knn1_grid_scratch_bytes": _i64, "gs_update_map_scratch_bytes": _i64, "gs_global_maps_pose_backward_scratch_bytes": _i64, "gs_icp_tape_bytes": _i64, "gs_icp_backward_scratch_bytes": _i64,
-            "gs_localize_scratch_bytes": _i64, "gs_frame_maps_backward_kbar_scratch_bytes": _i64}
+            "gs_localize_scratch_bytes": _i64, "gs_frame_maps_backward_kbar_scratch_bytes": _i64,
+            "gs_render_scratch_bytes": _i64}
 EXPORTS = tuple(_PROTOS)
 
 

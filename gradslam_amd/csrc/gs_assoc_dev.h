@@ -29,12 +29,17 @@ GS_DEV GsCamera gs_camera(const float* __restrict__ pose16, const float* __restr
 // slam/fusionutils.py:250-274 for one point: pixel (h, w) it projects to; false when it falls outside the frame or
 // behind the camera.  32-bit integer arithmetic throughout: in_frame bounds u, v to (-1e-3, W - 0.999) x (-1e-3,
 // H - 0.999), so the rounded coordinates fit (the reference's int64 casts and clamps are value-identical).
-GS_DEV bool gs_project_point_hw(const GsCamera& c, float p0, float p1, float p2, int H, int W, float u_hi, float v_hi,
-                                int& h_out, int& w_out) {
+// The _q form also hands out the camera-frame point q (the model view of gs_render.hip takes its depth q[2] and its
+// back-face test from it); q is written whether or not the point is in the frame.
+GS_DEV bool gs_project_point_hw_q(const GsCamera& c, float p0, float p1, float p2, int H, int W, float u_hi, float v_hi,
+                                  int& h_out, int& w_out, float* q) {
   // Pointclouds.transform: rotate_ (einsum over N: FMA chain) then offset_
   const float q0 = gs_dot3_fma(p0, p1, p2, c.Ri[0], c.Ri[1], c.Ri[2]) + c.ti[0];
   const float q1 = gs_dot3_fma(p0, p1, p2, c.Ri[3], c.Ri[4], c.Ri[5]) + c.ti[1];
   const float q2 = gs_dot3_fma(p0, p1, p2, c.Ri[6], c.Ri[7], c.Ri[8]) + c.ti[2];
+  q[0] = q0;
+  q[1] = q1;
+  q[2] = q2;
   const bool front = q2 > 0.0f;
   // project_points: 4x4 . (x, y, z, 1), tiny matmul: plain, ascending k
   float r[3];
@@ -56,6 +61,11 @@ GS_DEV bool gs_project_point_hw(const GsCamera& c, float p0, float p1, float p2,
   h_out = hi;
   w_out = wi;
   return true;
+}
+GS_DEV bool gs_project_point_hw(const GsCamera& c, float p0, float p1, float p2, int H, int W, float u_hi, float v_hi,
+                                int& h_out, int& w_out) {
+  float q[3];
+  return gs_project_point_hw_q(c, p0, p1, p2, H, W, u_hi, v_hi, h_out, w_out, q);
 }
 
 // the same as the flat pixel index h * W + w, or -1

@@ -1,6 +1,7 @@
 """Tensor-level wrappers of the C-ABI (one sequence per call).  Each function validates
 devices, allocates outputs with torch, and enqueues the HIP kernels on torch's current stream.
 Nothing here computes with torch: arithmetic happens in libgradslam_hip.so or not at all."""
+import collections
 import os
 
 import torch
@@ -828,6 +829,85 @@ def update_map_fusion_batch_(maps, vertex, normal, depth, rgb, alpha, poses, K, 
     check(L.gs_update_map_fusion_batch_f32(seqs, Bn, H, W, float(dist_th), float(dot_th), 1 if renorm_all else 0,
                                            stream(dev)), "gs_update_map_fusion_batch_f32")
     return cnt, gv, gn, best
+
+
+# ----------------------------------------------------------------------------------- the model view
+RenderedViews = collections.namedtuple("RenderedViews", ["depth", "color", "normal", "confidence", "index"])
+
+
+def render_map_batch(maps, poses, K, H, W, radius=0, min_confidence=0.0, cull_backfaces=False, out=None):
+    """The maps of B sequences seen from L poses each (gs_render_map_dc_f32: a z-buffered point render, forward only,
+    one key launch and one resolve launch per 8 sequences x 4 views).  maps: per sequence (points, normals, colors,
+    ccounts, n_bound, n_dev) -- (rows, 3) / (rows, 1) float32 tensors of which the first n_bound rows (min(n_dev[0],
+    n_bound) when the device count n_dev is given) are the map; normals / colors / ccounts may be None, the images that
+    need them are then None.  poses (B, L, 4, 4) camera-to-world, K (B, 4, 4).  Returns RenderedViews(depth (B, L, H,
+    W, 1), color (B, L, H, W, 3), normal (B, L, H, W, 3), confidence (B, L, H, W, 1), index (B, L, H, W) int64);
+    pixels no row lands on hold 0 (index: -1).  out: a RenderedViews (or 5-tuple) of tensors to write into."""
+    _warn_detached("render_map", poses, K, *[t for m in maps for t in m[:4]])
+    poses, K = _c(poses.detach()), _c(K.detach())
+    dev = require_device(poses, K)
+    Bn, Lv = int(poses.shape[0]), int(poses.shape[1])
+    H, W = int(H), int(W)
+    if len(maps) != Bn or tuple(poses.shape[2:]) != (4, 4) or tuple(K.shape) != (Bn, 4, 4):
+        raise ValueError("render_map: expected poses (B, L, 4, 4) and K (B, 4, 4) for B = %d maps; got %s and %s"
+                         % (len(maps), tuple(poses.shape), tuple(K.shape)))
+    if Lv == 0 or H <= 0 or W <= 0:
+        raise ValueError("render_map: needs at least one view and a positive image size")
+    held = [tuple(None if t is None else _c(t.detach()) for t in m[:4]) for m in maps]
+    have = [all(h[i] is not None for h in held) for i in range(4)]
+    if not have[0]:
+        raise ValueError("render_map: a map without points")
+    shapes = ((Bn, Lv, H, W, 1), (Bn, Lv, H, W, 3), (Bn, Lv, H, W, 3), (Bn, Lv, H, W, 1), (Bn, Lv, H, W))
+    wanted = (True, have[2], have[1], have[3], True)
+    imgs = []
+    for i, (shape, want) in enumerate(zip(shapes, wanted)):
+        t = None if out is None else out[i]
+        if t is None and want:
+            t = torch.empty(shape, dtype=torch.int64 if i == 4 else f32, device=dev)
+        elif t is not None:
+            if not want:
+                raise ValueError("render_map: out.%s given but the maps lack the attribute it shows" % RenderedViews._fields[i])
+            if tuple(t.shape) != shape or t.dtype != (torch.int64 if i == 4 else f32) or not t.is_contiguous():
+                raise ValueError("render_map: out.%s must be a contiguous %s tensor of shape %s"
+                                 % (RenderedViews._fields[i], "int64" if i == 4 else "float32", shape))
+        imgs.append(t)
+    require_device(*imgs)
+    ws = Workspace.get(dev)
+    L = lib()
+    seqs = (_C.RenderSeq * Bn)()
+    nbytes = L.gs_render_scratch_bytes(Lv, H, W)
+    per_seq = [0 if t is None else t[0].numel() * t.element_size() for t in imgs]
+    for b in range(Bn):
+        P, N, Cc, F = held[b]
+        n_bound, n_dev = maps[b][4], maps[b][5]
+        require_device(P, N, Cc, F, n_dev, poses)
+        if P.ndim != 2 or P.shape[1] != 3 or any(t is not None and t.shape[0] < P.shape[0] for t in (N, Cc, F)):
+            raise ValueError("render_map: points must be (rows, 3) and every attribute must hold as many rows")
+        n_bound = P.shape[0] if n_bound is None else min(int(n_bound), int(P.shape[0]))
+        u = seqs[b]
+        u.map = _C.MapView(*[0 if t is None else t.data_ptr() for t in (P, N, Cc, F)], int(P.shape[0]), n_bound,
+                           0 if n_dev is None else n_dev.data_ptr())
+        u.poses16, u.K16 = poses.data_ptr() + b * Lv * 64, K.data_ptr() + b * 64
+        u.depth, u.color, u.normal, u.confidence, u.index = (
+            None if t is None else t.data_ptr() + b * sz for t, sz in zip(imgs, per_seq))
+        u.scratch = ws.bytes("render%d" % b, nbytes).data_ptr()
+    check(L.gs_render_map_dc_f32(seqs, Bn, Lv, H, W, int(radius), float(min_confidence), 1 if cull_backfaces else 0,
+                                 stream(dev)), "gs_render_map_dc_f32")
+    return RenderedViews(*imgs)
+
+
+def render_map(points, normals, colors, ccounts, poses, K, H, W, n_dev=None, radius=0, min_confidence=0.0,
+               cull_backfaces=False, out=None):
+    """One map seen from L poses: render_map_batch for B = 1 without the batch dimension.  poses (L, 4, 4) or (4, 4),
+    K (4, 4); n_dev: device int64[1] holding the actual row count (points.shape[0] is then an upper bound).  Returns
+    RenderedViews(depth (L, H, W, 1), color (L, H, W, 3), normal (L, H, W, 3), confidence (L, H, W, 1), index (L, H, W))."""
+    if poses.ndim == 2:
+        poses = poses.unsqueeze(0)
+    if out is not None:
+        out = tuple(None if t is None else t.unsqueeze(0) for t in out)
+    r = render_map_batch([(points, normals, colors, ccounts, None, n_dev)], poses.unsqueeze(0), K.reshape(1, 4, 4), H, W,
+                         radius=radius, min_confidence=min_confidence, cull_backfaces=cull_backfaces, out=out)
+    return RenderedViews(*[None if t is None else t[0] for t in r])
 
 
 # ----------------------------------------------------------------------------------- K7 (autograd)

@@ -488,6 +488,60 @@ class Pointclouds(object):
         self._padded_cache.clear()
         self.equisized = True if B == 1 else None
 
+    # ------------------------------------------------------------------ the model view
+    def render(self, intrinsics: torch.Tensor, poses: torch.Tensor, height: int, width: int, *, radius: int = 0,
+               min_confidence: float = 0.0, cull_backfaces: bool = False, return_extras: bool = False):
+        r"""The map seen from camera poses: a z-buffered point render (HIP, forward only; the result is detached).
+
+        Every point competes for the pixel it projects to (the projection of the SLAM association, with the image size
+        `height` x `width`, which need not be the capture size -- scale the intrinsics to match); the nearest point
+        wins, the lowest row index among points at bit-equal depth.  Pixels no point lands on hold depth 0 / colour 0.
+
+        Args:
+            intrinsics: (B, 1, 4, 4), as in `RGBDImages`
+            poses: (B, L, 4, 4) camera-to-world
+            radius: 0..3; a point competes for the (2 radius + 1)^2 pixel square around its pixel (closes the holes of
+                a view that is nearer than the capture)
+            min_confidence: points whose confidence count (the first and only feature channel) is below it are skipped
+            cull_backfaces: points whose normal n has n.q >= 0 at their camera-frame position q (facing away from the
+                camera, or edge-on) are skipped.  Mind the orientation of the map's normals: the frame normals of
+                `RGBDImages` (and of the reference) mostly point away from the camera that saw them, so on a map fused
+                from them this removes the visible side
+            return_extras: also return {"normal": (B, L, H, W, 3) camera-frame normal of the winner, "confidence":
+                (B, L, H, W, 1), "index": (B, L, H, W) int64 row of the winner or -1}
+
+        Returns:
+            RGBDImages of shape (B, L, height, width) holding the rendered colour and depth with `intrinsics` and
+            `poses` (and the extras dict with `return_extras`).
+
+        The map buffers are only read: counts that live on the device stay there, nothing is reallocated."""
+        from .. import ops
+        from .rgbdimages import RGBDImages
+        for name, val in (("intrinsics", intrinsics), ("poses", poses)):
+            if not torch.is_tensor(val):
+                raise TypeError("Expected {} to be of type tensor; got {}".format(name, type(val)))
+        B = len(self)
+        if B == 0 or self._buf["points"] is None:
+            raise ValueError("cannot render an empty pointclouds object")
+        if any(self._buf[k] is None for k in ("normals", "colors", "features")) or self.num_features != 1:
+            raise ValueError("render needs a surfel map: points, normals, colors and one feature channel (confidence)")
+        if poses.ndim != 4 or tuple(poses.shape[2:]) != (4, 4) or poses.shape[0] != B or poses.shape[1] == 0:
+            raise ValueError("poses should have shape ({}, L, 4, 4), but had shape {}".format(B, tuple(poses.shape)))
+        if tuple(intrinsics.shape) != (B, 1, 4, 4):
+            raise ValueError("intrinsics should have shape {}, but had shape {}".format((B, 1, 4, 4),
+                                                                                     tuple(intrinsics.shape)))
+        maps = []
+        for b in range(B):
+            bound, n_dev = self._count_of(b)   # (never forces a device-side count to the host)
+            maps.append(tuple(self._buf[k][b] for k in _ATTRS) + (bound, n_dev))
+        out = ops.render_map_batch(maps, poses, intrinsics[:, 0], int(height), int(width), radius=radius,
+                                   min_confidence=min_confidence, cull_backfaces=cull_backfaces)
+        frames = RGBDImages(out.color, out.depth, intrinsics.detach().to(torch.float32),
+                            poses.detach().to(torch.float32))
+        if return_extras:
+            return frames, {"normal": out.normal, "confidence": out.confidence, "index": out.index}
+        return frames
+
     # ------------------------------------------------------------------ copies / moves
     def clone(self):
         other = Pointclouds(device=self.device)

@@ -559,6 +559,37 @@ GS_API int gs_unproject_points_f32(const float* pixel_coords, int pdim, int64_t 
                                    int64_t pts_per_mat, const float* depths, float* out_xyz, void* stream);
 GS_API int gs_lie_small_f32(int op, const float* in, float* out, void* stream);
 
+/* ------------------------------------------------------------------ the model view ------
+ * A surfel map seen from a pose: a z-buffered point render of B maps under L views each, forward only (the reference
+ * has no such call; its Pointclouds.open3d / .plotly viewers are the nearest thing, structures/pointclouds.py:1239, :1296).
+ * Row i of a map lands on the pixel (h, w) that gs_project_map_f32 gives it for the view's pose and the image size
+ * H x W (which need not be the capture size); its depth z is the third camera-frame coordinate of that projection.  The
+ * winner of a pixel is the row of smallest z, the lowest row index among equal z: one 64-bit key (bits(z) << 32 | i)
+ * under atomicMin, so every output is a pure function of the inputs (no dependence on thread order).
+ * Filters (all off at 0): rows with ccount < min_confidence are skipped (min_confidence > 0); with cull_backfaces rows
+ * whose camera-frame normal nc has (nc0 q0 + nc1 q1) + nc2 q2 >= 0 at their camera-frame point q are skipped; a row
+ * competes for every pixel of the (2 radius + 1)^2 square around (h, w) clipped to the image, radius in 0..3.
+ * Outputs per sequence, (L, H, W, C) row-major, any may be NULL: depth (C = 1) = z of the winner, else 0; color (3) =
+ * its colour, else 0; normal (3) = its normal rotated into the camera frame, else 0; confidence (1) = its ccount, else
+ * 0; index (int64, no C) = its row, else -1.  map.normals / colors / ccounts may be NULL where no requested output or
+ * filter reads them; map.capacity is not used; maps of 2^32 rows or more are rejected.  poses16: L camera-to-world
+ * matrices; K16: one intrinsics matrix.  scratch: gs_render_scratch_bytes(L, H, W) bytes per sequence (its contents
+ * before and after the call mean nothing).  Views are served 4 per launch; the map is read once per launch. */
+typedef struct gs_render_seq {
+  gs_map_view map;
+  const float* poses16;  /* (L, 16) */
+  const float* K16;
+  float* depth;          /* out (L, H, W) */
+  float* color;          /* out (L, H, W, 3) */
+  float* normal;         /* out (L, H, W, 3) */
+  float* confidence;     /* out (L, H, W) */
+  int64_t* index;        /* out (L, H, W) */
+  void* scratch;
+} gs_render_seq;
+GS_API int64_t gs_render_scratch_bytes(int views, int H, int W);
+GS_API int gs_render_map_dc_f32(const gs_render_seq* seqs_host, int B, int L, int H, int W, int radius,
+                                float min_confidence, int cull_backfaces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
