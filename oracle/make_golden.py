@@ -18,6 +18,9 @@ Fixtures
                   depth -> downsample_rgbdimages -> point_to_plane_gradICP (96x128).
   fusion_kat.npz  hand-made known-answer cases for find_best_unique_correspondences and
                   fuse_with_map (mirrors tests/slam/test_fusionutils.py:672-750, :918-986).
+  icp_init_grad.npz  the reference's autograd through gradICP and hard-LM ICP (5 iterations) started from a
+                  NON-identity initial transform: T and d<W,T>/d(src, tgt, normals, init).  On its own:
+                  python -m oracle.make_golden --icp-init
 """
 import math
 import os
@@ -31,6 +34,32 @@ sys.path.insert(0, REPO)
 from oracle import refimport  # noqa: E402
 
 OUT = os.path.join(REPO, "tests", "golden")
+
+
+def icp_init_transform():
+    """The non-identity initial transform of icp_init_grad.npz: about one degree about a generic axis, a few cm."""
+    from oracle.icp_backward import se3_exp
+    return se3_exp(np.array([0.03, -0.02, 0.04, 0.010, -0.012, 0.008])).astype(np.float32)
+
+
+def icp_init_grad():
+    """icp_init_grad.npz: the icp_unit clouds, W of icp_grad.npz, init = icp_init_transform() as a leaf."""
+    refimport.import_reference()
+    import torch
+    from gradslam.odometry import icputils
+    gi = np.load(os.path.join(OUT, "icp_unit.npz"))
+    Wt = np.load(os.path.join(OUT, "icp_grad.npz"))["W"]
+    init0 = icp_init_transform()
+    gg = dict(W=Wt, init=init0, numiters=np.int64(5))
+    for tag, fn in (("grad", icputils.point_to_plane_gradICP), ("hard", icputils.point_to_plane_ICP)):
+        leaf = [torch.from_numpy(gi[k]).clone().requires_grad_(True) for k in ("src", "tgt", "tgt_normals")]
+        init = torch.from_numpy(init0).clone().requires_grad_(True)
+        Tg, _ = fn(leaf[0][None], leaf[1][None], leaf[2][None], init, numiters=5)
+        (Tg * torch.from_numpy(Wt)).sum().backward()
+        gg[tag + "_T"] = Tg.detach().numpy()
+        for name, t in zip(("src", "tgt", "tn", "init"), leaf + [init]):
+            gg[tag + "_" + name] = t.grad.numpy()
+    np.savez_compressed(os.path.join(OUT, "icp_init_grad.npz"), **gg)
 
 
 def main():
@@ -236,9 +265,11 @@ def main():
     g["fused0_points"], g["fused0_ccounts"] = fused0.points_list[0].numpy(), fused0.features_list[0].numpy()
     np.savez_compressed(os.path.join(OUT, "fusion_kat.npz"), **g)
 
+    icp_init_grad()
+
     for f in sorted(os.listdir(OUT)):
         print("%-18s %8.1f KiB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))
 
 
 if __name__ == "__main__":
-    main()
+    icp_init_grad() if "--icp-init" in sys.argv else main()
