@@ -63,6 +63,15 @@ class RenderSeq(C.Structure):
                 ("scratch", C.c_void_p)]
 
 
+class RenderBackwardSeq(C.Structure):
+    """gs_render_backward_seq: one map, its L views, the saved index image, upstream adjoints and outputs."""
+    _fields_ = [("map", MapView), ("poses16", C.c_void_p), ("K16", C.c_void_p), ("index", C.c_void_p),
+                ("depth_bar", C.c_void_p), ("color_bar", C.c_void_p), ("normal_bar", C.c_void_p),
+                ("confidence_bar", C.c_void_p), ("points_bar", C.c_void_p), ("normals_bar", C.c_void_p),
+                ("colors_bar", C.c_void_p), ("ccounts_bar", C.c_void_p), ("poses_bar", C.c_void_p),
+                ("scratch", C.c_void_p)]
+
+
 # name -> argtypes (return type is int unless listed in _RESTYPE)
 _PROTOS = {
     "gs_abi_version": [],
@@ -144,11 +153,13 @@ _PROTOS = {
     "gs_pointfusion_step_batch_f32": [C.POINTER(StepSeq), _i32, _i32, _i32, _i32, C.POINTER(IcpParams), _f, _f, _f, _i32, _vp],
     "gs_render_scratch_bytes": [_i32, _i32, _i32],
     "gs_render_map_dc_f32": [C.POINTER(RenderSeq), _i32, _i32, _i32, _i32, _i32, _f, _i32, _vp],
+    "gs_render_backward_scratch_bytes": [_i32, _i32, _i32, _i64],
+    "gs_render_map_backward_dc_f32": [C.POINTER(RenderBackwardSeq), _i32, _i32, _i32, _i32, _i32, _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,
             "gs_knn1_grid_scratch_bytes": _i64, "gs_update_map_scratch_bytes": _i64, "gs_global_maps_pose_backward_scratch_bytes": _i64, "gs_icp_tape_bytes": _i64, "gs_icp_backward_scratch_bytes": _i64,
             "gs_localize_scratch_bytes": _i64, "gs_frame_maps_backward_kbar_scratch_bytes": _i64,
-            "gs_render_scratch_bytes": _i64}
+            "gs_render_scratch_bytes": _i64, "gs_render_backward_scratch_bytes": _i64}
 EXPORTS = tuple(_PROTOS)
 
 

@@ -1,5 +1,5 @@
 // gs_render.hip — the model view: a surfel map seen from a pose as depth / colour / normal / confidence / index
-// images (forward only).  A z-buffered point render in two passes:
+// images, and its reverse mode (at the end of the file).  The forward is a z-buffered point render in two passes:
 //
 //   key pass      one thread per map row: project the row under every view of the launch (the projection of the
 //                 association, gs_project_point_hw_q) and let it compete for its pixel(s) with a 64-bit atomicMin on
@@ -201,6 +201,269 @@ extern "C" int gs_render_map_dc_f32(const gs_render_seq* seqs_host, int B, int L
       }
       const unsigned pblocks = (unsigned)nb * (unsigned)gs_ceil_div((int64_t)rb.V * P, 256);
       hipLaunchKernelGGL(gs_render_resolve_kernel, dim3(pblocks), dim3(256), 0, st, rb);
+      GS_LAUNCH_CHECK();
+    }
+  }
+  return GS_OK;
+}
+
+// ---------------------------------------------------------------- reverse mode of the model view ----
+// The winner of a pixel (the index image of the forward) and the two filters are constants; gradients flow through the
+// values the resolve pass writes for the winner (T = [R t; 0 1] camera-to-world, row n wins pixel i of view v, upstream
+// adjoints zb / cb(3) / ob(3) / fb):
+//   depth   z   = sum_k R[k][2] (p_k - t_k):  points_bar[n][k] += R[k][2] zb,  T_bar[k][2] += (p_k - t_k) zb,
+//                                             T_bar[k][3] -= R[k][2] zb
+//   normal  o_j = sum_k n_k R[k][j]:          normals_bar[n][k] += sum_j R[k][j] ob_j,  T_bar[k][j] += n_k ob_j
+//   colour, confidence: copies:               colors_bar[n] += cb,  ccounts_bar[n] += fb
+// A row-centric gather, no float atomics: one thread per map row re-projects its row under every view of the launch
+// (gs_project_point_hw_q: the forward's arithmetic, hence the forward's (h, w)), scans the clipped (2 radius + 1)^2 square
+// of the saved index image for pixels it won (raster order) and adds up their adjoints in float64; every row of the four
+// row outputs is written exactly once per launch (zeros for rows that win nothing or lie beyond the count: no memset).
+// A row that the forward filtered out is in no pixel of the index image and needs no test here.  Upstream images are
+// read only at pixels some row won: whatever they hold at empty pixels (index -1) never enters.
+// Pose adjoint: each thread holds its row's 12 contributions to T_bar of a view (3x3 part, then the translation column),
+// a block reduction (float64, fixed order) writes one partial row per block and view to the caller's scratch, and a
+// second launch adds the partial rows up in a fixed order.  Views beyond GS_RV_MAX_VIEWS are served by further launches
+// on the same stream that add to the row outputs of the launches before them (read back as the float32 values they
+// were rounded to: one more rounding per group of 4 views): a fixed order as well, so every output
+// is a pure function of the inputs (bitwise reproducible; T_bar of a view does not depend on the other views).
+// (The kernels are named gs_rview_*: "gs_render_" stays the prefix of the two forward passes, whose register budget
+// tests/test_render_cpu.py pins by that prefix.)
+constexpr int GS_RB_NV = 12;
+
+struct RbSeq {
+  const float* points;
+  const float* normals;
+  GsCount n;
+  int64_t rows;           // rows of the four row outputs (= the host-side bound of the map)
+  int nblk;               // blocks of 256 rows
+  const float* poses16;   // first view of the launch
+  const float* K16;
+  const int64_t* index;   // (views of the launch, H * W) ...
+  const float* zb;        // ... upstream adjoints, any may be NULL
+  const float* cb;
+  const float* ob;
+  const float* fb;
+  float* points_bar;      // (rows, 3), any may be NULL
+  float* normals_bar;
+  float* colors_bar;
+  float* ccounts_bar;     // (rows)
+  double* partials;       // (views of the launch, nblk, 12); NULL: no pose adjoint
+  float* poses_bar;       // first view of the launch
+};
+struct RbBatch {
+  RbSeq s[GS_MAX_BATCH];
+  int B, V, H, W, radius, accumulate;
+  int64_t P;
+  float u_hi, v_hi;
+};
+
+__global__ void __launch_bounds__(256) gs_rview_backward_rows_kernel(const RbBatch rb) {
+  __shared__ GsCamera cams[GS_RV_MAX_VIEWS];
+  __shared__ float trans[GS_RV_MAX_VIEWS][3];
+  __shared__ double red[GS_RV_MAX_VIEWS][256 / GS_WAVE][GS_RB_NV];
+  const RbSeq& q = rb.s[blockIdx.x % rb.B];
+  const int blk = blockIdx.x / rb.B;
+  if (blk >= q.nblk) return;   // (the whole block: a shorter map of the batch)
+  if ((int)threadIdx.x < rb.V) {
+    const float* T = q.poses16 + 16 * threadIdx.x;
+    cams[threadIdx.x] = gs_camera(T, q.K16);
+    trans[threadIdx.x][0] = T[3];
+    trans[threadIdx.x][1] = T[7];
+    trans[threadIdx.x][2] = T[11];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & (GS_WAVE - 1), wave = threadIdx.x / GS_WAVE;
+  const int64_t n = (int64_t)blk * 256 + threadIdx.x;
+  const bool live = n < gs_count(q.n);
+  const bool want_n = q.ob != nullptr && q.normals != nullptr;
+  float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
+  if (live) {
+    p0 = q.points[3 * n];
+    p1 = q.points[3 * n + 1];
+    p2 = q.points[3 * n + 2];
+    if (want_n) {
+      n0 = q.normals[3 * n];
+      n1 = q.normals[3 * n + 1];
+      n2 = q.normals[3 * n + 2];
+    }
+  }
+  double aP[3] = {0.0, 0.0, 0.0}, aN[3] = {0.0, 0.0, 0.0}, aC[3] = {0.0, 0.0, 0.0}, aF = 0.0;
+  const int r = rb.radius;
+  for (int v = 0; v < rb.V; ++v) {
+    const GsCamera& c = cams[v];
+    double Z = 0.0, O[3] = {0.0, 0.0, 0.0};
+    bool won = false;
+    int h, w;
+    float cq[3];
+    if (live && gs_project_point_hw_q(c, p0, p1, p2, rb.H, rb.W, rb.u_hi, rb.v_hi, h, w, cq)) {
+      const int64_t base = (int64_t)v * rb.P;
+      const int h0 = h - r < 0 ? 0 : h - r, h1 = h + r > rb.H - 1 ? rb.H - 1 : h + r;
+      const int w0 = w - r < 0 ? 0 : w - r, w1 = w + r > rb.W - 1 ? rb.W - 1 : w + r;
+      for (int hh = h0; hh <= h1; ++hh)
+        for (int ww = w0; ww <= w1; ++ww) {
+          const int64_t i = base + ((int64_t)hh * rb.W + ww);
+          if (q.index[i] != n) continue;
+          won = true;
+          if (q.zb) Z += (double)q.zb[i];
+          if (want_n) {
+            O[0] += (double)q.ob[3 * i];
+            O[1] += (double)q.ob[3 * i + 1];
+            O[2] += (double)q.ob[3 * i + 2];
+          }
+          if (q.cb) {
+            aC[0] += (double)q.cb[3 * i];
+            aC[1] += (double)q.cb[3 * i + 1];
+            aC[2] += (double)q.cb[3 * i + 2];
+          }
+          if (q.fb) aF += (double)q.fb[i];
+        }
+    }
+    // R[k][j] = Ri[3 j + k]
+    if (won) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        aP[k] += (double)c.Ri[6 + k] * Z;
+        aN[k] += ((double)c.Ri[k] * O[0] + (double)c.Ri[3 + k] * O[1]) + (double)c.Ri[6 + k] * O[2];
+      }
+    }
+    if (q.partials) {
+      double t[GS_RB_NV];
+#pragma unroll
+      for (int i = 0; i < GS_RB_NV; ++i) t[i] = 0.0;
+      if (won) {
+        const double pn[3] = {(double)n0, (double)n1, (double)n2};
+        const double pt[3] = {(double)p0 - (double)trans[v][0], (double)p1 - (double)trans[v][1],
+                              (double)p2 - (double)trans[v][2]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          t[3 * k] = pn[k] * O[0];
+          t[3 * k + 1] = pn[k] * O[1];
+          t[3 * k + 2] = pn[k] * O[2] + pt[k] * Z;
+          t[9 + k] = -((double)c.Ri[6 + k] * Z);
+        }
+      }
+      // a wave none of whose rows won a pixel of this view contributes exact zeros: skip its shuffles
+      const bool any = __ballot(won) != 0ull;
+#pragma unroll
+      for (int i = 0; i < GS_RB_NV; ++i) {
+        const double sum = any ? gs_wave_sum_f64(t[i]) : 0.0;
+        if (lane == 0) red[v][wave][i] = sum;
+      }
+    }
+  }
+  if (q.partials) {
+    __syncthreads();
+    if ((int)threadIdx.x < GS_RB_NV * rb.V) {
+      const int v = threadIdx.x / GS_RB_NV, i = threadIdx.x % GS_RB_NV;
+      double t = 0.0;
+      for (int wv = 0; wv < 256 / GS_WAVE; ++wv) t += red[v][wv][i];
+      q.partials[((int64_t)v * q.nblk + blk) * GS_RB_NV + i] = t;
+    }
+  }
+  if (n >= q.rows) return;
+  if (rb.accumulate) {   // a later launch of the same call: add to what the views before left
+    if (q.points_bar)
+      for (int k = 0; k < 3; ++k) aP[k] += (double)q.points_bar[3 * n + k];
+    if (q.normals_bar)
+      for (int k = 0; k < 3; ++k) aN[k] += (double)q.normals_bar[3 * n + k];
+    if (q.colors_bar)
+      for (int k = 0; k < 3; ++k) aC[k] += (double)q.colors_bar[3 * n + k];
+    if (q.ccounts_bar) aF += (double)q.ccounts_bar[n];
+  }
+  if (q.points_bar)
+    for (int k = 0; k < 3; ++k) q.points_bar[3 * n + k] = (float)aP[k];
+  if (q.normals_bar)
+    for (int k = 0; k < 3; ++k) q.normals_bar[3 * n + k] = (float)aN[k];
+  if (q.colors_bar)
+    for (int k = 0; k < 3; ++k) q.colors_bar[3 * n + k] = (float)aC[k];
+  if (q.ccounts_bar) q.ccounts_bar[n] = (float)aF;
+}
+
+// One wave per (sequence, view) adds the partial rows up (rows strided over the lanes, then across the lanes: a fixed
+// order) and writes the 4x4 pose adjoint, bottom row zero.
+__global__ void __launch_bounds__(GS_WAVE) gs_rview_backward_pose_kernel(const RbBatch rb) {
+  const RbSeq& q = rb.s[blockIdx.y];
+  if (!q.partials || !q.poses_bar) return;
+  const int v = blockIdx.x, lane = threadIdx.x;
+  const double* part = q.partials + (int64_t)v * q.nblk * GS_RB_NV;
+  float* out = q.poses_bar + 16 * v;
+  for (int i = 0; i < GS_RB_NV; ++i) {
+    double s = 0.0;
+    for (int b = lane; b < q.nblk; b += GS_WAVE) s += part[(int64_t)b * GS_RB_NV + i];
+    s = gs_wave_sum_f64(s);
+    if (lane == 0) out[i < 9 ? 4 * (i / 3) + i % 3 : 4 * (i - 9) + 3] = (float)s;
+  }
+  if (lane < 4) out[12 + lane] = 0.0f;
+}
+
+static size_t render_backward_scratch_per_seq(int views, int64_t n_bound) {
+  const int v = views < GS_RV_MAX_VIEWS ? views : GS_RV_MAX_VIEWS;
+  return gs_align((size_t)v * (size_t)gs_ceil_div(n_bound, 256) * GS_RB_NV * sizeof(double)) + 256;
+}
+
+extern "C" int64_t gs_render_backward_scratch_bytes(int views, int H, int W, int64_t n_bound) {
+  if (views <= 0 || H <= 0 || W <= 0 || n_bound < 0 || n_bound >= (1ll << 32)) return 0;
+  return (int64_t)render_backward_scratch_per_seq(views, n_bound);
+}
+
+extern "C" int gs_render_map_backward_dc_f32(const gs_render_backward_seq* seqs_host, int B, int L, int H, int W,
+                                             int radius, void* stream) {
+  GS_REQUIRE(seqs_host && B > 0 && L > 0 && H > 0 && W > 0, "bad arguments");
+  GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
+  GS_REQUIRE(radius >= 0 && radius <= GS_RV_MAX_RADIUS, "radius must be 0, 1, 2 or 3");
+  for (int b = 0; b < B; ++b) {
+    const gs_render_backward_seq& u = seqs_host[b];
+    GS_REQUIRE(u.map.n_bound >= 0, "bad map size");
+    GS_REQUIRE(u.map.n_bound < (1ll << 32), "maps of 2^32 rows or more are not supported (32-bit row index in the key)");
+    GS_REQUIRE(u.poses16 && u.K16 && u.index, "NULL pointer");
+    GS_REQUIRE(!u.poses_bar || u.scratch, "NULL pointer (scratch: needed by poses_bar)");
+    if (u.map.n_bound > 0) {
+      GS_REQUIRE(u.map.points, "NULL pointer (points)");
+      GS_REQUIRE(u.map.normals || !u.normal_bar, "NULL pointer (normals: needed by the terms of normal_bar)");
+    }
+  }
+  hipStream_t st = gs_stream(stream);
+  const int64_t P = (int64_t)H * W;
+  for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
+    const int nb = B - c0 < GS_MAX_BATCH ? B - c0 : GS_MAX_BATCH;
+    for (int v0 = 0; v0 < L; v0 += GS_RV_MAX_VIEWS) {
+      RbBatch rb;
+      rb.B = nb;
+      rb.V = L - v0 < GS_RV_MAX_VIEWS ? L - v0 : GS_RV_MAX_VIEWS;
+      rb.H = H; rb.W = W; rb.P = P;
+      rb.radius = radius;
+      rb.accumulate = v0 > 0 ? 1 : 0;
+      rb.u_hi = (float)((double)W - 0.999); rb.v_hi = (float)((double)H - 0.999);
+      int64_t n_max = 0;
+      bool any_pose = false;
+      const int64_t off = (int64_t)v0 * P;   // first pixel of the launch in the (L, H, W) stacks
+      for (int b = 0; b < nb; ++b) {
+        const gs_render_backward_seq& u = seqs_host[c0 + b];
+        RbSeq& s = rb.s[b];
+        s.points = u.map.points; s.normals = u.map.normals;
+        s.n = GsCount{u.map.n_bound, u.map.n_dev};
+        s.rows = u.map.n_bound;
+        s.nblk = (int)gs_ceil_div(u.map.n_bound, 256);   // < 2^24
+        s.poses16 = u.poses16 + 16 * (int64_t)v0;
+        s.K16 = u.K16;
+        s.index = u.index + off;
+        s.zb = u.depth_bar ? u.depth_bar + off : nullptr;
+        s.cb = u.color_bar ? u.color_bar + 3 * off : nullptr;
+        s.ob = u.normal_bar ? u.normal_bar + 3 * off : nullptr;
+        s.fb = u.confidence_bar ? u.confidence_bar + off : nullptr;
+        s.points_bar = u.points_bar; s.normals_bar = u.normals_bar;
+        s.colors_bar = u.colors_bar; s.ccounts_bar = u.ccounts_bar;
+        s.partials = u.poses_bar ? static_cast<double*>(u.scratch) : nullptr;
+        s.poses_bar = u.poses_bar ? u.poses_bar + 16 * (int64_t)v0 : nullptr;
+        any_pose = any_pose || u.poses_bar;
+        n_max = u.map.n_bound > n_max ? u.map.n_bound : n_max;
+      }
+      if (n_max > 0) {
+        const unsigned blocks = (unsigned)nb * (unsigned)gs_ceil_div(n_max, 256);   // < 8 * 2^24
+        hipLaunchKernelGGL(gs_rview_backward_rows_kernel, dim3(blocks), dim3(256), 0, st, rb);
+      }
+      if (any_pose) hipLaunchKernelGGL(gs_rview_backward_pose_kernel, dim3(rb.V, nb), dim3(GS_WAVE), 0, st, rb);
       GS_LAUNCH_CHECK();
     }
   }

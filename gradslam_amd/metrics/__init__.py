@@ -4,16 +4,17 @@ The reference ships an EMPTY `gradslam.metrics` package (gradslam/metrics/__init
 assign the reporters the parity harness needs to this build: pose ATE and RPE against a reference trajectory, the
 distance between two fused maps (exact nearest neighbours through the HIP grid engine, gs_knn1_grid_f32), the number of
 differing rows of two `pc2im_bnhw` correspondence tables, the per-frame drift of surfel counts, and the depth residual
-between the rendered map and the frames it was built from (the reference-free consistency measure of a surfel map).
-bench.py and the parity tests import these (inputs may be torch tensors on any device or numpy arrays; only `map_chamfer`
-and `depth_residual` need the GPU).
+between the rendered map and the frames it was built from (the reference-free consistency measure of a surfel map), as
+a report (`depth_residual`) and as a loss on the autograd tape (`render_loss`).
+bench.py and the parity tests import these (inputs may be torch tensors on any device or numpy arrays; only `map_chamfer`,
+`depth_residual` and `render_loss` need the GPU).
 """
 from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
 
-__all__ = ["ate_rmse", "rpe", "map_chamfer", "table_parity", "count_drift", "depth_residual"]
+__all__ = ["ate_rmse", "rpe", "map_chamfer", "table_parity", "count_drift", "depth_residual", "render_loss"]
 
 
 def _poses(p) -> torch.Tensor:
@@ -161,3 +162,38 @@ def depth_residual(pointclouds, rgbdimages, **render_kwargs) -> Dict[str, torch.
                          torch.where(some, med, nan), torch.where(some, ((dz * dz).sum(-1) / nf64).sqrt(), nan), nf64])
     stats = stats.cpu()
     return {"coverage": stats[0], "mean_abs": stats[1], "median_abs": stats[2], "rmse": stats[3], "pixels": stats[4]}
+
+
+def render_loss(pointclouds, rgbdimages, *, depth_weight: float = 1.0, color_weight: float = 0.0,
+                **render_kwargs) -> torch.Tensor:
+    """Photometric / geometric consistency of a surfel map with frames, ON THE AUTOGRAD TAPE: the map is rendered from
+    every frame's pose (`Pointclouds.render(differentiable=True)`; render_kwargs: radius, min_confidence,
+    cull_backfaces) and compared with the frame.  Per sequence and frame -- a (B, L) float32 tensor on the device:
+      depth_weight * mean of 1/2 (rendered - frame depth)^2  +  color_weight * mean of 1/2 |rendered - frame colour|^2
+    both means over the pixels valid in both (rendered depth > 0 and frame depth > 0: the mask of `depth_residual`, a
+    constant of the gradient), so that with the defaults the value is 1/2 rmse^2 of `depth_residual`.  A frame without
+    such a pixel gives 0 and no gradient (never NaN).  Gradients reach the map buffers and the frames' poses through
+    the HIP backward of the render (the winner of every pixel is a constant); the frames' own depth and colour are
+    targets (detached).  Differences and sums are taken in float64 on the device, the result is rounded once."""
+    if not rgbdimages.has_poses:
+        raise ValueError("render_loss needs frames with poses")
+    B, L, H, W = rgbdimages.shape
+    rendered = pointclouds.render(rgbdimages.intrinsics, rgbdimages.poses, H, W, differentiable=True, **render_kwargs)
+    fd = rgbdimages.depth_image.detach()
+    fd = (fd[:, :, 0] if rgbdimages.channels_first else fd[..., 0]).reshape(B, L, H * W).to(torch.float64)
+    rd = rendered.depth_image[..., 0].reshape(B, L, H * W).to(torch.float64)
+    both = (fd > 0) & (rd.detach() > 0)
+    n = both.sum(-1).to(torch.float64)
+    inv = torch.where(n > 0, 1.0 / n.clamp(min=1.0), torch.zeros_like(n))
+    zero = torch.zeros_like(rd)
+    loss = torch.zeros((B, L), dtype=torch.float64, device=rd.device)
+    if depth_weight:
+        d = torch.where(both, rd - fd, zero)
+        loss = loss + float(depth_weight) * 0.5 * (d * d).sum(-1) * inv
+    if color_weight:
+        fc = rgbdimages.rgb_image.detach()
+        fc = (fc.permute(0, 1, 3, 4, 2) if rgbdimages.channels_first else fc).reshape(B, L, H * W, 3).to(torch.float64)
+        rc = rendered.rgb_image.reshape(B, L, H * W, 3).to(torch.float64)
+        c = torch.where(both.unsqueeze(-1), rc - fc, torch.zeros_like(rc))
+        loss = loss + float(color_weight) * 0.5 * (c * c).sum((-1, -2)) * inv
+    return loss.to(torch.float32)

@@ -835,14 +835,33 @@ def update_map_fusion_batch_(maps, vertex, normal, depth, rgb, alpha, poses, K, 
 RenderedViews = collections.namedtuple("RenderedViews", ["depth", "color", "normal", "confidence", "index"])
 
 
-def render_map_batch(maps, poses, K, H, W, radius=0, min_confidence=0.0, cull_backfaces=False, out=None):
-    """The maps of B sequences seen from L poses each (gs_render_map_dc_f32: a z-buffered point render, forward only,
-    one key launch and one resolve launch per 8 sequences x 4 views).  maps: per sequence (points, normals, colors,
+def render_map_batch(maps, poses, K, H, W, radius=0, min_confidence=0.0, cull_backfaces=False, out=None,
+                     differentiable=False, guard=None):
+    """The maps of B sequences seen from L poses each (gs_render_map_dc_f32: a z-buffered point render, one key launch
+    and one resolve launch per 8 sequences x 4 views).  maps: per sequence (points, normals, colors,
     ccounts, n_bound, n_dev) -- (rows, 3) / (rows, 1) float32 tensors of which the first n_bound rows (min(n_dev[0],
     n_bound) when the device count n_dev is given) are the map; normals / colors / ccounts may be None, the images that
     need them are then None.  poses (B, L, 4, 4) camera-to-world, K (B, 4, 4).  Returns RenderedViews(depth (B, L, H,
     W, 1), color (B, L, H, W, 3), normal (B, L, H, W, 3), confidence (B, L, H, W, 1), index (B, L, H, W) int64);
-    pixels no row lands on hold 0 (index: -1).  out: a RenderedViews (or 5-tuple) of tensors to write into."""
+    pixels no row lands on hold 0 (index: -1).  out: a RenderedViews (or 5-tuple) of tensors to write into.
+    differentiable=False: the result is detached (with a warning when an input requires grad).  differentiable=True:
+    the four float images are on the autograd tape (RenderMapFunction per sequence: gradients reach the map rows and
+    the poses, not K; index stays a plain tensor); `out` is then refused.  guard: see RenderMapFunction."""
+    if differentiable:
+        if out is not None:
+            raise ValueError("render_map: out= cannot be combined with differentiable=True (autograd owns the outputs)")
+        if len(maps) != int(poses.shape[0]) or K.ndim != 3 or K.shape[0] != len(maps):
+            raise ValueError("render_map: expected poses (B, L, 4, 4) and K (B, 4, 4) for B = %d maps; got %s and %s"
+                             % (len(maps), tuple(poses.shape), tuple(K.shape)))
+        poses = poses.to(f32)
+        per = [RenderMapFunction.apply(m[0], m[1], m[2], m[3], poses[b], K[b].detach(), m[4], m[5], int(H), int(W),
+                                       int(radius), float(min_confidence), bool(cull_backfaces), guard)
+               for b, m in enumerate(maps)]
+        if any((per[0][i] is None) != (r[i] is None) for r in per for i in range(5)):
+            raise ValueError("render_map: every map of a batch must carry the same attributes")
+        return RenderedViews(*[None if per[0][i] is None else
+                               (per[0][i].unsqueeze(0) if len(per) == 1 else torch.stack([r[i] for r in per]))
+                               for i in range(5)])
     _warn_detached("render_map", poses, K, *[t for m in maps for t in m[:4]])
     poses, K = _c(poses.detach()), _c(K.detach())
     dev = require_device(poses, K)
@@ -897,17 +916,128 @@ def render_map_batch(maps, poses, K, H, W, radius=0, min_confidence=0.0, cull_ba
 
 
 def render_map(points, normals, colors, ccounts, poses, K, H, W, n_dev=None, radius=0, min_confidence=0.0,
-               cull_backfaces=False, out=None):
+               cull_backfaces=False, out=None, differentiable=False):
     """One map seen from L poses: render_map_batch for B = 1 without the batch dimension.  poses (L, 4, 4) or (4, 4),
     K (4, 4); n_dev: device int64[1] holding the actual row count (points.shape[0] is then an upper bound).  Returns
-    RenderedViews(depth (L, H, W, 1), color (L, H, W, 3), normal (L, H, W, 3), confidence (L, H, W, 1), index (L, H, W))."""
+    RenderedViews(depth (L, H, W, 1), color (L, H, W, 3), normal (L, H, W, 3), confidence (L, H, W, 1), index (L, H, W)).
+    differentiable: see render_map_batch."""
     if poses.ndim == 2:
         poses = poses.unsqueeze(0)
     if out is not None:
         out = tuple(None if t is None else t.unsqueeze(0) for t in out)
     r = render_map_batch([(points, normals, colors, ccounts, None, n_dev)], poses.unsqueeze(0), K.reshape(1, 4, 4), H, W,
-                         radius=radius, min_confidence=min_confidence, cull_backfaces=cull_backfaces, out=out)
+                         radius=radius, min_confidence=min_confidence, cull_backfaces=cull_backfaces, out=out,
+                         differentiable=differentiable)
     return RenderedViews(*[None if t is None else t[0] for t in r])
+
+
+def render_map_backward_batch(maps, poses, K, index, upstream, H, W, radius=0, want=(True, True, True, True, True)):
+    """Reverse mode of render_map_batch for B sequences in ONE call of gs_render_map_backward_dc_f32 (8 sequences and 4
+    views per launch).  maps: per sequence (points, normals, n_bound, n_dev) as given to the forward (normals may be
+    None when upstream[2] is); poses (B, L, 4, 4), K (B, 4, 4), index (B, L, H, W) int64: the index image of the
+    forward; upstream: (depth_bar (B, L, H, W[, 1]), color_bar (B, L, H, W, 3), normal_bar (B, L, H, W, 3),
+    confidence_bar (B, L, H, W[, 1])), any of them None (its terms are skipped).  want: which of (points_bar,
+    normals_bar, colors_bar, ccounts_bar, poses_bar) to compute.  Returns (per-sequence list of (points_bar (rows, 3),
+    normals_bar (rows, 3), colors_bar (rows, 3), ccounts_bar (rows, 1)) with None where not wanted, poses_bar (B, L, 4,
+    4) or None); rows = points.shape[0], rows at or beyond the count hold zeros."""
+    poses, K, index = _c(poses.detach()), _c(K.detach()), _c(index, torch.int64)
+    ups = [None if t is None else _c(t.detach()) for t in upstream]
+    dev = require_device(poses, K, index, *ups)
+    Bn, Lv = int(poses.shape[0]), int(poses.shape[1])
+    H, W = int(H), int(W)
+    if len(maps) != Bn or tuple(poses.shape[2:]) != (4, 4) or tuple(K.shape) != (Bn, 4, 4) or \
+            tuple(index.shape) != (Bn, Lv, H, W) or Lv == 0:
+        raise ValueError("render_map_backward: expected poses (B, L, 4, 4), K (B, 4, 4) and index (B, L, H, W) for B = %d "
+                         "maps; got %s, %s and %s" % (len(maps), tuple(poses.shape), tuple(K.shape), tuple(index.shape)))
+    for t, c in zip(ups, (1, 3, 3, 1)):
+        if t is not None and t.numel() != Bn * Lv * H * W * c:
+            raise ValueError("render_map_backward: an upstream image does not match (B, L, H, W, %d)" % c)
+    T_bar = torch.empty((Bn, Lv, 4, 4), dtype=f32, device=dev) if want[4] else None
+    L = lib()
+    ws = Workspace.get(dev)
+    seqs = (_C.RenderBackwardSeq * Bn)()
+    P1 = Lv * H * W
+    rows_out = []
+    held = []
+    for b in range(Bn):
+        P, N = _c(maps[b][0].detach()), (None if maps[b][1] is None else _c(maps[b][1].detach()))
+        n_bound, n_dev = maps[b][2], maps[b][3]
+        require_device(P, N, n_dev, poses)
+        rows = int(P.shape[0])
+        if P.ndim != 2 or P.shape[1] != 3 or (N is not None and N.shape[0] < rows):
+            raise ValueError("render_map_backward: points must be (rows, 3) and the normals must hold as many rows")
+        if N is None and ups[2] is not None:
+            raise ValueError("render_map_backward: normal_bar given but the map has no normals")
+        n_bound = rows if n_bound is None else min(int(n_bound), rows)
+        outs = []
+        for i, c in enumerate((3, 3, 3, 1)):
+            t = None
+            if want[i]:
+                t = torch.empty((rows, c), dtype=f32, device=dev)
+                if n_bound < rows:
+                    t[n_bound:].zero_()   # (rows of the buffer behind the bound: the kernel writes the first n_bound rows)
+            outs.append(t)
+        rows_out.append(tuple(outs))
+        held.append((P, N))
+        u = seqs[b]
+        u.map = _C.MapView(P.data_ptr(), 0 if N is None else N.data_ptr(), 0, 0, rows, n_bound,
+                           0 if n_dev is None else n_dev.data_ptr())
+        u.poses16, u.K16, u.index = poses.data_ptr() + b * Lv * 64, K.data_ptr() + b * 64, index.data_ptr() + b * P1 * 8
+        u.depth_bar, u.color_bar, u.normal_bar, u.confidence_bar = (
+            None if t is None else t.data_ptr() + b * P1 * c * 4 for t, c in zip(ups, (1, 3, 3, 1)))
+        u.points_bar, u.normals_bar, u.colors_bar, u.ccounts_bar = (None if t is None else t.data_ptr() for t in outs)
+        if T_bar is not None:
+            u.poses_bar = T_bar.data_ptr() + b * Lv * 64
+            u.scratch = ws.bytes("render_bwd%d" % b, L.gs_render_backward_scratch_bytes(Lv, H, W, n_bound)).data_ptr()
+    check(L.gs_render_map_backward_dc_f32(seqs, Bn, Lv, H, W, int(radius), stream(dev)), "gs_render_map_backward_dc_f32")
+    return rows_out, T_bar
+
+
+class RenderMapFunction(torch.autograd.Function):
+    """The model view of ONE sequence on the autograd tape: forward = gs_render_map_dc_f32 (the plain render, which also
+    yields the index image), backward = one call of gs_render_map_backward_dc_f32 (render_map_backward_batch).  The
+    render is a hard z-buffer: the winner of every pixel and the min_confidence / cull_backfaces filters are constants
+    (as the correspondences of FuseAppendFunction are); gradients flow through the winner's depth, colour, camera-frame
+    normal and confidence to the map rows and to the poses.  K and the index image get none.  Images the loss does not
+    use reach the kernel as NULL (their terms are skipped; no zero images are made up).  The backward re-projects the
+    map rows, so the map buffers must hold at backward time what they held at the forward (run backward before the next
+    in-place step); in-place steps write through raw pointers, which torch's version counters do not see, so a caller
+    that can tell passes `guard`, a callable that raises when the map has changed (Pointclouds.render does)."""
+
+    @staticmethod
+    def forward(ctx, points, normals, colors, ccounts, poses, K, n_bound, n_dev, H, W, radius, min_confidence,
+                cull_backfaces, guard=None):
+        if poses.ndim != 3 or tuple(poses.shape[1:]) != (4, 4) or tuple(K.shape) != (4, 4):
+            raise ValueError("render_map: expected poses (L, 4, 4) and K (4, 4) per map; got %s and %s"
+                             % (tuple(poses.shape), tuple(K.shape)))
+        r = render_map_batch([(points, normals, colors, ccounts, n_bound, n_dev)], poses.unsqueeze(0), K.unsqueeze(0),
+                             H, W, radius=radius, min_confidence=min_confidence, cull_backfaces=cull_backfaces)
+        r = RenderedViews(*[None if t is None else t[0] for t in r])
+        ctx.save_for_backward(points, normals, poses, K, r.index, n_dev)
+        ctx.geom = (H, W, radius, n_bound)
+        ctx.shapes = tuple(None if t is None else tuple(t.shape) for t in (points, normals, colors, ccounts))
+        ctx.guard = guard
+        ctx.set_materialize_grads(False)   # an image the loss does not use arrives as None, not as a zero image
+        ctx.mark_non_differentiable(r.index)
+        return tuple(r)
+
+    @staticmethod
+    def backward(ctx, depth_bar, color_bar, normal_bar, conf_bar, _index_bar):
+        if ctx.guard is not None:
+            ctx.guard()
+        points, normals, poses, K, index, n_dev = ctx.saved_tensors
+        H, W, radius, n_bound = ctx.geom
+        need = ctx.needs_input_grad
+        ups = (depth_bar, color_bar, normal_bar, conf_bar)
+        if all(t is None for t in ups):
+            return (None,) * 14
+        want = tuple(bool(need[i]) and ctx.shapes[i] is not None for i in range(4)) + (bool(need[4]),)
+        rows_out, T_bar = render_map_backward_batch([(points, normals, n_bound, n_dev)], poses.unsqueeze(0),
+                                                    K.unsqueeze(0), index.unsqueeze(0),
+                                                    [None if t is None else t.unsqueeze(0) for t in ups], H, W, radius,
+                                                    want=want)
+        outs = [None if t is None else t.view(shape) for t, shape in zip(rows_out[0], ctx.shapes)]
+        return (outs[0], outs[1], outs[2], outs[3], None if T_bar is None else T_bar[0]) + (None,) * 9
 
 
 # ----------------------------------------------------------------------------------- K7 (autograd)

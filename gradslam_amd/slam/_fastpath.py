@@ -171,6 +171,7 @@ class StepPlan(object):
         else:
             live._global_vertex_map = live._global_normal_map = None    # (computed on demand under the new pose)
         grp.advance(cnt_new, P)
+        pc._generation += 1
         pc._padded_cache.clear()
         pc.equisized = True if B == 1 else None
         return pc, live._poses

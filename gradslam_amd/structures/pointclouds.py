@@ -141,6 +141,7 @@ class Pointclouds(object):
         self._dcount = {}                       # b -> _DeviceCount while the count of b is device-side
         self._n_host: List[int] = []            # points per sequence (see the `_n` property)
         self._padded_cache = {}
+        self._generation = 0   # bumped by everything that changes the map in place (see render(differentiable=True))
         self.equisized = None
 
         if isinstance(points, list):
@@ -387,6 +388,7 @@ class Pointclouds(object):
     # ------------------------------------------------------------------ surfel-store interface
     # (used by gradslam_amd.slam.fusionutils; not part of the reference API)
     def _invalidate(self):
+        self._generation += 1
         self._padded_cache.clear()
         self.equisized = (len(set(self._n)) == 1) if self._n else None
 
@@ -434,6 +436,7 @@ class Pointclouds(object):
                 new = torch.empty((new_cap, old.shape[-1]), dtype=old.dtype, device=self.device)
                 new[:n_b] = old[:n_b]
                 self._buf[k][b] = new
+            self._generation += 1
             self._padded_cache.clear()
         return tuple(None if self._buf[k] is None else self._buf[k][b] for k in _ATTRS)
 
@@ -468,6 +471,7 @@ class Pointclouds(object):
             self._dcount[b] = _DeviceCount(_CountGroup(dev_count.reshape(1), [bound]), 0)
         else:
             dc.group.advance(dev_count.reshape(1), max_growth)
+        self._generation += 1
         self._padded_cache.clear()
         self.equisized = True if len(self._n_host) == 1 else None
 
@@ -485,13 +489,16 @@ class Pointclouds(object):
             grp = _CountGroup(dev_counts, bounds)
             for b in range(B):
                 self._dcount[b] = _DeviceCount(grp, b)
+        self._generation += 1
         self._padded_cache.clear()
         self.equisized = True if B == 1 else None
 
     # ------------------------------------------------------------------ the model view
     def render(self, intrinsics: torch.Tensor, poses: torch.Tensor, height: int, width: int, *, radius: int = 0,
-               min_confidence: float = 0.0, cull_backfaces: bool = False, return_extras: bool = False):
-        r"""The map seen from camera poses: a z-buffered point render (HIP, forward only; the result is detached).
+               min_confidence: float = 0.0, cull_backfaces: bool = False, return_extras: bool = False,
+               differentiable: bool = False):
+        r"""The map seen from camera poses: a z-buffered point render (HIP; the result is detached unless
+        `differentiable` is set).
 
         Every point competes for the pixel it projects to (the projection of the SLAM association, with the image size
         `height` x `width`, which need not be the capture size -- scale the intrinsics to match); the nearest point
@@ -509,6 +516,12 @@ class Pointclouds(object):
                 from them this removes the visible side
             return_extras: also return {"normal": (B, L, H, W, 3) camera-frame normal of the winner, "confidence":
                 (B, L, H, W, 1), "index": (B, L, H, W) int64 row of the winner or -1}
+            differentiable: keep the rendered depth, colour, normal and confidence on the autograd tape
+                (`ops.RenderMapFunction`, a HIP backward kernel): a loss on them reaches the map buffers and `poses`,
+                neither of which is detached.  The z-buffer is hard: which point wins a pixel, and the two filters, are
+                constants of the gradient; `intrinsics` and the index image get none.  The backward pass re-projects
+                the map, so run it before the map is changed in place (before the next `PointFusion.step`); a
+                backward after such a change raises instead of returning gradients of the wrong rows.
 
         Returns:
             RGBDImages of shape (B, L, height, width) holding the rendered colour and depth with `intrinsics` and
@@ -534,10 +547,20 @@ class Pointclouds(object):
         for b in range(B):
             bound, n_dev = self._count_of(b)   # (never forces a device-side count to the host)
             maps.append(tuple(self._buf[k][b] for k in _ATTRS) + (bound, n_dev))
+        guard = None
+        if differentiable:
+            generation = self._generation
+
+            def guard():
+                if self._generation != generation:
+                    raise RuntimeError("the map was changed in place after render(differentiable=True) and before its "
+                                       "backward pass: the saved winners no longer belong to the map rows (run backward "
+                                       "before the next PointFusion.step, or render again)")
         out = ops.render_map_batch(maps, poses, intrinsics[:, 0], int(height), int(width), radius=radius,
-                                   min_confidence=min_confidence, cull_backfaces=cull_backfaces)
+                                   min_confidence=min_confidence, cull_backfaces=cull_backfaces,
+                                   differentiable=differentiable, guard=guard)
         frames = RGBDImages(out.color, out.depth, intrinsics.detach().to(torch.float32),
-                            poses.detach().to(torch.float32))
+                            poses.to(torch.float32) if differentiable else poses.detach().to(torch.float32))
         if return_extras:
             return frames, {"normal": out.normal, "confidence": out.confidence, "index": out.index}
         return frames

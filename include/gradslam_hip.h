@@ -560,7 +560,7 @@ GS_API int gs_unproject_points_f32(const float* pixel_coords, int pdim, int64_t 
 GS_API int gs_lie_small_f32(int op, const float* in, float* out, void* stream);
 
 /* ------------------------------------------------------------------ the model view ------
- * A surfel map seen from a pose: a z-buffered point render of B maps under L views each, forward only (the reference
+ * A surfel map seen from a pose: a z-buffered point render of B maps under L views each (the reference
  * has no such call; its Pointclouds.open3d / .plotly viewers are the nearest thing, structures/pointclouds.py:1239, :1296).
  * Row i of a map lands on the pixel (h, w) that gs_project_map_f32 gives it for the view's pose and the image size
  * H x W (which need not be the capture size); its depth z is the third camera-frame coordinate of that projection.  The
@@ -589,6 +589,43 @@ typedef struct gs_render_seq {
 GS_API int64_t gs_render_scratch_bytes(int views, int H, int W);
 GS_API int gs_render_map_dc_f32(const gs_render_seq* seqs_host, int B, int L, int H, int W, int radius,
                                 float min_confidence, int cull_backfaces, void* stream);
+
+/* Reverse mode of gs_render_map_dc_f32.  The render is a hard z-buffer: which row wins which pixel (the `index` image of
+ * the forward, passed back in) and the two filters are constants; gradients flow through the values written for the
+ * winner.  With T = [R t; 0 1] the view's pose, row n the winner of pixel i and zb / cb / ob / fb the adjoints of the
+ * depth / colour / normal / confidence images at i:
+ *   points_bar[n][k] += R[k][2] zb;  normals_bar[n][k] += sum_j R[k][j] ob_j;  colors_bar[n] += cb;  ccounts_bar[n] += fb;
+ *   poses_bar[v][k][j] += n_k ob_j (j < 3);  poses_bar[v][k][2] += (p_k - t_k) zb;  poses_bar[v][k][3] -= R[k][2] zb
+ * summed over all pixels and views a row wins (row outputs) / all pixels of the view (poses_bar[v], bottom row zero).
+ * K16 gets no gradient.  map, poses16, K16, H, W and radius must be those of the forward call (the map rows are
+ * re-projected to find the pixels they could have won); map.colors / ccounts / capacity are not used.  Any upstream image
+ * may be NULL: its terms are skipped; they are read only at pixels with a winner (their contents at empty pixels mean
+ * nothing).  Any output may be NULL.  The row outputs hold map.n_bound rows ((n_bound, 3), ccounts_bar (n_bound)), every
+ * row is written: rows that win nothing and rows at or beyond the count (map.n_dev included) receive exact zeros, so the
+ * buffers need no clearing.  scratch: gs_render_backward_scratch_bytes(L, H, W, map.n_bound) bytes per sequence, needed
+ * with poses_bar.  No float atomics: sums are taken in float64 in a fixed order, every output is bitwise reproducible and
+ * poses_bar[v] does not depend on the other views of the call.  Views are served 4 per launch: with L > 4 the row outputs
+ * are rounded to float32 after each group of 4 views and the next group adds its float64 sums to those float32 values
+ * (one more rounding per group, in view order); B sequences are served 8 per launch, each exactly as in a call of its own. */
+typedef struct gs_render_backward_seq {
+  gs_map_view map;
+  const float* poses16;        /* (L, 16) */
+  const float* K16;
+  const int64_t* index;        /* (L, H, W): the index image the forward wrote */
+  const float* depth_bar;      /* upstream adjoints: (L, H, W) */
+  const float* color_bar;      /* (L, H, W, 3) */
+  const float* normal_bar;     /* (L, H, W, 3) */
+  const float* confidence_bar; /* (L, H, W) */
+  float* points_bar;           /* out (n_bound, 3) */
+  float* normals_bar;          /* out (n_bound, 3) */
+  float* colors_bar;           /* out (n_bound, 3) */
+  float* ccounts_bar;          /* out (n_bound) */
+  float* poses_bar;            /* out (L, 16) */
+  void* scratch;
+} gs_render_backward_seq;
+GS_API int64_t gs_render_backward_scratch_bytes(int views, int H, int W, int64_t n_bound);
+GS_API int gs_render_map_backward_dc_f32(const gs_render_backward_seq* seqs_host, int B, int L, int H, int W,
+                                         int radius, void* stream);
 
 #ifdef __cplusplus
 }

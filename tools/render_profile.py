@@ -5,6 +5,7 @@
                                                                 rocprofv3 --kernel-trace --stats, no counters)
     python tools/render_profile.py --kernel-stats small=CSV large=CSV [--out FILE]
                                                                 algorithmic bytes over the kernel times of those runs
+    python tools/render_profile.py --backward [--out FILE]      forward and backward of the differentiable render, timed
 
 new       one Pointclouds.render call, one view, all five images.
 baseline  the same five images from ops.project_map + ops.transform_points + int64 key packing +
@@ -187,6 +188,67 @@ def compare(out):
         sys.exit("the new call is not ahead of the baseline at both sizes")
 
 
+def two_frame_case(gs, torch):
+    """the 480x640 map of two frames (ground-truth odometry) seen from its second pose"""
+    from gradslam_amd.datasets.synthetic import make_sequence
+    s = make_sequence(2, 480, 640, seed=5)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    frames = gs.RGBDImages(T(s["colors"][None]), T(s["depths"][None]), T(s["intrinsics"][None]), T(s["poses"][None]))
+    pc, _ = gs.slam.PointFusion(odom="gt", device="cuda")(frames)
+    return pc, frames.intrinsics, frames.poses[:, 1:].contiguous(), 480, 640
+
+
+def backward_times(out):
+    """Forward (the plain render, five images) and backward (gs_render_map_backward_dc_f32 through autograd: all four
+    upstream images, gradients for the four map attributes and the pose) of one view, microseconds per call."""
+    import torch
+    import gradslam_amd as gs
+    from gradslam_amd import ops
+    assert torch.cuda.is_available(), "needs the MI355X"
+    lines = ["# tools/render_profile.py --backward: ops.render_map (one view, five images) and the backward of",
+             "# ops.render_map(differentiable=True) (torch.autograd.grad: four upstream images -> points, normals, colours, counts,",
+             "# pose); microseconds per call, device events, forward and backward windows alternating"]
+    for name, case, radius in (("two-frame 640x480", two_frame_case, 0), ("two-frame 640x480", two_frame_case, 1),
+                               ("large", large_case, 0)):
+        pc, K, pose, H, W = case(gs, torch)
+        n = int(pc.num_points_per_pointcloud[0])
+        leaves = [pc._buf[k][0][:n].detach().clone().requires_grad_(True) for k in ("points", "normals", "colors", "features")]
+        T4 = pose[0].detach().clone().requires_grad_(True)
+        K4 = K[0, 0].contiguous()
+        plain = [t.detach() for t in leaves]
+
+        def fwd():
+            return ops.render_map(*plain, T4.detach(), K4, H, W, radius=radius)
+        r = ops.render_map(*leaves, T4, K4, H, W, radius=radius, differentiable=True)
+        outs = [r.depth, r.color, r.normal, r.confidence]
+        ups = [torch.randn_like(t) for t in outs]
+
+        def bwd():
+            return torch.autograd.grad(outs, leaves + [T4], ups, retain_graph=True)
+        hits = int((r.index >= 0).sum())
+        for _ in range(3):
+            fwd(), bwd()
+        torch.cuda.synchronize()
+        reps_f = max(10, int(math.ceil(5000.0 / timed(torch, fwd, 10))))
+        reps_b = max(10, int(math.ceil(5000.0 / timed(torch, bwd, 10))))
+        tf, tb = [], []
+        for _ in range(9):
+            tf.append(timed(torch, fwd, reps_f))
+            tb.append(timed(torch, bwd, reps_b))
+        med = lambda x: float(np.median(x))  # noqa: E731
+        lines += ["", "## %s, radius %d: %d x %d view of %d surfels, %d of %d pixels covered" % (name, radius, W, H, n, hits, H * W),
+                  "forward   median %9.1f us   min %9.1f   max %9.1f   (%d calls per window, 9 windows)" % (med(tf), min(tf), max(tf), reps_f),
+                  "backward  median %9.1f us   min %9.1f   max %9.1f   (%d calls per window, 9 windows)" % (med(tb), min(tb), max(tb), reps_b),
+                  "backward / forward = %.2f" % (med(tb) / med(tf))]
+        del pc, leaves, plain, r, outs, ups
+        torch.cuda.empty_cache()
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out:
+        with open(out, "a") as f:
+            f.write(text)
+
+
 def trace_run(which, calls=30):
     import torch
     import gradslam_amd as gs
@@ -225,8 +287,11 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=None, help="append the report to this file")
     ap.add_argument("--trace-run", choices=["small", "large"], default=None)
     ap.add_argument("--kernel-stats", nargs="+", metavar="NAME=CSV,n,H,W,hits", default=None)
+    ap.add_argument("--backward", action="store_true", help="time forward and backward of the differentiable render")
     a = ap.parse_args()
-    if a.trace_run:
+    if a.backward:
+        backward_times(a.out)
+    elif a.trace_run:
         trace_run(a.trace_run)
     elif a.kernel_stats:
         kernel_stats(a.kernel_stats, a.out)
