@@ -19,8 +19,10 @@
 #include <string.h>
 
 #include <memory>
+#include <mutex>
 #include <type_traits>
 
+#include "gs_env.h"
 #include "gs_icp_math.h"
 #include "gs_knn.h"
 #include "gs_knn_bbox.h"
@@ -121,8 +123,8 @@ GS_DEV void icp_sum_rows_split(const double* __restrict__ partials, int nrows, d
         // has to wait for ALL outstanding loads wherever it needs an older one -- here that would drain the gathers the
         // hook puts in flight.  Rows beyond nrows (at most 24 x 18 of them from the start of the buffer, 97 KB; the
         // single-column variant below: FS_BLOCK rows, 172 KB) are read from what follows the rows in the caller's
-        // scratch (the second row buffer, the grid, the lists -- localize_chunk checks that they cover it before it
-        // plans a solve with lists) and never looked at; one base address + immediate offsets, as in icp_sum_rows.
+        // scratch (the second row buffer, the grid, the lists -- loc_lists_fit checks that they cover it before a
+        // solve with lists is planned) and never looked at; one base address + immediate offsets, as in icp_sum_rows.
         const int b0 = b + half * HC;
         const int left = act ? nrows - b0 : 0;
         const double* base = partials + (int64_t)b0 * LIN_NV + i;
@@ -937,12 +939,25 @@ __global__ void __launch_bounds__(FS_BLOCK, 6) gs_icp_half_batch_kernel(const Ic
 
 #include "gs_icp_persist.h"
 
-// the persistent solve's sync record lives in the padding behind the one row of large solves (icp_carve: rowred)
-constexpr int ICP_ROWRED_DOUBLES = 32;
-static_assert(sizeof(double) * ICP_ROWRED_DOUBLES >= sizeof(double) * LIN_NV + sizeof(unsigned) * PS_WORDS,
-              "the sync record does not fit behind rowred + LIN_NV");
-
 static size_t icp_rows(int64_t n_src) { return (size_t)gs_ceil_div(n_src, FS_QPB); }  // >= ceil(n_src / LIN_BLOCK)
+
+// What the host asks of a device, once per device: its CU count, and whether the persistent solve fits it.  That solve
+// puts a sequence's blocks on ONE XCD of PS_CUS_PER_XCD CUs (gs_icp_persist.h): only a whole gfx950 device qualifies (a
+// partitioned one shows fewer CUs).
+struct IcpDevice { int cus = 256; bool ps_fits = false; };
+static IcpDevice icp_device() {
+  constexpr int MAX_DEV = 64;
+  static IcpDevice facts[MAX_DEV]; static std::once_flag asked[MAX_DEV];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return IcpDevice{};
+  std::call_once(asked[dev], [dev] {
+    int v = 0; hipDeviceProp_t p;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) facts[dev].cus = v;
+    facts[dev].ps_fits = hipGetDeviceProperties(&p, dev) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0 &&
+                         p.multiProcessorCount == (int)(GS_XCDS * PS_CUS_PER_XCD);
+  });
+  return facts[dev];
+}
 
 // Launch geometry of a half-iteration: lanes per query G, blocks per sequence nb and row units per block upb.
 // Every sequence of the batch gets an equal share of the blocks; the largest G whose blocks all fit that share wins
@@ -953,27 +968,12 @@ static size_t icp_rows(int64_t n_src) { return (size_t)gs_ceil_div(n_src, FS_QPB
 // otherwise (8 sequences of 640x480: 400 blocks at 2 lanes per point).
 // GRADSLAM_HIP_ICP_LANES = 2 | 4 | 8 forces G, GRADSLAM_HIP_ICP_BLOCKS_PER_CU the share (A/B runs: the results do not
 // depend on either).
-struct IcpHalfPlan {
-  int G, nb, upb;
-};
-static IcpHalfPlan icp_half_plan(int64_t n_src, int B, int g_max = 8) {
-  static int cus = 0, forced = -1, per_cu = 0;   // (per_cu 0: one block per CU if some G fits that, else two)
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      cus = v;
-    else
-      cus = 256;
-  }
-  if (forced < 0) {
-    const char* e = getenv("GRADSLAM_HIP_ICP_LANES");
-    forced = e ? atoi(e) : 0;
-    const char* f = getenv("GRADSLAM_HIP_ICP_BLOCKS_PER_CU");  // resident-block budget per CU (experiments)
-    if (f && atoi(f) > 0) per_cu = atoi(f);
-  }
+struct IcpHalfPlan { int G, nb, upb; };
+static IcpHalfPlan icp_half_plan(const GsEnv& env, int cus, int64_t n_src, int B, int g_max = 8) {
+  const int forced = env.icp_lanes;
   const int nunits = (int)icp_rows(n_src);
-  int share = per_cu;
-  if (share == 0) {
+  int share = env.icp_blocks_per_cu;   // (not set: one block per CU if some G fits that, else two)
+  if (share <= 0) {
     const int NU2 = FS_BLOCK / 2 / FS_QPB;   // (the fewest blocks a single group of units per block needs: G = 2)
     share = (nunits + NU2 - 1) / NU2 <= cus / B ? 1 : 2;
   }
@@ -991,30 +991,15 @@ static IcpHalfPlan icp_half_plan(int64_t n_src, int B, int g_max = 8) {
   }
   return pl;
 }
-static unsigned long long* g_icp_tl_buf = nullptr;
+
+#include "gs_icp_timeline.h"
+
 // lmode: what the launch does with the candidate lists of ordinary queries (icp_half_body; 0 = the variant without them)
 template <bool FULL>
 static void icp_half_launch(const IcpHalfPlan& pl, IcpHalfBatch& hb, GsCount n_src_c, const gs_icp_params* prm, int it,
                             int rows_in_reduced, hipStream_t st, int lmode = 0) {
   hb.upb = pl.upb;
-  // debugging aid (library built with -DGS_ICP_TIMELINE): per-block time stamps of the LAST iteration's two launches,
-  // the first half into <path>, the look-ahead that follows it back to back into <path>.next (their first block starts
-  // are one launch period apart); both are written after the second launch
-  static const char* tl_path = getenv("GRADSLAM_HIP_ICP_TIMELINE");
-  unsigned long long*& tl_buf = g_icp_tl_buf;   // (one buffer for both instantiations of this template)
-  constexpr size_t TL_HALF = 72 * 7000;
-  hb.timeline = nullptr;
-  const size_t tl_n = 72 * (size_t)hb.B * pl.nb;
-  static const char* tl_it_env = getenv("GRADSLAM_HIP_ICP_TIMELINE_IT");   // the iteration recorded (default: the last)
-  const int tl_it = tl_it_env ? atoi(tl_it_env) : prm->numiters - 1;
-  const bool tl = tl_path && it == tl_it;
-  if (tl) {
-    if (!tl_buf && hipMalloc(&tl_buf, 8 * 2 * TL_HALF) != hipSuccess) tl_buf = nullptr;
-    if (tl_buf && tl_n <= TL_HALF) {
-      hb.timeline = tl_buf + (FULL ? 0 : TL_HALF);
-      if (FULL) (void)hipMemsetAsync(tl_buf, 0, 8 * 2 * TL_HALF, st);
-    }
-  }
+  hb.timeline = icp_tl_arm(FULL, hb.B * pl.nb, it, prm->numiters, st);
   const dim3 grid((unsigned)(hb.B * pl.nb)), block(FS_BLOCK);
   const bool far = hb.s[0].far_cq != nullptr;   // candidate lists of far queries: the same for all sequences of a batch
 #define GS_HALF_LAUNCH(G_, FAR_, LMODE_)                                                                               \
@@ -1027,33 +1012,14 @@ static void icp_half_launch(const IcpHalfPlan& pl, IcpHalfBatch& hb, GsCount n_s
     else if (lmode == 3 && G_ == 2) GS_HALF_LAUNCH(2, false, 3);             \
     else GS_HALF_LAUNCH(G_, false, 0);                                       \
   } while (0)
-  // (no 8-lane variant with far-candidate lists: its first half does not fit the register budget; localize_chunk plans
-  // solves with such lists for at most 4 lanes per query)
-  const bool lists = lmode != 0 && !far && hb.l[0].lq != nullptr;
-  if (!lists) lmode = 0;
+  // (no 8-lane variant with far-candidate lists: its first half does not fit the register budget; icp_engine_plan plans
+  // solves with such lists for at most 4 lanes per query, and a list mode other than 0 only for solves without them)
   if (pl.G == 8) GS_HALF_LAUNCH_L(8);
   else if (pl.G == 4) { if (far) GS_HALF_LAUNCH(4, true, 0); else GS_HALF_LAUNCH_L(4); }
   else { if (far) GS_HALF_LAUNCH(2, true, 0); else GS_HALF_LAUNCH_L(2); }
 #undef GS_HALF_LAUNCH_L
 #undef GS_HALF_LAUNCH
-  if (hb.timeline && !FULL) {  // debugging aid: synchronous dump of the two launches' block records
-    std::unique_ptr<unsigned long long[]> h(new unsigned long long[2 * TL_HALF]);
-    if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(h.get(), tl_buf, 8 * 2 * TL_HALF, hipMemcpyDeviceToHost) == hipSuccess) {
-      for (int part = 0; part < 2; ++part) {
-        char path[1024];
-        snprintf(path, sizeof(path), "%s%s", tl_path, part ? ".next" : "");
-        FILE* f = fopen(path, "w");
-        if (!f) continue;
-        fprintf(f, "# B=%d G=%d nb=%d upb=%d lmode=%d: block start end(100MHz ticks) hw_id xcc_id after_prologue after_search after_unres n_unres\n", hb.B, pl.G, pl.nb, pl.upb, lmode);
-        for (size_t i = 0; i < tl_n / 72; ++i) {
-          fprintf(f, "%zu", i);
-          for (int k = 0; k < 72; ++k) fprintf(f, " %llu", h[part * TL_HALF + 72 * i + k]);
-          fprintf(f, "\n");
-        }
-        fclose(f);
-      }
-    }
-  }
+  if (hb.timeline && !FULL) icp_tl_dump(hb, pl, lmode, st);   // (synchronous: both launches' block records)
   hb.timeline = nullptr;
 }
 
@@ -1200,47 +1166,43 @@ __global__ void gs_icp_init_kernel(GsIcpState* __restrict__ st, const float* __r
   if (numiters == 0) icp_write_result(sm, compose16, out_T16);  // degenerate: the (composed) initial transform
 }
 
+template <class T>
+static T* gs_at(void* base, size_t offset) { return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + offset); }
+struct GsTake { size_t end = 0; size_t operator()(size_t n) { end += n; return end - n; } };   // consecutive byte ranges
+
+// Scratch of one solve as byte offsets from its start: state | rowred | best | srcA | srcB | partials[2] | grid | spare.
+// The ONE description of it: gs_icp_scratch_bytes returns its total, icp_carve applies it to a base pointer.
+constexpr int ICP_ROWRED_DOUBLES = 32;
+struct IcpLayout { size_t state, rowred, sync, best, srcA, srcB, partials[2], grid, total; };
+static IcpLayout icp_layout(int64_t n_src, int64_t n_tgt) {
+  GsTake take;
+  IcpLayout L;
+  L.state = take(gs_align(sizeof(GsIcpState)));
+  L.rowred = take(gs_align(sizeof(double) * ICP_ROWRED_DOUBLES));
+  // the persistent solve's sync record (gs_icp_persist.h: PS_WORDS words) lives in the padding behind the one row
+  L.sync = L.rowred + sizeof(double) * LIN_NV;
+  static_assert(8 * ICP_ROWRED_DOUBLES >= 8 * LIN_NV + 4 * PS_WORDS, "the sync record does not fit behind rowred + LIN_NV");
+  L.best = take(gs_align(8 * (size_t)n_src));
+  L.srcA = take(gs_align(12 * (size_t)n_src)); L.srcB = take(gs_align(12 * (size_t)n_src));
+  for (int k = 0; k < 2; ++k) L.partials[k] = take(gs_align(sizeof(double) * LIN_NV * icp_rows(n_src)));
+  L.grid = take(gs_knn_grid_scratch_bytes(n_src, n_tgt));
+  L.total = take.end + 4096;
+  return L;
+}
 struct IcpScratch {
   GsIcpState* state;
   double* rowred;  // one partial row (large solves: gs_icp_reduce_rows_kernel)
-  unsigned long long* best;
-  float* srcA;
-  float* srcB;
-  double* partials[2];
-  void* grid;
+  unsigned* sync;  // [PS_WORDS] ticket / arrival / error words of the persistent solve
+  unsigned long long* best; float *srcA, *srcB;
+  double* partials[2]; void* grid;
 };
-static IcpScratch icp_carve(void* scratch, int64_t n_src) {
-  char* p = reinterpret_cast<char*>(scratch);
-  IcpScratch s;
-  s.state = reinterpret_cast<GsIcpState*>(p); p += gs_align(sizeof(GsIcpState));
-  s.rowred = reinterpret_cast<double*>(p); p += gs_align(sizeof(double) * ICP_ROWRED_DOUBLES);
-  s.best = reinterpret_cast<unsigned long long*>(p); p += gs_align(8 * (size_t)n_src);
-  s.srcA = reinterpret_cast<float*>(p); p += gs_align(12 * (size_t)n_src);
-  s.srcB = reinterpret_cast<float*>(p); p += gs_align(12 * (size_t)n_src);
-  for (int k = 0; k < 2; ++k) {
-    s.partials[k] = reinterpret_cast<double*>(p);
-    p += gs_align(sizeof(double) * LIN_NV * icp_rows(n_src));
-  }
-  s.grid = p;
-  return s;
+static IcpScratch icp_carve(void* p, const IcpLayout& L) {
+  return IcpScratch{gs_at<GsIcpState>(p, L.state), gs_at<double>(p, L.rowred), gs_at<unsigned>(p, L.sync),
+                    gs_at<unsigned long long>(p, L.best), gs_at<float>(p, L.srcA), gs_at<float>(p, L.srcB),
+                    {gs_at<double>(p, L.partials[0]), gs_at<double>(p, L.partials[1])}, gs_at<void>(p, L.grid)};
 }
 
-// GRADSLAM_HIP_KNN=brute forces the brute-force engine (A/B runs; results are identical).
-static bool icp_grid_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GRADSLAM_HIP_KNN");
-    v = (e && strcmp(e, "brute") == 0) ? 0 : 1;
-  }
-  return v == 1;
-}
-
-extern "C" int64_t gs_icp_scratch_bytes(int64_t n_src, int64_t n_tgt) {
-  if (n_src < 1) n_src = 1;
-  return (int64_t)(gs_align(sizeof(GsIcpState)) + gs_align(sizeof(double) * ICP_ROWRED_DOUBLES) + gs_align(8 * (size_t)n_src) + 2 * gs_align(12 * (size_t)n_src) +
-                   2 * gs_align(sizeof(double) * LIN_NV * icp_rows(n_src)) + gs_knn_grid_scratch_bytes(n_src, n_tgt) +
-                   4096);
-}
+extern "C" int64_t gs_icp_scratch_bytes(int64_t n_src, int64_t n_tgt) { return (int64_t)icp_layout(n_src < 1 ? 1 : n_src, n_tgt).total; }
 
 // the per-iteration trace [err, new_err, damp_after, sigmoid, xi(6), 0, 0] completes the tape
 static int icp_tape_finish(void* tape, const GsIcpState* state, int64_t n_src, int numiters, hipStream_t st) {
@@ -1273,12 +1235,12 @@ static int icp_run(const float* src, int64_t n_src, const float* tgt, const floa
   GS_REQUIRE(prm->numiters >= 0 && prm->numiters <= GS_ICP_MAX_ITERS, "numiters must be in [0, 1024]");
   GS_REQUIRE(prm->mode == 0 || prm->mode == 1, "mode must be 0 (ICP) or 1 (gradICP)");
   hipStream_t st = gs_stream(stream);
-  IcpScratch sc = icp_carve(icp_scratch, n_src);
+  IcpScratch sc = icp_carve(icp_scratch, icp_layout(n_src, n_tgt));
   hipLaunchKernelGGL(gs_icp_init_kernel, dim3(1), dim3(64), 0, st, sc.state, init16, prm->damp, prm->numiters,
                      compose16, out_T16);
   // device-side counts (n_src / n_tgt are then upper bounds) always take the grid path
   const bool dev_counts = n_src_dev || n_tgt_dev || flt.pix;  // a target filter exists only in the grid path
-  const bool use_grid = prm->numiters > 0 && (dev_counts || (icp_grid_enabled() && gs_knn_use_grid(n_src, n_tgt)));
+  const bool use_grid = prm->numiters > 0 && (dev_counts || (!gs_env().knn_brute && gs_knn_use_grid(n_src, n_tgt)));
   const GsCount n_src_c{n_src, n_src_dev}, n_tgt_c{n_tgt, n_tgt_dev};
   float* bufs[2] = {sc.srcA, sc.srcB};
   TapePtrs tp = {nullptr, nullptr, nullptr};
@@ -1313,7 +1275,7 @@ static int icp_run(const float* src, int64_t n_src, const float* tgt, const floa
       prof_bytes = icp_alg_bytes(prm->numiters, n_src, n_src, n_binned);
     }
     std::unique_ptr<GsProf> prof_loop(new GsProf(GS_PROF_ICP_FUSED, prof_bytes, st, 2 * prm->numiters));
-    const IcpHalfPlan plan = icp_half_plan(n_src, 1);
+    const IcpHalfPlan plan = icp_half_plan(gs_env(), icp_device().cus, n_src, 1);
     IcpHalfBatch hb;
     hb.B = 1;
     hb.weak_room = 0.0f;
@@ -1569,17 +1531,6 @@ struct ListMem {
   int* stat;       // [3 * GL_STAT_LAUNCHES] per launch of the solve: lists that failed their proof, points whose list
                    // is empty (nothing fitted), points the 2x2x2 stage cannot prove (no list)
 };
-static size_t list_mem_bytes(int64_t n_lat) {
-  return gs_align(16 * (size_t)n_lat) + gs_align(4 * GL_SLOTS * (size_t)n_lat) + gs_align(4 * 3 * GL_STAT_LAUNCHES);
-}
-static ListMem list_carve(void* base, int64_t n_lat) {
-  char* p = reinterpret_cast<char*>(base);
-  ListMem m;
-  m.lq = reinterpret_cast<float4*>(p); p += gs_align(16 * (size_t)n_lat);
-  m.ls = reinterpret_cast<uint32_t*>(p); p += gs_align(4 * GL_SLOTS * (size_t)n_lat);
-  m.stat = reinterpret_cast<int*>(p);
-  return m;
-}
 
 // candidate lists of far queries (gs_knn.h), behind the lists of the ordinary ones
 struct FarMem {
@@ -1588,19 +1539,6 @@ struct FarMem {
   int* idx;       // [FS_FAR_PASSES][n_lat] source points handed to the list builder
   int* n;         // [FS_FAR_PASSES] how many
 };
-static size_t far_mem_bytes(int64_t n_lat) {
-  return gs_align(4 * GS_FAR_SLOTS * (size_t)n_lat) + gs_align(16 * (size_t)n_lat) +
-         gs_align(4 * FS_FAR_PASSES * (size_t)n_lat) + 256;
-}
-static FarMem far_carve(void* base, int64_t n_lat) {
-  char* p = reinterpret_cast<char*>(base);
-  FarMem m;
-  m.c = reinterpret_cast<uint32_t*>(p); p += gs_align(4 * GS_FAR_SLOTS * (size_t)n_lat);
-  m.cq = reinterpret_cast<float4*>(p); p += gs_align(16 * (size_t)n_lat);
-  m.idx = reinterpret_cast<int*>(p); p += gs_align(4 * FS_FAR_PASSES * (size_t)n_lat);
-  m.n = reinterpret_cast<int*>(p);
-  return m;
-}
 
 // Lists for the source points a first half found far from every target (IcpHalfSeq::far_idx): one launch behind the
 // first halves of iterations 0, 1, 4, 8, ... (fs_far_pass; the step of iteration 0 is the large one of a solve: lists
@@ -1685,354 +1623,281 @@ __global__ void __launch_bounds__(FAR_BLOCK) gs_icp_far_build_kernel(const FarBu
   }
 }
 
-extern "C" int64_t gs_localize_scratch_bytes(int H, int W, int ds, int64_t n_map_bound) {
-  if (H < 1 || W < 1 || ds < 1) return 0;
-  const int64_t n_lat = loc_lattice(H, W, ds);
-  return (int64_t)(gs_align(12 * (size_t)n_lat) + gs_align(4 * (size_t)(n_map_bound > 0 ? n_map_bound : 1)) + 256) +
-         gs_icp_scratch_bytes(n_lat, n_map_bound) + (int64_t)list_mem_bytes(n_lat) +
-         (int64_t)far_mem_bytes(n_lat);
-}
-
 static int64_t loc_rows(const gs_map_view& m) { return m.capacity > m.n_bound ? m.capacity : m.n_bound; }
 
-// scratch of one sequence: lattice | pix | n_valid | ICP scratch (which holds the grid)
-struct LocCarve {
-  float* lattice;
-  int32_t* pix;
-  int64_t* n_valid;
-  IcpScratch sc;
-  GridMem gm;
+// Scratch of one sequence of the batched localisation as byte offsets from its start: lattice | pix | n_valid | the solve's
+// scratch (IcpLayout sc, counted from `icp`; it holds the grid) | lists of ordinary queries (ListMem) | lists of far queries,
+// or the wide lists of hard ones (FarMem) + result words.  The ONE description of it: gs_localize_scratch_bytes returns its
+// total, loc_carve applies it to a base pointer.  `rows` is the map's CAPACITY (what the scratch was sized for), not the count
+// bound of a frame: every pointer then stays where it is from frame to frame while the map grows (the fast path keeps one
+// scratch per sequence and checks buffer identity), and the stats exporters, given the capacity, find what the solve left.
+struct LocLayout {
+  int64_t n_lat, rows;
+  IcpLayout sc;
+  size_t lattice, pix, n_valid, icp, lq, ls, lstat, far_c, far_cq, far_idx, far_n, far_out4, total;
 };
-static LocCarve loc_carve(const gs_localize_seq& q, int64_t n_lat) {
-  LocCarve c;
-  char* p = reinterpret_cast<char*>(q.scratch);
-  c.lattice = reinterpret_cast<float*>(p); p += gs_align(12 * (size_t)n_lat);
-  // the layout follows the map's CAPACITY (what the scratch was sized for), not the count bound of this frame: every
-  // pointer below then stays the same from frame to frame (the half-iteration launches are replayed as a graph)
-  const int64_t rows = loc_rows(q.map);
-  c.pix = reinterpret_cast<int32_t*>(p); p += gs_align(4 * (size_t)rows);
-  c.n_valid = reinterpret_cast<int64_t*>(p); p += 256;
-  c.sc = icp_carve(p, n_lat);
-  c.gm = grid_carve(c.sc.grid, n_lat, rows);
-  return c;
+static LocLayout loc_layout(int64_t n_lat, int64_t rows) {
+  GsTake take;
+  LocLayout L;
+  L.n_lat = n_lat; L.rows = rows > 0 ? rows : 1;
+  L.lattice = take(gs_align(12 * (size_t)n_lat));
+  L.pix = take(gs_align(4 * (size_t)L.rows));
+  L.n_valid = take(256);
+  L.sc = icp_layout(n_lat, L.rows);
+  L.icp = take(L.sc.total);
+  L.lq = take(gs_align(16 * (size_t)n_lat));
+  L.ls = take(gs_align(4 * GL_SLOTS * (size_t)n_lat));
+  L.lstat = take(gs_align(4 * 3 * GL_STAT_LAUNCHES));
+  L.far_c = take(gs_align(4 * GS_FAR_SLOTS * (size_t)n_lat));
+  L.far_cq = take(gs_align(16 * (size_t)n_lat));
+  L.far_idx = take(gs_align(4 * FS_FAR_PASSES * (size_t)n_lat));
+  L.far_n = take(256);   // the FS_FAR_PASSES counters and, behind them, the 4 result words of gs_localize_far_stats_i64
+  L.far_out4 = L.far_n + 4 * 8;
+  static_assert(FS_FAR_PASSES <= 8, "the far-list counters run into the result words");
+  L.total = take.end;
+  return L;
+}
+// The list variants sum the partial rows with UNCONDITIONAL loads, masked afterwards (icp_sum_col27_hook: row threadIdx.x
+// of every thread; icp_sum_rows_split: 24 x 18 rows): FS_BLOCK rows of LIN_NV doubles from the start of a row buffer
+// whatever the row count.  What follows the LAST row buffer in the scratch (the grid, the lists; rowred and the first
+// buffer have more behind them) must cover that, or the solve keeps no lists.
+static bool loc_lists_fit(const LocLayout& L) { return L.total - (L.icp + L.sc.partials[1]) >= sizeof(double) * LIN_NV * FS_BLOCK; }
+
+extern "C" int64_t gs_localize_scratch_bytes(int H, int W, int ds, int64_t n_map_bound) {
+  if (H < 1 || W < 1 || ds < 1) return 0;
+  return (int64_t)loc_layout(loc_lattice(H, W, ds), n_map_bound).total;
 }
 
-// The persistent solve puts a sequence's blocks on ONE XCD of PS_CUS_PER_XCD CUs (gs_icp_persist.h): only a whole gfx950
-// device qualifies (a partitioned one shows fewer CUs).  Asked once per device.
-static bool ps_device_fits() {
-  constexpr int MAX_DEV = 64;
-  static signed char fits[MAX_DEV] = {};   // 0: not asked yet, 1: yes, -1: no
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return false;
-  if (fits[dev] == 0) {
-    hipDeviceProp_t p;
-    const bool ok = hipGetDeviceProperties(&p, dev) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0 &&
-                    p.multiProcessorCount == (int)(GS_XCDS * PS_CUS_PER_XCD);
-    fits[dev] = ok ? 1 : -1;
+struct LocCarve {
+  float* lattice; int32_t* pix; int64_t* n_valid;
+  IcpScratch sc; GridMem gm; ListMem lm;
+  FarMem fm; int* far_out4;   // the far lists, or the wide lists whenever those are not in use; the stats result words
+};
+static LocCarve loc_carve(void* p, const LocLayout& L) {
+  const IcpScratch sc = icp_carve(gs_at<char>(p, L.icp), L.sc);
+  return LocCarve{gs_at<float>(p, L.lattice), gs_at<int32_t>(p, L.pix), gs_at<int64_t>(p, L.n_valid), sc,
+                  grid_carve(sc.grid, L.n_lat, L.rows),
+                  ListMem{gs_at<float4>(p, L.lq), gs_at<uint32_t>(p, L.ls), gs_at<int>(p, L.lstat)},
+                  FarMem{gs_at<uint32_t>(p, L.far_c), gs_at<float4>(p, L.far_cq), gs_at<int>(p, L.far_idx), gs_at<int>(p, L.far_n)},
+                  gs_at<int>(p, L.far_out4)};
+}
+// (the stats exporters and the one-call step: the scratch of a solve of HxW images at dsratio ds against map_rows rows)
+static LocCarve loc_carve_of(const void* scratch, int H, int W, int ds, int64_t map_rows) {
+  return loc_carve(const_cast<void*>(scratch), loc_layout(loc_lattice(H, W, ds), map_rows));
+}
+
+// Which engines a batched solve runs, decided ONCE, before its first launch (icp_engine_plan: no HIP call in there).
+struct IcpEnginePlan {
+  // candidate lists of far queries (opt-in; instead of the ordinary ones) / wide lists of hard queries, in the memory of the
+  // far lists / candidate lists of ordinary queries / the half-iterations from ps_it0 on as ONE launch (gs_icp_persist.h)
+  bool far_on, wide_on, lists_on, persist_on;
+  bool binned_normals;  // the matches' normals come from the binned copy, not from the map
+  bool reduce_rows;     // large solves: one extra launch per iteration adds the rows up once (FS_REDUCE_ROWS)
+  int lists_from;       // the lists are built behind the look-ahead search of this iteration, tried from the next on
+  IcpHalfPlan half;     // geometry of the half-iteration launches
+  int ps_it0, ps_nb, ps_upb;   // persistent launch: first iteration it serves (numiters: none), blocks per sequence, units per block
+  float weak_room;
+  // what a launch does with the ordinary lists (icp_half_body: LMODE): 0 nothing, 1 build 4-entry lists, 2 try them,
+  // 3 build the 8-entry lists the persistent kernel takes over (it keeps the four nearest of a list in registers and falls
+  // back on the other four, lane by lane, before anything is re-searched)
+  int lmode(int it, bool look_ahead) const {
+    if (!lists_on || it < lists_from) return 0;
+    if (it > lists_from) return 2;
+    return look_ahead ? (persist_on ? 3 : 1) : 0;
   }
-  return fits[dev] == 1;
+};
+static IcpEnginePlan icp_engine_plan(const GsEnv& env, const IcpDevice& dev, int B, int64_t n_lat, int numiters,
+                                     const LocLayout* layouts) {
+  IcpEnginePlan p;
+  const int64_t rows = (int64_t)icp_rows(n_lat);
+  p.binned_normals = env.icp_binned_normals; p.weak_room = env.icp_weak_room;
+  p.lists_from = env.icp_lists_from >= 0 ? env.icp_lists_from : FS_LISTS_FROM;
+  p.reduce_rows = rows > FS_REDUCE_ROWS;
+  p.far_on = env.icp_far && numiters > 0;
+  p.wide_on = env.icp_wide && !p.far_on && numiters > 0;
+  // The persistent solve: a sequence's source points must fit the 32 CUs of one XCD at 672 per block (640x480 at dsratio 4:
+  // 200 row units -> 29 blocks of 7, as few as the CUs allow, equally loaded), it reads the ordinary lists and the binned
+  // normals, and an iteration must be left for it behind the list-building look-ahead (the earliest start won: 4-entry lists
+  // and a start at 2 / 5 / 7 / 9 / 12 gave 7 924 / 7 857 / 7 872 / 7 816 / 7 763 frames/s against 7 623 without).
+  p.ps_upb = (int)gs_ceil_div(rows, PS_CUS_PER_XCD);
+  p.ps_nb = (int)gs_ceil_div(rows, p.ps_upb > 0 ? p.ps_upb : 1);
+  const bool persist_asked = env.icp_persist && env.icp_lists && !p.far_on && B <= (int)GS_XCDS && p.ps_upb <= PS_UPB &&
+                             numiters > p.lists_from + 1 && !env.icp_timeline && !env.icp_lanes_set && dev.ps_fits &&
+                             p.binned_normals;
+  // The launches in front of the persistent one run at 2 lanes per point (it reads the 4-entry lists two lanes write); far
+  // lists have no 8-lane variant.  QUIRK, kept: the cap of 2 follows what was ASKED for -- a solve whose persistent launch
+  // is ruled out below (no lists after all) still runs at 2 lanes.  Lifting it changes the speed of an opt-in path.
+  p.half = icp_half_plan(env, dev.cus, n_lat, B, p.far_on ? 4 : (persist_asked ? 2 : 8));
+  // (a block reads the lists of ONE group of row units: solves whose blocks walk several groups keep none)
+  p.lists_on = env.icp_lists && !p.far_on && p.half.upb * p.half.G * FS_QPB <= FS_BLOCK;
+  for (int b = 0; b < B && p.lists_on; ++b) p.lists_on = loc_lists_fit(layouts[b]);
+  p.persist_on = persist_asked && p.half.G == 2 && p.lists_on;
+  p.ps_it0 = p.persist_on ? p.lists_from + 1 : numiters;
+  return p;
+}
+
+// ---- the steps of a chunk: bind, prep + grid build, half-iterations, persistent launch, finish (c[b]: the carved scratch of sequence b)
+static void loc_bind(const gs_localize_seq* seqs, int B, int H, int W, int ds, const gs_icp_params* prm,
+                     const IcpEnginePlan& plan, LocCarve* c, LocBatch& lb, GsGridBatch& gb) {
+  lb.B = gb.B = B; lb.W = gb.W = W; gb.H = H; lb.ds = gb.ds = ds;
+  lb.Wl = (W + ds - 1) / ds; lb.n_lat = loc_lattice(H, W, ds); lb.damp = prm->damp; lb.numiters = prm->numiters;
+  gb.cells_cap = gs_knn_grid_cells_cap(lb.n_lat);
+  for (int b = 0; b < B; ++b) {
+    const gs_localize_seq& q = seqs[b];
+    if (!plan.binned_normals) c[b].gm.sorted_n = nullptr;
+    // (the prep launch zeroes the counters of the far and of the ordinary lists whether or not this solve keeps such lists)
+    lb.s[b] = LocSeq{q.vertex, q.depth, q.prev_pose16, c[b].lattice, c[b].sc.state, q.out_pose16,
+                     reinterpret_cast<char*>(c[b].gm.g), c[b].n_valid, c[b].fm.n, c[b].lm.stat,
+                     plan.wide_on ? c[b].fm.cq : nullptr, c[b].sc.sync};
+    gb.s[b] = GsGridSeq{q.map.points, GsCount{q.map.n_bound, q.map.n_dev}, c[b].pix, q.prev_pose16, q.K16,
+                        plan.binned_normals ? q.map.normals : nullptr, c[b].gm};
+  }
+  lb.count_valid = g_gs_prof_on ? 1 : 0;
+  lb.clear_bytes = gs_knn_grid_clear_bytes(c[0].gm, gb.cells_cap);  // same layout offsets for every sequence
 }
 
 // grid_cleared: the caller has zeroed the first gs_knn_grid_clear_bytes() bytes of every sequence's grid scratch
 // (loc_carve().gm.g) on the stream already
-static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int ds, const gs_icp_params* prm,
-                          hipStream_t st, bool grid_cleared) {
-  const int64_t n_lat = loc_lattice(H, W, ds);
-  const int Wl = (W + ds - 1) / ds;
-  LocBatch lb;
-  GsGridBatch gb;
-  IcpScratch sc[GS_MAX_BATCH];
-  GridMem gm[GS_MAX_BATCH];
-  lb.B = gb.B = B;
-  lb.W = gb.W = W; gb.H = H;
-  lb.ds = gb.ds = ds;
-  lb.Wl = Wl; lb.n_lat = n_lat; lb.damp = prm->damp; lb.numiters = prm->numiters;
-  gb.cells_cap = gs_knn_grid_cells_cap(n_lat);
-  for (int b = 0; b < B; ++b) {
-    const gs_localize_seq& q = seqs[b];
-    const LocCarve cv = loc_carve(q, n_lat);
-    float* lattice = cv.lattice;
-    int32_t* pix = cv.pix;
-    int64_t* n_valid = cv.n_valid;
-    sc[b] = cv.sc;
-    gm[b] = cv.gm;
-    lb.s[b] = LocSeq{q.vertex, q.depth, q.prev_pose16, lattice, sc[b].state, q.out_pose16,
-                     reinterpret_cast<char*>(gm[b].g), n_valid, nullptr, nullptr, nullptr,
-                     reinterpret_cast<unsigned*>(sc[b].rowred + LIN_NV)};   // (behind the one row of large solves)
-    static int binned_normals = -1;  // GRADSLAM_HIP_ICP_BINNED_NORMALS=0: gather the matches' normals from the map (A/B)
-    if (binned_normals < 0) {
-      const char* e = getenv("GRADSLAM_HIP_ICP_BINNED_NORMALS");
-      binned_normals = (e && atoi(e) == 0) ? 0 : 1;
-    }
-    if (!binned_normals) gm[b].sorted_n = nullptr;
-    gb.s[b] = GsGridSeq{q.map.points, GsCount{q.map.n_bound, q.map.n_dev}, pix, q.prev_pose16, q.K16,
-                        binned_normals ? q.map.normals : nullptr, gm[b]};
-    if (g_gs_prof_on) GS_HIP(hipMemsetAsync(n_valid, 0, 8, st));
-  }
-  // candidate lists of far queries (gs_knn.h; the results do not depend on them), behind the ordinary lists in the scratch.
-  // Policy: round 3 built them for 1296x968 (78k source points, clusters of far ones at the frame borders: +4 % frames/s
-  // over 200 frames), where they REPLACED the ordinary lists (the two do not fit one kernel).  Round 5: the wide lists of
-  // hard queries (below) give those points lists inside the variants with ordinary lists, and ordinary + wide lists beat the
-  // far lists at 1296x968 by 18 % (780 vs 662 frames/s over 150 frames, same poses: profiles/r05_c5_far_vs_wide.txt) --
-  // so the far lists are opt-in now: GRADSLAM_HIP_ICP_FAR=1.
-  static int far_lists = -1;
-  if (far_lists < 0) {
-    const char* e = getenv("GRADSLAM_HIP_ICP_FAR");
-    far_lists = (e && atoi(e) != 0) ? 1 : 0;
-  }
-  const bool far_on = far_lists == 1 && prm->numiters > 0;
-  FarMem fm[GS_MAX_BATCH];
-  for (int b = 0; b < B; ++b) {
-    fm[b] = far_carve(reinterpret_cast<char*>(sc[b].state) + gs_icp_scratch_bytes(n_lat, loc_rows(seqs[b].map)) +
-                          list_mem_bytes(n_lat), n_lat);
-    lb.s[b].far_n = fm[b].n;   // (zeroed by the prep launch whether or not this solve keeps lists: gs_localize_far_stats_i64)
-    if (!far_on) fm[b] = FarMem{nullptr, nullptr, nullptr, nullptr};
-  }
-  // candidate lists of ordinary queries (gs_knn.h: gl_*; the results do not depend on them): every solve that keeps no
-  // far lists.  GRADSLAM_HIP_ICP_LISTS=0 switches them off (A/B runs).
-  // GRADSLAM_HIP_ICP_LISTS_FROM=k: the lists are built behind the look-ahead search of iteration k and tried from
-  // iteration k + 1 on.  Default FS_LISTS_FROM = 1: the step of iteration 0 is the large one of a solve (millimetres);
-  // a list built before it would not survive it.  Later starts were measured too: 0 / 1 / 4 / 8 give
-  // 7.40 / 7.42 / 7.42 / 7.31 k frames/s at 8 sequences per GPU.
-  static int ord_lists = -1, lists_from = FS_LISTS_FROM;
-  if (ord_lists < 0) {
-    const char* e = getenv("GRADSLAM_HIP_ICP_LISTS");
-    ord_lists = (e && atoi(e) == 0) ? 0 : 1;
-    const char* f = getenv("GRADSLAM_HIP_ICP_LISTS_FROM");
-    if (f && atoi(f) >= 0) lists_from = atoi(f);
-  }
-  ListMem lm[GS_MAX_BATCH];
-  for (int b = 0; b < B; ++b) {
-    lm[b] = list_carve(reinterpret_cast<char*>(sc[b].state) + gs_icp_scratch_bytes(n_lat, loc_rows(seqs[b].map)), n_lat);
-    lb.s[b].lstat = lm[b].stat;   // (zeroed by the prep launch whether or not this solve keeps lists)
-  }
-  // wide lists of hard queries (gs_knn.h; the results do not depend on them): in the memory of the far lists, whenever
-  // those are not in use.  GRADSLAM_HIP_ICP_WIDE=0 switches them off (A/B runs).
-  static int wide_lists = -1;
-  if (wide_lists < 0) {
-    const char* e = getenv("GRADSLAM_HIP_ICP_WIDE");
-    wide_lists = (e && atoi(e) == 0) ? 0 : 1;
-  }
-  const bool wide_on = wide_lists == 1 && !far_on && prm->numiters > 0;
-  FarMem wm[GS_MAX_BATCH];
-  for (int b = 0; b < B; ++b) {
-    wm[b] = far_carve(reinterpret_cast<char*>(sc[b].state) + gs_icp_scratch_bytes(n_lat, loc_rows(seqs[b].map)) +
-                          list_mem_bytes(n_lat), n_lat);
-    lb.s[b].wl_cq = wide_on ? wm[b].cq : nullptr;
-  }
-  lb.count_valid = g_gs_prof_on ? 1 : 0;
-  lb.clear_bytes = gs_knn_grid_clear_bytes(gm[0], gb.cells_cap);  // same layout offsets for every sequence
-  const unsigned nb_lat = (unsigned)gs_ceil_div(n_lat, 256);
+static int loc_prep(const gs_localize_seq* seqs, const LocBatch& lb, const GsGridBatch& gb, hipStream_t st, bool grid_cleared) {
+  const int B = lb.B;
+  if (g_gs_prof_on)
+    for (int b = 0; b < B; ++b) GS_HIP(hipMemsetAsync(lb.s[b].n_valid, 0, 8, st));
+  const unsigned nb_lat = (unsigned)gs_ceil_div(lb.n_lat, 256);
   const unsigned nb_clear = (unsigned)gs_ceil_div((int64_t)(lb.clear_bytes / 16), 256 * LP_CLEAR_ITEMS);
-  {
-    double bytes = 0.0;  // lattice 28 B per slot; projection 16 B + two filter passes 4 B per map row; cell table
-    for (int b = 0; b < B; ++b) bytes += 28.0 * n_lat + 24.0 * seqs[b].map.n_bound + 16.0 * gb.cells_cap;
-    GsProf prof(GS_PROF_COMPACT, bytes, st, grid_cleared ? 4 : 5);
-    int rc;
-    if (grid_cleared) {
-      const float u_hi = (float)((double)W - 0.999), v_hi = (float)((double)H - 0.999);   // (as gs_knn_grid_build_batch)
-      hipLaunchKernelGGL(gs_loc_prep_bbox_kernel, dim3((unsigned)B * nb_lat + gs_knn_gridb_bbox_blocks(gb)), dim3(256), 0, st,
-                         lb, gb, nb_lat, u_hi, v_hi);
-      rc = gs_knn_grid_build_batch(gb, st, true);
-    } else {
-      hipLaunchKernelGGL(gs_loc_prep_kernel, dim3((unsigned)B * (nb_lat + nb_clear)), dim3(256), 0, st, lb, nb_lat);
-      rc = gs_knn_grid_build_batch(gb, st);
-    }
-    if (rc != GS_OK) return rc;
+  double bytes = 0.0;  // lattice 28 B per slot; projection 16 B + two filter passes 4 B per map row; cell table
+  for (int b = 0; b < B; ++b) bytes += 28.0 * lb.n_lat + 24.0 * seqs[b].map.n_bound + 16.0 * gb.cells_cap;
+  GsProf prof(GS_PROF_COMPACT, bytes, st, grid_cleared ? 4 : 5);
+  if (grid_cleared) {
+    const float u_hi = (float)((double)gb.W - 0.999), v_hi = (float)((double)gb.H - 0.999);   // (as gs_knn_grid_build_batch)
+    hipLaunchKernelGGL(gs_loc_prep_bbox_kernel, dim3((unsigned)B * nb_lat + gs_knn_gridb_bbox_blocks(gb)), dim3(256), 0, st,
+                       lb, gb, nb_lat, u_hi, v_hi);
+    return gs_knn_grid_build_batch(gb, st, true);
   }
-  if (prm->numiters == 0) { GS_LAUNCH_CHECK(); return GS_OK; }
+  hipLaunchKernelGGL(gs_loc_prep_kernel, dim3((unsigned)B * (nb_lat + nb_clear)), dim3(256), 0, st, lb, nb_lat);
+  return gs_knn_grid_build_batch(gb, st);
+}
 
-  const int nfs = (int)icp_rows(n_lat);
-  const bool reduce_rows = nfs > FS_REDUCE_ROWS;
+// profile passes only (one sync per sequence): exact counts for the roofline line
+static int loc_prof_bytes(int B, const LocCarve* c, int64_t n_lat, int numiters, hipStream_t st, double* bytes) {
+  for (int b = 0; b < B; ++b) {
+    unsigned hits = 0; int64_t nv = 0;
+    GS_HIP(hipMemcpyAsync(&hits, c[b].gm.bbox + 6, 4, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipMemcpyAsync(&nv, c[b].n_valid, 8, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    *bytes += icp_alg_bytes(numiters, n_lat, nv, hits);
+  }
+  return GS_OK;
+}
+
+// iterations [0, plan.ps_it0): two launches each (+ the far-list builder, + the row sums of large solves); half-iteration
+// h reads state s[h & 1] and the rows partials[(h + 1) & 1], writes the others
+static void loc_half_iterations(const gs_localize_seq* seqs, int B, const IcpEnginePlan& plan, const LocCarve* c,
+                                int64_t n_lat, const gs_icp_params* prm, hipStream_t st) {
   const GsCount n_src_c{n_lat, nullptr};
-  double prof_bytes = 0.0;
-  if (g_gs_prof_on) {  // exact counts for the roofline line (profile passes only: one sync)
-    for (int b = 0; b < B; ++b) {
-      unsigned hits = 0;
-      int64_t nv = 0;
-      GS_HIP(hipMemcpyAsync(&hits, gm[b].bbox + 6, 4, hipMemcpyDeviceToHost, st));
-      GS_HIP(hipMemcpyAsync(&nv, lb.s[b].n_valid, 8, hipMemcpyDeviceToHost, st));
-      GS_HIP(hipStreamSynchronize(st));
-      prof_bytes += icp_alg_bytes(prm->numiters, n_lat, nv, hits);
-    }
-  }
-  std::unique_ptr<GsProf> prof_loop(new GsProf(GS_PROF_ICP_FUSED, prof_bytes, st, 2 * prm->numiters));
-  // The list-checking half-iterations as ONE persistent launch per XCD-resident sequence (gs_icp_persist.h) whenever a
-  // sequence's source points fit the 32 CUs of one XCD at 672 per block (640x480 at dsratio 4: 29 blocks); the launches in
-  // front of it then run at 2 lanes per point (the persistent kernel reads the 4-entry lists two lanes write).
-  // OPT-IN (GRADSLAM_HIP_ICP_PERSIST=1; the results do not depend on it: tests/test_hip_batch.py::
-  // test_persistent_xcd_solve_leaves_results_identical).  Measured, round 6 (profiles/r06_xcd_persistent_*): its steady-state
-  // half-iteration takes 6.5 - 7.6 us against 10.5 - 12.5 us per launch, but a half-iteration in which any list of a block
-  // fails costs ~27 us (re-search 9 + cubes 5 + new lists 3 on top), solves that still move lose lists in every look-ahead,
-  // and the launches in front of it run at 2 lanes per point: +3.9 / +3.2 / +7.8 % at 8 / 4 / 2 sequences per GPU over the
-  // 20-step window, -1.2 % over the 200-step window, -2 ... -6 % for a lone sequence (profiles/r06_xcd_persistent_ab_bench.json).
-  // Its liveness also rests on the dispatcher placing at least 29 of the launch's blocks on every XCD (every wait is
-  // bounded: a NaN pose, not a hang).  The launch-per-half-iteration path stays the default.
-  static int persist_env = -1;
-  if (persist_env < 0) {
-    const char* e = getenv("GRADSLAM_HIP_ICP_PERSIST");
-    persist_env = (e && atoi(e) == 1) ? 1 : 0;
-  }
-  // (as few blocks as the XCD's CUs allow, equally loaded: 200 row units -> 29 blocks of 7)
-  const int ps_upb = (int)gs_ceil_div((int64_t)icp_rows(n_lat), PS_CUS_PER_XCD);
-  const int ps_nb = (int)gs_ceil_div((int64_t)icp_rows(n_lat), ps_upb > 0 ? ps_upb : 1);
-  bool persist_on = persist_env == 1 && ord_lists == 1 && !far_on && B <= (int)GS_XCDS && ps_upb <= PS_UPB &&
-                    prm->numiters > lists_from + 1 && !getenv("GRADSLAM_HIP_ICP_TIMELINE") &&
-                    !getenv("GRADSLAM_HIP_ICP_LANES") && ps_device_fits();
-  for (int b = 0; b < B && persist_on; ++b) persist_on = gm[b].sorted_n != nullptr;
-  const IcpHalfPlan plan = icp_half_plan(n_lat, B, far_on ? 4 : (persist_on ? 2 : 8));
-  // (a block reads the lists of ONE group of row units: solves whose blocks walk several groups keep none)
-  bool lists_on = ord_lists == 1 && !far_on && plan.upb * plan.G * FS_QPB <= FS_BLOCK;
-  if (plan.G != 2) persist_on = false;
-  // The list variants sum the partial rows with UNCONDITIONAL loads, masked afterwards (icp_sum_col27_hook: row
-  // threadIdx.x of every thread; icp_sum_rows_split: 24 x 18 rows): up to FS_BLOCK rows of LIN_NV doubles from the start
-  // of a row buffer whatever the row count.  What follows the buffers in the scratch (the grid, the lists) must cover
-  // that, or the solve keeps no lists (nothing else enforces the layout).
-  for (int b = 0; b < B && lists_on; ++b) {
-    const char* end = reinterpret_cast<const char*>(seqs[b].scratch) + gs_localize_scratch_bytes(H, W, ds, loc_rows(seqs[b].map));
-    const char* first = reinterpret_cast<const char*>(reduce_rows ? sc[b].rowred : sc[b].partials[1]);
-    if (reinterpret_cast<const char*>(sc[b].partials[0]) > first) first = reinterpret_cast<const char*>(sc[b].partials[0]);
-    if (reinterpret_cast<const char*>(sc[b].partials[1]) > first) first = reinterpret_cast<const char*>(sc[b].partials[1]);
-    if (end - first < (ptrdiff_t)(sizeof(double) * LIN_NV * FS_BLOCK)) lists_on = false;
-  }
+  const FarMem no_far{nullptr, nullptr, nullptr, nullptr};
   IcpHalfBatch hb;
-  hb.B = B;
-  // GRADSLAM_HIP_ICP_WEAK_ROOM=<cells> (0: off): see the list-building branch of icp_half_body
-  static float weak_room = -1.0f;
-  if (weak_room < 0.0f) {
-    const char* e = getenv("GRADSLAM_HIP_ICP_WEAK_ROOM");
-    weak_room = e ? (float)atof(e) : 0.0f;
-    if (!(weak_room >= 0.0f && weak_room < 1.0f)) weak_room = 0.0f;
-  }
-  hb.weak_room = weak_room;
-  int h = 0;
-  if (!lists_on) persist_on = false;
-  // The persistent launch takes over behind the list-building look-ahead, which then leaves 8-entry lists (LMODE 3): the
-  // persistent kernel keeps the four nearest of a list in registers and falls back on the other four, lane by lane, before
-  // anything is re-searched (gs_icp_persist.h).  (Measured with 4-entry lists and a later start, GRADSLAM_HIP_ICP_PERSIST_FROM
-  // = 2 / 5 / 7 / 9 / 12: 7 924 / 7 857 / 7 872 / 7 816 / 7 763 frames/s against 7 623 without -- the earliest start won.)
-  int ps_it0 = prm->numiters, ps_h0 = 0;
-  if (persist_on) {
-    ps_it0 = lists_from + 1;
-    if (ps_it0 >= prm->numiters) { persist_on = false; ps_it0 = prm->numiters; }
-  }
-  for (int it = 0; it < ps_it0; ++it) {
+  hb.B = B; hb.weak_room = plan.weak_room;
+  for (int it = 0; it < plan.ps_it0; ++it) {
+    int h = 2 * it;
     for (int b = 0; b < B; ++b) {
       const gs_localize_seq& q = seqs[b];
-      const float* cur_in = it == 0 ? lb.s[b].lattice : (((it - 1) & 1) ? sc[b].srcB : sc[b].srcA);
-      float* cur = (it & 1) ? sc[b].srcB : sc[b].srcA;
-      hb.s[b] = IcpHalfSeq{cur_in, cur, q.map.points, q.map.normals, GsCount{q.map.n_bound, q.map.n_dev}, gm[b].g,
-                           gm[b].cell_start, gm[b].sorted, gm[b].sorted_n, reinterpret_cast<float*>(sc[b].best),
-                           sc[b].partials[(h + 1) & 1], sc[b].partials[h & 1],
-                           &sc[b].state->s[h & 1], &sc[b].state->s[(h + 1) & 1], sc[b].state->trace, nullptr, nullptr,
-                           nullptr, fm[b].cq, fm[b].c, fm[b].idx, fm[b].n};
-      hb.w[b] = wide_on ? IcpHalfWide{wm[b].cq, wm[b].c} : IcpHalfWide{nullptr, nullptr};
-      hb.l[b] = lists_on ? IcpHalfLists{lm[b].lq, lm[b].ls, lm[b].stat, lb.s[b].sync + PS_WEAK}
-                         : IcpHalfLists{nullptr, nullptr, nullptr, nullptr};
+      const IcpScratch& sc = c[b].sc; const GridMem& gm = c[b].gm;
+      const FarMem& fm = plan.far_on ? c[b].fm : no_far;
+      const float* cur_in = it == 0 ? c[b].lattice : (((it - 1) & 1) ? sc.srcB : sc.srcA);
+      float* cur = (it & 1) ? sc.srcB : sc.srcA;
+      hb.s[b] = IcpHalfSeq{cur_in, cur, q.map.points, q.map.normals, GsCount{q.map.n_bound, q.map.n_dev}, gm.g,
+                           gm.cell_start, gm.sorted, gm.sorted_n, reinterpret_cast<float*>(sc.best),
+                           sc.partials[(h + 1) & 1], sc.partials[h & 1], &sc.state->s[h & 1], &sc.state->s[(h + 1) & 1],
+                           sc.state->trace, nullptr, nullptr, nullptr, fm.cq, fm.c, fm.idx, fm.n};
+      hb.w[b] = plan.wide_on ? IcpHalfWide{c[b].fm.cq, c[b].fm.c} : IcpHalfWide{nullptr, nullptr};
+      hb.l[b] = plan.lists_on ? IcpHalfLists{c[b].lm.lq, c[b].lm.ls, c[b].lm.stat, sc.sync + PS_WEAK}
+                              : IcpHalfLists{nullptr, nullptr, nullptr, nullptr};
     }
-    // lists: built behind the look-ahead search of iteration lists_from, tried from then on
-    icp_half_launch<true>(plan, hb, n_src_c, prm, it, 0, st, lists_on && it > lists_from ? 2 : 0);
-    if (far_on && fs_far_pass(it) >= 0) {   // lists for the far source points this search found
+    icp_half_launch<true>(plan.half, hb, n_src_c, prm, it, 0, st, plan.lmode(it, false));
+    if (plan.far_on && fs_far_pass(it) >= 0) {   // lists for the far source points this search found
       const int fp = fs_far_pass(it);
-      FarBuildBatch fbb;
-      fbb.B = B;
+      FarBuildBatch fbb; fbb.B = B;
       for (int b = 0; b < B; ++b)
-        fbb.s[b] = FarBuildSeq{(it & 1) ? sc[b].srcB : sc[b].srcA, fm[b].idx + (int64_t)fp * n_lat, fm[b].n + fp, gm[b].g,
-                               gm[b].cell_start, gm[b].sorted, reinterpret_cast<float*>(sc[b].best), fm[b]};
+        fbb.s[b] = FarBuildSeq{(it & 1) ? c[b].sc.srcB : c[b].sc.srcA, c[b].fm.idx + (int64_t)fp * n_lat, c[b].fm.n + fp,
+                               c[b].gm.g, c[b].gm.cell_start, c[b].gm.sorted, reinterpret_cast<float*>(c[b].sc.best), c[b].fm};
       hipLaunchKernelGGL(gs_icp_far_build_kernel, dim3((unsigned)B * FAR_BLOCKS_PER_SEQ), dim3(FAR_BLOCK), 0, st, fbb);
     }
     ++h;
-    if (reduce_rows) {
-      IcpRowsBatch rb;
-      rb.B = B;
-      for (int b = 0; b < B; ++b) { rb.in[b] = sc[b].partials[(h + 1) & 1]; rb.out[b] = sc[b].rowred; }
+    if (plan.reduce_rows) {
+      IcpRowsBatch rb; rb.B = B;
+      for (int b = 0; b < B; ++b) { rb.in[b] = c[b].sc.partials[(h + 1) & 1]; rb.out[b] = c[b].sc.rowred; }
       hipLaunchKernelGGL(gs_icp_reduce_rows_batch_kernel, dim3((unsigned)B), dim3(FS_BLOCK), 0, st, rb, n_src_c);
     }
     for (int b = 0; b < B; ++b) {
+      const IcpScratch& sc = c[b].sc;
       IcpHalfSeq& u = hb.s[b];
-      u.src_in = (it & 1) ? sc[b].srcB : sc[b].srcA;
-      u.src_out = nullptr;
-      u.partials_in = reduce_rows ? sc[b].rowred : sc[b].partials[(h + 1) & 1];
-      u.partials_out = sc[b].partials[h & 1];
-      u.st_in = &sc[b].state->s[h & 1];
-      u.st_out = &sc[b].state->s[(h + 1) & 1];
+      u.src_in = (it & 1) ? sc.srcB : sc.srcA; u.src_out = nullptr;
+      u.partials_in = plan.reduce_rows ? sc.rowred : sc.partials[(h + 1) & 1];
+      u.partials_out = sc.partials[h & 1];
+      u.st_in = &sc.state->s[h & 1]; u.st_out = &sc.state->s[(h + 1) & 1];
     }
-    icp_half_launch<false>(plan, hb, n_src_c, prm, it, reduce_rows ? 1 : 0, st,
-                           lists_on ? (it == lists_from ? (persist_on ? 3 : 1) : (it > lists_from ? 2 : 0)) : 0);
-    ++h;
+    icp_half_launch<false>(plan.half, hb, n_src_c, prm, it, plan.reduce_rows ? 1 : 0, st, plan.lmode(it, true));
   }
-  if (persist_on) {
-    IcpPersistBatch pb;
-    pb.B = B;
-    pb.nb = ps_nb;
-    pb.upb = ps_upb;
-    pb.h0 = ps_h0 = h;
-    pb.tl_h = 0;
-    pb.timeline = nullptr;
-    for (int b = 0; b < B; ++b) {
-      const gs_localize_seq& q = seqs[b];
-      pb.s[b] = IcpPersistSeq{((ps_it0 - 1) & 1) ? sc[b].srcB : sc[b].srcA, GsCount{q.map.n_bound, q.map.n_dev}, gm[b].g, gm[b].cell_start,
-                              gm[b].sorted, gm[b].sorted_n, {sc[b].partials[0], sc[b].partials[1]}, sc[b].state, lm[b].lq, lm[b].ls,
-                              lm[b].stat, wide_on ? wm[b].cq : nullptr, wide_on ? wm[b].c : nullptr, lb.s[b].sync};
-    }
-#ifdef GS_ICP_TIMELINE
-    // debugging aid (library built with -DGS_ICP_TIMELINE; GRADSLAM_HIP_ICP_PERSIST_TIMELINE=<path>): per block, the phase
-    // stamps of the LAST iteration's two half-iterations (tools/icp_persist_timeline.py)
-    static const char* ptl_path = getenv("GRADSLAM_HIP_ICP_PERSIST_TIMELINE");
-    static unsigned long long* ptl_buf = nullptr;
-    constexpr size_t PTL_WORDS = 72 * (size_t)GS_XCDS * PS_CUS_PER_XCD;
-    if (ptl_path) {
-      if (!ptl_buf && hipMalloc(&ptl_buf, 8 * PTL_WORDS) != hipSuccess) ptl_buf = nullptr;
-      if (ptl_buf) {
-        (void)hipMemsetAsync(ptl_buf, 0, 8 * PTL_WORDS, st);
-        pb.timeline = ptl_buf;
-        static const char* tl_it_env = getenv("GRADSLAM_HIP_ICP_TIMELINE_IT");
-        pb.tl_h = 2 * (tl_it_env ? atoi(tl_it_env) : prm->numiters - 1);
-      }
-    }
-#endif
-    hipLaunchKernelGGL(gs_icp_persist_kernel, dim3(GS_XCDS * PS_CUS_PER_XCD), dim3(PS_BLOCK), 0, st, pb, n_lat, prm->dist_thresh,
-                       *prm);
-#ifdef GS_ICP_TIMELINE
-    if (pb.timeline) {
-      std::unique_ptr<unsigned long long[]> hbuf(new unsigned long long[PTL_WORDS]);
-      if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(hbuf.get(), ptl_buf, 8 * PTL_WORDS, hipMemcpyDeviceToHost) == hipSuccess) {
-        FILE* f = fopen(ptl_path, "w");
-        if (f) {
-          fprintf(f, "# B=%d nb=%d upb=%d h0=%d tl_h=%d: per block: xcc lb end | first half: wait_done sums scalar check rare arrived at_barrier research hard brute - - | look-ahead: the same | start releases... (100 MHz ticks)\n",
-                  B, pb.nb, pb.upb, pb.h0, pb.tl_h);
-          for (size_t i = 0; i < PTL_WORDS / 72; ++i) {
-            const unsigned long long* r = hbuf.get() + 72 * i;
-            if (!r[0]) continue;
-            fprintf(f, "%llu %llu %llu |", r[1], r[2], r[3]);
-            for (int k = 8; k < 32; ++k) fprintf(f, " %llu%s", r[k], k == 19 ? " |" : "");
-            fprintf(f, " | %llu", r[4]);   // block start, then the release time of every half-iteration, then the end
-            for (int k = 32; k < 72; ++k) fprintf(f, " %llu", r[k]);
-            fprintf(f, "\n");
-          }
-          fclose(f);
-        }
-      }
-    }
-#endif
-    h = 2 * prm->numiters;
+}
+
+// iterations [plan.ps_it0, numiters) as ONE launch: it takes over behind the list-building look-ahead (LMODE 3)
+static void loc_persist(const gs_localize_seq* seqs, int B, const IcpEnginePlan& plan, const LocCarve* c, int64_t n_lat,
+                        const gs_icp_params* prm, hipStream_t st) {
+  IcpPersistBatch pb;
+  pb.B = B; pb.nb = plan.ps_nb; pb.upb = plan.ps_upb; pb.h0 = 2 * plan.ps_it0; pb.tl_h = 0; pb.timeline = nullptr;
+  for (int b = 0; b < B; ++b) {
+    const gs_localize_seq& q = seqs[b];
+    const IcpScratch& sc = c[b].sc; const GridMem& gm = c[b].gm;
+    pb.s[b] = IcpPersistSeq{((plan.ps_it0 - 1) & 1) ? sc.srcB : sc.srcA, GsCount{q.map.n_bound, q.map.n_dev}, gm.g, gm.cell_start,
+                            gm.sorted, gm.sorted_n, {sc.partials[0], sc.partials[1]}, sc.state, c[b].lm.lq, c[b].lm.ls,
+                            c[b].lm.stat, plan.wide_on ? c[b].fm.cq : nullptr, plan.wide_on ? c[b].fm.c : nullptr, sc.sync};
   }
-  prof_loop.reset();
+#ifdef GS_ICP_TIMELINE
+  ps_tl_arm(pb, prm->numiters, st);
+#endif
+  hipLaunchKernelGGL(gs_icp_persist_kernel, dim3(GS_XCDS * PS_CUS_PER_XCD), dim3(PS_BLOCK), 0, st, pb, n_lat, prm->dist_thresh, *prm);
+#ifdef GS_ICP_TIMELINE
+  ps_tl_dump(pb, st);
+#endif
+}
+
+// final LM / gradLM update and the composed pose; a persistent solve that did not run completely leaves a NaN pose
+static void loc_finish(const gs_localize_seq* seqs, int B, const IcpEnginePlan& plan, const LocCarve* c, int64_t n_lat,
+                       const gs_icp_params* prm, hipStream_t st) {
+  const int h = 2 * prm->numiters;
+  GsProf prof(GS_PROF_SOLVE, 1.0, st);
+  IcpFinishBatch fb;
+  fb.B = B; fb.nb = plan.persist_on ? plan.ps_nb : 0; fb.h0 = plan.persist_on ? 2 * plan.ps_it0 : 0;
+  for (int b = 0; b < B; ++b) {
+    fb.partials_in[b] = c[b].sc.partials[(h + 1) & 1];
+    fb.st[b] = c[b].sc.state; fb.compose16[b] = seqs[b].prev_pose16; fb.out_T16[b] = seqs[b].out_pose16;
+    fb.sync[b] = plan.persist_on ? c[b].sc.sync : nullptr;
+  }
+  hipLaunchKernelGGL(gs_icp_finish_batch_kernel, dim3((unsigned)B), dim3(FS_BLOCK), 0, st, fb, GsCount{n_lat, nullptr}, h & 1, *prm);
+}
+
+static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int ds, const gs_icp_params* prm,
+                          hipStream_t st, bool grid_cleared) {
+  const int64_t n_lat = loc_lattice(H, W, ds);
+  LocLayout layouts[GS_MAX_BATCH]; LocCarve c[GS_MAX_BATCH];
+  for (int b = 0; b < B; ++b) {
+    layouts[b] = loc_layout(n_lat, loc_rows(seqs[b].map));
+    c[b] = loc_carve(seqs[b].scratch, layouts[b]);
+  }
+  const IcpEnginePlan plan = icp_engine_plan(gs_env(), icp_device(), B, n_lat, prm->numiters, layouts);
+  LocBatch lb; GsGridBatch gb;
+  loc_bind(seqs, B, H, W, ds, prm, plan, c, lb, gb);
+  int rc = loc_prep(seqs, lb, gb, st, grid_cleared);
+  if (rc != GS_OK) return rc;
+  if (prm->numiters == 0) { GS_LAUNCH_CHECK(); return GS_OK; }
+  double prof_bytes = 0.0;
+  if (g_gs_prof_on && (rc = loc_prof_bytes(B, c, n_lat, prm->numiters, st, &prof_bytes)) != GS_OK) return rc;
   {
-    GsProf prof(GS_PROF_SOLVE, 1.0, st);
-    IcpFinishBatch fb;
-    fb.B = B;
-    fb.nb = persist_on ? ps_nb : 0;
-    fb.h0 = persist_on ? ps_h0 : 0;
-    for (int b = 0; b < B; ++b) {
-      fb.partials_in[b] = sc[b].partials[(h + 1) & 1];
-      fb.st[b] = sc[b].state;
-      fb.compose16[b] = seqs[b].prev_pose16;
-      fb.out_T16[b] = seqs[b].out_pose16;
-      fb.sync[b] = persist_on ? lb.s[b].sync : nullptr;
-    }
-    hipLaunchKernelGGL(gs_icp_finish_batch_kernel, dim3((unsigned)B), dim3(FS_BLOCK), 0, st, fb, n_src_c, h & 1, *prm);
+    GsProf prof(GS_PROF_ICP_FUSED, prof_bytes, st, 2 * prm->numiters);
+    loc_half_iterations(seqs, B, plan, c, n_lat, prm, st);
+    if (plan.persist_on) loc_persist(seqs, B, plan, c, n_lat, prm, st);
   }
+  loc_finish(seqs, B, plan, c, n_lat, prm, st);
   GS_LAUNCH_CHECK();
   return GS_OK;
 }
@@ -2083,16 +1948,9 @@ extern "C" int gs_localize_far_stats_i64(const void* scratch, int H, int W, int 
                                          void* stream) {
   GS_REQUIRE(scratch && out4_host && H > 0 && W > 0 && ds > 0 && map_rows > 0, "bad arguments");
   const int64_t n_lat = loc_lattice(H, W, ds);
-  gs_localize_seq q;
-  memset(&q, 0, sizeof(q));
-  q.scratch = const_cast<void*>(scratch);
-  q.map.capacity = map_rows; q.map.n_bound = map_rows;
-  const LocCarve cv = loc_carve(q, n_lat);
-  const FarMem fm = far_carve(reinterpret_cast<char*>(cv.sc.state) + gs_icp_scratch_bytes(n_lat, map_rows) +
-                                  list_mem_bytes(n_lat), n_lat);
-  hipStream_t st = gs_stream(stream);
-  // (the result words live behind the counters, in the 256 bytes reserved for them)
-  int* out4 = fm.n + 8;
+  const LocCarve cv = loc_carve_of(scratch, H, W, ds, map_rows);
+  const FarMem& fm = cv.fm; hipStream_t st = gs_stream(stream);
+  int* out4 = cv.far_out4;   // (behind the counters, in the 256 bytes reserved for them)
   GS_HIP(hipMemsetAsync(out4, 0, 16, st));
   hipLaunchKernelGGL(gs_far_stats_kernel, dim3(64), dim3(256), 0, st, fm.idx, fm.n, reinterpret_cast<const float*>(cv.sc.best),
                      fm.cq, n_lat, out4);
@@ -2102,7 +1960,7 @@ extern "C" int gs_localize_far_stats_i64(const void* scratch, int H, int W, int 
   GS_HIP(hipMemcpyAsync(&g, cv.gm.g, sizeof(g), hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   for (int i = 0; i < 4; ++i) out4_host[i] = h[i];
-  if (getenv("GRADSLAM_HIP_DEBUG_GRID"))
+  if (gs_env().debug_grid)
     fprintf(stderr, "grid: box (%.3f %.3f %.3f)-(%.3f %.3f %.3f) c %.4f cells %d x %d x %d = %d\n", g.ox, g.oy, g.oz, g.mx,
             g.my, g.mz, g.c, g.nx, g.ny, g.nz, g.ncell);
   return GS_OK;
@@ -2111,13 +1969,7 @@ extern "C" int gs_localize_far_stats_i64(const void* scratch, int H, int W, int 
 extern "C" int gs_localize_list_stats_i64(const void* scratch, int H, int W, int ds, int64_t map_rows, int64_t* out192_host,
                                           void* stream) {
   GS_REQUIRE(scratch && out192_host && H > 0 && W > 0 && ds > 0 && map_rows > 0, "bad arguments");
-  const int64_t n_lat = loc_lattice(H, W, ds);
-  gs_localize_seq q;
-  memset(&q, 0, sizeof(q));
-  q.scratch = const_cast<void*>(scratch);
-  q.map.capacity = map_rows; q.map.n_bound = map_rows;
-  const LocCarve cv = loc_carve(q, n_lat);
-  const ListMem lm = list_carve(reinterpret_cast<char*>(cv.sc.state) + gs_icp_scratch_bytes(n_lat, map_rows), n_lat);
+  const ListMem lm = loc_carve_of(scratch, H, W, ds, map_rows).lm;
   int h[3 * GL_STAT_LAUNCHES];
   hipStream_t st = gs_stream(stream);
   GS_HIP(hipMemcpyAsync(h, lm.stat, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -2129,15 +1981,10 @@ extern "C" int gs_localize_list_stats_i64(const void* scratch, int H, int W, int
 extern "C" int gs_localize_solve_stats_i64(const void* scratch, int H, int W, int ds, int64_t map_rows, int64_t* out8_host,
                                            void* stream) {
   GS_REQUIRE(scratch && out8_host && H > 0 && W > 0 && ds > 0 && map_rows > 0, "bad arguments");
-  const int64_t n_lat = loc_lattice(H, W, ds);
-  gs_localize_seq q;
-  memset(&q, 0, sizeof(q));
-  q.scratch = const_cast<void*>(scratch);
-  q.map.capacity = map_rows; q.map.n_bound = map_rows;
-  const LocCarve cv = loc_carve(q, n_lat);
+  const LocCarve cv = loc_carve_of(scratch, H, W, ds, map_rows);
   unsigned h[PS_WORDS];
   hipStream_t st = gs_stream(stream);
-  GS_HIP(hipMemcpyAsync(h, cv.sc.rowred + LIN_NV, sizeof(h), hipMemcpyDeviceToHost, st));   // (the sync record: LocSeq::sync)
+  GS_HIP(hipMemcpyAsync(h, cv.sc.sync, sizeof(h), hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   static_assert(PS_WORDS == 8, "out8");
   for (int i = 0; i < PS_WORDS; ++i) out8_host[i] = h[i];
@@ -2186,14 +2033,13 @@ extern "C" int gs_pointfusion_step_batch_f32(const gs_step_seq* seqs_host, int B
     }
     // the frame-map launch also zeroes the grid scratch of this chunk's localisation (which then starts with ONE launch
     // for the source lattice and the map projection instead of a clearing launch followed by the projection)
-    const int64_t n_lat = loc_lattice(H, W, ds);
     GsClearJob job;
     job.n = nb;
     for (int b = 0; b < nb; ++b) {
       GS_REQUIRE(ls[b].map.points && ls[b].map.n_bound > 0, "every sequence needs a non-empty map");
-      const LocCarve cv = loc_carve(ls[b], n_lat);
+      const LocCarve cv = loc_carve_of(ls[b].scratch, H, W, ds, loc_rows(ls[b].map));
       job.ptr[b] = reinterpret_cast<char*>(cv.gm.g);
-      if (b == 0) job.bytes = gs_knn_grid_clear_bytes(cv.gm, gs_knn_grid_cells_cap(n_lat));
+      if (b == 0) job.bytes = gs_knn_grid_clear_bytes(cv.gm, gs_knn_grid_cells_cap(loc_lattice(H, W, ds)));
     }
     GsPixelTables tabs{};
     tabs.n = implicit_global ? nb : 0;

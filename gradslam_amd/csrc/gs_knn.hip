@@ -23,6 +23,7 @@
 #include <stdlib.h>
 
 #include "gs_assoc_dev.h"
+#include "gs_env.h"
 #include "gs_knn_bbox.h"
 
 constexpr int KNN_BLOCK = 256;
@@ -108,11 +109,7 @@ int gs_knn_brute_launch(const float* src_in, const float* Tapply, float* src_out
                         const float* tgt, int64_t n_tgt, unsigned long long* best, hipStream_t st) {
   // source points per thread: 8 amortises the LDS broadcast and loop overhead over more pairs on
   // large problems; 4 keeps more workgroups in flight on small ones (GRADSLAM_HIP_KNN_SPT overrides)
-  static int spt_env = -1;
-  if (spt_env < 0) {
-    const char* e = getenv("GRADSLAM_HIP_KNN_SPT");
-    spt_env = e ? atoi(e) : 0;
-  }
+  const int spt_env = gs_env().knn_spt;
   const int spt = spt_env == 4 || spt_env == 8 ? spt_env : (n_src * n_tgt >= (int64_t)1 << 27 ? 8 : 4);
   GsProf prof(GS_PROF_KNN, (double)n_src * (double)n_tgt, st);  // work unit: pair distances
   if (spt == 8) {
