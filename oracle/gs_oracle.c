@@ -860,7 +860,9 @@ EXPORT int64_t gs_or_fuse_append(float* points, float* normals, float* colors, f
   size_t P = (size_t)H * W;
   int any = 0;
   for (size_t p = 0; p < P; ++p) if (best_pix[p] >= 0) { any = 1; break; }
-  if (n_map > 0 && any) { /* :659 merge branch only when the table is non-empty */
+  /* :659 merge branch only when the table is non-empty -- the table of the WHOLE batch: renorm_all == 2 says
+     "another sequence of the batch has a match" (as gs_fuse_append_f32 takes it) */
+  if (n_map > 0 && (any || renorm_all == 2)) {
     int32_t* pix_of = (int32_t*)malloc(sizeof(int32_t) * (size_t)n_map);
     for (int64_t n = 0; n < n_map; ++n) pix_of[n] = -1;
     for (size_t p = 0; p < P; ++p) if (best_pix[p] >= 0) pix_of[best_pix[p]] = (int32_t)p;

@@ -311,7 +311,8 @@ def rows_to_best_pix(rows, H, W):
 # ------------------------------------------------------------------------------- K6
 def fuse_append(points, normals, colors, ccounts, best_pix, gvertex, gnormal, rgb, alpha_img, depth,
                 renorm_all=True):
-    """Returns new (points, normals, colors, ccounts) arrays (inputs are not modified)."""
+    """Returns new (points, normals, colors, ccounts) arrays (inputs are not modified).  renorm_all = 2: every row is
+    rewritten even when this sequence has no match (another sequence of the batch has one, fusionutils.py:659)."""
     H, W = depth.shape
     N = points.shape[0]
     cap = N + H * W
@@ -323,7 +324,7 @@ def fuse_append(points, normals, colors, ccounts, best_pix, gvertex, gnormal, rg
                                 _c(best_pix, np.int32).ctypes.data_as(i32p), _f(_c(gvertex, np.float32)),
                                 _f(_c(gnormal, np.float32)), _f(_c(rgb, np.float32)),
                                 _f(_c(alpha_img, np.float32)), _f(_c(depth, np.float32)), H, W,
-                                1 if renorm_all else 0)
+                                2 if renorm_all == 2 else (1 if renorm_all else 0))
     assert c >= 0
     return P[:c].copy(), Nn[:c].copy(), Cc[:c].copy(), F[:c].copy()
 
