@@ -20,6 +20,7 @@
 
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <type_traits>
 
 #include "gs_env.h"
@@ -1024,33 +1025,56 @@ static void icp_half_launch(const IcpHalfPlan& pl, IcpHalfBatch& hb, GsCount n_s
 }
 
 // Large solves (more rows than FS_REDUCE_ROWS): every block of the next kernel adding up all rows is
-// O(rows^2) L2 traffic.  One extra single-block launch adds them up once, in the same order, into a one-row
+// O(rows^2) L2 traffic.  One extra launch of a block per sequence adds them up once, in the same order, into a one-row
 // buffer.  The threshold sits above the 815 rows of a 1296x968 frame at dsratio 4: there the 20 extra launches per
 // solve cost more than the 182 KB of rows per block (measured 2 % of the frame).
 constexpr int FS_REDUCE_ROWS = 1024;
-__global__ void __launch_bounds__(FS_BLOCK) gs_icp_reduce_rows_kernel(const double* __restrict__ partials_in,
-                                                                      GsCount n_src_c, double* __restrict__ row_out) {
+struct IcpRowsBatch {
+  int B;
+  const double* in[GS_MAX_BATCH];
+  double* out[GS_MAX_BATCH];
+};
+__global__ void __launch_bounds__(FS_BLOCK) gs_icp_reduce_rows_batch_kernel(const IcpRowsBatch rb, GsCount n_src_c) {
   __shared__ double S[32];
   __shared__ double sub[FS_BLOCK / 32][32];
   const int nrows = (int)((gs_count(n_src_c) + FS_QPB - 1) / FS_QPB);
-  icp_sum_rows<FS_BLOCK>(partials_in, nrows, S, sub);
-  if (threadIdx.x < LIN_NV) row_out[threadIdx.x] = S[threadIdx.x];
+  icp_sum_rows<FS_BLOCK>(rb.in[blockIdx.x], nrows, S, sub);
+  if (threadIdx.x < LIN_NV) rb.out[blockIdx.x][threadIdx.x] = S[threadIdx.x];
 }
 
 // After the last look-ahead: final LM / gradLM update and the (composed) result.
-__global__ void __launch_bounds__(FS_BLOCK) gs_icp_finish_kernel(const double* __restrict__ partials_in, GsCount n_src_c,
-                                                                 GsIcpState* __restrict__ st, int buf,
-                                                                 gs_icp_params prm, const float* __restrict__ compose16,
-                                                                 float* __restrict__ out_T16) {
+struct IcpFinishBatch {
+  int B;
+  const double* partials_in[GS_MAX_BATCH];
+  GsIcpState* st[GS_MAX_BATCH];
+  const float* compose16[GS_MAX_BATCH];
+  float* out_T16[GS_MAX_BATCH];
+  unsigned* sync[GS_MAX_BATCH];   // sync record of a persistent solve (NULL: none): anything but a complete run = NaN pose
+  int nb, h0;                     // (persistent solve) blocks per sequence, first half-iteration it served
+};
+__global__ void __launch_bounds__(FS_BLOCK) gs_icp_finish_batch_kernel(const IcpFinishBatch fb, GsCount n_src_c, int buf,
+                                                                       gs_icp_params prm) {
   __shared__ double red[FS_BLOCK / GS_WAVE];
+  const int b = blockIdx.x;
   const int nrows_in = (int)((gs_count(n_src_c) + FS_QPB - 1) / FS_QPB);
-  const double e1 = icp_sum_col27<FS_BLOCK>(partials_in, nrows_in, red);
+  const double e1 = icp_sum_col27<FS_BLOCK>(fb.partials_in[b], nrows_in, red);
   if (threadIdx.x != 0) return;
+  GsIcpState* st = fb.st[b];
   IcpSmall sm = st->s[buf];
   const int it = prm.numiters - 1;
   icp_update_math((float)e1, sm, prm, it < GS_ICP_MAX_ITERS ? st->trace + 12 * it : nullptr);
   st->s[buf ^ 1] = sm;
-  icp_write_result(sm, compose16, out_T16);
+  icp_write_result(sm, fb.compose16[b], fb.out_T16[b]);
+  // The persistent solve (gs_icp_persist.h) counts as run only if no block gave up waiting (error word), every one of its
+  // nb blocks arrived at every half-iteration it served, and its XCD handed out at least nb tickets: an XCD that got no
+  // block at all raises no error, and its partial rows and state are those of the launch before -- fail loudly instead.
+  if (unsigned* sy = fb.sync[b]) {
+    const unsigned arrived = sy[PS_ARRIVED], want = (unsigned)fb.nb * (unsigned)(2 * prm.numiters - fb.h0);
+    if (!(sy[PS_ERROR] == 0u && arrived == want && sy[PS_TICKET] >= (unsigned)fb.nb))
+      for (int i = 0; i < 16; ++i) fb.out_T16[b][i] = __builtin_nanf("");
+    sy[PS_NB] = (unsigned)fb.nb;   // (diagnostics: gs_localize_solve_stats_i64)
+    sy[PS_H0] = (unsigned)fb.h0;
+  }
 }
 
 // ---------------------------------------------------------------- brute-force path ------
@@ -1148,9 +1172,8 @@ __global__ void __launch_bounds__(SUM_BLOCK) gs_icp_update_kernel(const double* 
 }
 
 // ---------------------------------------------------------------- host side ------------
-__global__ void gs_icp_init_kernel(GsIcpState* __restrict__ st, const float* __restrict__ init16, float damp,
-                                   int numiters, const float* __restrict__ compose16, float* __restrict__ out_T16) {
-  if (threadIdx.x != 0) return;
+// the state a solve starts from (both buffers): nothing accumulated, the initial transform pending
+GS_DEV IcpSmall icp_state_init(const float* __restrict__ init16, float damp) {
   IcpSmall sm;
   for (int i = 0; i < 16; ++i) {
     sm.T_total[i] = init16[i];
@@ -1161,6 +1184,12 @@ __global__ void gs_icp_init_kernel(GsIcpState* __restrict__ st, const float* __r
   sm.damp = damp;
   sm.err = 0.0f;
   sm.pad[0] = sm.pad[1] = 0.0f;
+  return sm;
+}
+__global__ void gs_icp_init_kernel(GsIcpState* __restrict__ st, const float* __restrict__ init16, float damp,
+                                   int numiters, const float* __restrict__ compose16, float* __restrict__ out_T16) {
+  if (threadIdx.x != 0) return;
+  const IcpSmall sm = icp_state_init(init16, damp);
   st->s[0] = sm;
   st->s[1] = sm;
   if (numiters == 0) icp_write_result(sm, compose16, out_T16);  // degenerate: the (composed) initial transform
@@ -1191,7 +1220,7 @@ static IcpLayout icp_layout(int64_t n_src, int64_t n_tgt) {
 }
 struct IcpScratch {
   GsIcpState* state;
-  double* rowred;  // one partial row (large solves: gs_icp_reduce_rows_kernel)
+  double* rowred;  // one partial row (large solves: gs_icp_reduce_rows_batch_kernel)
   unsigned* sync;  // [PS_WORDS] ticket / arrival / error words of the persistent solve
   unsigned long long* best; float *srcA, *srcB;
   double* partials[2]; void* grid;
@@ -1222,159 +1251,6 @@ static double icp_alg_bytes(int numiters, int64_t n_slots, int64_t n_queries, in
   const double look = 12.0 * n_slots + 24.0 * n_queries + 8.0 * rows + 16.0 * n_binned;
   return (double)numiters * (full + look);
 }
-
-static int icp_run(const float* src, int64_t n_src, const float* tgt, const float* tgt_normals,
-                   int64_t n_tgt, const float* init16, const float* compose16,
-                   const gs_icp_params* prm, float* out_T16, int64_t* out_idx, void* icp_scratch,
-                   void* tape, void* stream, const int64_t* n_src_dev = nullptr,
-                   const int64_t* n_tgt_dev = nullptr, GsTargetFilter flt = GsTargetFilter{nullptr, 1, 1}) {
-  GS_REQUIRE(prm, "params_host must not be NULL");
-  GS_REQUIRE(n_src > 0 && n_tgt > 0, "empty point set");
-  GS_REQUIRE(n_tgt < 0x7fffffffll && n_src < 0x7fffffffll, "too many points");
-  GS_REQUIRE(src && tgt && tgt_normals && init16 && out_T16 && icp_scratch, "NULL pointer");
-  GS_REQUIRE(prm->numiters >= 0 && prm->numiters <= GS_ICP_MAX_ITERS, "numiters must be in [0, 1024]");
-  GS_REQUIRE(prm->mode == 0 || prm->mode == 1, "mode must be 0 (ICP) or 1 (gradICP)");
-  hipStream_t st = gs_stream(stream);
-  IcpScratch sc = icp_carve(icp_scratch, icp_layout(n_src, n_tgt));
-  hipLaunchKernelGGL(gs_icp_init_kernel, dim3(1), dim3(64), 0, st, sc.state, init16, prm->damp, prm->numiters,
-                     compose16, out_T16);
-  // device-side counts (n_src / n_tgt are then upper bounds) always take the grid path
-  const bool dev_counts = n_src_dev || n_tgt_dev || flt.pix;  // a target filter exists only in the grid path
-  const bool use_grid = prm->numiters > 0 && (dev_counts || (!gs_env().knn_brute && gs_knn_use_grid(n_src, n_tgt)));
-  const GsCount n_src_c{n_src, n_src_dev}, n_tgt_c{n_tgt, n_tgt_dev};
-  float* bufs[2] = {sc.srcA, sc.srcB};
-  TapePtrs tp = {nullptr, nullptr, nullptr};
-  if (tape) {
-    GsIcpTape t = gs_icp_tape_carve(tape, n_src, prm->numiters);
-    tp.src = t.src; tp.idx = t.idx; tp.sys = t.sys;
-  }
-  // iteration it works on the cloud bufs[it & 1], or on its tape slot when a tape is recorded
-  auto cloud = [&](int it) { return tp.src ? tp.src + (size_t)it * 3 * (size_t)n_src : bufs[it & 1]; };
-  auto tidx = [&](int it, int which) { return tp.idx ? tp.idx + ((size_t)it * 2 + which) * (size_t)n_src : nullptr; };
-
-  if (use_grid) {
-    // the target set is fixed for all 2*numiters searches of this solve: bin it once
-    int rc = gs_knn_grid_build(tgt, n_tgt_c, n_src, sc.grid, st, flt, tgt_normals);
-    if (rc != GS_OK) return rc;
-    GridMem gm = grid_carve(sc.grid, n_src, n_tgt);
-    const int nfs = (int)icp_rows(n_src);
-    const bool reduce_rows = nfs > FS_REDUCE_ROWS;
-    const float* cur_in = src;  // cloud before the pending transform of the half-iteration
-    int h = 0;                  // half-iteration index: kernel h reads s[h&1] / partials[(h+1)&1], writes the others
-    // one event pair around the 2 x numiters half-iteration kernels; work = algorithmic bytes (icp_alg_bytes).
-    // With a target filter n_tgt is the whole map: the binned count is read back (profile passes only).
-    double prof_bytes = 0.0;
-    if (g_gs_prof_on) {
-      int64_t n_binned = n_tgt;
-      if (flt.pix) {
-        unsigned hits = 0;
-        GS_HIP(hipMemcpyAsync(&hits, gm.bbox + 6, 4, hipMemcpyDeviceToHost, st));
-        GS_HIP(hipStreamSynchronize(st));
-        n_binned = hits;
-      }
-      prof_bytes = icp_alg_bytes(prm->numiters, n_src, n_src, n_binned);
-    }
-    std::unique_ptr<GsProf> prof_loop(new GsProf(GS_PROF_ICP_FUSED, prof_bytes, st, 2 * prm->numiters));
-    const IcpHalfPlan plan = icp_half_plan(gs_env(), icp_device().cus, n_src, 1);
-    IcpHalfBatch hb;
-    hb.B = 1;
-    hb.weak_room = 0.0f;
-    hb.l[0] = IcpHalfLists{nullptr, nullptr, nullptr, nullptr};
-    hb.w[0] = IcpHalfWide{nullptr, nullptr};
-    for (int it = 0; it < prm->numiters; ++it) {
-      float* cur = cloud(it);
-      hb.s[0] = IcpHalfSeq{cur_in, cur, tgt, tgt_normals, n_tgt_c, gm.g, gm.cell_start, gm.sorted, gm.sorted_n,
-                           reinterpret_cast<float*>(sc.best), sc.partials[(h + 1) & 1], sc.partials[h & 1], &sc.state->s[h & 1], &sc.state->s[(h + 1) & 1],
-                           sc.state->trace, out_idx, tidx(it, 0), nullptr};
-      icp_half_launch<true>(plan, hb, n_src_c, prm, it, 0, st);
-      ++h;
-      if (reduce_rows) {
-        GsProf prof(GS_PROF_SOLVE, 1.0, st);
-        hipLaunchKernelGGL(gs_icp_reduce_rows_kernel, dim3(1), dim3(FS_BLOCK), 0, st, sc.partials[(h + 1) & 1], n_src_c,
-                           sc.rowred);
-      }
-      hb.s[0] = IcpHalfSeq{cur, nullptr, tgt, tgt_normals, n_tgt_c, gm.g, gm.cell_start, gm.sorted, gm.sorted_n,
-                           reinterpret_cast<float*>(sc.best), reduce_rows ? sc.rowred : sc.partials[(h + 1) & 1], sc.partials[h & 1], &sc.state->s[h & 1],
-                           &sc.state->s[(h + 1) & 1], sc.state->trace, nullptr, tidx(it, 1), tp.sys};
-      icp_half_launch<false>(plan, hb, n_src_c, prm, it, reduce_rows ? 1 : 0, st);
-      ++h;
-      cur_in = cur;
-    }
-    prof_loop.reset();  // closing event right behind the last half-iteration kernel
-    if (prm->numiters > 0) {
-      GsProf prof(GS_PROF_SOLVE, 1.0, st);
-      hipLaunchKernelGGL(gs_icp_finish_kernel, dim3(1), dim3(FS_BLOCK), 0, st, sc.partials[(h + 1) & 1], n_src_c,
-                         sc.state, h & 1, *prm, compose16, out_T16);
-    }
-    GS_LAUNCH_CHECK();
-    if (tape) return icp_tape_finish(tape, sc.state, n_src, prm->numiters, st);
-    return GS_OK;
-  }
-
-  // ---- brute-force path
-  GS_HIP(hipMemsetAsync(sc.best, 0xff, 8 * (size_t)n_src, st));
-  const int nblk = (int)gs_ceil_div(n_src, LIN_BLOCK);
-  double* partials = sc.partials[0];
-  const float* cur_in = src;
-  for (int it = 0; it < prm->numiters; ++it) {
-    float* cur = cloud(it);
-    // apply the pending transform (initial transform or last T_step) while searching
-    gs_knn_brute_launch(cur_in, sc.state->s[0].T_step, cur, n_src, tgt, n_tgt, sc.best, st);
-    {
-      GsProf prof(GS_PROF_LINEARIZE, 44.0 * (double)n_src, st);  // 8 B best + 12 B src + 24 B gather
-      hipLaunchKernelGGL((gs_icp_linearize_kernel<true>), dim3(nblk), dim3(LIN_BLOCK), 0, st, cur, nullptr, n_src,
-                         tgt, tgt_normals, n_tgt, sc.best, prm->dist_thresh, partials, out_idx, tidx(it, 0));
-    }
-    {
-      GsProf prof(GS_PROF_SOLVE, 1.0, st);
-      hipLaunchKernelGGL(gs_icp_solve_kernel, dim3(1), dim3(SUM_BLOCK), 0, st, partials, nblk, sc.state, it, tp.sys);
-    }
-    // look-ahead: one_step = Tr * cur, searched and reduced without materialising it
-    gs_knn_brute_launch(cur, sc.state->s[0].Tr, nullptr, n_src, tgt, n_tgt, sc.best, st);
-    {
-      GsProf prof(GS_PROF_LINEARIZE, 44.0 * (double)n_src, st);
-      hipLaunchKernelGGL((gs_icp_linearize_kernel<false>), dim3(nblk), dim3(LIN_BLOCK), 0, st, cur,
-                         sc.state->s[0].Tr, n_src, tgt, tgt_normals, n_tgt, sc.best, prm->dist_thresh, partials,
-                         nullptr, tidx(it, 1));
-    }
-    {
-      GsProf prof(GS_PROF_SOLVE, 1.0, st);
-      hipLaunchKernelGGL(gs_icp_update_kernel, dim3(1), dim3(SUM_BLOCK), 0, st, partials, nblk, sc.state, *prm, it,
-                         compose16, out_T16);
-    }
-    cur_in = cur;
-  }
-  GS_LAUNCH_CHECK();
-  if (tape) return icp_tape_finish(tape, sc.state, n_src, prm->numiters, st);
-  return GS_OK;
-}
-
-extern "C" int gs_icp_f32(const float* src, int64_t n_src, const float* tgt, const float* tgt_normals,
-                          int64_t n_tgt, const float* init16, const float* compose16,
-                          const gs_icp_params* prm, float* out_T16, int64_t* out_idx, void* icp_scratch,
-                          void* stream) {
-  return icp_run(src, n_src, tgt, tgt_normals, n_tgt, init16, compose16, prm, out_T16, out_idx, icp_scratch, nullptr,
-                 stream);
-}
-
-extern "C" int gs_icp_dc_f32(const float* src, int64_t n_src_bound, const int64_t* n_src_dev, const float* tgt,
-                             const float* tgt_normals, int64_t n_tgt_bound, const int64_t* n_tgt_dev,
-                             const float* init16, const float* compose16, const gs_icp_params* prm, float* out_T16,
-                             int64_t* out_idx, void* icp_scratch, void* stream) {
-  return icp_run(src, n_src_bound, tgt, tgt_normals, n_tgt_bound, init16, compose16, prm, out_T16, out_idx,
-                 icp_scratch, nullptr, stream, n_src_dev, n_tgt_dev);
-}
-
-extern "C" int gs_icp_map_dc_f32(const float* src, int64_t n_src_bound, const int64_t* n_src_dev,
-                                 const float* map_points, const float* map_normals, const int32_t* pix,
-                                 int64_t n_map_bound, const int64_t* n_map_dev, int W, int ds, const float* init16,
-                                 const float* compose16, const gs_icp_params* prm, float* out_T16,
-                                 void* icp_scratch, void* stream) {
-  GS_REQUIRE(pix && W > 0 && ds > 0, "bad target filter");
-  return icp_run(src, n_src_bound, map_points, map_normals, n_map_bound, init16, compose16, prm, out_T16, nullptr,
-                 icp_scratch, nullptr, stream, n_src_dev, n_map_dev, GsTargetFilter{pix, W, ds});
-}
-
 
 // ---------------------------------------------------------------- batched localisation -----
 // ICPSLAM._localize (slam/icpslam.py:238-247) for B independent sequences in ONE chain of launches: every kernel
@@ -1430,15 +1306,9 @@ GS_DEV void loc_prep_block(const LocBatch& lb, const unsigned bid, const unsigne
     const unsigned long long m = lb.count_valid ? __ballot(valid) : 0ull;
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(reinterpret_cast<unsigned long long*>(q.n_valid), (unsigned long long)__popcll(m));
     if (blk == 0 && threadIdx.x == 0) {  // gs_icp_init_kernel with init = identity
-      IcpSmall sm;
-      for (int i = 0; i < 16; ++i) {
-        const float id = (i % 5 == 0) ? 1.0f : 0.0f;
-        sm.T_total[i] = id; sm.T_step[i] = id; sm.Tr[i] = id;
-      }
-      for (int i = 0; i < 8; ++i) sm.xi[i] = 0.0f;
-      sm.damp = lb.damp;
-      sm.err = 0.0f;
-      sm.pad[0] = sm.pad[1] = 0.0f;
+      float id[16];
+      for (int i = 0; i < 16; ++i) id[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+      const IcpSmall sm = icp_state_init(id, lb.damp);
       q.state->s[0] = sm;
       q.state->s[1] = sm;
       if (q.far_n)
@@ -1472,53 +1342,6 @@ __global__ void __launch_bounds__(256) gs_loc_prep_bbox_kernel(const LocBatch lb
   const unsigned n_prep = (unsigned)lb.B * nb_lat;
   if (blockIdx.x < n_prep) loc_prep_block(lb, blockIdx.x, nb_lat);
   else gridb_bbox_block(gb, blockIdx.x - n_prep, u_hi, v_hi);
-}
-
-struct IcpRowsBatch {
-  int B;
-  const double* in[GS_MAX_BATCH];
-  double* out[GS_MAX_BATCH];
-};
-__global__ void __launch_bounds__(FS_BLOCK) gs_icp_reduce_rows_batch_kernel(const IcpRowsBatch rb, GsCount n_src_c) {
-  __shared__ double S[32];
-  __shared__ double sub[FS_BLOCK / 32][32];
-  const int nrows = (int)((gs_count(n_src_c) + FS_QPB - 1) / FS_QPB);
-  icp_sum_rows<FS_BLOCK>(rb.in[blockIdx.x], nrows, S, sub);
-  if (threadIdx.x < LIN_NV) rb.out[blockIdx.x][threadIdx.x] = S[threadIdx.x];
-}
-
-struct IcpFinishBatch {
-  int B;
-  const double* partials_in[GS_MAX_BATCH];
-  GsIcpState* st[GS_MAX_BATCH];
-  const float* compose16[GS_MAX_BATCH];
-  float* out_T16[GS_MAX_BATCH];
-  unsigned* sync[GS_MAX_BATCH];   // sync record of a persistent solve (NULL: none): anything but a complete run = NaN pose
-  int nb, h0;                     // (persistent solve) blocks per sequence, first half-iteration it served
-};
-__global__ void __launch_bounds__(FS_BLOCK) gs_icp_finish_batch_kernel(const IcpFinishBatch fb, GsCount n_src_c, int buf,
-                                                                       gs_icp_params prm) {
-  __shared__ double red[FS_BLOCK / GS_WAVE];
-  const int b = blockIdx.x;
-  const int nrows_in = (int)((gs_count(n_src_c) + FS_QPB - 1) / FS_QPB);
-  const double e1 = icp_sum_col27<FS_BLOCK>(fb.partials_in[b], nrows_in, red);
-  if (threadIdx.x != 0) return;
-  GsIcpState* st = fb.st[b];
-  IcpSmall sm = st->s[buf];
-  const int it = prm.numiters - 1;
-  icp_update_math((float)e1, sm, prm, it < GS_ICP_MAX_ITERS ? st->trace + 12 * it : nullptr);
-  st->s[buf ^ 1] = sm;
-  icp_write_result(sm, fb.compose16[b], fb.out_T16[b]);
-  // The persistent solve (gs_icp_persist.h) counts as run only if no block gave up waiting (error word), every one of its
-  // nb blocks arrived at every half-iteration it served, and its XCD handed out at least nb tickets: an XCD that got no
-  // block at all raises no error, and its partial rows and state are those of the launch before -- fail loudly instead.
-  if (unsigned* sy = fb.sync[b]) {
-    const unsigned arrived = sy[PS_ARRIVED], want = (unsigned)fb.nb * (unsigned)(2 * prm.numiters - fb.h0);
-    if (!(sy[PS_ERROR] == 0u && arrived == want && sy[PS_TICKET] >= (unsigned)fb.nb))
-      for (int i = 0; i < 16; ++i) fb.out_T16[b][i] = __builtin_nanf("");
-    sy[PS_NB] = (unsigned)fb.nb;   // (diagnostics: gs_localize_solve_stats_i64)
-    sy[PS_H0] = (unsigned)fb.h0;
-  }
 }
 
 static int64_t loc_lattice(int H, int W, int ds) { return (int64_t)((H + ds - 1) / ds) * ((W + ds - 1) / ds); }
@@ -1735,10 +1558,31 @@ static IcpEnginePlan icp_engine_plan(const GsEnv& env, const IcpDevice& dev, int
   p.ps_it0 = p.persist_on ? p.lists_from + 1 : numiters;
   return p;
 }
+// the plan of a solve with every engine off (the single solve): numiters iterations of two plain launches each
+static IcpEnginePlan icp_plain_plan(const IcpHalfPlan& half, int64_t n_src, int numiters) {
+  IcpEnginePlan p{};   // (no lists of any kind, no persistent launch, no weak room)
+  p.binned_normals = true; p.reduce_rows = icp_rows(n_src) > FS_REDUCE_ROWS;
+  p.half = half; p.ps_it0 = numiters;
+  return p;
+}
 
-// ---- the steps of a chunk: bind, prep + grid build, half-iterations, persistent launch, finish (c[b]: the carved scratch of sequence b)
+// Where the solve of one sequence lives, filled once per call: the single solve fills one from its arguments (icp_run),
+// the batched localisation one per sequence from its carved scratch (loc_bind).  What a solve does not keep is NULL.
+struct IcpSolveView {
+  const float* src0;                     // source of the first iteration (later ones: icp_cloud)
+  const float *tgt, *tn; GsCount n_tgt;  // targets and their normals
+  IcpScratch sc; GridMem gm;
+  int64_t* out_idx;                      // (optional) match of every source point in the last iteration
+  TapePtrs tape;                         // (optional) forward tape
+  IcpHalfLists lists; IcpHalfWide wide; FarMem far;   // (optional) candidate lists: ordinary, wide, far
+  const float* compose16; float* out_T16;
+  unsigned* sync;                        // (optional) sync record of a persistent solve, checked by the finish
+};
+
+// ---- the steps of a chunk: bind, prep + grid build, half-iterations, persistent launch, finish (c[b]: the carved scratch
+// of sequence b, v[b]: the view of its solve)
 static void loc_bind(const gs_localize_seq* seqs, int B, int H, int W, int ds, const gs_icp_params* prm,
-                     const IcpEnginePlan& plan, LocCarve* c, LocBatch& lb, GsGridBatch& gb) {
+                     const IcpEnginePlan& plan, LocCarve* c, LocBatch& lb, GsGridBatch& gb, IcpSolveView* v) {
   lb.B = gb.B = B; lb.W = gb.W = W; gb.H = H; lb.ds = gb.ds = ds;
   lb.Wl = (W + ds - 1) / ds; lb.n_lat = loc_lattice(H, W, ds); lb.damp = prm->damp; lb.numiters = prm->numiters;
   gb.cells_cap = gs_knn_grid_cells_cap(lb.n_lat);
@@ -1751,6 +1595,13 @@ static void loc_bind(const gs_localize_seq* seqs, int B, int H, int W, int ds, c
                      plan.wide_on ? c[b].fm.cq : nullptr, c[b].sc.sync};
     gb.s[b] = GsGridSeq{q.map.points, GsCount{q.map.n_bound, q.map.n_dev}, c[b].pix, q.prev_pose16, q.K16,
                         plan.binned_normals ? q.map.normals : nullptr, c[b].gm};
+    v[b] = IcpSolveView{c[b].lattice, q.map.points, q.map.normals, GsCount{q.map.n_bound, q.map.n_dev}, c[b].sc, c[b].gm,
+                        nullptr, TapePtrs{nullptr, nullptr, nullptr},
+                        plan.lists_on ? IcpHalfLists{c[b].lm.lq, c[b].lm.ls, c[b].lm.stat, c[b].sc.sync + PS_WEAK}
+                                      : IcpHalfLists{nullptr, nullptr, nullptr, nullptr},
+                        plan.wide_on ? IcpHalfWide{c[b].fm.cq, c[b].fm.c} : IcpHalfWide{nullptr, nullptr},
+                        plan.far_on ? c[b].fm : FarMem{nullptr, nullptr, nullptr, nullptr},
+                        q.prev_pose16, q.out_pose16, plan.persist_on ? c[b].sc.sync : nullptr};
   }
   lb.count_valid = g_gs_prof_on ? 1 : 0;
   lb.clear_bytes = gs_knn_grid_clear_bytes(c[0].gm, gb.cells_cap);  // same layout offsets for every sequence
@@ -1789,68 +1640,90 @@ static int loc_prof_bytes(int B, const LocCarve* c, int64_t n_lat, int numiters,
   return GS_OK;
 }
 
-// iterations [0, plan.ps_it0): two launches each (+ the far-list builder, + the row sums of large solves); half-iteration
-// h reads state s[h & 1] and the rows partials[(h + 1) & 1], writes the others
-static void loc_half_iterations(const gs_localize_seq* seqs, int B, const IcpEnginePlan& plan, const LocCarve* c,
-                                int64_t n_lat, const gs_icp_params* prm, hipStream_t st) {
-  const GsCount n_src_c{n_lat, nullptr};
-  const FarMem no_far{nullptr, nullptr, nullptr, nullptr};
+// what every entry point asks of the solver's parameters: NULL, or what is wrong with them
+static const char* icp_params_error(const gs_icp_params* prm) {
+  if (!(prm->numiters >= 0 && prm->numiters <= GS_ICP_MAX_ITERS)) return "numiters must be in [0, 1024]";
+  return prm->mode == 0 || prm->mode == 1 ? nullptr : "mode must be 0 (ICP) or 1 (gradICP)";
+}
+
+// The half-iteration indexing, written once for every client.  A solve of numiters iterations is 2 x numiters
+// half-iterations h = 2 * it (first half: search with T_step applied, full normal equations) and h = 2 * it + 1 (look-ahead:
+// search with Tr applied, residual only), then the finish at h = 2 * numiters.  State and partial rows are double-buffered
+// between consecutive launches: half-iteration h (and the finish) reads the state s[h & 1] and the rows
+// partials[(h + 1) & 1] that h - 1 left and writes the others; large solves put one launch in front of a look-ahead that
+// adds the rows it reads up to the one row `rowred`.  Iteration `it` reads the cloud of iteration it - 1 (the first one:
+// the caller's source) and writes its own, which its look-ahead reads: srcA / srcB in turn, or slot `it` of the tape when
+// one is recorded.
+struct IcpHalfIo { const double* rows_in; double* rows_out; const IcpSmall* st_in; IcpSmall* st_out; };
+static IcpHalfIo icp_half_io(const IcpScratch& sc, int h) {
+  return IcpHalfIo{sc.partials[(h + 1) & 1], sc.partials[h & 1], &sc.state->s[h & 1], &sc.state->s[(h + 1) & 1]};
+}
+static float* icp_cloud(const IcpSolveView& v, int it, int64_t n_src) {
+  return v.tape.src ? v.tape.src + (size_t)it * 3 * (size_t)n_src : ((it & 1) ? v.sc.srcB : v.sc.srcA);
+}
+static int32_t* icp_tape_idx(const IcpSolveView& v, int it, int look_ahead, int64_t n_src) {
+  return v.tape.idx ? v.tape.idx + ((size_t)it * 2 + look_ahead) * (size_t)n_src : nullptr;
+}
+
+// iterations [0, plan.ps_it0) of B solves: two launches each (+ the far-list builder, + the row sums of large solves)
+// prof_rows: the row sums get a profile record of their own (the single solve)
+static void loc_half_iterations(const IcpSolveView* v, int B, const IcpEnginePlan& plan, GsCount n_src_c,
+                                const gs_icp_params* prm, hipStream_t st, bool prof_rows) {
+  const int64_t n_src = n_src_c.host;
   IcpHalfBatch hb;
   hb.B = B; hb.weak_room = plan.weak_room;
+  for (int b = 0; b < B; ++b) { hb.w[b] = v[b].wide; hb.l[b] = v[b].lists; }
   for (int it = 0; it < plan.ps_it0; ++it) {
     int h = 2 * it;
     for (int b = 0; b < B; ++b) {
-      const gs_localize_seq& q = seqs[b];
-      const IcpScratch& sc = c[b].sc; const GridMem& gm = c[b].gm;
-      const FarMem& fm = plan.far_on ? c[b].fm : no_far;
-      const float* cur_in = it == 0 ? c[b].lattice : (((it - 1) & 1) ? sc.srcB : sc.srcA);
-      float* cur = (it & 1) ? sc.srcB : sc.srcA;
-      hb.s[b] = IcpHalfSeq{cur_in, cur, q.map.points, q.map.normals, GsCount{q.map.n_bound, q.map.n_dev}, gm.g,
-                           gm.cell_start, gm.sorted, gm.sorted_n, reinterpret_cast<float*>(sc.best),
-                           sc.partials[(h + 1) & 1], sc.partials[h & 1], &sc.state->s[h & 1], &sc.state->s[(h + 1) & 1],
-                           sc.state->trace, nullptr, nullptr, nullptr, fm.cq, fm.c, fm.idx, fm.n};
-      hb.w[b] = plan.wide_on ? IcpHalfWide{c[b].fm.cq, c[b].fm.c} : IcpHalfWide{nullptr, nullptr};
-      hb.l[b] = plan.lists_on ? IcpHalfLists{c[b].lm.lq, c[b].lm.ls, c[b].lm.stat, sc.sync + PS_WEAK}
-                              : IcpHalfLists{nullptr, nullptr, nullptr, nullptr};
+      const IcpSolveView& q = v[b];
+      const IcpHalfIo io = icp_half_io(q.sc, h);
+      hb.s[b] = IcpHalfSeq{it == 0 ? q.src0 : icp_cloud(q, it - 1, n_src), icp_cloud(q, it, n_src), q.tgt, q.tn, q.n_tgt, q.gm.g,
+                           q.gm.cell_start, q.gm.sorted, q.gm.sorted_n, reinterpret_cast<float*>(q.sc.best),
+                           io.rows_in, io.rows_out, io.st_in, io.st_out, q.sc.state->trace, q.out_idx,
+                           icp_tape_idx(q, it, 0, n_src), nullptr, q.far.cq, q.far.c, q.far.idx, q.far.n};
     }
     icp_half_launch<true>(plan.half, hb, n_src_c, prm, it, 0, st, plan.lmode(it, false));
     if (plan.far_on && fs_far_pass(it) >= 0) {   // lists for the far source points this search found
       const int fp = fs_far_pass(it);
       FarBuildBatch fbb; fbb.B = B;
       for (int b = 0; b < B; ++b)
-        fbb.s[b] = FarBuildSeq{(it & 1) ? c[b].sc.srcB : c[b].sc.srcA, c[b].fm.idx + (int64_t)fp * n_lat, c[b].fm.n + fp,
-                               c[b].gm.g, c[b].gm.cell_start, c[b].gm.sorted, reinterpret_cast<float*>(c[b].sc.best), c[b].fm};
+        fbb.s[b] = FarBuildSeq{icp_cloud(v[b], it, n_src), v[b].far.idx + (int64_t)fp * n_src, v[b].far.n + fp,
+                               v[b].gm.g, v[b].gm.cell_start, v[b].gm.sorted, reinterpret_cast<float*>(v[b].sc.best), v[b].far};
       hipLaunchKernelGGL(gs_icp_far_build_kernel, dim3((unsigned)B * FAR_BLOCKS_PER_SEQ), dim3(FAR_BLOCK), 0, st, fbb);
     }
     ++h;
     if (plan.reduce_rows) {
+      std::optional<GsProf> prof;
+      if (prof_rows) prof.emplace(GS_PROF_SOLVE, 1.0, st);
       IcpRowsBatch rb; rb.B = B;
-      for (int b = 0; b < B; ++b) { rb.in[b] = c[b].sc.partials[(h + 1) & 1]; rb.out[b] = c[b].sc.rowred; }
+      for (int b = 0; b < B; ++b) { rb.in[b] = icp_half_io(v[b].sc, h).rows_in; rb.out[b] = v[b].sc.rowred; }
       hipLaunchKernelGGL(gs_icp_reduce_rows_batch_kernel, dim3((unsigned)B), dim3(FS_BLOCK), 0, st, rb, n_src_c);
     }
     for (int b = 0; b < B; ++b) {
-      const IcpScratch& sc = c[b].sc;
+      const IcpSolveView& q = v[b];
+      const IcpHalfIo io = icp_half_io(q.sc, h);
       IcpHalfSeq& u = hb.s[b];
-      u.src_in = (it & 1) ? sc.srcB : sc.srcA; u.src_out = nullptr;
-      u.partials_in = plan.reduce_rows ? sc.rowred : sc.partials[(h + 1) & 1];
-      u.partials_out = sc.partials[h & 1];
-      u.st_in = &sc.state->s[h & 1]; u.st_out = &sc.state->s[(h + 1) & 1];
+      u.src_in = icp_cloud(q, it, n_src); u.src_out = nullptr;
+      u.partials_in = plan.reduce_rows ? q.sc.rowred : io.rows_in; u.partials_out = io.rows_out;
+      u.st_in = io.st_in; u.st_out = io.st_out;
+      u.out_idx = nullptr; u.tape_idx = icp_tape_idx(q, it, 1, n_src); u.tape_sys = q.tape.sys;
     }
     icp_half_launch<false>(plan.half, hb, n_src_c, prm, it, plan.reduce_rows ? 1 : 0, st, plan.lmode(it, true));
   }
 }
 
 // iterations [plan.ps_it0, numiters) as ONE launch: it takes over behind the list-building look-ahead (LMODE 3)
-static void loc_persist(const gs_localize_seq* seqs, int B, const IcpEnginePlan& plan, const LocCarve* c, int64_t n_lat,
-                        const gs_icp_params* prm, hipStream_t st) {
+static void loc_persist(const IcpSolveView* v, int B, const IcpEnginePlan& plan, int64_t n_lat, const gs_icp_params* prm,
+                        hipStream_t st) {
   IcpPersistBatch pb;
   pb.B = B; pb.nb = plan.ps_nb; pb.upb = plan.ps_upb; pb.h0 = 2 * plan.ps_it0; pb.tl_h = 0; pb.timeline = nullptr;
   for (int b = 0; b < B; ++b) {
-    const gs_localize_seq& q = seqs[b];
-    const IcpScratch& sc = c[b].sc; const GridMem& gm = c[b].gm;
-    pb.s[b] = IcpPersistSeq{((plan.ps_it0 - 1) & 1) ? sc.srcB : sc.srcA, GsCount{q.map.n_bound, q.map.n_dev}, gm.g, gm.cell_start,
-                            gm.sorted, gm.sorted_n, {sc.partials[0], sc.partials[1]}, sc.state, c[b].lm.lq, c[b].lm.ls,
-                            c[b].lm.stat, plan.wide_on ? c[b].fm.cq : nullptr, plan.wide_on ? c[b].fm.c : nullptr, sc.sync};
+    const IcpSolveView& q = v[b];
+    const IcpScratch& sc = q.sc; const GridMem& gm = q.gm;
+    pb.s[b] = IcpPersistSeq{icp_cloud(q, plan.ps_it0 - 1, n_lat), q.n_tgt, gm.g, gm.cell_start,
+                            gm.sorted, gm.sorted_n, {sc.partials[0], sc.partials[1]}, sc.state, q.lists.lq, q.lists.ls,
+                            q.lists.lstat, q.wide.cq, q.wide.c, sc.sync};
   }
 #ifdef GS_ICP_TIMELINE
   ps_tl_arm(pb, prm->numiters, st);
@@ -1861,19 +1734,143 @@ static void loc_persist(const gs_localize_seq* seqs, int B, const IcpEnginePlan&
 #endif
 }
 
-// final LM / gradLM update and the composed pose; a persistent solve that did not run completely leaves a NaN pose
-static void loc_finish(const gs_localize_seq* seqs, int B, const IcpEnginePlan& plan, const LocCarve* c, int64_t n_lat,
-                       const gs_icp_params* prm, hipStream_t st) {
+// final LM / gradLM update and the composed result; a persistent solve that did not run completely leaves a NaN pose
+static void loc_finish(const IcpSolveView* v, int B, const IcpEnginePlan& plan, GsCount n_src_c, const gs_icp_params* prm,
+                       hipStream_t st) {
   const int h = 2 * prm->numiters;
   GsProf prof(GS_PROF_SOLVE, 1.0, st);
   IcpFinishBatch fb;
   fb.B = B; fb.nb = plan.persist_on ? plan.ps_nb : 0; fb.h0 = plan.persist_on ? 2 * plan.ps_it0 : 0;
   for (int b = 0; b < B; ++b) {
-    fb.partials_in[b] = c[b].sc.partials[(h + 1) & 1];
-    fb.st[b] = c[b].sc.state; fb.compose16[b] = seqs[b].prev_pose16; fb.out_T16[b] = seqs[b].out_pose16;
-    fb.sync[b] = plan.persist_on ? c[b].sc.sync : nullptr;
+    fb.partials_in[b] = icp_half_io(v[b].sc, h).rows_in;
+    fb.st[b] = v[b].sc.state; fb.compose16[b] = v[b].compose16; fb.out_T16[b] = v[b].out_T16; fb.sync[b] = v[b].sync;
   }
-  hipLaunchKernelGGL(gs_icp_finish_batch_kernel, dim3((unsigned)B), dim3(FS_BLOCK), 0, st, fb, GsCount{n_lat, nullptr}, h & 1, *prm);
+  hipLaunchKernelGGL(gs_icp_finish_batch_kernel, dim3((unsigned)B), dim3(FS_BLOCK), 0, st, fb, n_src_c, h & 1, *prm);   // (reads s[h & 1])
+}
+
+// ---- the single solve: one sequence through the same driver and finish, every engine off (grid path), or the brute-force
+// path of small problems
+static int icp_run(const float* src, int64_t n_src, const float* tgt, const float* tgt_normals,
+                   int64_t n_tgt, const float* init16, const float* compose16,
+                   const gs_icp_params* prm, float* out_T16, int64_t* out_idx, void* icp_scratch,
+                   void* tape, void* stream, const int64_t* n_src_dev = nullptr,
+                   const int64_t* n_tgt_dev = nullptr, GsTargetFilter flt = GsTargetFilter{nullptr, 1, 1}) {
+  GS_REQUIRE(prm, "params_host must not be NULL");
+  GS_REQUIRE(n_src > 0 && n_tgt > 0, "empty point set");
+  GS_REQUIRE(n_tgt < 0x7fffffffll && n_src < 0x7fffffffll, "too many points");
+  GS_REQUIRE(src && tgt && tgt_normals && init16 && out_T16 && icp_scratch, "NULL pointer");
+  GS_REQUIRE(!icp_params_error(prm), icp_params_error(prm));
+  hipStream_t st = gs_stream(stream);
+  IcpScratch sc = icp_carve(icp_scratch, icp_layout(n_src, n_tgt));
+  hipLaunchKernelGGL(gs_icp_init_kernel, dim3(1), dim3(64), 0, st, sc.state, init16, prm->damp, prm->numiters,
+                     compose16, out_T16);
+  // device-side counts (n_src / n_tgt are then upper bounds) always take the grid path
+  const bool dev_counts = n_src_dev || n_tgt_dev || flt.pix;  // a target filter exists only in the grid path
+  const bool use_grid = prm->numiters > 0 && (dev_counts || (!gs_env().knn_brute && gs_knn_use_grid(n_src, n_tgt)));
+  const GsCount n_src_c{n_src, n_src_dev}, n_tgt_c{n_tgt, n_tgt_dev};
+  TapePtrs tp = {nullptr, nullptr, nullptr};
+  if (tape) {
+    GsIcpTape t = gs_icp_tape_carve(tape, n_src, prm->numiters);
+    tp.src = t.src; tp.idx = t.idx; tp.sys = t.sys;
+  }
+  // the solve as the shared driver sees it: one sequence, no candidate lists, no sync record
+  const IcpSolveView v{src, tgt, tgt_normals, n_tgt_c, sc, grid_carve(sc.grid, n_src, n_tgt), out_idx, tp,
+                       IcpHalfLists{nullptr, nullptr, nullptr, nullptr}, IcpHalfWide{nullptr, nullptr},
+                       FarMem{nullptr, nullptr, nullptr, nullptr}, compose16, out_T16, nullptr};
+  auto cloud = [&](int it) { return icp_cloud(v, it, n_src); };
+  auto tidx = [&](int it, int which) { return icp_tape_idx(v, it, which, n_src); };
+
+  if (use_grid) {
+    // the target set is fixed for all 2*numiters searches of this solve: bin it once
+    int rc = gs_knn_grid_build(tgt, n_tgt_c, n_src, sc.grid, st, flt, tgt_normals);
+    if (rc != GS_OK) return rc;
+    // one event pair around the 2 x numiters half-iteration kernels; work = algorithmic bytes (icp_alg_bytes).
+    // With a target filter n_tgt is the whole map: the binned count is read back (profile passes only).
+    double prof_bytes = 0.0;
+    if (g_gs_prof_on) {
+      int64_t n_binned = n_tgt;
+      if (flt.pix) {
+        unsigned hits = 0;
+        GS_HIP(hipMemcpyAsync(&hits, v.gm.bbox + 6, 4, hipMemcpyDeviceToHost, st));
+        GS_HIP(hipStreamSynchronize(st));
+        n_binned = hits;
+      }
+      prof_bytes = icp_alg_bytes(prm->numiters, n_src, n_src, n_binned);
+    }
+    // the B = 1, engines-off client of the batched driver
+    const IcpEnginePlan plan = icp_plain_plan(icp_half_plan(gs_env(), icp_device().cus, n_src, 1), n_src, prm->numiters);
+    {
+      GsProf prof(GS_PROF_ICP_FUSED, prof_bytes, st, 2 * prm->numiters);
+      loc_half_iterations(&v, 1, plan, n_src_c, prm, st, true);
+    }   // closing event right behind the last half-iteration kernel
+    loc_finish(&v, 1, plan, n_src_c, prm, st);
+    GS_LAUNCH_CHECK();
+    if (tape) return icp_tape_finish(tape, sc.state, n_src, prm->numiters, st);
+    return GS_OK;
+  }
+
+  // ---- brute-force path
+  GS_HIP(hipMemsetAsync(sc.best, 0xff, 8 * (size_t)n_src, st));
+  const int nblk = (int)gs_ceil_div(n_src, LIN_BLOCK);
+  double* partials = sc.partials[0];
+  const float* cur_in = src;
+  for (int it = 0; it < prm->numiters; ++it) {
+    float* cur = cloud(it);
+    // apply the pending transform (initial transform or last T_step) while searching
+    gs_knn_brute_launch(cur_in, sc.state->s[0].T_step, cur, n_src, tgt, n_tgt, sc.best, st);
+    {
+      GsProf prof(GS_PROF_LINEARIZE, 44.0 * (double)n_src, st);  // 8 B best + 12 B src + 24 B gather
+      hipLaunchKernelGGL((gs_icp_linearize_kernel<true>), dim3(nblk), dim3(LIN_BLOCK), 0, st, cur, nullptr, n_src,
+                         tgt, tgt_normals, n_tgt, sc.best, prm->dist_thresh, partials, out_idx, tidx(it, 0));
+    }
+    {
+      GsProf prof(GS_PROF_SOLVE, 1.0, st);
+      hipLaunchKernelGGL(gs_icp_solve_kernel, dim3(1), dim3(SUM_BLOCK), 0, st, partials, nblk, sc.state, it, tp.sys);
+    }
+    // look-ahead: one_step = Tr * cur, searched and reduced without materialising it
+    gs_knn_brute_launch(cur, sc.state->s[0].Tr, nullptr, n_src, tgt, n_tgt, sc.best, st);
+    {
+      GsProf prof(GS_PROF_LINEARIZE, 44.0 * (double)n_src, st);
+      hipLaunchKernelGGL((gs_icp_linearize_kernel<false>), dim3(nblk), dim3(LIN_BLOCK), 0, st, cur,
+                         sc.state->s[0].Tr, n_src, tgt, tgt_normals, n_tgt, sc.best, prm->dist_thresh, partials,
+                         nullptr, tidx(it, 1));
+    }
+    {
+      GsProf prof(GS_PROF_SOLVE, 1.0, st);
+      hipLaunchKernelGGL(gs_icp_update_kernel, dim3(1), dim3(SUM_BLOCK), 0, st, partials, nblk, sc.state, *prm, it,
+                         compose16, out_T16);
+    }
+    cur_in = cur;
+  }
+  GS_LAUNCH_CHECK();
+  if (tape) return icp_tape_finish(tape, sc.state, n_src, prm->numiters, st);
+  return GS_OK;
+}
+
+extern "C" int gs_icp_f32(const float* src, int64_t n_src, const float* tgt, const float* tgt_normals,
+                          int64_t n_tgt, const float* init16, const float* compose16,
+                          const gs_icp_params* prm, float* out_T16, int64_t* out_idx, void* icp_scratch,
+                          void* stream) {
+  return icp_run(src, n_src, tgt, tgt_normals, n_tgt, init16, compose16, prm, out_T16, out_idx, icp_scratch, nullptr,
+                 stream);
+}
+
+extern "C" int gs_icp_dc_f32(const float* src, int64_t n_src_bound, const int64_t* n_src_dev, const float* tgt,
+                             const float* tgt_normals, int64_t n_tgt_bound, const int64_t* n_tgt_dev,
+                             const float* init16, const float* compose16, const gs_icp_params* prm, float* out_T16,
+                             int64_t* out_idx, void* icp_scratch, void* stream) {
+  return icp_run(src, n_src_bound, tgt, tgt_normals, n_tgt_bound, init16, compose16, prm, out_T16, out_idx,
+                 icp_scratch, nullptr, stream, n_src_dev, n_tgt_dev);
+}
+
+extern "C" int gs_icp_map_dc_f32(const float* src, int64_t n_src_bound, const int64_t* n_src_dev,
+                                 const float* map_points, const float* map_normals, const int32_t* pix,
+                                 int64_t n_map_bound, const int64_t* n_map_dev, int W, int ds, const float* init16,
+                                 const float* compose16, const gs_icp_params* prm, float* out_T16,
+                                 void* icp_scratch, void* stream) {
+  GS_REQUIRE(pix && W > 0 && ds > 0, "bad target filter");
+  return icp_run(src, n_src_bound, map_points, map_normals, n_map_bound, init16, compose16, prm, out_T16, nullptr,
+                 icp_scratch, nullptr, stream, n_src_dev, n_map_dev, GsTargetFilter{pix, W, ds});
 }
 
 static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int ds, const gs_icp_params* prm,
@@ -1885,8 +1882,8 @@ static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int 
     c[b] = loc_carve(seqs[b].scratch, layouts[b]);
   }
   const IcpEnginePlan plan = icp_engine_plan(gs_env(), icp_device(), B, n_lat, prm->numiters, layouts);
-  LocBatch lb; GsGridBatch gb;
-  loc_bind(seqs, B, H, W, ds, prm, plan, c, lb, gb);
+  LocBatch lb; GsGridBatch gb; IcpSolveView v[GS_MAX_BATCH];
+  loc_bind(seqs, B, H, W, ds, prm, plan, c, lb, gb, v);
   int rc = loc_prep(seqs, lb, gb, st, grid_cleared);
   if (rc != GS_OK) return rc;
   if (prm->numiters == 0) { GS_LAUNCH_CHECK(); return GS_OK; }
@@ -1894,10 +1891,10 @@ static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int 
   if (g_gs_prof_on && (rc = loc_prof_bytes(B, c, n_lat, prm->numiters, st, &prof_bytes)) != GS_OK) return rc;
   {
     GsProf prof(GS_PROF_ICP_FUSED, prof_bytes, st, 2 * prm->numiters);
-    loc_half_iterations(seqs, B, plan, c, n_lat, prm, st);
-    if (plan.persist_on) loc_persist(seqs, B, plan, c, n_lat, prm, st);
+    loc_half_iterations(v, B, plan, GsCount{n_lat, nullptr}, prm, st, false);
+    if (plan.persist_on) loc_persist(v, B, plan, n_lat, prm, st);
   }
-  loc_finish(seqs, B, plan, c, n_lat, prm, st);
+  loc_finish(v, B, plan, GsCount{n_lat, nullptr}, prm, st);
   GS_LAUNCH_CHECK();
   return GS_OK;
 }
@@ -1905,8 +1902,7 @@ static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int 
 static int localize_batch(const gs_localize_seq* seqs_host, int B, int H, int W, int ds, const gs_icp_params* prm,
                           void* stream, bool grid_cleared) {
   GS_REQUIRE(seqs_host && prm && B > 0 && H > 0 && W > 0 && ds > 0, "bad arguments");
-  GS_REQUIRE(prm->numiters >= 0 && prm->numiters <= GS_ICP_MAX_ITERS, "numiters must be in [0, 1024]");
-  GS_REQUIRE(prm->mode == 0 || prm->mode == 1, "mode must be 0 (ICP) or 1 (gradICP)");
+  GS_REQUIRE(!icp_params_error(prm), icp_params_error(prm));
   GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   for (int b = 0; b < B; ++b) {
     const gs_localize_seq& q = seqs_host[b];
