@@ -72,6 +72,16 @@ class RenderBackwardSeq(C.Structure):
                 ("scratch", C.c_void_p)]
 
 
+class PruneSeq(C.Structure):
+    """gs_prune_seq: one map, its destination buffers and controls for gs_prune_map_dc_f32."""
+    _fields_ = [("points", C.c_void_p), ("normals", C.c_void_p), ("colors", C.c_void_p), ("features", C.c_void_p),
+                ("F", C.c_int32), ("n_bound", C.c_int64), ("n_dev", C.c_void_p),
+                ("points_out", C.c_void_p), ("normals_out", C.c_void_p), ("colors_out", C.c_void_p),
+                ("features_out", C.c_void_p), ("capacity_out", C.c_int64), ("keep", C.c_void_p),
+                ("marks", C.c_void_p), ("n_marks", C.c_int32), ("young_mark", C.c_int32),
+                ("n_out", C.c_void_p), ("removed_out", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 # name -> argtypes (return type is int unless listed in _RESTYPE)
 _PROTOS = {
     "gs_abi_version": [],
@@ -155,11 +165,14 @@ _PROTOS = {
     "gs_render_map_dc_f32": [C.POINTER(RenderSeq), _i32, _i32, _i32, _i32, _i32, _f, _i32, _vp],
     "gs_render_backward_scratch_bytes": [_i32, _i32, _i32, _i64],
     "gs_render_map_backward_dc_f32": [C.POINTER(RenderBackwardSeq), _i32, _i32, _i32, _i32, _i32, _vp],
+    "gs_prune_scratch_bytes": [_i64],
+    "gs_prune_map_dc_f32": [C.POINTER(PruneSeq), _i32, _f, _i32, _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,
             "gs_knn1_grid_scratch_bytes": _i64, "gs_update_map_scratch_bytes": _i64, "gs_global_maps_pose_backward_scratch_bytes": _i64, "gs_icp_tape_bytes": _i64, "gs_icp_backward_scratch_bytes": _i64,
             "gs_localize_scratch_bytes": _i64, "gs_frame_maps_backward_kbar_scratch_bytes": _i64,
-            "gs_render_scratch_bytes": _i64, "gs_render_backward_scratch_bytes": _i64}
+            "gs_render_scratch_bytes": _i64, "gs_render_backward_scratch_bytes": _i64,
+            "gs_prune_scratch_bytes": _i64}
 EXPORTS = tuple(_PROTOS)
 
 

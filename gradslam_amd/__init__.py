@@ -6,7 +6,12 @@
 Same classes, functions, argument meaning and error behaviour as gradslam v0.1.0 for the path
 depth -> vertex/normal maps -> (grad)ICP odometry -> PointFusion map update; the bodies are
 hand-written HIP kernels for gfx950 in gradslam_amd/csrc (C-ABI: include/gradslam_hip.h).
-The HIP library is loaded on first use and there is no CPU / PyTorch fallback."""
+The HIP library is loaded on first use and there is no CPU / PyTorch fallback.
+
+Beyond the reference: `Pointclouds.render` (the model view: the map seen from camera poses, optionally differentiable)
+and `Pointclouds.mark_epoch / prune_ / prune` with `PointFusion(prune_min_confidence=..., prune_min_age=...,
+prune_every=...)` (off by default): a stable, batched compaction of the map that removes surfels whose confidence stays
+below a threshold after a number of steps, without a read-back and without a per-surfel age channel."""
 from .version import __version__  # noqa: F401
 from .geometry import *  # noqa: F401,F403
 from . import odometry, slam, metrics  # noqa: F401

@@ -931,6 +931,102 @@ def render_map(points, normals, colors, ccounts, poses, K, H, W, n_dev=None, rad
     return RenderedViews(*[None if t is None else t[0] for t in r])
 
 
+# ----------------------------------------------------------------------------------- pruning the map
+PrunedMaps = collections.namedtuple("PrunedMaps", ["maps", "counts", "removed"])
+PRUNE_MAX_MARKS = 64
+
+
+def prune_map_batch(maps, min_confidence=None, keep=None, marks=None, young_mark=-1, out=None):
+    """Stable compaction of the maps of B sequences into NEW buffers (gs_prune_map_dc_f32: count, tile scan, scatter and
+    marks launch per 8 sequences; nothing is read back).  maps: per sequence (points, normals, colors, features,
+    n_bound, n_dev) as in render_map_batch -- normals / colors / features may be None, features is (rows, F).  With n =
+    min(n_dev[0], n_bound), row r < n survives iff (keep is None or keep[r] != 0) and (min_confidence is None or r >=
+    young_from or features[r, 0] >= min_confidence); min_confidence needs F == 1 (the confidence count).  keep: per
+    sequence a (rows,) bool / uint8 tensor or None.  marks: per sequence a device int64 tensor of at most 64 ascending row
+    indices or None; young_from = marks[b][young_mark] (young_mark, an int or one int per sequence; -1: every row is old
+    enough), and the call REWRITES each mark as the number of survivors in front of it.  out: per sequence the four
+    destination tensors (None where the source is None), at least n_bound rows each; default: new tensors of the sources'
+    shapes (same capacity).  Returns PrunedMaps(maps = per sequence (points, normals, colors, features), counts (B,) int64
+    on the device, removed (B,) int64 on the device); destination rows at or beyond the new count are not written."""
+    Bn = len(maps)
+    if Bn == 0:
+        raise ValueError("prune_map: no maps")
+    for name, val in (("keep", keep), ("marks", marks), ("out", out)):
+        if val is not None and len(val) != Bn:
+            raise ValueError("prune_map: %s must have one entry per map (%d), got %d" % (name, Bn, len(val)))
+    young = [int(young_mark)] * Bn if not isinstance(young_mark, (list, tuple)) else [int(y) for y in young_mark]
+    if len(young) != Bn:
+        raise ValueError("prune_map: young_mark must be an int or one int per map")
+    _warn_detached("prune_map", *[t for m in maps for t in m[:4]])
+    held = [tuple(None if t is None else _c(t.detach()) for t in m[:4]) for m in maps]
+    dev = require_device(*[t for h in held for t in h])
+    if dev is None or held[0][0] is None:
+        raise ValueError("prune_map: a map without points")
+    ws = Workspace.get(dev)
+    L = lib()
+    seqs = (_C.PruneSeq * Bn)()
+    cnt = torch.empty((2, Bn), dtype=torch.int64, device=dev)
+    c0 = cnt.data_ptr()
+    res, alive = [], []
+    for b in range(Bn):
+        P, N, Cc, F = held[b]
+        n_bound, n_dev = maps[b][4], maps[b][5]
+        if P is None or P.ndim != 2 or P.shape[1] != 3:
+            raise ValueError("prune_map: points must be (rows, 3)")
+        if any(t is not None and (t.ndim != 2 or t.shape[0] < P.shape[0]) for t in (N, Cc, F)) or \
+                any(t is not None and t.shape[1] != 3 for t in (N, Cc)):
+            raise ValueError("prune_map: normals / colors must be (rows, 3), features (rows, F), with as many rows as points")
+        n_bound = P.shape[0] if n_bound is None else min(int(n_bound), int(P.shape[0]))
+        if min_confidence is not None and (F is None or F.shape[1] != 1):
+            raise ValueError("prune_map: min_confidence needs one feature channel (the confidence count)")
+        if out is None:
+            dst = tuple(None if t is None else torch.empty_like(t) for t in (P, N, Cc, F))
+        else:
+            dst = tuple(out[b])
+            for s, d in zip((P, N, Cc, F), dst):
+                if (s is None) != (d is None) or (d is not None and (
+                        d.dtype != f32 or not d.is_contiguous() or d.ndim != 2 or d.shape[1] != s.shape[1])):
+                    raise ValueError("prune_map: out must hold a contiguous float32 tensor of the source's width for "
+                                     "every attribute the map has, and None elsewhere")
+        require_device(*dst, n_dev)
+        kp = None if keep is None else keep[b]
+        if kp is not None:
+            if kp.dtype not in (torch.bool, torch.uint8) or kp.ndim != 1 or kp.shape[0] < n_bound:
+                raise ValueError("prune_map: keep must be a (rows,) bool / uint8 tensor of at least n_bound rows")
+            kp = kp.contiguous()
+            kp = kp.view(torch.uint8) if kp.dtype == torch.bool else kp
+        mk = None if marks is None else marks[b]
+        if mk is not None and (mk.dtype != torch.int64 or mk.ndim != 1 or not mk.is_contiguous()):
+            raise ValueError("prune_map: marks must be contiguous 1-d int64 tensors")
+        require_device(kp, mk, P)
+        u = seqs[b]
+        u.points, u.normals, u.colors, u.features = (0 if t is None else t.data_ptr() for t in (P, N, Cc, F))
+        u.F = 0 if F is None else int(F.shape[1])
+        u.n_bound, u.n_dev = n_bound, (0 if n_dev is None else n_dev.data_ptr())
+        u.points_out, u.normals_out, u.colors_out, u.features_out = (0 if t is None else t.data_ptr() for t in dst)
+        u.capacity_out = min(int(t.shape[0]) for t in dst if t is not None)
+        u.keep = 0 if kp is None else kp.data_ptr()
+        u.marks, u.n_marks = (0, 0) if mk is None or mk.numel() == 0 else (mk.data_ptr(), int(mk.numel()))
+        u.young_mark = young[b]
+        u.n_out, u.removed_out = c0 + 8 * b, c0 + 8 * (Bn + b)
+        u.scratch = ws.bytes("prune%d" % b, L.gs_prune_scratch_bytes(n_bound)).data_ptr()
+        res.append(dst)
+        alive.append((kp, mk))
+    check(L.gs_prune_map_dc_f32(seqs, Bn, 0.0 if min_confidence is None else float(min_confidence),
+                                0 if min_confidence is None else 1, stream(dev)), "gs_prune_map_dc_f32")
+    return PrunedMaps(res, cnt[0], cnt[1])
+
+
+def prune_map(points, normals, colors, features, n_dev=None, min_confidence=None, keep=None, marks=None, young_mark=-1,
+              out=None):
+    """prune_map_batch for one map: returns PrunedMaps((points, normals, colors, features), count int64[1], removed
+    int64[1]), both counts on the device."""
+    r = prune_map_batch([(points, normals, colors, features, None, n_dev)], min_confidence=min_confidence,
+                        keep=None if keep is None else [keep], marks=None if marks is None else [marks],
+                        young_mark=young_mark, out=None if out is None else [out])
+    return PrunedMaps(r.maps[0], r.counts, r.removed)
+
+
 def render_map_backward_batch(maps, poses, K, index, upstream, H, W, radius=0, want=(True, True, True, True, True)):
     """Reverse mode of render_map_batch for B sequences in ONE call of gs_render_map_backward_dc_f32 (8 sequences and 4
     views per launch).  maps: per sequence (points, normals, n_bound, n_dev) as given to the forward (normals may be

@@ -15,13 +15,20 @@ __all__ = ["PointFusion"]
 
 
 class PointFusion(ICPSLAM):
-    r"""Point-based Fusion (Keller et al.) on top of ICP/gradICP odometry."""
+    r"""Point-based Fusion (Keller et al.) on top of ICP/gradICP odometry.
+
+    Pruning (off by default): with `prune_min_confidence` set, every `step` ends with `pointclouds.mark_epoch()`, and
+    every `prune_every`-th step of a map first runs `pointclouds.prune_(prune_min_confidence, min_age=prune_min_age)`:
+    surfels whose confidence count is still below the threshold `prune_min_age` steps after they were appended are
+    removed (Keller et al.'s removal of points that stay unstable).  The step counter and the marks live with the map.
+    With `prune_min_confidence=None` a step makes none of these calls."""
 
     def __init__(self, *, odom: str = "gradicp", dist_th: Union[float, int] = 0.05, angle_th: Union[float, int] = 20,
                  sigma: Union[float, int] = 0.6, dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0,
                  B: Union[float, int] = 1.0, B2: Union[float, int] = 1.0, nu: Union[float, int] = 200.0,
-                 device: Union[torch.device, str, None] = None):
+                 device: Union[torch.device, str, None] = None, prune_min_confidence: Union[float, int, None] = None,
+                 prune_min_age: int = 20, prune_every: int = 10):
         super().__init__(odom=odom, dsratio=dsratio, numiters=numiters, damp=damp, dist_thresh=dist_thresh,
                          lambda_max=lambda_max, B=B, B2=B2, nu=nu, device=device)
         if not (isinstance(dist_th, float) or isinstance(dist_th, int)):
@@ -38,18 +45,50 @@ class PointFusion(ICPSLAM):
         rad_th = (angle_th * math.pi) / 180
         self.dot_th = torch.cos(rad_th) if torch.is_tensor(rad_th) else math.cos(rad_th)
         self.sigma = sigma
+        if not (prune_min_confidence is None or
+                (isinstance(prune_min_confidence, (float, int)) and not isinstance(prune_min_confidence, bool))):
+            raise TypeError("Prune confidence threshold must be of type float or int or None; but was of type {}.".format(
+                type(prune_min_confidence)))
+        for name, val in (("prune_min_age", prune_min_age), ("prune_every", prune_every)):
+            if not isinstance(val, int) or isinstance(val, bool):
+                raise TypeError("{} must be of type int; but was of type {}.".format(name, type(val)))
+        if prune_min_age < 0:
+            raise ValueError("prune_min_age ({}) must be non-negative.".format(prune_min_age))
+        if prune_every < 1:
+            raise ValueError("prune_every ({}) must be at least 1.".format(prune_every))
+        if prune_min_confidence is not None and prune_min_confidence < 0:
+            warnings.warn("Prune confidence threshold ({}) should be non-negative.".format(prune_min_confidence))
+        if prune_min_age > Pointclouds.MAX_MARKS:
+            warnings.warn("prune_min_age ({}) exceeds the {} epochs a map remembers: every surfel stays young and "
+                          "nothing is pruned.".format(prune_min_age, Pointclouds.MAX_MARKS))
+        self.prune_min_confidence = prune_min_confidence
+        self.prune_min_age = prune_min_age
+        self.prune_every = prune_every
 
     def step(self, pointclouds: Pointclouds, live_frame: RGBDImages, prev_frame=None, inplace: bool = False):
         # the plain SLAM loop (in place, nothing on the autograd tape, a map with surfels): one foreign call per frame
         # (slam/_fastpath.py: same kernels in the same order as _localize + _map below); anything else, and every
         # subclass that overrides _localize / _map, takes the generic path
+        res = None
         if inplace and type(self) is PointFusion and isinstance(live_frame, RGBDImages) and \
                 isinstance(prev_frame, RGBDImages) and isinstance(pointclouds, Pointclouds):
             from ._fastpath import try_step
             res = try_step(self, pointclouds, live_frame, prev_frame)
-            if res is not None:
-                return res
-        return super().step(pointclouds, live_frame, prev_frame, inplace)
+        if res is None:
+            res = super().step(pointclouds, live_frame, prev_frame, inplace)
+        if self.prune_min_confidence is not None:
+            self._end_step(pointclouds, res[0])
+        return res
+
+    def _end_step(self, before: Pointclouds, pointclouds: Pointclouds):
+        """the pruning schedule of a step (fast and generic path alike): prune on every prune_every-th step of this map,
+        then record the epoch.  The prune comes first, so that min_age = k protects the rows of the last k steps."""
+        if pointclouds is not before:     # (an out-of-place step returns a new container)
+            pointclouds._carry_epochs(before)
+        pointclouds._prune_steps += 1
+        if pointclouds._prune_steps % self.prune_every == 0:
+            pointclouds.prune_(self.prune_min_confidence, min_age=self.prune_min_age)
+        pointclouds.mark_epoch()
 
     def _localize(self, pointclouds: Pointclouds, live_frame: RGBDImages, prev_frame: RGBDImages):
         if isinstance(live_frame, RGBDImages):

@@ -72,6 +72,13 @@ class _CountGroup(object):
                 _CountGroup.wait_s += time.perf_counter() - t0
         self.poll()
 
+    def shrink(self, dev):
+        """A prune wrote smaller counts to `dev`.  The host bounds stay as they are: they, and the read-backs already in
+        flight (counts from before the prune), remain upper bounds.  One more read-back is queued, so that `poll()`
+        tightens the bounds to the pruned counts without a wait."""
+        self.dev = dev
+        self._queue_copy()
+
     def poll(self):
         while self._pending and self._events[self._pending[0][0]].query():
             s, grown = self._pending.pop(0)
@@ -142,6 +149,10 @@ class Pointclouds(object):
         self._n_host: List[int] = []            # points per sequence (see the `_n` property)
         self._padded_cache = {}
         self._generation = 0   # bumped by everything that changes the map in place (see render(differentiable=True))
+        self._marks = None      # (B, MAX_MARKS) int64 on self.device: the counts at the last _n_marks epochs (mark_epoch)
+        self._n_marks = 0
+        self._prune_steps = 0   # steps a pruning PointFusion has taken on this map (the step counter lives with the map)
+        self.last_pruned = None  # (B,) int64: rows the last prune_ removed per sequence (on the map's device, never synced)
         self.equisized = None
 
         if isinstance(points, list):
@@ -241,7 +252,9 @@ class Pointclouds(object):
         if len(ids) == 0:
             raise IndexError("Incorrect indexing at dimension 0, make sure range is within 0 and %d" % len(self))
         lists = {k: (None if self._buf[k] is None else [self._buf[k][i][: self._n[i]] for i in ids]) for k in _ATTRS}
-        return Pointclouds(lists["points"], lists["normals"], lists["colors"], lists["features"])
+        other = Pointclouds(lists["points"], lists["normals"], lists["colors"], lists["features"])
+        other._carry_epochs(self, ids)
+        return other
 
     # ------------------------------------------------------------------ has_*
     @property
@@ -565,6 +578,188 @@ class Pointclouds(object):
             return frames, {"normal": out.normal, "confidence": out.confidence, "index": out.index}
         return frames
 
+    # ------------------------------------------------------------------ pruning
+    # Rows are appended after all older rows and a prune keeps their order, so the index of a row is monotone in the step
+    # that created it: "appended since epoch e" is "row >= the count at e".  The map remembers the counts of its last
+    # MAX_MARKS epochs (the marks); a prune rewrites each mark as the number of survivors in front of it.
+    MAX_MARKS = 64
+
+    def _carry_epochs(self, other, ids=None):
+        """takes the epoch marks and the step counter of `other` (of its sequences `ids`)"""
+        self._prune_steps = other._prune_steps
+        self._n_marks = other._n_marks if other._marks is not None else 0
+        if other._marks is None:
+            self._marks = None
+        else:
+            self._marks = (other._marks if ids is None else other._marks[ids]).clone().to(self.device)
+
+    def _count_group(self):
+        """the _CountGroup that holds the device-side counts of ALL sequences, in order, or None"""
+        B = len(self._n_host)
+        dc = self._dcount
+        if B == 0 or len(dc) != B:
+            return None
+        g0 = dc[0].group
+        if len(g0.bounds) != B or any(dc[b].group is not g0 or dc[b].index != b for b in range(B)):
+            return None
+        return g0
+
+    def mark_epoch(self):
+        r"""Records the current counts as the newest epoch mark (at most `MAX_MARKS` are kept, the oldest is dropped).
+        `prune_(..., min_age=k)` protects the rows appended since the k-th newest mark.  Counts that live on the device are
+        copied device-to-device: nothing is read back."""
+        B = len(self._n_host)
+        if B == 0:
+            return self
+        if self._marks is None or self._marks.shape[0] != B or self._marks.device != self.device:
+            self._marks = torch.zeros((B, self.MAX_MARKS), dtype=torch.int64, device=self.device)
+            self._n_marks = 0
+        if self._n_marks == self.MAX_MARKS:
+            self._marks[:, :-1] = self._marks[:, 1:].clone()
+            self._n_marks -= 1
+        k = self._n_marks
+        grp = self._count_group()
+        if grp is not None:
+            self._marks[:, k].copy_(grp.dev)
+        elif self._dcount:
+            for b in range(B):
+                dc = self._dcount.get(b)
+                if dc is not None:
+                    self._marks[b, k:k + 1].copy_(dc.dev)
+                else:
+                    self._marks[b, k] = self._n_host[b]
+        else:
+            self._marks[:, k] = torch.tensor(self._n_host, dtype=torch.int64)
+        self._n_marks = k + 1
+        return self
+
+    def _keep_list(self, keep):
+        B = len(self._n_host)
+        if keep is None:
+            return [None] * B
+        if torch.is_tensor(keep):
+            if keep.ndim != 2 or keep.shape[0] != B:
+                raise ValueError("keep should have shape ({}, N), but had shape {}".format(B, tuple(keep.shape)))
+            keep = [keep[b] for b in range(B)]
+        elif not isinstance(keep, list):
+            raise TypeError("Expected keep to be of type list or tensor or None; got %r" % type(keep))
+        if len(keep) != B:
+            raise ValueError("keep must have one entry per pointcloud. Got {} != {}.".format(len(keep), B))
+        for t in keep:
+            if not torch.is_tensor(t) or t.ndim != 1 or t.dtype not in (torch.bool, torch.uint8):
+                raise TypeError("keep must hold 1-d bool / uint8 tensors, one per pointcloud")
+        return [t.to(self.device) for t in keep]
+
+    def prune_(self, min_confidence: Optional[float] = None, *, keep=None, min_age: int = 0):
+        r"""Removes rows in place, keeping the order of the rest.  Row r of a sequence survives iff
+
+            (keep is None or keep[r] != 0) and (min_confidence is None or r is young or confidence[r] >= min_confidence)
+
+        (float32 compare: a NaN confidence is removed, a confidence equal to the threshold stays).
+
+        Args:
+            min_confidence: threshold on the confidence count (the first and only feature channel of a surfel map)
+            keep: list of (N_b,) bool / uint8 tensors, or a (B, N) tensor; rows beyond a sequence's tensor are removed
+            min_age: k > 0 protects ("young") the rows appended since the k-th newest `mark_epoch()` from the confidence
+                rule; with fewer than k marks recorded every row is young.  0 protects nothing.
+
+        On a HIP device this is one batched compaction (gs_prune_map_dc_f32) into new buffers of the same capacity;
+        counts that live on the device stay there (nothing is read back; the host-side bounds tighten with the next
+        read-back that lands).  `last_pruned` holds the removed rows per sequence.  Returns self."""
+        B = len(self._n_host)
+        if B == 0 or self._buf["points"] is None:
+            raise ValueError("cannot prune an empty pointclouds object")
+        if not (min_confidence is None or isinstance(min_confidence, (float, int))):
+            raise TypeError("min_confidence must be of type float or int or None; but was of type {}.".format(
+                type(min_confidence)))
+        if not isinstance(min_age, int) or isinstance(min_age, bool) or min_age < 0:
+            raise ValueError("min_age must be a non-negative int; got {!r}".format(min_age))
+        if min_confidence is not None and (any(self._buf[k] is None for k in ("normals", "colors", "features")) or
+                                           self.num_features != 1):
+            raise ValueError("prune needs a surfel map: points, normals, colors and one feature channel (confidence)")
+        keep = self._keep_list(keep)
+        conf, young_mark = min_confidence, -1
+        if conf is not None and min_age > 0:
+            n_marks = self._n_marks if self._marks is not None else 0
+            if n_marks < min_age:
+                conf = None          # every row is young: the confidence rule removes nothing
+            else:
+                young_mark = n_marks - min_age
+        taped = torch.is_grad_enabled() and any(t.requires_grad for k in _ATTRS if self._buf[k] is not None
+                                                for t in self._buf[k])
+        f32 = all(t.dtype == torch.float32 for k in _ATTRS if self._buf[k] is not None for t in self._buf[k])
+        if conf is None and all(k is None for k in keep):
+            self.last_pruned = torch.zeros(B, dtype=torch.int64, device=self.device)
+        elif self.device.type == "cuda" and f32 and not taped:
+            self._prune_hip(conf, keep, young_mark)
+        else:
+            self._prune_torch(conf, keep, young_mark)
+        self._generation += 1
+        self._padded_cache.clear()
+        return self
+
+    def prune(self, min_confidence: Optional[float] = None, *, keep=None, min_age: int = 0):
+        r"""Out-of-place `prune_`: returns a pruned copy (the copy resolves device-side counts, as `clone` does)."""
+        return self.clone().prune_(min_confidence, keep=keep, min_age=min_age)
+
+    def _prune_hip(self, conf, keep, young_mark):
+        from .. import ops
+        B = len(self._n_host)
+        maps, keeps = [], []
+        for b in range(B):
+            bound, n_dev = self._count_of(b)
+            maps.append(tuple(None if self._buf[k] is None else self._buf[k][b] for k in _ATTRS) + (bound, n_dev))
+            kp = keep[b]
+            if kp is not None and kp.shape[0] < bound:   # (rows the caller's tensor does not cover are removed)
+                kp = torch.cat([kp.to(torch.uint8), torch.zeros(bound - kp.shape[0], dtype=torch.uint8, device=kp.device)])
+            keeps.append(kp)
+        n_marks = self._n_marks if self._marks is not None else 0
+        marks = [self._marks[b, :n_marks] for b in range(B)] if n_marks else None
+        r = ops.prune_map_batch(maps, min_confidence=conf, keep=keeps if any(k is not None for k in keeps) else None,
+                                marks=marks, young_mark=young_mark)
+        for b in range(B):
+            for i, k in enumerate(_ATTRS):
+                if self._buf[k] is not None:
+                    self._buf[k][b] = r.maps[b][i]     # same capacity: nothing that follows the capacity is re-sized
+        grp = self._count_group()
+        if grp is not None:
+            grp.shrink(r.counts)
+            self.equisized = True if B == 1 else None
+        else:
+            self._n = [int(v) for v in r.counts.tolist()]     # host-side counts: one read-back
+            self.equisized = len(set(self._n_host)) == 1
+        self.last_pruned = r.removed
+
+    def _prune_torch(self, conf, keep, young_mark):
+        """the same rule through boolean indexing (CPU maps, maps on the autograd tape: the kept rows stay on it)"""
+        n = self._n
+        n_marks = self._n_marks if self._marks is not None else 0
+        new_n, removed = [], []
+        for b, nb in enumerate(n):
+            s = torch.ones(nb, dtype=torch.bool, device=self.device)
+            if keep[b] is not None:
+                kp = keep[b][:nb] != 0
+                s[: kp.shape[0]] &= kp
+                s[kp.shape[0]:] = False
+            if conf is not None:
+                cc = self._buf["features"][b][:nb, 0].detach().to(torch.float32)
+                passes = cc >= torch.tensor(conf, dtype=torch.float32, device=self.device)
+                if young_mark >= 0:
+                    passes |= torch.arange(nb, device=self.device) >= self._marks[b, young_mark]
+                s &= passes
+            for k in _ATTRS:
+                if self._buf[k] is not None:
+                    self._buf[k][b] = self._buf[k][b][:nb][s]
+            if n_marks:
+                before = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(s, 0)])
+                self._marks[b, :n_marks] = before[self._marks[b, :n_marks].clamp(0, nb)]
+            kept = int(s.sum())
+            new_n.append(kept)
+            removed.append(nb - kept)
+        self._n = new_n
+        self.equisized = len(set(new_n)) == 1
+        self.last_pruned = torch.tensor(removed, dtype=torch.int64, device=self.device)
+
     # ------------------------------------------------------------------ copies / moves
     def clone(self):
         other = Pointclouds(device=self.device)
@@ -572,6 +767,7 @@ class Pointclouds(object):
         for k in _ATTRS:
             other._buf[k] = None if self._buf[k] is None else [t[:n].clone() for t, n in zip(self._buf[k], self._n)]
         other.equisized = self.equisized
+        other._carry_epochs(self)
         return other
 
     def detach(self):
@@ -580,6 +776,7 @@ class Pointclouds(object):
         for k in _ATTRS:
             other._buf[k] = None if self._buf[k] is None else [t.detach() for t in self._buf[k]]
         other.equisized = self.equisized
+        other._carry_epochs(self)
         return other
 
     def to(self, device, copy: bool = False):
@@ -592,6 +789,8 @@ class Pointclouds(object):
             for k in _ATTRS:
                 if other._buf[k] is not None:
                     other._buf[k] = [t.to(device) for t in other._buf[k]]
+            if other._marks is not None:
+                other._marks = other._marks.to(device)
         return other
 
     def cpu(self):

@@ -627,6 +627,46 @@ GS_API int64_t gs_render_backward_scratch_bytes(int views, int H, int W, int64_t
 GS_API int gs_render_map_backward_dc_f32(const gs_render_backward_seq* seqs_host, int B, int L, int H, int W,
                                          int radius, void* stream);
 
+/* ------------------------------------------------------------------ pruning the map ------
+ * A stable, out-of-place compaction of B maps (the reference never removes a surfel; Keller et al.'s point-based fusion
+ * drops those that stay unstable).  With n = min(*n_dev, n_bound) (n_bound when n_dev is NULL), row r < n survives iff
+ *   (keep == NULL || keep[r] != 0)  &&  (!use_confidence || r >= young_from || features[r] >= min_confidence)
+ * in float32: a NaN confidence fails the test, a confidence bit-equal to min_confidence passes.  Survivor k of the input
+ * is row k of every destination, moved bit for bit; *n_out = number of survivors, *removed_out = n - *n_out; destination
+ * rows at or beyond *n_out are not written.  Rows are appended in birth order and the compaction keeps order, so "young"
+ * is a row index: young_from = marks[young_mark] as it stands before the call (young_mark = -1: every row is old enough).
+ * marks: up to 64 ascending row indices on the device ("epoch marks": the counts at earlier steps); the call rewrites
+ * each mark m as the number of survivors among the rows < min(m, n).
+ * normals / colors / features may be NULL (their destinations are then not used); use_confidence needs features with
+ * F == 1 (the confidence count).  A destination must not be its source (GS_ERR_INVALID): the scatter of one tile lands
+ * on the input of lower tiles that other blocks may still have to read.  scratch: gs_prune_scratch_bytes(n_bound) bytes
+ * per sequence.  Sequences are served 8 per group of launches (count, tile scan, scatter, marks), whatever their sizes;
+ * nothing is read back.  Every argument is checked before the first HIP call. */
+typedef struct gs_prune_seq {
+  const float* points;      /* (n_bound, 3) */
+  const float* normals;     /* (n_bound, 3) or NULL */
+  const float* colors;      /* (n_bound, 3) or NULL */
+  const float* features;    /* (n_bound, F) or NULL; channel 0 is the confidence count when F == 1 */
+  int32_t F;
+  int64_t n_bound;          /* host-side upper bound of the row count (launch geometry, scratch sizing) */
+  const int64_t* n_dev;     /* device int64[1]: the actual count, or NULL when n_bound is exact */
+  float* points_out;        /* destinations: (capacity_out, 3) / (capacity_out, F) */
+  float* normals_out;
+  float* colors_out;
+  float* features_out;
+  int64_t capacity_out;     /* rows the destinations hold, >= n_bound */
+  const uint8_t* keep;      /* (n_bound) or NULL */
+  int64_t* marks;           /* device int64[n_marks], rewritten in place; may be NULL with n_marks == 0 */
+  int32_t n_marks;          /* 0..64 */
+  int32_t young_mark;       /* index into marks, or -1 */
+  int64_t* n_out;           /* device int64[1] */
+  int64_t* removed_out;     /* device int64[1] or NULL */
+  void* scratch;
+} gs_prune_seq;
+GS_API int64_t gs_prune_scratch_bytes(int64_t n_bound);
+GS_API int gs_prune_map_dc_f32(const gs_prune_seq* seqs_host, int B, float min_confidence, int use_confidence,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif
