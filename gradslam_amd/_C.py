@@ -167,6 +167,8 @@ _PROTOS = {
     "gs_render_map_backward_dc_f32": [C.POINTER(RenderBackwardSeq), _i32, _i32, _i32, _i32, _i32, _vp],
     "gs_prune_scratch_bytes": [_i64],
     "gs_prune_map_dc_f32": [C.POINTER(PruneSeq), _i32, _f, _i32, _vp],
+    "gs_bilateral_depth_f32": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _f, _f, _vp, _vp, _vp],
+    "gs_bilateral_depth_backward_f32": [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f, _f, _vp, _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,
             "gs_knn1_grid_scratch_bytes": _i64, "gs_update_map_scratch_bytes": _i64, "gs_global_maps_pose_backward_scratch_bytes": _i64, "gs_icp_tape_bytes": _i64, "gs_icp_backward_scratch_bytes": _i64,

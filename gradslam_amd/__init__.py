@@ -11,7 +11,9 @@ The HIP library is loaded on first use and there is no CPU / PyTorch fallback.
 Beyond the reference: `Pointclouds.render` (the model view: the map seen from camera poses, optionally differentiable)
 and `Pointclouds.mark_epoch / prune_ / prune` with `PointFusion(prune_min_confidence=..., prune_min_age=...,
 prune_every=...)` (off by default): a stable, batched compaction of the map that removes surfels whose confidence stays
-below a threshold after a number of steps, without a read-back and without a per-surfel age channel."""
+below a threshold after a number of steps, without a read-back and without a per-surfel age channel;
+`RGBDImages.bilateral_filter` with `ICPSLAM / PointFusion(depth_filter=...)` (off by default): the edge-preserving
+pre-pass on the raw depth in front of the vertex and normal maps, differentiable down to the sensor depth."""
 from .version import __version__  # noqa: F401
 from .geometry import *  # noqa: F401,F403
 from . import odometry, slam, metrics  # noqa: F401

@@ -1027,6 +1027,112 @@ def prune_map(points, normals, colors, features, n_dev=None, min_confidence=None
     return PrunedMaps(r.maps[0], r.counts, r.removed)
 
 
+# ----------------------------------------------------------------------------------- bilateral depth filter
+BILATERAL_MAX_RADIUS = 8
+
+
+def _bilateral_args(radius, sigma_space, sigma_range):
+    import math
+    if isinstance(radius, bool) or not isinstance(radius, int):
+        raise TypeError("bilateral_depth: radius must be of type int; but was of type {}.".format(type(radius)))
+    if not 0 <= radius <= BILATERAL_MAX_RADIUS:
+        raise ValueError("bilateral_depth: radius ({}) must be 0 ... {}.".format(radius, BILATERAL_MAX_RADIUS))
+    for name, val in (("sigma_space", sigma_space), ("sigma_range", sigma_range)):
+        if isinstance(val, bool) or not isinstance(val, (float, int)):
+            raise TypeError("bilateral_depth: {} must be of type float or int; but was of type {}.".format(name, type(val)))
+        if not (math.isfinite(val) and val > 0):
+            raise ValueError("bilateral_depth: {} ({}) must be finite and > 0.".format(name, val))
+    return radius, float(sigma_space), float(sigma_range)
+
+
+def _bilateral_frames(depth):
+    """(..., H, W) float32 device tensor -> ((n, H, W) tensor whose rows are contiguous, read in place where the leading
+    dimensions collapse to one stride -- a frame slice of a longer stack, a channels-first stack, a column crop -- and
+    copied otherwise)."""
+    if depth.dtype != f32:
+        depth = depth.to(f32)
+    H, W = depth.shape[-2:]
+    if depth.numel() == 0:
+        raise ValueError("bilateral_depth: empty depth of shape {}".format(tuple(depth.shape)))
+    d3 = depth.reshape(-1, H, W)     # (a view whenever the strides allow it)
+    if d3.stride(2) != 1 or d3.stride(1) < W or (d3.shape[0] > 1 and d3.stride(0) < (H - 1) * d3.stride(1) + W):
+        d3 = d3.contiguous()
+    return d3
+
+
+def _bilateral_forward(depth, radius, sigma_space, sigma_range, out=None, want_wsum=False):
+    if not depth.is_cuda:
+        require_device(depth)      # (raises: no CPU fallback)
+    d3 = _bilateral_frames(depth)
+    n, H, W = d3.shape
+    dev = d3.device
+    shape = tuple(depth.shape)
+    if out is None:
+        out = torch.empty(shape, dtype=f32, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != f32:
+        raise ValueError("bilateral_depth: out must be a float32 tensor of shape {}".format(shape))
+    wsum = torch.empty(shape, dtype=f32, device=dev) if want_wsum else None
+    if require_device(out, wsum) != dev:
+        raise _C.HipExtensionError("tensors live on different devices: %s vs %s" % (dev, out.device))
+    check(lib().gs_bilateral_depth_f32(d3.data_ptr(), d3.stride(0) if n > 1 else H * d3.stride(1), d3.stride(1), n, H, W,
+                                       radius, two_sigma_sq(sigma_space), two_sigma_sq(sigma_range), ptr(out), ptr(wsum),
+                                       stream(dev)), "gs_bilateral_depth_f32")
+    return out, wsum
+
+
+class BilateralDepthFunction(torch.autograd.Function):
+    """depth (..., H, W) -> (bilaterally filtered depth, normaliser W); differentiable w.r.t. depth
+    (gs_bilateral_depth_backward_f32: a gather per input pixel in a fixed order, bitwise reproducible).  Which pixels are
+    valid is a constant; W is returned for inspection and carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, depth, radius, sigma_space, sigma_range):
+        d = depth.detach()
+        out, wsum = _bilateral_forward(d, radius, sigma_space, sigma_range, want_wsum=True)
+        ctx.save_for_backward(d, out, wsum)
+        ctx.mark_non_differentiable(wsum)
+        ctx.prm = (radius, sigma_space, sigma_range)
+        return out, wsum
+
+    @staticmethod
+    def backward(ctx, out_bar, _wsum_bar):
+        if out_bar is None:
+            return None, None, None, None
+        depth, out, wsum = ctx.saved_tensors
+        radius, sigma_space, sigma_range = ctx.prm
+        d3 = _bilateral_frames(depth)
+        n, H, W = d3.shape
+        dev = d3.device
+        out_bar = _c(out_bar)
+        d_bar = torch.empty(tuple(depth.shape), dtype=f32, device=dev)
+        require_device(out, wsum, out_bar, d_bar)
+        check(lib().gs_bilateral_depth_backward_f32(d3.data_ptr(), d3.stride(0) if n > 1 else H * d3.stride(1),
+                                                    d3.stride(1), ptr(out), ptr(wsum), ptr(out_bar), n, H, W, radius,
+                                                    two_sigma_sq(sigma_space), two_sigma_sq(sigma_range), ptr(d_bar),
+                                                    stream(dev)), "gs_bilateral_depth_backward_f32")
+        return d_bar.to(depth.dtype), None, None, None
+
+
+def bilateral_depth(depth, radius=3, sigma_space=2.0, sigma_range=0.03, out=None, return_wsum=False):
+    """Bilateral filter of every (H, W) image of a (..., H, W) depth stack in one launch (gs_bilateral_depth_f32; the
+    arithmetic is pinned operation by operation, include/gradslam_hip.h).  A pixel is valid when depth > 0; invalid
+    pixels are copied through and never contribute, so the valid mask is unchanged.  radius 0 ... 8 (0: the input
+    bits), sigma_space in pixels, sigma_range in the unit of the depth.  The stack is read in place when its rows are
+    contiguous and its leading dimensions collapse to one stride.  out: optional contiguous float32 tensor of depth's
+    shape (not depth itself).  return_wsum: also return the normaliser W per pixel (0 at invalid pixels).
+    With depth.requires_grad the call goes on the autograd tape (BilateralDepthFunction); `out` is then refused."""
+    radius, sigma_space, sigma_range = _bilateral_args(radius, sigma_space, sigma_range)
+    if depth.ndim < 2:
+        raise ValueError("bilateral_depth: depth must be (..., H, W), got shape {}".format(tuple(depth.shape)))
+    if torch.is_grad_enabled() and depth.requires_grad:
+        if out is not None:
+            raise ValueError("bilateral_depth: `out` cannot be given for a depth that requires grad")
+        res, wsum = BilateralDepthFunction.apply(depth, radius, sigma_space, sigma_range)
+        return (res, wsum) if return_wsum else res
+    res, wsum = _bilateral_forward(depth, radius, sigma_space, sigma_range, out=out, want_wsum=return_wsum)
+    return (res, wsum) if return_wsum else res
+
+
 def render_map_backward_batch(maps, poses, K, index, upstream, H, W, radius=0, want=(True, True, True, True, True)):
     """Reverse mode of render_map_batch for B sequences in ONE call of gs_render_map_backward_dc_f32 (8 sequences and 4
     views per launch).  maps: per sequence (points, normals, n_bound, n_dev) as given to the forward (normals may be

@@ -20,13 +20,20 @@ __all__ = ["ICPSLAM"]
 
 
 class ICPSLAM(nn.Module):
-    r"""Point-to-plane ICP odometry + aggregate mapping (every valid pixel is appended)."""
+    r"""Point-to-plane ICP odometry + aggregate mapping (every valid pixel is appended).
+
+    Depth pre-filter (off by default): with `depth_filter=dict(radius=..., sigma_space=..., sigma_range=...)` (any
+    subset of the keys; the rest take the defaults of `RGBDImages.bilateral_filter`) every `step` works on the
+    bilaterally filtered copy of the live frame -- localisation and map update alike -- and writes the recovered pose
+    back to the caller's frame.  `prev_frame` is only read for its poses and is not filtered.  With `depth_filter=None`
+    a step makes no new call."""
 
     def __init__(self, *, odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0,
                  B: Union[float, int] = 1.0, B2: Union[float, int] = 1.0, nu: Union[float, int] = 200.0,
-                 device: Union[torch.device, str, None] = None):
+                 device: Union[torch.device, str, None] = None, depth_filter: Optional[dict] = None):
         super().__init__()
+        self.depth_filter = _check_depth_filter(depth_filter)
         if odom not in ["gt", "icp", "gradicp"]:
             msg = "odometry method ({}) not supported for PointFusion. ".format(odom)
             msg += "Currently supported odometry modules for PointFusion are: 'gt', 'icp', 'gradicp'"
@@ -65,9 +72,24 @@ class ICPSLAM(nn.Module):
         if not isinstance(live_frame, RGBDImages):
             raise TypeError("Expected live_frame to be of type gradslam.RGBDImages. Got {0}.".format(
                 type(live_frame)))
+        if self.depth_filter is None:
+            return self._step(pointclouds, live_frame, prev_frame, inplace)
+        work = self._filtered(live_frame)
+        res = self._step(pointclouds, work, prev_frame, inplace)
+        live_frame.poses = work.poses
+        return res
+
+    def _step(self, pointclouds: Pointclouds, live_frame: RGBDImages, prev_frame: Optional[RGBDImages], inplace: bool):
+        """localise and map on the frame as given (`step` hands over the filtered copy when `depth_filter` is set)"""
         live_frame.poses = self._localize(pointclouds, live_frame, prev_frame)
         pointclouds = self._map(pointclouds, live_frame, inplace)
         return pointclouds, live_frame.poses
+
+    def _filtered(self, live_frame: RGBDImages):
+        """the frame a step works on: the live frame itself, or its bilaterally filtered copy (`depth_filter`)"""
+        if self.depth_filter is None:
+            return live_frame
+        return live_frame.bilateral_filter(**self.depth_filter)
 
     def _localize(self, pointclouds: Pointclouds, live_frame: RGBDImages, prev_frame: RGBDImages):
         if not isinstance(pointclouds, Pointclouds):
@@ -163,6 +185,22 @@ class ICPSLAM(nn.Module):
 
     def _map(self, pointclouds: Pointclouds, live_frame: RGBDImages, inplace: bool = False):
         return update_map_aggregate(pointclouds, live_frame, inplace)
+
+
+def _check_depth_filter(depth_filter):
+    """None, or the complete keyword dict of RGBDImages.bilateral_filter (type and value checks of the constructor)."""
+    if depth_filter is None:
+        return None
+    if not isinstance(depth_filter, dict):
+        raise TypeError("depth_filter must be of type dict or None; but was of type {}.".format(type(depth_filter)))
+    full = dict(radius=3, sigma_space=2.0, sigma_range=0.03)
+    unknown = sorted(set(depth_filter) - set(full), key=str)
+    if unknown:
+        raise ValueError("depth_filter has unknown keys {}; expected a subset of {}.".format(unknown, sorted(full)))
+    full.update(depth_filter)
+    from .. import ops
+    ops._bilateral_args(**full)      # (the type and value checks of ops.bilateral_depth)
+    return full
 
 
 def _map_requires_grad(pointclouds):

@@ -2,7 +2,7 @@
 (slam/pointfusion.py:16-112): ICPSLAM odometry + surfel fusion map update."""
 import math
 import warnings
-from typing import Union
+from typing import Optional, Union
 
 import torch
 
@@ -21,16 +21,20 @@ class PointFusion(ICPSLAM):
     every `prune_every`-th step of a map first runs `pointclouds.prune_(prune_min_confidence, min_age=prune_min_age)`:
     surfels whose confidence count is still below the threshold `prune_min_age` steps after they were appended are
     removed (Keller et al.'s removal of points that stay unstable).  The step counter and the marks live with the map.
-    With `prune_min_confidence=None` a step makes none of these calls."""
+    With `prune_min_confidence=None` a step makes none of these calls.
+
+    Depth pre-filter (off by default): `depth_filter=dict(radius=..., sigma_space=..., sigma_range=...)` as in `ICPSLAM`:
+    the step -- fast path, generic path and `forward` alike -- works on the bilaterally filtered copy of the live frame
+    and writes the recovered pose back to the caller's frame."""
 
     def __init__(self, *, odom: str = "gradicp", dist_th: Union[float, int] = 0.05, angle_th: Union[float, int] = 20,
                  sigma: Union[float, int] = 0.6, dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0,
                  B: Union[float, int] = 1.0, B2: Union[float, int] = 1.0, nu: Union[float, int] = 200.0,
                  device: Union[torch.device, str, None] = None, prune_min_confidence: Union[float, int, None] = None,
-                 prune_min_age: int = 20, prune_every: int = 10):
+                 prune_min_age: int = 20, prune_every: int = 10, depth_filter: Optional[dict] = None):
         super().__init__(odom=odom, dsratio=dsratio, numiters=numiters, damp=damp, dist_thresh=dist_thresh,
-                         lambda_max=lambda_max, B=B, B2=B2, nu=nu, device=device)
+                         lambda_max=lambda_max, B=B, B2=B2, nu=nu, device=device, depth_filter=depth_filter)
         if not (isinstance(dist_th, float) or isinstance(dist_th, int)):
             raise TypeError("Distance threshold must be of type float or int; but was of type {}.".format(
                 type(dist_th)))
@@ -70,12 +74,18 @@ class PointFusion(ICPSLAM):
         # (slam/_fastpath.py: same kernels in the same order as _localize + _map below); anything else, and every
         # subclass that overrides _localize / _map, takes the generic path
         res = None
+        work = live_frame
+        if self.depth_filter is not None and isinstance(live_frame, RGBDImages):
+            work = self._filtered(live_frame)      # (filtered once, whichever path the step takes)
         if inplace and type(self) is PointFusion and isinstance(live_frame, RGBDImages) and \
                 isinstance(prev_frame, RGBDImages) and isinstance(pointclouds, Pointclouds):
             from ._fastpath import try_step
-            res = try_step(self, pointclouds, live_frame, prev_frame)
+            res = try_step(self, pointclouds, work, prev_frame)
         if res is None:
-            res = super().step(pointclouds, live_frame, prev_frame, inplace)
+            res = super().step(pointclouds, live_frame, prev_frame, inplace) if work is live_frame else \
+                self._step(pointclouds, work, prev_frame, inplace)
+        if work is not live_frame:
+            live_frame.poses = work.poses
         if self.prune_min_confidence is not None:
             self._end_step(pointclouds, res[0])
         return res

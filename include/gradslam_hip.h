@@ -667,6 +667,33 @@ GS_API int64_t gs_prune_scratch_bytes(int64_t n_bound);
 GS_API int gs_prune_map_dc_f32(const gs_prune_seq* seqs_host, int B, float min_confidence, int use_confidence,
                                void* stream);
 
+/* ------------------------------------------------------------------ bilateral depth filter ------
+ * The edge-preserving pre-pass on the raw depth of Keller et al. and KinectFusion (no counterpart in the reference),
+ * batched over n frames of H x W.  Frame f starts at depth + f * stride_frame and its row h at + h * stride_row (in
+ * elements; stride_row >= W, rows contiguous): a frame slice of a longer stack and a channels-first stack are read in
+ * place.  out (n, H, W) and the optional wsum (n, H, W) are contiguous.
+ * A pixel is valid when d > 0 (false for 0, negatives and NaN).  An invalid centre is copied through, wsum = 0.  For a
+ * valid centre q the window is visited in row-major order (dy = -radius..radius outer, dx inner, the centre in its
+ * place); a neighbour p outside the image or invalid is skipped, otherwise, in float32 with one rounding per operation,
+ *   g = alpha_of(dx, dy, 0, two_sigma_space_sq, eps 0)    e = alpha_of(d_p - d_q, 0, 0, two_sigma_range_sq, eps 0)
+ *   w = g * e    S = S + w * d_p    W = W + w,            out_q = S / W,  wsum_q = W
+ * with the specified exp of the alpha map.  two_sigma_*_sq = (float)(2 * sigma * sigma) evaluated in
+ * double by the caller; both must be finite and > 0.  radius 0 ... 8; radius 0 returns the input bits.  out / wsum must
+ * not overlap depth (GS_ERR_INVALID): blocks read each other's halo.  One launch per 65535 frames; every argument is
+ * checked before the first HIP call. */
+GS_API int gs_bilateral_depth_f32(const float* depth, int64_t stride_frame, int64_t stride_row, int n, int H, int W,
+                                  int radius, float two_sigma_space_sq, float two_sigma_range_sq, float* out,
+                                  float* wsum, void* stream);
+/* Reverse mode of the above: depth_bar (n, H, W) from out_bar (n, H, W), the forward's out and wsum and the depth it
+ * read.  A gather per input pixel in the window order of the forward, without atomics: bitwise reproducible.  Which
+ * neighbours are valid is a constant of the gradient; at an invalid pixel depth_bar = out_bar.  The weights w are the
+ * forward's float32 values, every other factor and both sums are float64, rounded once at the store.  depth_bar must
+ * not overlap an input. */
+GS_API int gs_bilateral_depth_backward_f32(const float* depth, int64_t stride_frame, int64_t stride_row,
+                                           const float* out, const float* wsum, const float* out_bar, int n, int H,
+                                           int W, int radius, float two_sigma_space_sq, float two_sigma_range_sq,
+                                           float* depth_bar, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
