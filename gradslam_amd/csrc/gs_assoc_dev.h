@@ -115,14 +115,19 @@ GS_DEV uint64_t gs_assoc_key(const float* __restrict__ points, const float* __re
   ray = ray + d2 * d2;
   return ((uint64_t)__float_as_uint(inv) << 32) | (uint64_t)__float_as_uint(ray);
 }
-// the same key with the pixel's global vertex f in registers
-GS_DEV uint64_t gs_assoc_key_v(const float* __restrict__ points, const float* __restrict__ ccounts, const float* f,
-                               int64_t n) {
-  const float inv = 1.0f / (ccounts[n] + 1e-20f);
+// the same key with the pixel's global vertex f in registers, as its two words: the high one needs the row's confidence
+// count alone, so a pass that only asks "does row n hold this key" (the merge of the one-call map update, which recomputes
+// the key instead of reading back a stored copy) can turn most losers away before it gathers the pixel's vertex
+GS_DEV uint32_t gs_assoc_key_hi(const float cc) { return __float_as_uint(1.0f / (cc + 1e-20f)); }
+GS_DEV uint32_t gs_assoc_key_lo_v(const float* __restrict__ points, const float* f, int64_t n) {
   const float d0 = points[3 * n] - f[0];
   const float d1 = points[3 * n + 1] - f[1];
   const float d2 = points[3 * n + 2] - f[2];
   float ray = d0 * d0 + d1 * d1;
   ray = ray + d2 * d2;
-  return ((uint64_t)__float_as_uint(inv) << 32) | (uint64_t)__float_as_uint(ray);
+  return __float_as_uint(ray);
+}
+GS_DEV uint64_t gs_assoc_key_v(const float* __restrict__ points, const float* __restrict__ ccounts, const float* f,
+                               int64_t n) {
+  return ((uint64_t)gs_assoc_key_hi(ccounts[n]) << 32) | (uint64_t)gs_assoc_key_lo_v(points, f, n);
 }

@@ -104,12 +104,16 @@ GS_DEV FrameLocalMaps frame_local_maps(const float* vertex, const float* normal,
   return f;
 }
 
-template <class Frame>
+// `cc` = ccounts[n], loaded by the caller.  HAVE_VERTEX: the caller already holds the global vertex of pixel p in `fv` (the
+// one-call update's winner test gathers it to rebuild the row's key) and it is not gathered a second time.
+// (ccounts[n] is stored even where cc + 0.0f leaves its bits alone: a store only for the rows whose count changes was
+// measured and saves nothing)
+template <bool HAVE_VERTEX = false, class Frame>
 GS_DEV void fuse_merge_row(float* __restrict__ points, float* __restrict__ normals, float* __restrict__ colors,
                            float* __restrict__ ccounts, const int64_t n, const int32_t p, const Frame& frame,
-                           const float* __restrict__ rgb, const float* __restrict__ alpha) {
+                           const float* __restrict__ rgb, const float* __restrict__ alpha, const float cc,
+                           const float* fv = nullptr) {
   const float a = p >= 0 ? alpha[p] : 0.0f;
-  const float cc = ccounts[n];
   float P[3], N[3], C[3], fp[3] = {0.0f, 0.0f, 0.0f}, fn[3] = {0.0f, 0.0f, 0.0f}, fc[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -118,7 +122,13 @@ GS_DEV void fuse_merge_row(float* __restrict__ points, float* __restrict__ norma
     C[k] = colors[3 * n + k];
   }
   if (p >= 0) {
-    frame((int64_t)p, fp, fn);
+    if (HAVE_VERTEX) {
+      frame.normal_of((int64_t)p, fn);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) fp[k] = fv[k];
+    } else {
+      frame((int64_t)p, fp, fn);
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) fc[k] = rgb[3 * (int64_t)p + k];
   }
@@ -154,7 +164,7 @@ __global__ void __launch_bounds__(256) gs_fuse_merge_kernel(
   if (*any_flag == 0 && renorm_all != 2) return;
   const int32_t p = pix_of[n];
   if (p < 0 && !renorm_all) return;
-  fuse_merge_row(points, normals, colors, ccounts, n, p, FrameGlobalMaps{gvertex, gnormal}, rgb, alpha);
+  fuse_merge_row(points, normals, colors, ccounts, n, p, FrameGlobalMaps{gvertex, gnormal}, rgb, alpha, ccounts[n]);
 }
 
 struct PredNewPixel {
@@ -419,6 +429,13 @@ extern "C" int gs_fuse_append_backward_f32(const float* points, const float* nor
 //   U4 per pixel : "any match" flag, count of new pixels per tile (a pixel is matched iff its key was written)
 //   U5 per surfel: winner test (key attained, and no lower-indexed row holds the pixel) + confidence-weighted merge
 //                  (parity mode rewrites every row); the winner writes best_pix                } one launch
+//      The key of a row is never stored: whoever asks whether row n attains the key of its pixel (U5, and the tie
+//      settling of U4) computes it again -- gs_assoc_key_hi / gs_assoc_key_lo_v on points[n], ccounts[n] and the pixel's
+//      global vertex, the very functions and inputs of U2, hence the very bits.  Those inputs are still what U2 saw: the
+//      frame does not change during an update, and a map row is written by ONE thread only, the thread of the merge
+//      launch that owns it, after that thread's own reads (appended rows lie behind n_map and take no part).  The only
+//      pass in which a thread reads rows other than by that ownership is the tie settling, and it runs in the launch
+//      BEFORE the merge; within the merge launch no thread reads another thread's row.
 //   U6 per pixel : ordered append of the new pixels; every block derives its output offset from the tile
 //                  counts itself (no separate scan launch); block 0 also writes the new surfel count
 constexpr int32_t MU_TIE_MARK = 0x7fffffff;   // best_pix of a pixel with two rows of the same key, until settled
@@ -435,7 +452,6 @@ struct MuSeq {
   int32_t* any_flag;
   uint64_t* key_pix;
   int32_t* tile_counts;
-  uint64_t* key_pt;
   int32_t* pix;
   int32_t* pix_of;
 };
@@ -482,8 +498,8 @@ __global__ void __launch_bounds__(256) gs_mu_project_key_kernel(const MuBatch mb
   const GsCamera c = gs_camera(q.pose16, q.K16);
   const int32_t p = gs_project_point(c, q.points[3 * n], q.points[3 * n + 1], q.points[3 * n + 2], mb.H, mb.W, mb.u_hi,
                                      mb.v_hi);
-  // pix[n] = the pixel this row competes for, or -1 (not in the frame, or not similar to the pixel): the pick pass
-  // then reads 4 bytes of most rows instead of 12, and the key is only stored for the rows that have one
+  // pix[n] = the pixel this row competes for, or -1 (not in the frame, or not similar to the pixel): all the merge needs
+  // to know of this pass (it rebuilds the key of a competing row from the row itself, see U5 above)
   int32_t pk = -1;
   if (p >= 0) {
     // the pixel's global vertex / normal: materialised by the pixel pass, or computed here (MuSeq::gvertex == NULL: the
@@ -502,7 +518,6 @@ __global__ void __launch_bounds__(256) gs_mu_project_key_kernel(const MuBatch mb
         q.best_pix[p] = MU_TIE_MARK;
         q.any_flag[1] = 1;   // benign race: every writer stores the same value
       }
-      q.key_pt[n] = k;
       pk = p;
     }
   }
@@ -518,7 +533,10 @@ GS_DEV void mu_settle_ties(const MuSeq& q, const unsigned blk, const unsigned nb
   for (int64_t n = (int64_t)blk * GS_CP_BLOCK + threadIdx.x; n < n_map; n += (int64_t)nblk * GS_CP_BLOCK) {
     const int32_t p = q.pix[n];
     if (p < 0 || q.best_pix[p] == -1) continue;   // (-1: unmarked pixel -- its key has one holder)
-    if (q.key_pt[n] == q.key_pix[p]) atomicMin(reinterpret_cast<unsigned*>(&q.best_pix[p]), (unsigned)n);
+    float fp[3];
+    if (q.gvertex) FrameGlobalMaps{q.gvertex, q.gnormal}.vertex_of((int64_t)p, fp);
+    else frame_local_maps(q.vertex, q.normal, q.pose16).vertex_of((int64_t)p, fp);
+    if (gs_assoc_key_v(q.points, q.ccounts, fp, n) == q.key_pix[p]) atomicMin(reinterpret_cast<unsigned*>(&q.best_pix[p]), (unsigned)n);
   }
 }
 
@@ -558,6 +576,31 @@ __global__ void __launch_bounds__(GS_CP_BLOCK) gs_mu_winner_count_kernel(const M
   mu_settle_ties(q, blk, gridDim.x / mb.B);
 }
 
+template <class Frame>
+GS_DEV void mu_merge_row(const MuBatch& mb, const MuSeq& q, const int64_t n, const Frame& frame) {
+  // the pixel this row competes for; it wins iff it attains the pixel's key and no lower-indexed row with the same key
+  // holds the pixel (best_pix: -1 = the key has one holder, else the settled holder).  The row's key is computed again
+  // (see U5 above), high word first: it needs nothing but ccounts[n], which the merge loads anyway, and almost every row
+  // that lost its pixel lost it on confidence.  Only a row that ties the high word gathers the pixel's vertex for the low
+  // word -- and, if it wins, hands that vertex on to the merge.
+  int32_t p = q.pix[n];
+  const float cc = q.ccounts[n];
+  float fp[3] = {0.0f, 0.0f, 0.0f};
+  if (p >= 0) {
+    const uint64_t kp = q.key_pix[p];
+    bool win = (uint32_t)(kp >> 32) == gs_assoc_key_hi(cc);
+    if (win) {   // (only the holders of the key act on the entry: an unmarked pixel's has one reader and writer)
+      frame.vertex_of((int64_t)p, fp);
+      const int32_t bp = q.best_pix[p];
+      win = (uint32_t)kp == gs_assoc_key_lo_v(q.points, fp, n) && (bp == -1 || bp == (int32_t)n);
+      if (win && bp == -1) q.best_pix[p] = (int32_t)n;
+    }
+    if (!win) p = -1;
+  }
+  if (p < 0 && !mb.renorm_all) return;
+  fuse_merge_row<true>(q.points, q.normals, q.colors, q.ccounts, n, p, frame, q.rgb, q.alpha, cc, fp);
+}
+
 GS_DEV void mu_merge_body(const MuBatch& mb, const unsigned bid) {
   const MuSeq& q = mb.s[bid % mb.B];
   const int64_t n = (int64_t)(bid / mb.B) * 256 + threadIdx.x;
@@ -566,21 +609,8 @@ GS_DEV void mu_merge_body(const MuBatch& mb, const unsigned bid) {
   // (pc2im_bnhw.shape[0] != 0 is a batch-level test): a sequence without matches is still renormalised when
   // another sequence of the same call has some
   if (*mb.call_flag == 0) return;
-  // the pixel this row competes for; it wins iff it attains the pixel's key and no lower-indexed row with the same key
-  // holds the pixel (best_pix: -1 = the key has one holder, else the settled holder)
-  int32_t p = q.pix[n];
-  if (p >= 0) {
-    bool win = q.key_pt[n] == q.key_pix[p];
-    if (win) {   // (only the holders of the key look at the entry: an unmarked pixel's has one reader and writer)
-      const int32_t bp = q.best_pix[p];
-      win = bp == -1 || bp == (int32_t)n;
-      if (win && bp == -1) q.best_pix[p] = (int32_t)n;
-    }
-    if (!win) p = -1;
-  }
-  if (p < 0 && !mb.renorm_all) return;
-  if (q.gvertex) fuse_merge_row(q.points, q.normals, q.colors, q.ccounts, n, p, FrameGlobalMaps{q.gvertex, q.gnormal}, q.rgb, q.alpha);
-  else fuse_merge_row(q.points, q.normals, q.colors, q.ccounts, n, p, frame_local_maps(q.vertex, q.normal, q.pose16), q.rgb, q.alpha);
+  if (q.gvertex) mu_merge_row(mb, q, n, FrameGlobalMaps{q.gvertex, q.gnormal});
+  else mu_merge_row(mb, q, n, frame_local_maps(q.vertex, q.normal, q.pose16));
 }
 
 // ordered append without a scan launch: block b adds up the counts of the tiles before it (fixed order)
@@ -655,7 +685,6 @@ __global__ void __launch_bounds__(256) gs_mu_merge_append_kernel(const MuBatch m
 extern "C" int64_t gs_update_map_scratch_bytes(int64_t n_map_bound, int H, int W) {
   const int64_t P = (int64_t)H * W;
   return (int64_t)(256 + gs_align(8 * (size_t)P) + gs_align(4 * (size_t)gs_cp_tiles(P)) +
-                   gs_align(8 * (size_t)(n_map_bound > 0 ? n_map_bound : 1)) +
                    2 * gs_align(4 * (size_t)(n_map_bound > 0 ? n_map_bound : 1)) + 4096);
 }
 
@@ -694,13 +723,13 @@ static int update_chunk(const gs_update_seq* seqs, int B, int H, int W, float di
     m.any_flag = reinterpret_cast<int32_t*>(q); q += 256;
     m.key_pix = reinterpret_cast<uint64_t*>(q); q += gs_align(8 * (size_t)mb.P);
     m.tile_counts = reinterpret_cast<int32_t*>(q); q += gs_align(4 * (size_t)mb.ntiles);
-    m.key_pt = reinterpret_cast<uint64_t*>(q); q += gs_align(8 * (size_t)(n_map > 0 ? n_map : 1));
     m.pix = reinterpret_cast<int32_t*>(q); q += gs_align(4 * (size_t)(n_map > 0 ? n_map : 1));
     m.pix_of = reinterpret_cast<int32_t*>(q);
-    // as built: projection 28 B read + 12 B written (+ 24 B frame gather and 8 B key per competing row); merge 4 + 80 B per
-    // row (+ 20 B of keys / winner entry per competing row), 49 B per pixel for the winner count and the append
-    bytes_assoc += 72.0 * (double)n_map;
-    bytes_fuse += 104.0 * (double)n_map + 49.0 * (double)mb.P;
+    // as built: projection 28 B read + 4 B written (+ 24 B frame gather and 8 B key per competing row); merge 4 + 80 B per
+    // row (+ 12 B of key / winner entry per competing row; the vertex gathered for the low word of the key is the one a
+    // winner gathers for the merge anyway), 49 B per pixel for the winner count and the append
+    bytes_assoc += 64.0 * (double)n_map;
+    bytes_fuse += 96.0 * (double)n_map + 49.0 * (double)mb.P;
   }
   const unsigned uB = (unsigned)B;
   const unsigned pb = uB * (unsigned)gs_ceil_div(mb.P, 256), nb = uB * (unsigned)gs_ceil_div(n_max > 0 ? n_max : 1, 256);

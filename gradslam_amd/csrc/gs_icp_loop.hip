@@ -1448,7 +1448,7 @@ __global__ void __launch_bounds__(FAR_BLOCK) gs_icp_far_build_kernel(const FarBu
 
 static int64_t loc_rows(const gs_map_view& m) { return m.capacity > m.n_bound ? m.capacity : m.n_bound; }
 
-// Scratch of one sequence of the batched localisation as byte offsets from its start: lattice | pix | n_valid | the solve's
+// Scratch of one sequence of the batched localisation as byte offsets from its start: lattice | n_valid | the solve's
 // scratch (IcpLayout sc, counted from `icp`; it holds the grid) | lists of ordinary queries (ListMem) | lists of far queries,
 // or the wide lists of hard ones (FarMem) + result words.  The ONE description of it: gs_localize_scratch_bytes returns its
 // total, loc_carve applies it to a base pointer.  `rows` is the map's CAPACITY (what the scratch was sized for), not the count
@@ -1457,14 +1457,13 @@ static int64_t loc_rows(const gs_map_view& m) { return m.capacity > m.n_bound ? 
 struct LocLayout {
   int64_t n_lat, rows;
   IcpLayout sc;
-  size_t lattice, pix, n_valid, icp, lq, ls, lstat, far_c, far_cq, far_idx, far_n, far_out4, total;
+  size_t lattice, n_valid, icp, lq, ls, lstat, far_c, far_cq, far_idx, far_n, far_out4, total;
 };
 static LocLayout loc_layout(int64_t n_lat, int64_t rows) {
   GsTake take;
   LocLayout L;
   L.n_lat = n_lat; L.rows = rows > 0 ? rows : 1;
   L.lattice = take(gs_align(12 * (size_t)n_lat));
-  L.pix = take(gs_align(4 * (size_t)L.rows));
   L.n_valid = take(256);
   L.sc = icp_layout(n_lat, L.rows);
   L.icp = take(L.sc.total);
@@ -1492,13 +1491,13 @@ extern "C" int64_t gs_localize_scratch_bytes(int H, int W, int ds, int64_t n_map
 }
 
 struct LocCarve {
-  float* lattice; int32_t* pix; int64_t* n_valid;
+  float* lattice; int64_t* n_valid;
   IcpScratch sc; GridMem gm; ListMem lm;
   FarMem fm; int* far_out4;   // the far lists, or the wide lists whenever those are not in use; the stats result words
 };
 static LocCarve loc_carve(void* p, const LocLayout& L) {
   const IcpScratch sc = icp_carve(gs_at<char>(p, L.icp), L.sc);
-  return LocCarve{gs_at<float>(p, L.lattice), gs_at<int32_t>(p, L.pix), gs_at<int64_t>(p, L.n_valid), sc,
+  return LocCarve{gs_at<float>(p, L.lattice), gs_at<int64_t>(p, L.n_valid), sc,
                   grid_carve(sc.grid, L.n_lat, L.rows),
                   ListMem{gs_at<float4>(p, L.lq), gs_at<uint32_t>(p, L.ls), gs_at<int>(p, L.lstat)},
                   FarMem{gs_at<uint32_t>(p, L.far_c), gs_at<float4>(p, L.far_cq), gs_at<int>(p, L.far_idx), gs_at<int>(p, L.far_n)},
@@ -1584,6 +1583,7 @@ struct IcpSolveView {
 static void loc_bind(const gs_localize_seq* seqs, int B, int H, int W, int ds, const gs_icp_params* prm,
                      const IcpEnginePlan& plan, LocCarve* c, LocBatch& lb, GsGridBatch& gb, IcpSolveView* v) {
   lb.B = gb.B = B; lb.W = gb.W = W; gb.H = H; lb.ds = gb.ds = ds;
+  gb.listed = 1;   // the ICP targets are the map rows that project onto the lattice under the previous pose
   lb.Wl = (W + ds - 1) / ds; lb.n_lat = loc_lattice(H, W, ds); lb.damp = prm->damp; lb.numiters = prm->numiters;
   gb.cells_cap = gs_knn_grid_cells_cap(lb.n_lat);
   for (int b = 0; b < B; ++b) {
@@ -1593,7 +1593,7 @@ static void loc_bind(const gs_localize_seq* seqs, int B, int H, int W, int ds, c
     lb.s[b] = LocSeq{q.vertex, q.depth, q.prev_pose16, c[b].lattice, c[b].sc.state, q.out_pose16,
                      reinterpret_cast<char*>(c[b].gm.g), c[b].n_valid, c[b].fm.n, c[b].lm.stat,
                      plan.wide_on ? c[b].fm.cq : nullptr, c[b].sc.sync};
-    gb.s[b] = GsGridSeq{q.map.points, GsCount{q.map.n_bound, q.map.n_dev}, c[b].pix, q.prev_pose16, q.K16,
+    gb.s[b] = GsGridSeq{q.map.points, GsCount{q.map.n_bound, q.map.n_dev}, nullptr, q.prev_pose16, q.K16,
                         plan.binned_normals ? q.map.normals : nullptr, c[b].gm};
     v[b] = IcpSolveView{c[b].lattice, q.map.points, q.map.normals, GsCount{q.map.n_bound, q.map.n_dev}, c[b].sc, c[b].gm,
                         nullptr, TapePtrs{nullptr, nullptr, nullptr},
@@ -1615,8 +1615,10 @@ static int loc_prep(const gs_localize_seq* seqs, const LocBatch& lb, const GsGri
     for (int b = 0; b < B; ++b) GS_HIP(hipMemsetAsync(lb.s[b].n_valid, 0, 8, st));
   const unsigned nb_lat = (unsigned)gs_ceil_div(lb.n_lat, 256);
   const unsigned nb_clear = (unsigned)gs_ceil_div((int64_t)(lb.clear_bytes / 16), 256 * LP_CLEAR_ITEMS);
-  double bytes = 0.0;  // lattice 28 B per slot; projection 16 B + two filter passes 4 B per map row; cell table
-  for (int b = 0; b < B; ++b) bytes += 28.0 * lb.n_lat + 24.0 * seqs[b].map.n_bound + 16.0 * gb.cells_cap;
+  // lattice 28 B per slot; projection 12 B read per map row (it is not stored: the count and scatter passes walk the list of
+  // the rows that passed, which the 16 B per cell below more than cover); cell table
+  double bytes = 0.0;
+  for (int b = 0; b < B; ++b) bytes += 28.0 * lb.n_lat + 12.0 * seqs[b].map.n_bound + 16.0 * gb.cells_cap;
   GsProf prof(GS_PROF_COMPACT, bytes, st, grid_cleared ? 4 : 5);
   if (grid_cleared) {
     const float u_hi = (float)((double)gb.W - 0.999), v_hi = (float)((double)gb.H - 0.999);   // (as gs_knn_grid_build_batch)
@@ -1754,7 +1756,7 @@ static int icp_run(const float* src, int64_t n_src, const float* tgt, const floa
                    int64_t n_tgt, const float* init16, const float* compose16,
                    const gs_icp_params* prm, float* out_T16, int64_t* out_idx, void* icp_scratch,
                    void* tape, void* stream, const int64_t* n_src_dev = nullptr,
-                   const int64_t* n_tgt_dev = nullptr, GsTargetFilter flt = GsTargetFilter{nullptr, 1, 1}) {
+                   const int64_t* n_tgt_dev = nullptr, GsTargetFilter flt = GsTargetFilter{nullptr, 1, 1, 0}) {
   GS_REQUIRE(prm, "params_host must not be NULL");
   GS_REQUIRE(n_src > 0 && n_tgt > 0, "empty point set");
   GS_REQUIRE(n_tgt < 0x7fffffffll && n_src < 0x7fffffffll, "too many points");
@@ -1765,7 +1767,7 @@ static int icp_run(const float* src, int64_t n_src, const float* tgt, const floa
   hipLaunchKernelGGL(gs_icp_init_kernel, dim3(1), dim3(64), 0, st, sc.state, init16, prm->damp, prm->numiters,
                      compose16, out_T16);
   // device-side counts (n_src / n_tgt are then upper bounds) always take the grid path
-  const bool dev_counts = n_src_dev || n_tgt_dev || flt.pix;  // a target filter exists only in the grid path
+  const bool dev_counts = n_src_dev || n_tgt_dev || flt.listed;  // a target filter exists only in the grid path
   const bool use_grid = prm->numiters > 0 && (dev_counts || (!gs_env().knn_brute && gs_knn_use_grid(n_src, n_tgt)));
   const GsCount n_src_c{n_src, n_src_dev}, n_tgt_c{n_tgt, n_tgt_dev};
   TapePtrs tp = {nullptr, nullptr, nullptr};
@@ -1789,7 +1791,7 @@ static int icp_run(const float* src, int64_t n_src, const float* tgt, const floa
     double prof_bytes = 0.0;
     if (g_gs_prof_on) {
       int64_t n_binned = n_tgt;
-      if (flt.pix) {
+      if (flt.listed) {
         unsigned hits = 0;
         GS_HIP(hipMemcpyAsync(&hits, v.gm.bbox + 6, 4, hipMemcpyDeviceToHost, st));
         GS_HIP(hipStreamSynchronize(st));
@@ -1870,7 +1872,7 @@ extern "C" int gs_icp_map_dc_f32(const float* src, int64_t n_src_bound, const in
                                  void* icp_scratch, void* stream) {
   GS_REQUIRE(pix && W > 0 && ds > 0, "bad target filter");
   return icp_run(src, n_src_bound, map_points, map_normals, n_map_bound, init16, compose16, prm, out_T16, nullptr,
-                 icp_scratch, nullptr, stream, n_src_dev, n_map_dev, GsTargetFilter{pix, W, ds});
+                 icp_scratch, nullptr, stream, n_src_dev, n_map_dev, GsTargetFilter{pix, W, ds, 1});
 }
 
 static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int ds, const gs_icp_params* prm,

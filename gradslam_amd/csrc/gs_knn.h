@@ -34,9 +34,13 @@ struct GsGrid {
 // lands on the [::ds, ::ds] pixel lattice (the selection of gs_select_targets_f32, evaluated in place: the
 // ICP target set of the SLAM loop is then never gathered into a compact array; candidate keys carry the
 // map row index, whose order is the order of the compacted set, so ties break identically).
+// `listed` says that the build is a FILTERED one: its bbox pass compacts the rows that pass into GridMem::tlist and the count
+// and scatter passes walk that list.  It is a flag of its own, not "pix != NULL": a bbox pass that projects the rows itself
+// (GsGridSeq::pose16) filters on the value in registers and need not store pix at all.
 struct GsTargetFilter {
   const int32_t* pix;
   int W, ds;
+  int listed;
 };
 GS_DEV bool gs_is_target(const GsTargetFilter& f, int64_t n) {
   if (!f.pix) return true;
@@ -84,14 +88,15 @@ size_t gs_knn_grid_scratch_bytes(int64_t n_src, int64_t n_tgt);
 struct GsGridSeq {
   const float* tgt;      // target rows (the whole map when a filter is given)
   GsCount n_tgt;
-  int32_t* pix;          // target filter (with W, ds of the batch); when pose16 != NULL it is WRITTEN first:
-  const float* pose16;   //   pix[n] = projection of row n under (pose16, K16) (gs_project_map_f32)
-  const float* K16;
+  int32_t* pix;          // target filter (with W, ds of the batch); when pose16 != NULL it is an OUTPUT:
+  const float* pose16;   //   pix[n] = projection of row n under (pose16, K16) (gs_project_map_f32), or NULL: the projection is
+  const float* K16;      //   used by the bbox pass alone and never stored (the batched localisation: nothing reads it again)
   const float* nrm;      // normals of the target rows (NULL: none): binned next to the points (m.sorted_n)
   GridMem m;             // grid_carve(scratch, n_src, n_tgt.host)
 };
 struct GsGridBatch {
   int B, H, W, ds;
+  int listed;            // filtered build (GsTargetFilter::listed) of every sequence
   int cells_cap;
   GsGridSeq s[GS_MAX_BATCH];
 };
@@ -105,7 +110,7 @@ size_t gs_knn_grid_clear_bytes(const GridMem& m, int cells_cap);
 int gs_knn_grid_build_batch(const GsGridBatch& gb, hipStream_t st, bool bbox_done = false);
 
 int gs_knn_grid_build(const float* tgt, GsCount n_tgt, int64_t n_src, void* grid_scratch, hipStream_t st,
-                      GsTargetFilter filter = GsTargetFilter{nullptr, 1, 1}, const float* nrm = nullptr);
+                      GsTargetFilter filter = GsTargetFilter{nullptr, 1, 1, 0}, const float* nrm = nullptr);
 int gs_knn_grid_query(const float* src_in, const float* Tapply, float* src_out, int64_t n_src,
                       const float* tgt, int64_t n_tgt, unsigned long long* best, void* grid_scratch,
                       hipStream_t st);

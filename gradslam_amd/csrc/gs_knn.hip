@@ -186,7 +186,7 @@ GS_DEV void grid_count_body(const float* __restrict__ tgt, const int64_t n_tgt, 
                             const unsigned blk, const unsigned nblk) {
   __shared__ GsGrid gsh;
   __shared__ int th[GS_GRID_MAXCELL / GS_GRID_TILE + 1];
-  const int64_t n_items = flt.pix ? (int64_t)bbox[6] : n_tgt;   // filtered build: the compacted list of the bbox pass
+  const int64_t n_items = flt.listed ? (int64_t)bbox[6] : n_tgt;   // filtered build: the compacted list of the bbox pass
   if ((int64_t)blk * 256 >= n_items && blk != 0) return;
   if (threadIdx.x == 0) {
     gsh = grid_from_bbox(bbox, n_items, cells_cap);
@@ -197,7 +197,7 @@ GS_DEV void grid_count_body(const float* __restrict__ tgt, const int64_t n_tgt, 
   const int ntile = g.ncell / GS_GRID_TILE + 1;
   for (int t = threadIdx.x; t < ntile; t += 256) th[t] = 0;
   __syncthreads();
-  if (flt.pix) {
+  if (flt.listed) {
     for (int64_t i = (int64_t)blk * 256 + threadIdx.x; i < n_items; i += (int64_t)nblk * 256) {
       const float4 t = tlist[i];
       const int cid = grid_cell(g, t.x, t.y, t.z);
@@ -266,7 +266,7 @@ GS_DEV void grid_scatter_body(const float* __restrict__ tgt, const int64_t n_tgt
                               const float4* __restrict__ tlist, const unsigned* __restrict__ bbox,
                               const float* __restrict__ nrm, float4* __restrict__ sorted_n, const unsigned blk,
                               const unsigned nblk) {
-  if (flt.pix) {
+  if (flt.listed) {
     const int64_t n_list = (int64_t)bbox[6];
     if ((int64_t)blk * 256 >= n_list) return;
     const GsGrid g = *gp;
@@ -313,7 +313,7 @@ __global__ void __launch_bounds__(GB_BLOCK) gs_gridb_bbox_kernel(const GsGridBat
 }
 __global__ void __launch_bounds__(256) gs_gridb_count_kernel(const GsGridBatch gb) {
   const GsGridSeq& q = gb.s[blockIdx.x % gb.B];
-  grid_count_body(q.tgt, gs_count(q.n_tgt), GsTargetFilter{q.pix, gb.W, gb.ds}, q.m.bbox, q.m.g, q.m.cell_count,
+  grid_count_body(q.tgt, gs_count(q.n_tgt), GsTargetFilter{q.pix, gb.W, gb.ds, gb.listed}, q.m.bbox, q.m.g, q.m.cell_count,
                   q.m.tile_sums, gb.cells_cap, q.m.tlist, blockIdx.x / gb.B, gridDim.x / gb.B);
 }
 __global__ void __launch_bounds__(256) gs_gridb_scan_kernel(const GsGridBatch gb) {
@@ -322,7 +322,7 @@ __global__ void __launch_bounds__(256) gs_gridb_scan_kernel(const GsGridBatch gb
 }
 __global__ void __launch_bounds__(256) gs_gridb_scatter_kernel(const GsGridBatch gb) {
   const GsGridSeq& q = gb.s[blockIdx.x % gb.B];
-  grid_scatter_body(q.tgt, gs_count(q.n_tgt), GsTargetFilter{q.pix, gb.W, gb.ds}, q.m.g, q.m.cell_start, q.m.cell_count,
+  grid_scatter_body(q.tgt, gs_count(q.n_tgt), GsTargetFilter{q.pix, gb.W, gb.ds, gb.listed}, q.m.g, q.m.cell_start, q.m.cell_count,
                     q.m.sorted, q.m.tlist, q.m.bbox, q.nrm, q.m.sorted_n, blockIdx.x / gb.B, gridDim.x / gb.B);
 }
 
@@ -353,8 +353,7 @@ int gs_knn_grid_build_batch(const GsGridBatch& gb, hipStream_t st, bool bbox_don
   if (!bbox_done)   // (else the caller ran gridb_bbox_block for gs_knn_gridb_bbox_blocks(gb) blocks in a launch of its own)
     hipLaunchKernelGGL(gs_gridb_bbox_kernel, dim3(gs_knn_gridb_bbox_blocks(gb)), dim3(GB_BLOCK), 0, st, gb, u_hi, v_hi);
   // filtered builds walk the compacted target list (a few entries per lattice slot) with a grid-stride loop
-  bool listed = true;
-  for (int b = 0; b < gb.B; ++b) listed = listed && gb.s[b].pix != nullptr;
+  const bool listed = gb.listed != 0;
   const int64_t slots = (int64_t)gs_ceil_div(gb.H, gb.ds) * gs_ceil_div(gb.W, gb.ds);
   unsigned nb_pts = (unsigned)gs_ceil_div(n_max, 256);
   if (listed && gb.H > 0 && (unsigned)gs_ceil_div(3 * slots, 256) < nb_pts) nb_pts = (unsigned)gs_ceil_div(3 * slots, 256);

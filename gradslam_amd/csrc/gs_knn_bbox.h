@@ -18,8 +18,8 @@ GS_DEV float grid_decode(unsigned c) {
 constexpr int GB_BLOCK = 256;
 constexpr int GB_ITEMS = 8;
 // Body shared by the single-sequence and the batched kernels (blk = block index within the sequence).
-// cam != NULL: pix[] is an OUTPUT (projection of every row under the camera, gs_project_map_f32) and the
-// filter is evaluated on the value just computed.
+// cam != NULL: the filter is evaluated on the projection of every row under the camera (gs_project_map_f32), computed
+// here; pix_out[] receives it unless it is NULL (a caller that has no other reader of it saves 4 B per map row).
 GS_DEV void grid_bbox_body(const float* __restrict__ tgt, const int64_t n_tgt, const GsTargetFilter flt,
                            const GsCamera* cam, int H, float u_hi, float v_hi, int32_t* __restrict__ pix_out,
                            unsigned* __restrict__ bbox, int* __restrict__ unres_count, float4* __restrict__ tlist,
@@ -49,7 +49,7 @@ GS_DEV void grid_bbox_body(const float* __restrict__ tgt, const int64_t n_tgt, c
       if (i < n_tgt) {
         int ph = 0, pw = 0;
         const bool in = gs_project_point_hw(*cam, v[u][0], v[u][1], v[u][2], H, flt.W, u_hi, v_hi, ph, pw);
-        pix_out[i] = in ? (int32_t)(ph * flt.W + pw) : -1;
+        if (pix_out) pix_out[i] = in ? (int32_t)(ph * flt.W + pw) : -1;
         // lattice test on (h, w) directly: dividing the flat index by run-time W and ds again was most of this pass's
         // instructions, and the pass is VALU-bound (SQ counters: 77 VALU instructions per row at 4 cycles per wave64)
         if (in && gs_on_lattice(ph, pw, flt.ds)) {
@@ -113,9 +113,8 @@ GS_DEV void grid_bbox_body(const float* __restrict__ tgt, const int64_t n_tgt, c
     }
     if (lane == 0) { red[k][wave] = a; red[3 + k][wave] = b; }
   }
-  const bool filtered = flt.pix != nullptr || cam != nullptr;
   __syncthreads();
-  if (filtered) {
+  if (flt.listed) {
     // the rows that passed the filter (a few per cent of a map) are compacted into tlist: the count and scatter
     // passes then walk that list instead of the map.  One atomic per block hands out the slots (bbox[6] is also the
     // number of targets the cell-size heuristic needs); the order of the list does not matter (see the scatter).
@@ -155,7 +154,7 @@ GS_DEV void grid_bbox_body(const float* __restrict__ tgt, const int64_t n_tgt, c
 GS_DEV void gridb_bbox_block(const GsGridBatch& gb, const unsigned bid, float u_hi, float v_hi) {
   const GsGridSeq& q = gb.s[bid % gb.B];
   const unsigned blk = bid / gb.B;
-  const GsTargetFilter flt{q.pix, gb.W, gb.ds};
+  const GsTargetFilter flt{q.pix, gb.W, gb.ds, gb.listed};
   if (q.pose16) {
     const GsCamera cam = gs_camera(q.pose16, q.K16);
     grid_bbox_body(q.tgt, gs_count(q.n_tgt), flt, &cam, gb.H, u_hi, v_hi, q.pix, q.m.bbox, q.m.unres_count, q.m.tlist,
