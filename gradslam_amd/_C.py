@@ -82,6 +82,18 @@ class PruneSeq(C.Structure):
                 ("n_out", C.c_void_p), ("removed_out", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class PicpSeq(C.Structure):
+    """gs_picp_seq: one live frame, the model view's index image and the map for the projective ICP."""
+    _fields_ = [("vertex", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("K16", C.c_void_p),
+                ("index", C.c_void_p), ("model_pose16", C.c_void_p), ("map", MapView), ("init_pose16", C.c_void_p),
+                ("out_pose16", C.c_void_p), ("trace", C.c_void_p), ("scratch", C.c_void_p)]
+
+
+class PicpParams(C.Structure):
+    _fields_ = [("stride", C.c_int), ("numiters", C.c_int), ("damp", C.c_float), ("dist_th", C.c_float),
+                ("dot_th", C.c_float)]
+
+
 # name -> argtypes (return type is int unless listed in _RESTYPE)
 _PROTOS = {
     "gs_abi_version": [],
@@ -169,12 +181,15 @@ _PROTOS = {
     "gs_prune_map_dc_f32": [C.POINTER(PruneSeq), _i32, _f, _i32, _vp],
     "gs_bilateral_depth_f32": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _f, _f, _vp, _vp, _vp],
     "gs_bilateral_depth_backward_f32": [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f, _f, _vp, _vp],
+    "gs_projective_icp_scratch_bytes": [_i32, _i32, _i32],
+    "gs_projective_icp_batch_f32": [C.POINTER(PicpSeq), _i32, _i32, _i32, C.POINTER(PicpParams), _vp],
+    "gs_projective_icp_rows_f32": [C.POINTER(PicpSeq), _i32, _i32, _i32, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,
             "gs_knn1_grid_scratch_bytes": _i64, "gs_update_map_scratch_bytes": _i64, "gs_global_maps_pose_backward_scratch_bytes": _i64, "gs_icp_tape_bytes": _i64, "gs_icp_backward_scratch_bytes": _i64,
             "gs_localize_scratch_bytes": _i64, "gs_frame_maps_backward_kbar_scratch_bytes": _i64,
             "gs_render_scratch_bytes": _i64, "gs_render_backward_scratch_bytes": _i64,
-            "gs_prune_scratch_bytes": _i64}
+            "gs_prune_scratch_bytes": _i64, "gs_projective_icp_scratch_bytes": _i64}
 EXPORTS = tuple(_PROTOS)
 
 

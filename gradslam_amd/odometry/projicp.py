@@ -1,0 +1,87 @@
+"""ProjectiveICPOdometryProvider: frame-to-model tracking by projective data association (Keller et al., KinectFusion;
+the reference has no counterpart).  The map is rendered at the previous pose (gs_render_map_dc_f32), every lattice pixel
+of the live frame is paired with the surfel that won the pixel it projects to under the current estimate, and
+point-to-plane Gauss-Newton steps with constant damping follow (gs_projective_icp_batch_f32) -- no nearest-neighbour
+search.  The result is detached: there is no backward pass."""
+from typing import Optional, Union
+
+import torch
+
+from ..structures.pointclouds import Pointclouds
+from ..structures.rgbdimages import RGBDImages
+from .base import OdometryProvider
+
+__all__ = ["ProjectiveICPOdometryProvider"]
+
+
+class ProjectiveICPOdometryProvider(OdometryProvider):
+    r"""Projective-association point-to-plane ICP against the model view.
+
+    Args:
+        numiters: Gauss-Newton iterations
+        damp: constant damping added to the diagonal of the normal equations (> 0)
+        dist_thresh: a pair is used when the transformed live vertex is within this many metres of the surfel ...
+        angle_thresh: ... and their normals are within this many degrees (0..90)
+        stride: the live frame's [::stride, ::stride] lattice is the source set (None: every pixel)
+        min_confidence, radius: forwarded to the render of the model view (`Pointclouds.render`)
+
+    Unlike the point-cloud-pair providers it needs the map and the live frame themselves: call
+    `localize(pointclouds, live_frame, prev_poses)`."""
+
+    def __init__(self, numiters: int = 10, damp: float = 1e-8, dist_thresh: Union[float, int] = 0.1,
+                 angle_thresh: Union[float, int] = 30, stride: Optional[int] = None,
+                 min_confidence: Union[float, int] = 0.0, radius: int = 0):
+        from .. import ops
+        ops._picp_args(1 if stride is None else stride, numiters, damp, dist_thresh, angle_thresh)
+        self.numiters = numiters
+        self.damp = damp
+        self.dist_thresh = dist_thresh
+        self.angle_thresh = angle_thresh
+        self.stride = stride
+        self.min_confidence = min_confidence
+        self.radius = radius
+
+    def _kwargs(self):
+        return dict(stride=1 if self.stride is None else self.stride, numiters=self.numiters, damp=self.damp,
+                    dist_thresh=self.dist_thresh, angle_thresh=self.angle_thresh)
+
+    def provide(self, *args, **kwargs):
+        raise TypeError("ProjectiveICPOdometryProvider aligns a live frame with the rendered map, not two point clouds: "
+                        "call localize(pointclouds, live_frame, prev_poses)")
+
+    def localize(self, pointclouds: Pointclouds, live_frame: RGBDImages, prev_poses: torch.Tensor) -> torch.Tensor:
+        r"""Poses (B, 1, 4, 4) of `live_frame` (B sequences, one frame each) against the map `pointclouds`, starting from
+        `prev_poses` (B, 1, 4, 4) or (B, 4, 4), at which the model view is rendered.  The map is read in place; counts
+        that live on the device stay there."""
+        if not isinstance(pointclouds, Pointclouds):
+            raise TypeError("Expected pointclouds to be of type gradslam.Pointclouds. Got {0}.".format(type(pointclouds)))
+        if not isinstance(live_frame, RGBDImages):
+            raise TypeError("Expected live_frame to be of type gradslam.RGBDImages. Got {0}.".format(type(live_frame)))
+        if not torch.is_tensor(prev_poses):
+            raise TypeError("Expected prev_poses to be of type tensor. Got {0}.".format(type(prev_poses)))
+        from .. import ops
+        fr = live_frame.to_channels_last()
+        B, L, H, W = fr.shape
+        if L != 1:
+            raise ValueError("Expected live_frame to have sequence length of 1. Got {0}.".format(L))
+        if len(pointclouds) != B or pointclouds._buf["points"] is None or pointclouds._buf["normals"] is None:
+            raise ValueError("Expected a map with points and normals for each of the {0} sequences of live_frame "
+                             "(got {1}).".format(B, len(pointclouds)))
+        if tuple(prev_poses.shape) not in ((B, 1, 4, 4), (B, 4, 4)):
+            raise ValueError("prev_poses should have shape {0}, but had shape {1}".format((B, 1, 4, 4),
+                                                                                         tuple(prev_poses.shape)))
+        poses = prev_poses.reshape(B, 4, 4).contiguous().float()
+        K = fr.intrinsics[:, 0].contiguous().float()
+        feats = pointclouds._buf["features"]
+        maps = []
+        for b in range(B):
+            bound, n_dev = pointclouds._count_of(b)   # (never forces a device-side count to the host)
+            # the index image is all the solve reads of the view: no colour, normal or confidence image is rendered
+            conf = feats[b] if feats is not None and self.min_confidence > 0 else None
+            maps.append((pointclouds._buf["points"][b], pointclouds._buf["normals"][b], None, conf, bound, n_dev))
+        view = ops.render_map_batch([(m[0], None) + m[2:] for m in maps], poses.view(B, 1, 4, 4), K, H, W,
+                                    radius=self.radius, min_confidence=self.min_confidence)
+        out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=poses.device)
+        ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
+                                 view.index[:, 0], poses, maps, poses, out=out.view(B, 4, 4), **self._kwargs())
+        return out

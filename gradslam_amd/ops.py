@@ -931,6 +931,160 @@ def render_map(points, normals, colors, ccounts, poses, K, H, W, n_dev=None, rad
     return RenderedViews(*[None if t is None else t[0] for t in r])
 
 
+# ----------------------------------------------------------------------------------- projective ICP
+ProjectiveRows = collections.namedtuple("ProjectiveRows", ["code", "row", "a", "b", "sums", "count"])
+PICP_TRACE = 8
+
+
+def _picp_args(stride, numiters, damp, dist_thresh, angle_thresh):
+    """the value checks of the projective ICP; returns (dist_th, dot_th) as the Python doubles the library casts"""
+    import math
+    for name, val in (("stride", stride), ("numiters", numiters)):
+        if isinstance(val, bool) or not isinstance(val, int):
+            raise TypeError("projective_icp: {} must be of type int; but was of type {}.".format(name, type(val)))
+        if val < 1:
+            raise ValueError("projective_icp: {} ({}) must be at least 1.".format(name, val))
+    for name, val in (("damp", damp), ("dist_thresh", dist_thresh), ("angle_thresh", angle_thresh)):
+        if isinstance(val, bool) or not isinstance(val, (float, int)):
+            raise TypeError("projective_icp: {} must be of type float or int; but was of type {}.".format(name, type(val)))
+        if math.isnan(val):
+            raise ValueError("projective_icp: {} is NaN.".format(name))
+    if not (damp > 0 and math.isfinite(damp)):
+        raise ValueError("projective_icp: damp ({}) must be positive and finite.".format(damp))
+    if not 0 <= angle_thresh <= 90:
+        raise ValueError("projective_icp: angle_thresh ({}) must be within [0, 90] degrees.".format(angle_thresh))
+    return float(dist_thresh), math.cos((angle_thresh * math.pi) / 180)
+
+
+def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride):
+    """Shape / dtype / device checks shared by the batched solve and the table-level call; fills the descriptors.
+    Returns (seqs, tensors kept alive, device, B, H, W)."""
+    tensors = (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
+               ("model_pose", model_poses), ("init_pose", init_poses))
+    for name, t in tensors:
+        if not torch.is_tensor(t):
+            raise TypeError("{}: expected {} to be of type tensor; got {}".format(who, name, type(t)))
+    if depth.ndim != 3:
+        raise ValueError("{}: expected depth (B, H, W); got {}".format(who, tuple(depth.shape)))
+    Bn, H, W = (int(x) for x in depth.shape)
+    want = {"vertex": (Bn, H, W, 3), "normal": (Bn, H, W, 3), "K": (Bn, 4, 4), "index": (Bn, H, W),
+            "model_pose": (Bn, 4, 4), "init_pose": (Bn, 4, 4)}
+    for name, t in tensors:
+        if name in want and tuple(t.shape) != want[name]:
+            raise ValueError("{}: expected {} of shape {} for depth {}; got {}".format(
+                who, name, want[name], tuple(depth.shape), tuple(t.shape)))
+    if Bn == 0 or H == 0 or W == 0 or len(maps) != Bn:
+        raise ValueError("{}: needs at least one sequence, a positive image size and one map per sequence "
+                         "(B = {}, {} maps)".format(who, Bn, len(maps)))
+    if index.dtype != torch.int64:
+        raise ValueError("{}: index must be the int64 index image of render_map; got {}".format(who, index.dtype))
+    for m in maps:
+        P, N = m[0], m[1]
+        if P is None or N is None:
+            raise ValueError("{}: a map without points or normals".format(who))
+        if P.dtype != f32 or N.dtype != f32 or P.ndim != 2 or P.shape[1] != 3 or N.ndim != 2 or N.shape[1] != 3 or \
+                N.shape[0] < P.shape[0] or not P.is_contiguous() or not N.is_contiguous():
+            raise ValueError("{}: map points / normals must be contiguous float32 (rows, 3) tensors, normals with at "
+                             "least as many rows as points (got {} {} / {} {})".format(
+                                 who, P.dtype, tuple(P.shape), N.dtype, tuple(N.shape)))
+    _warn_detached(who, vertex, normal, depth, K, model_poses, init_poses, *[t for m in maps for t in m[:2]])
+    vertex, normal, depth, K, model_poses, init_poses = (_c(t.detach()) for t in (vertex, normal, depth, K, model_poses,
+                                                                                  init_poses))
+    index = index.contiguous()
+    dev = require_device(vertex, normal, depth, K, index, model_poses, init_poses)
+    held = [vertex, normal, depth, K, index, model_poses, init_poses]
+    ws = Workspace.get(dev)
+    L = lib()
+    nbytes = L.gs_projective_icp_scratch_bytes(H, W, int(stride))
+    seqs = (_C.PicpSeq * Bn)()
+    P3, P1 = H * W * 12, H * W * 4
+    for b in range(Bn):
+        P, N = maps[b][0], maps[b][1]
+        n_bound, n_dev = maps[b][-2], maps[b][-1]
+        require_device(P.detach(), N.detach(), n_dev, vertex)
+        if n_dev is not None and (n_dev.dtype != torch.int64 or n_dev.numel() < 1):
+            raise ValueError("{}: the device count must be an int64 tensor".format(who))
+        n_bound = P.shape[0] if n_bound is None else min(int(n_bound), int(P.shape[0]))
+        held += [P, N, n_dev]
+        u = seqs[b]
+        u.vertex, u.normal, u.depth = vertex.data_ptr() + b * P3, normal.data_ptr() + b * P3, depth.data_ptr() + b * P1
+        u.K16, u.index, u.model_pose16 = K.data_ptr() + b * 64, index.data_ptr() + b * H * W * 8, \
+            model_poses.data_ptr() + b * 64
+        u.map = _C.MapView(P.data_ptr(), N.data_ptr(), 0, 0, int(P.shape[0]), max(n_bound, 0),
+                           0 if n_dev is None else n_dev.data_ptr())
+        u.init_pose16 = init_poses.data_ptr() + b * 64
+        u.scratch = ws.bytes("picp%d" % b, nbytes).data_ptr()
+    return seqs, held, dev, Bn, H, W
+
+
+def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, init_poses, *, stride=1, numiters=10,
+                         damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False, out=None):
+    """Frame-to-model tracking by projective data association for B sequences (gs_projective_icp_batch_f32: two launches
+    per iteration for 8 sequences, nothing read back).  vertex / normal (B, H, W, 3): LOCAL maps of the live frames,
+    depth (B, H, W), K (B, 4, 4); index (B, H, W) int64: the index image of render_map_batch at model_poses (B, 4, 4);
+    maps: per sequence the tuple render_map_batch takes, (points, normals, colors, ccounts, n_bound, n_dev), or the short
+    form (points, normals, n_bound, n_dev); init_poses (B, 4, 4).  Every lattice pixel [::stride, ::stride] with depth is
+    carried by the current estimate into the model view and paired with the map row that won the pixel it lands on, if
+    that row is within dist_thresh metres and angle_thresh degrees (normals); numiters point-to-plane Gauss-Newton steps
+    with constant damping follow.  Returns the poses (B, 4, 4), detached; with return_trace also (B, numiters, 8) rows
+    [inliers, sum of squared residuals, xi(6)].  An iteration without inliers leaves the pose as it is."""
+    dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
+    seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp", vertex, normal, depth, K, index, model_poses, maps,
+                                           init_poses, stride)
+    T = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if out is None else out
+    if tuple(T.shape) != (Bn, 4, 4) or T.dtype != f32 or not T.is_contiguous() or T.device != dev:
+        raise ValueError("projective_icp: out must be a contiguous float32 tensor of shape %s on %s" % ((Bn, 4, 4), dev))
+    trace = torch.empty((Bn, int(numiters), PICP_TRACE), dtype=f32, device=dev) if return_trace else None
+    for b in range(Bn):
+        seqs[b].out_pose16 = T.data_ptr() + b * 64
+        seqs[b].trace = 0 if trace is None else trace.data_ptr() + b * int(numiters) * PICP_TRACE * 4
+    prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
+    check(lib().gs_projective_icp_batch_f32(seqs, Bn, H, W, prm, stream(dev)), "gs_projective_icp_batch_f32")
+    return (T, trace) if return_trace else T
+
+
+def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, *, n_dev=None,
+                   stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False):
+    """projective_icp_batch for one sequence without the batch dimension: vertex / normal (H, W, 3), depth (H, W), K /
+    model_pose / init_pose (4, 4), index (H, W) int64; n_dev: device int64[1] holding the actual row count of the map
+    (map_points.shape[0] is then an upper bound).  Returns the pose (4, 4) (and the trace (numiters, 8))."""
+    for name, t in (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
+                    ("model_pose", model_pose), ("init_pose", init_pose)):
+        if not torch.is_tensor(t):
+            raise TypeError("projective_icp: expected {} to be of type tensor; got {}".format(name, type(t)))
+    r = projective_icp_batch(vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0), K.reshape(1, 4, 4),
+                             index.unsqueeze(0), model_pose.reshape(1, 4, 4), [(map_points, map_normals, None, n_dev)],
+                             init_pose.reshape(1, 4, 4), stride=stride, numiters=numiters, damp=damp,
+                             dist_thresh=dist_thresh, angle_thresh=angle_thresh, return_trace=return_trace)
+    return (r[0][0], r[1][0]) if return_trace else r[0]
+
+
+def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points, map_normals, pose, *, n_dev=None,
+                        stride=1, dist_thresh=0.1, angle_thresh=30.0):
+    """ONE linearisation of the projective ICP at `pose` (gs_projective_icp_rows_f32), arguments as projective_icp.  With
+    nslots = ceil(H / stride) * ceil(W / stride), slot i * ceil(W / stride) + j standing for pixel (i stride, j stride):
+    ProjectiveRows(code int32 (nslots,): 0 used, 1 no depth, 2 outside the model view, 3 no (or a stale) winner, 4 too
+    far, 5 normals disagree; row int64 (nslots,): the index image's entry where one was read (codes 0, 3, 4, 5), else -1;
+    a (nslots, 6), b (nslots,): the point-to-plane row, zeros unless used; sums float64 (28,): 21 upper-triangular a_i
+    a_j, 6 a_i b, b b; count int64 (1,))."""
+    dist_th, dot_th = _picp_args(stride, 1, 1.0, dist_thresh, angle_thresh)
+    for name, t in (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
+                    ("model_pose", model_pose), ("pose", pose)):
+        if not torch.is_tensor(t):
+            raise TypeError("projective_icp_rows: expected {} to be of type tensor; got {}".format(name, type(t)))
+    seqs, held, dev, _, H, W = _picp_seqs("projective_icp_rows", vertex.unsqueeze(0), normal.unsqueeze(0),
+                                          depth.unsqueeze(0), K.reshape(1, 4, 4), index.unsqueeze(0),
+                                          model_pose.reshape(1, 4, 4), [(map_points, map_normals, None, n_dev)],
+                                          pose.reshape(1, 4, 4), stride)
+    ns = ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
+    res = ProjectiveRows(torch.empty(ns, dtype=torch.int32, device=dev), torch.empty(ns, dtype=torch.int64, device=dev),
+                         torch.empty((ns, 6), dtype=f32, device=dev), torch.empty(ns, dtype=f32, device=dev),
+                         torch.empty(28, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.int64, device=dev))
+    check(lib().gs_projective_icp_rows_f32(seqs, H, W, int(stride), dist_th, dot_th, *[ptr(t) for t in res], stream(dev)),
+          "gs_projective_icp_rows_f32")
+    return res
+
+
 # ----------------------------------------------------------------------------------- pruning the map
 PrunedMaps = collections.namedtuple("PrunedMaps", ["maps", "counts", "removed"])
 PRUNE_MAX_MARKS = 64

@@ -12,6 +12,7 @@ import torch.nn as nn
 
 from ..odometry.gradicp import GradICPOdometryProvider
 from ..odometry.icp import ICPOdometryProvider
+from ..odometry.projicp import ProjectiveICPOdometryProvider
 from ..structures.pointclouds import Pointclouds
 from ..structures.rgbdimages import RGBDImages
 from .fusionutils import update_map_aggregate
@@ -34,15 +35,20 @@ class ICPSLAM(nn.Module):
                  device: Union[torch.device, str, None] = None, depth_filter: Optional[dict] = None):
         super().__init__()
         self.depth_filter = _check_depth_filter(depth_filter)
-        if odom not in ["gt", "icp", "gradicp"]:
+        if odom not in ["gt", "icp", "gradicp", "projicp"]:
             msg = "odometry method ({}) not supported for PointFusion. ".format(odom)
-            msg += "Currently supported odometry modules for PointFusion are: 'gt', 'icp', 'gradicp'"
+            msg += "Currently supported odometry modules for PointFusion are: 'gt', 'icp', 'gradicp', 'projicp'"
             raise ValueError(msg)
         odomprov = None
         if odom == "icp":
             odomprov = ICPOdometryProvider(numiters, damp, dist_thresh)
         elif odom == "gradicp":
             odomprov = GradICPOdometryProvider(numiters, damp, dist_thresh, lambda_max, B, B2, nu)
+        elif odom == "projicp":
+            # frame-to-model tracking against the rendered map: dsratio is the lattice stride, dist_thresh=None the
+            # provider's 0.1 m (the gate is part of the association, it cannot be switched off)
+            odomprov = ProjectiveICPOdometryProvider(numiters, damp, 0.1 if dist_thresh is None else dist_thresh,
+                                                     stride=dsratio)
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio
@@ -113,6 +119,11 @@ class ICPSLAM(nn.Module):
             if not live_frame.has_poses:
                 raise ValueError("`live_frame` must have poses when `prev_frame` is None or `odom='gt'`.")
             return live_frame.poses
+
+        if self.odom == "projicp":
+            # the model view at the previous pose is target and initial guess; the result is detached (a requires-grad
+            # input warns): there is no backward pass
+            return self.odomprov.localize(pointclouds, live_frame, prev_frame.poses[:, :1])
 
         if self.odom in ["icp", "gradicp"]:
             from .. import ops

@@ -694,6 +694,59 @@ GS_API int gs_bilateral_depth_backward_f32(const float* depth, int64_t stride_fr
                                            int W, int radius, float two_sigma_space_sq, float two_sigma_range_sq,
                                            float* depth_bar, void* stream);
 
+/* ------------------------------------------------------------------ projective ICP against the model view ------
+ * Frame-to-model tracking by projective data association (Keller et al., KinectFusion; no counterpart in the reference,
+ * whose trackers search a 1-NN): every pixel of the live frame's [::stride, ::stride] lattice is carried by the current
+ * pose estimate T into the model view -- the `index` image gs_render_map_dc_f32 wrote for the pose model_pose16 -- and is
+ * paired with the map row that won the pixel it lands on; a point-to-plane Gauss-Newton step with constant damping
+ * follows.  Slot k = i * Wl + j (Wl = ceil(W / stride)) stands for pixel (h, w) = (i stride, j stride); in float32, one
+ * rounding per operation, with the device functions of the association and of the ICP solve:
+ *   code 1  unless depth[h, w] > 0 (false for NaN)
+ *   s = T v (the chain of gs_transform_points_f32), g = R_T n (the same chain without the translation)
+ *   code 2  unless s projects into the model view (gs_project_map_f32's pixel for model_pose16, K16, H, W) at (h', w')
+ *   code 3  unless 0 <= row = index[h', w'] < min(*map.n_dev, map.n_bound): a stale index is never dereferenced
+ *   code 4  unless |s - points[row]| < dist_th;  code 5 unless g . normals[row] > dot_th   (gs_similar_rows_f32's tests)
+ *   code 0: the row (a[6], b) of gs_gauss_newton_rows_f32 for source s and target points[row], normals[row]
+ * The 28 sums (21 upper-triangular a_i a_j, 6 a_i b, b b) are float64 sums of exact products, in a FIXED order: chunks of
+ * 256 consecutive slots (the last one padded with +0.0; a rejected slot is +0.0), inside a chunk a pairwise adjacent tree
+ * (8 levels), the chunk partials added in ascending chunk order starting from the first.  No float atomics: every output
+ * is bitwise reproducible.  An iteration then solves (AtA + damp I) xi = Atb as gs_solve_normal_eq_f32 does, and sets
+ * T <- se3_exp(xi) T (the 4x4 product of the ICP loop); with no inlier xi = 0 and T keeps its bits.
+ * gs_projective_icp_batch_f32 runs numiters iterations from init_pose16 for B sequences (8 per launch, two launches per
+ * iteration, nothing read back) and writes out_pose16 and, when trace is not NULL, one row [inliers, (float)sum b b,
+ * xi(6)] per iteration.  out_pose16 may be init_pose16.  scratch: gs_projective_icp_scratch_bytes(H, W, stride) bytes per
+ * sequence.  dot_th = cos(angle threshold), dist_th in metres; damp > 0.  Every argument is checked before the first HIP
+ * call. */
+typedef struct gs_picp_seq {
+  const float* vertex;        /* live frame, LOCAL vertex map (H, W, 3) */
+  const float* normal;        /* live frame, LOCAL normal map (H, W, 3) */
+  const float* depth;         /* live frame depth (H, W) */
+  const float* K16;
+  const int64_t* index;       /* (H, W): winning map row of the model view, or -1 */
+  const float* model_pose16;  /* camera-to-world pose of the model view */
+  gs_map_view map;            /* points + normals are read; colors / ccounts / capacity are not used */
+  const float* init_pose16;   /* initial estimate (the batch entry) / the pose to linearise at (the rows entry) */
+  float* out_pose16;          /* out: the estimate after numiters iterations (not used by the rows entry) */
+  float* trace;               /* out, optional: (numiters, 8) */
+  void* scratch;
+} gs_picp_seq;
+typedef struct gs_picp_params {
+  int stride;
+  int numiters;
+  float damp;
+  float dist_th;
+  float dot_th;
+} gs_picp_params;
+GS_API int64_t gs_projective_icp_scratch_bytes(int H, int W, int stride);
+GS_API int gs_projective_icp_batch_f32(const gs_picp_seq* seqs_host, int B, int H, int W,
+                                       const gs_picp_params* params_host, void* stream);
+/* ONE linearisation of one sequence at T = init_pose16: per slot (nslots = ceil(H / stride) * ceil(W / stride)) the code
+ * (0 = used), the row (the index image's entry where one was read, i.e. codes 0, 3, 4, 5; else -1), a6 (nslots, 6) and b
+ * (zeros unless the slot is used), plus the 28 sums (float64) and the inlier count.  Any output may be NULL. */
+GS_API int gs_projective_icp_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
+                                      float dot_th, int32_t* code, int64_t* row, float* a6, float* b, double* sums28,
+                                      int64_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,190 @@
+"""Projective-association ICP against the model view: what one localisation costs next to the grid-search ICP, what the
+frame loop gains or loses with it, and what a launch of it costs (needs the MI355X; fails without one).
+
+    python tools/projective_icp_profile.py [--out FILE] [--only localize|slam|launches] [--steps K]
+
+1. One localisation.  640x480 frames of the benchmark's synthetic sequences, the map fused from the first 10 frames under
+   the ground-truth poses, frame 10 localised from the pose of frame 9; B = 1 and B = 8.
+     new       ProjectiveICPOdometryProvider.localize: the render of the index image (ops.render_map_batch) + 10
+               Gauss-Newton iterations (ops.projective_icp_batch), strides 4 and 1.
+     baseline  ops.localize_batch on the same frames and maps: the grid-search gradICP at ds = 4 with the driver's 20
+               iterations, and with 10.
+   Timing: device events around `reps` back-to-back calls that end in a synchronise, the variants alternating in one
+   process after a warm-up of each; median / min / max over the rounds.  Next to each time: the translation error of the
+   pose against the ground truth (the variants solve different problems: this is a cost and accuracy report, not a
+   parity check).
+
+2. The frame loop.  A 20-step window of the B = 8 run at 640x480 (10 warm-up frames) with PointFusion(odom="projicp") and
+   PointFusion(odom="gradicp"), both with the drivers' defaults (dsratio 4, 20 iterations): frames/s, ms per step and the
+   ATE (RMSE of the translation error against the ground truth over the timed frames) of both, gradicp repeated for the
+   spread of the same code.
+
+3. Launches.  The solve alone (no render) at 10 and at 40 iterations: the slope is the time of one iteration = one
+   linearise launch + one finish launch; and the render alone.  For the split between the two kernels run
+       rocprofv3 --kernel-trace --stats -d DIR -- python tools/projective_icp_profile.py --only launches
+   in a run of its own (tracing slows the host: no end-to-end number comes from that run)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+H, W = 480, 640
+MAP_FRAMES = 10
+
+
+def stats(ms):
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "rounds": len(ms)}
+
+
+def time_round_robin(torch, fns, reps, rounds):
+    res = {k: [] for k in fns}
+    for _ in range(rounds):
+        for key, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            res[key].append(e0.elapsed_time(e1) / reps)
+    return {k: stats(v) for k, v in res.items()}
+
+
+def scene(torch, gs, B):
+    """(map fused from MAP_FRAMES frames under the ground truth, live frame, previous poses, ground truth of the live frame)"""
+    import bench
+    device = torch.device("cuda")
+    frames, gt = bench.make_sequences_on_device(gs, list(range(B)), MAP_FRAMES + 1, H, W, device)
+    gt_poses = torch.from_numpy(gt[0]["poses"]).to(device)
+    frames.poses = gt_poses.unsqueeze(0).expand(B, -1, 4, 4).contiguous()
+    slam = gs.slam.PointFusion(odom="gt", device=device)
+    pc = gs.Pointclouds(device=device)
+    for s in range(MAP_FRAMES):
+        pc, _ = slam.step(pc, frames[:, s], None, inplace=True)
+    live = frames[:, MAP_FRAMES]
+    prev = gt_poses[MAP_FRAMES - 1].view(1, 1, 4, 4).expand(B, 1, 4, 4).contiguous()
+    torch.cuda.synchronize()
+    return pc, live, prev, gt_poses[MAP_FRAMES]
+
+
+def translation_error(T, gt):
+    return [float(x) for x in (T.reshape(-1, 4, 4)[:, :3, 3].double() - gt[:3, 3].double()).norm(dim=1).cpu()]
+
+
+def localize_times(torch, gs, ops, reps=5, rounds=7):
+    from gradslam_amd.odometry import ProjectiveICPOdometryProvider
+    out = []
+    for B in (1, 8):
+        pc, live, prev, gt = scene(torch, gs, B)
+        fr = live.to_channels_last()
+        K = fr.intrinsics[:, 0].contiguous()
+        vertex, depth = fr.vertex_map[:, 0], fr.depth_image[:, 0, ..., 0]
+        fr.normal_map   # (the frame maps are computed once, outside the timed region, for every variant)
+        maps4 = [(pc._buf["points"][b], pc._buf["normals"][b]) + tuple(pc._count_of(b)) for b in range(B)]
+        rows = pc._tighten_counts()
+        prov = {s: ProjectiveICPOdometryProvider(numiters=10, stride=s) for s in (4, 1)}
+        fns = {
+            "projicp_stride4_10it": lambda: prov[4].localize(pc, live, prev),
+            "projicp_stride1_10it": lambda: prov[1].localize(pc, live, prev),
+            "gradicp_ds4_20it": lambda: ops.localize_batch(vertex, depth, K, prev[:, 0], maps4, 4, mode=1, numiters=20),
+            "gradicp_ds4_10it": lambda: ops.localize_batch(vertex, depth, K, prev[:, 0], maps4, 4, mode=1, numiters=10),
+        }
+        err = {k: translation_error(fn(), gt) for k, fn in fns.items()}
+        for fn in fns.values():
+            fn(), fn()
+        t = time_round_robin(torch, fns, reps, rounds)
+        rec = {"B": B, "H": H, "W": W, "map_rows": rows, "initial_translation_error_m": translation_error(prev, gt)[0],
+               "variants": {k: dict(t[k], translation_error_m=err[k]) for k in fns}}
+        for s in (4, 1):
+            rec["speedup_stride%d_vs_gradicp_20it" % s] = \
+                t["gradicp_ds4_20it"]["median_ms"] / t["projicp_stride%d_10it" % s]["median_ms"]
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+    return out
+
+
+def launch_times(torch, gs, ops, reps=5, rounds=7):
+    out = []
+    for B in (1, 8):
+        pc, live, prev, _ = scene(torch, gs, B)
+        fr = live.to_channels_last()
+        K = fr.intrinsics[:, 0].contiguous()
+        maps = [(pc._buf["points"][b], None, None, None) + tuple(pc._count_of(b)) for b in range(B)]
+        maps_n = [(pc._buf["points"][b], pc._buf["normals"][b]) + tuple(pc._count_of(b)) for b in range(B)]
+        index = ops.render_map_batch(maps, prev, K, H, W).index[:, 0]
+        args = (fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K, index, prev[:, 0], maps_n,
+                prev[:, 0])
+        for stride in (4, 1):
+            fns = {"render": lambda: ops.render_map_batch(maps, prev, K, H, W),
+                   "solve_10it": lambda: ops.projective_icp_batch(*args, stride=stride, numiters=10),
+                   "solve_40it": lambda: ops.projective_icp_batch(*args, stride=stride, numiters=40)}
+            for fn in fns.values():
+                fn(), fn()
+            t = time_round_robin(torch, fns, reps, rounds)
+            per_it = (t["solve_40it"]["median_ms"] - t["solve_10it"]["median_ms"]) / 30
+            nslots = -(-H // stride) * -(-W // stride)
+            rec = {"B": B, "stride": stride, "slots": nslots, "chunks": -(-nslots // 256), "times": t,
+                   "us_per_iteration": per_it * 1e3, "us_per_launch_mean": per_it * 1e3 / 2,
+                   "us_outside_the_iterations": (t["solve_10it"]["median_ms"] - 10 * per_it) * 1e3}
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+    return out
+
+
+def slam_runs(torch, gs, steps, warmup=10):
+    import bench
+    B = 8
+    device = torch.device("cuda")
+    frames, gt = bench.make_sequences_on_device(gs, list(range(B)), warmup + steps, H, W, device)
+    gt_t = torch.from_numpy(gt[0]["poses"][warmup:warmup + steps, :3, 3]).to(device).double()
+
+    def run(odom):
+        slam = gs.slam.PointFusion(odom=odom, device=device)
+        r = bench.timed_steps(gs, slam, frames, warmup, steps, device, lambda: torch.cuda.synchronize(device))
+        e = (r["poses"][:, warmup:warmup + steps, :3, 3].double() - gt_t).norm(dim=-1)     # (B, steps)
+        return {"odom": odom, "frames_per_s": B * steps / r["elapsed"], "ms_per_step": r["elapsed"] / steps * 1e3,
+                "gpu_ms_per_step_median": statistics.median(r["step_ms"]),
+                "ate_rmse_m": float((e * e).mean().sqrt()), "ate_max_m": float(e.max()),
+                "last_frame_error_m_mean": float(e[:, -1].mean())}
+
+    run("gradicp"), run("projicp")   # warm-up of every shape: allocator size classes, code objects
+    base = run("gradicp")
+    new = run("projicp")
+    base2 = run("gradicp")
+    out = {"B": B, "H": H, "W": W, "warmup": warmup, "steps": steps, "gradicp": base, "projicp": new,
+           "gradicp_repeated": base2, "frames_per_s_ratio": new["frames_per_s"] / base["frames_per_s"]}
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--only", choices=("localize", "slam", "launches"), default=None)
+    ap.add_argument("--steps", type=int, default=20)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("tools/projective_icp_profile.py measures on the GPU: no HIP device found (nothing is measured on the CPU)")
+    import gradslam_amd as gs
+    from gradslam_amd import ops
+    out = {"device": torch.cuda.get_device_name(0)}
+    if args.only in (None, "localize"):
+        out["one_localisation"] = localize_times(torch, gs, ops)
+    if args.only in (None, "slam"):
+        out["slam_window"] = slam_runs(torch, gs, args.steps)
+    if args.only in (None, "launches"):
+        out["launches"] = launch_times(torch, gs, ops)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
