@@ -89,6 +89,15 @@ class PicpSeq(C.Structure):
                 ("out_pose16", C.c_void_p), ("trace", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class PicpBackwardSeq(C.Structure):
+    """gs_picp_backward_seq: the forward's inputs, its tape, the upstream adjoint and the gradient outputs."""
+    _fields_ = [("vertex", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("K16", C.c_void_p),
+                ("index", C.c_void_p), ("model_pose16", C.c_void_p), ("map", MapView), ("tape", C.c_void_p),
+                ("pose_bar16", C.c_void_p), ("vertex_bar", C.c_void_p), ("points_bar", C.c_void_p),
+                ("normals_bar", C.c_void_p), ("init_pose_bar16", C.c_void_p), ("scratch", C.c_void_p),
+                ("scratch_bytes", C.c_int64)]
+
+
 class PicpParams(C.Structure):
     _fields_ = [("stride", C.c_int), ("numiters", C.c_int), ("damp", C.c_float), ("dist_th", C.c_float),
                 ("dot_th", C.c_float)]
@@ -184,12 +193,18 @@ _PROTOS = {
     "gs_projective_icp_scratch_bytes": [_i32, _i32, _i32],
     "gs_projective_icp_batch_f32": [C.POINTER(PicpSeq), _i32, _i32, _i32, C.POINTER(PicpParams), _vp],
     "gs_projective_icp_rows_f32": [C.POINTER(PicpSeq), _i32, _i32, _i32, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gs_projective_icp_tape_bytes": [_i32],
+    "gs_projective_icp_tape_batch_f32": [C.POINTER(PicpSeq), C.POINTER(C.c_void_p), _i32, _i32, _i32,
+                                         C.POINTER(PicpParams), _vp],
+    "gs_projective_icp_backward_scratch_bytes": [_i32, _i32, _i32, _i64],
+    "gs_projective_icp_backward_batch_f32": [C.POINTER(PicpBackwardSeq), _i32, _i32, _i32, C.POINTER(PicpParams), _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,
             "gs_knn1_grid_scratch_bytes": _i64, "gs_update_map_scratch_bytes": _i64, "gs_global_maps_pose_backward_scratch_bytes": _i64, "gs_icp_tape_bytes": _i64, "gs_icp_backward_scratch_bytes": _i64,
             "gs_localize_scratch_bytes": _i64, "gs_frame_maps_backward_kbar_scratch_bytes": _i64,
             "gs_render_scratch_bytes": _i64, "gs_render_backward_scratch_bytes": _i64,
-            "gs_prune_scratch_bytes": _i64, "gs_projective_icp_scratch_bytes": _i64}
+            "gs_prune_scratch_bytes": _i64, "gs_projective_icp_scratch_bytes": _i64,
+            "gs_projective_icp_tape_bytes": _i64, "gs_projective_icp_backward_scratch_bytes": _i64}
 EXPORTS = tuple(_PROTOS)
 
 

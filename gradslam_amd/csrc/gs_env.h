@@ -1,6 +1,8 @@
 // gs_env.h — every GRADSLAM_HIP_* environment switch the library reads, in ONE place (README: the knob table).
 // gs_env() reads them once per process (a function-local static: thread-safe).  None of them changes a result (tests/
-// test_hip_engine_matrix.py, tests/test_hip_batch.py).  Not here: GRADSLAM_HIP_DETERMINISTIC_BACKWARD, read per call (gs_icp_bwd.hip).
+// test_hip_engine_matrix.py, tests/test_hip_batch.py).  Not here: GRADSLAM_HIP_DETERMINISTIC_BACKWARD, read per call (gs_icp_bwd.hip);
+// it covers the ICP backward only -- the map scatter of the projective ICP's backward (gs_picp_bwd.hip) is float64 atomics in
+// every mode.
 #pragma once
 #include <stdlib.h>
 #include <string.h>

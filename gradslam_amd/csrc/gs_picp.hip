@@ -24,11 +24,10 @@
 // lane l ^ d: both lanes of a pair form the same sum, a + b == b + a), then (w0 + w1) + (w2 + w3) over the four waves;
 // slots beyond the lattice are +0.0.  The chunk partials are added in ascending chunk order starting from the first.
 // The inlier count is an integer sum.
-#include "gs_assoc_dev.h"
-#include "gs_icp_math.h"
-
-constexpr int GS_PI_CHUNK = 256;
-constexpr int GS_PI_TRACE = 8;   // floats per trace row: count, (float)S[27], xi(6)
+// The taped entry (gs_projective_icp_tape_batch_f32) is the same two kernels: the finish kernel also writes the pose it
+// read, the 28 sums, the step and the inlier count of every iteration to the caller's tape (PiTapeRow), which is all the
+// backward pass (gs_picp_bwd.hip) needs besides the inputs.  The pose bits are those of the untaped call.
+#include "gs_picp_dev.h"
 
 struct PiSeq {
   const float* vertex;
@@ -43,6 +42,7 @@ struct PiSeq {
   const float* T_in;       // pose estimate the launch reads (iteration 0: the caller's initial pose; then T_out)
   float* T_out;            // finish: the updated estimate (NULL: sums only)
   float* trace_row;        // finish: this iteration's trace row, or NULL
+  PiTapeRow* tape_row;     // finish: this iteration's tape row, or NULL
   double* partials;        // (nchunks, 28)
   int32_t* counts;         // (nchunks)
   int32_t* code_out;       // table-level outputs, any may be NULL: (nslots)
@@ -57,15 +57,6 @@ struct PiBatch {
   int B, H, W, stride, Wl, nslots, nchunks;
   float u_hi, v_hi, dist_th, dot_th, damp;
 };
-
-// levels 1..6 of the tree: lane l adds the value of lane l ^ d, d = 1, 2, ..., 32 (every lane ends with the wave's sum)
-GS_DEV double pi_wave_tree(double x, const bool any) {
-  if (any) {
-#pragma unroll
-    for (int d = 1; d < GS_WAVE; d <<= 1) x = x + __shfl_xor(x, d, GS_WAVE);
-  }
-  return x;
-}
 
 __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_linearize_kernel(const PiBatch pb) {
   __shared__ GsCamera cam;
@@ -87,29 +78,11 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_linearize_kernel(const Pi
   if (in_lattice) {
     const int i = k / pb.Wl, j = k - i * pb.Wl;
     const int64_t p = (int64_t)(i * pb.stride) * pb.W + j * pb.stride;
-    if (q.depth[p] > 0.0f) {
-      float s[3], g[3];
-      gs_rigid_fma(Ts, q.vertex[3 * p], q.vertex[3 * p + 1], q.vertex[3 * p + 2], s[0], s[1], s[2]);
-      const float n0 = q.normal[3 * p], n1 = q.normal[3 * p + 1], n2 = q.normal[3 * p + 2];
-      g[0] = gs_dot3_fma(Ts[0], Ts[1], Ts[2], n0, n1, n2);
-      g[1] = gs_dot3_fma(Ts[4], Ts[5], Ts[6], n0, n1, n2);
-      g[2] = gs_dot3_fma(Ts[8], Ts[9], Ts[10], n0, n1, n2);
-      int h2, w2;
-      code = 2;
-      if (gs_project_point_hw(cam, s[0], s[1], s[2], pb.H, pb.W, pb.u_hi, pb.v_hi, h2, w2)) {
-        row = q.index[(int64_t)h2 * pb.W + w2];
-        code = 3;
-        if (row >= 0 && row < n_map) {
-          // the two tests of gs_is_similar_v, apart: which one fails is the slot's code
-          const float4 d = make_float4(q.points[3 * row], q.points[3 * row + 1], q.points[3 * row + 2], 0.0f);
-          const float4 m = make_float4(q.normals[3 * row], q.normals[3 * row + 1], q.normals[3 * row + 2], 0.0f);
-          const float dist = gs_norm3(s[0] - d.x, s[1] - d.y, s[2] - d.z);
-          const float dot = gs_dot3_plain(g[0], g[1], g[2], m.x, m.y, m.z);
-          code = !(dist < pb.dist_th) ? 4 : (!(dot > pb.dot_th) ? 5 : 0);
-          if (code == 0) gn_row_pn(s[0], s[1], s[2], d, m, a, b);
-        }
-      }
-    }
+    float s[3];
+    float4 d, m;
+    code = pi_associate(Ts, cam, q.vertex, q.normal, q.depth, q.index, q.points, q.normals, n_map, p, pb.H, pb.W, pb.u_hi,
+                        pb.v_hi, pb.dist_th, pb.dot_th, row, s, d, m);
+    if (code == 0) gn_row_pn(s[0], s[1], s[2], d, m, a, b);
     if (q.code_out) q.code_out[k] = code;
     if (q.row_out) q.row_out[k] = row;
     if (q.a_out) {
@@ -219,6 +192,10 @@ __global__ void __launch_bounds__(GS_PI_FIN) gs_picp_finish_kernel(const PiBatch
     float T[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) T[i] = q.T_in[i];
+    if (q.tape_row) {   // the pose this iteration linearised at (T_out below may be the same buffer)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) q.tape_row->T[i] = T[i];
+    }
     if (n > 0) {   // no inlier: xi = 0 and T keeps its bits (a product with the identity would turn a -0 into +0)
       float Tr[16];
       gs_se3_exp_dev(xi, Tr);
@@ -232,12 +209,18 @@ __global__ void __launch_bounds__(GS_PI_FIN) gs_picp_finish_kernel(const PiBatch
 #pragma unroll
       for (int i = 0; i < 6; ++i) q.trace_row[2 + i] = xi[i];
     }
+    if (q.tape_row) {
+      PiTapeRow& tr = *q.tape_row;
+#pragma unroll
+      for (int i = 0; i < LIN_NV; ++i) tr.S[i] = S[i];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) tr.xi[i] = xi[i];
+      tr.pad[0] = 0.0f; tr.pad[1] = 0.0f;
+      tr.count = n;
+    }
   }
 }
 
-static int64_t picp_slots(int H, int W, int stride) {
-  return gs_ceil_div(H, stride) * gs_ceil_div(W, stride);
-}
 static size_t picp_partials_bytes(int64_t nchunks) { return gs_align((size_t)nchunks * LIN_NV * sizeof(double)); }
 
 extern "C" int64_t gs_projective_icp_scratch_bytes(int H, int W, int stride) {
@@ -246,13 +229,21 @@ extern "C" int64_t gs_projective_icp_scratch_bytes(int H, int W, int stride) {
   return (int64_t)(picp_partials_bytes(nchunks) + gs_align((size_t)nchunks * sizeof(int32_t)));
 }
 
-#define PICP_CHECK_SEQ(u)                                                                                            \
-  do {                                                                                                             \
-    GS_REQUIRE((u).vertex && (u).normal && (u).depth && (u).K16 && (u).index && (u).model_pose16 &&                \
-                   (u).init_pose16 && (u).scratch,                                                                 \
-               "NULL pointer");                                                                                    \
-    GS_REQUIRE((u).map.n_bound >= 0, "bad map size");                                                              \
-    GS_REQUIRE((u).map.n_bound == 0 || ((u).map.points && (u).map.normals), "NULL pointer (map points / normals)"); \
+// (the checks of the solve run in a helper shared by two entries: the message names the entry that was called)
+#define PICP_REQUIRE(who, cond, msg)           \
+  do {                                         \
+    if (!(cond)) {                             \
+      gs_set_error("%s: %s", who, msg);        \
+      return GS_ERR_INVALID;                   \
+    }                                          \
+  } while (0)
+#define PICP_CHECK_SEQ(who, u)                                                                                          \
+  do {                                                                                                                  \
+    PICP_REQUIRE(who, (u).vertex && (u).normal && (u).depth && (u).K16 && (u).index && (u).model_pose16 &&              \
+                          (u).init_pose16 && (u).scratch,                                                               \
+                 "NULL pointer");                                                                                       \
+    PICP_REQUIRE(who, (u).map.n_bound >= 0, "bad map size");                                                            \
+    PICP_REQUIRE(who, (u).map.n_bound == 0 || ((u).map.points && (u).map.normals), "NULL pointer (map points / normals)"); \
   } while (0)
 
 static void picp_fill(PiBatch& pb, int H, int W, int stride, float dist_th, float dot_th, float damp) {
@@ -271,23 +262,29 @@ static void picp_fill_seq(PiSeq& s, const gs_picp_seq& u, int nchunks) {
   s.n = GsCount{u.map.n_bound, u.map.n_dev};
   s.partials = static_cast<double*>(u.scratch);
   s.counts = reinterpret_cast<int32_t*>(static_cast<char*>(u.scratch) + picp_partials_bytes(nchunks));
-  s.T_in = u.init_pose16; s.T_out = nullptr; s.trace_row = nullptr;
+  s.T_in = u.init_pose16; s.T_out = nullptr; s.trace_row = nullptr; s.tape_row = nullptr;
   s.code_out = nullptr; s.row_out = nullptr; s.a_out = nullptr; s.b_out = nullptr;
   s.sums_out = nullptr; s.count_out = nullptr;
 }
 
-extern "C" int gs_projective_icp_batch_f32(const gs_picp_seq* seqs_host, int B, int H, int W,
-                                           const gs_picp_params* params_host, void* stream) {
-  GS_REQUIRE(seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
-  GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
+extern "C" int64_t gs_projective_icp_tape_bytes(int numiters) {
+  return numiters >= 1 ? (int64_t)numiters * (int64_t)sizeof(PiTapeRow) : 0;
+}
+
+// the solve behind both entries; tapes_host: per sequence the device buffer of numiters tape rows, or NULL (untaped)
+static int picp_solve(const char* who, const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H, int W,
+                      const gs_picp_params* params_host, void* stream) {
+  PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
+  PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   const gs_picp_params& prm = *params_host;
-  GS_REQUIRE(prm.stride >= 1, "stride must be at least 1");
-  GS_REQUIRE(prm.numiters >= 1, "numiters must be at least 1");
-  GS_REQUIRE(prm.damp > 0.0f && prm.damp < __builtin_inff(), "damp must be positive and finite");
-  GS_REQUIRE(!(prm.dist_th != prm.dist_th) && !(prm.dot_th != prm.dot_th), "a threshold is NaN");
+  PICP_REQUIRE(who, prm.stride >= 1, "stride must be at least 1");
+  PICP_REQUIRE(who, prm.numiters >= 1, "numiters must be at least 1");
+  PICP_REQUIRE(who, prm.damp > 0.0f && prm.damp < __builtin_inff(), "damp must be positive and finite");
+  PICP_REQUIRE(who, !(prm.dist_th != prm.dist_th) && !(prm.dot_th != prm.dot_th), "a threshold is NaN");
   for (int b = 0; b < B; ++b) {
-    PICP_CHECK_SEQ(seqs_host[b]);
-    GS_REQUIRE(seqs_host[b].out_pose16, "NULL pointer (out_pose16)");
+    PICP_CHECK_SEQ(who, seqs_host[b]);
+    PICP_REQUIRE(who, seqs_host[b].out_pose16, "NULL pointer (out_pose16)");
+    PICP_REQUIRE(who, !tapes_host || (tapes_host[b] && ((uintptr_t)tapes_host[b] & 7) == 0), "NULL or misaligned tape");
   }
   hipStream_t st = gs_stream(stream);
   for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
@@ -305,6 +302,7 @@ extern "C" int gs_projective_icp_batch_f32(const gs_picp_seq* seqs_host, int B, 
         const gs_picp_seq& u = seqs_host[c0 + b];
         pb.s[b].T_in = it == 0 ? u.init_pose16 : u.out_pose16;
         pb.s[b].trace_row = u.trace ? u.trace + (int64_t)GS_PI_TRACE * it : nullptr;
+        pb.s[b].tape_row = tapes_host ? static_cast<PiTapeRow*>(tapes_host[c0 + b]) + it : nullptr;
       }
       hipLaunchKernelGGL(gs_picp_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb);
       hipLaunchKernelGGL(gs_picp_finish_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb);
@@ -314,6 +312,17 @@ extern "C" int gs_projective_icp_batch_f32(const gs_picp_seq* seqs_host, int B, 
   return GS_OK;
 }
 
+extern "C" int gs_projective_icp_batch_f32(const gs_picp_seq* seqs_host, int B, int H, int W,
+                                           const gs_picp_params* params_host, void* stream) {
+  return picp_solve(__func__, seqs_host, nullptr, B, H, W, params_host, stream);
+}
+
+extern "C" int gs_projective_icp_tape_batch_f32(const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H, int W,
+                                                const gs_picp_params* params_host, void* stream) {
+  GS_REQUIRE(tapes_host, "NULL pointer (tapes)");
+  return picp_solve(__func__, seqs_host, tapes_host, B, H, W, params_host, stream);
+}
+
 extern "C" int gs_projective_icp_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
                                           float dot_th, int32_t* code, int64_t* row, float* a6, float* b,
                                           double* sums28, int64_t* count, void* stream) {
@@ -321,7 +330,7 @@ extern "C" int gs_projective_icp_rows_f32(const gs_picp_seq* seq_host, int H, in
   GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   GS_REQUIRE(stride >= 1, "stride must be at least 1");
   GS_REQUIRE(!(dist_th != dist_th) && !(dot_th != dot_th), "a threshold is NaN");
-  PICP_CHECK_SEQ(*seq_host);
+  PICP_CHECK_SEQ(__func__, *seq_host);
   hipStream_t st = gs_stream(stream);
   PiBatch pb;
   pb.B = 1;

@@ -1,0 +1,374 @@
+// gs_picp_bwd.hip — backward pass of the projective-association ICP (gs_picp.hip): reverse-mode differentiation of its
+// numiters Gauss-Newton iterations given the forward tape (gs_projective_icp_tape_batch_f32), from dL/dT to the live
+// vertex map, the map points, the map normals and the initial pose.
+//
+// What is differentiated, for iteration k with pose T_k = [R | t] (the taped float32 bits), per used slot with live
+// vertex v, map row `row`, p = points[row], m = normals[row]:
+//   s = R v + t,  a = [m ; s x m],  b = m . (p - s),  A = sum a a^T,  g = sum a b,  xi = (A + damp I)^-1 g,
+//   T_{k+1} = exp(xi) T_k.
+// Constants of the differentiation, as in the render and fuse backward: which slots are used and their rows (the reject
+// codes, both gates, the projection into the model view, the index image), the device count, K, model_pose, depth and the
+// live normal (it only feeds the gate).  The float32 roundings of the forward are treated as the identity.  The
+// association is NOT taped: the point stage recomputes it with the forward's own device function (pi_associate,
+// gs_picp_dev.h) at the taped float32 pose, so it is the forward's association exactly, and a stale index entry is
+// still never dereferenced.
+//
+// One step backwards, given Tb = dL/dT_{k+1}:
+//   scalar stage (one block per sequence)   Tb += the 12 sums of the point stage of iteration k + 1 (chunk partials in
+//       ascending order); without inliers Tb passes through; else xib = adjoint of exp at xi applied to Tb T_k^T,
+//       u = (A + damp I)^-1 xib, Tb <- exp(xi)^T Tb
+//   point stage (one thread per lattice slot, 256 per block = one chunk)   c = xi . a, e = u . a,
+//       ab = (b - c) u - e xi, w = ab[3:6], sb = m x w - e m;  points_bar[row] += e m;
+//       normals_bar[row] += ab[0:3] + w x s + e (p - s);  vertex_bar[slot] += R^T sb;  12 sums of sb [v^T 1]
+// and after iteration 0 a last scalar stage adds the sums of its point stage: init_pose_bar = Tb (top three rows, a zero
+// bottom row).  Where no point stage contributed nothing is added: with no inlier in any iteration init_pose_bar is the
+// upstream adjoint's top three rows bit for bit, a -0.0 included.  2 numiters + 1 launches per 8 sequences, enqueued back
+// to back, nothing read back.
+//
+// All arithmetic is float64, rounded to float32 once at the end.  The 12 sums use the forward's reduction shape (an xor
+// tree per wave, (w0 + w1) + (w2 + w3), chunk partials in ascending order; no float atomics) and vertex_bar is
+// accumulated per slot by the slot's own thread across the serialised iterations (a slot is its own pixel): vertex_bar
+// and init_pose_bar are BITWISE REPRODUCIBLE.  Several slots can land on the same surfel, so points_bar and normals_bar
+// are float64 atomic adds into float64 (n_bound, 3) buffers, rounded once: reproducible up to the order of the float64
+// additions (GRADSLAM_HIP_DETERMINISTIC_BACKWARD does not apply here; a sorted scatter is not built).
+// Every output may be NULL: its work and its buffer are skipped; with both map outputs NULL nothing of map size is
+// touched.
+#include "gs_picp_dev.h"
+#include "gs_se3_f64.h"
+
+constexpr int PB_NV = 12;          // 3x3 outer-product sum + 3-vector sum
+constexpr int PB_FIN = 256;        // threads of the scalar-stage block
+constexpr int PB_TILE = 256;       // chunk partial rows per LDS tile: 256 * 12 doubles = 24 KB
+
+struct PbState {       // per sequence, between the launches
+  double Tb[12];       // dL/dT of the iteration boundary being crossed, without the sums of the point stage after it
+  double u[6];         // scalar stage -> point stage
+  double xi[6];
+  int32_t active;      // 0: the iteration had no inlier (nothing flows through its step)
+  int32_t pad;
+};
+
+struct PbSeq {
+  const float* vertex;
+  const float* normal;
+  const float* depth;
+  const float* K16;
+  const int64_t* index;
+  const float* model_pose16;
+  const float* points;
+  const float* normals;
+  GsCount n;
+  const PiTapeRow* tape;
+  const float* pose_bar16;
+  float* vertex_bar;        // (H, W, 3) or NULL
+  float* init_pose_bar16;   // (16) or NULL
+  PbState* state;
+  double* partials;         // (nchunks, 12)
+  double* vacc;             // (nslots, 3) or NULL (no vertex_bar)
+  double* pbar;             // (n_bound, 3) or NULL
+  double* mbar;             // (n_bound, 3) or NULL
+};
+struct PbBatch {
+  PbSeq s[GS_MAX_BATCH];
+  int B, H, W, stride, Wl, nslots, nchunks, numiters;
+  float u_hi, v_hi, dist_th, dot_th, damp;
+};
+
+// Scalar stage in front of the point stage of iteration `it` (it == -1: the last one, which only hands out
+// init_pose_bar).  have_sums: a point stage ran before (false for the first launch, whose Tb is the upstream adjoint).
+__global__ void __launch_bounds__(PB_FIN) gs_picp_bwd_scalar_kernel(const PbBatch pb, const int it, const int have_sums) {
+  static_assert(PB_TILE * PB_NV % PB_FIN == 0, "a tile is a whole number of loads per thread");
+  constexpr int PER = PB_TILE * PB_NV / PB_FIN;   // 12
+  __shared__ double tile[PB_TILE * PB_NV];
+  __shared__ double G[PB_NV];
+  const PbSeq& q = pb.s[blockIdx.x];
+  const int tid = threadIdx.x;
+  // The sums are added only where a point stage contributed: behind an iteration without inliers (and in front of the
+  // first one) Tb keeps its bits -- x + 0.0 would turn a -0.0 of the upstream adjoint into +0.0.  (state->active is the
+  // flag of the point stage that ran last; this launch rewrites it only after every thread has passed the barrier below.)
+  const bool add_sums = have_sums && q.state->active != 0;
+  if (add_sums) {   // the forward's finish kernel: the table moves through LDS, column i is added up in ascending order
+    const int64_t total = (int64_t)pb.nchunks * PB_NV;
+    double nxt[PER];
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+      const int64_t i = tid + PB_FIN * r;
+      nxt[r] = i < total ? q.partials[i] : 0.0;
+    }
+    double s = 0.0;
+    for (int base = 0; base < pb.nchunks; base += PB_TILE) {
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < PER; ++r) tile[tid + PB_FIN * r] = nxt[r];
+      __syncthreads();
+      if (base + PB_TILE < pb.nchunks) {
+#pragma unroll
+        for (int r = 0; r < PER; ++r) {
+          const int64_t i = (int64_t)(base + PB_TILE) * PB_NV + tid + PB_FIN * r;
+          nxt[r] = i < total ? q.partials[i] : 0.0;
+        }
+      }
+      if (tid < PB_NV) {
+        const int m = pb.nchunks - base < PB_TILE ? pb.nchunks - base : PB_TILE;
+#pragma unroll 8
+        for (int c = 0; c < m; ++c) s = s + tile[c * PB_NV + tid];
+      }
+    }
+    if (tid < PB_NV) G[tid] = s;
+  } else if (tid < PB_NV) {
+    G[tid] = 0.0;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double Tb[16];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 4; ++j)
+      Tb[4 * i + j] = have_sums ? q.state->Tb[4 * i + j] : (double)q.pose_bar16[4 * i + j];
+    if (add_sums) {
+      for (int j = 0; j < 3; ++j) Tb[4 * i + j] += G[3 * i + j];
+      Tb[4 * i + 3] += G[9 + i];
+    }
+  }
+  for (int j = 0; j < 4; ++j) Tb[12 + j] = 0.0;
+  if (it < 0) {
+    if (q.init_pose_bar16) {
+      for (int i = 0; i < 12; ++i) q.init_pose_bar16[i] = (float)Tb[i];
+      for (int j = 0; j < 4; ++j) q.init_pose_bar16[12 + j] = 0.0f;
+    }
+    return;
+  }
+  const PiTapeRow& tr = q.tape[it];
+  PbState& st = *q.state;
+  if (tr.count <= 0) {   // no inlier: T_{k+1} = T_k, the adjoint passes through
+    for (int i = 0; i < 12; ++i) st.Tb[i] = Tb[i];
+    for (int i = 0; i < 6; ++i) { st.u[i] = 0.0; st.xi[i] = 0.0; }
+    st.active = 0;
+    return;
+  }
+  double xi[6], Tk[16], E[16], Eb[16], xb[6], u[6], Hm[36];
+  for (int i = 0; i < 6; ++i) xi[i] = (double)tr.xi[i];
+  for (int i = 0; i < 16; ++i) Tk[i] = (double)tr.T[i];
+  // Eb = Tb T_k^T (the bottom row of Tb is zero), xib = the adjoint of exp at xi
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) {
+      double acc = 0.0;
+      for (int m = 0; m < 4; ++m) acc += Tb[4 * i + m] * Tk[4 * j + m];
+      Eb[4 * i + j] = acc;
+    }
+  d_se3_exp_adjoint(xi, Eb, xb);
+  // u = (A + damp I)^-1 xib: the forward's system (the float32 roundings of S and of the damped diagonal included)
+  int t = 0;
+  for (int r = 0; r < 6; ++r)
+    for (int c = r; c < 6; ++c) {
+      const float v = (float)tr.S[t];
+      ++t;
+      Hm[6 * r + c] = Hm[6 * c + r] = (double)(r == c ? v + pb.damp : v);
+    }
+  d_solve6(Hm, xb, u);
+  // Tb <- exp(xi)^T Tb
+  d_se3_exp(xi, E);
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 4; ++j) {
+      double acc = 0.0;
+      for (int m = 0; m < 3; ++m) acc += E[4 * m + i] * Tb[4 * m + j];
+      st.Tb[4 * i + j] = acc;
+    }
+  for (int i = 0; i < 6; ++i) { st.u[i] = u[i]; st.xi[i] = xi[i]; }
+  st.active = 1;
+}
+
+// Point stage of iteration `it`.  first: the first point stage of the call (vacc is written, not added to);
+// last: iteration 0 (vertex_bar is rounded and stored).
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_bwd_point_kernel(const PbBatch pb, const int it, const int first,
+                                                                        const int last) {
+  __shared__ GsCamera cam;
+  __shared__ float Ts[12];
+  __shared__ double ux[12];   // u(6), xi(6)
+  __shared__ int active;
+  __shared__ double red[GS_PI_CHUNK / GS_WAVE][PB_NV];
+  const PbSeq& q = pb.s[blockIdx.x % pb.B];
+  const int chunk = blockIdx.x / pb.B;
+  if (threadIdx.x == 0) {
+    cam = gs_camera(q.model_pose16, q.K16);
+    active = q.state->active;
+  }
+  if (threadIdx.x >= GS_WAVE && threadIdx.x < GS_WAVE + 12) Ts[threadIdx.x - GS_WAVE] = q.tape[it].T[threadIdx.x - GS_WAVE];
+  if (threadIdx.x >= 2 * GS_WAVE && threadIdx.x < 2 * GS_WAVE + 12) {
+    const int i = threadIdx.x - 2 * GS_WAVE;
+    ux[i] = i < 6 ? q.state->u[i] : q.state->xi[i - 6];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & (GS_WAVE - 1), wave = threadIdx.x / GS_WAVE;
+  const int k = chunk * GS_PI_CHUNK + (int)threadIdx.x;
+  const bool in_lattice = k < pb.nslots;
+  bool used = false;
+  double sb[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
+  int64_t p = 0;
+  if (in_lattice) {
+    const int i = k / pb.Wl, j = k - i * pb.Wl;
+    p = (int64_t)(i * pb.stride) * pb.W + j * pb.stride;
+    if (active) {   // (block-uniform; an iteration without inliers has no used slot)
+      const int64_t n_map = gs_count(q.n);
+      int64_t row;
+      float sf[3];
+      float4 df, mf;
+      used = pi_associate(Ts, cam, q.vertex, q.normal, q.depth, q.index, q.points, q.normals, n_map, p, pb.H, pb.W,
+                          pb.u_hi, pb.v_hi, pb.dist_th, pb.dot_th, row, sf, df, mf) == 0;
+      if (used) {
+        double s[3], a[6];
+        const double d[3] = {(double)df.x, (double)df.y, (double)df.z}, m[3] = {(double)mf.x, (double)mf.y, (double)mf.z};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = (double)q.vertex[3 * p + c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          s[c] = (double)Ts[4 * c] * v[0] + (double)Ts[4 * c + 1] * v[1] + (double)Ts[4 * c + 2] * v[2] + (double)Ts[4 * c + 3];
+        a[0] = m[0]; a[1] = m[1]; a[2] = m[2];
+        a[3] = s[1] * m[2] - s[2] * m[1];
+        a[4] = s[2] * m[0] - s[0] * m[2];
+        a[5] = s[0] * m[1] - s[1] * m[0];
+        const double r[3] = {d[0] - s[0], d[1] - s[1], d[2] - s[2]};
+        const double b = m[0] * r[0] + m[1] * r[1] + m[2] * r[2];
+        double cc = 0.0, e = 0.0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          cc += ux[6 + c] * a[c];
+          e += ux[c] * a[c];
+        }
+        double ab[6];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) ab[c] = (b - cc) * ux[c] - e * ux[6 + c];
+        const double* w = ab + 3;
+        sb[0] = (m[1] * w[2] - m[2] * w[1]) - e * m[0];
+        sb[1] = (m[2] * w[0] - m[0] * w[2]) - e * m[1];
+        sb[2] = (m[0] * w[1] - m[1] * w[0]) - e * m[2];
+        if (q.pbar) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) atomicAdd(&q.pbar[3 * row + c], e * m[c]);
+        }
+        if (q.mbar) {
+          const double wxs[3] = {w[1] * s[2] - w[2] * s[1], w[2] * s[0] - w[0] * s[2], w[0] * s[1] - w[1] * s[0]};
+#pragma unroll
+          for (int c = 0; c < 3; ++c) atomicAdd(&q.mbar[3 * row + c], ab[c] + wxs[c] + e * r[c]);
+        }
+      }
+    }
+    if (q.vacc) {   // a slot is its own pixel and the iterations are serialised: no atomics
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        double acc = first ? 0.0 : q.vacc[3 * (int64_t)k + c];
+        if (used) acc += (double)Ts[c] * sb[0] + (double)Ts[4 + c] * sb[1] + (double)Ts[8 + c] * sb[2];
+        if (last) q.vertex_bar[3 * p + c] = (float)acc;
+        else q.vacc[3 * (int64_t)k + c] = acc;
+      }
+    }
+  }
+  // the 12 sums of sb [v^T 1] in the forward's reduction shape; a wave without a used slot adds up +0.0 only
+  const bool any = __ballot(used) != 0ull;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double x = pi_wave_tree(sb[r] * v[c], any);
+      if (lane == 0) red[wave][3 * r + c] = x;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double x = pi_wave_tree(sb[r], any);
+    if (lane == 0) red[wave][9 + r] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < PB_NV)
+    q.partials[(int64_t)chunk * PB_NV + threadIdx.x] =
+        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(256) gs_picp_bwd_cast_kernel(const double* __restrict__ in, int64_t n,
+                                                               float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = (float)in[i];
+}
+
+// scratch of one sequence: state | partials (nchunks, 12) | vacc (nslots, 3) | pbar (n_map, 3) | mbar (n_map, 3)
+static size_t pb_partials_bytes(int64_t nchunks) { return gs_align((size_t)nchunks * PB_NV * sizeof(double)); }
+static size_t pb_rows_bytes(int64_t rows) { return gs_align((size_t)(rows > 0 ? rows : 0) * 3 * sizeof(double)); }
+
+extern "C" int64_t gs_projective_icp_backward_scratch_bytes(int H, int W, int stride, int64_t n_map) {
+  if (H <= 0 || W <= 0 || stride <= 0 || n_map < 0 || (int64_t)H * W >= (1ll << 31)) return 0;
+  const int64_t nslots = picp_slots(H, W, stride), nchunks = gs_ceil_div(nslots, GS_PI_CHUNK);
+  return (int64_t)(gs_align(sizeof(PbState)) + pb_partials_bytes(nchunks) + pb_rows_bytes(nslots) +
+                   2 * pb_rows_bytes(n_map));
+}
+
+extern "C" int gs_projective_icp_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
+                                                    const gs_picp_params* params_host, void* stream) {
+  GS_REQUIRE(seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
+  GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
+  const gs_picp_params& prm = *params_host;
+  GS_REQUIRE(prm.stride >= 1, "stride must be at least 1");
+  GS_REQUIRE(prm.numiters >= 1, "numiters must be at least 1");
+  GS_REQUIRE(prm.damp > 0.0f && prm.damp < __builtin_inff(), "damp must be positive and finite");
+  GS_REQUIRE(!(prm.dist_th != prm.dist_th) && !(prm.dot_th != prm.dot_th), "a threshold is NaN");
+  const int64_t nslots = picp_slots(H, W, prm.stride), nchunks = gs_ceil_div(nslots, GS_PI_CHUNK);
+  for (int b = 0; b < B; ++b) {
+    const gs_picp_backward_seq& u = seqs_host[b];
+    GS_REQUIRE(u.vertex && u.normal && u.depth && u.K16 && u.index && u.model_pose16 && u.tape && u.pose_bar16 &&
+                   u.scratch,
+               "NULL pointer");
+    GS_REQUIRE(((uintptr_t)u.tape & 7) == 0 && ((uintptr_t)u.scratch & 7) == 0, "misaligned tape or scratch");
+    GS_REQUIRE(u.map.n_bound >= 0, "bad map size");
+    GS_REQUIRE(u.map.n_bound == 0 || (u.map.points && u.map.normals), "NULL pointer (map points / normals)");
+    const bool want_map = u.points_bar || u.normals_bar;
+    GS_REQUIRE(u.scratch_bytes >= gs_projective_icp_backward_scratch_bytes(H, W, prm.stride, want_map ? u.map.n_bound : 0),
+               "scratch too small");
+  }
+  hipStream_t st = gs_stream(stream);
+  for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
+    const int nb = B - c0 < GS_MAX_BATCH ? B - c0 : GS_MAX_BATCH;
+    PbBatch pb;
+    pb.B = nb; pb.H = H; pb.W = W; pb.stride = prm.stride;
+    pb.Wl = (int)gs_ceil_div(W, prm.stride);
+    pb.nslots = (int)nslots; pb.nchunks = (int)nchunks; pb.numiters = prm.numiters;
+    pb.u_hi = (float)((double)W - 0.999); pb.v_hi = (float)((double)H - 0.999);
+    pb.dist_th = prm.dist_th; pb.dot_th = prm.dot_th; pb.damp = prm.damp;
+    for (int b = 0; b < nb; ++b) {
+      const gs_picp_backward_seq& u = seqs_host[c0 + b];
+      PbSeq& s = pb.s[b];
+      s.vertex = u.vertex; s.normal = u.normal; s.depth = u.depth; s.K16 = u.K16; s.index = u.index;
+      s.model_pose16 = u.model_pose16; s.points = u.map.points; s.normals = u.map.normals;
+      s.n = GsCount{u.map.n_bound, u.map.n_dev};
+      s.tape = static_cast<const PiTapeRow*>(u.tape);
+      s.pose_bar16 = u.pose_bar16; s.vertex_bar = u.vertex_bar; s.init_pose_bar16 = u.init_pose_bar16;
+      char* p = static_cast<char*>(u.scratch);
+      s.state = reinterpret_cast<PbState*>(p); p += gs_align(sizeof(PbState));
+      s.partials = reinterpret_cast<double*>(p); p += pb_partials_bytes(nchunks);
+      s.vacc = u.vertex_bar ? reinterpret_cast<double*>(p) : nullptr; p += pb_rows_bytes(nslots);
+      const size_t map_bytes = (size_t)u.map.n_bound * 3 * sizeof(double);
+      s.pbar = (u.points_bar && u.map.n_bound > 0) ? reinterpret_cast<double*>(p) : nullptr;
+      s.mbar = (u.normals_bar && u.map.n_bound > 0) ? reinterpret_cast<double*>(p + pb_rows_bytes(u.map.n_bound)) : nullptr;
+      if (s.pbar) GS_HIP(hipMemsetAsync(s.pbar, 0, map_bytes, st));
+      if (s.mbar) GS_HIP(hipMemsetAsync(s.mbar, 0, map_bytes, st));
+      // pixels off the lattice get no gradient (the last point stage stores the lattice pixels)
+      if (u.vertex_bar && prm.stride > 1) GS_HIP(hipMemsetAsync(u.vertex_bar, 0, (size_t)H * W * 3 * sizeof(float), st));
+    }
+    const unsigned blocks = (unsigned)nb * (unsigned)nchunks;
+    for (int it = prm.numiters - 1; it >= 0; --it) {
+      const int first = it == prm.numiters - 1;
+      hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(PB_FIN), 0, st, pb, it, first ? 0 : 1);
+      hipLaunchKernelGGL(gs_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first, it == 0 ? 1 : 0);
+    }
+    hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(PB_FIN), 0, st, pb, -1, 1);
+    for (int b = 0; b < nb; ++b) {
+      const gs_picp_backward_seq& u = seqs_host[c0 + b];
+      const int64_t n3 = 3 * u.map.n_bound;
+      if (pb.s[b].pbar)
+        hipLaunchKernelGGL(gs_picp_bwd_cast_kernel, dim3((unsigned)gs_ceil_div(n3, 256)), dim3(256), 0, st, pb.s[b].pbar, n3,
+                           u.points_bar);
+      if (pb.s[b].mbar)
+        hipLaunchKernelGGL(gs_picp_bwd_cast_kernel, dim3((unsigned)gs_ceil_div(n3, 256)), dim3(256), 0, st, pb.s[b].mbar, n3,
+                           u.normals_bar);
+    }
+    GS_LAUNCH_CHECK();
+  }
+  return GS_OK;
+}

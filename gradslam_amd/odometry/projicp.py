@@ -2,7 +2,8 @@
 the reference has no counterpart).  The map is rendered at the previous pose (gs_render_map_dc_f32), every lattice pixel
 of the live frame is paired with the surfel that won the pixel it projects to under the current estimate, and
 point-to-plane Gauss-Newton steps with constant damping follow (gs_projective_icp_batch_f32) -- no nearest-neighbour
-search.  The result is detached: there is no backward pass."""
+search.  The result is detached unless `differentiable` is set: the poses are then on the autograd tape
+(ops.ProjectiveICPFunction, a HIP backward through the Gauss-Newton iterations)."""
 from typing import Optional, Union
 
 import torch
@@ -24,14 +25,24 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
         angle_thresh: ... and their normals are within this many degrees (0..90)
         stride: the live frame's [::stride, ::stride] lattice is the source set (None: every pixel)
         min_confidence, radius: forwarded to the render of the model view (`Pointclouds.render`)
+        differentiable: `localize` returns poses on the autograd tape: gradients reach the live frame's vertex map (and
+            through the frame maps its depth), `prev_poses` as the initial estimate, and the map's points and normals
+            where they require grad.  The association is hard and a constant of the gradient; the render that yields
+            the index image stays non-differentiable (`prev_poses` as the pose of the model view gets no gradient).
+            The backward pass re-reads the map rows, so run it before the map is changed in place (a
+            non-differentiable in-place `step`, `prune_`); a backward after such a change raises instead of returning
+            gradients of the wrong rows.  A map update that itself ran on the tape hands the map new tensors and
+            leaves the saved ones intact: the backward of a loss over several such frames works.
 
     Unlike the point-cloud-pair providers it needs the map and the live frame themselves: call
     `localize(pointclouds, live_frame, prev_poses)`."""
 
     def __init__(self, numiters: int = 10, damp: float = 1e-8, dist_thresh: Union[float, int] = 0.1,
                  angle_thresh: Union[float, int] = 30, stride: Optional[int] = None,
-                 min_confidence: Union[float, int] = 0.0, radius: int = 0):
+                 min_confidence: Union[float, int] = 0.0, radius: int = 0, differentiable: bool = False):
         from .. import ops
+        if not isinstance(differentiable, bool):
+            raise TypeError("differentiable must be of type bool; but was of type {}.".format(type(differentiable)))
         ops._picp_args(1 if stride is None else stride, numiters, damp, dist_thresh, angle_thresh)
         self.numiters = numiters
         self.damp = damp
@@ -40,6 +51,7 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
         self.stride = stride
         self.min_confidence = min_confidence
         self.radius = radius
+        self.differentiable = differentiable
 
     def _kwargs(self):
         return dict(stride=1 if self.stride is None else self.stride, numiters=self.numiters, damp=self.damp,
@@ -79,6 +91,22 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             # the index image is all the solve reads of the view: no colour, normal or confidence image is rendered
             conf = feats[b] if feats is not None and self.min_confidence > 0 else None
             maps.append((pointclouds._buf["points"][b], pointclouds._buf["normals"][b], None, conf, bound, n_dev))
+        if self.differentiable:
+            # the render stays off the tape (the winners are constants): it sees detached tensors and does not warn
+            view = ops.render_map_batch([(m[0].detach(), None) + m[2:] for m in maps], poses.detach().view(B, 1, 4, 4), K,
+                                        H, W, radius=self.radius, min_confidence=self.min_confidence)
+            key = pointclouds._rewrites()
+
+            def guard():
+                if pointclouds._rewrites() != key:
+                    raise RuntimeError("the map was changed in place after localize(differentiable=True) and before its "
+                                       "backward pass: the saved association no longer belongs to the map rows (run "
+                                       "backward before the next in-place PointFusion.step or prune_, or keep the map "
+                                       "update on the autograd tape)")
+            T = ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
+                                         view.index[:, 0], poses.detach(), maps, poses, differentiable=True, guard=guard,
+                                         **self._kwargs())
+            return T.unsqueeze(1)
         view = ops.render_map_batch([(m[0], None) + m[2:] for m in maps], poses.view(B, 1, 4, 4), K, H, W,
                                     radius=self.radius, min_confidence=self.min_confidence)
         out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=poses.device)

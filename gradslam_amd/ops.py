@@ -1018,7 +1018,8 @@ def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_pos
 
 
 def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, init_poses, *, stride=1, numiters=10,
-                         damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False, out=None):
+                         damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False, out=None,
+                         differentiable=False, guard=None):
     """Frame-to-model tracking by projective data association for B sequences (gs_projective_icp_batch_f32: two launches
     per iteration for 8 sequences, nothing read back).  vertex / normal (B, H, W, 3): LOCAL maps of the live frames,
     depth (B, H, W), K (B, 4, 4); index (B, H, W) int64: the index image of render_map_batch at model_poses (B, 4, 4);
@@ -1027,8 +1028,31 @@ def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, ini
     carried by the current estimate into the model view and paired with the map row that won the pixel it lands on, if
     that row is within dist_thresh metres and angle_thresh degrees (normals); numiters point-to-plane Gauss-Newton steps
     with constant damping follow.  Returns the poses (B, 4, 4), detached; with return_trace also (B, numiters, 8) rows
-    [inliers, sum of squared residuals, xi(6)].  An iteration without inliers leaves the pose as it is."""
+    [inliers, sum of squared residuals, xi(6)].  An iteration without inliers leaves the pose as it is.
+    differentiable=True: the same pose bits, on the autograd tape (ProjectiveICPFunction: gradients reach vertex, the map
+    points and normals and init_poses; the association, depth, K, model_poses and the live normals are constants);
+    `out` is then refused.  guard: see ProjectiveICPFunction."""
+    if not isinstance(differentiable, bool):
+        raise TypeError("projective_icp: differentiable must be of type bool; but was of type {}.".format(
+            type(differentiable)))
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
+    if differentiable:
+        if out is not None:
+            raise ValueError("projective_icp: out= cannot be combined with differentiable=True (autograd owns the "
+                             "outputs)")
+        cfg = dict(stride=stride, numiters=numiters, damp=damp, dist_thresh=dist_thresh, angle_thresh=angle_thresh,
+                   guard=guard, counts=[(m[-2], m[-1]) for m in maps])
+        flat = [t for m in maps for t in m[:2]]
+        T, trace = ProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses, cfg, *flat)
+        return (T, trace) if return_trace else T
+    return _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, numiters, damp, dist_th,
+                       dot_th, return_trace, out, None)
+
+
+def _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, numiters, damp, dist_th, dot_th,
+                return_trace, out, tapes):
+    """the solve behind projective_icp_batch and ProjectiveICPFunction.forward; tapes: None, or the uint8 (B, tape bytes)
+    buffer the taped entry fills (the same kernels and pose bits)"""
     seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp", vertex, normal, depth, K, index, model_poses, maps,
                                            init_poses, stride)
     T = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if out is None else out
@@ -1039,15 +1063,131 @@ def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, ini
         seqs[b].out_pose16 = T.data_ptr() + b * 64
         seqs[b].trace = 0 if trace is None else trace.data_ptr() + b * int(numiters) * PICP_TRACE * 4
     prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
-    check(lib().gs_projective_icp_batch_f32(seqs, Bn, H, W, prm, stream(dev)), "gs_projective_icp_batch_f32")
+    if tapes is not None:
+        ptrs = (_C.C.c_void_p * Bn)(*[tapes.data_ptr() + b * tapes.shape[1] for b in range(Bn)])
+        check(lib().gs_projective_icp_tape_batch_f32(seqs, ptrs, Bn, H, W, prm, stream(dev)),
+              "gs_projective_icp_tape_batch_f32")
+    else:
+        check(lib().gs_projective_icp_batch_f32(seqs, Bn, H, W, prm, stream(dev)), "gs_projective_icp_batch_f32")
     return (T, trace) if return_trace else T
 
 
+def projective_icp_tape_bytes(numiters):
+    """bytes of one sequence's forward tape (328 per iteration: the pose, the 28 sums, the step, the inlier count)"""
+    return int(lib().gs_projective_icp_tape_bytes(int(numiters)))
+
+
+def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, maps, tapes, pose_bar, *, stride=1,
+                                  numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, want_vertex=True,
+                                  want_init=True, want_maps=None):
+    """Reverse mode of projective_icp_batch (gs_projective_icp_backward_batch_f32), arguments as the forward's; tapes:
+    the (B, projective_icp_tape_bytes(numiters)) uint8 buffer the taped forward filled; pose_bar (B, 4, 4): the adjoint of
+    the poses.  want_maps: per sequence (points, normals) flags, default all True.  Returns (vertex_bar (B, H, W, 3) or
+    None, per sequence (points_bar, normals_bar) of the buffers' shapes (None where not wanted), init_pose_bar (B, 4, 4)
+    or None).  vertex_bar and init_pose_bar are bitwise reproducible, the map gradients up to the order of float64
+    additions.  An output that is not wanted costs nothing: without map outputs nothing of map size is allocated."""
+    dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
+    with torch.no_grad():
+        seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp_backward", vertex, normal, depth, K, index, model_poses,
+                                               maps, pose_bar, stride)
+    if not torch.is_tensor(tapes) or tapes.dtype != torch.uint8 or tapes.ndim != 2 or not tapes.is_contiguous() or \
+            tuple(tapes.shape) != (Bn, projective_icp_tape_bytes(numiters)) or tapes.device != dev:
+        raise ValueError("projective_icp_backward: tapes must be the contiguous uint8 (B, %d) buffer of the taped forward"
+                         % projective_icp_tape_bytes(numiters))
+    want_maps = [(True, True)] * Bn if want_maps is None else [tuple(bool(x) for x in w) for w in want_maps]
+    if len(want_maps) != Bn:
+        raise ValueError("projective_icp_backward: want_maps needs one (points, normals) pair per sequence")
+    pose_bar = held[6]   # (contiguous float32, as _picp_seqs made it)
+    vertex_bar = torch.empty((Bn, H, W, 3), dtype=f32, device=dev) if want_vertex else None
+    init_bar = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if want_init else None
+    ws = Workspace.get(dev)
+    L = lib()
+    bseqs = (_C.PicpBackwardSeq * Bn)()
+    rows_out = []
+    for b in range(Bn):
+        u, f = bseqs[b], seqs[b]
+        u.vertex, u.normal, u.depth, u.K16, u.index, u.model_pose16 = f.vertex, f.normal, f.depth, f.K16, f.index, \
+            f.model_pose16
+        u.map = f.map
+        P, N = maps[b][0], maps[b][1]
+        n_bound = int(f.map.n_bound)
+        outs = []
+        for t, w in zip((P, N), want_maps[b]):
+            g = None
+            if w:
+                g = torch.empty((int(t.shape[0]), 3), dtype=f32, device=dev)
+                if n_bound < g.shape[0]:
+                    g[n_bound:].zero_()   # (rows of the buffer behind the bound: the kernel writes the first n_bound rows)
+            outs.append(g)
+        rows_out.append(tuple(outs))
+        u.tape = tapes.data_ptr() + b * tapes.shape[1]
+        u.pose_bar16 = pose_bar.data_ptr() + b * 64
+        u.vertex_bar = None if vertex_bar is None else vertex_bar.data_ptr() + b * H * W * 12
+        u.points_bar, u.normals_bar = (None if g is None else g.data_ptr() for g in outs)
+        u.init_pose_bar16 = None if init_bar is None else init_bar.data_ptr() + b * 64
+        nbytes = L.gs_projective_icp_backward_scratch_bytes(H, W, int(stride), n_bound if any(want_maps[b]) else 0)
+        buf = ws.bytes("picp_bwd%d" % b, nbytes)
+        u.scratch, u.scratch_bytes = buf.data_ptr(), int(buf.numel())
+    prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
+    check(L.gs_projective_icp_backward_batch_f32(bseqs, Bn, H, W, prm, stream(dev)),
+          "gs_projective_icp_backward_batch_f32")
+    return vertex_bar, rows_out, init_bar
+
+
+class ProjectiveICPFunction(torch.autograd.Function):
+    """projective_icp_batch on the autograd tape: forward = gs_projective_icp_tape_batch_f32 (the plain solve's kernels
+    and pose bits, plus the tape), backward = one call of gs_projective_icp_backward_batch_f32.  Inputs: vertex, normal,
+    depth, K, index, model_poses, init_poses, cfg (the keyword arguments, `counts` = per sequence (n_bound, n_dev) and
+    `guard`), then points and normals of every sequence's map.  Gradients reach vertex, init_poses and the map points /
+    normals that require grad (needs_input_grad decides which outputs the kernel is asked for); the association is hard
+    and a constant, as are depth, K, model_poses and the live normals.  The backward re-reads the map rows, so the map
+    buffers must hold at backward time what they held at the forward; in-place steps write through raw pointers, which
+    torch's version counters do not see, so a caller that can tell passes `guard`, a callable that raises when the map
+    has changed (ProjectiveICPOdometryProvider does).  Returns (poses (B, 4, 4), trace (B, numiters, 8), not
+    differentiable)."""
+
+    @staticmethod
+    def forward(ctx, vertex, normal, depth, K, index, model_poses, init_poses, cfg, *flat):
+        Bn = len(flat) // 2
+        kw = {k: cfg[k] for k in ("stride", "numiters", "damp", "dist_thresh", "angle_thresh")}
+        maps = [(flat[2 * b], flat[2 * b + 1]) + tuple(cfg["counts"][b]) for b in range(Bn)]
+        tapes = torch.empty((int(depth.shape[0]), projective_icp_tape_bytes(kw["numiters"])), dtype=torch.uint8,
+                            device=depth.device)
+        dist_th, dot_th = _picp_args(kw["stride"], kw["numiters"], kw["damp"], kw["dist_thresh"], kw["angle_thresh"])
+        T, trace = _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, kw["stride"],
+                               kw["numiters"], kw["damp"], dist_th, dot_th, True, None, tapes)
+        ctx.save_for_backward(vertex, normal, depth, K, index, model_poses, tapes, *flat,
+                              *[c[1] for c in cfg["counts"]])
+        ctx.kw, ctx.bounds, ctx.guard = kw, [c[0] for c in cfg["counts"]], cfg.get("guard")
+        ctx.mark_non_differentiable(trace)
+        return T, trace
+
+    @staticmethod
+    def backward(ctx, T_bar, _trace_bar):
+        if ctx.guard is not None:
+            ctx.guard()
+        saved = ctx.saved_tensors
+        vertex, normal, depth, K, index, model_poses, tapes = saved[:7]
+        Bn = len(ctx.bounds)
+        flat, n_devs = saved[7:7 + 2 * Bn], saved[7 + 2 * Bn:]
+        need = ctx.needs_input_grad
+        want_maps = [(bool(need[8 + 2 * b]), bool(need[9 + 2 * b])) for b in range(Bn)]
+        if T_bar is None or not (need[0] or need[6] or any(any(w) for w in want_maps)):
+            return (None,) * (8 + 2 * Bn)
+        maps = [(flat[2 * b], flat[2 * b + 1], ctx.bounds[b], n_devs[b]) for b in range(Bn)]
+        vb, rows, ib = projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, maps, tapes, T_bar,
+                                                     want_vertex=bool(need[0]), want_init=bool(need[6]),
+                                                     want_maps=want_maps, **ctx.kw)
+        return (vb, None, None, None, None, None, ib, None) + tuple(g for r in rows for g in r)
+
+
 def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, *, n_dev=None,
-                   stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False):
+                   stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False,
+                   differentiable=False):
     """projective_icp_batch for one sequence without the batch dimension: vertex / normal (H, W, 3), depth (H, W), K /
     model_pose / init_pose (4, 4), index (H, W) int64; n_dev: device int64[1] holding the actual row count of the map
-    (map_points.shape[0] is then an upper bound).  Returns the pose (4, 4) (and the trace (numiters, 8))."""
+    (map_points.shape[0] is then an upper bound).  Returns the pose (4, 4) (and the trace (numiters, 8)).
+    differentiable: see projective_icp_batch."""
     for name, t in (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                     ("model_pose", model_pose), ("init_pose", init_pose)):
         if not torch.is_tensor(t):
@@ -1055,7 +1195,8 @@ def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_
     r = projective_icp_batch(vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0), K.reshape(1, 4, 4),
                              index.unsqueeze(0), model_pose.reshape(1, 4, 4), [(map_points, map_normals, None, n_dev)],
                              init_pose.reshape(1, 4, 4), stride=stride, numiters=numiters, damp=damp,
-                             dist_thresh=dist_thresh, angle_thresh=angle_thresh, return_trace=return_trace)
+                             dist_thresh=dist_thresh, angle_thresh=angle_thresh, return_trace=return_trace,
+                             differentiable=differentiable)
     return (r[0][0], r[1][0]) if return_trace else r[0]
 
 

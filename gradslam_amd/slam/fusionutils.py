@@ -406,6 +406,7 @@ def _aggregate_differentiable(pointclouds, rgbdimages, inplace):
         out._buf[k] = new[k]
     out._n = [t.shape[0] for t in new["points"]]
     out._invalidate()
+    out._taped_swaps += 1   # (new tensors, out of place: a backward that saved the old ones is still valid)
     return out
 
 
@@ -494,6 +495,7 @@ def _fuse_differentiable(pointclouds, rgbdimages, dist_th, dot_th, sigma, inplac
         out._buf[k] = new[k]
     out._n = [t.shape[0] for t in new["points"]]
     out._invalidate()
+    out._taped_swaps += 1   # (new tensors, out of place: a backward that saved the old ones is still valid)
     return out
 
 

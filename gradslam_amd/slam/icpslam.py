@@ -27,13 +27,26 @@ class ICPSLAM(nn.Module):
     subset of the keys; the rest take the defaults of `RGBDImages.bilateral_filter`) every `step` works on the
     bilaterally filtered copy of the live frame -- localisation and map update alike -- and writes the recovered pose
     back to the caller's frame.  `prev_frame` is only read for its poses and is not filtered.  With `depth_filter=None`
-    a step makes no new call."""
+    a step makes no new call.
+
+    `odom_differentiable` (off by default, `odom="projicp"` only): the projective ICP runs on the autograd tape
+    (`ProjectiveICPOdometryProvider(differentiable=True)`): the poses of `forward` and of `step` carry a `grad_fn`, and a
+    loss on them reaches the depth of the frames, the initial pose and a map that requires grad.  With it off the poses
+    are detached, bit for bit what they are with it on."""
 
     def __init__(self, *, odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0,
                  B: Union[float, int] = 1.0, B2: Union[float, int] = 1.0, nu: Union[float, int] = 200.0,
-                 device: Union[torch.device, str, None] = None, depth_filter: Optional[dict] = None):
+                 device: Union[torch.device, str, None] = None, depth_filter: Optional[dict] = None,
+                 odom_differentiable: bool = False):
         super().__init__()
+        if not isinstance(odom_differentiable, bool):
+            raise TypeError("odom_differentiable must be of type bool; but was of type {}.".format(
+                type(odom_differentiable)))
+        if odom_differentiable and odom != "projicp":
+            raise ValueError("odom_differentiable is the switch of odom='projicp' (got odom={!r}): 'icp' and 'gradicp' "
+                             "go on the autograd tape by themselves when an input requires grad".format(odom))
+        self.odom_differentiable = odom_differentiable
         self.depth_filter = _check_depth_filter(depth_filter)
         if odom not in ["gt", "icp", "gradicp", "projicp"]:
             msg = "odometry method ({}) not supported for PointFusion. ".format(odom)
@@ -48,7 +61,7 @@ class ICPSLAM(nn.Module):
             # frame-to-model tracking against the rendered map: dsratio is the lattice stride, dist_thresh=None the
             # provider's 0.1 m (the gate is part of the association, it cannot be switched off)
             odomprov = ProjectiveICPOdometryProvider(numiters, damp, 0.1 if dist_thresh is None else dist_thresh,
-                                                     stride=dsratio)
+                                                     stride=dsratio, differentiable=odom_differentiable)
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio
@@ -121,8 +134,8 @@ class ICPSLAM(nn.Module):
             return live_frame.poses
 
         if self.odom == "projicp":
-            # the model view at the previous pose is target and initial guess; the result is detached (a requires-grad
-            # input warns): there is no backward pass
+            # the model view at the previous pose is target and initial guess; without odom_differentiable the result is
+            # detached (a requires-grad input warns)
             return self.odomprov.localize(pointclouds, live_frame, prev_frame.poses[:, :1])
 
         if self.odom in ["icp", "gradicp"]:

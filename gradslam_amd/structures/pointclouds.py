@@ -149,6 +149,8 @@ class Pointclouds(object):
         self._n_host: List[int] = []            # points per sequence (see the `_n` property)
         self._padded_cache = {}
         self._generation = 0   # bumped by everything that changes the map in place (see render(differentiable=True))
+        self._taped_swaps = 0  # of those, the ones that leave the old buffers as they were: taped map updates (new
+        #                        autograd tensors) and read-backs of the device counts (_rewrites)
         self._marks = None      # (B, MAX_MARKS) int64 on self.device: the counts at the last _n_marks epochs (mark_epoch)
         self._n_marks = 0
         self._prune_steps = 0   # steps a pruning PointFusion has taken on this map (the step counter lives with the map)
@@ -216,6 +218,7 @@ class Pointclouds(object):
                 self._n_host[b] = exact[id(dc.group)][dc.index]
             self._dcount = {}
             self._invalidate()
+            self._taped_swaps += 1   # (a count read back: the buffers hold what they held, see _rewrites)
         return self._n_host
 
     @_n.setter
@@ -404,6 +407,13 @@ class Pointclouds(object):
         self._generation += 1
         self._padded_cache.clear()
         self.equisized = (len(set(self._n)) == 1) if self._n else None
+
+    def _rewrites(self):
+        """How often the buffers were rewritten or exchanged behind autograd's back (in-place steps through raw
+        pointers, reallocation, prune_).  A taped map update (_fuse_differentiable / _aggregate_differentiable) hands
+        the object new autograd tensors and leaves the old ones -- which a saved backward holds -- as they were, and
+        reading `_n` only resolves device-side counts: both count in _generation but not here (the guard of ProjectiveICPOdometryProvider.localize)."""
+        return self._generation - self._taped_swaps
 
     RESERVE_FRAMES = 16   # capacity a SLAM driver asks for up front, in frames (see _reserve)
 

@@ -747,6 +747,52 @@ GS_API int gs_projective_icp_rows_f32(const gs_picp_seq* seq_host, int H, int W,
                                       float dot_th, int32_t* code, int64_t* row, float* a6, float* b, double* sums28,
                                       int64_t* count, void* stream);
 
+/* ------------------------------------------------------------------ projective ICP: taped forward and backward ------
+ * gs_projective_icp_tape_batch_f32 is gs_projective_icp_batch_f32 (same kernels, the same pose and trace bits) whose
+ * finish kernel also writes, per iteration, the pose it linearised at (16 floats), the 28 float64 sums, the step xi (6
+ * floats, 0 without inliers) and the inlier count to tapes_host[b], a device buffer of
+ * gs_projective_icp_tape_bytes(numiters) bytes (328 per iteration: double S[28], float T[16], float xi[6], float pad[2],
+ * int64 count), 8-byte aligned.
+ *
+ * gs_projective_icp_backward_batch_f32 is the reverse-mode pass through the numiters iterations: from pose_bar16 =
+ * dL/d(out_pose) (its top three rows are read) to vertex_bar (H, W, 3; zero off the lattice), points_bar / normals_bar
+ * (the first map.n_bound rows are written) and init_pose_bar16 (top three rows, a zero bottom row).  Differentiated per
+ * used slot: s = R v + t, a = [m ; s x m], b = m . (p - s), A = sum a a^T, g = sum a b, xi = (A + damp I)^-1 g,
+ * T <- exp(xi) T.  Constants: which slots are used and their rows (codes 1-5, both gates, the projection, the index
+ * image), the device count, K, model_pose, depth and the live normal; the float32 roundings of the forward are treated as
+ * the identity; an iteration without inliers passes the adjoint through.  The association is recomputed with the
+ * forward's device functions at the taped float32 pose, so the inputs (the map rows included) must hold what they held
+ * at the forward; a stale index entry is never dereferenced.  float64 inside, rounded once.  vertex_bar and
+ * init_pose_bar16 are bitwise reproducible (the forward's fixed reduction shape, no atomics); points_bar / normals_bar
+ * are float64 atomic adds, reproducible up to the order of the float64 additions.  Any output may be NULL: its work and
+ * its buffer are skipped (with both map outputs NULL nothing of map size is touched).  scratch:
+ * gs_projective_icp_backward_scratch_bytes(H, W, stride, n_map) bytes per sequence, n_map = map.n_bound when a map output
+ * is asked for, else 0; scratch_bytes is what the caller provides and is checked.  8 sequences per launch, 2 numiters + 1
+ * launches (plus one per map output), nothing read back.  Every argument is checked before the first HIP call. */
+typedef struct gs_picp_backward_seq {
+  const float* vertex;        /* the forward's inputs, as in gs_picp_seq */
+  const float* normal;
+  const float* depth;
+  const float* K16;
+  const int64_t* index;
+  const float* model_pose16;
+  gs_map_view map;
+  const void* tape;           /* what the taped forward wrote */
+  const float* pose_bar16;    /* upstream adjoint of the pose */
+  float* vertex_bar;          /* out (H, W, 3), or NULL */
+  float* points_bar;          /* out (n_bound, 3), or NULL */
+  float* normals_bar;         /* out (n_bound, 3), or NULL */
+  float* init_pose_bar16;     /* out (16), or NULL */
+  void* scratch;
+  int64_t scratch_bytes;
+} gs_picp_backward_seq;
+GS_API int64_t gs_projective_icp_tape_bytes(int numiters);
+GS_API int gs_projective_icp_tape_batch_f32(const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H, int W,
+                                            const gs_picp_params* params_host, void* stream);
+GS_API int64_t gs_projective_icp_backward_scratch_bytes(int H, int W, int stride, int64_t n_map);
+GS_API int gs_projective_icp_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
+                                                const gs_picp_params* params_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
