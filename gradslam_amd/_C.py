@@ -98,6 +98,11 @@ class PicpBackwardSeq(C.Structure):
                 ("scratch_bytes", C.c_int64)]
 
 
+class PicpColorSeq(C.Structure):
+    """gs_picp_color_seq: gs_picp_seq plus the live colour image and the model intensity of the view."""
+    _fields_ = [("base", PicpSeq), ("color", C.c_void_p), ("model_intensity", C.c_void_p)]
+
+
 class PicpParams(C.Structure):
     _fields_ = [("stride", C.c_int), ("numiters", C.c_int), ("damp", C.c_float), ("dist_th", C.c_float),
                 ("dot_th", C.c_float)]
@@ -198,13 +203,19 @@ _PROTOS = {
                                          C.POINTER(PicpParams), _vp],
     "gs_projective_icp_backward_scratch_bytes": [_i32, _i32, _i32, _i64],
     "gs_projective_icp_backward_batch_f32": [C.POINTER(PicpBackwardSeq), _i32, _i32, _i32, C.POINTER(PicpParams), _vp],
+    "gs_model_intensity_f32": [_vp, _vp, _i32, _i32, _i32, _vp, _vp],
+    "gs_projective_icp_color_scratch_bytes": [_i32, _i32, _i32],
+    "gs_projective_icp_color_batch_f32": [C.POINTER(PicpColorSeq), _i32, _i32, _i32, C.POINTER(PicpParams), _f, _vp],
+    "gs_projective_icp_color_rows_f32": [C.POINTER(PicpColorSeq), _i32, _i32, _i32, _f, _f, _f, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,
             "gs_knn1_grid_scratch_bytes": _i64, "gs_update_map_scratch_bytes": _i64, "gs_global_maps_pose_backward_scratch_bytes": _i64, "gs_icp_tape_bytes": _i64, "gs_icp_backward_scratch_bytes": _i64,
             "gs_localize_scratch_bytes": _i64, "gs_frame_maps_backward_kbar_scratch_bytes": _i64,
             "gs_render_scratch_bytes": _i64, "gs_render_backward_scratch_bytes": _i64,
             "gs_prune_scratch_bytes": _i64, "gs_projective_icp_scratch_bytes": _i64,
-            "gs_projective_icp_tape_bytes": _i64, "gs_projective_icp_backward_scratch_bytes": _i64}
+            "gs_projective_icp_tape_bytes": _i64, "gs_projective_icp_backward_scratch_bytes": _i64,
+            "gs_projective_icp_color_scratch_bytes": _i64}
 EXPORTS = tuple(_PROTOS)
 
 

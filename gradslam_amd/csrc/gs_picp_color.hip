@@ -1,0 +1,338 @@
+// gs_picp_color.hip — the projective ICP (gs_picp.hip) with a photometric term (Steinbruecker / Kerl; the hybrid odometry
+// of Kintinuous, ElasticFusion and Open3D): a slot of the live frame's lattice contributes its point-to-plane row and, where
+// the model view has an intensity gradient, a colour row against the rendered colour of the map.  The association, the
+// reject codes, the reduction order, the solve and the update are those of gs_picp.hip (gs_picp_dev.h: ONE definition of
+// each); what this file adds is
+//
+//   model intensity  one thread per pixel of the model view (a 32 x 8 tile with a one-pixel halo in LDS), batched over B:
+//                    (I, gx, gy, ok) of the rendered colour, once per localisation
+//   linearise        gs_picp_linearize_kernel's slot, plus the colour row: one 16-byte gather of the model pixel and the
+//                    three colour loads of the live pixel
+//   finish           pi_finish<true>: the plain finish, which also adds up the colour-row counts
+//
+// Two launches per iteration for up to 8 sequences, nothing read back, the map count read on the device.
+//
+// Arithmetic (-ffp-contract=off; float32, one rounding per operation, NO FMA anywhere in what this file adds: every product
+// and sum below is plain, every division the correctly rounded float32 '/'; tests/picp_color_ref.py restates it).
+// luma(R, G, B) = (0.299f * R + 0.587f * G) + 0.114f * B.
+// Model intensity at pixel (h, w), I = luma(color[h, w]):
+//   ok = 1.0f iff 0 < h < H - 1, 0 < w < W - 1 and index >= 0 at (h, w), (h, w - 1), (h, w + 1), (h - 1, w), (h + 1, w)
+//   gx = 0.5f * (I[h, w + 1] - I[h, w - 1]),  gy = 0.5f * (I[h + 1, w] - I[h - 1, w])   when ok, else gx = gy = +0.0f
+//   out[h, w] = (I, gx, gy, ok): I is the luma of whatever the render left at the pixel (0 in a hole); a hole of the view
+//   never leaks a gradient.
+// Colour row of a slot with code 0 (s, d, m of pi_associate), (q, h2, w2) = gs_project_point_hw_q(cam, s):
+//   (u, v) = the projector's continuous pixel: r_j = ((K[j,0] q0 + K[j,1] q1) + K[j,2] q2) + K[j,3] * 1, z = r_2 (1 if 0),
+//            u = r_0 / z, v = r_1 / z               (the operations of gs_project_point_hw_q, restated by pic_project_uv)
+//   (I, gx, gy, ok) = model[h2, w2]; the slot has a colour row iff ok == 1.0f
+//   Il = luma(color[pixel of the slot])
+//   r  = Il - ((I + gx * (u - (float)w2)) + gy * (v - (float)h2))
+//   ax = gx * K[0,0], ay = gy * K[1,1]
+//   Jq = (ax / q2, ay / q2, (-(ax * q0 + ay * q1)) / (q2 * q2))
+//   Js_j = (R_m[j,0] Jq0 + R_m[j,1] Jq1) + R_m[j,2] Jq2                    (gs_dot3_plain, R_m = the model pose's rotation)
+//   c  = s x Js with the operations of gn_row_pn: (Js2 s1 - Js1 s2, Js0 s2 - Js2 s0, Js1 s0 - Js0 s1)
+//   a_c = (w Js0, w Js1, w Js2, w c0, w c1, w c2),  b_c = w r,  w = color_weight (metres per intensity unit)
+// A slot without a colour row has a_c = b_c = +0.0f.
+// The 28 terms of a slot are (double)x_g (double)y_g + (double)x_c (double)y_c: two exact products of float32 factors,
+// their sum rounded once; a rejected slot contributes +0.0.  The reduction, the solve, the update and the "no geometric
+// inlier keeps the pose bits" rule are gs_picp.hip's; the colour rows are counted alongside as an integer.
+#include "gs_picp_dev.h"
+
+struct PicSeq {
+  PiSeq g;
+  const float* color;       // live frame (H, W, 3)
+  const float4* model;      // model intensity (H, W)
+  int32_t* ccounts;         // (nchunks) colour rows per chunk
+  int32_t* cflag_out;       // table-level outputs, any may be NULL: (nslots)
+  float* ac_out;            // (nslots, 6)
+  float* bc_out;            // (nslots)
+  int64_t* ccount_out;      // finish: (1), or NULL
+};
+struct PicBatch {
+  PicSeq s[GS_MAX_BATCH];
+  PiGeom g;
+  float weight;
+};
+
+GS_DEV float pic_luma(const float r, const float g, const float b) {
+  const float t = 0.299f * r + 0.587f * g;
+  return t + 0.114f * b;
+}
+
+// the continuous pixel (u, v) of the camera-frame point q: the operations of gs_project_point_hw_q
+GS_DEV void pic_project_uv(const GsCamera& c, const float* q, float& u, float& v) {
+  float r[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    float acc = c.K[4 * j] * q[0];
+    acc = acc + c.K[4 * j + 1] * q[1];
+    acc = acc + c.K[4 * j + 2] * q[2];
+    acc = acc + c.K[4 * j + 3] * 1.0f;
+    r[j] = acc;
+  }
+  const float zz = (r[2] != 0.0f) ? r[2] : 1.0f;
+  u = r[0] / zz;
+  v = r[1] / zz;
+}
+
+// ------------------------------------------------------------------ model intensity
+constexpr int PIC_TX = 32, PIC_TY = 8;   // 256 threads: a row of the tile is 32 pixels = 384 contiguous bytes of colour
+
+__global__ void __launch_bounds__(PIC_TX * PIC_TY) gs_picp_color_intensity_kernel(const float* __restrict__ color,
+                                                                                  const int64_t* __restrict__ index,
+                                                                                  float4* __restrict__ out, const int H,
+                                                                                  const int W) {
+  __shared__ float lum[PIC_TY + 2][PIC_TX + 2];
+  __shared__ uint8_t hit[PIC_TY + 2][PIC_TX + 2];
+  const int64_t img = (int64_t)blockIdx.z * H * W;
+  const int w0 = blockIdx.x * PIC_TX - 1, h0 = blockIdx.y * PIC_TY - 1;
+  for (int e = threadIdx.x; e < (PIC_TY + 2) * (PIC_TX + 2); e += PIC_TX * PIC_TY) {
+    const int ly = e / (PIC_TX + 2), lx = e - ly * (PIC_TX + 2);
+    const int h = h0 + ly, w = w0 + lx;
+    float I = 0.0f;
+    uint8_t ok = 0;
+    if (h >= 0 && h < H && w >= 0 && w < W) {
+      const int64_t p = img + (int64_t)h * W + w;
+      I = pic_luma(color[3 * p], color[3 * p + 1], color[3 * p + 2]);
+      ok = index[p] >= 0;
+    }
+    lum[ly][lx] = I;
+    hit[ly][lx] = ok;
+  }
+  __syncthreads();
+  const int lx = threadIdx.x % PIC_TX + 1, ly = threadIdx.x / PIC_TX + 1;
+  const int h = h0 + ly, w = w0 + lx;
+  if (h >= H || w >= W) return;
+  // (a neighbour outside the image has hit = 0)
+  const bool ok = hit[ly][lx] && hit[ly][lx - 1] && hit[ly][lx + 1] && hit[ly - 1][lx] && hit[ly + 1][lx];
+  float gx = 0.0f, gy = 0.0f;
+  if (ok) {
+    gx = 0.5f * (lum[ly][lx + 1] - lum[ly][lx - 1]);
+    gy = 0.5f * (lum[ly + 1][lx] - lum[ly - 1][lx]);
+  }
+  out[img + (int64_t)h * W + w] = make_float4(lum[ly][lx], gx, gy, ok ? 1.0f : 0.0f);
+}
+
+extern "C" int gs_model_intensity_f32(const float* color, const int64_t* index, int B, int H, int W, float* out,
+                                      void* stream) {
+  GS_REQUIRE(color && index && out, "NULL pointer");
+  GS_REQUIRE(B > 0 && H > 0 && W > 0, "bad sizes");
+  GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
+  GS_REQUIRE(((uintptr_t)out & 15) == 0, "out must be 16-byte aligned");
+  GS_REQUIRE(out != color, "out must not be an input");
+  hipStream_t st = gs_stream(stream);
+  const dim3 tiles((unsigned)gs_ceil_div(W, PIC_TX), (unsigned)gs_ceil_div(H, PIC_TY), 1);
+  GS_REQUIRE(tiles.y <= 65535u, "image too tall");
+  for (int b0 = 0; b0 < B; b0 += 65535) {   // (the z extent of a grid)
+    const int nb = B - b0 < 65535 ? B - b0 : 65535;
+    const int64_t off = (int64_t)b0 * H * W;
+    hipLaunchKernelGGL(gs_picp_color_intensity_kernel, dim3(tiles.x, tiles.y, (unsigned)nb), dim3(PIC_TX * PIC_TY), 0, st,
+                       color + 3 * off, index + off, reinterpret_cast<float4*>(out) + off, H, W);
+  }
+  GS_LAUNCH_CHECK();
+  return GS_OK;
+}
+
+// ------------------------------------------------------------------ the joint linearisation
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_color_linearize_kernel(const PicBatch pb) {
+  __shared__ GsCamera cam;
+  __shared__ float Ts[12];
+  __shared__ double red[GS_PI_CHUNK / GS_WAVE][LIN_NV];
+  __shared__ int cnt[GS_PI_CHUNK / GS_WAVE], ccnt[GS_PI_CHUNK / GS_WAVE];
+  const PicSeq& qc = pb.s[blockIdx.x % pb.g.B];
+  const PiSeq& q = qc.g;
+  const int chunk = blockIdx.x / pb.g.B;
+  if (threadIdx.x == 0) cam = gs_camera(q.model_pose16, q.K16);
+  if (threadIdx.x >= GS_WAVE && threadIdx.x < GS_WAVE + 12) Ts[threadIdx.x - GS_WAVE] = q.T_in[threadIdx.x - GS_WAVE];
+  __syncthreads();
+  const int lane = threadIdx.x & (GS_WAVE - 1), wave = threadIdx.x / GS_WAVE;
+  const int k = chunk * GS_PI_CHUNK + (int)threadIdx.x;
+  const bool in_lattice = k < pb.g.nslots;
+  const int64_t n_map = gs_count(q.n);
+  int code = 1;
+  bool colored = false;
+  int64_t row = -1;
+  float a[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, b = 0.0f;
+  float ac[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, bc = 0.0f;
+  if (in_lattice) {
+    const int i = k / pb.g.Wl, j = k - i * pb.g.Wl;
+    const int64_t p = (int64_t)(i * pb.g.stride) * pb.g.W + j * pb.g.stride;
+    float s[3];
+    float4 d, m;
+    code = pi_associate(Ts, cam, q.vertex, q.normal, q.depth, q.index, q.points, q.normals, n_map, p, pb.g.H, pb.g.W,
+                        pb.g.u_hi, pb.g.v_hi, pb.g.dist_th, pb.g.dot_th, row, s, d, m);
+    if (code == 0) {
+      gn_row_pn(s[0], s[1], s[2], d, m, a, b);
+      // the pixel the association read, again, with the camera-frame point (the same device function on the same
+      // operands: the same (h2, w2), inside the view -- the slot would be code 2 otherwise)
+      int h2 = 0, w2 = 0;
+      float cq[3];
+      gs_project_point_hw_q(cam, s[0], s[1], s[2], pb.g.H, pb.g.W, pb.g.u_hi, pb.g.v_hi, h2, w2, cq);
+      const float4 M = qc.model[(int64_t)h2 * pb.g.W + w2];   // (I, gx, gy, ok)
+      colored = M.w == 1.0f;
+      if (colored) {
+        float u, v;
+        pic_project_uv(cam, cq, u, v);
+        const float Il = pic_luma(qc.color[3 * p], qc.color[3 * p + 1], qc.color[3 * p + 2]);
+        const float lin = M.x + M.y * (u - (float)w2);
+        const float r = Il - (lin + M.z * (v - (float)h2));
+        const float ax = M.y * cam.K[0], ay = M.z * cam.K[5];
+        const float j0 = ax / cq[2], j1 = ay / cq[2];
+        const float j2 = (-(ax * cq[0] + ay * cq[1])) / (cq[2] * cq[2]);
+        // R_m[j][k] = cam.Ri[3 * k + j]
+        const float J0 = gs_dot3_plain(cam.Ri[0], cam.Ri[3], cam.Ri[6], j0, j1, j2);
+        const float J1 = gs_dot3_plain(cam.Ri[1], cam.Ri[4], cam.Ri[7], j0, j1, j2);
+        const float J2 = gs_dot3_plain(cam.Ri[2], cam.Ri[5], cam.Ri[8], j0, j1, j2);
+        const float wgt = pb.weight;
+        ac[0] = wgt * J0; ac[1] = wgt * J1; ac[2] = wgt * J2;
+        ac[3] = wgt * (J2 * s[1] - J1 * s[2]);
+        ac[4] = wgt * (J0 * s[2] - J2 * s[0]);
+        ac[5] = wgt * (J1 * s[0] - J0 * s[1]);
+        bc = wgt * r;
+      }
+    }
+    if (q.code_out) q.code_out[k] = code;
+    if (q.row_out) q.row_out[k] = row;
+    if (q.a_out) {
+#pragma unroll
+      for (int c = 0; c < 6; ++c) q.a_out[6 * (int64_t)k + c] = a[c];
+    }
+    if (q.b_out) q.b_out[k] = b;
+    if (qc.cflag_out) qc.cflag_out[k] = colored ? 1 : 0;
+    if (qc.ac_out) {
+#pragma unroll
+      for (int c = 0; c < 6; ++c) qc.ac_out[6 * (int64_t)k + c] = ac[c];
+    }
+    if (qc.bc_out) qc.bc_out[k] = bc;
+  }
+  const bool used = code == 0;   // (a, b, ac, bc are zero otherwise: every term below is then +0.0)
+  const unsigned long long mask = __ballot(used);
+  const unsigned long long cmask = __ballot(colored);
+  if (lane == 0) {
+    cnt[wave] = __popcll(mask);
+    ccnt[wave] = __popcll(cmask);
+  }
+  // a wave without a used slot adds up +0.0 only (a colour row needs a used slot): no shuffle needed
+  const bool any = mask != 0ull;
+  int t = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+#pragma unroll
+    for (int c = r; c < 6; ++c) {
+      const double x = pi_wave_tree((double)a[r] * (double)a[c] + (double)ac[r] * (double)ac[c], any);
+      if (lane == 0) red[wave][t] = x;
+      ++t;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    const double x = pi_wave_tree((double)a[r] * (double)b + (double)ac[r] * (double)bc, any);
+    if (lane == 0) red[wave][21 + r] = x;
+  }
+  {
+    const double x = pi_wave_tree((double)b * (double)b + (double)bc * (double)bc, any);
+    if (lane == 0) red[wave][27] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < LIN_NV)
+    q.partials[(int64_t)chunk * LIN_NV + threadIdx.x] =
+        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  if (threadIdx.x == GS_WAVE) q.counts[chunk] = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
+  if (threadIdx.x == GS_WAVE + 1) qc.ccounts[chunk] = (ccnt[0] + ccnt[1]) + (ccnt[2] + ccnt[3]);
+}
+
+__global__ void __launch_bounds__(GS_PI_FIN) gs_picp_color_finish_kernel(const PicBatch pb) {
+  const PicSeq& qc = pb.s[blockIdx.x];
+  pi_finish<true>(qc.g, pb.g.nchunks, pb.g.damp, qc.ccounts, qc.ccount_out);
+}
+
+// ------------------------------------------------------------------ entry points
+// scratch of a sequence: the plain solve's (partials, counts), then the colour-row counts
+extern "C" int64_t gs_projective_icp_color_scratch_bytes(int H, int W, int stride) {
+  if (H <= 0 || W <= 0 || stride <= 0 || (int64_t)H * W >= (1ll << 31)) return 0;
+  const int64_t nchunks = gs_ceil_div(picp_slots(H, W, stride), GS_PI_CHUNK);
+  return (int64_t)(picp_partials_bytes(nchunks) + 2 * picp_counts_bytes(nchunks));
+}
+
+#define PIC_CHECK_SEQ(who, u)                                                                                  \
+  do {                                                                                                         \
+    PICP_CHECK_SEQ(who, (u).base);                                                                             \
+    PICP_REQUIRE(who, (u).color && (u).model_intensity, "NULL pointer (color / model_intensity)");             \
+    PICP_REQUIRE(who, ((uintptr_t)(u).model_intensity & 15) == 0, "model_intensity must be 16-byte aligned");  \
+  } while (0)
+#define PIC_CHECK_WEIGHT(who, w) \
+  PICP_REQUIRE(who, (w) >= 0.0f && (w) < __builtin_inff(), "color_weight must be finite and not negative")
+
+static void pic_fill_seq(PicSeq& s, const gs_picp_color_seq& u, int nchunks) {
+  picp_fill_seq(s.g, u.base, nchunks);
+  s.color = u.color;
+  s.model = reinterpret_cast<const float4*>(u.model_intensity);
+  s.ccounts = reinterpret_cast<int32_t*>(static_cast<char*>(u.base.scratch) + picp_partials_bytes(nchunks) +
+                                         picp_counts_bytes(nchunks));
+  s.cflag_out = nullptr; s.ac_out = nullptr; s.bc_out = nullptr; s.ccount_out = nullptr;
+}
+
+extern "C" int gs_projective_icp_color_batch_f32(const gs_picp_color_seq* seqs_host, int B, int H, int W,
+                                                 const gs_picp_params* params_host, float color_weight, void* stream) {
+  const char* who = __func__;
+  PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
+  PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
+  const gs_picp_params& prm = *params_host;
+  PICP_CHECK_PARAMS(who, prm);
+  PIC_CHECK_WEIGHT(who, color_weight);
+  for (int b = 0; b < B; ++b) {
+    PIC_CHECK_SEQ(who, seqs_host[b]);
+    PICP_REQUIRE(who, seqs_host[b].base.out_pose16, "NULL pointer (out_pose16)");
+  }
+  hipStream_t st = gs_stream(stream);
+  for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
+    const int nb = B - c0 < GS_MAX_BATCH ? B - c0 : GS_MAX_BATCH;
+    PicBatch pb;
+    pb.g.B = nb;
+    pb.weight = color_weight;
+    picp_fill(pb.g, H, W, prm.stride, prm.dist_th, prm.dot_th, prm.damp);
+    for (int b = 0; b < nb; ++b) {
+      pic_fill_seq(pb.s[b], seqs_host[c0 + b], pb.g.nchunks);
+      pb.s[b].g.T_out = seqs_host[c0 + b].base.out_pose16;
+    }
+    const unsigned blocks = (unsigned)nb * (unsigned)pb.g.nchunks;   // < 8 * 2^23
+    for (int it = 0; it < prm.numiters; ++it) {
+      for (int b = 0; b < nb; ++b) {
+        const gs_picp_seq& u = seqs_host[c0 + b].base;
+        pb.s[b].g.T_in = it == 0 ? u.init_pose16 : u.out_pose16;
+        pb.s[b].g.trace_row = u.trace ? u.trace + (int64_t)GS_PIC_TRACE * it : nullptr;
+      }
+      hipLaunchKernelGGL(gs_picp_color_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb);
+      hipLaunchKernelGGL(gs_picp_color_finish_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb);
+    }
+    GS_LAUNCH_CHECK();
+  }
+  return GS_OK;
+}
+
+extern "C" int gs_projective_icp_color_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
+                                                float dist_th, float dot_th, float color_weight, int32_t* code,
+                                                int64_t* row, float* a6, float* b, float* ac6, float* bc,
+                                                int32_t* colored, double* sums28, int64_t* count, int64_t* color_count,
+                                                void* stream) {
+  GS_REQUIRE(seq_host && H > 0 && W > 0, "bad arguments");
+  GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
+  GS_REQUIRE(stride >= 1, "stride must be at least 1");
+  GS_REQUIRE(!(dist_th != dist_th) && !(dot_th != dot_th), "a threshold is NaN");
+  PIC_CHECK_WEIGHT(__func__, color_weight);
+  PIC_CHECK_SEQ(__func__, *seq_host);
+  hipStream_t st = gs_stream(stream);
+  PicBatch pb;
+  pb.g.B = 1;
+  pb.weight = color_weight;
+  picp_fill(pb.g, H, W, stride, dist_th, dot_th, 1.0f);
+  pic_fill_seq(pb.s[0], *seq_host, pb.g.nchunks);
+  PicSeq& s = pb.s[0];
+  s.g.code_out = code; s.g.row_out = row; s.g.a_out = a6; s.g.b_out = b;
+  s.ac_out = ac6; s.bc_out = bc; s.cflag_out = colored;
+  s.g.sums_out = sums28; s.g.count_out = count; s.ccount_out = color_count;
+  hipLaunchKernelGGL(gs_picp_color_linearize_kernel, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb);
+  if (sums28 || count || color_count)
+    hipLaunchKernelGGL(gs_picp_color_finish_kernel, dim3(1), dim3(GS_PI_FIN), 0, st, pb);
+  GS_LAUNCH_CHECK();
+  return GS_OK;
+}

@@ -3,7 +3,9 @@ the reference has no counterpart).  The map is rendered at the previous pose (gs
 of the live frame is paired with the surfel that won the pixel it projects to under the current estimate, and
 point-to-plane Gauss-Newton steps with constant damping follow (gs_projective_icp_batch_f32) -- no nearest-neighbour
 search.  The result is detached unless `differentiable` is set: the poses are then on the autograd tape
-(ops.ProjectiveICPFunction, a HIP backward through the Gauss-Newton iterations)."""
+(ops.ProjectiveICPFunction, a HIP backward through the Gauss-Newton iterations).  With `color_weight` > 0 the solve
+is the joint geometric + photometric one (gs_projective_icp_color_batch_f32): the view's colour image is rendered too and
+the live frame's colour is compared with it."""
 from typing import Optional, Union
 
 import torch
@@ -33,17 +35,27 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             non-differentiable in-place `step`, `prune_`); a backward after such a change raises instead of returning
             gradients of the wrong rows.  A map update that itself ran on the tape hands the map new tensors and
             leaves the saved ones intact: the backward of a loss over several such frames works.
+        color_weight: weight of the photometric term in metres per intensity unit (0, the default: the geometric solve,
+            bit for bit).  With a weight the map must have colours, and the live frame's `rgb_image` is read in the units
+            the map's colours are stored in: for colours in 0 ... 255 start from the weight that suits [0, 1] divided by
+            255.  It has no backward pass yet: a weight together with `differentiable=True` raises.
 
     Unlike the point-cloud-pair providers it needs the map and the live frame themselves: call
     `localize(pointclouds, live_frame, prev_poses)`."""
 
     def __init__(self, numiters: int = 10, damp: float = 1e-8, dist_thresh: Union[float, int] = 0.1,
                  angle_thresh: Union[float, int] = 30, stride: Optional[int] = None,
-                 min_confidence: Union[float, int] = 0.0, radius: int = 0, differentiable: bool = False):
+                 min_confidence: Union[float, int] = 0.0, radius: int = 0, differentiable: bool = False,
+                 color_weight: Union[float, int] = 0.0):
         from .. import ops
         if not isinstance(differentiable, bool):
             raise TypeError("differentiable must be of type bool; but was of type {}.".format(type(differentiable)))
         ops._picp_args(1 if stride is None else stride, numiters, damp, dist_thresh, angle_thresh)
+        ops._picp_color_weight(color_weight)
+        if color_weight > 0 and differentiable:
+            raise ValueError("color_weight > 0 cannot be combined with differentiable=True: the colour term has no "
+                             "backward pass yet")
+        self.color_weight = color_weight   # (carried next to _kwargs(): the plain solve does not take it)
         self.numiters = numiters
         self.damp = damp
         self.dist_thresh = dist_thresh
@@ -107,9 +119,22 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                          view.index[:, 0], poses.detach(), maps, poses, differentiable=True, guard=guard,
                                          **self._kwargs())
             return T.unsqueeze(1)
+        out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=poses.device)
+        if self.color_weight > 0:
+            # the joint solve: the view's colour image next to the index image, their intensity image, the live colour
+            colors = pointclouds._buf["colors"]
+            if colors is None or any(c is None for c in colors):
+                raise ValueError("color_weight > 0 needs a map with colours")
+            view = ops.render_map_batch([(m[0], None, colors[b]) + m[3:] for b, m in enumerate(maps)],
+                                        poses.view(B, 1, 4, 4), K, H, W, radius=self.radius,
+                                        min_confidence=self.min_confidence)
+            model = ops.model_intensity(view.color[:, 0], view.index[:, 0])
+            ops.projective_icp_color_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
+                                           view.index[:, 0], poses, maps, poses, fr.rgb_image[:, 0], model,
+                                           color_weight=self.color_weight, out=out.view(B, 4, 4), **self._kwargs())
+            return out
         view = ops.render_map_batch([(m[0], None) + m[2:] for m in maps], poses.view(B, 1, 4, 4), K, H, W,
                                     radius=self.radius, min_confidence=self.min_confidence)
-        out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=poses.device)
         ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
                                  view.index[:, 0], poses, maps, poses, out=out.view(B, 4, 4), **self._kwargs())
         return out

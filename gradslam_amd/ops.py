@@ -956,9 +956,10 @@ def _picp_args(stride, numiters, damp, dist_thresh, angle_thresh):
     return float(dist_thresh), math.cos((angle_thresh * math.pi) / 180)
 
 
-def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride):
+def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, color=False):
     """Shape / dtype / device checks shared by the batched solve and the table-level call; fills the descriptors.
-    Returns (seqs, tensors kept alive, device, B, H, W)."""
+    Returns (seqs, tensors kept alive, device, B, H, W).  color: the scratch is sized for the colour solve (the plain
+    layout plus the colour-row counts)."""
     tensors = (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                ("model_pose", model_poses), ("init_pose", init_poses))
     for name, t in tensors:
@@ -995,7 +996,7 @@ def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_pos
     held = [vertex, normal, depth, K, index, model_poses, init_poses]
     ws = Workspace.get(dev)
     L = lib()
-    nbytes = L.gs_projective_icp_scratch_bytes(H, W, int(stride))
+    nbytes = (L.gs_projective_icp_color_scratch_bytes if color else L.gs_projective_icp_scratch_bytes)(H, W, int(stride))
     seqs = (_C.PicpSeq * Bn)()
     P3, P1 = H * W * 12, H * W * 4
     for b in range(Bn):
@@ -1223,6 +1224,159 @@ def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points,
                          torch.empty(28, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.int64, device=dev))
     check(lib().gs_projective_icp_rows_f32(seqs, H, W, int(stride), dist_th, dot_th, *[ptr(t) for t in res], stream(dev)),
           "gs_projective_icp_rows_f32")
+    return res
+
+
+# ----------------------------------------------------------------------------------- projective ICP with a colour term
+ProjectiveColorRows = collections.namedtuple("ProjectiveColorRows", ["code", "row", "a", "b", "ac", "bc", "colored",
+                                                                     "sums", "count", "color_count"])
+PICP_COLOR_TRACE = 9
+
+
+def _picp_color_weight(color_weight):
+    """the value check of the colour weight (metres per intensity unit): a finite number >= 0"""
+    import math
+    if isinstance(color_weight, bool) or not isinstance(color_weight, (float, int)):
+        raise TypeError("projective_icp_color: color_weight must be of type float or int; but was of type {}.".format(
+            type(color_weight)))
+    if not (math.isfinite(color_weight) and color_weight >= 0):
+        raise ValueError("projective_icp_color: color_weight ({}) must be finite and not negative.".format(color_weight))
+    return float(color_weight)
+
+
+def _picp_refuse_differentiable(differentiable):
+    if not isinstance(differentiable, bool):
+        raise TypeError("projective_icp_color: differentiable must be of type bool; but was of type {}.".format(
+            type(differentiable)))
+    if differentiable:
+        raise ValueError("projective_icp_color: the colour term has no backward pass yet (differentiable=True is not "
+                         "supported; use projective_icp_batch for a pose on the autograd tape)")
+
+
+def model_intensity(color, index):
+    """The intensity image of a model view for the colour term (gs_model_intensity_f32): color (..., H, W, 3) float32 and
+    index (..., H, W) int64 as render_map / render_map_batch return them -> (..., H, W, 4) float32 = (I, gx, gy, ok):
+    I = 0.299 R + 0.587 G + 0.114 B, central differences gx, gy, ok = 1 where the pixel and its four neighbours are
+    inside the image and hold a surfel (index >= 0), else ok = gx = gy = 0.  Built once per localisation."""
+    for name, t in (("color", color), ("index", index)):
+        if not torch.is_tensor(t):
+            raise TypeError("model_intensity: expected {} to be of type tensor; got {}".format(name, type(t)))
+    if color.ndim < 3 or color.shape[-1] != 3 or tuple(index.shape) != tuple(color.shape[:-1]) or color.numel() == 0:
+        raise ValueError("model_intensity: expected color (..., H, W, 3) and index (..., H, W); got {} and {}".format(
+            tuple(color.shape), tuple(index.shape)))
+    if color.dtype != f32 or index.dtype != torch.int64:
+        raise ValueError("model_intensity: color must be float32 and index int64; got {} and {}".format(
+            color.dtype, index.dtype))
+    _warn_detached("model_intensity", color)
+    color, index = _c(color.detach()), index.contiguous()
+    dev = require_device(color, index)
+    H, W = int(color.shape[-3]), int(color.shape[-2])
+    out = torch.empty(tuple(color.shape[:-1]) + (4,), dtype=f32, device=dev)
+    check(lib().gs_model_intensity_f32(ptr(color), ptr(index), color.numel() // (3 * H * W), H, W, ptr(out), stream(dev)),
+          "gs_model_intensity_f32")
+    return out
+
+
+def _picp_color_seqs(who, seqs, held, Bn, H, W, color, model):
+    """the colour descriptors on top of the plain ones (_picp_seqs(..., color=True)): shape / dtype / device checks of the
+    live colour and the model intensity"""
+    for name, t, shape in (("color", color, (Bn, H, W, 3)), ("model_intensity", model, (Bn, H, W, 4))):
+        if not torch.is_tensor(t):
+            raise TypeError("{}: expected {} to be of type tensor; got {}".format(who, name, type(t)))
+        if tuple(t.shape) != shape or t.dtype != f32:
+            raise ValueError("{}: expected {} to be float32 of shape {}; got {} {}".format(who, name, shape, t.dtype,
+                                                                                           tuple(t.shape)))
+    _warn_detached(who, color, model)
+    color, model = _c(color.detach()), _c(model.detach())
+    require_device(color, model, held[0])
+    held += [color, model]
+    cseqs = (_C.PicpColorSeq * Bn)()
+    for b in range(Bn):
+        cseqs[b].base = seqs[b]
+        cseqs[b].color = color.data_ptr() + b * H * W * 12
+        cseqs[b].model_intensity = model.data_ptr() + b * H * W * 16
+    return cseqs
+
+
+def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, maps, init_poses, color, model, *,
+                               color_weight, stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0,
+                               return_trace=False, out=None, differentiable=False):
+    """projective_icp_batch with a photometric term (gs_projective_icp_color_batch_f32: the same two launches per
+    iteration for 8 sequences, nothing read back).  The arguments of projective_icp_batch, then color (B, H, W, 3): the
+    live frames' colour, and model (B, H, W, 4): model_intensity of the views' rendered colour and index images.  A slot
+    that passes the geometric gates and lands on a pixel with an intensity gradient (ok = 1) adds the row
+    color_weight * (luma(color) - first-order model intensity at its projection) to the normal equations, next to its
+    point-to-plane row.  color_weight: metres per intensity unit, finite and >= 0 (0 leaves the geometric solve).  Returns
+    the poses (B, 4, 4), detached; with return_trace also (B, numiters, 9) rows [inliers, joint sum of squared residuals,
+    xi(6), colour rows].  An iteration without geometric inliers leaves the pose as it is.  differentiable=True is
+    refused: the colour term has no backward pass."""
+    _picp_refuse_differentiable(differentiable)
+    weight = _picp_color_weight(color_weight)
+    dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
+    who = "projective_icp_color"
+    seqs, held, dev, Bn, H, W = _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride,
+                                           color=True)
+    cseqs = _picp_color_seqs(who, seqs, held, Bn, H, W, color, model)
+    T = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if out is None else out
+    if tuple(T.shape) != (Bn, 4, 4) or T.dtype != f32 or not T.is_contiguous() or T.device != dev:
+        raise ValueError("projective_icp_color: out must be a contiguous float32 tensor of shape %s on %s"
+                         % ((Bn, 4, 4), dev))
+    trace = torch.empty((Bn, int(numiters), PICP_COLOR_TRACE), dtype=f32, device=dev) if return_trace else None
+    for b in range(Bn):
+        cseqs[b].base.out_pose16 = T.data_ptr() + b * 64
+        cseqs[b].base.trace = 0 if trace is None else trace.data_ptr() + b * int(numiters) * PICP_COLOR_TRACE * 4
+    prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
+    check(lib().gs_projective_icp_color_batch_f32(cseqs, Bn, H, W, prm, weight, stream(dev)),
+          "gs_projective_icp_color_batch_f32")
+    return (T, trace) if return_trace else T
+
+
+def _picp_color_single(who, named):
+    for name, t in named:
+        if not torch.is_tensor(t):
+            raise TypeError("{}: expected {} to be of type tensor; got {}".format(who, name, type(t)))
+
+
+def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, color, model,
+                         *, color_weight, n_dev=None, stride=1, numiters=10, damp=1e-8, dist_thresh=0.1,
+                         angle_thresh=30.0, return_trace=False, differentiable=False):
+    """projective_icp_color_batch for one sequence without the batch dimension (arguments as projective_icp, then color
+    (H, W, 3) and model (H, W, 4)).  Returns the pose (4, 4) (and the trace (numiters, 9))."""
+    _picp_color_single("projective_icp_color", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K),
+                                                ("index", index), ("model_pose", model_pose), ("init_pose", init_pose),
+                                                ("color", color), ("model_intensity", model)))
+    r = projective_icp_color_batch(vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0), K.reshape(1, 4, 4),
+                                   index.unsqueeze(0), model_pose.reshape(1, 4, 4),
+                                   [(map_points, map_normals, None, n_dev)], init_pose.reshape(1, 4, 4),
+                                   color.unsqueeze(0), model.unsqueeze(0), color_weight=color_weight, stride=stride,
+                                   numiters=numiters, damp=damp, dist_thresh=dist_thresh, angle_thresh=angle_thresh,
+                                   return_trace=return_trace, differentiable=differentiable)
+    return (r[0][0], r[1][0]) if return_trace else r[0]
+
+
+def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_points, map_normals, pose, color, model,
+                              *, color_weight, n_dev=None, stride=1, dist_thresh=0.1, angle_thresh=30.0):
+    """ONE joint linearisation at `pose` (gs_projective_icp_color_rows_f32), arguments as projective_icp_color.
+    ProjectiveColorRows: code, row, a, b as projective_icp_rows; ac (nslots, 6), bc (nslots,): the colour row, zeros
+    unless colored; colored int32 (nslots,): 1 where the slot is used and its model pixel has ok = 1; sums float64 (28,):
+    the joint sums; count, color_count int64 (1,)."""
+    weight = _picp_color_weight(color_weight)
+    dist_th, dot_th = _picp_args(stride, 1, 1.0, dist_thresh, angle_thresh)
+    who = "projective_icp_color_rows"
+    _picp_color_single(who, (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
+                             ("model_pose", model_pose), ("pose", pose), ("color", color), ("model_intensity", model)))
+    seqs, held, dev, _, H, W = _picp_seqs(who, vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0),
+                                          K.reshape(1, 4, 4), index.unsqueeze(0), model_pose.reshape(1, 4, 4),
+                                          [(map_points, map_normals, None, n_dev)], pose.reshape(1, 4, 4), stride,
+                                          color=True)
+    cseqs = _picp_color_seqs(who, seqs, held, 1, H, W, color.unsqueeze(0), model.unsqueeze(0))
+    ns = ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
+    e = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)   # noqa: E731
+    res = ProjectiveColorRows(e(ns, torch.int32), e(ns, torch.int64), e((ns, 6), f32), e(ns, f32), e((ns, 6), f32),
+                              e(ns, f32), e(ns, torch.int32), e(28, torch.float64), e(1, torch.int64), e(1, torch.int64))
+    check(lib().gs_projective_icp_color_rows_f32(cseqs, H, W, int(stride), dist_th, dot_th, weight,
+                                                 *[ptr(t) for t in res], stream(dev)),
+          "gs_projective_icp_color_rows_f32")
     return res
 
 

@@ -32,14 +32,22 @@ class ICPSLAM(nn.Module):
     `odom_differentiable` (off by default, `odom="projicp"` only): the projective ICP runs on the autograd tape
     (`ProjectiveICPOdometryProvider(differentiable=True)`): the poses of `forward` and of `step` carry a `grad_fn`, and a
     loss on them reaches the depth of the frames, the initial pose and a map that requires grad.  With it off the poses
-    are detached, bit for bit what they are with it on."""
+    are detached, bit for bit what they are with it on.
+
+    `color_weight` (0 by default, `odom="projicp"` only): weight of the photometric term of the projective ICP in metres
+    per intensity unit (`ProjectiveICPOdometryProvider(color_weight=...)`); the map must then carry colours."""
 
     def __init__(self, *, odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0,
                  B: Union[float, int] = 1.0, B2: Union[float, int] = 1.0, nu: Union[float, int] = 200.0,
                  device: Union[torch.device, str, None] = None, depth_filter: Optional[dict] = None,
-                 odom_differentiable: bool = False):
+                 odom_differentiable: bool = False, color_weight: Union[float, int] = 0.0):
         super().__init__()
+        from .. import ops
+        ops._picp_color_weight(color_weight)
+        if color_weight > 0 and odom != "projicp":
+            raise ValueError("color_weight is the photometric term of odom='projicp' (got odom={!r})".format(odom))
+        self.color_weight = color_weight
         if not isinstance(odom_differentiable, bool):
             raise TypeError("odom_differentiable must be of type bool; but was of type {}.".format(
                 type(odom_differentiable)))
@@ -61,7 +69,8 @@ class ICPSLAM(nn.Module):
             # frame-to-model tracking against the rendered map: dsratio is the lattice stride, dist_thresh=None the
             # provider's 0.1 m (the gate is part of the association, it cannot be switched off)
             odomprov = ProjectiveICPOdometryProvider(numiters, damp, 0.1 if dist_thresh is None else dist_thresh,
-                                                     stride=dsratio, differentiable=odom_differentiable)
+                                                     stride=dsratio, differentiable=odom_differentiable,
+                                                     color_weight=color_weight)
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio

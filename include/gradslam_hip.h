@@ -793,6 +793,46 @@ GS_API int64_t gs_projective_icp_backward_scratch_bytes(int H, int W, int stride
 GS_API int gs_projective_icp_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
                                                 const gs_picp_params* params_host, void* stream);
 
+/* ------------------------------------------------------------------ projective ICP with a colour term ------
+ * The projective ICP above plus a photometric row per slot (Steinbruecker / Kerl; Kintinuous, ElasticFusion, Open3D's
+ * hybrid odometry): geometry alone does not constrain a pose on a wall or a floor, the texture does.  In float32, one
+ * rounding per operation, no FMA in what is added here (gs_picp_color.hip spells out every operation):
+ *
+ * gs_model_intensity_f32: color (B, H, W, 3) and index (B, H, W) of gs_render_map_dc_f32 -> out (B, H, W, 4) =
+ * (I, gx, gy, ok) per pixel, 16-byte aligned: I = (0.299 R + 0.587 G) + 0.114 B, gx = 0.5 (I[h, w+1] - I[h, w-1]),
+ * gy = 0.5 (I[h+1, w] - I[h-1, w]); ok = 1 iff the pixel and its four neighbours are inside the image and have index >= 0,
+ * else ok = 0 and gx = gy = 0 (a hole of the view never leaks a gradient).  Built once per localisation.
+ *
+ * A slot gets a colour row iff its code is 0 and ok = 1 at the pixel (h', w') the association read.  With q = R_m^T (s -
+ * t_m) the camera-frame point and (u, v) the continuous pixel of the projector, Il the luma of color at the slot's pixel:
+ *   r   = Il - ((I + gx (u - w')) + gy (v - h'))                     first-order model intensity at (u, v)
+ *   Jq  = (gx fx / q2, gy fy / q2, -(gx fx q0 + gy fy q1) / q2^2),   Js = R_m Jq
+ *   a_c = color_weight [Js, s x Js],  b_c = color_weight r           (the layout and signs of the geometric row)
+ * color_weight is in metres per intensity unit, finite and >= 0.  The 28 terms of a slot are the exact float64 product of
+ * the geometric factors plus that of the colour factors, the sum rounded once; then the fixed reduction order, the solve
+ * and the update of the plain call: no float atomics, bitwise reproducible.  `count` stays the number of geometric
+ * inliers (an iteration without one keeps the pose bits); the colour rows are counted alongside.
+ * gs_projective_icp_color_batch_f32: as gs_projective_icp_batch_f32; base.trace rows are 9 floats: [inliers, (float) joint
+ * sum of squares, xi(6), colour rows]; base.scratch: gs_projective_icp_color_scratch_bytes(H, W, stride) bytes.  Two
+ * launches per iteration for 8 sequences, nothing read back.  Every argument is checked before the first HIP call. */
+typedef struct gs_picp_color_seq {
+  gs_picp_seq base;              /* as in the plain call (trace: (numiters, 9)) */
+  const float* color;            /* live frame colour (H, W, 3) */
+  const float* model_intensity;  /* (H, W, 4) of gs_model_intensity_f32 for the model view */
+} gs_picp_color_seq;
+GS_API int gs_model_intensity_f32(const float* color, const int64_t* index, int B, int H, int W, float* out,
+                                  void* stream);
+GS_API int64_t gs_projective_icp_color_scratch_bytes(int H, int W, int stride);
+GS_API int gs_projective_icp_color_batch_f32(const gs_picp_color_seq* seqs_host, int B, int H, int W,
+                                             const gs_picp_params* params_host, float color_weight, void* stream);
+/* ONE joint linearisation at T = base.init_pose16: the outputs of gs_projective_icp_rows_f32 (sums28 now the joint sums),
+ * plus per slot ac6 (nslots, 6), bc and colored (int32: 1 where the slot has a colour row; ac6 / bc are zero elsewhere),
+ * and the number of colour rows.  Any output may be NULL. */
+GS_API int gs_projective_icp_color_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride, float dist_th,
+                                            float dot_th, float color_weight, int32_t* code, int64_t* row, float* a6,
+                                            float* b, float* ac6, float* bc, int32_t* colored, double* sums28,
+                                            int64_t* count, int64_t* color_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

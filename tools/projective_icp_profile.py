@@ -1,7 +1,7 @@
 """Projective-association ICP against the model view: what one localisation costs next to the grid-search ICP, what the
 frame loop gains or loses with it, and what a launch of it costs (needs the MI355X; fails without one).
 
-    python tools/projective_icp_profile.py [--out FILE] [--only localize|slam|launches] [--steps K]
+    python tools/projective_icp_profile.py [--out FILE] [--only localize|slam|launches] [--steps K] [--color-weight W]
 
 1. One localisation.  640x480 frames of the benchmark's synthetic sequences, the map fused from the first 10 frames under
    the ground-truth poses, frame 10 localised from the pose of frame 9; B = 1 and B = 8.
@@ -22,7 +22,12 @@ frame loop gains or loses with it, and what a launch of it costs (needs the MI35
 3. Launches.  The solve alone (no render) at 10 and at 40 iterations: the slope is the time of one iteration = one
    linearise launch + one finish launch; and the render alone.  For the split between the two kernels run
        rocprofv3 --kernel-trace --stats -d DIR -- python tools/projective_icp_profile.py --only launches
-   in a run of its own (tracing slows the host: no end-to-end number comes from that run)."""
+   in a run of its own (tracing slows the host: no end-to-end number comes from that run).
+
+--color-weight W (W > 0) adds the joint geometric + photometric solve to parts 1 and 3, alternating with the plain one in
+the same process: the provider with color_weight=W (render with the colour image + ops.model_intensity +
+ops.projective_icp_color_batch), and in part 3 the intensity pre-pass and the colour solve alone.  The benchmark's frame
+colours are per-frame noise: the times hold, the poses of these variants say nothing."""
 import argparse
 import json
 import os
@@ -75,7 +80,7 @@ def translation_error(T, gt):
     return [float(x) for x in (T.reshape(-1, 4, 4)[:, :3, 3].double() - gt[:3, 3].double()).norm(dim=1).cpu()]
 
 
-def localize_times(torch, gs, ops, reps=5, rounds=7):
+def localize_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0):
     from gradslam_amd.odometry import ProjectiveICPOdometryProvider
     out = []
     for B in (1, 8):
@@ -93,11 +98,15 @@ def localize_times(torch, gs, ops, reps=5, rounds=7):
             "gradicp_ds4_20it": lambda: ops.localize_batch(vertex, depth, K, prev[:, 0], maps4, 4, mode=1, numiters=20),
             "gradicp_ds4_10it": lambda: ops.localize_batch(vertex, depth, K, prev[:, 0], maps4, 4, mode=1, numiters=10),
         }
+        if color_weight > 0:
+            cprov = {s: ProjectiveICPOdometryProvider(numiters=10, stride=s, color_weight=color_weight) for s in (4, 1)}
+            fns["projicp_color_stride4_10it"] = lambda: cprov[4].localize(pc, live, prev)
+            fns["projicp_color_stride1_10it"] = lambda: cprov[1].localize(pc, live, prev)
         err = {k: translation_error(fn(), gt) for k, fn in fns.items()}
         for fn in fns.values():
             fn(), fn()
         t = time_round_robin(torch, fns, reps, rounds)
-        rec = {"B": B, "H": H, "W": W, "map_rows": rows, "initial_translation_error_m": translation_error(prev, gt)[0],
+        rec = {"B": B, "color_weight": color_weight, "H": H, "W": W, "map_rows": rows, "initial_translation_error_m": translation_error(prev, gt)[0],
                "variants": {k: dict(t[k], translation_error_m=err[k]) for k in fns}}
         for s in (4, 1):
             rec["speedup_stride%d_vs_gradicp_20it" % s] = \
@@ -107,7 +116,7 @@ def localize_times(torch, gs, ops, reps=5, rounds=7):
     return out
 
 
-def launch_times(torch, gs, ops, reps=5, rounds=7):
+def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0):
     out = []
     for B in (1, 8):
         pc, live, prev, _ = scene(torch, gs, B)
@@ -118,10 +127,21 @@ def launch_times(torch, gs, ops, reps=5, rounds=7):
         index = ops.render_map_batch(maps, prev, K, H, W).index[:, 0]
         args = (fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K, index, prev[:, 0], maps_n,
                 prev[:, 0])
+        if color_weight > 0:
+            maps_c = [(pc._buf["points"][b], None, pc._buf["colors"][b], None) + tuple(pc._count_of(b)) for b in range(B)]
+            view = ops.render_map_batch(maps_c, prev, K, H, W)
+            model = ops.model_intensity(view.color[:, 0], view.index[:, 0])
+            cargs = args + (fr.rgb_image[:, 0].contiguous(), model)
         for stride in (4, 1):
             fns = {"render": lambda: ops.render_map_batch(maps, prev, K, H, W),
                    "solve_10it": lambda: ops.projective_icp_batch(*args, stride=stride, numiters=10),
                    "solve_40it": lambda: ops.projective_icp_batch(*args, stride=stride, numiters=40)}
+            if color_weight > 0:
+                kw = dict(color_weight=color_weight, stride=stride)
+                fns.update({"render_with_color": lambda: ops.render_map_batch(maps_c, prev, K, H, W),
+                            "model_intensity": lambda: ops.model_intensity(view.color[:, 0], view.index[:, 0]),
+                            "solve_color_10it": lambda: ops.projective_icp_color_batch(*cargs, numiters=10, **kw),
+                            "solve_color_40it": lambda: ops.projective_icp_color_batch(*cargs, numiters=40, **kw)})
             for fn in fns.values():
                 fn(), fn()
             t = time_round_robin(torch, fns, reps, rounds)
@@ -130,6 +150,10 @@ def launch_times(torch, gs, ops, reps=5, rounds=7):
             rec = {"B": B, "stride": stride, "slots": nslots, "chunks": -(-nslots // 256), "times": t,
                    "us_per_iteration": per_it * 1e3, "us_per_launch_mean": per_it * 1e3 / 2,
                    "us_outside_the_iterations": (t["solve_10it"]["median_ms"] - 10 * per_it) * 1e3}
+            if color_weight > 0:
+                rec["color_weight"] = color_weight
+                rec["us_per_iteration_color"] = \
+                    (t["solve_color_40it"]["median_ms"] - t["solve_color_10it"]["median_ms"]) / 30 * 1e3
             print(json.dumps(rec), flush=True)
             out.append(rec)
     return out
@@ -166,7 +190,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", choices=("localize", "slam", "launches"), default=None)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--color-weight", type=float, default=0.0,
+                    help="> 0: also time the joint geometric + photometric solve (parts 1 and 3)")
     args = ap.parse_args()
+    if not (args.color_weight >= 0 and args.color_weight < float("inf")):
+        ap.error("--color-weight must be finite and not negative")
     import torch
     if not torch.cuda.is_available():
         sys.exit("tools/projective_icp_profile.py measures on the GPU: no HIP device found (nothing is measured on the CPU)")
@@ -174,11 +202,11 @@ def main():
     from gradslam_amd import ops
     out = {"device": torch.cuda.get_device_name(0)}
     if args.only in (None, "localize"):
-        out["one_localisation"] = localize_times(torch, gs, ops)
+        out["one_localisation"] = localize_times(torch, gs, ops, color_weight=args.color_weight)
     if args.only in (None, "slam"):
         out["slam_window"] = slam_runs(torch, gs, args.steps)
     if args.only in (None, "launches"):
-        out["launches"] = launch_times(torch, gs, ops)
+        out["launches"] = launch_times(torch, gs, ops, color_weight=args.color_weight)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
