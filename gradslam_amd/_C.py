@@ -208,6 +208,16 @@ _PROTOS = {
     "gs_projective_icp_color_batch_f32": [C.POINTER(PicpColorSeq), _i32, _i32, _i32, C.POINTER(PicpParams), _f, _vp],
     "gs_projective_icp_color_rows_f32": [C.POINTER(PicpColorSeq), _i32, _i32, _i32, _f, _f, _f, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp],
+    "gs_projective_icp_robust_batch_f32": [C.POINTER(PicpSeq), C.POINTER(C.c_void_p), _i32, _i32, _i32,
+                                           C.POINTER(PicpParams), _f, _vp],
+    "gs_projective_icp_robust_rows_f32": [C.POINTER(PicpSeq), _i32, _i32, _i32, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp],
+    "gs_projective_icp_robust_backward_batch_f32": [C.POINTER(PicpBackwardSeq), _i32, _i32, _i32, C.POINTER(PicpParams),
+                                                    _f, _vp],
+    "gs_projective_icp_color_robust_batch_f32": [C.POINTER(PicpColorSeq), _i32, _i32, _i32, C.POINTER(PicpParams), _f, _f,
+                                                 _f, _vp],
+    "gs_projective_icp_color_robust_rows_f32": [C.POINTER(PicpColorSeq), _i32, _i32, _i32, _f, _f, _f, _f, _f, _vp, _vp,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,
             "gs_knn1_grid_scratch_bytes": _i64, "gs_update_map_scratch_bytes": _i64, "gs_global_maps_pose_backward_scratch_bytes": _i64, "gs_icp_tape_bytes": _i64, "gs_icp_backward_scratch_bytes": _i64,

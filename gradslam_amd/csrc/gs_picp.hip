@@ -27,9 +27,17 @@
 // The taped entry (gs_projective_icp_tape_batch_f32) is the same two kernels: the finish kernel also writes the pose it
 // read, the 28 sums, the step and the inlier count of every iteration to the caller's tape (PiTapeRow), which is all the
 // backward pass (gs_picp_bwd.hip) needs besides the inputs.  The pose bits are those of the untaped call.
+// The robust entries (gs_projective_icp_robust_batch_f32 / _rows_f32, huber_delta > 0) launch the ROBUST instance of the
+// linearise body: w = |b| > delta ? delta / |b| : 1 in float32 (pi_huber_weight), every term (double)w * ((double)x *
+// (double)y); the finish kernel, the reduction and the counts are the plain ones, S[27] is the weighted sum of squares.
+// With delta = 0 they launch the plain kernel.
 #include "gs_picp_dev.h"
 
-__global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_linearize_kernel(const PiBatch pb) {
+// The linearise kernel's body.  ROBUST: every term of a used slot carries the Huber weight of its residual b
+// (pi_huber_weight, gs_picp_dev.h), which also goes to weight_out (nslots, 0 for a slot that is not used) when asked for;
+// the plain instance is the kernel as it was.
+template <bool ROBUST>
+GS_DEV void pi_linearize(const PiBatch& pb, const float delta, float* __restrict__ weight_out) {
   __shared__ GsCamera cam;
   __shared__ float Ts[12];
   __shared__ double red[GS_PI_CHUNK / GS_WAVE][LIN_NV];
@@ -45,7 +53,7 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_linearize_kernel(const Pi
   const int64_t n_map = gs_count(q.n);
   int code = 1;
   int64_t row = -1;
-  float a[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, b = 0.0f;
+  float a[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, b = 0.0f, w = 1.0f;
   if (in_lattice) {
     const int i = k / pb.g.Wl, j = k - i * pb.g.Wl;
     const int64_t p = (int64_t)(i * pb.g.stride) * pb.g.W + j * pb.g.stride;
@@ -61,6 +69,10 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_linearize_kernel(const Pi
       for (int c = 0; c < 6; ++c) q.a_out[6 * (int64_t)k + c] = a[c];
     }
     if (q.b_out) q.b_out[k] = b;
+    if (ROBUST) {
+      if (code == 0) w = pi_huber_weight(pi_huber_clipped(b, delta), b, delta);
+      if (weight_out) weight_out[k] = code == 0 ? w : 0.0f;
+    }
   }
   const bool used = code == 0;   // (a, b are zero otherwise: every term below is then +0.0)
   const unsigned long long mask = __ballot(used);
@@ -72,18 +84,18 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_linearize_kernel(const Pi
   for (int r = 0; r < 6; ++r) {
 #pragma unroll
     for (int c = r; c < 6; ++c) {
-      const double x = pi_wave_tree((double)a[r] * (double)a[c], any);
+      const double x = pi_wave_tree(ROBUST ? pi_term(w, a[r], a[c]) : (double)a[r] * (double)a[c], any);
       if (lane == 0) red[wave][t] = x;
       ++t;
     }
   }
 #pragma unroll
   for (int r = 0; r < 6; ++r) {
-    const double x = pi_wave_tree((double)a[r] * (double)b, any);
+    const double x = pi_wave_tree(ROBUST ? pi_term(w, a[r], b) : (double)a[r] * (double)b, any);
     if (lane == 0) red[wave][21 + r] = x;
   }
   {
-    const double x = pi_wave_tree((double)b * (double)b, any);
+    const double x = pi_wave_tree(ROBUST ? pi_term(w, b, b) : (double)b * (double)b, any);
     if (lane == 0) red[wave][27] = x;
   }
   __syncthreads();
@@ -91,6 +103,15 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_linearize_kernel(const Pi
     q.partials[(int64_t)chunk * LIN_NV + threadIdx.x] =
         (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
   if (threadIdx.x == GS_WAVE) q.counts[chunk] = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
+}
+
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_linearize_kernel(const PiBatch pb) {
+  pi_linearize<false>(pb, 0.0f, nullptr);
+}
+
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_linearize_kernel(const PiBatch pb, const float delta,
+                                                                               float* __restrict__ weight_out) {
+  pi_linearize<true>(pb, delta, weight_out);
 }
 
 __global__ void __launch_bounds__(GS_PI_FIN) gs_picp_finish_kernel(const PiBatch pb) {
@@ -107,13 +128,15 @@ extern "C" int64_t gs_projective_icp_tape_bytes(int numiters) {
   return numiters >= 1 ? (int64_t)numiters * (int64_t)sizeof(PiTapeRow) : 0;
 }
 
-// the solve behind both entries; tapes_host: per sequence the device buffer of numiters tape rows, or NULL (untaped)
+// the solve behind the batch entries; tapes_host: per sequence the device buffer of numiters tape rows, or NULL
+// (untaped); delta: the Huber threshold of the robust entry (0: the plain kernel)
 static int picp_solve(const char* who, const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H, int W,
-                      const gs_picp_params* params_host, void* stream) {
+                      const gs_picp_params* params_host, float delta, void* stream) {
   PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
   PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   const gs_picp_params& prm = *params_host;
   PICP_CHECK_PARAMS(who, prm);
+  PICP_CHECK_DELTA(who, delta, "huber_delta");
   for (int b = 0; b < B; ++b) {
     PICP_CHECK_SEQ(who, seqs_host[b]);
     PICP_REQUIRE(who, seqs_host[b].out_pose16, "NULL pointer (out_pose16)");
@@ -137,7 +160,11 @@ static int picp_solve(const char* who, const gs_picp_seq* seqs_host, void* const
         pb.s[b].trace_row = u.trace ? u.trace + (int64_t)GS_PI_TRACE * it : nullptr;
         pb.s[b].tape_row = tapes_host ? static_cast<PiTapeRow*>(tapes_host[c0 + b]) + it : nullptr;
       }
-      hipLaunchKernelGGL(gs_picp_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb);
+      if (delta > 0.0f)
+        hipLaunchKernelGGL(gs_robust_picp_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, delta,
+                           static_cast<float*>(nullptr));
+      else
+        hipLaunchKernelGGL(gs_picp_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb);
       hipLaunchKernelGGL(gs_picp_finish_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb);
     }
     GS_LAUNCH_CHECK();
@@ -147,23 +174,31 @@ static int picp_solve(const char* who, const gs_picp_seq* seqs_host, void* const
 
 extern "C" int gs_projective_icp_batch_f32(const gs_picp_seq* seqs_host, int B, int H, int W,
                                            const gs_picp_params* params_host, void* stream) {
-  return picp_solve(__func__, seqs_host, nullptr, B, H, W, params_host, stream);
+  return picp_solve(__func__, seqs_host, nullptr, B, H, W, params_host, 0.0f, stream);
 }
 
 extern "C" int gs_projective_icp_tape_batch_f32(const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H, int W,
                                                 const gs_picp_params* params_host, void* stream) {
   GS_REQUIRE(tapes_host, "NULL pointer (tapes)");
-  return picp_solve(__func__, seqs_host, tapes_host, B, H, W, params_host, stream);
+  return picp_solve(__func__, seqs_host, tapes_host, B, H, W, params_host, 0.0f, stream);
 }
 
-extern "C" int gs_projective_icp_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
-                                          float dot_th, int32_t* code, int64_t* row, float* a6, float* b,
-                                          double* sums28, int64_t* count, void* stream) {
-  GS_REQUIRE(seq_host && H > 0 && W > 0, "bad arguments");
-  GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
-  GS_REQUIRE(stride >= 1, "stride must be at least 1");
-  GS_REQUIRE(!(dist_th != dist_th) && !(dot_th != dot_th), "a threshold is NaN");
-  PICP_CHECK_SEQ(__func__, *seq_host);
+extern "C" int gs_projective_icp_robust_batch_f32(const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H,
+                                                  int W, const gs_picp_params* params_host, float huber_delta,
+                                                  void* stream) {
+  return picp_solve(__func__, seqs_host, tapes_host, B, H, W, params_host, huber_delta, stream);
+}
+
+// the linearisation behind both table-level entries; weight: the robust entry's output, or NULL
+static int picp_rows(const char* who, const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th, float dot_th,
+                     float delta, int32_t* code, int64_t* row, float* a6, float* b, float* weight, double* sums28,
+                     int64_t* count, void* stream) {
+  PICP_REQUIRE(who, seq_host && H > 0 && W > 0, "bad arguments");
+  PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
+  PICP_REQUIRE(who, stride >= 1, "stride must be at least 1");
+  PICP_REQUIRE(who, !(dist_th != dist_th) && !(dot_th != dot_th), "a threshold is NaN");
+  PICP_CHECK_DELTA(who, delta, "huber_delta");
+  PICP_CHECK_SEQ(who, *seq_host);
   hipStream_t st = gs_stream(stream);
   PiBatch pb;
   pb.g.B = 1;
@@ -171,8 +206,26 @@ extern "C" int gs_projective_icp_rows_f32(const gs_picp_seq* seq_host, int H, in
   picp_fill_seq(pb.s[0], *seq_host, pb.g.nchunks);
   pb.s[0].code_out = code; pb.s[0].row_out = row; pb.s[0].a_out = a6; pb.s[0].b_out = b;
   pb.s[0].sums_out = sums28; pb.s[0].count_out = count;
-  hipLaunchKernelGGL(gs_picp_linearize_kernel, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb);
+  if (delta > 0.0f || weight)   // (delta == 0 with a weight table: the robust kernel writes 1 for every used slot)
+    hipLaunchKernelGGL(gs_robust_picp_linearize_kernel, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb, delta,
+                       weight);
+  else
+    hipLaunchKernelGGL(gs_picp_linearize_kernel, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb);
   if (sums28 || count) hipLaunchKernelGGL(gs_picp_finish_kernel, dim3(1), dim3(GS_PI_FIN), 0, st, pb);
   GS_LAUNCH_CHECK();
   return GS_OK;
+}
+
+extern "C" int gs_projective_icp_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
+                                          float dot_th, int32_t* code, int64_t* row, float* a6, float* b,
+                                          double* sums28, int64_t* count, void* stream) {
+  return picp_rows(__func__, seq_host, H, W, stride, dist_th, dot_th, 0.0f, code, row, a6, b, nullptr, sums28, count,
+                   stream);
+}
+
+extern "C" int gs_projective_icp_robust_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
+                                                 float dot_th, float huber_delta, int32_t* code, int64_t* row, float* a6,
+                                                 float* b, float* weight, double* sums28, int64_t* count, void* stream) {
+  return picp_rows(__func__, seq_host, H, W, stride, dist_th, dot_th, huber_delta, code, row, a6, b, weight, sums28,
+                   count, stream);
 }

@@ -33,6 +33,8 @@
 // additions (GRADSLAM_HIP_DETERMINISTIC_BACKWARD does not apply here; a sorted scatter is not built).
 // Every output may be NULL: its work and its buffer are skipped; with both map outputs NULL nothing of map size is
 // touched.
+// gs_projective_icp_robust_backward_batch_f32 (a tape of the forward with Huber weights, the same huber_delta) launches
+// the ROBUST instance of the point stage (see pb_point); everything else, the scalar stage included, is shared.
 #include "gs_picp_dev.h"
 #include "gs_se3_f64.h"
 
@@ -179,8 +181,13 @@ __global__ void __launch_bounds__(PB_FIN) gs_picp_bwd_scalar_kernel(const PbBatc
 
 // Point stage of iteration `it`.  first: the first point stage of the call (vacc is written, not added to);
 // last: iteration 0 (vertex_bar is rounded and stored).
-__global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_bwd_point_kernel(const PbBatch pb, const int it, const int first,
-                                                                        const int last) {
+// ROBUST (the forward ran with Huber weights, delta > 0): the taped S is the weighted system, so the scalar stage is
+// unchanged; here the weight w(b) = delta / |b| of a clipped slot is differentiated, the clip flag is frozen like the
+// association and recomputed as the forward computed it (pi_huber_clipped on the float32 b of gn_row_pn at the taped
+// pose).  With w' = dw/db (-w / b clipped, 0 otherwise): ab = w ((b - c) u - e xi), and the residual's adjoint
+// bb = e (w + w' (b - c)) takes the place of e in sb, points_bar and normals_bar.
+template <bool ROBUST>
+GS_DEV void pb_point(const PbBatch& pb, const int it, const int first, const int last, const float delta) {
   __shared__ GsCamera cam;
   __shared__ float Ts[12];
   __shared__ double ux[12];   // u(6), xi(6)
@@ -237,6 +244,16 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_bwd_point_kernel(const Pb
         double ab[6];
 #pragma unroll
         for (int c = 0; c < 6; ++c) ab[c] = (b - cc) * ux[c] - e * ux[6 + c];
+        if (ROBUST) {   // (e becomes the residual's adjoint bb)
+          float af[6], bf;
+          gn_row_pn(sf[0], sf[1], sf[2], df, mf, af, bf);
+          const bool clipped = pi_huber_clipped(bf, delta);
+          const double hw = pi_huber_weight(clipped, b, (double)delta);
+          const double hd = clipped ? -hw / b : 0.0;
+#pragma unroll
+          for (int c = 0; c < 6; ++c) ab[c] = hw * ab[c];
+          e = e * (hw + hd * (b - cc));
+        }
         const double* w = ab + 3;
         sb[0] = (m[1] * w[2] - m[2] * w[1]) - e * m[0];
         sb[1] = (m[2] * w[0] - m[0] * w[2]) - e * m[1];
@@ -283,6 +300,17 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_bwd_point_kernel(const Pb
         (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_bwd_point_kernel(const PbBatch pb, const int it, const int first,
+                                                                        const int last) {
+  pb_point<false>(pb, it, first, last, 0.0f);
+}
+
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_bwd_point_kernel(const PbBatch pb, const int it,
+                                                                               const int first, const int last,
+                                                                               const float delta) {
+  pb_point<true>(pb, it, first, last, delta);
+}
+
 __global__ void __launch_bounds__(256) gs_picp_bwd_cast_kernel(const double* __restrict__ in, int64_t n,
                                                                float* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -300,26 +328,28 @@ extern "C" int64_t gs_projective_icp_backward_scratch_bytes(int H, int W, int st
                    2 * pb_rows_bytes(n_map));
 }
 
-extern "C" int gs_projective_icp_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
-                                                    const gs_picp_params* params_host, void* stream) {
-  GS_REQUIRE(seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
-  GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
+// the pass behind both entries; delta: the Huber threshold the forward ran with (0: the plain point kernel)
+static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, int B, int H, int W,
+                       const gs_picp_params* params_host, float delta, void* stream) {
+  PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
+  PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   const gs_picp_params& prm = *params_host;
-  GS_REQUIRE(prm.stride >= 1, "stride must be at least 1");
-  GS_REQUIRE(prm.numiters >= 1, "numiters must be at least 1");
-  GS_REQUIRE(prm.damp > 0.0f && prm.damp < __builtin_inff(), "damp must be positive and finite");
-  GS_REQUIRE(!(prm.dist_th != prm.dist_th) && !(prm.dot_th != prm.dot_th), "a threshold is NaN");
+  PICP_REQUIRE(who, prm.stride >= 1, "stride must be at least 1");
+  PICP_REQUIRE(who, prm.numiters >= 1, "numiters must be at least 1");
+  PICP_REQUIRE(who, prm.damp > 0.0f && prm.damp < __builtin_inff(), "damp must be positive and finite");
+  PICP_REQUIRE(who, !(prm.dist_th != prm.dist_th) && !(prm.dot_th != prm.dot_th), "a threshold is NaN");
+  PICP_CHECK_DELTA(who, delta, "huber_delta");
   const int64_t nslots = picp_slots(H, W, prm.stride), nchunks = gs_ceil_div(nslots, GS_PI_CHUNK);
   for (int b = 0; b < B; ++b) {
     const gs_picp_backward_seq& u = seqs_host[b];
-    GS_REQUIRE(u.vertex && u.normal && u.depth && u.K16 && u.index && u.model_pose16 && u.tape && u.pose_bar16 &&
+    PICP_REQUIRE(who, u.vertex && u.normal && u.depth && u.K16 && u.index && u.model_pose16 && u.tape && u.pose_bar16 &&
                    u.scratch,
                "NULL pointer");
-    GS_REQUIRE(((uintptr_t)u.tape & 7) == 0 && ((uintptr_t)u.scratch & 7) == 0, "misaligned tape or scratch");
-    GS_REQUIRE(u.map.n_bound >= 0, "bad map size");
-    GS_REQUIRE(u.map.n_bound == 0 || (u.map.points && u.map.normals), "NULL pointer (map points / normals)");
+    PICP_REQUIRE(who, ((uintptr_t)u.tape & 7) == 0 && ((uintptr_t)u.scratch & 7) == 0, "misaligned tape or scratch");
+    PICP_REQUIRE(who, u.map.n_bound >= 0, "bad map size");
+    PICP_REQUIRE(who, u.map.n_bound == 0 || (u.map.points && u.map.normals), "NULL pointer (map points / normals)");
     const bool want_map = u.points_bar || u.normals_bar;
-    GS_REQUIRE(u.scratch_bytes >= gs_projective_icp_backward_scratch_bytes(H, W, prm.stride, want_map ? u.map.n_bound : 0),
+    PICP_REQUIRE(who, u.scratch_bytes >= gs_projective_icp_backward_scratch_bytes(H, W, prm.stride, want_map ? u.map.n_bound : 0),
                "scratch too small");
   }
   hipStream_t st = gs_stream(stream);
@@ -355,7 +385,11 @@ extern "C" int gs_projective_icp_backward_batch_f32(const gs_picp_backward_seq* 
     for (int it = prm.numiters - 1; it >= 0; --it) {
       const int first = it == prm.numiters - 1;
       hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(PB_FIN), 0, st, pb, it, first ? 0 : 1);
-      hipLaunchKernelGGL(gs_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first, it == 0 ? 1 : 0);
+      if (delta > 0.0f)
+        hipLaunchKernelGGL(gs_robust_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first,
+                           it == 0 ? 1 : 0, delta);
+      else
+        hipLaunchKernelGGL(gs_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first, it == 0 ? 1 : 0);
     }
     hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(PB_FIN), 0, st, pb, -1, 1);
     for (int b = 0; b < nb; ++b) {
@@ -371,4 +405,15 @@ extern "C" int gs_projective_icp_backward_batch_f32(const gs_picp_backward_seq* 
     GS_LAUNCH_CHECK();
   }
   return GS_OK;
+}
+
+extern "C" int gs_projective_icp_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
+                                                    const gs_picp_params* params_host, void* stream) {
+  return pb_backward(__func__, seqs_host, B, H, W, params_host, 0.0f, stream);
+}
+
+extern "C" int gs_projective_icp_robust_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
+                                                           const gs_picp_params* params_host, float huber_delta,
+                                                           void* stream) {
+  return pb_backward(__func__, seqs_host, B, H, W, params_host, huber_delta, stream);
 }

@@ -35,6 +35,10 @@
 // The 28 terms of a slot are (double)x_g (double)y_g + (double)x_c (double)y_c: two exact products of float32 factors,
 // their sum rounded once; a rejected slot contributes +0.0.  The reduction, the solve, the update and the "no geometric
 // inlier keeps the pose bits" rule are gs_picp.hip's; the colour rows are counted alongside as an integer.
+// The robust entries (gs_projective_icp_color_robust_batch_f32 / _rows_f32) launch the ROBUST instance of the joint body:
+// w as in gs_picp.hip for b, wc = |r| > cdelta ? cdelta / |r| : 1 for the colour residual r BEFORE the weight w is applied
+// (a threshold of 0: that weight is 1), terms (double)w * (x_g y_g) + (double)wc * (x_c y_c), each product exact and
+// rounded once by its weight.  With both thresholds 0 they launch the plain kernel.
 #include "gs_picp_dev.h"
 
 struct PicSeq {
@@ -133,7 +137,19 @@ extern "C" int gs_model_intensity_f32(const float* color, const int64_t* index, 
 }
 
 // ------------------------------------------------------------------ the joint linearisation
-__global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_color_linearize_kernel(const PicBatch pb) {
+// Huber thresholds and weight tables of the robust entries (delta: the point-to-plane residual, metres; cdelta: the
+// colour residual r before color_weight is applied, intensity units; 0 = off; the tables (nslots) may be NULL)
+struct PicRobust {
+  float delta, cdelta;
+  float* weight_out;    // w of a used slot, 0 elsewhere
+  float* cweight_out;   // wc of a slot with a colour row, 0 elsewhere
+};
+
+// The joint linearise kernel's body.  ROBUST: the geometric product of every term carries the Huber weight w of the
+// slot's residual b, the colour product the weight wc of its colour residual r (pi_huber_weight, gs_picp_dev.h); the plain
+// instance is the kernel as it was.
+template <bool ROBUST>
+GS_DEV void pic_linearize(const PicBatch& pb, const PicRobust& rb) {
   __shared__ GsCamera cam;
   __shared__ float Ts[12];
   __shared__ double red[GS_PI_CHUNK / GS_WAVE][LIN_NV];
@@ -153,6 +169,7 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_color_linearize_kernel(co
   int64_t row = -1;
   float a[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, b = 0.0f;
   float ac[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, bc = 0.0f;
+  float w = 1.0f, wc = 1.0f;
   if (in_lattice) {
     const int i = k / pb.g.Wl, j = k - i * pb.g.Wl;
     const int64_t p = (int64_t)(i * pb.g.stride) * pb.g.W + j * pb.g.stride;
@@ -162,6 +179,7 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_color_linearize_kernel(co
                         pb.g.u_hi, pb.g.v_hi, pb.g.dist_th, pb.g.dot_th, row, s, d, m);
     if (code == 0) {
       gn_row_pn(s[0], s[1], s[2], d, m, a, b);
+      if (ROBUST) w = pi_huber_weight(pi_huber_clipped(b, rb.delta), b, rb.delta);
       // the pixel the association read, again, with the camera-frame point (the same device function on the same
       // operands: the same (h2, w2), inside the view -- the slot would be code 2 otherwise)
       int h2 = 0, w2 = 0;
@@ -188,6 +206,7 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_color_linearize_kernel(co
         ac[4] = wgt * (J0 * s[2] - J2 * s[0]);
         ac[5] = wgt * (J1 * s[0] - J0 * s[1]);
         bc = wgt * r;
+        if (ROBUST) wc = pi_huber_weight(pi_huber_clipped(r, rb.cdelta), r, rb.cdelta);
       }
     }
     if (q.code_out) q.code_out[k] = code;
@@ -203,6 +222,10 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_color_linearize_kernel(co
       for (int c = 0; c < 6; ++c) qc.ac_out[6 * (int64_t)k + c] = ac[c];
     }
     if (qc.bc_out) qc.bc_out[k] = bc;
+    if (ROBUST) {
+      if (rb.weight_out) rb.weight_out[k] = code == 0 ? w : 0.0f;
+      if (rb.cweight_out) rb.cweight_out[k] = colored ? wc : 0.0f;
+    }
   }
   const bool used = code == 0;   // (a, b, ac, bc are zero otherwise: every term below is then +0.0)
   const unsigned long long mask = __ballot(used);
@@ -218,18 +241,21 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_color_linearize_kernel(co
   for (int r = 0; r < 6; ++r) {
 #pragma unroll
     for (int c = r; c < 6; ++c) {
-      const double x = pi_wave_tree((double)a[r] * (double)a[c] + (double)ac[r] * (double)ac[c], any);
+      const double x = pi_wave_tree(ROBUST ? pi_term(w, a[r], a[c]) + pi_term(wc, ac[r], ac[c])
+                                             : (double)a[r] * (double)a[c] + (double)ac[r] * (double)ac[c], any);
       if (lane == 0) red[wave][t] = x;
       ++t;
     }
   }
 #pragma unroll
   for (int r = 0; r < 6; ++r) {
-    const double x = pi_wave_tree((double)a[r] * (double)b + (double)ac[r] * (double)bc, any);
+    const double x = pi_wave_tree(ROBUST ? pi_term(w, a[r], b) + pi_term(wc, ac[r], bc)
+                                           : (double)a[r] * (double)b + (double)ac[r] * (double)bc, any);
     if (lane == 0) red[wave][21 + r] = x;
   }
   {
-    const double x = pi_wave_tree((double)b * (double)b + (double)bc * (double)bc, any);
+    const double x = pi_wave_tree(ROBUST ? pi_term(w, b, b) + pi_term(wc, bc, bc)
+                                           : (double)b * (double)b + (double)bc * (double)bc, any);
     if (lane == 0) red[wave][27] = x;
   }
   __syncthreads();
@@ -238,6 +264,15 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_color_linearize_kernel(co
         (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
   if (threadIdx.x == GS_WAVE) q.counts[chunk] = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
   if (threadIdx.x == GS_WAVE + 1) qc.ccounts[chunk] = (ccnt[0] + ccnt[1]) + (ccnt[2] + ccnt[3]);
+}
+
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_color_linearize_kernel(const PicBatch pb) {
+  pic_linearize<false>(pb, PicRobust{0.0f, 0.0f, nullptr, nullptr});
+}
+
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_color_linearize_kernel(const PicBatch pb,
+                                                                                     const PicRobust rb) {
+  pic_linearize<true>(pb, rb);
 }
 
 __global__ void __launch_bounds__(GS_PI_FIN) gs_picp_color_finish_kernel(const PicBatch pb) {
@@ -271,19 +306,23 @@ static void pic_fill_seq(PicSeq& s, const gs_picp_color_seq& u, int nchunks) {
   s.cflag_out = nullptr; s.ac_out = nullptr; s.bc_out = nullptr; s.ccount_out = nullptr;
 }
 
-extern "C" int gs_projective_icp_color_batch_f32(const gs_picp_color_seq* seqs_host, int B, int H, int W,
-                                                 const gs_picp_params* params_host, float color_weight, void* stream) {
-  const char* who = __func__;
+// the solve behind both batch entries; delta / cdelta: the robust entry's thresholds (both 0: the plain kernel)
+static int pic_solve(const char* who, const gs_picp_color_seq* seqs_host, int B, int H, int W,
+                     const gs_picp_params* params_host, float color_weight, float delta, float cdelta, void* stream) {
   PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
   PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   const gs_picp_params& prm = *params_host;
   PICP_CHECK_PARAMS(who, prm);
   PIC_CHECK_WEIGHT(who, color_weight);
+  PICP_CHECK_DELTA(who, delta, "huber_delta");
+  PICP_CHECK_DELTA(who, cdelta, "color_huber_delta");
   for (int b = 0; b < B; ++b) {
     PIC_CHECK_SEQ(who, seqs_host[b]);
     PICP_REQUIRE(who, seqs_host[b].base.out_pose16, "NULL pointer (out_pose16)");
   }
   hipStream_t st = gs_stream(stream);
+  const PicRobust rb{delta, cdelta, nullptr, nullptr};
+  const bool robust = delta > 0.0f || cdelta > 0.0f;
   for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
     const int nb = B - c0 < GS_MAX_BATCH ? B - c0 : GS_MAX_BATCH;
     PicBatch pb;
@@ -301,7 +340,10 @@ extern "C" int gs_projective_icp_color_batch_f32(const gs_picp_color_seq* seqs_h
         pb.s[b].g.T_in = it == 0 ? u.init_pose16 : u.out_pose16;
         pb.s[b].g.trace_row = u.trace ? u.trace + (int64_t)GS_PIC_TRACE * it : nullptr;
       }
-      hipLaunchKernelGGL(gs_picp_color_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb);
+      if (robust)
+        hipLaunchKernelGGL(gs_robust_picp_color_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, rb);
+      else
+        hipLaunchKernelGGL(gs_picp_color_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb);
       hipLaunchKernelGGL(gs_picp_color_finish_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb);
     }
     GS_LAUNCH_CHECK();
@@ -309,17 +351,30 @@ extern "C" int gs_projective_icp_color_batch_f32(const gs_picp_color_seq* seqs_h
   return GS_OK;
 }
 
-extern "C" int gs_projective_icp_color_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
-                                                float dist_th, float dot_th, float color_weight, int32_t* code,
-                                                int64_t* row, float* a6, float* b, float* ac6, float* bc,
-                                                int32_t* colored, double* sums28, int64_t* count, int64_t* color_count,
-                                                void* stream) {
-  GS_REQUIRE(seq_host && H > 0 && W > 0, "bad arguments");
-  GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
-  GS_REQUIRE(stride >= 1, "stride must be at least 1");
-  GS_REQUIRE(!(dist_th != dist_th) && !(dot_th != dot_th), "a threshold is NaN");
-  PIC_CHECK_WEIGHT(__func__, color_weight);
-  PIC_CHECK_SEQ(__func__, *seq_host);
+extern "C" int gs_projective_icp_color_batch_f32(const gs_picp_color_seq* seqs_host, int B, int H, int W,
+                                                 const gs_picp_params* params_host, float color_weight, void* stream) {
+  return pic_solve(__func__, seqs_host, B, H, W, params_host, color_weight, 0.0f, 0.0f, stream);
+}
+
+extern "C" int gs_projective_icp_color_robust_batch_f32(const gs_picp_color_seq* seqs_host, int B, int H, int W,
+                                                        const gs_picp_params* params_host, float color_weight,
+                                                        float huber_delta, float color_huber_delta, void* stream) {
+  return pic_solve(__func__, seqs_host, B, H, W, params_host, color_weight, huber_delta, color_huber_delta, stream);
+}
+
+// the joint linearisation behind both table-level entries; weight / cweight: the robust entry's outputs, or NULL
+static int pic_rows(const char* who, const gs_picp_color_seq* seq_host, int H, int W, int stride, float dist_th,
+                    float dot_th, float color_weight, float delta, float cdelta, int32_t* code, int64_t* row, float* a6,
+                    float* b, float* ac6, float* bc, int32_t* colored, float* weight, float* cweight, double* sums28,
+                    int64_t* count, int64_t* color_count, void* stream) {
+  PICP_REQUIRE(who, seq_host && H > 0 && W > 0, "bad arguments");
+  PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
+  PICP_REQUIRE(who, stride >= 1, "stride must be at least 1");
+  PICP_REQUIRE(who, !(dist_th != dist_th) && !(dot_th != dot_th), "a threshold is NaN");
+  PIC_CHECK_WEIGHT(who, color_weight);
+  PICP_CHECK_DELTA(who, delta, "huber_delta");
+  PICP_CHECK_DELTA(who, cdelta, "color_huber_delta");
+  PIC_CHECK_SEQ(who, *seq_host);
   hipStream_t st = gs_stream(stream);
   PicBatch pb;
   pb.g.B = 1;
@@ -330,9 +385,33 @@ extern "C" int gs_projective_icp_color_rows_f32(const gs_picp_color_seq* seq_hos
   s.g.code_out = code; s.g.row_out = row; s.g.a_out = a6; s.g.b_out = b;
   s.ac_out = ac6; s.bc_out = bc; s.cflag_out = colored;
   s.g.sums_out = sums28; s.g.count_out = count; s.ccount_out = color_count;
-  hipLaunchKernelGGL(gs_picp_color_linearize_kernel, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb);
+  if (delta > 0.0f || cdelta > 0.0f || weight || cweight)   // (both 0 with a table: 1 for every row there is)
+    hipLaunchKernelGGL(gs_robust_picp_color_linearize_kernel, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb,
+                       PicRobust{delta, cdelta, weight, cweight});
+  else
+    hipLaunchKernelGGL(gs_picp_color_linearize_kernel, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb);
   if (sums28 || count || color_count)
     hipLaunchKernelGGL(gs_picp_color_finish_kernel, dim3(1), dim3(GS_PI_FIN), 0, st, pb);
   GS_LAUNCH_CHECK();
   return GS_OK;
+}
+
+extern "C" int gs_projective_icp_color_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
+                                                float dist_th, float dot_th, float color_weight, int32_t* code,
+                                                int64_t* row, float* a6, float* b, float* ac6, float* bc,
+                                                int32_t* colored, double* sums28, int64_t* count, int64_t* color_count,
+                                                void* stream) {
+  return pic_rows(__func__, seq_host, H, W, stride, dist_th, dot_th, color_weight, 0.0f, 0.0f, code, row, a6, b, ac6, bc,
+                  colored, nullptr, nullptr, sums28, count, color_count, stream);
+}
+
+extern "C" int gs_projective_icp_color_robust_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
+                                                       float dist_th, float dot_th, float color_weight,
+                                                       float huber_delta, float color_huber_delta, int32_t* code,
+                                                       int64_t* row, float* a6, float* b, float* ac6, float* bc,
+                                                       int32_t* colored, float* weight, float* color_weight_out,
+                                                       double* sums28, int64_t* count, int64_t* color_count,
+                                                       void* stream) {
+  return pic_rows(__func__, seq_host, H, W, stride, dist_th, dot_th, color_weight, huber_delta, color_huber_delta, code,
+                  row, a6, b, ac6, bc, colored, weight, color_weight_out, sums28, count, color_count, stream);
 }

@@ -1,7 +1,7 @@
 // gs_picp_dev.h — what the projective ICP (gs_picp.hip), its colour form (gs_picp_color.hip) and its backward pass
 // (gs_picp_bwd.hip) share: the lattice geometry, the slot's association at a pose (ONE definition: the backward uses the
-// forward's association exactly, at the taped float32 pose), the fixed-shape wave reduction, the layout of the forward
-// tape, and -- for the two forward files -- the descriptors of a launch, the body of the finish kernel and the checks of
+// forward's association exactly, at the taped float32 pose), the fixed-shape wave reduction, the Huber weight of the
+// robust entries (ONE definition as well), the layout of the forward tape, and -- for the two forward files -- the descriptors of a launch, the body of the finish kernel and the checks of
 // the entry points.
 #pragma once
 #include "gs_assoc_dev.h"
@@ -35,6 +35,18 @@ GS_DEV double pi_wave_tree(double x, const bool any) {
   }
   return x;
 }
+
+// ------------------------------------------------------------------ robust (Huber) weights
+// ONE definition for the forward kernels (float) and the backward pass (double): a residual r beyond the threshold is
+// clipped, its row enters the normal equations with weight delta / |r|, every other row with 1.  delta == 0 switches the
+// weight off; a NaN residual is not clipped.  The flag is always taken from the float32 residual of the forward.
+GS_DEV bool pi_huber_clipped(const float r, const float delta) { return delta > 0.0f && fabsf(r) > delta; }
+template <typename T>
+GS_DEV T pi_huber_weight(const bool clipped, const T r, const T delta) {
+  return clipped ? delta / (r < T(0) ? -r : r) : T(1);
+}
+// a term of the normal equations: the exact product of two float32 factors, weighted (one rounding)
+GS_DEV double pi_term(const float w, const float x, const float y) { return (double)w * ((double)x * (double)y); }
 
 // The association of lattice pixel p at pose Ts (12 floats): the slot's code (0 used, 1 .. 5 the reject codes of the
 // header), the index image's entry where one was read (else -1), the live vertex under Ts and, for a row that was read
@@ -240,6 +252,9 @@ static inline size_t picp_counts_bytes(int64_t nchunks) { return gs_align((size_
     PICP_REQUIRE(who, (prm).damp > 0.0f && (prm).damp < __builtin_inff(), "damp must be positive and finite");          \
     PICP_REQUIRE(who, !((prm).dist_th != (prm).dist_th) && !((prm).dot_th != (prm).dot_th), "a threshold is NaN");      \
   } while (0)
+// a Huber threshold of a robust entry (0: off)
+#define PICP_CHECK_DELTA(who, d, name) \
+  PICP_REQUIRE(who, (d) >= 0.0f && (d) < __builtin_inff(), name " must be finite and not negative")
 
 static inline void picp_fill(PiGeom& g, int H, int W, int stride, float dist_th, float dot_th, float damp) {
   g.H = H; g.W = W; g.stride = stride;

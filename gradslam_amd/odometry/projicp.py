@@ -5,7 +5,8 @@ point-to-plane Gauss-Newton steps with constant damping follow (gs_projective_ic
 search.  The result is detached unless `differentiable` is set: the poses are then on the autograd tape
 (ops.ProjectiveICPFunction, a HIP backward through the Gauss-Newton iterations).  With `color_weight` > 0 the solve
 is the joint geometric + photometric one (gs_projective_icp_color_batch_f32): the view's colour image is rendered too and
-the live frame's colour is compared with it."""
+the live frame's colour is compared with it.  `huber_delta` / `color_huber_delta` > 0 switch on Huber weights
+(the *_robust_* entry points): rows with a large residual are down-weighted instead of pulling the pose at full weight."""
 from typing import Optional, Union
 
 import torch
@@ -39,6 +40,11 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             bit for bit).  With a weight the map must have colours, and the live frame's `rgb_image` is read in the units
             the map's colours are stored in: for colours in 0 ... 255 start from the weight that suits [0, 1] divided by
             255.  It has no backward pass yet: a weight together with `differentiable=True` raises.
+        huber_delta: Huber threshold of the point-to-plane residual in metres (0, the default: off, the plain solve bit
+            for bit).  A used pair whose residual b exceeds it gets the weight huber_delta / |b|.  Works with
+            `differentiable=True`.
+        color_huber_delta: Huber threshold of the colour residual in the intensity units of the map's colours (0: off);
+            needs `color_weight` > 0.
 
     Unlike the point-cloud-pair providers it needs the map and the live frame themselves: call
     `localize(pointclouds, live_frame, prev_poses)`."""
@@ -46,7 +52,8 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
     def __init__(self, numiters: int = 10, damp: float = 1e-8, dist_thresh: Union[float, int] = 0.1,
                  angle_thresh: Union[float, int] = 30, stride: Optional[int] = None,
                  min_confidence: Union[float, int] = 0.0, radius: int = 0, differentiable: bool = False,
-                 color_weight: Union[float, int] = 0.0):
+                 color_weight: Union[float, int] = 0.0, huber_delta: Union[float, int] = 0.0,
+                 color_huber_delta: Union[float, int] = 0.0):
         from .. import ops
         if not isinstance(differentiable, bool):
             raise TypeError("differentiable must be of type bool; but was of type {}.".format(type(differentiable)))
@@ -55,7 +62,13 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
         if color_weight > 0 and differentiable:
             raise ValueError("color_weight > 0 cannot be combined with differentiable=True: the colour term has no "
                              "backward pass yet")
+        ops._picp_huber("huber_delta", huber_delta, "ProjectiveICPOdometryProvider")
+        ops._picp_huber("color_huber_delta", color_huber_delta, "ProjectiveICPOdometryProvider")
+        if color_huber_delta > 0 and not color_weight > 0:
+            raise ValueError("color_huber_delta > 0 needs color_weight > 0: it is the Huber threshold of the colour term")
         self.color_weight = color_weight   # (carried next to _kwargs(): the plain solve does not take it)
+        self.huber_delta = huber_delta     # (as are the Huber thresholds)
+        self.color_huber_delta = color_huber_delta
         self.numiters = numiters
         self.damp = damp
         self.dist_thresh = dist_thresh
@@ -117,7 +130,7 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                        "update on the autograd tape)")
             T = ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
                                          view.index[:, 0], poses.detach(), maps, poses, differentiable=True, guard=guard,
-                                         **self._kwargs())
+                                         huber_delta=self.huber_delta, **self._kwargs())
             return T.unsqueeze(1)
         out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=poses.device)
         if self.color_weight > 0:
@@ -131,10 +144,13 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             model = ops.model_intensity(view.color[:, 0], view.index[:, 0])
             ops.projective_icp_color_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
                                            view.index[:, 0], poses, maps, poses, fr.rgb_image[:, 0], model,
-                                           color_weight=self.color_weight, out=out.view(B, 4, 4), **self._kwargs())
+                                           color_weight=self.color_weight, out=out.view(B, 4, 4),
+                                           huber_delta=self.huber_delta, color_huber_delta=self.color_huber_delta,
+                                           **self._kwargs())
             return out
         view = ops.render_map_batch([(m[0], None) + m[2:] for m in maps], poses.view(B, 1, 4, 4), K, H, W,
                                     radius=self.radius, min_confidence=self.min_confidence)
         ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
-                                 view.index[:, 0], poses, maps, poses, out=out.view(B, 4, 4), **self._kwargs())
+                                 view.index[:, 0], poses, maps, poses, out=out.view(B, 4, 4),
+                                 huber_delta=self.huber_delta, **self._kwargs())
         return out

@@ -956,6 +956,17 @@ def _picp_args(stride, numiters, damp, dist_thresh, angle_thresh):
     return float(dist_thresh), math.cos((angle_thresh * math.pi) / 180)
 
 
+def _picp_huber(name, delta, who="projective_icp"):
+    """the value check of a Huber threshold (huber_delta: metres, color_huber_delta: intensity units): a finite number
+    >= 0, 0 = off"""
+    import math
+    if isinstance(delta, bool) or not isinstance(delta, (float, int)):
+        raise TypeError("{}: {} must be of type float or int; but was of type {}.".format(who, name, type(delta)))
+    if not (math.isfinite(delta) and delta >= 0):
+        raise ValueError("{}: {} ({}) must be finite and not negative.".format(who, name, delta))
+    return float(delta)
+
+
 def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, color=False):
     """Shape / dtype / device checks shared by the batched solve and the table-level call; fills the descriptors.
     Returns (seqs, tensors kept alive, device, B, H, W).  color: the scratch is sized for the colour solve (the plain
@@ -1020,7 +1031,7 @@ def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_pos
 
 def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, init_poses, *, stride=1, numiters=10,
                          damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False, out=None,
-                         differentiable=False, guard=None):
+                         differentiable=False, guard=None, huber_delta=0.0):
     """Frame-to-model tracking by projective data association for B sequences (gs_projective_icp_batch_f32: two launches
     per iteration for 8 sequences, nothing read back).  vertex / normal (B, H, W, 3): LOCAL maps of the live frames,
     depth (B, H, W), K (B, 4, 4); index (B, H, W) int64: the index image of render_map_batch at model_poses (B, 4, 4);
@@ -1032,28 +1043,33 @@ def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, ini
     [inliers, sum of squared residuals, xi(6)].  An iteration without inliers leaves the pose as it is.
     differentiable=True: the same pose bits, on the autograd tape (ProjectiveICPFunction: gradients reach vertex, the map
     points and normals and init_poses; the association, depth, K, model_poses and the live normals are constants);
-    `out` is then refused.  guard: see ProjectiveICPFunction."""
+    `out` is then refused.  guard: see ProjectiveICPFunction.
+    huber_delta (metres, 0 = off): Huber weights (gs_projective_icp_robust_batch_f32): a used slot whose point-to-plane
+    residual b exceeds it enters the normal equations with the weight huber_delta / |b|; the trace's second column is
+    then the weighted sum of squares.  It works with differentiable=True (the weight is differentiated, which slots are
+    clipped is a constant)."""
     if not isinstance(differentiable, bool):
         raise TypeError("projective_icp: differentiable must be of type bool; but was of type {}.".format(
             type(differentiable)))
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
+    huber_delta = _picp_huber("huber_delta", huber_delta)
     if differentiable:
         if out is not None:
             raise ValueError("projective_icp: out= cannot be combined with differentiable=True (autograd owns the "
                              "outputs)")
         cfg = dict(stride=stride, numiters=numiters, damp=damp, dist_thresh=dist_thresh, angle_thresh=angle_thresh,
-                   guard=guard, counts=[(m[-2], m[-1]) for m in maps])
+                   guard=guard, counts=[(m[-2], m[-1]) for m in maps], huber_delta=huber_delta)
         flat = [t for m in maps for t in m[:2]]
         T, trace = ProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses, cfg, *flat)
         return (T, trace) if return_trace else T
     return _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, numiters, damp, dist_th,
-                       dot_th, return_trace, out, None)
+                       dot_th, return_trace, out, None, huber_delta)
 
 
 def _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, numiters, damp, dist_th, dot_th,
-                return_trace, out, tapes):
+                return_trace, out, tapes, huber_delta=0.0):
     """the solve behind projective_icp_batch and ProjectiveICPFunction.forward; tapes: None, or the uint8 (B, tape bytes)
-    buffer the taped entry fills (the same kernels and pose bits)"""
+    buffer the taped entry fills (the same kernels and pose bits); huber_delta > 0: the robust entry"""
     seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp", vertex, normal, depth, K, index, model_poses, maps,
                                            init_poses, stride)
     T = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if out is None else out
@@ -1064,8 +1080,12 @@ def _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, 
         seqs[b].out_pose16 = T.data_ptr() + b * 64
         seqs[b].trace = 0 if trace is None else trace.data_ptr() + b * int(numiters) * PICP_TRACE * 4
     prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
-    if tapes is not None:
-        ptrs = (_C.C.c_void_p * Bn)(*[tapes.data_ptr() + b * tapes.shape[1] for b in range(Bn)])
+    ptrs = None if tapes is None else \
+        (_C.C.c_void_p * Bn)(*[tapes.data_ptr() + b * tapes.shape[1] for b in range(Bn)])
+    if huber_delta > 0:
+        check(lib().gs_projective_icp_robust_batch_f32(seqs, ptrs, Bn, H, W, prm, huber_delta, stream(dev)),
+              "gs_projective_icp_robust_batch_f32")
+    elif tapes is not None:
         check(lib().gs_projective_icp_tape_batch_f32(seqs, ptrs, Bn, H, W, prm, stream(dev)),
               "gs_projective_icp_tape_batch_f32")
     else:
@@ -1080,14 +1100,16 @@ def projective_icp_tape_bytes(numiters):
 
 def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, maps, tapes, pose_bar, *, stride=1,
                                   numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, want_vertex=True,
-                                  want_init=True, want_maps=None):
+                                  want_init=True, want_maps=None, huber_delta=0.0):
     """Reverse mode of projective_icp_batch (gs_projective_icp_backward_batch_f32), arguments as the forward's; tapes:
     the (B, projective_icp_tape_bytes(numiters)) uint8 buffer the taped forward filled; pose_bar (B, 4, 4): the adjoint of
     the poses.  want_maps: per sequence (points, normals) flags, default all True.  Returns (vertex_bar (B, H, W, 3) or
     None, per sequence (points_bar, normals_bar) of the buffers' shapes (None where not wanted), init_pose_bar (B, 4, 4)
     or None).  vertex_bar and init_pose_bar are bitwise reproducible, the map gradients up to the order of float64
-    additions.  An output that is not wanted costs nothing: without map outputs nothing of map size is allocated."""
+    additions.  An output that is not wanted costs nothing: without map outputs nothing of map size is allocated.
+    huber_delta: the threshold the taped forward ran with (gs_projective_icp_robust_backward_batch_f32 when > 0)."""
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
+    huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_backward")
     with torch.no_grad():
         seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp_backward", vertex, normal, depth, K, index, model_poses,
                                                maps, pose_bar, stride)
@@ -1130,16 +1152,20 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
         buf = ws.bytes("picp_bwd%d" % b, nbytes)
         u.scratch, u.scratch_bytes = buf.data_ptr(), int(buf.numel())
     prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
-    check(L.gs_projective_icp_backward_batch_f32(bseqs, Bn, H, W, prm, stream(dev)),
-          "gs_projective_icp_backward_batch_f32")
+    if huber_delta > 0:
+        check(L.gs_projective_icp_robust_backward_batch_f32(bseqs, Bn, H, W, prm, huber_delta, stream(dev)),
+              "gs_projective_icp_robust_backward_batch_f32")
+    else:
+        check(L.gs_projective_icp_backward_batch_f32(bseqs, Bn, H, W, prm, stream(dev)),
+              "gs_projective_icp_backward_batch_f32")
     return vertex_bar, rows_out, init_bar
 
 
 class ProjectiveICPFunction(torch.autograd.Function):
     """projective_icp_batch on the autograd tape: forward = gs_projective_icp_tape_batch_f32 (the plain solve's kernels
     and pose bits, plus the tape), backward = one call of gs_projective_icp_backward_batch_f32.  Inputs: vertex, normal,
-    depth, K, index, model_poses, init_poses, cfg (the keyword arguments, `counts` = per sequence (n_bound, n_dev) and
-    `guard`), then points and normals of every sequence's map.  Gradients reach vertex, init_poses and the map points /
+    depth, K, index, model_poses, init_poses, cfg (the keyword arguments, `counts` = per sequence (n_bound, n_dev),
+    `guard` and optionally `huber_delta`: both passes then run the robust entries), then points and normals of every sequence's map.  Gradients reach vertex, init_poses and the map points /
     normals that require grad (needs_input_grad decides which outputs the kernel is asked for); the association is hard
     and a constant, as are depth, K, model_poses and the live normals.  The backward re-reads the map rows, so the map
     buffers must hold at backward time what they held at the forward; in-place steps write through raw pointers, which
@@ -1155,8 +1181,10 @@ class ProjectiveICPFunction(torch.autograd.Function):
         tapes = torch.empty((int(depth.shape[0]), projective_icp_tape_bytes(kw["numiters"])), dtype=torch.uint8,
                             device=depth.device)
         dist_th, dot_th = _picp_args(kw["stride"], kw["numiters"], kw["damp"], kw["dist_thresh"], kw["angle_thresh"])
+        huber_delta = _picp_huber("huber_delta", cfg.get("huber_delta", 0.0))
         T, trace = _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, kw["stride"],
-                               kw["numiters"], kw["damp"], dist_th, dot_th, True, None, tapes)
+                               kw["numiters"], kw["damp"], dist_th, dot_th, True, None, tapes, huber_delta)
+        kw["huber_delta"] = huber_delta
         ctx.save_for_backward(vertex, normal, depth, K, index, model_poses, tapes, *flat,
                               *[c[1] for c in cfg["counts"]])
         ctx.kw, ctx.bounds, ctx.guard = kw, [c[0] for c in cfg["counts"]], cfg.get("guard")
@@ -1184,11 +1212,11 @@ class ProjectiveICPFunction(torch.autograd.Function):
 
 def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, *, n_dev=None,
                    stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False,
-                   differentiable=False):
+                   differentiable=False, huber_delta=0.0):
     """projective_icp_batch for one sequence without the batch dimension: vertex / normal (H, W, 3), depth (H, W), K /
     model_pose / init_pose (4, 4), index (H, W) int64; n_dev: device int64[1] holding the actual row count of the map
     (map_points.shape[0] is then an upper bound).  Returns the pose (4, 4) (and the trace (numiters, 8)).
-    differentiable: see projective_icp_batch."""
+    differentiable, huber_delta: see projective_icp_batch."""
     for name, t in (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                     ("model_pose", model_pose), ("init_pose", init_pose)):
         if not torch.is_tensor(t):
@@ -1197,19 +1225,25 @@ def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_
                              index.unsqueeze(0), model_pose.reshape(1, 4, 4), [(map_points, map_normals, None, n_dev)],
                              init_pose.reshape(1, 4, 4), stride=stride, numiters=numiters, damp=damp,
                              dist_thresh=dist_thresh, angle_thresh=angle_thresh, return_trace=return_trace,
-                             differentiable=differentiable)
+                             differentiable=differentiable, huber_delta=huber_delta)
     return (r[0][0], r[1][0]) if return_trace else r[0]
 
 
 def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points, map_normals, pose, *, n_dev=None,
-                        stride=1, dist_thresh=0.1, angle_thresh=30.0):
+                        stride=1, dist_thresh=0.1, angle_thresh=30.0, huber_delta=0.0, return_weights=False):
     """ONE linearisation of the projective ICP at `pose` (gs_projective_icp_rows_f32), arguments as projective_icp.  With
     nslots = ceil(H / stride) * ceil(W / stride), slot i * ceil(W / stride) + j standing for pixel (i stride, j stride):
     ProjectiveRows(code int32 (nslots,): 0 used, 1 no depth, 2 outside the model view, 3 no (or a stale) winner, 4 too
     far, 5 normals disagree; row int64 (nslots,): the index image's entry where one was read (codes 0, 3, 4, 5), else -1;
     a (nslots, 6), b (nslots,): the point-to-plane row, zeros unless used; sums float64 (28,): 21 upper-triangular a_i
-    a_j, 6 a_i b, b b; count int64 (1,))."""
+    a_j, 6 a_i b, b b; count int64 (1,)).
+    huber_delta > 0 (gs_projective_icp_robust_rows_f32): sums are the Huber-weighted sums, a and b stay unweighted;
+    return_weights=True returns (ProjectiveRows, weight float32 (nslots,): the weight of a used slot, 0 elsewhere)."""
     dist_th, dot_th = _picp_args(stride, 1, 1.0, dist_thresh, angle_thresh)
+    huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_rows")
+    if not isinstance(return_weights, bool):
+        raise TypeError("projective_icp_rows: return_weights must be of type bool; but was of type {}.".format(
+            type(return_weights)))
     for name, t in (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                     ("model_pose", model_pose), ("pose", pose)):
         if not torch.is_tensor(t):
@@ -1222,6 +1256,13 @@ def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points,
     res = ProjectiveRows(torch.empty(ns, dtype=torch.int32, device=dev), torch.empty(ns, dtype=torch.int64, device=dev),
                          torch.empty((ns, 6), dtype=f32, device=dev), torch.empty(ns, dtype=f32, device=dev),
                          torch.empty(28, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.int64, device=dev))
+    if huber_delta > 0 or return_weights:
+        weight = torch.empty(ns, dtype=f32, device=dev) if return_weights else None
+        check(lib().gs_projective_icp_robust_rows_f32(seqs, H, W, int(stride), dist_th, dot_th, huber_delta,
+                                                      *[ptr(t) for t in res[:4]], ptr(weight),
+                                                      *[ptr(t) for t in res[4:]], stream(dev)),
+              "gs_projective_icp_robust_rows_f32")
+        return (res, weight) if return_weights else res
     check(lib().gs_projective_icp_rows_f32(seqs, H, W, int(stride), dist_th, dot_th, *[ptr(t) for t in res], stream(dev)),
           "gs_projective_icp_rows_f32")
     return res
@@ -1300,7 +1341,8 @@ def _picp_color_seqs(who, seqs, held, Bn, H, W, color, model):
 
 def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, maps, init_poses, color, model, *,
                                color_weight, stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0,
-                               return_trace=False, out=None, differentiable=False):
+                               return_trace=False, out=None, differentiable=False, huber_delta=0.0,
+                               color_huber_delta=0.0):
     """projective_icp_batch with a photometric term (gs_projective_icp_color_batch_f32: the same two launches per
     iteration for 8 sequences, nothing read back).  The arguments of projective_icp_batch, then color (B, H, W, 3): the
     live frames' colour, and model (B, H, W, 4): model_intensity of the views' rendered colour and index images.  A slot
@@ -1309,9 +1351,14 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
     point-to-plane row.  color_weight: metres per intensity unit, finite and >= 0 (0 leaves the geometric solve).  Returns
     the poses (B, 4, 4), detached; with return_trace also (B, numiters, 9) rows [inliers, joint sum of squared residuals,
     xi(6), colour rows].  An iteration without geometric inliers leaves the pose as it is.  differentiable=True is
-    refused: the colour term has no backward pass."""
+    refused: the colour term has no backward pass.
+    huber_delta (metres) / color_huber_delta (intensity units), 0 = off: Huber weights on the point-to-plane residual and
+    on the colour residual before color_weight is applied (gs_projective_icp_color_robust_batch_f32); the trace's second
+    column is then the weighted joint sum of squares."""
     _picp_refuse_differentiable(differentiable)
     weight = _picp_color_weight(color_weight)
+    huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_color")
+    color_huber_delta = _picp_huber("color_huber_delta", color_huber_delta, "projective_icp_color")
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
     who = "projective_icp_color"
     seqs, held, dev, Bn, H, W = _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride,
@@ -1326,8 +1373,13 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
         cseqs[b].base.out_pose16 = T.data_ptr() + b * 64
         cseqs[b].base.trace = 0 if trace is None else trace.data_ptr() + b * int(numiters) * PICP_COLOR_TRACE * 4
     prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
-    check(lib().gs_projective_icp_color_batch_f32(cseqs, Bn, H, W, prm, weight, stream(dev)),
-          "gs_projective_icp_color_batch_f32")
+    if huber_delta > 0 or color_huber_delta > 0:
+        check(lib().gs_projective_icp_color_robust_batch_f32(cseqs, Bn, H, W, prm, weight, huber_delta, color_huber_delta,
+                                                             stream(dev)),
+              "gs_projective_icp_color_robust_batch_f32")
+    else:
+        check(lib().gs_projective_icp_color_batch_f32(cseqs, Bn, H, W, prm, weight, stream(dev)),
+              "gs_projective_icp_color_batch_f32")
     return (T, trace) if return_trace else T
 
 
@@ -1339,9 +1391,11 @@ def _picp_color_single(who, named):
 
 def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, color, model,
                          *, color_weight, n_dev=None, stride=1, numiters=10, damp=1e-8, dist_thresh=0.1,
-                         angle_thresh=30.0, return_trace=False, differentiable=False):
+                         angle_thresh=30.0, return_trace=False, differentiable=False, huber_delta=0.0,
+                         color_huber_delta=0.0):
     """projective_icp_color_batch for one sequence without the batch dimension (arguments as projective_icp, then color
-    (H, W, 3) and model (H, W, 4)).  Returns the pose (4, 4) (and the trace (numiters, 9))."""
+    (H, W, 3) and model (H, W, 4)).  Returns the pose (4, 4) (and the trace (numiters, 9)).  huber_delta,
+    color_huber_delta: see projective_icp_color_batch."""
     _picp_color_single("projective_icp_color", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K),
                                                 ("index", index), ("model_pose", model_pose), ("init_pose", init_pose),
                                                 ("color", color), ("model_intensity", model)))
@@ -1350,17 +1404,27 @@ def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points
                                    [(map_points, map_normals, None, n_dev)], init_pose.reshape(1, 4, 4),
                                    color.unsqueeze(0), model.unsqueeze(0), color_weight=color_weight, stride=stride,
                                    numiters=numiters, damp=damp, dist_thresh=dist_thresh, angle_thresh=angle_thresh,
-                                   return_trace=return_trace, differentiable=differentiable)
+                                   return_trace=return_trace, differentiable=differentiable, huber_delta=huber_delta,
+                                   color_huber_delta=color_huber_delta)
     return (r[0][0], r[1][0]) if return_trace else r[0]
 
 
 def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_points, map_normals, pose, color, model,
-                              *, color_weight, n_dev=None, stride=1, dist_thresh=0.1, angle_thresh=30.0):
+                              *, color_weight, n_dev=None, stride=1, dist_thresh=0.1, angle_thresh=30.0, huber_delta=0.0,
+                              color_huber_delta=0.0, return_weights=False):
     """ONE joint linearisation at `pose` (gs_projective_icp_color_rows_f32), arguments as projective_icp_color.
     ProjectiveColorRows: code, row, a, b as projective_icp_rows; ac (nslots, 6), bc (nslots,): the colour row, zeros
     unless colored; colored int32 (nslots,): 1 where the slot is used and its model pixel has ok = 1; sums float64 (28,):
-    the joint sums; count, color_count int64 (1,)."""
+    the joint sums; count, color_count int64 (1,).
+    huber_delta / color_huber_delta > 0 (gs_projective_icp_color_robust_rows_f32): sums are the Huber-weighted joint sums,
+    the rows stay unweighted; return_weights=True returns (ProjectiveColorRows, weight, color_weight) float32 (nslots,):
+    the weight of a used slot and of a colour row, 0 elsewhere."""
     weight = _picp_color_weight(color_weight)
+    huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_color_rows")
+    color_huber_delta = _picp_huber("color_huber_delta", color_huber_delta, "projective_icp_color_rows")
+    if not isinstance(return_weights, bool):
+        raise TypeError("projective_icp_color_rows: return_weights must be of type bool; but was of type {}.".format(
+            type(return_weights)))
     dist_th, dot_th = _picp_args(stride, 1, 1.0, dist_thresh, angle_thresh)
     who = "projective_icp_color_rows"
     _picp_color_single(who, (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
@@ -1374,6 +1438,14 @@ def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_p
     e = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)   # noqa: E731
     res = ProjectiveColorRows(e(ns, torch.int32), e(ns, torch.int64), e((ns, 6), f32), e(ns, f32), e((ns, 6), f32),
                               e(ns, f32), e(ns, torch.int32), e(28, torch.float64), e(1, torch.int64), e(1, torch.int64))
+    if huber_delta > 0 or color_huber_delta > 0 or return_weights:
+        wt = (e(ns, f32), e(ns, f32)) if return_weights else (None, None)
+        check(lib().gs_projective_icp_color_robust_rows_f32(cseqs, H, W, int(stride), dist_th, dot_th, weight,
+                                                            huber_delta, color_huber_delta, *[ptr(t) for t in res[:7]],
+                                                            ptr(wt[0]), ptr(wt[1]), *[ptr(t) for t in res[7:]],
+                                                            stream(dev)),
+              "gs_projective_icp_color_robust_rows_f32")
+        return (res,) + wt if return_weights else res
     check(lib().gs_projective_icp_color_rows_f32(cseqs, H, W, int(stride), dist_th, dot_th, weight,
                                                  *[ptr(t) for t in res], stream(dev)),
           "gs_projective_icp_color_rows_f32")

@@ -35,19 +35,30 @@ class ICPSLAM(nn.Module):
     are detached, bit for bit what they are with it on.
 
     `color_weight` (0 by default, `odom="projicp"` only): weight of the photometric term of the projective ICP in metres
-    per intensity unit (`ProjectiveICPOdometryProvider(color_weight=...)`); the map must then carry colours."""
+    per intensity unit (`ProjectiveICPOdometryProvider(color_weight=...)`); the map must then carry colours.
+
+    `huber_delta`, `color_huber_delta` (0 by default, `odom="projicp"` only): Huber thresholds of the projective ICP's
+    point-to-plane residual (metres) and colour residual (intensity units; needs `color_weight`), as in
+    `ProjectiveICPOdometryProvider`."""
 
     def __init__(self, *, odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0,
                  B: Union[float, int] = 1.0, B2: Union[float, int] = 1.0, nu: Union[float, int] = 200.0,
                  device: Union[torch.device, str, None] = None, depth_filter: Optional[dict] = None,
-                 odom_differentiable: bool = False, color_weight: Union[float, int] = 0.0):
+                 odom_differentiable: bool = False, color_weight: Union[float, int] = 0.0,
+                 huber_delta: Union[float, int] = 0.0, color_huber_delta: Union[float, int] = 0.0):
         super().__init__()
         from .. import ops
         ops._picp_color_weight(color_weight)
         if color_weight > 0 and odom != "projicp":
             raise ValueError("color_weight is the photometric term of odom='projicp' (got odom={!r})".format(odom))
         self.color_weight = color_weight
+        for name, val in (("huber_delta", huber_delta), ("color_huber_delta", color_huber_delta)):
+            ops._picp_huber(name, val, type(self).__name__)
+            if val > 0 and odom != "projicp":
+                raise ValueError("{} is a Huber threshold of odom='projicp' (got odom={!r})".format(name, odom))
+        self.huber_delta = huber_delta
+        self.color_huber_delta = color_huber_delta
         if not isinstance(odom_differentiable, bool):
             raise TypeError("odom_differentiable must be of type bool; but was of type {}.".format(
                 type(odom_differentiable)))
@@ -70,7 +81,8 @@ class ICPSLAM(nn.Module):
             # provider's 0.1 m (the gate is part of the association, it cannot be switched off)
             odomprov = ProjectiveICPOdometryProvider(numiters, damp, 0.1 if dist_thresh is None else dist_thresh,
                                                      stride=dsratio, differentiable=odom_differentiable,
-                                                     color_weight=color_weight)
+                                                     color_weight=color_weight, huber_delta=huber_delta,
+                                                     color_huber_delta=color_huber_delta)
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio

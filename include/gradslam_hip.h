@@ -833,6 +833,51 @@ GS_API int gs_projective_icp_color_rows_f32(const gs_picp_color_seq* seq_host, i
                                             float* b, float* ac6, float* bc, int32_t* colored, double* sums28,
                                             int64_t* count, int64_t* color_count, void* stream);
 
+/* ------------------------------------------------------------------ projective ICP: robust (Huber) weights ------
+ * Opt-in Huber weights for every solve above (additions only: no struct or signature above changes, the tape row and
+ * every *_scratch_bytes function are reused).  huber_delta (metres) applies to the point-to-plane residual b of a used
+ * slot, color_huber_delta (intensity units of the map's colours) to the colour residual r before color_weight is applied;
+ * both finite and >= 0, 0 = off.  In float32, one rounding per operation, no FMA:
+ *   w  = |b| > huber_delta       ? huber_delta / |b|       : 1        (a NaN residual is not clipped)
+ *   wc = |r| > color_huber_delta ? color_huber_delta / |r| : 1        (1 when color_huber_delta is 0)
+ * The 28 terms of a used slot are (double)w * ((double)x * (double)y) -- the exact product, then one rounding -- and in
+ * the joint solve (double)w * ((double)x_g * (double)y_g) + (double)wc * ((double)x_c * (double)y_c).  Everything else is
+ * the plain solve's: the reduction order, the finish, the update, the counts (the inlier count does not depend on the
+ * weights), "no geometric inlier keeps the pose bits".  The sum of squares (sums28[27], the second float of a trace row,
+ * S[27] of a tape row) is the WEIGHTED sum of squares.  With every delta 0 an entry below launches the kernels of its
+ * plain counterpart: the same bits.
+ *
+ * gs_projective_icp_robust_batch_f32: gs_projective_icp_batch_f32 (tapes_host NULL) or gs_projective_icp_tape_batch_f32
+ * (per sequence a tape buffer) with Huber weights.
+ * gs_projective_icp_robust_rows_f32: gs_projective_icp_rows_f32 plus weight (nslots): w of a used slot, 0 elsewhere; a6 / b
+ * stay the unweighted rows, sums28 are the weighted sums.
+ * gs_projective_icp_robust_backward_batch_f32: gs_projective_icp_backward_batch_f32 for a tape of the robust forward
+ * with the same huber_delta.  The weight is differentiated; the clip flag of a used slot is a constant like the
+ * association and is recomputed as the forward computed it (the float32 b at the taped pose against huber_delta).  With
+ * c = xi . a, e = u . a, w' = -w / b for a clipped slot and 0 otherwise: ab = w ((b - c) u - e xi), and
+ * bb = e (w + w' (b - c)) takes the place of e in sb, points_bar and normals_bar; the scalar stage is unchanged (the
+ * taped S is the weighted system).  Reproducibility, NULL outputs, scratch and launch count as in the plain pass.
+ * gs_projective_icp_color_robust_batch_f32 / _rows_f32: the colour entries with both thresholds; the rows entry also
+ * returns weight (nslots) and color_weight_out (nslots): wc of a slot with a colour row, 0 elsewhere; ac6 / bc stay
+ * unweighted.  Every argument is checked before the first HIP call. */
+GS_API int gs_projective_icp_robust_batch_f32(const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H, int W,
+                                              const gs_picp_params* params_host, float huber_delta, void* stream);
+GS_API int gs_projective_icp_robust_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
+                                             float dot_th, float huber_delta, int32_t* code, int64_t* row, float* a6,
+                                             float* b, float* weight, double* sums28, int64_t* count, void* stream);
+GS_API int gs_projective_icp_robust_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
+                                                       const gs_picp_params* params_host, float huber_delta,
+                                                       void* stream);
+GS_API int gs_projective_icp_color_robust_batch_f32(const gs_picp_color_seq* seqs_host, int B, int H, int W,
+                                                    const gs_picp_params* params_host, float color_weight,
+                                                    float huber_delta, float color_huber_delta, void* stream);
+GS_API int gs_projective_icp_color_robust_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
+                                                   float dist_th, float dot_th, float color_weight, float huber_delta,
+                                                   float color_huber_delta, int32_t* code, int64_t* row, float* a6,
+                                                   float* b, float* ac6, float* bc, int32_t* colored, float* weight,
+                                                   float* color_weight_out, double* sums28, int64_t* count,
+                                                   int64_t* color_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

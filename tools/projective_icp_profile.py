@@ -2,6 +2,7 @@
 frame loop gains or loses with it, and what a launch of it costs (needs the MI355X; fails without one).
 
     python tools/projective_icp_profile.py [--out FILE] [--only localize|slam|launches] [--steps K] [--color-weight W]
+                                           [--huber-delta D] [--color-huber-delta C]
 
 1. One localisation.  640x480 frames of the benchmark's synthetic sequences, the map fused from the first 10 frames under
    the ground-truth poses, frame 10 localised from the pose of frame 9; B = 1 and B = 8.
@@ -27,7 +28,12 @@ frame loop gains or loses with it, and what a launch of it costs (needs the MI35
 --color-weight W (W > 0) adds the joint geometric + photometric solve to parts 1 and 3, alternating with the plain one in
 the same process: the provider with color_weight=W (render with the colour image + ops.model_intensity +
 ops.projective_icp_color_batch), and in part 3 the intensity pre-pass and the colour solve alone.  The benchmark's frame
-colours are per-frame noise: the times hold, the poses of these variants say nothing."""
+colours are per-frame noise: the times hold, the poses of these variants say nothing.
+
+--huber-delta D (metres, D > 0) adds the solve with Huber weights to parts 1 and 3, alternating with the plain one in the
+same process: the provider with huber_delta=D, and in part 3 the robust solve alone (10 and 40 iterations: the slope is
+one robust linearise launch + the plain finish launch).  --color-huber-delta C (C > 0, needs --color-weight) does the
+same for the joint solve with both thresholds."""
 import argparse
 import json
 import os
@@ -80,7 +86,7 @@ def translation_error(T, gt):
     return [float(x) for x in (T.reshape(-1, 4, 4)[:, :3, 3].double() - gt[:3, 3].double()).norm(dim=1).cpu()]
 
 
-def localize_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0):
+def localize_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta=0.0, color_huber_delta=0.0):
     from gradslam_amd.odometry import ProjectiveICPOdometryProvider
     out = []
     for B in (1, 8):
@@ -102,11 +108,21 @@ def localize_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0):
             cprov = {s: ProjectiveICPOdometryProvider(numiters=10, stride=s, color_weight=color_weight) for s in (4, 1)}
             fns["projicp_color_stride4_10it"] = lambda: cprov[4].localize(pc, live, prev)
             fns["projicp_color_stride1_10it"] = lambda: cprov[1].localize(pc, live, prev)
+        if huber_delta > 0:
+            rprov = {s: ProjectiveICPOdometryProvider(numiters=10, stride=s, huber_delta=huber_delta) for s in (4, 1)}
+            fns["projicp_robust_stride4_10it"] = lambda: rprov[4].localize(pc, live, prev)
+            fns["projicp_robust_stride1_10it"] = lambda: rprov[1].localize(pc, live, prev)
+        if color_weight > 0 and (huber_delta > 0 or color_huber_delta > 0):
+            rcprov = {s: ProjectiveICPOdometryProvider(numiters=10, stride=s, color_weight=color_weight,
+                                                       huber_delta=huber_delta, color_huber_delta=color_huber_delta)
+                      for s in (4, 1)}
+            fns["projicp_color_robust_stride4_10it"] = lambda: rcprov[4].localize(pc, live, prev)
+            fns["projicp_color_robust_stride1_10it"] = lambda: rcprov[1].localize(pc, live, prev)
         err = {k: translation_error(fn(), gt) for k, fn in fns.items()}
         for fn in fns.values():
             fn(), fn()
         t = time_round_robin(torch, fns, reps, rounds)
-        rec = {"B": B, "color_weight": color_weight, "H": H, "W": W, "map_rows": rows, "initial_translation_error_m": translation_error(prev, gt)[0],
+        rec = {"B": B, "color_weight": color_weight, "huber_delta": huber_delta, "color_huber_delta": color_huber_delta, "H": H, "W": W, "map_rows": rows, "initial_translation_error_m": translation_error(prev, gt)[0],
                "variants": {k: dict(t[k], translation_error_m=err[k]) for k in fns}}
         for s in (4, 1):
             rec["speedup_stride%d_vs_gradicp_20it" % s] = \
@@ -116,7 +132,7 @@ def localize_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0):
     return out
 
 
-def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0):
+def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta=0.0, color_huber_delta=0.0):
     out = []
     for B in (1, 8):
         pc, live, prev, _ = scene(torch, gs, B)
@@ -142,6 +158,14 @@ def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0):
                             "model_intensity": lambda: ops.model_intensity(view.color[:, 0], view.index[:, 0]),
                             "solve_color_10it": lambda: ops.projective_icp_color_batch(*cargs, numiters=10, **kw),
                             "solve_color_40it": lambda: ops.projective_icp_color_batch(*cargs, numiters=40, **kw)})
+            if huber_delta > 0:
+                fns.update({"solve_robust_%dit" % n: (lambda n=n: ops.projective_icp_batch(
+                    *args, stride=stride, numiters=n, huber_delta=huber_delta)) for n in (10, 40)})
+            robust_color = color_weight > 0 and (huber_delta > 0 or color_huber_delta > 0)
+            if robust_color:
+                fns.update({"solve_color_robust_%dit" % n: (lambda n=n: ops.projective_icp_color_batch(
+                    *cargs, numiters=n, huber_delta=huber_delta, color_huber_delta=color_huber_delta, **kw))
+                    for n in (10, 40)})
             for fn in fns.values():
                 fn(), fn()
             t = time_round_robin(torch, fns, reps, rounds)
@@ -154,6 +178,14 @@ def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0):
                 rec["color_weight"] = color_weight
                 rec["us_per_iteration_color"] = \
                     (t["solve_color_40it"]["median_ms"] - t["solve_color_10it"]["median_ms"]) / 30 * 1e3
+            if huber_delta > 0:
+                rec["huber_delta"] = huber_delta
+                rec["us_per_iteration_robust"] = \
+                    (t["solve_robust_40it"]["median_ms"] - t["solve_robust_10it"]["median_ms"]) / 30 * 1e3
+            if robust_color:
+                rec["color_huber_delta"] = color_huber_delta
+                rec["us_per_iteration_color_robust"] = \
+                    (t["solve_color_robust_40it"]["median_ms"] - t["solve_color_robust_10it"]["median_ms"]) / 30 * 1e3
             print(json.dumps(rec), flush=True)
             out.append(rec)
     return out
@@ -192,9 +224,18 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--color-weight", type=float, default=0.0,
                     help="> 0: also time the joint geometric + photometric solve (parts 1 and 3)")
+    ap.add_argument("--huber-delta", type=float, default=0.0,
+                    help="> 0 (metres): also time the solve with Huber weights (parts 1 and 3)")
+    ap.add_argument("--color-huber-delta", type=float, default=0.0,
+                    help="> 0 (intensity units, needs --color-weight): Huber weights on the colour rows of the joint solve")
     args = ap.parse_args()
     if not (args.color_weight >= 0 and args.color_weight < float("inf")):
         ap.error("--color-weight must be finite and not negative")
+    for name in ("huber_delta", "color_huber_delta"):
+        if not (getattr(args, name) >= 0 and getattr(args, name) < float("inf")):
+            ap.error("--%s must be finite and not negative" % name.replace("_", "-"))
+    if args.color_huber_delta > 0 and not args.color_weight > 0:
+        ap.error("--color-huber-delta needs --color-weight")
     import torch
     if not torch.cuda.is_available():
         sys.exit("tools/projective_icp_profile.py measures on the GPU: no HIP device found (nothing is measured on the CPU)")
@@ -202,11 +243,13 @@ def main():
     from gradslam_amd import ops
     out = {"device": torch.cuda.get_device_name(0)}
     if args.only in (None, "localize"):
-        out["one_localisation"] = localize_times(torch, gs, ops, color_weight=args.color_weight)
+        out["one_localisation"] = localize_times(torch, gs, ops, color_weight=args.color_weight,
+                                                 huber_delta=args.huber_delta, color_huber_delta=args.color_huber_delta)
     if args.only in (None, "slam"):
         out["slam_window"] = slam_runs(torch, gs, args.steps)
     if args.only in (None, "launches"):
-        out["launches"] = launch_times(torch, gs, ops, color_weight=args.color_weight)
+        out["launches"] = launch_times(torch, gs, ops, color_weight=args.color_weight, huber_delta=args.huber_delta,
+                                       color_huber_delta=args.color_huber_delta)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
