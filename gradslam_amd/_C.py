@@ -82,6 +82,12 @@ class PruneSeq(C.Structure):
                 ("n_out", C.c_void_p), ("removed_out", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class CarveSeq(C.Structure):
+    """gs_carve_seq: one map, its L depth views with poses, and the two outputs of gs_free_space_dc_f32."""
+    _fields_ = [("map", MapView), ("depth", C.c_void_p), ("depth_stride_view", C.c_int64), ("poses16", C.c_void_p),
+                ("K16", C.c_void_p), ("violations", C.c_void_p), ("keep", C.c_void_p)]
+
+
 class PicpSeq(C.Structure):
     """gs_picp_seq: one live frame, the model view's index image and the map for the projective ICP."""
     _fields_ = [("vertex", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("K16", C.c_void_p),
@@ -193,6 +199,7 @@ _PROTOS = {
     "gs_render_map_backward_dc_f32": [C.POINTER(RenderBackwardSeq), _i32, _i32, _i32, _i32, _i32, _vp],
     "gs_prune_scratch_bytes": [_i64],
     "gs_prune_map_dc_f32": [C.POINTER(PruneSeq), _i32, _f, _i32, _vp],
+    "gs_free_space_dc_f32": [C.POINTER(CarveSeq), _i32, _i32, _i32, _i32, _f, _i32, _i32, _vp],
     "gs_bilateral_depth_f32": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _f, _f, _vp, _vp, _vp],
     "gs_bilateral_depth_backward_f32": [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f, _f, _vp, _vp],
     "gs_projective_icp_scratch_bytes": [_i32, _i32, _i32],

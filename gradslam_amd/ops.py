@@ -1548,6 +1548,135 @@ def prune_map(points, normals, colors, features, n_dev=None, min_confidence=None
     return PrunedMaps(r.maps[0], r.counts, r.removed)
 
 
+# ----------------------------------------------------------------------------------- free-space carving
+FreeSpace = collections.namedtuple("FreeSpace", ["violations", "keep"])
+CARVE_MAX_WINDOW = 3
+
+
+def _carve_args(who, margin, window, min_views):
+    """the checks the C entry repeats, made before anything is allocated; names the argument"""
+    if isinstance(margin, bool) or not isinstance(margin, (float, int)):
+        raise TypeError("%s: margin must be of type float or int; but was of type %s." % (who, type(margin)))
+    for name, val in (("window", window), ("min_views", min_views)):
+        if isinstance(val, bool) or not isinstance(val, int):
+            raise TypeError("%s: %s must be of type int; but was of type %s." % (who, name, type(val)))
+    margin = float(margin)
+    if not (margin >= 0.0 and margin != float("inf")):
+        raise ValueError("%s: margin must be finite and >= 0; got %r" % (who, margin))
+    if not 0 <= window <= CARVE_MAX_WINDOW:
+        raise ValueError("%s: window must be in 0..%d; got %r" % (who, CARVE_MAX_WINDOW, window))
+    if min_views < 1:
+        raise ValueError("%s: min_views must be >= 1; got %r" % (who, min_views))
+    return margin, int(window), int(min_views)
+
+
+def free_space_batch(maps, depth, poses, K, *, margin=0.05, window=1, min_views=1, out=None):
+    """Which rows of B maps do L depth frames each see through (gs_free_space_dc_f32: one launch per 8 sequences,
+    whatever L is; nothing is read back).  maps: per sequence (points, normals, colors, ccounts, n_bound, n_dev) as in
+    render_map_batch -- only points and the counts are read.  depth (B, L, H, W) or (B, L, H, W, 1), poses (B, L, 4, 4)
+    camera-to-world, K (B, 4, 4).  A row violates a view iff it projects into the frame (the projection of the map update
+    and of render_map), its pixel has depth > 0 and every pixel with depth > 0 of the (2 window + 1)^2 square around it,
+    clipped to the image, has (depth - z) > margin in float32 (z: the row's camera-frame depth).  Returns
+    FreeSpace(violations, keep): per sequence an (n_bound,) int32 tensor (views the row violates) and an (n_bound,) uint8
+    tensor (violations < min_views); rows at or beyond the device count hold 0 in both.  out: a FreeSpace (or pair) of
+    per-sequence lists to write into (a list, or an entry of it, may be None: that output is then not produced).  The
+    result is detached and never on the autograd tape: the mask is a constant, like the association."""
+    who = "free_space"
+    margin, window, min_views = _carve_args(who, margin, window, min_views)
+    for name, val in (("depth", depth), ("poses", poses), ("K", K)):
+        if not torch.is_tensor(val):
+            raise TypeError("%s: expected %s to be of type tensor; got %s" % (who, name, type(val)))
+    if not isinstance(maps, (list, tuple)) or len(maps) == 0:
+        raise ValueError("%s: maps must be a non-empty list of (points, normals, colors, ccounts, n_bound, n_dev)" % who)
+    Bn = len(maps)
+    if depth.ndim == 5 and depth.shape[-1] == 1:
+        depth = depth[..., 0]
+    if depth.ndim != 4 or depth.shape[0] != Bn or depth.shape[1] == 0 or depth.shape[2] == 0 or depth.shape[3] == 0:
+        raise ValueError("%s: depth must be (B, L, H, W) or (B, L, H, W, 1) with B = %d maps and L, H, W >= 1; got %s"
+                         % (who, Bn, tuple(depth.shape)))
+    Lv, H, W = (int(s) for s in depth.shape[1:])
+    if tuple(poses.shape) != (Bn, Lv, 4, 4):
+        raise ValueError("%s: poses must be %s; got %s" % (who, (Bn, Lv, 4, 4), tuple(poses.shape)))
+    if tuple(K.shape) != (Bn, 4, 4):
+        raise ValueError("%s: K must be %s; got %s" % (who, (Bn, 4, 4), tuple(K.shape)))
+    if H * W >= 1 << 31:
+        raise ValueError("%s: depth images of 2^31 pixels or more are not supported" % who)
+    if out is not None and (len(out) != 2 or any(o is not None and len(o) != Bn for o in out)):
+        raise ValueError("%s: out must be (violations, keep), each a list with one entry per map or None" % who)
+    for b, m in enumerate(maps):
+        if not isinstance(m, (list, tuple)) or len(m) != 6 or not torch.is_tensor(m[0]):
+            raise ValueError("%s: maps[%d] must be (points, normals, colors, ccounts, n_bound, n_dev)" % (who, b))
+        if m[0].ndim != 2 or m[0].shape[1] != 3:
+            raise ValueError("%s: points must be (rows, 3); got %s for maps[%d]" % (who, tuple(m[0].shape), b))
+    poses, K = _c(poses.detach()), _c(K.detach())
+    # the images are read in place where their rows are contiguous (a frame slice of a longer stack keeps its strides)
+    depth = depth.detach() if depth.dtype == f32 else depth.detach().to(f32)
+    if depth.stride(3) != 1 or depth.stride(2) != W:
+        depth = depth.contiguous()
+    dev = require_device(poses, K, depth[0, 0])
+    seqs = (_C.CarveSeq * Bn)()
+    # held: where _c had to copy a sequence's points, the copy must outlive the loop -- freed at the next iteration, its
+    # block could be handed to a later sequence's output before the one launch below is enqueued
+    viol, keep, held = [], [], []
+    for b in range(Bn):
+        m = maps[b]
+        P, n_bound, n_dev = _c(m[0].detach()), m[4], m[5]
+        require_device(P, n_dev, poses)
+        n_bound = int(P.shape[0]) if n_bound is None else min(int(n_bound), int(P.shape[0]))
+        if n_bound < 0:
+            raise ValueError("%s: negative n_bound" % who)
+        outs = []
+        for i, (name, dtype) in enumerate((("violations", torch.int32), ("keep", torch.uint8))):
+            if out is None:
+                t = torch.empty((n_bound,), dtype=dtype, device=dev)
+            else:
+                t = None if out[i] is None else out[i][b]
+                if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (n_bound,) or
+                                      not t.is_contiguous()):
+                    raise ValueError("%s: out.%s[%d] must be a contiguous %s tensor of shape (%d,)"
+                                     % (who, name, b, str(dtype).split(".")[-1], n_bound))
+            outs.append(t)
+        if outs[0] is None and outs[1] is None:
+            raise ValueError("%s: out must ask for violations or keep (or both) of every map" % who)
+        require_device(outs[0], outs[1], poses)
+        u = seqs[b]
+        u.map = _C.MapView(P.data_ptr() if n_bound > 0 else 0, 0, 0, 0, int(P.shape[0]), n_bound,
+                           0 if n_dev is None else n_dev.data_ptr())
+        u.depth = depth.data_ptr() + b * int(depth.stride(0)) * 4
+        u.depth_stride_view = int(depth.stride(1)) if Lv > 1 else H * W
+        u.poses16, u.K16 = poses.data_ptr() + b * Lv * 64, K.data_ptr() + b * 64
+        u.violations, u.keep = (0 if t is None else t.data_ptr() for t in outs)
+        viol.append(outs[0])
+        keep.append(outs[1])
+        held.append(P)
+    check(lib().gs_free_space_dc_f32(seqs, Bn, Lv, H, W, margin, window, min_views, stream(dev)),
+          "gs_free_space_dc_f32")
+    return FreeSpace(viol, keep)
+
+
+def free_space(points, depth, poses, K, *, n_dev=None, margin=0.05, window=1, min_views=1, out=None):
+    """One map against L depth frames: free_space_batch for B = 1 without the batch dimension.  points (rows, 3); depth
+    (L, H, W), (L, H, W, 1) or (H, W); poses (L, 4, 4) or (4, 4); K (4, 4); n_dev: device int64[1] holding the actual
+    row count (points.shape[0] is then an upper bound).  Returns FreeSpace(violations (rows,) int32, keep (rows,)
+    uint8)."""
+    for name, val in (("points", points), ("depth", depth), ("poses", poses), ("K", K)):
+        if not torch.is_tensor(val):
+            raise TypeError("free_space: expected %s to be of type tensor; got %s" % (name, type(val)))
+    if depth.ndim == 2:
+        depth = depth.unsqueeze(0)
+    if poses.ndim == 2:
+        poses = poses.unsqueeze(0)
+    if tuple(K.shape) != (4, 4):
+        raise ValueError("free_space: K must be (4, 4); got %s" % (tuple(K.shape),))
+    if out is not None:
+        if len(out) != 2:
+            raise ValueError("free_space: out must be (violations, keep)")
+        out = tuple(None if t is None else [t] for t in out)
+    r = free_space_batch([(points, None, None, None, None, n_dev)], depth.unsqueeze(0), poses.unsqueeze(0),
+                         K.reshape(1, 4, 4), margin=margin, window=window, min_views=min_views, out=out)
+    return FreeSpace(r.violations[0], r.keep[0])
+
+
 # ----------------------------------------------------------------------------------- bilateral depth filter
 BILATERAL_MAX_RADIUS = 8
 

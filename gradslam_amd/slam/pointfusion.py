@@ -27,6 +27,13 @@ class PointFusion(ICPSLAM):
     the step -- fast path, generic path and `forward` alike -- works on the bilaterally filtered copy of the live frame
     and writes the recovered pose back to the caller's frame.
 
+    Free-space carving (off by default): with `carve_margin` set, every `carve_every`-th `step` of a map ends its map
+    update with `pointclouds.carve_(frame, margin=carve_margin, window=carve_window)` against the frame it just fused
+    (the filtered copy when `depth_filter` is set: what was fused is what is tested) under the pose the step recovered:
+    surfels the frame sees through -- something that has moved away -- are removed (Keller et al.'s free-space
+    violations).  It runs before the pruning schedule, on the fast path, the generic path and `forward` alike.  With
+    `carve_margin=None` a step makes no such call.
+
     `odom_differentiable`: as in `ICPSLAM` (the projective ICP of `odom="projicp"` on the autograd tape).
     `color_weight`: as in `ICPSLAM` (the photometric term of `odom="projicp"`).
     `huber_delta`, `color_huber_delta`: as in `ICPSLAM` (the Huber thresholds of `odom="projicp"`)."""
@@ -38,7 +45,8 @@ class PointFusion(ICPSLAM):
                  device: Union[torch.device, str, None] = None, prune_min_confidence: Union[float, int, None] = None,
                  prune_min_age: int = 20, prune_every: int = 10, depth_filter: Optional[dict] = None,
                  odom_differentiable: bool = False, color_weight: Union[float, int] = 0.0,
-                 huber_delta: Union[float, int] = 0.0, color_huber_delta: Union[float, int] = 0.0):
+                 huber_delta: Union[float, int] = 0.0, color_huber_delta: Union[float, int] = 0.0,
+                 carve_margin: Union[float, int, None] = None, carve_window: int = 1, carve_every: int = 1):
         super().__init__(odom=odom, dsratio=dsratio, numiters=numiters, damp=damp, dist_thresh=dist_thresh,
                          lambda_max=lambda_max, B=B, B2=B2, nu=nu, device=device, depth_filter=depth_filter,
                          odom_differentiable=odom_differentiable, color_weight=color_weight, huber_delta=huber_delta,
@@ -76,6 +84,22 @@ class PointFusion(ICPSLAM):
         self.prune_min_confidence = prune_min_confidence
         self.prune_min_age = prune_min_age
         self.prune_every = prune_every
+        if not (carve_margin is None or
+                (isinstance(carve_margin, (float, int)) and not isinstance(carve_margin, bool))):
+            raise TypeError("Carve margin must be of type float or int or None; but was of type {}.".format(
+                type(carve_margin)))
+        for name, val in (("carve_window", carve_window), ("carve_every", carve_every)):
+            if not isinstance(val, int) or isinstance(val, bool):
+                raise TypeError("{} must be of type int; but was of type {}.".format(name, type(val)))
+        if carve_margin is not None and not (0 <= carve_margin < math.inf):
+            raise ValueError("carve_margin ({}) must be finite and non-negative.".format(carve_margin))
+        if not 0 <= carve_window <= 3:
+            raise ValueError("carve_window ({}) must be in 0..3.".format(carve_window))
+        if carve_every < 1:
+            raise ValueError("carve_every ({}) must be at least 1.".format(carve_every))
+        self.carve_margin = carve_margin
+        self.carve_window = carve_window
+        self.carve_every = carve_every
 
     def step(self, pointclouds: Pointclouds, live_frame: RGBDImages, prev_frame=None, inplace: bool = False):
         # the plain SLAM loop (in place, nothing on the autograd tape, a map with surfels): one foreign call per frame
@@ -94,15 +118,28 @@ class PointFusion(ICPSLAM):
                 self._step(pointclouds, work, prev_frame, inplace)
         if work is not live_frame:
             live_frame.poses = work.poses
-        if self.prune_min_confidence is not None:
-            self._end_step(pointclouds, res[0])
+        if self.carve_margin is not None or self.prune_min_confidence is not None:
+            if res[0] is not pointclouds:
+                # an out-of-place step returns a new container: it takes the marks and the step counters once, before
+                # the carve, whose compaction rewrites the marks that the pruning schedule then reads
+                res[0]._carry_epochs(pointclouds)
+            if self.carve_margin is not None:
+                self._carve_step(res[0], work)
+            if self.prune_min_confidence is not None:
+                self._end_step(res[0])
         return res
 
-    def _end_step(self, before: Pointclouds, pointclouds: Pointclouds):
+    def _carve_step(self, pointclouds: Pointclouds, frame: RGBDImages):
+        """free-space carving of a step (fast and generic path alike): on every carve_every-th step of this map, remove
+        the surfels that the frame just fused (`frame`: the filtered copy with depth_filter; it carries the recovered
+        pose) sees through"""
+        pointclouds._carve_steps += 1
+        if pointclouds._carve_steps % self.carve_every == 0:
+            pointclouds.carve_(frame, margin=self.carve_margin, window=self.carve_window, min_views=1)
+
+    def _end_step(self, pointclouds: Pointclouds):
         """the pruning schedule of a step (fast and generic path alike): prune on every prune_every-th step of this map,
         then record the epoch.  The prune comes first, so that min_age = k protects the rows of the last k steps."""
-        if pointclouds is not before:     # (an out-of-place step returns a new container)
-            pointclouds._carry_epochs(before)
         pointclouds._prune_steps += 1
         if pointclouds._prune_steps % self.prune_every == 0:
             pointclouds.prune_(self.prune_min_confidence, min_age=self.prune_min_age)

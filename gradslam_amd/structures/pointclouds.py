@@ -154,6 +154,7 @@ class Pointclouds(object):
         self._marks = None      # (B, MAX_MARKS) int64 on self.device: the counts at the last _n_marks epochs (mark_epoch)
         self._n_marks = 0
         self._prune_steps = 0   # steps a pruning PointFusion has taken on this map (the step counter lives with the map)
+        self._carve_steps = 0   # the same for a carving PointFusion (carve_margin)
         self.last_pruned = None  # (B,) int64: rows the last prune_ removed per sequence (on the map's device, never synced)
         self.equisized = None
 
@@ -597,6 +598,7 @@ class Pointclouds(object):
     def _carry_epochs(self, other, ids=None):
         """takes the epoch marks and the step counter of `other` (of its sequences `ids`)"""
         self._prune_steps = other._prune_steps
+        self._carve_steps = other._carve_steps
         self._n_marks = other._n_marks if other._marks is not None else 0
         if other._marks is None:
             self._marks = None
@@ -711,6 +713,57 @@ class Pointclouds(object):
     def prune(self, min_confidence: Optional[float] = None, *, keep=None, min_age: int = 0):
         r"""Out-of-place `prune_`: returns a pruned copy (the copy resolves device-side counts, as `clone` does)."""
         return self.clone().prune_(min_confidence, keep=keep, min_age=min_age)
+
+    # ------------------------------------------------------------------ free-space carving
+    def _free_space(self, who, frames, margin, window, min_views, want):
+        """ops.free_space_batch of the map, read in place with its device-side counts, against all frames of `frames`;
+        want: (violations, keep)"""
+        from .. import ops
+        from .rgbdimages import RGBDImages
+        if not isinstance(frames, RGBDImages):
+            raise TypeError("Expected frames to be of type gradslam.RGBDImages. Got {0}.".format(type(frames)))
+        margin, window, min_views = ops._carve_args(who, margin, window, min_views)
+        B = len(self._n_host)
+        if B == 0 or self._buf["points"] is None:
+            raise ValueError("cannot carve an empty pointclouds object")
+        if frames.poses is None:
+            raise ValueError("{} needs frames with poses".format(who))
+        if frames.shape[0] != B:
+            raise ValueError("frames must hold one sequence per pointcloud. Got {} != {}.".format(frames.shape[0], B))
+        d = frames.depth_image
+        d = d[:, :, 0] if frames.channels_first else d[..., 0]   # (B, L, H, W), a view: one channel either way
+        maps, out_v, out_k = [], [], []
+        for b in range(B):
+            bound, n_dev = self._count_of(b)   # (never forces a device-side count to the host)
+            maps.append((self._buf["points"][b], None, None, None, bound, n_dev))
+            rows = min(bound, int(self._buf["points"][b].shape[0]))
+            out_v.append(torch.empty(rows, dtype=torch.int32, device=self.device) if want[0] else None)
+            out_k.append(torch.empty(rows, dtype=torch.uint8, device=self.device) if want[1] else None)
+        return ops.free_space_batch(maps, d, frames.poses, frames.intrinsics[:, 0], margin=margin, window=window,
+                                    min_views=min_views, out=(out_v, out_k))
+
+    def free_space_violations(self, frames, *, margin: float = 0.05, window: int = 1):
+        r"""Per sequence the (N_b,) int32 number of frames of `frames` (an `RGBDImages` of shape (B, L, H, W) with poses)
+        that see through each point: the point projects into the frame (the projection of the map update and of
+        `render`), its pixel has depth, and every pixel with depth of the (2 window + 1)^2 square around it measures
+        more than `margin` behind the point (`ops.free_space_batch`; HIP, detached).  The map is only read, with its
+        device-side counts: it can be called between steps; rows the host-side bound holds beyond a device-side count
+        read 0."""
+        return self._free_space("free_space_violations", frames, margin, window, 1, (True, False)).violations
+
+    def carve_(self, frames, *, margin: float = 0.05, window: int = 1, min_views: int = 1):
+        r"""Free-space carving in place: removes the points that at least `min_views` frames of `frames` see through
+        (`free_space_violations`), keeping the order of the rest.  No confidence rule is applied.  The removal is
+        `prune_(keep=...)` with the mask the carve kernel wrote: counts stay on the device, the epoch marks are
+        rewritten, `last_pruned` holds the removed rows, and a differentiable render or projective-ICP solve taken before
+        it refuses a late backward, as for `prune_`.  A map on the autograd tape takes `prune_`'s torch path with the
+        (detached) mask.  Returns self."""
+        keep = self._free_space("carve_", frames, margin, window, min_views, (False, True)).keep
+        return self.prune_(None, keep=keep)
+
+    def carve(self, frames, *, margin: float = 0.05, window: int = 1, min_views: int = 1):
+        r"""Out-of-place `carve_`: returns a carved copy (the copy resolves device-side counts, as `clone` does)."""
+        return self.clone().carve_(frames, margin=margin, window=window, min_views=min_views)
 
     def _prune_hip(self, conf, keep, young_mark):
         from .. import ops

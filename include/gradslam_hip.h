@@ -667,6 +667,38 @@ GS_API int64_t gs_prune_scratch_bytes(int64_t n_bound);
 GS_API int gs_prune_map_dc_f32(const gs_prune_seq* seqs_host, int B, float min_confidence, int use_confidence,
                                void* stream);
 
+/* ------------------------------------------------------------------ free-space carving ------
+ * Which rows of B maps do L depth frames each see through (Keller et al.'s "free-space violations"; the reference never
+ * removes a surfel)?  The pass only marks; the removal is gs_prune_map_dc_f32 with the keep mask written here.
+ * With n = min(*map.n_dev, map.n_bound) (n_bound when n_dev is NULL), row r < n with point p, and view l with the
+ * camera-to-world pose T_l = poses16 + 16 l, the intrinsics K16 and the H x W depth image D_l = depth + l *
+ * depth_stride_view: the row projects as in gs_project_map_f32 / gs_render_map_dc_f32 (the same device function: the
+ * pixel (h, w) the map update and the model view give it, u_hi = (float)((double)W - 0.999), v_hi likewise), z is the
+ * third camera-frame coordinate of that projection.  Row r VIOLATES view l iff all of
+ *   - it projects into the frame, in front of the camera (rows behind the camera or outside the frame never violate);
+ *   - D_l[h, w] > 0 (false for 0, negative values and NaN: no measurement, no evidence);
+ *   - for every pixel (hh, ww) of the (2 window + 1)^2 square around (h, w), clipped to the image, with D_l[hh, ww] > 0:
+ *     (D_l[hh, ww] - z) > margin, in float32, one subtraction and one compare.  Equality does not violate, a NaN z does
+ *     not violate, pixels without depth abstain: the row lies in front of the nearest measured depth of its window.
+ * violations[r] = number of views of the call that r violates; keep[r] = (violations[r] < min_views) ? 1 : 0.  Rows in
+ * [n, n_bound) get violations = 0 and keep = 0 and are never read.  Both outputs hold n_bound elements, every one is
+ * written (no clearing needed); either may be NULL, not both.  Only map.points, map.n_bound and map.n_dev are read.  Rows
+ * of a depth image are contiguous; depth_stride_view is in floats (a (B, L, H, W, 1) stack is read in place).
+ * margin finite and >= 0, window in 0..3, min_views >= 1, H * W < 2^31; every argument is checked before the first HIP
+ * call.  One launch per 8 sequences whatever L is; no atomics, nothing is read back; the outputs are integers and a pure
+ * function of the inputs. */
+typedef struct gs_carve_seq {
+  gs_map_view map;
+  const float* depth;          /* view 0: (H, W), rows contiguous */
+  int64_t depth_stride_view;   /* floats from one view's image to the next */
+  const float* poses16;        /* (L, 16) */
+  const float* K16;
+  int32_t* violations;         /* out (n_bound) or NULL */
+  uint8_t* keep;               /* out (n_bound) or NULL */
+} gs_carve_seq;
+GS_API int gs_free_space_dc_f32(const gs_carve_seq* seqs_host, int B, int L, int H, int W, float margin, int window,
+                                int min_views, void* stream);
+
 /* ------------------------------------------------------------------ bilateral depth filter ------
  * The edge-preserving pre-pass on the raw depth of Keller et al. and KinectFusion (no counterpart in the reference),
  * batched over n frames of H x W.  Frame f starts at depth + f * stride_frame and its row h at + h * stride_row (in
