@@ -13,6 +13,7 @@ import torch
 
 from gradslam_amd.datasets.synthetic import make_sequence
 from oracle import oracle as o
+from tests import icp_lm_ref as lm
 
 pytestmark = pytest.mark.gpu
 
@@ -291,6 +292,18 @@ def test_icp_against_oracle_and_reference(ops, golden, mode, key, iters):
     assert (host(idx) == oidx).mean() >= 0.999
     np.testing.assert_allclose(host(tr)[:, :2], otr[:, :2], rtol=1e-4, atol=1e-9)   # err, new_err
     np.testing.assert_allclose(host(tr)[:, 4:10], otr[:, 4:10], rtol=1e-3, atol=1e-7)  # xi
+    # damp and sig: the rejects of this fixture sit at new_err == err to 7 digits, so the columns are held to the replay of
+    # the kernel's own err / new_err (tests/icp_lm_ref.py; the bounds are those of tests/test_hip_icp_lm.py), not to the
+    # oracle's decisions
+    r = lm.replay(host(tr), dict(mode=mode, damp=1e-8, lambda_max=2.0, B=1.0, B2=1.0, nu=200.0))
+    if mode == 0:
+        same_bits(host(tr)[:, 2], r["damp"])
+        same_bits(host(tr)[:, 3], np.ones(iters, np.float32))
+    else:
+        k = np.arange(iters)
+        assert np.all(np.abs(host(tr)[:, 2] - r["damp"].astype(np.float64)) <= 5 * (k + 1) * lm.EPS32 * r["damp"])
+        assert np.all(np.abs(host(tr)[:, 3] - r["sig"].astype(np.float64)) <= 4 * lm.EPS32 * r["sig"])
+    assert not host(tr)[:, 10:].any()
     np.testing.assert_allclose(host(T), g["%s%d_T" % (key, iters)], rtol=0, atol=2e-5)
     assert (host(idx) == g["%s%d_idx" % (key, iters)]).mean() > 0.995
 
