@@ -31,91 +31,60 @@
 // linearise body: w = |b| > delta ? delta / |b| : 1 in float32 (pi_huber_weight), every term (double)w * ((double)x *
 // (double)y); the finish kernel, the reduction and the counts are the plain ones, S[27] is the weighted sum of squares.
 // With delta = 0 they launch the plain kernel.
+// What this file holds: the body of the linearise kernel with its two term expressions, the traits of the plain solve and
+// the entries.  The block prologue (pi_prologue), the association (pi_associate), the chunk reduction (pi_chunk_reduce,
+// PI_PAIRS), the column sum of the partials (pi_column_sums), the finish body (pi_finish) and the host drivers
+// (picp_solve, picp_rows) are gs_picp_dev.h's, shared with gs_picp_color.hip and gs_picp_bwd.hip.
 #include "gs_picp_dev.h"
 
-// The linearise kernel's body.  ROBUST: every term of a used slot carries the Huber weight of its residual b
-// (pi_huber_weight, gs_picp_dev.h), which also goes to weight_out (nslots, 0 for a slot that is not used) when asked for;
-// the plain instance is the kernel as it was.
+// The linearise kernel's body: prologue, association, the row z = (a0 .. a5, b), the table outputs, the chunk reduction.
+// ROBUST: every term of a used slot carries the Huber weight of its residual b (pi_huber_weight), which also goes to
+// rb.weight_out (nslots, 0 for a slot that is not used) when asked for; the colour half of rb is ignored.
 template <bool ROBUST>
-GS_DEV void pi_linearize(const PiBatch& pb, const float delta, float* __restrict__ weight_out) {
+GS_DEV void pi_linearize(const PiBatch& pb, const PiRobust& rb) {
   __shared__ GsCamera cam;
   __shared__ float Ts[12];
-  __shared__ double red[GS_PI_CHUNK / GS_WAVE][LIN_NV];
   __shared__ int cnt[GS_PI_CHUNK / GS_WAVE];
   const PiSeq& q = pb.s[blockIdx.x % pb.g.B];
-  const int chunk = blockIdx.x / pb.g.B;
-  if (threadIdx.x == 0) cam = gs_camera(q.model_pose16, q.K16);
-  if (threadIdx.x >= GS_WAVE && threadIdx.x < GS_WAVE + 12) Ts[threadIdx.x - GS_WAVE] = q.T_in[threadIdx.x - GS_WAVE];
-  __syncthreads();
-  const int lane = threadIdx.x & (GS_WAVE - 1), wave = threadIdx.x / GS_WAVE;
-  const int k = chunk * GS_PI_CHUNK + (int)threadIdx.x;
-  const bool in_lattice = k < pb.g.nslots;
-  const int64_t n_map = gs_count(q.n);
+  const PiSlot t = pi_prologue(q.in, pb.g, q.T_in, cam, Ts);
+  const int64_t n_map = gs_count(q.in.n);
   int code = 1;
   int64_t row = -1;
-  float a[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, b = 0.0f, w = 1.0f;
-  if (in_lattice) {
-    const int i = k / pb.g.Wl, j = k - i * pb.g.Wl;
-    const int64_t p = (int64_t)(i * pb.g.stride) * pb.g.W + j * pb.g.stride;
+  float z[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, w = 1.0f;
+  if (t.in_lattice) {
     float s[3];
     float4 d, m;
-    code = pi_associate(Ts, cam, q.vertex, q.normal, q.depth, q.index, q.points, q.normals, n_map, p, pb.g.H, pb.g.W,
-                        pb.g.u_hi, pb.g.v_hi, pb.g.dist_th, pb.g.dot_th, row, s, d, m);
-    if (code == 0) gn_row_pn(s[0], s[1], s[2], d, m, a, b);
-    if (q.code_out) q.code_out[k] = code;
-    if (q.row_out) q.row_out[k] = row;
-    if (q.a_out) {
-#pragma unroll
-      for (int c = 0; c < 6; ++c) q.a_out[6 * (int64_t)k + c] = a[c];
-    }
-    if (q.b_out) q.b_out[k] = b;
+    code = pi_associate(Ts, cam, q.in, pb.g, n_map, t.p, row, s, d, m);
+    if (code == 0) gn_row_pn(s[0], s[1], s[2], d, m, z, z[6]);
+    pi_table_out(q, t.k, code, row, z);
     if (ROBUST) {
-      if (code == 0) w = pi_huber_weight(pi_huber_clipped(b, delta), b, delta);
-      if (weight_out) weight_out[k] = code == 0 ? w : 0.0f;
+      if (code == 0) w = pi_huber_weight(pi_huber_clipped(z[6], rb.delta), z[6], rb.delta);
+      if (rb.weight_out) rb.weight_out[t.k] = code == 0 ? w : 0.0f;
     }
   }
-  const bool used = code == 0;   // (a, b are zero otherwise: every term below is then +0.0)
+  const bool used = code == 0;   // (z is zero otherwise: every term below is then +0.0)
   const unsigned long long mask = __ballot(used);
-  if (lane == 0) cnt[wave] = __popcll(mask);
-  // a wave without a used slot adds up +0.0 only: its sums are +0.0, no shuffle needed
-  const bool any = mask != 0ull;
-  int t = 0;
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-#pragma unroll
-    for (int c = r; c < 6; ++c) {
-      const double x = pi_wave_tree(ROBUST ? pi_term(w, a[r], a[c]) : (double)a[r] * (double)a[c], any);
-      if (lane == 0) red[wave][t] = x;
-      ++t;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    const double x = pi_wave_tree(ROBUST ? pi_term(w, a[r], b) : (double)a[r] * (double)b, any);
-    if (lane == 0) red[wave][21 + r] = x;
-  }
-  {
-    const double x = pi_wave_tree(ROBUST ? pi_term(w, b, b) : (double)b * (double)b, any);
-    if (lane == 0) red[wave][27] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < LIN_NV)
-    q.partials[(int64_t)chunk * LIN_NV + threadIdx.x] =
-        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-  if (threadIdx.x == GS_WAVE) q.counts[chunk] = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
+  if (t.lane == 0) cnt[t.wave] = __popcll(mask);
+  double* partial_row = q.partials + (int64_t)t.chunk * LIN_NV;
+  if constexpr (ROBUST)
+    pi_chunk_reduce<LIN_NV>([&](const int i) { return pi_term(w, z[PI_PAIRS.x[i]], z[PI_PAIRS.y[i]]); }, mask != 0ull,
+                            partial_row);
+  else
+    pi_chunk_reduce<LIN_NV>([&](const int i) { return (double)z[PI_PAIRS.x[i]] * (double)z[PI_PAIRS.y[i]]; }, mask != 0ull,
+                            partial_row);
+  if (threadIdx.x == GS_WAVE) q.counts[t.chunk] = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
 }
 
 __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_linearize_kernel(const PiBatch pb) {
-  pi_linearize<false>(pb, 0.0f, nullptr);
+  pi_linearize<false>(pb, PiRobust{0.0f, 0.0f, nullptr, nullptr});
 }
 
-__global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_linearize_kernel(const PiBatch pb, const float delta,
-                                                                               float* __restrict__ weight_out) {
-  pi_linearize<true>(pb, delta, weight_out);
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_linearize_kernel(const PiBatch pb, const PiRobust rb) {
+  pi_linearize<true>(pb, rb);
 }
 
 __global__ void __launch_bounds__(GS_PI_FIN) gs_picp_finish_kernel(const PiBatch pb) {
-  pi_finish<false>(pb.s[blockIdx.x], pb.g.nchunks, pb.g.damp, nullptr, nullptr);   // (the body: gs_picp_dev.h)
+  pi_finish<false>(pb.s[blockIdx.x], pb.g.nchunks, pb.g.damp, nullptr, nullptr);
 }
 
 extern "C" int64_t gs_projective_icp_scratch_bytes(int H, int W, int stride) {
@@ -128,104 +97,52 @@ extern "C" int64_t gs_projective_icp_tape_bytes(int numiters) {
   return numiters >= 1 ? (int64_t)numiters * (int64_t)sizeof(PiTapeRow) : 0;
 }
 
-// the solve behind the batch entries; tapes_host: per sequence the device buffer of numiters tape rows, or NULL
-// (untaped); delta: the Huber threshold of the robust entry (0: the plain kernel)
-static int picp_solve(const char* who, const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H, int W,
-                      const gs_picp_params* params_host, float delta, void* stream) {
-  PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
-  PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
-  const gs_picp_params& prm = *params_host;
-  PICP_CHECK_PARAMS(who, prm);
-  PICP_CHECK_DELTA(who, delta, "huber_delta");
-  for (int b = 0; b < B; ++b) {
-    PICP_CHECK_SEQ(who, seqs_host[b]);
-    PICP_REQUIRE(who, seqs_host[b].out_pose16, "NULL pointer (out_pose16)");
-    PICP_REQUIRE(who, !tapes_host || (tapes_host[b] && ((uintptr_t)tapes_host[b] & 7) == 0), "NULL or misaligned tape");
+// the traits of the plain solve for the drivers of gs_picp_dev.h
+struct PiPlain {
+  using Seq = gs_picp_seq;
+  using Batch = PiBatch;
+  static constexpr int TRACE = GS_PI_TRACE;
+  static constexpr auto linearize = gs_picp_linearize_kernel;
+  static constexpr auto robust_linearize = gs_robust_picp_linearize_kernel;
+  static constexpr auto finish = gs_picp_finish_kernel;
+  static const gs_picp_seq& base(const Seq& u) { return u; }
+  static PiSeq& seq(Batch& pb, int b) { return pb.s[b]; }
+  static int check(const char* who, const Seq& u) {
+    PICP_CHECK_SEQ(who, u);
+    return GS_OK;
   }
-  hipStream_t st = gs_stream(stream);
-  for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
-    const int nb = B - c0 < GS_MAX_BATCH ? B - c0 : GS_MAX_BATCH;
-    PiBatch pb;
-    pb.g.B = nb;
-    picp_fill(pb.g, H, W, prm.stride, prm.dist_th, prm.dot_th, prm.damp);
-    for (int b = 0; b < nb; ++b) {
-      picp_fill_seq(pb.s[b], seqs_host[c0 + b], pb.g.nchunks);
-      pb.s[b].T_out = seqs_host[c0 + b].out_pose16;
-    }
-    const unsigned blocks = (unsigned)nb * (unsigned)pb.g.nchunks;   // < 8 * 2^23
-    for (int it = 0; it < prm.numiters; ++it) {
-      for (int b = 0; b < nb; ++b) {
-        const gs_picp_seq& u = seqs_host[c0 + b];
-        pb.s[b].T_in = it == 0 ? u.init_pose16 : u.out_pose16;
-        pb.s[b].trace_row = u.trace ? u.trace + (int64_t)GS_PI_TRACE * it : nullptr;
-        pb.s[b].tape_row = tapes_host ? static_cast<PiTapeRow*>(tapes_host[c0 + b]) + it : nullptr;
-      }
-      if (delta > 0.0f)
-        hipLaunchKernelGGL(gs_robust_picp_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, delta,
-                           static_cast<float*>(nullptr));
-      else
-        hipLaunchKernelGGL(gs_picp_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb);
-      hipLaunchKernelGGL(gs_picp_finish_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb);
-    }
-    GS_LAUNCH_CHECK();
-  }
-  return GS_OK;
-}
+  static void fill(Batch& pb, int b, const Seq& u, float) { picp_fill_seq(pb.s[b], u, pb.g.nchunks); }
+  static void color_outputs(Batch&, const PiRowsOut&) {}
+};
 
 extern "C" int gs_projective_icp_batch_f32(const gs_picp_seq* seqs_host, int B, int H, int W,
                                            const gs_picp_params* params_host, void* stream) {
-  return picp_solve(__func__, seqs_host, nullptr, B, H, W, params_host, 0.0f, stream);
+  return picp_solve<PiPlain>(__func__, seqs_host, nullptr, B, H, W, params_host, 0.0f, 0.0f, 0.0f, stream);
 }
 
 extern "C" int gs_projective_icp_tape_batch_f32(const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H, int W,
                                                 const gs_picp_params* params_host, void* stream) {
   GS_REQUIRE(tapes_host, "NULL pointer (tapes)");
-  return picp_solve(__func__, seqs_host, tapes_host, B, H, W, params_host, 0.0f, stream);
+  return picp_solve<PiPlain>(__func__, seqs_host, tapes_host, B, H, W, params_host, 0.0f, 0.0f, 0.0f, stream);
 }
 
 extern "C" int gs_projective_icp_robust_batch_f32(const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H,
                                                   int W, const gs_picp_params* params_host, float huber_delta,
                                                   void* stream) {
-  return picp_solve(__func__, seqs_host, tapes_host, B, H, W, params_host, huber_delta, stream);
-}
-
-// the linearisation behind both table-level entries; weight: the robust entry's output, or NULL
-static int picp_rows(const char* who, const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th, float dot_th,
-                     float delta, int32_t* code, int64_t* row, float* a6, float* b, float* weight, double* sums28,
-                     int64_t* count, void* stream) {
-  PICP_REQUIRE(who, seq_host && H > 0 && W > 0, "bad arguments");
-  PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
-  PICP_REQUIRE(who, stride >= 1, "stride must be at least 1");
-  PICP_REQUIRE(who, !(dist_th != dist_th) && !(dot_th != dot_th), "a threshold is NaN");
-  PICP_CHECK_DELTA(who, delta, "huber_delta");
-  PICP_CHECK_SEQ(who, *seq_host);
-  hipStream_t st = gs_stream(stream);
-  PiBatch pb;
-  pb.g.B = 1;
-  picp_fill(pb.g, H, W, stride, dist_th, dot_th, 1.0f);
-  picp_fill_seq(pb.s[0], *seq_host, pb.g.nchunks);
-  pb.s[0].code_out = code; pb.s[0].row_out = row; pb.s[0].a_out = a6; pb.s[0].b_out = b;
-  pb.s[0].sums_out = sums28; pb.s[0].count_out = count;
-  if (delta > 0.0f || weight)   // (delta == 0 with a weight table: the robust kernel writes 1 for every used slot)
-    hipLaunchKernelGGL(gs_robust_picp_linearize_kernel, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb, delta,
-                       weight);
-  else
-    hipLaunchKernelGGL(gs_picp_linearize_kernel, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb);
-  if (sums28 || count) hipLaunchKernelGGL(gs_picp_finish_kernel, dim3(1), dim3(GS_PI_FIN), 0, st, pb);
-  GS_LAUNCH_CHECK();
-  return GS_OK;
+  return picp_solve<PiPlain>(__func__, seqs_host, tapes_host, B, H, W, params_host, 0.0f, huber_delta, 0.0f, stream);
 }
 
 extern "C" int gs_projective_icp_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
                                           float dot_th, int32_t* code, int64_t* row, float* a6, float* b,
                                           double* sums28, int64_t* count, void* stream) {
-  return picp_rows(__func__, seq_host, H, W, stride, dist_th, dot_th, 0.0f, code, row, a6, b, nullptr, sums28, count,
-                   stream);
+  return picp_rows<PiPlain>(__func__, seq_host, H, W, stride, dist_th, dot_th, 0.0f, PiRobust{0.0f, 0.0f, nullptr, nullptr},
+                            PiRowsOut{code, row, a6, b, nullptr, nullptr, nullptr, sums28, count, nullptr}, stream);
 }
 
 extern "C" int gs_projective_icp_robust_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
                                                  float dot_th, float huber_delta, int32_t* code, int64_t* row, float* a6,
                                                  float* b, float* weight, double* sums28, int64_t* count, void* stream) {
-  return picp_rows(__func__, seq_host, H, W, stride, dist_th, dot_th, huber_delta, code, row, a6, b, weight, sums28,
-                   count, stream);
+  return picp_rows<PiPlain>(__func__, seq_host, H, W, stride, dist_th, dot_th, 0.0f,
+                            PiRobust{huber_delta, 0.0f, weight, nullptr},
+                            PiRowsOut{code, row, a6, b, nullptr, nullptr, nullptr, sums28, count, nullptr}, stream);
 }

@@ -35,12 +35,13 @@
 // touched.
 // gs_projective_icp_robust_backward_batch_f32 (a tape of the forward with Huber weights, the same huber_delta) launches
 // the ROBUST instance of the point stage (see pb_point); everything else, the scalar stage included, is shared.
+// From gs_picp_dev.h, ONE definition with the forward: the inputs and the geometry of a launch (PiInputs, PiGeom), the
+// point stage's block prologue (pi_prologue), pi_associate, the chunk reduction (pi_chunk_reduce, here with 12 terms) and
+// the scalar stage's column sum of the chunk partials (pi_column_sums, here starting from 0.0).
 #include "gs_picp_dev.h"
 #include "gs_se3_f64.h"
 
 constexpr int PB_NV = 12;          // 3x3 outer-product sum + 3-vector sum
-constexpr int PB_FIN = 256;        // threads of the scalar-stage block
-constexpr int PB_TILE = 256;       // chunk partial rows per LDS tile: 256 * 12 doubles = 24 KB
 
 struct PbState {       // per sequence, between the launches
   double Tb[12];       // dL/dT of the iteration boundary being crossed, without the sums of the point stage after it
@@ -51,15 +52,7 @@ struct PbState {       // per sequence, between the launches
 };
 
 struct PbSeq {
-  const float* vertex;
-  const float* normal;
-  const float* depth;
-  const float* K16;
-  const int64_t* index;
-  const float* model_pose16;
-  const float* points;
-  const float* normals;
-  GsCount n;
+  PiInputs in;
   const PiTapeRow* tape;
   const float* pose_bar16;
   float* vertex_bar;        // (H, W, 3) or NULL
@@ -72,16 +65,12 @@ struct PbSeq {
 };
 struct PbBatch {
   PbSeq s[GS_MAX_BATCH];
-  int B, H, W, stride, Wl, nslots, nchunks, numiters;
-  float u_hi, v_hi, dist_th, dot_th, damp;
+  PiGeom g;
 };
 
 // Scalar stage in front of the point stage of iteration `it` (it == -1: the last one, which only hands out
 // init_pose_bar).  have_sums: a point stage ran before (false for the first launch, whose Tb is the upstream adjoint).
-__global__ void __launch_bounds__(PB_FIN) gs_picp_bwd_scalar_kernel(const PbBatch pb, const int it, const int have_sums) {
-  static_assert(PB_TILE * PB_NV % PB_FIN == 0, "a tile is a whole number of loads per thread");
-  constexpr int PER = PB_TILE * PB_NV / PB_FIN;   // 12
-  __shared__ double tile[PB_TILE * PB_NV];
+__global__ void __launch_bounds__(GS_PI_FIN) gs_picp_bwd_scalar_kernel(const PbBatch pb, const int it, const int have_sums) {
   __shared__ double G[PB_NV];
   const PbSeq& q = pb.s[blockIdx.x];
   const int tid = threadIdx.x;
@@ -89,33 +78,8 @@ __global__ void __launch_bounds__(PB_FIN) gs_picp_bwd_scalar_kernel(const PbBatc
   // first one) Tb keeps its bits -- x + 0.0 would turn a -0.0 of the upstream adjoint into +0.0.  (state->active is the
   // flag of the point stage that ran last; this launch rewrites it only after every thread has passed the barrier below.)
   const bool add_sums = have_sums && q.state->active != 0;
-  if (add_sums) {   // the forward's finish kernel: the table moves through LDS, column i is added up in ascending order
-    const int64_t total = (int64_t)pb.nchunks * PB_NV;
-    double nxt[PER];
-#pragma unroll
-    for (int r = 0; r < PER; ++r) {
-      const int64_t i = tid + PB_FIN * r;
-      nxt[r] = i < total ? q.partials[i] : 0.0;
-    }
-    double s = 0.0;
-    for (int base = 0; base < pb.nchunks; base += PB_TILE) {
-      __syncthreads();
-#pragma unroll
-      for (int r = 0; r < PER; ++r) tile[tid + PB_FIN * r] = nxt[r];
-      __syncthreads();
-      if (base + PB_TILE < pb.nchunks) {
-#pragma unroll
-        for (int r = 0; r < PER; ++r) {
-          const int64_t i = (int64_t)(base + PB_TILE) * PB_NV + tid + PB_FIN * r;
-          nxt[r] = i < total ? q.partials[i] : 0.0;
-        }
-      }
-      if (tid < PB_NV) {
-        const int m = pb.nchunks - base < PB_TILE ? pb.nchunks - base : PB_TILE;
-#pragma unroll 8
-        for (int c = 0; c < m; ++c) s = s + tile[c * PB_NV + tid];
-      }
-    }
+  if (add_sums) {   // (block-uniform) column i in ascending chunk order, the chain starting from 0.0
+    const double s = pi_column_sums<PB_NV, false>(q.partials, pb.g.nchunks);
     if (tid < PB_NV) G[tid] = s;
   } else if (tid < PB_NV) {
     G[tid] = 0.0;
@@ -164,7 +128,7 @@ __global__ void __launch_bounds__(PB_FIN) gs_picp_bwd_scalar_kernel(const PbBatc
     for (int c = r; c < 6; ++c) {
       const float v = (float)tr.S[t];
       ++t;
-      Hm[6 * r + c] = Hm[6 * c + r] = (double)(r == c ? v + pb.damp : v);
+      Hm[6 * r + c] = Hm[6 * c + r] = (double)(r == c ? v + pb.g.damp : v);
     }
   d_solve6(Hm, xb, u);
   // Tb <- exp(xi)^T Tb
@@ -192,40 +156,30 @@ GS_DEV void pb_point(const PbBatch& pb, const int it, const int first, const int
   __shared__ float Ts[12];
   __shared__ double ux[12];   // u(6), xi(6)
   __shared__ int active;
-  __shared__ double red[GS_PI_CHUNK / GS_WAVE][PB_NV];
-  const PbSeq& q = pb.s[blockIdx.x % pb.B];
-  const int chunk = blockIdx.x / pb.B;
-  if (threadIdx.x == 0) {
-    cam = gs_camera(q.model_pose16, q.K16);
-    active = q.state->active;
-  }
-  if (threadIdx.x >= GS_WAVE && threadIdx.x < GS_WAVE + 12) Ts[threadIdx.x - GS_WAVE] = q.tape[it].T[threadIdx.x - GS_WAVE];
+  const PbSeq& q = pb.s[blockIdx.x % pb.g.B];
+  // (what this stage needs besides the camera and the pose, in front of the prologue's barrier)
+  if (threadIdx.x == 0) active = q.state->active;
   if (threadIdx.x >= 2 * GS_WAVE && threadIdx.x < 2 * GS_WAVE + 12) {
     const int i = threadIdx.x - 2 * GS_WAVE;
     ux[i] = i < 6 ? q.state->u[i] : q.state->xi[i - 6];
   }
-  __syncthreads();
-  const int lane = threadIdx.x & (GS_WAVE - 1), wave = threadIdx.x / GS_WAVE;
-  const int k = chunk * GS_PI_CHUNK + (int)threadIdx.x;
-  const bool in_lattice = k < pb.nslots;
+  const PiSlot t = pi_prologue(q.in, pb.g, q.tape[it].T, cam, Ts);
+  const int64_t p = t.p;
+  const int k = t.k;
   bool used = false;
   double sb[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
-  int64_t p = 0;
-  if (in_lattice) {
-    const int i = k / pb.Wl, j = k - i * pb.Wl;
-    p = (int64_t)(i * pb.stride) * pb.W + j * pb.stride;
+  if (t.in_lattice) {
     if (active) {   // (block-uniform; an iteration without inliers has no used slot)
-      const int64_t n_map = gs_count(q.n);
+      const int64_t n_map = gs_count(q.in.n);
       int64_t row;
       float sf[3];
       float4 df, mf;
-      used = pi_associate(Ts, cam, q.vertex, q.normal, q.depth, q.index, q.points, q.normals, n_map, p, pb.H, pb.W,
-                          pb.u_hi, pb.v_hi, pb.dist_th, pb.dot_th, row, sf, df, mf) == 0;
+      used = pi_associate(Ts, cam, q.in, pb.g, n_map, p, row, sf, df, mf) == 0;
       if (used) {
         double s[3], a[6];
         const double d[3] = {(double)df.x, (double)df.y, (double)df.z}, m[3] = {(double)mf.x, (double)mf.y, (double)mf.z};
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = (double)q.vertex[3 * p + c];
+        for (int c = 0; c < 3; ++c) v[c] = (double)q.in.vertex[3 * p + c];
 #pragma unroll
         for (int c = 0; c < 3; ++c)
           s[c] = (double)Ts[4 * c] * v[0] + (double)Ts[4 * c + 1] * v[1] + (double)Ts[4 * c + 2] * v[2] + (double)Ts[4 * c + 3];
@@ -279,25 +233,9 @@ GS_DEV void pb_point(const PbBatch& pb, const int it, const int first, const int
       }
     }
   }
-  // the 12 sums of sb [v^T 1] in the forward's reduction shape; a wave without a used slot adds up +0.0 only
-  const bool any = __ballot(used) != 0ull;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double x = pi_wave_tree(sb[r] * v[c], any);
-      if (lane == 0) red[wave][3 * r + c] = x;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const double x = pi_wave_tree(sb[r], any);
-    if (lane == 0) red[wave][9 + r] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < PB_NV)
-    q.partials[(int64_t)chunk * PB_NV + threadIdx.x] =
-        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  // the 12 sums of sb [v^T 1] in the forward's reduction shape: terms 0 .. 8 the outer product, 9 .. 11 sb
+  pi_chunk_reduce<PB_NV>([&](const int i) { return i < 9 ? sb[i / 3] * v[i % 3] : sb[i - 9]; }, __ballot(used) != 0ull,
+                         q.partials + (int64_t)t.chunk * PB_NV);
 }
 
 __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_bwd_point_kernel(const PbBatch pb, const int it, const int first,
@@ -334,10 +272,7 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
   PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
   PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   const gs_picp_params& prm = *params_host;
-  PICP_REQUIRE(who, prm.stride >= 1, "stride must be at least 1");
-  PICP_REQUIRE(who, prm.numiters >= 1, "numiters must be at least 1");
-  PICP_REQUIRE(who, prm.damp > 0.0f && prm.damp < __builtin_inff(), "damp must be positive and finite");
-  PICP_REQUIRE(who, !(prm.dist_th != prm.dist_th) && !(prm.dot_th != prm.dot_th), "a threshold is NaN");
+  PICP_CHECK_PARAMS(who, prm);
   PICP_CHECK_DELTA(who, delta, "huber_delta");
   const int64_t nslots = picp_slots(H, W, prm.stride), nchunks = gs_ceil_div(nslots, GS_PI_CHUNK);
   for (int b = 0; b < B; ++b) {
@@ -356,17 +291,11 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
   for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
     const int nb = B - c0 < GS_MAX_BATCH ? B - c0 : GS_MAX_BATCH;
     PbBatch pb;
-    pb.B = nb; pb.H = H; pb.W = W; pb.stride = prm.stride;
-    pb.Wl = (int)gs_ceil_div(W, prm.stride);
-    pb.nslots = (int)nslots; pb.nchunks = (int)nchunks; pb.numiters = prm.numiters;
-    pb.u_hi = (float)((double)W - 0.999); pb.v_hi = (float)((double)H - 0.999);
-    pb.dist_th = prm.dist_th; pb.dot_th = prm.dot_th; pb.damp = prm.damp;
+    picp_fill(pb.g, nb, H, W, prm.stride, prm.dist_th, prm.dot_th, prm.damp);
     for (int b = 0; b < nb; ++b) {
       const gs_picp_backward_seq& u = seqs_host[c0 + b];
       PbSeq& s = pb.s[b];
-      s.vertex = u.vertex; s.normal = u.normal; s.depth = u.depth; s.K16 = u.K16; s.index = u.index;
-      s.model_pose16 = u.model_pose16; s.points = u.map.points; s.normals = u.map.normals;
-      s.n = GsCount{u.map.n_bound, u.map.n_dev};
+      picp_fill_inputs(s.in, u);
       s.tape = static_cast<const PiTapeRow*>(u.tape);
       s.pose_bar16 = u.pose_bar16; s.vertex_bar = u.vertex_bar; s.init_pose_bar16 = u.init_pose_bar16;
       char* p = static_cast<char*>(u.scratch);
@@ -384,14 +313,14 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
     const unsigned blocks = (unsigned)nb * (unsigned)nchunks;
     for (int it = prm.numiters - 1; it >= 0; --it) {
       const int first = it == prm.numiters - 1;
-      hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(PB_FIN), 0, st, pb, it, first ? 0 : 1);
+      hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb, it, first ? 0 : 1);
       if (delta > 0.0f)
         hipLaunchKernelGGL(gs_robust_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first,
                            it == 0 ? 1 : 0, delta);
       else
         hipLaunchKernelGGL(gs_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first, it == 0 ? 1 : 0);
     }
-    hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(PB_FIN), 0, st, pb, -1, 1);
+    hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb, -1, 1);
     for (int b = 0; b < nb; ++b) {
       const gs_picp_backward_seq& u = seqs_host[c0 + b];
       const int64_t n3 = 3 * u.map.n_bound;

@@ -1,8 +1,10 @@
 // gs_picp_color.hip — the projective ICP (gs_picp.hip) with a photometric term (Steinbruecker / Kerl; the hybrid odometry
 // of Kintinuous, ElasticFusion and Open3D): a slot of the live frame's lattice contributes its point-to-plane row and, where
 // the model view has an intensity gradient, a colour row against the rendered colour of the map.  The association, the
-// reject codes, the reduction order, the solve and the update are those of gs_picp.hip (gs_picp_dev.h: ONE definition of
-// each); what this file adds is
+// reject codes, the reduction order, the solve and the update are those of gs_picp.hip: gs_picp_dev.h holds ONE
+// definition of each -- the block prologue (pi_prologue), pi_associate, the chunk reduction (pi_chunk_reduce, PI_PAIRS),
+// the finish body (pi_finish with pi_column_sums) and the host drivers (picp_solve, picp_rows), which this file
+// instantiates with its traits (PiJoint).  What this file adds is
 //
 //   model intensity  one thread per pixel of the model view (a 32 x 8 tile with a one-pixel halo in LDS), batched over B:
 //                    (I, gx, gy, ok) of the rendered colour, once per localisation
@@ -137,49 +139,30 @@ extern "C" int gs_model_intensity_f32(const float* color, const int64_t* index, 
 }
 
 // ------------------------------------------------------------------ the joint linearisation
-// Huber thresholds and weight tables of the robust entries (delta: the point-to-plane residual, metres; cdelta: the
-// colour residual r before color_weight is applied, intensity units; 0 = off; the tables (nslots) may be NULL)
-struct PicRobust {
-  float delta, cdelta;
-  float* weight_out;    // w of a used slot, 0 elsewhere
-  float* cweight_out;   // wc of a slot with a colour row, 0 elsewhere
-};
-
-// The joint linearise kernel's body.  ROBUST: the geometric product of every term carries the Huber weight w of the
-// slot's residual b, the colour product the weight wc of its colour residual r (pi_huber_weight, gs_picp_dev.h); the plain
-// instance is the kernel as it was.
+// The joint linearise kernel's body: prologue, association, the rows z = (a0 .. a5, b) and zc = (ac0 .. ac5, bc), the
+// table outputs, the chunk reduction.  ROBUST: the geometric product of every term carries the Huber weight w of the
+// slot's residual b, the colour product the weight wc of its colour residual r (pi_huber_weight, gs_picp_dev.h).
 template <bool ROBUST>
-GS_DEV void pic_linearize(const PicBatch& pb, const PicRobust& rb) {
+GS_DEV void pic_linearize(const PicBatch& pb, const PiRobust& rb) {
   __shared__ GsCamera cam;
   __shared__ float Ts[12];
-  __shared__ double red[GS_PI_CHUNK / GS_WAVE][LIN_NV];
   __shared__ int cnt[GS_PI_CHUNK / GS_WAVE], ccnt[GS_PI_CHUNK / GS_WAVE];
   const PicSeq& qc = pb.s[blockIdx.x % pb.g.B];
   const PiSeq& q = qc.g;
-  const int chunk = blockIdx.x / pb.g.B;
-  if (threadIdx.x == 0) cam = gs_camera(q.model_pose16, q.K16);
-  if (threadIdx.x >= GS_WAVE && threadIdx.x < GS_WAVE + 12) Ts[threadIdx.x - GS_WAVE] = q.T_in[threadIdx.x - GS_WAVE];
-  __syncthreads();
-  const int lane = threadIdx.x & (GS_WAVE - 1), wave = threadIdx.x / GS_WAVE;
-  const int k = chunk * GS_PI_CHUNK + (int)threadIdx.x;
-  const bool in_lattice = k < pb.g.nslots;
-  const int64_t n_map = gs_count(q.n);
+  const PiSlot t = pi_prologue(q.in, pb.g, q.T_in, cam, Ts);
+  const int64_t n_map = gs_count(q.in.n);
   int code = 1;
   bool colored = false;
   int64_t row = -1;
-  float a[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, b = 0.0f;
-  float ac[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, bc = 0.0f;
+  float z[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, zc[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   float w = 1.0f, wc = 1.0f;
-  if (in_lattice) {
-    const int i = k / pb.g.Wl, j = k - i * pb.g.Wl;
-    const int64_t p = (int64_t)(i * pb.g.stride) * pb.g.W + j * pb.g.stride;
+  if (t.in_lattice) {
     float s[3];
     float4 d, m;
-    code = pi_associate(Ts, cam, q.vertex, q.normal, q.depth, q.index, q.points, q.normals, n_map, p, pb.g.H, pb.g.W,
-                        pb.g.u_hi, pb.g.v_hi, pb.g.dist_th, pb.g.dot_th, row, s, d, m);
+    code = pi_associate(Ts, cam, q.in, pb.g, n_map, t.p, row, s, d, m);
     if (code == 0) {
-      gn_row_pn(s[0], s[1], s[2], d, m, a, b);
-      if (ROBUST) w = pi_huber_weight(pi_huber_clipped(b, rb.delta), b, rb.delta);
+      gn_row_pn(s[0], s[1], s[2], d, m, z, z[6]);
+      if (ROBUST) w = pi_huber_weight(pi_huber_clipped(z[6], rb.delta), z[6], rb.delta);
       // the pixel the association read, again, with the camera-frame point (the same device function on the same
       // operands: the same (h2, w2), inside the view -- the slot would be code 2 otherwise)
       int h2 = 0, w2 = 0;
@@ -190,7 +173,7 @@ GS_DEV void pic_linearize(const PicBatch& pb, const PicRobust& rb) {
       if (colored) {
         float u, v;
         pic_project_uv(cam, cq, u, v);
-        const float Il = pic_luma(qc.color[3 * p], qc.color[3 * p + 1], qc.color[3 * p + 2]);
+        const float Il = pic_luma(qc.color[3 * t.p], qc.color[3 * t.p + 1], qc.color[3 * t.p + 2]);
         const float lin = M.x + M.y * (u - (float)w2);
         const float r = Il - (lin + M.z * (v - (float)h2));
         const float ax = M.y * cam.K[0], ay = M.z * cam.K[5];
@@ -201,77 +184,58 @@ GS_DEV void pic_linearize(const PicBatch& pb, const PicRobust& rb) {
         const float J1 = gs_dot3_plain(cam.Ri[1], cam.Ri[4], cam.Ri[7], j0, j1, j2);
         const float J2 = gs_dot3_plain(cam.Ri[2], cam.Ri[5], cam.Ri[8], j0, j1, j2);
         const float wgt = pb.weight;
-        ac[0] = wgt * J0; ac[1] = wgt * J1; ac[2] = wgt * J2;
-        ac[3] = wgt * (J2 * s[1] - J1 * s[2]);
-        ac[4] = wgt * (J0 * s[2] - J2 * s[0]);
-        ac[5] = wgt * (J1 * s[0] - J0 * s[1]);
-        bc = wgt * r;
+        zc[0] = wgt * J0; zc[1] = wgt * J1; zc[2] = wgt * J2;
+        zc[3] = wgt * (J2 * s[1] - J1 * s[2]);
+        zc[4] = wgt * (J0 * s[2] - J2 * s[0]);
+        zc[5] = wgt * (J1 * s[0] - J0 * s[1]);
+        zc[6] = wgt * r;
         if (ROBUST) wc = pi_huber_weight(pi_huber_clipped(r, rb.cdelta), r, rb.cdelta);
       }
     }
-    if (q.code_out) q.code_out[k] = code;
-    if (q.row_out) q.row_out[k] = row;
-    if (q.a_out) {
-#pragma unroll
-      for (int c = 0; c < 6; ++c) q.a_out[6 * (int64_t)k + c] = a[c];
-    }
-    if (q.b_out) q.b_out[k] = b;
-    if (qc.cflag_out) qc.cflag_out[k] = colored ? 1 : 0;
+    pi_table_out(q, t.k, code, row, z);
+    if (qc.cflag_out) qc.cflag_out[t.k] = colored ? 1 : 0;
     if (qc.ac_out) {
 #pragma unroll
-      for (int c = 0; c < 6; ++c) qc.ac_out[6 * (int64_t)k + c] = ac[c];
+      for (int c = 0; c < 6; ++c) qc.ac_out[6 * (int64_t)t.k + c] = zc[c];
     }
-    if (qc.bc_out) qc.bc_out[k] = bc;
+    if (qc.bc_out) qc.bc_out[t.k] = zc[6];
     if (ROBUST) {
-      if (rb.weight_out) rb.weight_out[k] = code == 0 ? w : 0.0f;
-      if (rb.cweight_out) rb.cweight_out[k] = colored ? wc : 0.0f;
+      if (rb.weight_out) rb.weight_out[t.k] = code == 0 ? w : 0.0f;
+      if (rb.cweight_out) rb.cweight_out[t.k] = colored ? wc : 0.0f;
     }
   }
-  const bool used = code == 0;   // (a, b, ac, bc are zero otherwise: every term below is then +0.0)
+  const bool used = code == 0;   // (z, zc are zero otherwise: every term below is then +0.0)
   const unsigned long long mask = __ballot(used);
   const unsigned long long cmask = __ballot(colored);
-  if (lane == 0) {
-    cnt[wave] = __popcll(mask);
-    ccnt[wave] = __popcll(cmask);
+  if (t.lane == 0) {
+    cnt[t.wave] = __popcll(mask);
+    ccnt[t.wave] = __popcll(cmask);
   }
-  // a wave without a used slot adds up +0.0 only (a colour row needs a used slot): no shuffle needed
-  const bool any = mask != 0ull;
-  int t = 0;
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-#pragma unroll
-    for (int c = r; c < 6; ++c) {
-      const double x = pi_wave_tree(ROBUST ? pi_term(w, a[r], a[c]) + pi_term(wc, ac[r], ac[c])
-                                             : (double)a[r] * (double)a[c] + (double)ac[r] * (double)ac[c], any);
-      if (lane == 0) red[wave][t] = x;
-      ++t;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    const double x = pi_wave_tree(ROBUST ? pi_term(w, a[r], b) + pi_term(wc, ac[r], bc)
-                                           : (double)a[r] * (double)b + (double)ac[r] * (double)bc, any);
-    if (lane == 0) red[wave][21 + r] = x;
-  }
-  {
-    const double x = pi_wave_tree(ROBUST ? pi_term(w, b, b) + pi_term(wc, bc, bc)
-                                           : (double)b * (double)b + (double)bc * (double)bc, any);
-    if (lane == 0) red[wave][27] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < LIN_NV)
-    q.partials[(int64_t)chunk * LIN_NV + threadIdx.x] =
-        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-  if (threadIdx.x == GS_WAVE) q.counts[chunk] = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
-  if (threadIdx.x == GS_WAVE + 1) qc.ccounts[chunk] = (ccnt[0] + ccnt[1]) + (ccnt[2] + ccnt[3]);
+  // (a colour row needs a used slot: a wave without a used slot adds up +0.0 only)
+  double* partial_row = q.partials + (int64_t)t.chunk * LIN_NV;
+  if constexpr (ROBUST)
+    pi_chunk_reduce<LIN_NV>(
+        [&](const int i) {
+          const int x = PI_PAIRS.x[i], y = PI_PAIRS.y[i];
+          return pi_term(w, z[x], z[y]) + pi_term(wc, zc[x], zc[y]);
+        },
+        mask != 0ull, partial_row);
+  else
+    pi_chunk_reduce<LIN_NV>(
+        [&](const int i) {
+          const int x = PI_PAIRS.x[i], y = PI_PAIRS.y[i];
+          return (double)z[x] * (double)z[y] + (double)zc[x] * (double)zc[y];
+        },
+        mask != 0ull, partial_row);
+  if (threadIdx.x == GS_WAVE) q.counts[t.chunk] = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
+  if (threadIdx.x == GS_WAVE + 1) qc.ccounts[t.chunk] = (ccnt[0] + ccnt[1]) + (ccnt[2] + ccnt[3]);
 }
 
 __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_color_linearize_kernel(const PicBatch pb) {
-  pic_linearize<false>(pb, PicRobust{0.0f, 0.0f, nullptr, nullptr});
+  pic_linearize<false>(pb, PiRobust{0.0f, 0.0f, nullptr, nullptr});
 }
 
-__global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_color_linearize_kernel(const PicBatch pb,
-                                                                                     const PicRobust rb) {
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_color_linearize_kernel(const PicBatch pb, const PiRobust rb) {
   pic_linearize<true>(pb, rb);
 }
 
@@ -288,112 +252,49 @@ extern "C" int64_t gs_projective_icp_color_scratch_bytes(int H, int W, int strid
   return (int64_t)(picp_partials_bytes(nchunks) + 2 * picp_counts_bytes(nchunks));
 }
 
-#define PIC_CHECK_SEQ(who, u)                                                                                  \
-  do {                                                                                                         \
-    PICP_CHECK_SEQ(who, (u).base);                                                                             \
-    PICP_REQUIRE(who, (u).color && (u).model_intensity, "NULL pointer (color / model_intensity)");             \
-    PICP_REQUIRE(who, ((uintptr_t)(u).model_intensity & 15) == 0, "model_intensity must be 16-byte aligned");  \
-  } while (0)
-#define PIC_CHECK_WEIGHT(who, w) \
-  PICP_REQUIRE(who, (w) >= 0.0f && (w) < __builtin_inff(), "color_weight must be finite and not negative")
-
-static void pic_fill_seq(PicSeq& s, const gs_picp_color_seq& u, int nchunks) {
-  picp_fill_seq(s.g, u.base, nchunks);
-  s.color = u.color;
-  s.model = reinterpret_cast<const float4*>(u.model_intensity);
-  s.ccounts = reinterpret_cast<int32_t*>(static_cast<char*>(u.base.scratch) + picp_partials_bytes(nchunks) +
-                                         picp_counts_bytes(nchunks));
-  s.cflag_out = nullptr; s.ac_out = nullptr; s.bc_out = nullptr; s.ccount_out = nullptr;
-}
-
-// the solve behind both batch entries; delta / cdelta: the robust entry's thresholds (both 0: the plain kernel)
-static int pic_solve(const char* who, const gs_picp_color_seq* seqs_host, int B, int H, int W,
-                     const gs_picp_params* params_host, float color_weight, float delta, float cdelta, void* stream) {
-  PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
-  PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
-  const gs_picp_params& prm = *params_host;
-  PICP_CHECK_PARAMS(who, prm);
-  PIC_CHECK_WEIGHT(who, color_weight);
-  PICP_CHECK_DELTA(who, delta, "huber_delta");
-  PICP_CHECK_DELTA(who, cdelta, "color_huber_delta");
-  for (int b = 0; b < B; ++b) {
-    PIC_CHECK_SEQ(who, seqs_host[b]);
-    PICP_REQUIRE(who, seqs_host[b].base.out_pose16, "NULL pointer (out_pose16)");
+// the traits of the colour solve for the drivers of gs_picp_dev.h
+struct PiJoint {
+  using Seq = gs_picp_color_seq;
+  using Batch = PicBatch;
+  static constexpr int TRACE = GS_PIC_TRACE;
+  static constexpr auto linearize = gs_picp_color_linearize_kernel;
+  static constexpr auto robust_linearize = gs_robust_picp_color_linearize_kernel;
+  static constexpr auto finish = gs_picp_color_finish_kernel;
+  static const gs_picp_seq& base(const Seq& u) { return u.base; }
+  static PiSeq& seq(Batch& pb, int b) { return pb.s[b].g; }
+  static int check(const char* who, const Seq& u) {
+    PICP_CHECK_SEQ(who, u.base);
+    PICP_REQUIRE(who, u.color && u.model_intensity, "NULL pointer (color / model_intensity)");
+    PICP_REQUIRE(who, ((uintptr_t)u.model_intensity & 15) == 0, "model_intensity must be 16-byte aligned");
+    return GS_OK;
   }
-  hipStream_t st = gs_stream(stream);
-  const PicRobust rb{delta, cdelta, nullptr, nullptr};
-  const bool robust = delta > 0.0f || cdelta > 0.0f;
-  for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
-    const int nb = B - c0 < GS_MAX_BATCH ? B - c0 : GS_MAX_BATCH;
-    PicBatch pb;
-    pb.g.B = nb;
+  static void fill(Batch& pb, int b, const Seq& u, float color_weight) {
+    PicSeq& s = pb.s[b];
+    const int nchunks = pb.g.nchunks;
     pb.weight = color_weight;
-    picp_fill(pb.g, H, W, prm.stride, prm.dist_th, prm.dot_th, prm.damp);
-    for (int b = 0; b < nb; ++b) {
-      pic_fill_seq(pb.s[b], seqs_host[c0 + b], pb.g.nchunks);
-      pb.s[b].g.T_out = seqs_host[c0 + b].base.out_pose16;
-    }
-    const unsigned blocks = (unsigned)nb * (unsigned)pb.g.nchunks;   // < 8 * 2^23
-    for (int it = 0; it < prm.numiters; ++it) {
-      for (int b = 0; b < nb; ++b) {
-        const gs_picp_seq& u = seqs_host[c0 + b].base;
-        pb.s[b].g.T_in = it == 0 ? u.init_pose16 : u.out_pose16;
-        pb.s[b].g.trace_row = u.trace ? u.trace + (int64_t)GS_PIC_TRACE * it : nullptr;
-      }
-      if (robust)
-        hipLaunchKernelGGL(gs_robust_picp_color_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, rb);
-      else
-        hipLaunchKernelGGL(gs_picp_color_linearize_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb);
-      hipLaunchKernelGGL(gs_picp_color_finish_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb);
-    }
-    GS_LAUNCH_CHECK();
+    picp_fill_seq(s.g, u.base, nchunks);
+    s.color = u.color;
+    s.model = reinterpret_cast<const float4*>(u.model_intensity);
+    s.ccounts = reinterpret_cast<int32_t*>(static_cast<char*>(u.base.scratch) + picp_partials_bytes(nchunks) +
+                                           picp_counts_bytes(nchunks));
+    s.cflag_out = nullptr; s.ac_out = nullptr; s.bc_out = nullptr; s.ccount_out = nullptr;
   }
-  return GS_OK;
-}
+  static void color_outputs(Batch& pb, const PiRowsOut& o) {
+    PicSeq& s = pb.s[0];
+    s.ac_out = o.ac6; s.bc_out = o.bc; s.cflag_out = o.colored; s.ccount_out = o.color_count;
+  }
+};
 
 extern "C" int gs_projective_icp_color_batch_f32(const gs_picp_color_seq* seqs_host, int B, int H, int W,
                                                  const gs_picp_params* params_host, float color_weight, void* stream) {
-  return pic_solve(__func__, seqs_host, B, H, W, params_host, color_weight, 0.0f, 0.0f, stream);
+  return picp_solve<PiJoint>(__func__, seqs_host, nullptr, B, H, W, params_host, color_weight, 0.0f, 0.0f, stream);
 }
 
 extern "C" int gs_projective_icp_color_robust_batch_f32(const gs_picp_color_seq* seqs_host, int B, int H, int W,
                                                         const gs_picp_params* params_host, float color_weight,
                                                         float huber_delta, float color_huber_delta, void* stream) {
-  return pic_solve(__func__, seqs_host, B, H, W, params_host, color_weight, huber_delta, color_huber_delta, stream);
-}
-
-// the joint linearisation behind both table-level entries; weight / cweight: the robust entry's outputs, or NULL
-static int pic_rows(const char* who, const gs_picp_color_seq* seq_host, int H, int W, int stride, float dist_th,
-                    float dot_th, float color_weight, float delta, float cdelta, int32_t* code, int64_t* row, float* a6,
-                    float* b, float* ac6, float* bc, int32_t* colored, float* weight, float* cweight, double* sums28,
-                    int64_t* count, int64_t* color_count, void* stream) {
-  PICP_REQUIRE(who, seq_host && H > 0 && W > 0, "bad arguments");
-  PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
-  PICP_REQUIRE(who, stride >= 1, "stride must be at least 1");
-  PICP_REQUIRE(who, !(dist_th != dist_th) && !(dot_th != dot_th), "a threshold is NaN");
-  PIC_CHECK_WEIGHT(who, color_weight);
-  PICP_CHECK_DELTA(who, delta, "huber_delta");
-  PICP_CHECK_DELTA(who, cdelta, "color_huber_delta");
-  PIC_CHECK_SEQ(who, *seq_host);
-  hipStream_t st = gs_stream(stream);
-  PicBatch pb;
-  pb.g.B = 1;
-  pb.weight = color_weight;
-  picp_fill(pb.g, H, W, stride, dist_th, dot_th, 1.0f);
-  pic_fill_seq(pb.s[0], *seq_host, pb.g.nchunks);
-  PicSeq& s = pb.s[0];
-  s.g.code_out = code; s.g.row_out = row; s.g.a_out = a6; s.g.b_out = b;
-  s.ac_out = ac6; s.bc_out = bc; s.cflag_out = colored;
-  s.g.sums_out = sums28; s.g.count_out = count; s.ccount_out = color_count;
-  if (delta > 0.0f || cdelta > 0.0f || weight || cweight)   // (both 0 with a table: 1 for every row there is)
-    hipLaunchKernelGGL(gs_robust_picp_color_linearize_kernel, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb,
-                       PicRobust{delta, cdelta, weight, cweight});
-  else
-    hipLaunchKernelGGL(gs_picp_color_linearize_kernel, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb);
-  if (sums28 || count || color_count)
-    hipLaunchKernelGGL(gs_picp_color_finish_kernel, dim3(1), dim3(GS_PI_FIN), 0, st, pb);
-  GS_LAUNCH_CHECK();
-  return GS_OK;
+  return picp_solve<PiJoint>(__func__, seqs_host, nullptr, B, H, W, params_host, color_weight, huber_delta,
+                             color_huber_delta, stream);
 }
 
 extern "C" int gs_projective_icp_color_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
@@ -401,8 +302,9 @@ extern "C" int gs_projective_icp_color_rows_f32(const gs_picp_color_seq* seq_hos
                                                 int64_t* row, float* a6, float* b, float* ac6, float* bc,
                                                 int32_t* colored, double* sums28, int64_t* count, int64_t* color_count,
                                                 void* stream) {
-  return pic_rows(__func__, seq_host, H, W, stride, dist_th, dot_th, color_weight, 0.0f, 0.0f, code, row, a6, b, ac6, bc,
-                  colored, nullptr, nullptr, sums28, count, color_count, stream);
+  return picp_rows<PiJoint>(__func__, seq_host, H, W, stride, dist_th, dot_th, color_weight,
+                            PiRobust{0.0f, 0.0f, nullptr, nullptr},
+                            PiRowsOut{code, row, a6, b, ac6, bc, colored, sums28, count, color_count}, stream);
 }
 
 extern "C" int gs_projective_icp_color_robust_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
@@ -412,6 +314,7 @@ extern "C" int gs_projective_icp_color_robust_rows_f32(const gs_picp_color_seq* 
                                                        int32_t* colored, float* weight, float* color_weight_out,
                                                        double* sums28, int64_t* count, int64_t* color_count,
                                                        void* stream) {
-  return pic_rows(__func__, seq_host, H, W, stride, dist_th, dot_th, color_weight, huber_delta, color_huber_delta, code,
-                  row, a6, b, ac6, bc, colored, weight, color_weight_out, sums28, count, color_count, stream);
+  return picp_rows<PiJoint>(__func__, seq_host, H, W, stride, dist_th, dot_th, color_weight,
+                            PiRobust{huber_delta, color_huber_delta, weight, color_weight_out},
+                            PiRowsOut{code, row, a6, b, ac6, bc, colored, sums28, count, color_count}, stream);
 }

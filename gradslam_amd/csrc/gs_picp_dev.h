@@ -1,8 +1,11 @@
 // gs_picp_dev.h — what the projective ICP (gs_picp.hip), its colour form (gs_picp_color.hip) and its backward pass
-// (gs_picp_bwd.hip) share: the lattice geometry, the slot's association at a pose (ONE definition: the backward uses the
-// forward's association exactly, at the taped float32 pose), the fixed-shape wave reduction, the Huber weight of the
-// robust entries (ONE definition as well), the layout of the forward tape, and -- for the two forward files -- the descriptors of a launch, the body of the finish kernel and the checks of
-// the entry points.
+// (gs_picp_bwd.hip) share, ONE definition of each: the inputs of a sequence (PiInputs) and the lattice geometry (PiGeom),
+// the block prologue of the per-slot kernels (pi_prologue), the slot's association at a pose (pi_associate: the backward
+// uses the forward's association exactly, at the taped float32 pose), the fixed-shape chunk reduction (pi_chunk_reduce)
+// with the enumeration of the forward's 28 terms (PI_PAIRS), the tiled ascending column sum of the chunk partials
+// (pi_column_sums), the Huber weight of the robust entries, the layout of the forward tape, the checks of the entry
+// points, and -- for the two forward files -- the descriptors of a launch, the body of the finish kernel and the two host
+// drivers (picp_solve, picp_rows) behind the batch and the table-level entries.
 #pragma once
 #include "gs_assoc_dev.h"
 #include "gs_icp_math.h"
@@ -27,14 +30,22 @@ static inline int64_t picp_slots(int H, int W, int stride) {
   return gs_ceil_div(H, stride) * gs_ceil_div(W, stride);
 }
 
-// levels 1..6 of the tree: lane l adds the value of lane l ^ d, d = 1, 2, ..., 32 (every lane ends with the wave's sum)
-GS_DEV double pi_wave_tree(double x, const bool any) {
-  if (any) {
-#pragma unroll
-    for (int d = 1; d < GS_WAVE; d <<= 1) x = x + __shfl_xor(x, d, GS_WAVE);
-  }
-  return x;
-}
+// ------------------------------------------------------------------ inputs of a sequence, geometry of a launch
+struct PiInputs {
+  const float* vertex;
+  const float* normal;
+  const float* depth;
+  const float* K16;
+  const int64_t* index;
+  const float* model_pose16;
+  const float* points;
+  const float* normals;
+  GsCount n;
+};
+struct PiGeom {
+  int B, H, W, stride, Wl, nslots, nchunks;
+  float u_hi, v_hi, dist_th, dot_th, damp;
+};
 
 // ------------------------------------------------------------------ robust (Huber) weights
 // ONE definition for the forward kernels (float) and the backward pass (double): a residual r beyond the threshold is
@@ -48,46 +59,165 @@ GS_DEV T pi_huber_weight(const bool clipped, const T r, const T delta) {
 // a term of the normal equations: the exact product of two float32 factors, weighted (one rounding)
 GS_DEV double pi_term(const float w, const float x, const float y) { return (double)w * ((double)x * (double)y); }
 
+// Huber thresholds and weight tables of the robust forward kernels (delta: the point-to-plane residual, metres; cdelta:
+// the colour residual r before color_weight is applied, intensity units; 0 = off; the tables (nslots) may be NULL).  The
+// plain-geometry kernel ignores the colour half.
+struct PiRobust {
+  float delta, cdelta;
+  float* weight_out;    // w of a used slot, 0 elsewhere
+  float* cweight_out;   // wc of a slot with a colour row, 0 elsewhere
+};
+
+// ------------------------------------------------------------------ the block of a per-slot kernel
+// what a thread of a per-slot kernel (256 threads = one chunk of lattice slots) knows after the prologue
+struct PiSlot {
+  int lane, wave, chunk, k;   // k: the slot
+  bool in_lattice;            // k < nslots
+  int64_t p;                  // the slot's pixel (i stride, j stride), k = i Wl + j; meaningless beyond the lattice
+};
+
+// The prologue of a block of a grid of B * nchunks (the caller takes its sequence, blockIdx.x % B): the chunk from
+// blockIdx, the camera of the model view (thread 0) and the 12 pose floats (lanes 64 .. 75) into the caller's LDS, ONE
+// barrier -- a caller that stages more LDS does so on other lanes before the call -- then the thread's slot.
+GS_DEV PiSlot pi_prologue(const PiInputs& in, const PiGeom& g, const float* __restrict__ pose12, GsCamera& cam,
+                          float* Ts) {
+  if (threadIdx.x == 0) cam = gs_camera(in.model_pose16, in.K16);
+  if (threadIdx.x >= GS_WAVE && threadIdx.x < GS_WAVE + 12) Ts[threadIdx.x - GS_WAVE] = pose12[threadIdx.x - GS_WAVE];
+  __syncthreads();
+  PiSlot t;
+  t.lane = threadIdx.x & (GS_WAVE - 1);
+  t.wave = threadIdx.x / GS_WAVE;
+  t.chunk = blockIdx.x / g.B;
+  t.k = t.chunk * GS_PI_CHUNK + (int)threadIdx.x;
+  t.in_lattice = t.k < g.nslots;
+  const int i = t.k / g.Wl, j = t.k - i * g.Wl;
+  t.p = (int64_t)(i * g.stride) * g.W + j * g.stride;
+  return t;
+}
+
 // The association of lattice pixel p at pose Ts (12 floats): the slot's code (0 used, 1 .. 5 the reject codes of the
 // header), the index image's entry where one was read (else -1), the live vertex under Ts and, for a row that was read
 // (codes 0, 4, 5), the map point d and normal m.  n_map = min(device count, bound): a stale index is never dereferenced.
-GS_DEV int pi_associate(const float* Ts, const GsCamera& cam, const float* __restrict__ vertex,
-                        const float* __restrict__ normal, const float* __restrict__ depth,
-                        const int64_t* __restrict__ index, const float* __restrict__ points,
-                        const float* __restrict__ normals, const int64_t n_map, const int64_t p, const int H, const int W,
-                        const float u_hi, const float v_hi, const float dist_th, const float dot_th, int64_t& row,
-                        float* s, float4& d, float4& m) {
+GS_DEV int pi_associate(const float* Ts, const GsCamera& cam, const PiInputs& in, const PiGeom& geom, const int64_t n_map,
+                        const int64_t p, int64_t& row, float* s, float4& d, float4& m) {
   row = -1;
-  if (!(depth[p] > 0.0f)) return 1;
+  if (!(in.depth[p] > 0.0f)) return 1;
   float g[3];
-  gs_rigid_fma(Ts, vertex[3 * p], vertex[3 * p + 1], vertex[3 * p + 2], s[0], s[1], s[2]);
-  const float n0 = normal[3 * p], n1 = normal[3 * p + 1], n2 = normal[3 * p + 2];
+  gs_rigid_fma(Ts, in.vertex[3 * p], in.vertex[3 * p + 1], in.vertex[3 * p + 2], s[0], s[1], s[2]);
+  const float n0 = in.normal[3 * p], n1 = in.normal[3 * p + 1], n2 = in.normal[3 * p + 2];
   g[0] = gs_dot3_fma(Ts[0], Ts[1], Ts[2], n0, n1, n2);
   g[1] = gs_dot3_fma(Ts[4], Ts[5], Ts[6], n0, n1, n2);
   g[2] = gs_dot3_fma(Ts[8], Ts[9], Ts[10], n0, n1, n2);
   int h2, w2;
-  if (!gs_project_point_hw(cam, s[0], s[1], s[2], H, W, u_hi, v_hi, h2, w2)) return 2;
-  row = index[(int64_t)h2 * W + w2];
+  if (!gs_project_point_hw(cam, s[0], s[1], s[2], geom.H, geom.W, geom.u_hi, geom.v_hi, h2, w2)) return 2;
+  row = in.index[(int64_t)h2 * geom.W + w2];
   if (!(row >= 0 && row < n_map)) return 3;
   // the two tests of gs_is_similar_v, apart: which one fails is the slot's code
-  d = make_float4(points[3 * row], points[3 * row + 1], points[3 * row + 2], 0.0f);
-  m = make_float4(normals[3 * row], normals[3 * row + 1], normals[3 * row + 2], 0.0f);
+  d = make_float4(in.points[3 * row], in.points[3 * row + 1], in.points[3 * row + 2], 0.0f);
+  m = make_float4(in.normals[3 * row], in.normals[3 * row + 1], in.normals[3 * row + 2], 0.0f);
   const float dist = gs_norm3(s[0] - d.x, s[1] - d.y, s[2] - d.z);
   const float dot = gs_dot3_plain(g[0], g[1], g[2], m.x, m.y, m.z);
-  return !(dist < dist_th) ? 4 : (!(dot > dot_th) ? 5 : 0);
+  return !(dist < geom.dist_th) ? 4 : (!(dot > geom.dot_th) ? 5 : 0);
+}
+
+// ------------------------------------------------------------------ the fixed-shape reductions
+// levels 1..6 of the tree: lane l adds the value of lane l ^ d, d = 1, 2, ..., 32 (every lane ends with the wave's sum)
+GS_DEV double pi_wave_tree(double x, const bool any) {
+  if (any) {
+#pragma unroll
+    for (int d = 1; d < GS_WAVE; d <<= 1) x = x + __shfl_xor(x, d, GS_WAVE);
+  }
+  return x;
+}
+
+// The NV sums of a chunk.  term(t) is this thread's float64 value of term t (+0.0 for a slot that contributes nothing):
+// the xor tree in each wave, lane 0 -> LDS, a barrier, (w0 + w1) + (w2 + w3), and thread t stores term t of the chunk's
+// partial row.  any: the wave has a contributing slot (a wave without one adds up +0.0 only: its sums are +0.0, no
+// shuffle needed).  Integer counts that a caller put into LDS before the call may be read after it.
+template <int NV, typename Term>
+GS_DEV void pi_chunk_reduce(const Term& term, const bool any, double* __restrict__ partial_row) {
+  __shared__ double red[GS_PI_CHUNK / GS_WAVE][NV];
+  const int lane = threadIdx.x & (GS_WAVE - 1), wave = threadIdx.x / GS_WAVE;
+#pragma unroll
+  for (int t = 0; t < NV; ++t) {
+    const double x = pi_wave_tree(term(t), any);
+    if (lane == 0) red[wave][t] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < NV)
+    partial_row[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// The 28 terms of the forward as index pairs (x, y) into a slot's row z = (a0 .. a5, b): 21 upper-triangular a_x a_y row
+// by row, 6 a_x b, b b.  The flavours of the forward differ in what they form of z[x] and z[y], not in this order.
+struct PiPairs {
+  int x[LIN_NV], y[LIN_NV];
+};
+constexpr PiPairs pi_pairs() {
+  PiPairs p{};
+  int t = 0;
+  for (int r = 0; r < 6; ++r)
+    for (int c = r; c < 6; ++c, ++t) { p.x[t] = r; p.y[t] = c; }
+  for (int r = 0; r < 6; ++r, ++t) { p.x[t] = r; p.y[t] = 6; }
+  p.x[t] = 6; p.y[t] = 6;
+  return p;
+}
+constexpr PiPairs PI_PAIRS = pi_pairs();
+
+// Column i of a table of chunk partial rows (nchunks, NV), added up in ascending chunk order, for thread i < NV of a
+// block of 256 (the other threads get 0.0).  A serial chain by contract, so what has to be kept off it is the memory
+// latency -- a lane that loaded its partial of chunk c, added it and only then asked for chunk c + 1 would pay a trip to
+// memory per chunk (measured: 0.25 us each, 300 us at 1 200 chunks).  All 256 threads move the table through LDS a tile
+// of 256 chunks at a time (coalesced, NV loads in flight per thread, the next tile on its way while lane i < NV of wave 0
+// adds column i of the current one).  FROM_FIRST: the chain starts from the first partial, not from 0.0 + it (which
+// would turn a -0.0 into +0.0); otherwise it starts from 0.0.  Which of the two a caller takes is part of its bitwise
+// contract.
+constexpr int GS_PI_FIN = 256;    // threads of the block
+constexpr int GS_PI_TILE = 256;   // chunks per LDS tile: GS_PI_TILE * NV doubles (56 KB at 28, 24 KB at 12)
+
+template <int NV, bool FROM_FIRST>
+GS_DEV double pi_column_sums(const double* __restrict__ partials, const int nchunks) {
+  static_assert(GS_PI_TILE * NV % GS_PI_FIN == 0, "a tile is a whole number of loads per thread");
+  constexpr int PER = GS_PI_TILE * NV / GS_PI_FIN;   // NV
+  __shared__ double tile[GS_PI_TILE * NV];
+  const int tid = threadIdx.x;
+  const int64_t total = (int64_t)nchunks * NV;
+  double nxt[PER];
+#pragma unroll
+  for (int r = 0; r < PER; ++r) {
+    const int64_t i = tid + GS_PI_FIN * r;
+    nxt[r] = i < total ? partials[i] : 0.0;
+  }
+  double s = 0.0;
+  for (int base = 0; base < nchunks; base += GS_PI_TILE) {
+    __syncthreads();   // (the tile of the round before has been added up)
+#pragma unroll
+    for (int r = 0; r < PER; ++r) tile[tid + GS_PI_FIN * r] = nxt[r];
+    __syncthreads();
+    if (base + GS_PI_TILE < nchunks) {
+#pragma unroll
+      for (int r = 0; r < PER; ++r) {
+        const int64_t i = (int64_t)(base + GS_PI_TILE) * NV + tid + GS_PI_FIN * r;
+        nxt[r] = i < total ? partials[i] : 0.0;
+      }
+    }
+    if (tid < NV) {
+      const int m = nchunks - base < GS_PI_TILE ? nchunks - base : GS_PI_TILE;
+      int c = 0;
+      if (FROM_FIRST && base == 0) {
+        s = tile[tid];
+        c = 1;
+      }
+#pragma unroll 8
+      for (; c < m; ++c) s = s + tile[c * NV + tid];
+    }
+  }
+  return s;
 }
 
 // ------------------------------------------------------------------ the descriptors of a forward launch
 struct PiSeq {
-  const float* vertex;
-  const float* normal;
-  const float* depth;
-  const float* K16;
-  const int64_t* index;
-  const float* model_pose16;
-  const float* points;
-  const float* normals;
-  GsCount n;
+  PiInputs in;
   const float* T_in;       // pose estimate the launch reads (iteration 0: the caller's initial pose; then T_out)
   float* T_out;            // finish: the updated estimate (NULL: sums only)
   float* trace_row;        // finish: this iteration's trace row, or NULL
@@ -101,39 +231,36 @@ struct PiSeq {
   double* sums_out;        // finish: (28), or NULL
   int64_t* count_out;      // finish: (1), or NULL
 };
-struct PiGeom {
-  int B, H, W, stride, Wl, nslots, nchunks;
-  float u_hi, v_hi, dist_th, dot_th, damp;
-};
 struct PiBatch {
   PiSeq s[GS_MAX_BATCH];
   PiGeom g;
 };
 
+// the geometric table-level outputs of slot k: its code, its row and z = (a0 .. a5, b)
+GS_DEV void pi_table_out(const PiSeq& q, const int k, const int code, const int64_t row, const float* z) {
+  if (q.code_out) q.code_out[k] = code;
+  if (q.row_out) q.row_out[k] = row;
+  if (q.a_out) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) q.a_out[6 * (int64_t)k + c] = z[c];
+  }
+  if (q.b_out) q.b_out[k] = z[6];
+}
+
 // ------------------------------------------------------------------ the finish kernel's body
-// One block per sequence.  S = the chunk partials in ascending chunk order, starting from the first: a serial chain by
-// contract, so what has to be kept off it is the memory latency -- a lane that loaded its partial of chunk c, added it and
-// only then asked for chunk c + 1 would pay a trip to memory per chunk (measured: 0.25 us each, 300 us at 1 200 chunks).
-// All 256 threads move the table through LDS a tile of 256 chunks at a time (coalesced, 28 loads in flight per thread, the
-// next tile on its way while lane i < 28 of wave 0 adds column i of the current one); then wave 0 either hands out the
-// sums as they are (the table-level entry) or takes the Gauss-Newton step.
+// One block per sequence.  S = the chunk partials in ascending chunk order, starting from the first
+// (pi_column_sums<28, true>); then wave 0 either hands out the sums as they are (the table-level entry) or takes the
+// Gauss-Newton step.
 // COLOR: the colour solve's finish also adds up the chunks' colour-row counts (ccounts, an integer sum) and hands the
 // total out as the ninth float of the trace row and through ccount_out.
-constexpr int GS_PI_FIN = 256;    // threads of the finish block
-constexpr int GS_PI_TILE = 256;   // chunks per LDS tile: GS_PI_TILE * 28 doubles = 56 KB
-
 template <bool COLOR>
 GS_DEV void pi_finish(const PiSeq& q, const int nchunks, const float damp, const int32_t* __restrict__ ccounts,
                       int64_t* ccount_out) {
-  static_assert(GS_PI_TILE * LIN_NV % GS_PI_FIN == 0, "a tile is a whole number of loads per thread");
-  constexpr int PER = GS_PI_TILE * LIN_NV / GS_PI_FIN;   // 28
-  __shared__ double tile[GS_PI_TILE * LIN_NV];
   __shared__ double S[LIN_NV];
   __shared__ float xi[8];
   __shared__ int64_t cnt[GS_PI_FIN / GS_WAVE];
   __shared__ int64_t ccnt[COLOR ? GS_PI_FIN / GS_WAVE : 1];
   const int tid = threadIdx.x, lane = tid & (GS_WAVE - 1);
-  const int64_t total = (int64_t)nchunks * LIN_NV;
   int64_t n = 0;
   for (int c = tid; c < nchunks; c += GS_PI_FIN) n += q.counts[c];
 #pragma unroll
@@ -146,36 +273,7 @@ GS_DEV void pi_finish(const PiSeq& q, const int nchunks, const float damp, const
     for (int d = 1; d < GS_WAVE; d <<= 1) nc += __shfl_xor(nc, d, GS_WAVE);
     if (lane == 0) ccnt[tid / GS_WAVE] = nc;
   }
-  double nxt[PER];
-#pragma unroll
-  for (int r = 0; r < PER; ++r) {
-    const int64_t i = tid + GS_PI_FIN * r;
-    nxt[r] = i < total ? q.partials[i] : 0.0;
-  }
-  double s = 0.0;
-  for (int base = 0; base < nchunks; base += GS_PI_TILE) {
-    __syncthreads();   // (the tile of the round before has been added up)
-#pragma unroll
-    for (int r = 0; r < PER; ++r) tile[tid + GS_PI_FIN * r] = nxt[r];
-    __syncthreads();
-    if (base + GS_PI_TILE < nchunks) {
-#pragma unroll
-      for (int r = 0; r < PER; ++r) {
-        const int64_t i = (int64_t)(base + GS_PI_TILE) * LIN_NV + tid + GS_PI_FIN * r;
-        nxt[r] = i < total ? q.partials[i] : 0.0;
-      }
-    }
-    if (tid < LIN_NV) {
-      const int m = nchunks - base < GS_PI_TILE ? nchunks - base : GS_PI_TILE;
-      int c = 0;
-      if (base == 0) {   // the sum starts from the first partial, not from 0.0 + it (which would turn a -0.0 into +0.0)
-        s = tile[tid];
-        c = 1;
-      }
-#pragma unroll 8
-      for (; c < m; ++c) s = s + tile[c * LIN_NV + tid];
-    }
-  }
+  const double s = pi_column_sums<LIN_NV, true>(q.partials, nchunks);
   if (tid < LIN_NV) {
     S[tid] = s;
     if (q.sums_out) q.sums_out[tid] = s;
@@ -244,7 +342,7 @@ static inline size_t picp_counts_bytes(int64_t nchunks) { return gs_align((size_
     PICP_REQUIRE(who, (u).map.n_bound >= 0, "bad map size");                                                            \
     PICP_REQUIRE(who, (u).map.n_bound == 0 || ((u).map.points && (u).map.normals), "NULL pointer (map points / normals)"); \
   } while (0)
-// the parameter checks of a solve (the same for the plain and the colour entry)
+// the parameter checks of a solve (the same for the plain, the colour and the backward entries)
 #define PICP_CHECK_PARAMS(who, prm)                                                                                     \
   do {                                                                                                                  \
     PICP_REQUIRE(who, (prm).stride >= 1, "stride must be at least 1");                                                  \
@@ -252,12 +350,14 @@ static inline size_t picp_counts_bytes(int64_t nchunks) { return gs_align((size_
     PICP_REQUIRE(who, (prm).damp > 0.0f && (prm).damp < __builtin_inff(), "damp must be positive and finite");          \
     PICP_REQUIRE(who, !((prm).dist_th != (prm).dist_th) && !((prm).dot_th != (prm).dot_th), "a threshold is NaN");      \
   } while (0)
-// a Huber threshold of a robust entry (0: off)
+// a Huber threshold of a robust entry (0: off), the weight of the colour term (0 for the plain entries)
 #define PICP_CHECK_DELTA(who, d, name) \
   PICP_REQUIRE(who, (d) >= 0.0f && (d) < __builtin_inff(), name " must be finite and not negative")
+#define PICP_CHECK_WEIGHT(who, w) \
+  PICP_REQUIRE(who, (w) >= 0.0f && (w) < __builtin_inff(), "color_weight must be finite and not negative")
 
-static inline void picp_fill(PiGeom& g, int H, int W, int stride, float dist_th, float dot_th, float damp) {
-  g.H = H; g.W = W; g.stride = stride;
+static inline void picp_fill(PiGeom& g, int B, int H, int W, int stride, float dist_th, float dot_th, float damp) {
+  g.B = B; g.H = H; g.W = W; g.stride = stride;
   g.Wl = (int)gs_ceil_div(W, stride);
   g.nslots = (int)picp_slots(H, W, stride);
   g.nchunks = (int)gs_ceil_div(g.nslots, GS_PI_CHUNK);
@@ -265,14 +365,119 @@ static inline void picp_fill(PiGeom& g, int H, int W, int stride, float dist_th,
   g.dist_th = dist_th; g.dot_th = dot_th; g.damp = damp;
 }
 
+// U: gs_picp_seq or gs_picp_backward_seq (they name the nine common fields alike)
+template <typename U>
+static inline void picp_fill_inputs(PiInputs& in, const U& u) {
+  in.vertex = u.vertex; in.normal = u.normal; in.depth = u.depth; in.K16 = u.K16; in.index = u.index;
+  in.model_pose16 = u.model_pose16;
+  in.points = u.map.points; in.normals = u.map.normals;
+  in.n = GsCount{u.map.n_bound, u.map.n_dev};
+}
+
 static inline void picp_fill_seq(PiSeq& s, const gs_picp_seq& u, int nchunks) {
-  s.vertex = u.vertex; s.normal = u.normal; s.depth = u.depth; s.K16 = u.K16; s.index = u.index;
-  s.model_pose16 = u.model_pose16;
-  s.points = u.map.points; s.normals = u.map.normals;
-  s.n = GsCount{u.map.n_bound, u.map.n_dev};
+  picp_fill_inputs(s.in, u);
   s.partials = static_cast<double*>(u.scratch);
   s.counts = reinterpret_cast<int32_t*>(static_cast<char*>(u.scratch) + picp_partials_bytes(nchunks));
   s.T_in = u.init_pose16; s.T_out = nullptr; s.trace_row = nullptr; s.tape_row = nullptr;
   s.code_out = nullptr; s.row_out = nullptr; s.a_out = nullptr; s.b_out = nullptr;
   s.sums_out = nullptr; s.count_out = nullptr;
+}
+
+// ------------------------------------------------------------------ the host drivers of the forward entries
+// Both drivers are templates over the traits X of a forward file (PiPlain in gs_picp.hip, PiJoint in gs_picp_color.hip):
+//   X::Seq, X::Batch      the caller's descriptor of a sequence and the kernels' argument
+//   X::TRACE              floats per trace row
+//   X::linearize, X::robust_linearize, X::finish     the kernels: (Batch), (Batch, PiRobust), (Batch)
+//   X::base(u), X::seq(pb, b)      the gs_picp_seq inside a Seq, the PiSeq inside a Batch
+//   X::check(who, u)      the checks of a Seq (GS_OK or the error)
+//   X::fill(pb, b, u, color_weight)      sequence b of the batch from u, the scratch carved, every output NULL
+//   X::color_outputs(pb, o)       the colour tables of o into sequence 0
+// The plain entries pass color_weight = cdelta = 0 and no colour tables; the checks of these pass.
+
+// the table-level outputs, any may be NULL (the colour ones are NULL for the plain entries)
+struct PiRowsOut {
+  int32_t* code;
+  int64_t* row;
+  float *a6, *b, *ac6, *bc;
+  int32_t* colored;
+  double* sums28;
+  int64_t *count, *color_count;
+};
+
+// the solve behind the batch entries; tapes_host: per sequence the device buffer of numiters tape rows, or NULL
+// (untaped); delta / cdelta: the Huber thresholds of the robust entries (both 0: the plain kernel)
+template <typename X>
+static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* const* tapes_host, int B, int H, int W,
+                      const gs_picp_params* params_host, float color_weight, float delta, float cdelta, void* stream) {
+  PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
+  PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
+  const gs_picp_params& prm = *params_host;
+  PICP_CHECK_PARAMS(who, prm);
+  PICP_CHECK_WEIGHT(who, color_weight);
+  PICP_CHECK_DELTA(who, delta, "huber_delta");
+  PICP_CHECK_DELTA(who, cdelta, "color_huber_delta");
+  for (int b = 0; b < B; ++b) {
+    if (const int err = X::check(who, seqs_host[b])) return err;
+    PICP_REQUIRE(who, X::base(seqs_host[b]).out_pose16, "NULL pointer (out_pose16)");
+    PICP_REQUIRE(who, !tapes_host || (tapes_host[b] && ((uintptr_t)tapes_host[b] & 7) == 0), "NULL or misaligned tape");
+  }
+  hipStream_t st = gs_stream(stream);
+  const PiRobust rb{delta, cdelta, nullptr, nullptr};
+  const bool robust = delta > 0.0f || cdelta > 0.0f;
+  for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
+    const int nb = B - c0 < GS_MAX_BATCH ? B - c0 : GS_MAX_BATCH;
+    typename X::Batch pb;
+    picp_fill(pb.g, nb, H, W, prm.stride, prm.dist_th, prm.dot_th, prm.damp);
+    for (int b = 0; b < nb; ++b) {
+      X::fill(pb, b, seqs_host[c0 + b], color_weight);
+      X::seq(pb, b).T_out = X::base(seqs_host[c0 + b]).out_pose16;
+    }
+    const unsigned blocks = (unsigned)nb * (unsigned)pb.g.nchunks;   // < 8 * 2^23
+    for (int it = 0; it < prm.numiters; ++it) {
+      for (int b = 0; b < nb; ++b) {
+        const gs_picp_seq& u = X::base(seqs_host[c0 + b]);
+        PiSeq& s = X::seq(pb, b);
+        s.T_in = it == 0 ? u.init_pose16 : u.out_pose16;
+        s.trace_row = u.trace ? u.trace + (int64_t)X::TRACE * it : nullptr;
+        s.tape_row = tapes_host ? static_cast<PiTapeRow*>(tapes_host[c0 + b]) + it : nullptr;
+      }
+      if (robust)
+        hipLaunchKernelGGL(X::robust_linearize, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, rb);
+      else
+        hipLaunchKernelGGL(X::linearize, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb);
+      hipLaunchKernelGGL(X::finish, dim3(nb), dim3(GS_PI_FIN), 0, st, pb);
+    }
+    GS_LAUNCH_CHECK();
+  }
+  return GS_OK;
+}
+
+// the linearisation behind the table-level entries; rb: the thresholds and the weight tables of the robust entries (a
+// table with both thresholds 0: the robust kernel writes 1 for every row there is)
+template <typename X>
+static int picp_rows(const char* who, const typename X::Seq* seq_host, int H, int W, int stride, float dist_th,
+                     float dot_th, float color_weight, const PiRobust& rb, const PiRowsOut& o, void* stream) {
+  PICP_REQUIRE(who, seq_host && H > 0 && W > 0, "bad arguments");
+  PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
+  PICP_REQUIRE(who, stride >= 1, "stride must be at least 1");
+  PICP_REQUIRE(who, !(dist_th != dist_th) && !(dot_th != dot_th), "a threshold is NaN");
+  PICP_CHECK_WEIGHT(who, color_weight);
+  PICP_CHECK_DELTA(who, rb.delta, "huber_delta");
+  PICP_CHECK_DELTA(who, rb.cdelta, "color_huber_delta");
+  if (const int err = X::check(who, *seq_host)) return err;
+  hipStream_t st = gs_stream(stream);
+  typename X::Batch pb;
+  picp_fill(pb.g, 1, H, W, stride, dist_th, dot_th, 1.0f);
+  X::fill(pb, 0, *seq_host, color_weight);
+  PiSeq& s = X::seq(pb, 0);
+  s.code_out = o.code; s.row_out = o.row; s.a_out = o.a6; s.b_out = o.b;
+  s.sums_out = o.sums28; s.count_out = o.count;
+  X::color_outputs(pb, o);
+  if (rb.delta > 0.0f || rb.cdelta > 0.0f || rb.weight_out || rb.cweight_out)
+    hipLaunchKernelGGL(X::robust_linearize, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb, rb);
+  else
+    hipLaunchKernelGGL(X::linearize, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb);
+  if (o.sums28 || o.count || o.color_count) hipLaunchKernelGGL(X::finish, dim3(1), dim3(GS_PI_FIN), 0, st, pb);
+  GS_LAUNCH_CHECK();
+  return GS_OK;
 }

@@ -967,15 +967,25 @@ def _picp_huber(name, delta, who="projective_icp"):
     return float(delta)
 
 
+def _picp_tensors(who, named):
+    """every (name, value) of `named` is a tensor"""
+    for name, t in named:
+        if not torch.is_tensor(t):
+            raise TypeError("{}: expected {} to be of type tensor; got {}".format(who, name, type(t)))
+
+
+def _picp_nslots(H, W, stride):
+    """slots of the [::stride, ::stride] lattice"""
+    return ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
+
+
 def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, color=False):
     """Shape / dtype / device checks shared by the batched solve and the table-level call; fills the descriptors.
     Returns (seqs, tensors kept alive, device, B, H, W).  color: the scratch is sized for the colour solve (the plain
     layout plus the colour-row counts)."""
     tensors = (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                ("model_pose", model_poses), ("init_pose", init_poses))
-    for name, t in tensors:
-        if not torch.is_tensor(t):
-            raise TypeError("{}: expected {} to be of type tensor; got {}".format(who, name, type(t)))
+    _picp_tensors(who, tensors)
     if depth.ndim != 3:
         raise ValueError("{}: expected depth (B, H, W); got {}".format(who, tuple(depth.shape)))
     Bn, H, W = (int(x) for x in depth.shape)
@@ -1066,20 +1076,28 @@ def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, ini
                        dot_th, return_trace, out, None, huber_delta)
 
 
+def _picp_outputs(who, seqs, dev, out, return_trace, width, stride, numiters, damp, dist_th, dot_th):
+    """The outputs of a solve: `out` checked (or the poses allocated), the trace of `width` floats per iteration allocated
+    when asked for, both wired into seqs (the PicpSeq of every sequence), and the PicpParams.  Returns (T, trace, prm)."""
+    Bn = len(seqs)
+    T = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if out is None else out
+    if tuple(T.shape) != (Bn, 4, 4) or T.dtype != f32 or not T.is_contiguous() or T.device != dev:
+        raise ValueError("%s: out must be a contiguous float32 tensor of shape %s on %s" % (who, (Bn, 4, 4), dev))
+    trace = torch.empty((Bn, int(numiters), width), dtype=f32, device=dev) if return_trace else None
+    for b, u in enumerate(seqs):
+        u.out_pose16 = T.data_ptr() + b * 64
+        u.trace = 0 if trace is None else trace.data_ptr() + b * int(numiters) * width * 4
+    return T, trace, _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
+
+
 def _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, numiters, damp, dist_th, dot_th,
                 return_trace, out, tapes, huber_delta=0.0):
     """the solve behind projective_icp_batch and ProjectiveICPFunction.forward; tapes: None, or the uint8 (B, tape bytes)
     buffer the taped entry fills (the same kernels and pose bits); huber_delta > 0: the robust entry"""
     seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp", vertex, normal, depth, K, index, model_poses, maps,
                                            init_poses, stride)
-    T = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if out is None else out
-    if tuple(T.shape) != (Bn, 4, 4) or T.dtype != f32 or not T.is_contiguous() or T.device != dev:
-        raise ValueError("projective_icp: out must be a contiguous float32 tensor of shape %s on %s" % ((Bn, 4, 4), dev))
-    trace = torch.empty((Bn, int(numiters), PICP_TRACE), dtype=f32, device=dev) if return_trace else None
-    for b in range(Bn):
-        seqs[b].out_pose16 = T.data_ptr() + b * 64
-        seqs[b].trace = 0 if trace is None else trace.data_ptr() + b * int(numiters) * PICP_TRACE * 4
-    prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
+    T, trace, prm = _picp_outputs("projective_icp", list(seqs), dev, out, return_trace, PICP_TRACE, stride, numiters,
+                                  damp, dist_th, dot_th)
     ptrs = None if tapes is None else \
         (_C.C.c_void_p * Bn)(*[tapes.data_ptr() + b * tapes.shape[1] for b in range(Bn)])
     if huber_delta > 0:
@@ -1217,10 +1235,8 @@ def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_
     model_pose / init_pose (4, 4), index (H, W) int64; n_dev: device int64[1] holding the actual row count of the map
     (map_points.shape[0] is then an upper bound).  Returns the pose (4, 4) (and the trace (numiters, 8)).
     differentiable, huber_delta: see projective_icp_batch."""
-    for name, t in (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
-                    ("model_pose", model_pose), ("init_pose", init_pose)):
-        if not torch.is_tensor(t):
-            raise TypeError("projective_icp: expected {} to be of type tensor; got {}".format(name, type(t)))
+    _picp_tensors("projective_icp", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
+                                     ("model_pose", model_pose), ("init_pose", init_pose)))
     r = projective_icp_batch(vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0), K.reshape(1, 4, 4),
                              index.unsqueeze(0), model_pose.reshape(1, 4, 4), [(map_points, map_normals, None, n_dev)],
                              init_pose.reshape(1, 4, 4), stride=stride, numiters=numiters, damp=damp,
@@ -1244,15 +1260,13 @@ def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points,
     if not isinstance(return_weights, bool):
         raise TypeError("projective_icp_rows: return_weights must be of type bool; but was of type {}.".format(
             type(return_weights)))
-    for name, t in (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
-                    ("model_pose", model_pose), ("pose", pose)):
-        if not torch.is_tensor(t):
-            raise TypeError("projective_icp_rows: expected {} to be of type tensor; got {}".format(name, type(t)))
+    _picp_tensors("projective_icp_rows", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K),
+                                          ("index", index), ("model_pose", model_pose), ("pose", pose)))
     seqs, held, dev, _, H, W = _picp_seqs("projective_icp_rows", vertex.unsqueeze(0), normal.unsqueeze(0),
                                           depth.unsqueeze(0), K.reshape(1, 4, 4), index.unsqueeze(0),
                                           model_pose.reshape(1, 4, 4), [(map_points, map_normals, None, n_dev)],
                                           pose.reshape(1, 4, 4), stride)
-    ns = ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
+    ns = _picp_nslots(H, W, stride)
     res = ProjectiveRows(torch.empty(ns, dtype=torch.int32, device=dev), torch.empty(ns, dtype=torch.int64, device=dev),
                          torch.empty((ns, 6), dtype=f32, device=dev), torch.empty(ns, dtype=f32, device=dev),
                          torch.empty(28, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.int64, device=dev))
@@ -1299,9 +1313,7 @@ def model_intensity(color, index):
     index (..., H, W) int64 as render_map / render_map_batch return them -> (..., H, W, 4) float32 = (I, gx, gy, ok):
     I = 0.299 R + 0.587 G + 0.114 B, central differences gx, gy, ok = 1 where the pixel and its four neighbours are
     inside the image and hold a surfel (index >= 0), else ok = gx = gy = 0.  Built once per localisation."""
-    for name, t in (("color", color), ("index", index)):
-        if not torch.is_tensor(t):
-            raise TypeError("model_intensity: expected {} to be of type tensor; got {}".format(name, type(t)))
+    _picp_tensors("model_intensity", (("color", color), ("index", index)))
     if color.ndim < 3 or color.shape[-1] != 3 or tuple(index.shape) != tuple(color.shape[:-1]) or color.numel() == 0:
         raise ValueError("model_intensity: expected color (..., H, W, 3) and index (..., H, W); got {} and {}".format(
             tuple(color.shape), tuple(index.shape)))
@@ -1364,15 +1376,8 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
     seqs, held, dev, Bn, H, W = _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride,
                                            color=True)
     cseqs = _picp_color_seqs(who, seqs, held, Bn, H, W, color, model)
-    T = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if out is None else out
-    if tuple(T.shape) != (Bn, 4, 4) or T.dtype != f32 or not T.is_contiguous() or T.device != dev:
-        raise ValueError("projective_icp_color: out must be a contiguous float32 tensor of shape %s on %s"
-                         % ((Bn, 4, 4), dev))
-    trace = torch.empty((Bn, int(numiters), PICP_COLOR_TRACE), dtype=f32, device=dev) if return_trace else None
-    for b in range(Bn):
-        cseqs[b].base.out_pose16 = T.data_ptr() + b * 64
-        cseqs[b].base.trace = 0 if trace is None else trace.data_ptr() + b * int(numiters) * PICP_COLOR_TRACE * 4
-    prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
+    T, trace, prm = _picp_outputs(who, [c.base for c in cseqs], dev, out, return_trace, PICP_COLOR_TRACE, stride,
+                                  numiters, damp, dist_th, dot_th)
     if huber_delta > 0 or color_huber_delta > 0:
         check(lib().gs_projective_icp_color_robust_batch_f32(cseqs, Bn, H, W, prm, weight, huber_delta, color_huber_delta,
                                                              stream(dev)),
@@ -1383,12 +1388,6 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
     return (T, trace) if return_trace else T
 
 
-def _picp_color_single(who, named):
-    for name, t in named:
-        if not torch.is_tensor(t):
-            raise TypeError("{}: expected {} to be of type tensor; got {}".format(who, name, type(t)))
-
-
 def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, color, model,
                          *, color_weight, n_dev=None, stride=1, numiters=10, damp=1e-8, dist_thresh=0.1,
                          angle_thresh=30.0, return_trace=False, differentiable=False, huber_delta=0.0,
@@ -1396,9 +1395,9 @@ def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points
     """projective_icp_color_batch for one sequence without the batch dimension (arguments as projective_icp, then color
     (H, W, 3) and model (H, W, 4)).  Returns the pose (4, 4) (and the trace (numiters, 9)).  huber_delta,
     color_huber_delta: see projective_icp_color_batch."""
-    _picp_color_single("projective_icp_color", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K),
-                                                ("index", index), ("model_pose", model_pose), ("init_pose", init_pose),
-                                                ("color", color), ("model_intensity", model)))
+    _picp_tensors("projective_icp_color", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K),
+                                           ("index", index), ("model_pose", model_pose), ("init_pose", init_pose),
+                                           ("color", color), ("model_intensity", model)))
     r = projective_icp_color_batch(vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0), K.reshape(1, 4, 4),
                                    index.unsqueeze(0), model_pose.reshape(1, 4, 4),
                                    [(map_points, map_normals, None, n_dev)], init_pose.reshape(1, 4, 4),
@@ -1427,14 +1426,14 @@ def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_p
             type(return_weights)))
     dist_th, dot_th = _picp_args(stride, 1, 1.0, dist_thresh, angle_thresh)
     who = "projective_icp_color_rows"
-    _picp_color_single(who, (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
-                             ("model_pose", model_pose), ("pose", pose), ("color", color), ("model_intensity", model)))
+    _picp_tensors(who, (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
+                        ("model_pose", model_pose), ("pose", pose), ("color", color), ("model_intensity", model)))
     seqs, held, dev, _, H, W = _picp_seqs(who, vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0),
                                           K.reshape(1, 4, 4), index.unsqueeze(0), model_pose.reshape(1, 4, 4),
                                           [(map_points, map_normals, None, n_dev)], pose.reshape(1, 4, 4), stride,
                                           color=True)
     cseqs = _picp_color_seqs(who, seqs, held, 1, H, W, color.unsqueeze(0), model.unsqueeze(0))
-    ns = ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
+    ns = _picp_nslots(H, W, stride)
     e = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)   # noqa: E731
     res = ProjectiveColorRows(e(ns, torch.int32), e(ns, torch.int64), e((ns, 6), f32), e(ns, f32), e((ns, 6), f32),
                               e(ns, f32), e(ns, torch.int32), e(28, torch.float64), e(1, torch.int64), e(1, torch.int64))

@@ -36,6 +36,7 @@ CASES = {
     "edge_s1": ("edge1", 1, 6, 0.1),        # device count below the bound; stride 1: 1 961 slots, 7 chunks and a tail
     "stale_dc": ("stale", 2, 5, 0.1),       # the index image of a longer map: 400 stale rows behind a device-side count
     "radius1": ("radius1", 1, 5, 0.1),      # index image rendered with radius 1: one surfel behind up to nine pixels
+    "conv_t2": ("conv257", 1, 2, 0.1),      # 257 x 257: 66 049 slots, 259 chunks = two tiles of the scalar stage's column sum
 }
 NO_INLIER = ("no_winner", "no_depth")    # numiters 3, stride 1: the adjoint passes through
 KW = dict(damp=1e-8, dist_thresh=0.1, angle_thresh=30.0)
@@ -48,6 +49,8 @@ class Case:
 def _fixture(which):
     if which == "conv":
         fx = dict(pr.convergence_fixture())
+    elif which == "conv257":
+        fx = dict(pr.convergence_fixture(257, 257))
     elif which in ("edge3", "edge1"):
         from tests.test_hip_picp import edge_fixture
         fx = dict(edge_fixture(37, 53, 3 if which == "edge3" else 1))
@@ -189,6 +192,7 @@ GAP = {   # case: (vertex_bar, points_bar, normals_bar, init_pose_bar)
     'edge_s1': (7.2e-06, 7.2e-06, 3.9e-05, 6.1e-07),
     'stale_dc': (1.3e-04, 1.3e-04, 5.2e-04, 2.3e-06),
     'radius1': (5.3e-05, 2.5e-05, 4.2e-05, 3.9e-07),
+    'conv_t2': (1.9e-05, 1.3e-05, 1.5e-04, 5.3e-06),
 }
 # GAPS-END
 

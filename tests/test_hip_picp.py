@@ -110,10 +110,12 @@ def same_solve(got, want, what=""):
 
 
 # ------------------------------------------------------------------------------------------ rows
-@pytest.mark.parametrize("h,w,stride", [(60, 80, 1), (60, 80, 4), (37, 53, 3), (37, 53, 1)])
+@pytest.mark.parametrize("h,w,stride", [(60, 80, 1), (60, 80, 4), (37, 53, 3), (37, 53, 1), (257, 257, 1),
+                                        (363, 362, 1)])
 def test_rows_bit_for_bit(ops, h, w, stride):
     """37 x 53 stride 3: a 13 x 18 lattice, 234 slots, one partial chunk; stride 1: 1 961 slots, 7 chunks and a tail of
-    169"""
+    169; 257 x 257: 66 049 slots, 259 chunks, i.e. two tiles of the finish kernel's column sum, the second of 3 chunks,
+    and a last chunk of one slot; 363 x 362: 131 406 slots, 514 chunks, three tiles (the prefetch is taken twice)"""
     fx = edge_fixture(h, w, stride)
     want = pr.rows(*pr.args_of(fx), fx["T"], stride=stride)
     assert set(np.unique(want.code)) == {0, 1, 2, 3, 4, 5}, np.bincount(want.code)
@@ -133,21 +135,23 @@ def test_rows_bit_for_bit(ops, h, w, stride):
 
 
 # ------------------------------------------------------------------------------------------ solve
-@pytest.mark.parametrize("stride", [1, 4])
-def test_solve_bit_for_bit_on_the_convergence_fixture(ops, stride):
-    fx = pr.convergence_fixture()
-    want = pr.solve(*pr.args_of(fx), fx["T0"], stride=stride, numiters=10)
+@pytest.mark.parametrize("size,stride,numiters", [((60, 80), 1, 10), ((60, 80), 4, 10), ((257, 257), 1, 2)],
+                         ids=["1", "4", "257x257-1"])
+def test_solve_bit_for_bit_on_the_convergence_fixture(ops, size, stride, numiters):
+    """257 x 257: 259 chunks, two tiles of the finish kernel's column sum, in a solve"""
+    fx = pr.convergence_fixture(*size)
+    want = pr.solve(*pr.args_of(fx), fx["T0"], stride=stride, numiters=numiters)
     t = [dev(fx[k]) for k in pr.ARGS[:-1]]
-    got = ops.projective_icp(*t, dev(fx["T0"]), stride=stride, numiters=10, return_trace=True)
+    got = ops.projective_icp(*t, dev(fx["T0"]), stride=stride, numiters=numiters, return_trace=True)
     same_solve(got, want, "stride %d" % stride)
-    again = ops.projective_icp(*t, dev(fx["T0"]), stride=stride, numiters=10, return_trace=True)
+    again = ops.projective_icp(*t, dev(fx["T0"]), stride=stride, numiters=numiters, return_trace=True)
     assert np.array_equal(bits(host(got[0])), bits(host(again[0]))) and np.array_equal(bits(host(got[1])),
                                                                                         bits(host(again[1])))
     # against the ground truth: the bound the CPU test establishes for the restatement
     err = np.linalg.norm(host(got[0])[:3, 3].astype(np.float64) - fx["gt"][:3, 3])
     print("stride %d: HIP translation error %.3g m" % (stride, err))
     assert err <= 1e-3
-    plain = ops.projective_icp(*t, dev(fx["T0"]), stride=stride, numiters=10)
+    plain = ops.projective_icp(*t, dev(fx["T0"]), stride=stride, numiters=numiters)
     assert np.array_equal(bits(host(plain)), bits(host(got[0])))
 
 

@@ -98,8 +98,9 @@ def test_model_intensity_bit_for_bit(ops, h, w):
 
 
 # ------------------------------------------------------------------------------------------ rows
-@pytest.mark.parametrize("h,w,stride", [(60, 80, 1), (60, 80, 4), (37, 53, 3), (37, 53, 1)])
+@pytest.mark.parametrize("h,w,stride", [(60, 80, 1), (60, 80, 4), (37, 53, 3), (37, 53, 1), (257, 257, 1)])
 def test_rows_bit_for_bit(ops, h, w, stride):
+    """257 x 257: 259 chunks, two tiles of the finish kernel's column sum"""
     fx = color_edge_fixture(h, w, stride)
     want = pc.rows(*pc.args_of(fx), fx["T"], WEIGHT, stride=stride)
     assert set(np.unique(want.code)) == {0, 1, 2, 3, 4, 5}, np.bincount(want.code)
@@ -124,18 +125,21 @@ def test_rows_bit_for_bit(ops, h, w, stride):
 
 
 # ------------------------------------------------------------------------------------------ solve
-@pytest.mark.parametrize("scene", ["plane", "wave"])
-@pytest.mark.parametrize("stride", [1, 4])
-def test_solve_bit_for_bit(ops, scene, stride):
-    fx = pc.textured_fixture(scene=scene)
-    want = pc.solve(*pc.args_of(fx), fx["T0"], WEIGHT, stride=stride, numiters=10)
-    got = solve_hip(ops, fx, stride=stride, numiters=10)
+@pytest.mark.parametrize("scene,size,stride,numiters",
+                         [("plane", (60, 80), 1, 10), ("wave", (60, 80), 1, 10), ("plane", (60, 80), 4, 10),
+                          ("wave", (60, 80), 4, 10), ("wave", (257, 257), 1, 2)],
+                         ids=["1-plane", "1-wave", "4-plane", "4-wave", "257x257-1-wave"])
+def test_solve_bit_for_bit(ops, scene, size, stride, numiters):
+    """257 x 257: 259 chunks, two tiles of the finish kernel's column sum, in a solve"""
+    fx = pc.textured_fixture(*size, scene=scene)
+    want = pc.solve(*pc.args_of(fx), fx["T0"], WEIGHT, stride=stride, numiters=numiters)
+    got = solve_hip(ops, fx, stride=stride, numiters=numiters)
     same_solve(got, want, "%s stride %d" % (scene, stride))
-    again = solve_hip(ops, fx, stride=stride, numiters=10)          # two calls give identical bits
+    again = solve_hip(ops, fx, stride=stride, numiters=numiters)    # two calls give identical bits
     assert np.array_equal(bits(host(got[0])), bits(host(again[0]))) and np.array_equal(bits(host(got[1])),
                                                                                         bits(host(again[1])))
     t, c, _ = hip_args(fx)
-    no_trace = ops.projective_icp_color(*t, dev(fx["T0"]), *c, color_weight=WEIGHT, stride=stride, numiters=10)
+    no_trace = ops.projective_icp_color(*t, dev(fx["T0"]), *c, color_weight=WEIGHT, stride=stride, numiters=numiters)
     assert np.array_equal(bits(host(no_trace)), bits(host(got[0])))
 
 

@@ -74,7 +74,7 @@ def same_solve(got, want, what=""):
     assert np.array_equal(bits(trace), bits(rtrace)), (what, trace, rtrace)
 
 
-SIZES = [(37, 53, 1), (37, 53, 3), (60, 80, 1), (60, 80, 4)]
+SIZES = [(37, 53, 1), (37, 53, 3), (60, 80, 1), (60, 80, 4), (257, 257, 1)]   # (257 x 257: 259 chunks, two finish tiles)
 
 
 # ------------------------------------------------------------------------------------------ 1. forward
