@@ -31,6 +31,10 @@
 // linearise body: w = |b| > delta ? delta / |b| : 1 in float32 (pi_huber_weight), every term (double)w * ((double)x *
 // (double)y); the finish kernel, the reduction and the counts are the plain ones, S[27] is the weighted sum of squares.
 // With delta = 0 they launch the plain kernel.
+// The scaled entries (gs_projective_icp_scaled_batch_f32 / _rows_f32, huber_k > 0) put the two launches of
+// gs_picp_scale.hip in front of the robust linearisation: the kernel then reads its sequence's threshold of this iteration,
+// max(huber_k * 1.4826 * lower median |b|, huber_floor), from a device float (PiSeq::delta_dev; NULL: the constant above),
+// and the finish kernel tapes it in PiTapeRow::pad[0].
 // What this file holds: the body of the linearise kernel with its two term expressions, the traits of the plain solve and
 // the entries.  The block prologue (pi_prologue), the association (pi_associate), the chunk reduction (pi_chunk_reduce,
 // PI_PAIRS), the column sum of the partials (pi_column_sums), the finish body (pi_finish) and the host drivers
@@ -51,6 +55,7 @@ GS_DEV void pi_linearize(const PiBatch& pb, const PiRobust& rb) {
   int code = 1;
   int64_t row = -1;
   float z[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, w = 1.0f;
+  const float delta = ROBUST ? pi_huber_delta(q.delta_dev, rb) : 0.0f;
   if (t.in_lattice) {
     float s[3];
     float4 d, m;
@@ -58,7 +63,7 @@ GS_DEV void pi_linearize(const PiBatch& pb, const PiRobust& rb) {
     if (code == 0) gn_row_pn(s[0], s[1], s[2], d, m, z, z[6]);
     pi_table_out(q, t.k, code, row, z);
     if (ROBUST) {
-      if (code == 0) w = pi_huber_weight(pi_huber_clipped(z[6], rb.delta), z[6], rb.delta);
+      if (code == 0) w = pi_huber_weight(pi_huber_clipped(z[6], delta), z[6], delta);
       if (rb.weight_out) rb.weight_out[t.k] = code == 0 ? w : 0.0f;
     }
   }
@@ -93,6 +98,11 @@ extern "C" int64_t gs_projective_icp_scratch_bytes(int H, int W, int stride) {
   return (int64_t)(picp_partials_bytes(nchunks) + picp_counts_bytes(nchunks));
 }
 
+extern "C" int64_t gs_projective_icp_scaled_scratch_bytes(int H, int W, int stride) {
+  const int64_t base = gs_projective_icp_scratch_bytes(H, W, stride);
+  return base > 0 ? (int64_t)picp_scaled_bytes((size_t)base, picp_slots(H, W, stride)) : 0;
+}
+
 extern "C" int64_t gs_projective_icp_tape_bytes(int numiters) {
   return numiters >= 1 ? (int64_t)numiters * (int64_t)sizeof(PiTapeRow) : 0;
 }
@@ -112,31 +122,32 @@ struct PiPlain {
     return GS_OK;
   }
   static void fill(Batch& pb, int b, const Seq& u, float) { picp_fill_seq(pb.s[b], u, pb.g.nchunks); }
+  static size_t scratch_bytes(int64_t nchunks) { return picp_partials_bytes(nchunks) + picp_counts_bytes(nchunks); }
   static void color_outputs(Batch&, const PiRowsOut&) {}
 };
 
 extern "C" int gs_projective_icp_batch_f32(const gs_picp_seq* seqs_host, int B, int H, int W,
                                            const gs_picp_params* params_host, void* stream) {
-  return picp_solve<PiPlain>(__func__, seqs_host, nullptr, B, H, W, params_host, 0.0f, 0.0f, 0.0f, stream);
+  return picp_solve<PiPlain>(__func__, seqs_host, nullptr, B, H, W, params_host, 0.0f, 0.0f, 0.0f, nullptr, stream);
 }
 
 extern "C" int gs_projective_icp_tape_batch_f32(const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H, int W,
                                                 const gs_picp_params* params_host, void* stream) {
   GS_REQUIRE(tapes_host, "NULL pointer (tapes)");
-  return picp_solve<PiPlain>(__func__, seqs_host, tapes_host, B, H, W, params_host, 0.0f, 0.0f, 0.0f, stream);
+  return picp_solve<PiPlain>(__func__, seqs_host, tapes_host, B, H, W, params_host, 0.0f, 0.0f, 0.0f, nullptr, stream);
 }
 
 extern "C" int gs_projective_icp_robust_batch_f32(const gs_picp_seq* seqs_host, void* const* tapes_host, int B, int H,
                                                   int W, const gs_picp_params* params_host, float huber_delta,
                                                   void* stream) {
-  return picp_solve<PiPlain>(__func__, seqs_host, tapes_host, B, H, W, params_host, 0.0f, huber_delta, 0.0f, stream);
+  return picp_solve<PiPlain>(__func__, seqs_host, tapes_host, B, H, W, params_host, 0.0f, huber_delta, 0.0f, nullptr, stream);
 }
 
 extern "C" int gs_projective_icp_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
                                           float dot_th, int32_t* code, int64_t* row, float* a6, float* b,
                                           double* sums28, int64_t* count, void* stream) {
   return picp_rows<PiPlain>(__func__, seq_host, H, W, stride, dist_th, dot_th, 0.0f, PiRobust{0.0f, 0.0f, nullptr, nullptr},
-                            PiRowsOut{code, row, a6, b, nullptr, nullptr, nullptr, sums28, count, nullptr}, stream);
+                            PiRowsOut{code, row, a6, b, nullptr, nullptr, nullptr, sums28, count, nullptr}, nullptr, stream);
 }
 
 extern "C" int gs_projective_icp_robust_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
@@ -144,5 +155,27 @@ extern "C" int gs_projective_icp_robust_rows_f32(const gs_picp_seq* seq_host, in
                                                  float* b, float* weight, double* sums28, int64_t* count, void* stream) {
   return picp_rows<PiPlain>(__func__, seq_host, H, W, stride, dist_th, dot_th, 0.0f,
                             PiRobust{huber_delta, 0.0f, weight, nullptr},
-                            PiRowsOut{code, row, a6, b, nullptr, nullptr, nullptr, sums28, count, nullptr}, stream);
+                            PiRowsOut{code, row, a6, b, nullptr, nullptr, nullptr, sums28, count, nullptr}, nullptr, stream);
+}
+
+// The scaled entries: the Huber threshold of every sequence and iteration from the lower median of |b| over its used
+// slots (gs_picp_scale.hip: two launches in front of the robust linearisation), delta = max(c * median, huber_floor).
+extern "C" int gs_projective_icp_scaled_batch_f32(const gs_picp_seq* seqs_host, void* const* tapes_host,
+                                                  float* const* deltas_host, int B, int H, int W,
+                                                  const gs_picp_params* params_host, float huber_k, float huber_floor,
+                                                  void* stream) {
+  PICP_CHECK_SCALE(__func__, huber_k, huber_floor);
+  const PiScale sc{picp_scale_c(huber_k), huber_floor, deltas_host, nullptr};
+  return picp_solve<PiPlain>(__func__, seqs_host, tapes_host, B, H, W, params_host, 0.0f, 0.0f, 0.0f, &sc, stream);
+}
+
+extern "C" int gs_projective_icp_scaled_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
+                                                 float dot_th, float huber_k, float huber_floor, int32_t* code,
+                                                 int64_t* row, float* a6, float* b, float* weight, double* sums28,
+                                                 int64_t* count, float* delta_out, void* stream) {
+  PICP_CHECK_SCALE(__func__, huber_k, huber_floor);
+  const PiScale sc{picp_scale_c(huber_k), huber_floor, nullptr, delta_out};
+  return picp_rows<PiPlain>(__func__, seq_host, H, W, stride, dist_th, dot_th, 0.0f,
+                            PiRobust{0.0f, 0.0f, weight, nullptr},
+                            PiRowsOut{code, row, a6, b, nullptr, nullptr, nullptr, sums28, count, nullptr}, &sc, stream);
 }

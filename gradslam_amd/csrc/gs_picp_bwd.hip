@@ -35,6 +35,8 @@
 // touched.
 // gs_projective_icp_robust_backward_batch_f32 (a tape of the forward with Huber weights, the same huber_delta) launches
 // the ROBUST instance of the point stage (see pb_point); everything else, the scalar stage included, is shared.
+// gs_projective_icp_scaled_backward_batch_f32 (a tape of the forward with the threshold from the residuals' median) launches
+// the same instance, which then reads every iteration's threshold from its tape row.
 // From gs_picp_dev.h, ONE definition with the forward: the inputs and the geometry of a launch (PiInputs, PiGeom), the
 // point stage's block prologue (pi_prologue), pi_associate, the chunk reduction (pi_chunk_reduce, here with 12 terms) and
 // the scalar stage's column sum of the chunk partials (pi_column_sums, here starting from 0.0).
@@ -150,8 +152,11 @@ __global__ void __launch_bounds__(GS_PI_FIN) gs_picp_bwd_scalar_kernel(const PbB
 // association and recomputed as the forward computed it (pi_huber_clipped on the float32 b of gn_row_pn at the taped
 // pose).  With w' = dw/db (-w / b clipped, 0 otherwise): ab = w ((b - c) u - e xi), and the residual's adjoint
 // bb = e (w + w' (b - c)) takes the place of e in sb, points_bar and normals_bar.
+// taped (the scaled backward): the threshold is not the launch's but the one the forward derived for this iteration and
+// taped (PiTapeRow::pad[0], the median rule of gs_picp_scale.hip), a constant of the pass like the clip flags.
 template <bool ROBUST>
-GS_DEV void pb_point(const PbBatch& pb, const int it, const int first, const int last, const float delta) {
+GS_DEV void pb_point(const PbBatch& pb, const int it, const int first, const int last, const float delta_launch,
+                     const bool taped) {
   __shared__ GsCamera cam;
   __shared__ float Ts[12];
   __shared__ double ux[12];   // u(6), xi(6)
@@ -164,6 +169,7 @@ GS_DEV void pb_point(const PbBatch& pb, const int it, const int first, const int
     ux[i] = i < 6 ? q.state->u[i] : q.state->xi[i - 6];
   }
   const PiSlot t = pi_prologue(q.in, pb.g, q.tape[it].T, cam, Ts);
+  const float delta = (ROBUST && taped) ? q.tape[it].pad[0] : delta_launch;
   const int64_t p = t.p;
   const int k = t.k;
   bool used = false;
@@ -240,13 +246,13 @@ GS_DEV void pb_point(const PbBatch& pb, const int it, const int first, const int
 
 __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_bwd_point_kernel(const PbBatch pb, const int it, const int first,
                                                                         const int last) {
-  pb_point<false>(pb, it, first, last, 0.0f);
+  pb_point<false>(pb, it, first, last, 0.0f, false);
 }
 
 __global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_bwd_point_kernel(const PbBatch pb, const int it,
                                                                                const int first, const int last,
-                                                                               const float delta) {
-  pb_point<true>(pb, it, first, last, delta);
+                                                                               const float delta, const int taped) {
+  pb_point<true>(pb, it, first, last, delta, taped != 0);
 }
 
 __global__ void __launch_bounds__(256) gs_picp_bwd_cast_kernel(const double* __restrict__ in, int64_t n,
@@ -266,9 +272,10 @@ extern "C" int64_t gs_projective_icp_backward_scratch_bytes(int H, int W, int st
                    2 * pb_rows_bytes(n_map));
 }
 
-// the pass behind both entries; delta: the Huber threshold the forward ran with (0: the plain point kernel)
+// the pass behind the entries; delta: the Huber threshold the forward ran with (0: the plain point kernel); taped: the
+// robust point kernel with every iteration's threshold from the tape (delta is then not read)
 static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, int B, int H, int W,
-                       const gs_picp_params* params_host, float delta, void* stream) {
+                       const gs_picp_params* params_host, float delta, bool taped, void* stream) {
   PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
   PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   const gs_picp_params& prm = *params_host;
@@ -314,9 +321,9 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
     for (int it = prm.numiters - 1; it >= 0; --it) {
       const int first = it == prm.numiters - 1;
       hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb, it, first ? 0 : 1);
-      if (delta > 0.0f)
+      if (delta > 0.0f || taped)
         hipLaunchKernelGGL(gs_robust_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first,
-                           it == 0 ? 1 : 0, delta);
+                           it == 0 ? 1 : 0, delta, taped ? 1 : 0);
       else
         hipLaunchKernelGGL(gs_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first, it == 0 ? 1 : 0);
     }
@@ -338,11 +345,16 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
 
 extern "C" int gs_projective_icp_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
                                                     const gs_picp_params* params_host, void* stream) {
-  return pb_backward(__func__, seqs_host, B, H, W, params_host, 0.0f, stream);
+  return pb_backward(__func__, seqs_host, B, H, W, params_host, 0.0f, false, stream);
 }
 
 extern "C" int gs_projective_icp_robust_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
                                                            const gs_picp_params* params_host, float huber_delta,
                                                            void* stream) {
-  return pb_backward(__func__, seqs_host, B, H, W, params_host, huber_delta, stream);
+  return pb_backward(__func__, seqs_host, B, H, W, params_host, huber_delta, false, stream);
+}
+
+extern "C" int gs_projective_icp_scaled_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
+                                                           const gs_picp_params* params_host, void* stream) {
+  return pb_backward(__func__, seqs_host, B, H, W, params_host, 0.0f, true, stream);
 }

@@ -156,13 +156,14 @@ GS_DEV void pic_linearize(const PicBatch& pb, const PiRobust& rb) {
   int64_t row = -1;
   float z[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, zc[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   float w = 1.0f, wc = 1.0f;
+  const float delta = ROBUST ? pi_huber_delta(q.delta_dev, rb) : 0.0f;
   if (t.in_lattice) {
     float s[3];
     float4 d, m;
     code = pi_associate(Ts, cam, q.in, pb.g, n_map, t.p, row, s, d, m);
     if (code == 0) {
       gn_row_pn(s[0], s[1], s[2], d, m, z, z[6]);
-      if (ROBUST) w = pi_huber_weight(pi_huber_clipped(z[6], rb.delta), z[6], rb.delta);
+      if (ROBUST) w = pi_huber_weight(pi_huber_clipped(z[6], delta), z[6], delta);
       // the pixel the association read, again, with the camera-frame point (the same device function on the same
       // operands: the same (h2, w2), inside the view -- the slot would be code 2 otherwise)
       int h2 = 0, w2 = 0;
@@ -252,6 +253,11 @@ extern "C" int64_t gs_projective_icp_color_scratch_bytes(int H, int W, int strid
   return (int64_t)(picp_partials_bytes(nchunks) + 2 * picp_counts_bytes(nchunks));
 }
 
+extern "C" int64_t gs_projective_icp_color_scaled_scratch_bytes(int H, int W, int stride) {
+  const int64_t base = gs_projective_icp_color_scratch_bytes(H, W, stride);
+  return base > 0 ? (int64_t)picp_scaled_bytes((size_t)base, picp_slots(H, W, stride)) : 0;
+}
+
 // the traits of the colour solve for the drivers of gs_picp_dev.h
 struct PiJoint {
   using Seq = gs_picp_color_seq;
@@ -279,6 +285,7 @@ struct PiJoint {
                                            picp_counts_bytes(nchunks));
     s.cflag_out = nullptr; s.ac_out = nullptr; s.bc_out = nullptr; s.ccount_out = nullptr;
   }
+  static size_t scratch_bytes(int64_t nchunks) { return picp_partials_bytes(nchunks) + 2 * picp_counts_bytes(nchunks); }
   static void color_outputs(Batch& pb, const PiRowsOut& o) {
     PicSeq& s = pb.s[0];
     s.ac_out = o.ac6; s.bc_out = o.bc; s.cflag_out = o.colored; s.ccount_out = o.color_count;
@@ -287,14 +294,26 @@ struct PiJoint {
 
 extern "C" int gs_projective_icp_color_batch_f32(const gs_picp_color_seq* seqs_host, int B, int H, int W,
                                                  const gs_picp_params* params_host, float color_weight, void* stream) {
-  return picp_solve<PiJoint>(__func__, seqs_host, nullptr, B, H, W, params_host, color_weight, 0.0f, 0.0f, stream);
+  return picp_solve<PiJoint>(__func__, seqs_host, nullptr, B, H, W, params_host, color_weight, 0.0f, 0.0f, nullptr, stream);
 }
 
 extern "C" int gs_projective_icp_color_robust_batch_f32(const gs_picp_color_seq* seqs_host, int B, int H, int W,
                                                         const gs_picp_params* params_host, float color_weight,
                                                         float huber_delta, float color_huber_delta, void* stream) {
   return picp_solve<PiJoint>(__func__, seqs_host, nullptr, B, H, W, params_host, color_weight, huber_delta,
-                             color_huber_delta, stream);
+                             color_huber_delta, nullptr, stream);
+}
+
+// the joint solve with the geometric threshold from the median of |b| (gs_picp_scale.hip); the colour threshold stays
+// the caller's constant
+extern "C" int gs_projective_icp_color_scaled_batch_f32(const gs_picp_color_seq* seqs_host, float* const* deltas_host,
+                                                        int B, int H, int W, const gs_picp_params* params_host,
+                                                        float color_weight, float huber_k, float huber_floor,
+                                                        float color_huber_delta, void* stream) {
+  PICP_CHECK_SCALE(__func__, huber_k, huber_floor);
+  const PiScale sc{picp_scale_c(huber_k), huber_floor, deltas_host, nullptr};
+  return picp_solve<PiJoint>(__func__, seqs_host, nullptr, B, H, W, params_host, color_weight, 0.0f, color_huber_delta,
+                             &sc, stream);
 }
 
 extern "C" int gs_projective_icp_color_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
@@ -304,7 +323,7 @@ extern "C" int gs_projective_icp_color_rows_f32(const gs_picp_color_seq* seq_hos
                                                 void* stream) {
   return picp_rows<PiJoint>(__func__, seq_host, H, W, stride, dist_th, dot_th, color_weight,
                             PiRobust{0.0f, 0.0f, nullptr, nullptr},
-                            PiRowsOut{code, row, a6, b, ac6, bc, colored, sums28, count, color_count}, stream);
+                            PiRowsOut{code, row, a6, b, ac6, bc, colored, sums28, count, color_count}, nullptr, stream);
 }
 
 extern "C" int gs_projective_icp_color_robust_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
@@ -316,5 +335,5 @@ extern "C" int gs_projective_icp_color_robust_rows_f32(const gs_picp_color_seq* 
                                                        void* stream) {
   return picp_rows<PiJoint>(__func__, seq_host, H, W, stride, dist_th, dot_th, color_weight,
                             PiRobust{huber_delta, color_huber_delta, weight, color_weight_out},
-                            PiRowsOut{code, row, a6, b, ac6, bc, colored, sums28, count, color_count}, stream);
+                            PiRowsOut{code, row, a6, b, ac6, bc, colored, sums28, count, color_count}, nullptr, stream);
 }

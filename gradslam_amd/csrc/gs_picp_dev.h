@@ -5,7 +5,9 @@
 // with the enumeration of the forward's 28 terms (PI_PAIRS), the tiled ascending column sum of the chunk partials
 // (pi_column_sums), the Huber weight of the robust entries, the layout of the forward tape, the checks of the entry
 // points, and -- for the two forward files -- the descriptors of a launch, the body of the finish kernel and the two host
-// drivers (picp_solve, picp_rows) behind the batch and the table-level entries.
+// drivers (picp_solve, picp_rows) behind the batch and the table-level entries.  The scaled entries (the Huber threshold
+// from the residuals' median) add the descriptors and the launcher of gs_picp_scale.hip's two kernels, which the drivers
+// enqueue in front of the robust linearisation.
 #pragma once
 #include "gs_assoc_dev.h"
 #include "gs_icp_math.h"
@@ -67,6 +69,11 @@ struct PiRobust {
   float* weight_out;    // w of a used slot, 0 elsewhere
   float* cweight_out;   // wc of a slot with a colour row, 0 elsewhere
 };
+// the geometric threshold of a sequence in a robust kernel: its own device float where it has one (the median rule of
+// gs_picp_scale.hip, written by the select kernel in front of this launch), else the launch's constant
+GS_DEV float pi_huber_delta(const float* __restrict__ delta_dev, const PiRobust& rb) {
+  return delta_dev ? *delta_dev : rb.delta;
+}
 
 // ------------------------------------------------------------------ the block of a per-slot kernel
 // what a thread of a per-slot kernel (256 threads = one chunk of lattice slots) knows after the prologue
@@ -219,6 +226,7 @@ GS_DEV double pi_column_sums(const double* __restrict__ partials, const int nchu
 struct PiSeq {
   PiInputs in;
   const float* T_in;       // pose estimate the launch reads (iteration 0: the caller's initial pose; then T_out)
+  const float* delta_dev;  // the sequence's Huber threshold of this iteration (gs_picp_scale.hip), or NULL: PiRobust::delta
   float* T_out;            // finish: the updated estimate (NULL: sums only)
   float* trace_row;        // finish: this iteration's trace row, or NULL
   PiTapeRow* tape_row;     // finish: this iteration's tape row, or NULL
@@ -246,6 +254,48 @@ GS_DEV void pi_table_out(const PiSeq& q, const int k, const int code, const int6
   }
   if (q.b_out) q.b_out[k] = z[6];
 }
+
+// ------------------------------------------------------------------ the median rule (gs_picp_scale.hip)
+// What the two launches in front of a robust linearisation need of a sequence: they find the lower median of |b| over
+// the used slots at T_in and leave delta = max(c * median, floor) in *delta_dev (and in *delta_out when not NULL).
+struct PiScaleSeq {
+  PiInputs in;
+  const float* T_in;
+  uint32_t* keys;      // (nslots): bits(|b|) of a used slot, 0xFFFFFFFF elsewhere
+  uint32_t* hist;      // (GS_PS_BINS): used slots per value of the keys' top 11 bits; zero between the iterations (the
+                       // residual pass adds to it, the select block reads it and clears it; a call clears it first)
+  float* delta_dev;
+  float* delta_out;    // this iteration's entry of the caller's threshold table, or NULL
+};
+struct PiScaleBatch {
+  PiScaleSeq s[GS_MAX_BATCH];
+  PiGeom g;
+};
+// the caller's side of the rule: c = (float)huber_k * 1.4826f, the floor, and per sequence the device table of numiters
+// thresholds (deltas_host, or NULL; the rows entry: delta_out, one float)
+struct PiScale {
+  float c, floor;
+  float* const* deltas_host;
+  float* delta_out;
+};
+// the residual pass and the select, enqueued back to back (defined in gs_picp_scale.hip); first: the call's first use of
+// the descriptors: one more launch in front clears every sequence's counters (after it the select block leaves them
+// cleared)
+void picp_scale_launch(const PiScaleBatch& sb, float c, float floor, bool first, hipStream_t st);
+
+constexpr int GS_PS_BINS = 2048;   // values of an 11-bit digit of a key
+static inline size_t picp_keys_bytes(int64_t nslots) { return gs_align((size_t)nslots * sizeof(uint32_t)); }
+static inline size_t picp_hist_bytes() { return gs_align(GS_PS_BINS * sizeof(uint32_t)); }
+// scratch of the rule behind a solve's own scratch of `base` bytes: keys (nslots) | hist (2048) | delta (one float)
+static inline size_t picp_scaled_bytes(size_t base, int64_t nslots) {
+  return base + picp_keys_bytes(nslots) + picp_hist_bytes() + gs_align(sizeof(float));
+}
+static inline float picp_scale_c(float huber_k) { return huber_k * 1.4826f; }
+#define PICP_CHECK_SCALE(who, k, fl)                                                                    \
+  do {                                                                                                  \
+    PICP_REQUIRE(who, (k) > 0.0f && (k) < __builtin_inff(), "huber_k must be finite and positive");     \
+    PICP_REQUIRE(who, (fl) >= 0.0f && (fl) < __builtin_inff(), "huber_floor must be finite and not negative"); \
+  } while (0)
 
 // ------------------------------------------------------------------ the finish kernel's body
 // One block per sequence.  S = the chunk partials in ascending chunk order, starting from the first
@@ -316,7 +366,8 @@ GS_DEV void pi_finish(const PiSeq& q, const int nchunks, const float damp, const
       for (int i = 0; i < LIN_NV; ++i) tr.S[i] = S[i];
 #pragma unroll
       for (int i = 0; i < 6; ++i) tr.xi[i] = xi[i];
-      tr.pad[0] = 0.0f; tr.pad[1] = 0.0f;
+      tr.pad[0] = q.delta_dev ? *q.delta_dev : 0.0f;   // (the threshold of the median rule; 0 for every other entry)
+      tr.pad[1] = 0.0f;
       tr.count = n;
     }
   }
@@ -378,7 +429,7 @@ static inline void picp_fill_seq(PiSeq& s, const gs_picp_seq& u, int nchunks) {
   picp_fill_inputs(s.in, u);
   s.partials = static_cast<double*>(u.scratch);
   s.counts = reinterpret_cast<int32_t*>(static_cast<char*>(u.scratch) + picp_partials_bytes(nchunks));
-  s.T_in = u.init_pose16; s.T_out = nullptr; s.trace_row = nullptr; s.tape_row = nullptr;
+  s.T_in = u.init_pose16; s.delta_dev = nullptr; s.T_out = nullptr; s.trace_row = nullptr; s.tape_row = nullptr;
   s.code_out = nullptr; s.row_out = nullptr; s.a_out = nullptr; s.b_out = nullptr;
   s.sums_out = nullptr; s.count_out = nullptr;
 }
@@ -392,6 +443,7 @@ static inline void picp_fill_seq(PiSeq& s, const gs_picp_seq& u, int nchunks) {
 //   X::check(who, u)      the checks of a Seq (GS_OK or the error)
 //   X::fill(pb, b, u, color_weight)      sequence b of the batch from u, the scratch carved, every output NULL
 //   X::color_outputs(pb, o)       the colour tables of o into sequence 0
+//   X::scratch_bytes(nchunks)     bytes of a sequence's scratch (the median rule's keys and threshold lie behind them)
 // The plain entries pass color_weight = cdelta = 0 and no colour tables; the checks of these pass.
 
 // the table-level outputs, any may be NULL (the colour ones are NULL for the plain entries)
@@ -404,11 +456,28 @@ struct PiRowsOut {
   int64_t *count, *color_count;
 };
 
+// a sequence's descriptor of the median rule: the inputs of s, the scratch behind the solve's own (16-byte aligned, which
+// the scaled entries check: the select block reads the keys four at a time); s then reads its threshold from the rule's
+// device float
+template <typename X>
+static void picp_fill_scale(PiScaleSeq& z, PiSeq& s, const gs_picp_seq& u, const PiGeom& g) {
+  char* p = static_cast<char*>(u.scratch) + X::scratch_bytes(g.nchunks);
+  z.in = s.in;
+  z.T_in = s.T_in;
+  z.keys = reinterpret_cast<uint32_t*>(p);
+  z.hist = reinterpret_cast<uint32_t*>(p + picp_keys_bytes(g.nslots));
+  z.delta_dev = reinterpret_cast<float*>(p + picp_keys_bytes(g.nslots) + picp_hist_bytes());
+  z.delta_out = nullptr;
+  s.delta_dev = z.delta_dev;
+}
+
 // the solve behind the batch entries; tapes_host: per sequence the device buffer of numiters tape rows, or NULL
-// (untaped); delta / cdelta: the Huber thresholds of the robust entries (both 0: the plain kernel)
+// (untaped); delta / cdelta: the Huber thresholds of the robust entries (both 0: the plain kernel); sc: the median rule
+// of the scaled entries (delta is then not read: every sequence has its device threshold), or NULL
 template <typename X>
 static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* const* tapes_host, int B, int H, int W,
-                      const gs_picp_params* params_host, float color_weight, float delta, float cdelta, void* stream) {
+                      const gs_picp_params* params_host, float color_weight, float delta, float cdelta,
+                      const PiScale* sc, void* stream) {
   PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
   PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   const gs_picp_params& prm = *params_host;
@@ -419,18 +488,23 @@ static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* c
   for (int b = 0; b < B; ++b) {
     if (const int err = X::check(who, seqs_host[b])) return err;
     PICP_REQUIRE(who, X::base(seqs_host[b]).out_pose16, "NULL pointer (out_pose16)");
+    PICP_REQUIRE(who, !sc || !sc->deltas_host || sc->deltas_host[b], "NULL pointer (deltas)");
+    PICP_REQUIRE(who, !sc || ((uintptr_t)X::base(seqs_host[b]).scratch & 15) == 0, "scratch must be 16-byte aligned");
     PICP_REQUIRE(who, !tapes_host || (tapes_host[b] && ((uintptr_t)tapes_host[b] & 7) == 0), "NULL or misaligned tape");
   }
   hipStream_t st = gs_stream(stream);
   const PiRobust rb{delta, cdelta, nullptr, nullptr};
-  const bool robust = delta > 0.0f || cdelta > 0.0f;
+  const bool robust = delta > 0.0f || cdelta > 0.0f || sc;
   for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
     const int nb = B - c0 < GS_MAX_BATCH ? B - c0 : GS_MAX_BATCH;
     typename X::Batch pb;
+    PiScaleBatch sb;
     picp_fill(pb.g, nb, H, W, prm.stride, prm.dist_th, prm.dot_th, prm.damp);
+    sb.g = pb.g;
     for (int b = 0; b < nb; ++b) {
       X::fill(pb, b, seqs_host[c0 + b], color_weight);
       X::seq(pb, b).T_out = X::base(seqs_host[c0 + b]).out_pose16;
+      if (sc) picp_fill_scale<X>(sb.s[b], X::seq(pb, b), X::base(seqs_host[c0 + b]), pb.g);
     }
     const unsigned blocks = (unsigned)nb * (unsigned)pb.g.nchunks;   // < 8 * 2^23
     for (int it = 0; it < prm.numiters; ++it) {
@@ -440,7 +514,12 @@ static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* c
         s.T_in = it == 0 ? u.init_pose16 : u.out_pose16;
         s.trace_row = u.trace ? u.trace + (int64_t)X::TRACE * it : nullptr;
         s.tape_row = tapes_host ? static_cast<PiTapeRow*>(tapes_host[c0 + b]) + it : nullptr;
+        if (sc) {
+          sb.s[b].T_in = s.T_in;
+          sb.s[b].delta_out = sc->deltas_host ? sc->deltas_host[c0 + b] + it : nullptr;
+        }
       }
+      if (sc) picp_scale_launch(sb, sc->c, sc->floor, it == 0, st);
       if (robust)
         hipLaunchKernelGGL(X::robust_linearize, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, rb);
       else
@@ -453,10 +532,11 @@ static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* c
 }
 
 // the linearisation behind the table-level entries; rb: the thresholds and the weight tables of the robust entries (a
-// table with both thresholds 0: the robust kernel writes 1 for every row there is)
+// table with both thresholds 0: the robust kernel writes 1 for every row there is); sc: the median rule, or NULL
 template <typename X>
 static int picp_rows(const char* who, const typename X::Seq* seq_host, int H, int W, int stride, float dist_th,
-                     float dot_th, float color_weight, const PiRobust& rb, const PiRowsOut& o, void* stream) {
+                     float dot_th, float color_weight, const PiRobust& rb, const PiRowsOut& o, const PiScale* sc,
+                     void* stream) {
   PICP_REQUIRE(who, seq_host && H > 0 && W > 0, "bad arguments");
   PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   PICP_REQUIRE(who, stride >= 1, "stride must be at least 1");
@@ -465,6 +545,7 @@ static int picp_rows(const char* who, const typename X::Seq* seq_host, int H, in
   PICP_CHECK_DELTA(who, rb.delta, "huber_delta");
   PICP_CHECK_DELTA(who, rb.cdelta, "color_huber_delta");
   if (const int err = X::check(who, *seq_host)) return err;
+  PICP_REQUIRE(who, !sc || ((uintptr_t)X::base(*seq_host).scratch & 15) == 0, "scratch must be 16-byte aligned");
   hipStream_t st = gs_stream(stream);
   typename X::Batch pb;
   picp_fill(pb.g, 1, H, W, stride, dist_th, dot_th, 1.0f);
@@ -473,7 +554,14 @@ static int picp_rows(const char* who, const typename X::Seq* seq_host, int H, in
   s.code_out = o.code; s.row_out = o.row; s.a_out = o.a6; s.b_out = o.b;
   s.sums_out = o.sums28; s.count_out = o.count;
   X::color_outputs(pb, o);
-  if (rb.delta > 0.0f || rb.cdelta > 0.0f || rb.weight_out || rb.cweight_out)
+  if (sc) {   // the threshold at init_pose16 first: two launches in front of the robust linearisation
+    PiScaleBatch sb;
+    sb.g = pb.g;
+    picp_fill_scale<X>(sb.s[0], s, X::base(*seq_host), pb.g);
+    sb.s[0].delta_out = sc->delta_out;
+    picp_scale_launch(sb, sc->c, sc->floor, true, st);
+  }
+  if (sc || rb.delta > 0.0f || rb.cdelta > 0.0f || rb.weight_out || rb.cweight_out)
     hipLaunchKernelGGL(X::robust_linearize, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb, rb);
   else
     hipLaunchKernelGGL(X::linearize, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb);

@@ -6,7 +6,8 @@ search.  The result is detached unless `differentiable` is set: the poses are th
 (ops.ProjectiveICPFunction, a HIP backward through the Gauss-Newton iterations).  With `color_weight` > 0 the solve
 is the joint geometric + photometric one (gs_projective_icp_color_batch_f32): the view's colour image is rendered too and
 the live frame's colour is compared with it.  `huber_delta` / `color_huber_delta` > 0 switch on Huber weights
-(the *_robust_* entry points): rows with a large residual are down-weighted instead of pulling the pose at full weight."""
+(the *_robust_* entry points): rows with a large residual are down-weighted instead of pulling the pose at full weight.
+`huber_k` > 0 estimates the geometric threshold from the residuals in every iteration (the *_scaled_* entry points)."""
 from typing import Optional, Union
 
 import torch
@@ -45,6 +46,11 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             `differentiable=True`.
         color_huber_delta: Huber threshold of the colour residual in the intensity units of the map's colours (0: off);
             needs `color_weight` > 0.
+        huber_k: the geometric Huber threshold from the residuals themselves (0, the default: off): in every iteration
+            delta = max(huber_k * 1.4826 * median|b|, huber_delta) over the used pairs, so `huber_delta` becomes a floor
+            and no threshold has to be tuned per dataset; 1.345 is the usual constant.  Works with `differentiable=True`
+            (the thresholds are constants of the backward pass) and with `color_weight` (the colour threshold stays the
+            constant `color_huber_delta`).
 
     Unlike the point-cloud-pair providers it needs the map and the live frame themselves: call
     `localize(pointclouds, live_frame, prev_poses)`."""
@@ -53,7 +59,7 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                  angle_thresh: Union[float, int] = 30, stride: Optional[int] = None,
                  min_confidence: Union[float, int] = 0.0, radius: int = 0, differentiable: bool = False,
                  color_weight: Union[float, int] = 0.0, huber_delta: Union[float, int] = 0.0,
-                 color_huber_delta: Union[float, int] = 0.0):
+                 color_huber_delta: Union[float, int] = 0.0, huber_k: Union[float, int] = 0.0):
         from .. import ops
         if not isinstance(differentiable, bool):
             raise TypeError("differentiable must be of type bool; but was of type {}.".format(type(differentiable)))
@@ -66,6 +72,8 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
         ops._picp_huber("color_huber_delta", color_huber_delta, "ProjectiveICPOdometryProvider")
         if color_huber_delta > 0 and not color_weight > 0:
             raise ValueError("color_huber_delta > 0 needs color_weight > 0: it is the Huber threshold of the colour term")
+        ops._picp_huber_k(huber_k, "ProjectiveICPOdometryProvider")
+        self.huber_k = huber_k
         self.color_weight = color_weight   # (carried next to _kwargs(): the plain solve does not take it)
         self.huber_delta = huber_delta     # (as are the Huber thresholds)
         self.color_huber_delta = color_huber_delta
@@ -130,7 +138,7 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                        "update on the autograd tape)")
             T = ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
                                          view.index[:, 0], poses.detach(), maps, poses, differentiable=True, guard=guard,
-                                         huber_delta=self.huber_delta, **self._kwargs())
+                                         huber_delta=self.huber_delta, huber_k=self.huber_k, **self._kwargs())
             return T.unsqueeze(1)
         out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=poses.device)
         if self.color_weight > 0:
@@ -146,11 +154,11 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                            view.index[:, 0], poses, maps, poses, fr.rgb_image[:, 0], model,
                                            color_weight=self.color_weight, out=out.view(B, 4, 4),
                                            huber_delta=self.huber_delta, color_huber_delta=self.color_huber_delta,
-                                           **self._kwargs())
+                                           huber_k=self.huber_k, **self._kwargs())
             return out
         view = ops.render_map_batch([(m[0], None) + m[2:] for m in maps], poses.view(B, 1, 4, 4), K, H, W,
                                     radius=self.radius, min_confidence=self.min_confidence)
         ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
                                  view.index[:, 0], poses, maps, poses, out=out.view(B, 4, 4),
-                                 huber_delta=self.huber_delta, **self._kwargs())
+                                 huber_delta=self.huber_delta, huber_k=self.huber_k, **self._kwargs())
         return out

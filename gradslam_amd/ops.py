@@ -967,6 +967,29 @@ def _picp_huber(name, delta, who="projective_icp"):
     return float(delta)
 
 
+def _picp_huber_k(huber_k, who="projective_icp"):
+    """the value check of the median rule's constant (delta = huber_k * 1.4826 * median|b| per iteration): a finite
+    number >= 0, 0 = off (huber_delta is then the constant threshold it always was)"""
+    import math
+    if isinstance(huber_k, bool) or not isinstance(huber_k, (float, int)):
+        raise TypeError("{}: huber_k must be of type float or int; but was of type {}.".format(who, type(huber_k)))
+    if not (math.isfinite(huber_k) and huber_k >= 0):
+        raise ValueError("{}: huber_k ({}) must be finite and not negative.".format(who, huber_k))
+    return float(huber_k)
+
+
+def _picp_flag(who, name, val):
+    if not isinstance(val, bool):
+        raise TypeError("{}: {} must be of type bool; but was of type {}.".format(who, name, type(val)))
+    return val
+
+
+def _picp_scale_table(Bn, numiters, dev):
+    """the (B, numiters) table of thresholds of a scaled solve and its per-sequence device pointers"""
+    scale = torch.empty((Bn, int(numiters)), dtype=f32, device=dev)
+    return scale, (_C.C.c_void_p * Bn)(*[scale.data_ptr() + b * int(numiters) * 4 for b in range(Bn)])
+
+
 def _picp_tensors(who, named):
     """every (name, value) of `named` is a tensor"""
     for name, t in named:
@@ -979,10 +1002,10 @@ def _picp_nslots(H, W, stride):
     return ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
 
 
-def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, color=False):
+def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, color=False, scaled=False):
     """Shape / dtype / device checks shared by the batched solve and the table-level call; fills the descriptors.
     Returns (seqs, tensors kept alive, device, B, H, W).  color: the scratch is sized for the colour solve (the plain
-    layout plus the colour-row counts)."""
+    layout plus the colour-row counts); scaled: ... plus the key table and the threshold of the median rule."""
     tensors = (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                ("model_pose", model_poses), ("init_pose", init_poses))
     _picp_tensors(who, tensors)
@@ -1017,7 +1040,10 @@ def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_pos
     held = [vertex, normal, depth, K, index, model_poses, init_poses]
     ws = Workspace.get(dev)
     L = lib()
-    nbytes = (L.gs_projective_icp_color_scratch_bytes if color else L.gs_projective_icp_scratch_bytes)(H, W, int(stride))
+    sizer = {(False, False): L.gs_projective_icp_scratch_bytes, (True, False): L.gs_projective_icp_color_scratch_bytes,
+             (False, True): L.gs_projective_icp_scaled_scratch_bytes,
+             (True, True): L.gs_projective_icp_color_scaled_scratch_bytes}[(bool(color), bool(scaled))]
+    nbytes = sizer(H, W, int(stride))
     seqs = (_C.PicpSeq * Bn)()
     P3, P1 = H * W * 12, H * W * 4
     for b in range(Bn):
@@ -1041,7 +1067,7 @@ def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_pos
 
 def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, init_poses, *, stride=1, numiters=10,
                          damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False, out=None,
-                         differentiable=False, guard=None, huber_delta=0.0):
+                         differentiable=False, guard=None, huber_delta=0.0, huber_k=0.0, return_scale=False):
     """Frame-to-model tracking by projective data association for B sequences (gs_projective_icp_batch_f32: two launches
     per iteration for 8 sequences, nothing read back).  vertex / normal (B, H, W, 3): LOCAL maps of the live frames,
     depth (B, H, W), K (B, 4, 4); index (B, H, W) int64: the index image of render_map_batch at model_poses (B, 4, 4);
@@ -1057,23 +1083,41 @@ def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, ini
     huber_delta (metres, 0 = off): Huber weights (gs_projective_icp_robust_batch_f32): a used slot whose point-to-plane
     residual b exceeds it enters the normal equations with the weight huber_delta / |b|; the trace's second column is
     then the weighted sum of squares.  It works with differentiable=True (the weight is differentiated, which slots are
-    clipped is a constant)."""
+    clipped is a constant).
+    huber_k (0 = off; 1.345 is the usual constant): the threshold is estimated from the residuals, per sequence and per
+    iteration: delta = max(huber_k * 1.4826 * median|b|, huber_delta) with the lower median of |b| over the used slots at
+    the pose the iteration linearises at (gs_projective_icp_scaled_batch_f32: two more launches per iteration, nothing
+    read back, bit-exact); huber_delta is then a floor.  An iteration whose median is 0 has the plain solve's bits.  It
+    works with differentiable=True (the thresholds are constants of the backward pass, like the clip flags).
+    return_scale=True: the thresholds (B, numiters) float32 come last in the returned tuple (huber_k = 0: huber_delta in
+    every entry)."""
     if not isinstance(differentiable, bool):
         raise TypeError("projective_icp: differentiable must be of type bool; but was of type {}.".format(
             type(differentiable)))
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
     huber_delta = _picp_huber("huber_delta", huber_delta)
+    huber_k = _picp_huber_k(huber_k)
+    _picp_flag("projective_icp", "return_scale", return_scale)
     if differentiable:
         if out is not None:
             raise ValueError("projective_icp: out= cannot be combined with differentiable=True (autograd owns the "
                              "outputs)")
         cfg = dict(stride=stride, numiters=numiters, damp=damp, dist_thresh=dist_thresh, angle_thresh=angle_thresh,
-                   guard=guard, counts=[(m[-2], m[-1]) for m in maps], huber_delta=huber_delta)
+                   guard=guard, counts=[(m[-2], m[-1]) for m in maps], huber_delta=huber_delta, huber_k=huber_k)
         flat = [t for m in maps for t in m[:2]]
-        T, trace = ProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses, cfg, *flat)
-        return (T, trace) if return_trace else T
+        res = ProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses, cfg, *flat)
+        scale = None
+        if return_scale:
+            scale = res[2] if huber_k > 0 else torch.full_like(res[1][..., 0], huber_delta)
+        return _picp_pack(res[0], res[1], scale, return_trace, return_scale)
     return _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, numiters, damp, dist_th,
-                       dot_th, return_trace, out, None, huber_delta)
+                       dot_th, return_trace, out, None, huber_delta, huber_k, return_scale)
+
+
+def _picp_pack(T, trace, scale, return_trace, return_scale):
+    """what a solve returns: the poses, then the trace and the thresholds where asked for"""
+    res = (T,) + ((trace,) if return_trace else ()) + ((scale,) if return_scale else ())
+    return res if len(res) > 1 else T
 
 
 def _picp_outputs(who, seqs, dev, out, return_trace, width, stride, numiters, damp, dist_th, dot_th):
@@ -1091,16 +1135,23 @@ def _picp_outputs(who, seqs, dev, out, return_trace, width, stride, numiters, da
 
 
 def _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, numiters, damp, dist_th, dot_th,
-                return_trace, out, tapes, huber_delta=0.0):
+                return_trace, out, tapes, huber_delta=0.0, huber_k=0.0, return_scale=False):
     """the solve behind projective_icp_batch and ProjectiveICPFunction.forward; tapes: None, or the uint8 (B, tape bytes)
-    buffer the taped entry fills (the same kernels and pose bits); huber_delta > 0: the robust entry"""
+    buffer the taped entry fills (the same kernels and pose bits); huber_delta > 0: the robust entry; huber_k > 0: the
+    scaled entry (huber_delta its floor)"""
     seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp", vertex, normal, depth, K, index, model_poses, maps,
-                                           init_poses, stride)
+                                           init_poses, stride, scaled=huber_k > 0)
     T, trace, prm = _picp_outputs("projective_icp", list(seqs), dev, out, return_trace, PICP_TRACE, stride, numiters,
                                   damp, dist_th, dot_th)
     ptrs = None if tapes is None else \
         (_C.C.c_void_p * Bn)(*[tapes.data_ptr() + b * tapes.shape[1] for b in range(Bn)])
-    if huber_delta > 0:
+    scale = None
+    if huber_k > 0:
+        scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale else (None, None)
+        check(lib().gs_projective_icp_scaled_batch_f32(seqs, ptrs, dptrs, Bn, H, W, prm, huber_k, huber_delta,
+                                                       stream(dev)),
+              "gs_projective_icp_scaled_batch_f32")
+    elif huber_delta > 0:
         check(lib().gs_projective_icp_robust_batch_f32(seqs, ptrs, Bn, H, W, prm, huber_delta, stream(dev)),
               "gs_projective_icp_robust_batch_f32")
     elif tapes is not None:
@@ -1108,7 +1159,9 @@ def _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, 
               "gs_projective_icp_tape_batch_f32")
     else:
         check(lib().gs_projective_icp_batch_f32(seqs, Bn, H, W, prm, stream(dev)), "gs_projective_icp_batch_f32")
-    return (T, trace) if return_trace else T
+    if return_scale and scale is None:
+        scale = torch.full((Bn, int(numiters)), huber_delta, dtype=f32, device=dev)
+    return _picp_pack(T, trace, scale, return_trace, return_scale)
 
 
 def projective_icp_tape_bytes(numiters):
@@ -1118,16 +1171,19 @@ def projective_icp_tape_bytes(numiters):
 
 def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, maps, tapes, pose_bar, *, stride=1,
                                   numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, want_vertex=True,
-                                  want_init=True, want_maps=None, huber_delta=0.0):
+                                  want_init=True, want_maps=None, huber_delta=0.0, huber_k=0.0):
     """Reverse mode of projective_icp_batch (gs_projective_icp_backward_batch_f32), arguments as the forward's; tapes:
     the (B, projective_icp_tape_bytes(numiters)) uint8 buffer the taped forward filled; pose_bar (B, 4, 4): the adjoint of
     the poses.  want_maps: per sequence (points, normals) flags, default all True.  Returns (vertex_bar (B, H, W, 3) or
     None, per sequence (points_bar, normals_bar) of the buffers' shapes (None where not wanted), init_pose_bar (B, 4, 4)
     or None).  vertex_bar and init_pose_bar are bitwise reproducible, the map gradients up to the order of float64
     additions.  An output that is not wanted costs nothing: without map outputs nothing of map size is allocated.
-    huber_delta: the threshold the taped forward ran with (gs_projective_icp_robust_backward_batch_f32 when > 0)."""
+    huber_delta: the threshold the taped forward ran with (gs_projective_icp_robust_backward_batch_f32 when > 0).
+    huber_k > 0: the taped forward ran with the median rule (gs_projective_icp_scaled_backward_batch_f32): every
+    iteration's threshold is read from the tape and is a constant of the pass; huber_delta is then not read."""
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
     huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_backward")
+    huber_k = _picp_huber_k(huber_k, "projective_icp_backward")
     with torch.no_grad():
         seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp_backward", vertex, normal, depth, K, index, model_poses,
                                                maps, pose_bar, stride)
@@ -1170,7 +1226,10 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
         buf = ws.bytes("picp_bwd%d" % b, nbytes)
         u.scratch, u.scratch_bytes = buf.data_ptr(), int(buf.numel())
     prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
-    if huber_delta > 0:
+    if huber_k > 0:
+        check(L.gs_projective_icp_scaled_backward_batch_f32(bseqs, Bn, H, W, prm, stream(dev)),
+              "gs_projective_icp_scaled_backward_batch_f32")
+    elif huber_delta > 0:
         check(L.gs_projective_icp_robust_backward_batch_f32(bseqs, Bn, H, W, prm, huber_delta, stream(dev)),
               "gs_projective_icp_robust_backward_batch_f32")
     else:
@@ -1183,7 +1242,8 @@ class ProjectiveICPFunction(torch.autograd.Function):
     """projective_icp_batch on the autograd tape: forward = gs_projective_icp_tape_batch_f32 (the plain solve's kernels
     and pose bits, plus the tape), backward = one call of gs_projective_icp_backward_batch_f32.  Inputs: vertex, normal,
     depth, K, index, model_poses, init_poses, cfg (the keyword arguments, `counts` = per sequence (n_bound, n_dev),
-    `guard` and optionally `huber_delta`: both passes then run the robust entries), then points and normals of every sequence's map.  Gradients reach vertex, init_poses and the map points /
+    `guard` and optionally `huber_delta`: both passes then run the robust entries, or `huber_k`: the scaled entries, and
+    the thresholds (B, numiters) are a third, non-differentiable output), then points and normals of every sequence's map.  Gradients reach vertex, init_poses and the map points /
     normals that require grad (needs_input_grad decides which outputs the kernel is asked for); the association is hard
     and a constant, as are depth, K, model_poses and the live normals.  The backward re-reads the map rows, so the map
     buffers must hold at backward time what they held at the forward; in-place steps write through raw pointers, which
@@ -1200,17 +1260,19 @@ class ProjectiveICPFunction(torch.autograd.Function):
                             device=depth.device)
         dist_th, dot_th = _picp_args(kw["stride"], kw["numiters"], kw["damp"], kw["dist_thresh"], kw["angle_thresh"])
         huber_delta = _picp_huber("huber_delta", cfg.get("huber_delta", 0.0))
-        T, trace = _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, kw["stride"],
-                               kw["numiters"], kw["damp"], dist_th, dot_th, True, None, tapes, huber_delta)
-        kw["huber_delta"] = huber_delta
+        huber_k = _picp_huber_k(cfg.get("huber_k", 0.0))
+        res = _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, kw["stride"], kw["numiters"],
+                          kw["damp"], dist_th, dot_th, True, None, tapes, huber_delta, huber_k, huber_k > 0)
+        T, trace = res[0], res[1]
+        kw["huber_delta"], kw["huber_k"] = huber_delta, huber_k
         ctx.save_for_backward(vertex, normal, depth, K, index, model_poses, tapes, *flat,
                               *[c[1] for c in cfg["counts"]])
         ctx.kw, ctx.bounds, ctx.guard = kw, [c[0] for c in cfg["counts"]], cfg.get("guard")
-        ctx.mark_non_differentiable(trace)
-        return T, trace
+        ctx.mark_non_differentiable(*res[1:])
+        return res
 
     @staticmethod
-    def backward(ctx, T_bar, _trace_bar):
+    def backward(ctx, T_bar, *_constants_bar):
         if ctx.guard is not None:
             ctx.guard()
         saved = ctx.saved_tensors
@@ -1230,23 +1292,25 @@ class ProjectiveICPFunction(torch.autograd.Function):
 
 def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, *, n_dev=None,
                    stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False,
-                   differentiable=False, huber_delta=0.0):
+                   differentiable=False, huber_delta=0.0, huber_k=0.0, return_scale=False):
     """projective_icp_batch for one sequence without the batch dimension: vertex / normal (H, W, 3), depth (H, W), K /
     model_pose / init_pose (4, 4), index (H, W) int64; n_dev: device int64[1] holding the actual row count of the map
     (map_points.shape[0] is then an upper bound).  Returns the pose (4, 4) (and the trace (numiters, 8)).
-    differentiable, huber_delta: see projective_icp_batch."""
+    differentiable, huber_delta, huber_k, return_scale (the thresholds (numiters,)): see projective_icp_batch."""
     _picp_tensors("projective_icp", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                                      ("model_pose", model_pose), ("init_pose", init_pose)))
     r = projective_icp_batch(vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0), K.reshape(1, 4, 4),
                              index.unsqueeze(0), model_pose.reshape(1, 4, 4), [(map_points, map_normals, None, n_dev)],
                              init_pose.reshape(1, 4, 4), stride=stride, numiters=numiters, damp=damp,
                              dist_thresh=dist_thresh, angle_thresh=angle_thresh, return_trace=return_trace,
-                             differentiable=differentiable, huber_delta=huber_delta)
-    return (r[0][0], r[1][0]) if return_trace else r[0]
+                             differentiable=differentiable, huber_delta=huber_delta, huber_k=huber_k,
+                             return_scale=return_scale)
+    return tuple(x[0] for x in r) if isinstance(r, tuple) else r[0]
 
 
 def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points, map_normals, pose, *, n_dev=None,
-                        stride=1, dist_thresh=0.1, angle_thresh=30.0, huber_delta=0.0, return_weights=False):
+                        stride=1, dist_thresh=0.1, angle_thresh=30.0, huber_delta=0.0, return_weights=False,
+                        huber_k=0.0):
     """ONE linearisation of the projective ICP at `pose` (gs_projective_icp_rows_f32), arguments as projective_icp.  With
     nslots = ceil(H / stride) * ceil(W / stride), slot i * ceil(W / stride) + j standing for pixel (i stride, j stride):
     ProjectiveRows(code int32 (nslots,): 0 used, 1 no depth, 2 outside the model view, 3 no (or a stale) winner, 4 too
@@ -1254,9 +1318,13 @@ def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points,
     a (nslots, 6), b (nslots,): the point-to-plane row, zeros unless used; sums float64 (28,): 21 upper-triangular a_i
     a_j, 6 a_i b, b b; count int64 (1,)).
     huber_delta > 0 (gs_projective_icp_robust_rows_f32): sums are the Huber-weighted sums, a and b stay unweighted;
-    return_weights=True returns (ProjectiveRows, weight float32 (nslots,): the weight of a used slot, 0 elsewhere)."""
+    return_weights=True returns (ProjectiveRows, weight float32 (nslots,): the weight of a used slot, 0 elsewhere).
+    huber_k > 0 (gs_projective_icp_scaled_rows_f32): the threshold is max(huber_k * 1.4826 * the lower median of |b| over
+    the used slots, huber_delta), derived at `pose`; return_weights=True then returns (ProjectiveRows, weight, threshold
+    float32 (1,))."""
     dist_th, dot_th = _picp_args(stride, 1, 1.0, dist_thresh, angle_thresh)
     huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_rows")
+    huber_k = _picp_huber_k(huber_k, "projective_icp_rows")
     if not isinstance(return_weights, bool):
         raise TypeError("projective_icp_rows: return_weights must be of type bool; but was of type {}.".format(
             type(return_weights)))
@@ -1265,11 +1333,19 @@ def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points,
     seqs, held, dev, _, H, W = _picp_seqs("projective_icp_rows", vertex.unsqueeze(0), normal.unsqueeze(0),
                                           depth.unsqueeze(0), K.reshape(1, 4, 4), index.unsqueeze(0),
                                           model_pose.reshape(1, 4, 4), [(map_points, map_normals, None, n_dev)],
-                                          pose.reshape(1, 4, 4), stride)
+                                          pose.reshape(1, 4, 4), stride, scaled=huber_k > 0)
     ns = _picp_nslots(H, W, stride)
     res = ProjectiveRows(torch.empty(ns, dtype=torch.int32, device=dev), torch.empty(ns, dtype=torch.int64, device=dev),
                          torch.empty((ns, 6), dtype=f32, device=dev), torch.empty(ns, dtype=f32, device=dev),
                          torch.empty(28, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.int64, device=dev))
+    if huber_k > 0:
+        weight, delta = (torch.empty(ns, dtype=f32, device=dev), torch.empty(1, dtype=f32, device=dev)) \
+            if return_weights else (None, None)
+        check(lib().gs_projective_icp_scaled_rows_f32(seqs, H, W, int(stride), dist_th, dot_th, huber_k, huber_delta,
+                                                      *[ptr(t) for t in res[:4]], ptr(weight),
+                                                      *[ptr(t) for t in res[4:]], ptr(delta), stream(dev)),
+              "gs_projective_icp_scaled_rows_f32")
+        return (res, weight, delta) if return_weights else res
     if huber_delta > 0 or return_weights:
         weight = torch.empty(ns, dtype=f32, device=dev) if return_weights else None
         check(lib().gs_projective_icp_robust_rows_f32(seqs, H, W, int(stride), dist_th, dot_th, huber_delta,
@@ -1354,7 +1430,7 @@ def _picp_color_seqs(who, seqs, held, Bn, H, W, color, model):
 def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, maps, init_poses, color, model, *,
                                color_weight, stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0,
                                return_trace=False, out=None, differentiable=False, huber_delta=0.0,
-                               color_huber_delta=0.0):
+                               color_huber_delta=0.0, huber_k=0.0, return_scale=False):
     """projective_icp_batch with a photometric term (gs_projective_icp_color_batch_f32: the same two launches per
     iteration for 8 sequences, nothing read back).  The arguments of projective_icp_batch, then color (B, H, W, 3): the
     live frames' colour, and model (B, H, W, 4): model_intensity of the views' rendered colour and index images.  A slot
@@ -1366,35 +1442,47 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
     refused: the colour term has no backward pass.
     huber_delta (metres) / color_huber_delta (intensity units), 0 = off: Huber weights on the point-to-plane residual and
     on the colour residual before color_weight is applied (gs_projective_icp_color_robust_batch_f32); the trace's second
-    column is then the weighted joint sum of squares."""
+    column is then the weighted joint sum of squares.
+    huber_k, return_scale: as in projective_icp_batch, for the GEOMETRIC threshold (gs_projective_icp_color_scaled_batch_f32:
+    the median of |b|, huber_delta its floor); color_huber_delta stays a constant."""
     _picp_refuse_differentiable(differentiable)
     weight = _picp_color_weight(color_weight)
     huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_color")
+    huber_k = _picp_huber_k(huber_k, "projective_icp_color")
+    _picp_flag("projective_icp_color", "return_scale", return_scale)
     color_huber_delta = _picp_huber("color_huber_delta", color_huber_delta, "projective_icp_color")
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
     who = "projective_icp_color"
     seqs, held, dev, Bn, H, W = _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride,
-                                           color=True)
+                                           color=True, scaled=huber_k > 0)
     cseqs = _picp_color_seqs(who, seqs, held, Bn, H, W, color, model)
     T, trace, prm = _picp_outputs(who, [c.base for c in cseqs], dev, out, return_trace, PICP_COLOR_TRACE, stride,
                                   numiters, damp, dist_th, dot_th)
-    if huber_delta > 0 or color_huber_delta > 0:
+    scale = None
+    if huber_k > 0:
+        scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale else (None, None)
+        check(lib().gs_projective_icp_color_scaled_batch_f32(cseqs, dptrs, Bn, H, W, prm, weight, huber_k, huber_delta,
+                                                             color_huber_delta, stream(dev)),
+              "gs_projective_icp_color_scaled_batch_f32")
+    elif huber_delta > 0 or color_huber_delta > 0:
         check(lib().gs_projective_icp_color_robust_batch_f32(cseqs, Bn, H, W, prm, weight, huber_delta, color_huber_delta,
                                                              stream(dev)),
               "gs_projective_icp_color_robust_batch_f32")
     else:
         check(lib().gs_projective_icp_color_batch_f32(cseqs, Bn, H, W, prm, weight, stream(dev)),
               "gs_projective_icp_color_batch_f32")
-    return (T, trace) if return_trace else T
+    if return_scale and scale is None:
+        scale = torch.full((Bn, int(numiters)), huber_delta, dtype=f32, device=dev)
+    return _picp_pack(T, trace, scale, return_trace, return_scale)
 
 
 def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, color, model,
                          *, color_weight, n_dev=None, stride=1, numiters=10, damp=1e-8, dist_thresh=0.1,
                          angle_thresh=30.0, return_trace=False, differentiable=False, huber_delta=0.0,
-                         color_huber_delta=0.0):
+                         color_huber_delta=0.0, huber_k=0.0, return_scale=False):
     """projective_icp_color_batch for one sequence without the batch dimension (arguments as projective_icp, then color
     (H, W, 3) and model (H, W, 4)).  Returns the pose (4, 4) (and the trace (numiters, 9)).  huber_delta,
-    color_huber_delta: see projective_icp_color_batch."""
+    color_huber_delta, huber_k, return_scale: see projective_icp_color_batch."""
     _picp_tensors("projective_icp_color", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K),
                                            ("index", index), ("model_pose", model_pose), ("init_pose", init_pose),
                                            ("color", color), ("model_intensity", model)))
@@ -1404,8 +1492,8 @@ def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points
                                    color.unsqueeze(0), model.unsqueeze(0), color_weight=color_weight, stride=stride,
                                    numiters=numiters, damp=damp, dist_thresh=dist_thresh, angle_thresh=angle_thresh,
                                    return_trace=return_trace, differentiable=differentiable, huber_delta=huber_delta,
-                                   color_huber_delta=color_huber_delta)
-    return (r[0][0], r[1][0]) if return_trace else r[0]
+                                   color_huber_delta=color_huber_delta, huber_k=huber_k, return_scale=return_scale)
+    return tuple(x[0] for x in r) if isinstance(r, tuple) else r[0]
 
 
 def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_points, map_normals, pose, color, model,

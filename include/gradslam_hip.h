@@ -910,6 +910,49 @@ GS_API int gs_projective_icp_color_robust_rows_f32(const gs_picp_color_seq* seq_
                                                    float* color_weight_out, double* sums28, int64_t* count,
                                                    int64_t* color_count, void* stream);
 
+/* ------------------------------------------------------------------ projective ICP: Huber threshold from the median ------
+ * Opt-in (additions only; the ABI version, every struct and every signature above stay): the threshold of the robust
+ * weights is estimated from the residuals, per sequence and per iteration, at the pose T_k that iteration k linearises
+ * at.  With n the number of used slots and b_i their float32 residuals (the values the robust kernel weights):
+ *   med     = the LOWER MEDIAN of |b_i|: the element of 0-based rank (n - 1) / 2 in ascending order (an element of the
+ *             set, never an average: exact; selected on the bit patterns, which order like the non-negative floats)
+ *   c       = (float)huber_k * 1.4826f              one float32 product (huber_k = 1.345: the usual Huber constant)
+ *   delta_k = c * med (one float32 product), then huber_floor where the product is not above it (a NaN included)
+ *   n == 0:   delta_k = +0.0f, and the pose keeps its bits as in every other entry
+ * Weights and terms are those of the robust entries with delta_k for huber_delta; delta_k == 0 (a zero median) switches
+ * the weights off for that iteration, which then has the plain solve's bits.  huber_k must be finite and > 0,
+ * huber_floor finite and >= 0.  Two more launches per iteration for 8 sequences (a residual pass over the lattice and one
+ * select block per sequence: an 11 + 11 + 10 bit radix selection on integer counters) and one small clearing launch per
+ * call; nothing read back, no float atomics: bitwise reproducible.
+ * scratch: gs_projective_icp_scaled_scratch_bytes / gs_projective_icp_color_scaled_scratch_bytes (the plain / colour
+ * scratch, then the key table (nslots uint32), 2048 counters and the threshold), 16-byte aligned.
+ * gs_projective_icp_scaled_batch_f32: gs_projective_icp_robust_batch_f32 with the rule; tapes_host as there (NULL:
+ * untaped; a taped row holds delta_k in pad[0]); deltas_host: NULL, or per sequence a device buffer of numiters floats
+ * that receives delta_k.
+ * gs_projective_icp_scaled_rows_f32: gs_projective_icp_robust_rows_f32 with the threshold derived at init_pose16, which
+ * also goes to delta_out (1 float, or NULL).
+ * gs_projective_icp_color_scaled_batch_f32: gs_projective_icp_color_robust_batch_f32 with the rule for the geometric
+ * threshold; color_huber_delta stays a constant.
+ * gs_projective_icp_scaled_backward_batch_f32: gs_projective_icp_robust_backward_batch_f32 for a tape of the scaled
+ * forward: every iteration's threshold is read from its tape row and is a constant of the pass, like the clip flags (no
+ * gradient flows through the median).  Every argument is checked before the first HIP call. */
+GS_API int64_t gs_projective_icp_scaled_scratch_bytes(int H, int W, int stride);
+GS_API int64_t gs_projective_icp_color_scaled_scratch_bytes(int H, int W, int stride);
+GS_API int gs_projective_icp_scaled_batch_f32(const gs_picp_seq* seqs_host, void* const* tapes_host,
+                                              float* const* deltas_host, int B, int H, int W,
+                                              const gs_picp_params* params_host, float huber_k, float huber_floor,
+                                              void* stream);
+GS_API int gs_projective_icp_scaled_rows_f32(const gs_picp_seq* seq_host, int H, int W, int stride, float dist_th,
+                                             float dot_th, float huber_k, float huber_floor, int32_t* code, int64_t* row,
+                                             float* a6, float* b, float* weight, double* sums28, int64_t* count,
+                                             float* delta_out, void* stream);
+GS_API int gs_projective_icp_color_scaled_batch_f32(const gs_picp_color_seq* seqs_host, float* const* deltas_host, int B,
+                                                    int H, int W, const gs_picp_params* params_host, float color_weight,
+                                                    float huber_k, float huber_floor, float color_huber_delta,
+                                                    void* stream);
+GS_API int gs_projective_icp_scaled_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
+                                                       const gs_picp_params* params_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

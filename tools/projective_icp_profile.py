@@ -2,7 +2,7 @@
 frame loop gains or loses with it, and what a launch of it costs (needs the MI355X; fails without one).
 
     python tools/projective_icp_profile.py [--out FILE] [--only localize|slam|launches] [--steps K] [--color-weight W]
-                                           [--huber-delta D] [--color-huber-delta C]
+                                           [--huber-delta D] [--color-huber-delta C] [--huber-k K] [--parent-lib SO]
 
 1. One localisation.  640x480 frames of the benchmark's synthetic sequences, the map fused from the first 10 frames under
    the ground-truth poses, frame 10 localised from the pose of frame 9; B = 1 and B = 8.
@@ -33,7 +33,17 @@ colours are per-frame noise: the times hold, the poses of these variants say not
 --huber-delta D (metres, D > 0) adds the solve with Huber weights to parts 1 and 3, alternating with the plain one in the
 same process: the provider with huber_delta=D, and in part 3 the robust solve alone (10 and 40 iterations: the slope is
 one robust linearise launch + the plain finish launch).  --color-huber-delta C (C > 0, needs --color-weight) does the
-same for the joint solve with both thresholds."""
+same for the joint solve with both thresholds.
+
+--huber-k K (K > 0; 1.345 is the usual constant) adds the solve whose Huber threshold is estimated from the residuals'
+median in every iteration (--huber-delta is then its floor) to all three parts, alternating with the plain and the
+constant-threshold solve in the same process: the provider with huber_k=K in part 1, the scaled solve alone in part 3
+(the slope is its four launches: residual pass, select, robust linearise, finish) and PointFusion(odom="projicp",
+huber_k=K) in part 2 (frames/s and ATE next to the plain projicp run).
+
+--parent-lib SO (needs --huber-delta): the libgradslam_hip.so of another build of this project, e.g. of the parent commit
+(same ABI version), loaded next to this tree's.  Part 3 then also times ITS gs_projective_icp_robust_batch_f32 on the
+same descriptors, alternating with this tree's solves in the same process: what a change to the robust kernels cost."""
 import argparse
 import json
 import os
@@ -86,7 +96,8 @@ def translation_error(T, gt):
     return [float(x) for x in (T.reshape(-1, 4, 4)[:, :3, 3].double() - gt[:3, 3].double()).norm(dim=1).cpu()]
 
 
-def localize_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta=0.0, color_huber_delta=0.0):
+def localize_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta=0.0, color_huber_delta=0.0,
+                   huber_k=0.0):
     from gradslam_amd.odometry import ProjectiveICPOdometryProvider
     out = []
     for B in (1, 8):
@@ -112,6 +123,11 @@ def localize_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_del
             rprov = {s: ProjectiveICPOdometryProvider(numiters=10, stride=s, huber_delta=huber_delta) for s in (4, 1)}
             fns["projicp_robust_stride4_10it"] = lambda: rprov[4].localize(pc, live, prev)
             fns["projicp_robust_stride1_10it"] = lambda: rprov[1].localize(pc, live, prev)
+        if huber_k > 0:
+            sprov = {s: ProjectiveICPOdometryProvider(numiters=10, stride=s, huber_delta=huber_delta, huber_k=huber_k)
+                     for s in (4, 1)}
+            fns["projicp_scaled_stride4_10it"] = lambda: sprov[4].localize(pc, live, prev)
+            fns["projicp_scaled_stride1_10it"] = lambda: sprov[1].localize(pc, live, prev)
         if color_weight > 0 and (huber_delta > 0 or color_huber_delta > 0):
             rcprov = {s: ProjectiveICPOdometryProvider(numiters=10, stride=s, color_weight=color_weight,
                                                        huber_delta=huber_delta, color_huber_delta=color_huber_delta)
@@ -122,7 +138,8 @@ def localize_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_del
         for fn in fns.values():
             fn(), fn()
         t = time_round_robin(torch, fns, reps, rounds)
-        rec = {"B": B, "color_weight": color_weight, "huber_delta": huber_delta, "color_huber_delta": color_huber_delta, "H": H, "W": W, "map_rows": rows, "initial_translation_error_m": translation_error(prev, gt)[0],
+        rec = {"B": B, "color_weight": color_weight, "huber_delta": huber_delta, "color_huber_delta": color_huber_delta,
+               "huber_k": huber_k, "H": H, "W": W, "map_rows": rows, "initial_translation_error_m": translation_error(prev, gt)[0],
                "variants": {k: dict(t[k], translation_error_m=err[k]) for k in fns}}
         for s in (4, 1):
             rec["speedup_stride%d_vs_gradicp_20it" % s] = \
@@ -132,7 +149,36 @@ def localize_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_del
     return out
 
 
-def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta=0.0, color_huber_delta=0.0):
+def parent_robust_solve(ops, parent, args, stride, numiters, huber_delta):
+    """the constant-threshold robust solve of another build's library on descriptors filled by this tree's Python layer
+    (the structs are part of the ABI, which both share)"""
+    from gradslam_amd import _C
+    dist_th, dot_th = ops._picp_args(stride, numiters, 1e-8, 0.1, 30.0)
+    seqs, held, dev, Bn, Hh, Ww = ops._picp_seqs("projective_icp", *args, stride)
+    T, _, prm = ops._picp_outputs("projective_icp", list(seqs), dev, None, False, ops.PICP_TRACE, stride, numiters, 1e-8,
+                                  dist_th, dot_th)
+    st = ops.stream(dev)
+
+    def call():
+        status = parent.gs_projective_icp_robust_batch_f32(seqs, None, Bn, Hh, Ww, prm, huber_delta, st)
+        assert status == 0 and held and T is not None, parent.gs_last_error()
+    return call
+
+
+def load_parent(path):
+    import ctypes
+    from gradslam_amd import _C
+    parent = ctypes.CDLL(os.path.abspath(path))
+    fn = parent.gs_projective_icp_robust_batch_f32
+    fn.argtypes, fn.restype = _C._PROTOS["gs_projective_icp_robust_batch_f32"], ctypes.c_int
+    parent.gs_last_error.restype = ctypes.c_char_p
+    if parent.gs_abi_version() != _C.ABI_VERSION:
+        sys.exit("--parent-lib: ABI version %d, this tree has %d" % (parent.gs_abi_version(), _C.ABI_VERSION))
+    return parent
+
+
+def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta=0.0, color_huber_delta=0.0,
+                 huber_k=0.0, parent=None):
     out = []
     for B in (1, 8):
         pc, live, prev, _ = scene(torch, gs, B)
@@ -161,6 +207,12 @@ def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta
             if huber_delta > 0:
                 fns.update({"solve_robust_%dit" % n: (lambda n=n: ops.projective_icp_batch(
                     *args, stride=stride, numiters=n, huber_delta=huber_delta)) for n in (10, 40)})
+            if parent is not None:
+                fns.update({"solve_robust_parent_%dit" % n: parent_robust_solve(ops, parent, args, stride, n, huber_delta)
+                            for n in (10, 40)})
+            if huber_k > 0:
+                fns.update({"solve_scaled_%dit" % n: (lambda n=n: ops.projective_icp_batch(
+                    *args, stride=stride, numiters=n, huber_delta=huber_delta, huber_k=huber_k)) for n in (10, 40)})
             robust_color = color_weight > 0 and (huber_delta > 0 or color_huber_delta > 0)
             if robust_color:
                 fns.update({"solve_color_robust_%dit" % n: (lambda n=n: ops.projective_icp_color_batch(
@@ -182,6 +234,13 @@ def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta
                 rec["huber_delta"] = huber_delta
                 rec["us_per_iteration_robust"] = \
                     (t["solve_robust_40it"]["median_ms"] - t["solve_robust_10it"]["median_ms"]) / 30 * 1e3
+            if parent is not None:
+                rec["us_per_iteration_robust_parent"] = \
+                    (t["solve_robust_parent_40it"]["median_ms"] - t["solve_robust_parent_10it"]["median_ms"]) / 30 * 1e3
+            if huber_k > 0:
+                rec["huber_k"] = huber_k
+                rec["us_per_iteration_scaled"] = \
+                    (t["solve_scaled_40it"]["median_ms"] - t["solve_scaled_10it"]["median_ms"]) / 30 * 1e3
             if robust_color:
                 rec["color_huber_delta"] = color_huber_delta
                 rec["us_per_iteration_color_robust"] = \
@@ -191,15 +250,15 @@ def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta
     return out
 
 
-def slam_runs(torch, gs, steps, warmup=10):
+def slam_runs(torch, gs, steps, warmup=10, huber_delta=0.0, huber_k=0.0):
     import bench
     B = 8
     device = torch.device("cuda")
     frames, gt = bench.make_sequences_on_device(gs, list(range(B)), warmup + steps, H, W, device)
     gt_t = torch.from_numpy(gt[0]["poses"][warmup:warmup + steps, :3, 3]).to(device).double()
 
-    def run(odom):
-        slam = gs.slam.PointFusion(odom=odom, device=device)
+    def run(odom, **kw):
+        slam = gs.slam.PointFusion(odom=odom, device=device, **kw)
         r = bench.timed_steps(gs, slam, frames, warmup, steps, device, lambda: torch.cuda.synchronize(device))
         e = (r["poses"][:, warmup:warmup + steps, :3, 3].double() - gt_t).norm(dim=-1)     # (B, steps)
         return {"odom": odom, "frames_per_s": B * steps / r["elapsed"], "ms_per_step": r["elapsed"] / steps * 1e3,
@@ -213,6 +272,13 @@ def slam_runs(torch, gs, steps, warmup=10):
     base2 = run("gradicp")
     out = {"B": B, "H": H, "W": W, "warmup": warmup, "steps": steps, "gradicp": base, "projicp": new,
            "gradicp_repeated": base2, "frames_per_s_ratio": new["frames_per_s"] / base["frames_per_s"]}
+    if huber_k > 0:   # the median rule next to the plain projicp run, the plain one repeated for the spread
+        kw = dict(huber_delta=huber_delta, huber_k=huber_k)
+        run("projicp", **kw)
+        out["projicp_scaled"] = dict(run("projicp", **kw), **kw)
+        out["projicp_repeated"] = run("projicp")
+        out["projicp_scaled_repeated"] = dict(run("projicp", **kw), **kw)
+        out["frames_per_s_ratio_scaled_vs_projicp"] = out["projicp_scaled"]["frames_per_s"] / new["frames_per_s"]
     print(json.dumps(out), flush=True)
     return out
 
@@ -226,16 +292,23 @@ def main():
                     help="> 0: also time the joint geometric + photometric solve (parts 1 and 3)")
     ap.add_argument("--huber-delta", type=float, default=0.0,
                     help="> 0 (metres): also time the solve with Huber weights (parts 1 and 3)")
+    ap.add_argument("--huber-k", type=float, default=0.0,
+                    help="> 0: also time the solve with the Huber threshold from the residuals' median (all three parts; "
+                         "--huber-delta is then its floor)")
+    ap.add_argument("--parent-lib", default=None, metavar="SO",
+                    help="another build's libgradslam_hip.so (needs --huber-delta): part 3 also times its robust solve")
     ap.add_argument("--color-huber-delta", type=float, default=0.0,
                     help="> 0 (intensity units, needs --color-weight): Huber weights on the colour rows of the joint solve")
     args = ap.parse_args()
     if not (args.color_weight >= 0 and args.color_weight < float("inf")):
         ap.error("--color-weight must be finite and not negative")
-    for name in ("huber_delta", "color_huber_delta"):
+    for name in ("huber_delta", "color_huber_delta", "huber_k"):
         if not (getattr(args, name) >= 0 and getattr(args, name) < float("inf")):
             ap.error("--%s must be finite and not negative" % name.replace("_", "-"))
     if args.color_huber_delta > 0 and not args.color_weight > 0:
         ap.error("--color-huber-delta needs --color-weight")
+    if args.parent_lib and not args.huber_delta > 0:
+        ap.error("--parent-lib needs --huber-delta")
     import torch
     if not torch.cuda.is_available():
         sys.exit("tools/projective_icp_profile.py measures on the GPU: no HIP device found (nothing is measured on the CPU)")
@@ -244,12 +317,14 @@ def main():
     out = {"device": torch.cuda.get_device_name(0)}
     if args.only in (None, "localize"):
         out["one_localisation"] = localize_times(torch, gs, ops, color_weight=args.color_weight,
-                                                 huber_delta=args.huber_delta, color_huber_delta=args.color_huber_delta)
+                                                 huber_delta=args.huber_delta, color_huber_delta=args.color_huber_delta,
+                                                 huber_k=args.huber_k)
     if args.only in (None, "slam"):
-        out["slam_window"] = slam_runs(torch, gs, args.steps)
+        out["slam_window"] = slam_runs(torch, gs, args.steps, huber_delta=args.huber_delta, huber_k=args.huber_k)
     if args.only in (None, "launches"):
         out["launches"] = launch_times(torch, gs, ops, color_weight=args.color_weight, huber_delta=args.huber_delta,
-                                       color_huber_delta=args.color_huber_delta)
+                                       color_huber_delta=args.color_huber_delta, huber_k=args.huber_k,
+                                       parent=load_parent(args.parent_lib) if args.parent_lib else None)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
