@@ -16,6 +16,12 @@ LIB_PATH = os.environ.get("GRADSLAM_HIP_LIB") or os.path.join(_HERE, "csrc", "li
 if os.environ.get("GRADSLAM_HIP_LIB"):   # (a bench line must not come from an experimental build unnoticed)
     import warnings
     warnings.warn("GRADSLAM_HIP_LIB overrides the product library: %s" % LIB_PATH, RuntimeWarning)
+# knobs of engines that were measured, lost and removed: setting one must not pass silently
+RETIRED_KNOBS = ("GRADSLAM_HIP_ICP_PERSIST", "GRADSLAM_HIP_ICP_PERSIST_TIMELINE", "GRADSLAM_HIP_ICP_FAR")
+if any(k in os.environ for k in RETIRED_KNOBS):
+    import warnings
+    warnings.warn("retired knobs are set and ignored: %s (their engines were removed; the one ICP solve path runs)"
+                  % ", ".join(k for k in RETIRED_KNOBS if k in os.environ), RuntimeWarning)
 ABI_VERSION = 3
 
 _lib = None
@@ -189,7 +195,6 @@ _PROTOS = {
     "gs_project_points_f32": [_vp, _i32, _i64, _vp, _i64, _vp, _vp],
     "gs_unproject_points_f32": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp],
     "gs_lie_small_f32": [_i32, _vp, _vp, _vp],
-    "gs_localize_far_stats_i64": [_vp, _i32, _i32, _i32, _i64, C.POINTER(C.c_int64), _vp],
     "gs_localize_list_stats_i64": [_vp, _i32, _i32, _i32, _i64, C.POINTER(C.c_int64), _vp],
     "gs_localize_solve_stats_i64": [_vp, _i32, _i32, _i32, _i64, C.POINTER(C.c_int64), _vp],
     "gs_pointfusion_step_batch_f32": [C.POINTER(StepSeq), _i32, _i32, _i32, _i32, C.POINTER(IcpParams), _f, _f, _f, _i32, _vp],

@@ -9,48 +9,30 @@
 
 struct GsEnv {
   // ---- engines of the batched localisation (gs_icp_loop.hip: icp_engine_plan)
-  // ICP_LISTS=0: no candidate lists of ordinary queries (gs_knn.h: gl_*); by default every solve that keeps no far lists has them.
+  // ICP_LISTS=0: no candidate lists of ordinary queries (gs_knn.h: gl_*).
   bool icp_lists;
   // ICP_LISTS_FROM=k: the lists are built behind the look-ahead search of iteration k and tried from iteration k + 1 on
   // (unset or negative: FS_LISTS_FROM = 1).  The step of iteration 0 is the large one of a solve (millimetres); a list
   // built before it would not survive it.  Later starts were measured too: 0 / 1 / 4 / 8 give
   // 7.40 / 7.42 / 7.42 / 7.31 k frames/s at 8 sequences per GPU.
   int icp_lists_from;
-  // ICP_WIDE=0: no wide lists of hard queries (gs_knn.h), which live in the memory of the far lists whenever those are not in use.
+  // ICP_WIDE=0: no wide lists of hard queries (gs_knn.h).
   bool icp_wide;
-  // ICP_FAR=1: candidate lists of far queries (gs_knn.h).  Policy: round 3 built them for 1296x968 (78k source points,
-  // clusters of far ones at the frame borders: +4 % frames/s over 200 frames), where they REPLACED the ordinary lists (the
-  // two do not fit one kernel).  Round 5: the wide lists of hard queries give those points lists inside the variants with
-  // ordinary lists, and ordinary + wide lists beat the far lists at 1296x968 by 18 % (780 vs 662 frames/s over 150
-  // frames, same poses: profiles/r05_c5_far_vs_wide.txt) -- so the far lists are opt-in now.
-  bool icp_far;
   // ICP_BINNED_NORMALS=0: gather the matches' normals from the map instead of the binned copy (A/B)
   bool icp_binned_normals;
   // ICP_WEAK_ROOM=<cells> (0 = off = anything outside [0, 1)): see the list-building branch of icp_half_body
   float icp_weak_room;
-  // ICP_PERSIST=1 (exactly 1): the list-checking half-iterations as ONE persistent launch per XCD-resident sequence
-  // (gs_icp_persist.h).  OPT-IN; tests/test_hip_batch.py::test_persistent_xcd_solve_leaves_results_identical.  Measured,
-  // round 6 (profiles/r06_xcd_persistent_*): its steady-state half-iteration takes 6.5 - 7.6 us against 10.5 - 12.5 us per
-  // launch, but a half-iteration in which any list of a block fails costs ~27 us (re-search 9 + cubes 5 + new lists 3 on
-  // top), solves that still move lose lists in every look-ahead, and the launches in front of it run at 2 lanes per point:
-  // +3.9 / +3.2 / +7.8 % at 8 / 4 / 2 sequences per GPU over the 20-step window, -1.2 % over the 200-step window,
-  // -2 ... -6 % for a lone sequence (profiles/r06_xcd_persistent_ab_bench.json).  Its liveness also rests on the
-  // dispatcher placing at least 29 of the launch's blocks on every XCD (every wait is bounded: a NaN pose, not a hang).
-  // The launch-per-half-iteration path stays the default.
-  bool icp_persist;
   // ---- launch geometry of a half-iteration (icp_half_plan; A/B runs: the results do not depend on either)
-  bool icp_lanes_set;      // ICP_LANES is set at all (then no persistent solve)
-  int icp_lanes;           // ICP_LANES = 2 | 4 | 8 forces the lanes per query (0: unset)
+  int icp_lanes;         // ICP_LANES = 2 | 4 | 8 forces the lanes per query (0: unset)
   int icp_blocks_per_cu;   // ICP_BLOCKS_PER_CU > 0: resident-block budget per CU (experiments; else one if some G fits that, or two)
   // ---- debugging aids (library built with -DGS_ICP_TIMELINE; gs_icp_timeline.h)
-  const char* icp_timeline;           // ICP_TIMELINE=<path>; set at all: no persistent solve
-  const char* icp_persist_timeline;   // ICP_PERSIST_TIMELINE=<path>
+  const char* icp_timeline;           // ICP_TIMELINE=<path>
   bool icp_timeline_it_set; int icp_timeline_it;   // ICP_TIMELINE_IT=k: the iteration recorded (default: the last)
   int timeline_it(int numiters) const { return icp_timeline_it_set ? icp_timeline_it : numiters - 1; }
   // ---- generic solve
   bool knn_brute;    // KNN=brute forces the brute-force engine (A/B runs; results are identical)
   int knn_spt;       // KNN_SPT = 4 | 8: source points per thread of the brute-force search (anything else: the size rule)
-  bool debug_grid;   // DEBUG_GRID set: gs_localize_far_stats_i64 prints the grid header
+  bool debug_grid;   // DEBUG_GRID set: gs_localize_list_stats_i64 prints the grid header
 };
 
 inline const GsEnv& gs_env() {
@@ -60,17 +42,13 @@ inline const GsEnv& gs_env() {
     v.icp_lists = num("GRADSLAM_HIP_ICP_LISTS", 1) != 0;
     v.icp_lists_from = num("GRADSLAM_HIP_ICP_LISTS_FROM", -1);
     v.icp_wide = num("GRADSLAM_HIP_ICP_WIDE", 1) != 0;
-    v.icp_far = num("GRADSLAM_HIP_ICP_FAR", 0) != 0;
     v.icp_binned_normals = num("GRADSLAM_HIP_ICP_BINNED_NORMALS", 1) != 0;
     const char* room = getenv("GRADSLAM_HIP_ICP_WEAK_ROOM");
     v.icp_weak_room = room ? (float)atof(room) : 0.0f;
     if (!(v.icp_weak_room >= 0.0f && v.icp_weak_room < 1.0f)) v.icp_weak_room = 0.0f;
-    v.icp_persist = num("GRADSLAM_HIP_ICP_PERSIST", 0) == 1;
-    v.icp_lanes_set = getenv("GRADSLAM_HIP_ICP_LANES") != nullptr;
     v.icp_lanes = num("GRADSLAM_HIP_ICP_LANES", 0);
     v.icp_blocks_per_cu = num("GRADSLAM_HIP_ICP_BLOCKS_PER_CU", 0);
     v.icp_timeline = getenv("GRADSLAM_HIP_ICP_TIMELINE");
-    v.icp_persist_timeline = getenv("GRADSLAM_HIP_ICP_PERSIST_TIMELINE");
     v.icp_timeline_it_set = getenv("GRADSLAM_HIP_ICP_TIMELINE_IT") != nullptr;
     v.icp_timeline_it = num("GRADSLAM_HIP_ICP_TIMELINE_IT", 0);
     const char* knn = getenv("GRADSLAM_HIP_KNN");

@@ -8,10 +8,13 @@
 // Grid path (large target sets; the SLAM loop): ONE kernel per half-iteration.  Its prologue lets
 // every block redundantly finish the PREVIOUS half-iteration (add up the partial rows the previous
 // kernel left, then the scalar stage: solve + se3_exp, or LM / gradLM update) so that no separate
-// single-block kernels sit on the critical path; block 0 records the state.  Then GQ_G (8) lanes per
+// single-block kernels sit on the critical path; block 0 records the state.  Then 8, 4 or 2 lanes per
 // source point run the grid search (gs_knn.h), the block finishes unresolved queries by brute
-// force, builds the Gauss-Newton rows and emits one partial row.  State and partial rows are
-// double-buffered between consecutive kernels.  2 x numiters + 1 launches per solve.
+// force, builds the Gauss-Newton rows and emits one partial row per 96 source points.  State and
+// partial rows are double-buffered between consecutive kernels.  2 x numiters + 1 launches per solve.
+// This is the ONE solve path: the batched localisation adds candidate lists to it (ordinary lists of
+// every source point, wide lists of the hard ones: list modes 0 / 1 / 2 of the same kernel), the
+// single solve runs it without.
 //
 // Brute-force path (small problems, GRADSLAM_HIP_KNN=brute): search / linearise / solve / update
 // as separate kernels.
@@ -207,14 +210,6 @@ constexpr int FS_BQ = 4;                 // queries per pass of the block-wide b
 constexpr int FS_QPB = FS_BLOCK / GQ_G;  // 96 queries per block, their rows are built by the first two waves
 constexpr int FS_RPG = (FS_QPB / 4) * LIN_NV <= FS_BLOCK ? 4 : 8;  // rows per group in the block reduction
 constexpr int FS_RG = FS_QPB / FS_RPG;                            // row groups
-constexpr int FS_FAR_PASSES = 8;     // list-building launches per solve at most: behind the first halves of iterations
-                                     // 0, 1 (before / after the large first step of a solve) and of every 4th after that
-// pass index of iteration `it`, or -1 (host and device)
-__host__ __device__ inline int fs_far_pass(int it) {
-  const int p = it < 2 ? it : ((it & 3) == 0 ? 1 + it / 4 : -1);
-  return p < FS_FAR_PASSES ? p : -1;
-}
-constexpr int FS_FAR_MIN_RING = 2;   // queries served by a cube of at least this radius get a candidate list (gs_knn.h)
 constexpr int FS_HG = 16;  // lanes per query of the shell search for queries the 2x2x2 stage leaves open
 constexpr int FS_LISTS_FROM = 1;   // iteration behind whose look-ahead search the candidate lists of ordinary queries are built
 static_assert(FS_QPB <= 2 * GS_WAVE && FS_QPB % FS_RPG == 0 && FS_RG * LIN_NV <= FS_BLOCK, "block shape");
@@ -257,20 +252,12 @@ struct IcpHalfSeq {
   int64_t* out_idx;
   int32_t* tape_idx;
   float* tape_sys;
-  // candidate lists of far queries (gs_knn.h; NULL: none kept): far_cq[s] = (position the list of source point s was
-  // built at, exactness radius), far_c[GS_FAR_SLOTS * s ..] = its slots of `sorted`, written by gs_icp_far_build_kernel
-  // after the first search of a solve.  "s has a list" travels in the sign bit of d2prev[s], which every search loads
-  // anyway (and which the first search of a solve rewrites: nothing of an earlier frame is ever read).
-  float4* far_cq;
-  uint32_t* far_c;
-  int* far_idx;   // [FS_FAR_PASSES][n_src] source points a first half with a list-building pass behind it (fs_far_pass)
-  int* far_n;     // found far from every target, far_n[pass] of them
 };
-// WIDE lists of hard queries (round 5, gs_knn.h: far_write_from_top / block_brute_min_list_multi; cq == NULL: none kept;
-// the variants without the far-list machinery above only): cq[s] = (position the list of source point s was made at,
-// exactness radius; 0: no list), c[GS_FAR_SLOTS * s ..] = its slots.  Written by whatever serves a hard query (cube
-// scan, block-wide pass) in any launch of the solve, checked first thing by the 16-lane group that serves it in every
-// later launch; the prep launch of a frame clears every point's radius (nothing of an earlier frame is ever read).
+// WIDE lists of hard queries (round 5, gs_knn.h: far_write_from_top / block_brute_min_list_multi; cq == NULL: none kept):
+// cq[s] = (position the list of source point s was made at, exactness radius; 0: no list), c[GS_FAR_SLOTS * s ..] = its
+// slots.  Written by whatever serves a hard query (cube scan, block-wide pass) in any launch of the solve, checked first
+// thing by the 16-lane group that serves it in every later launch; the prep launch of a frame clears every point's radius
+// (nothing of an earlier frame is ever read).
 struct IcpHalfWide {
   float4* cq;
   uint32_t* c;
@@ -281,11 +268,12 @@ struct IcpHalfLists {
   float4* lq;
   uint32_t* ls;
   int* lstat;
-  unsigned* weak_n;   // (list-building launch with GRADSLAM_HIP_ICP_WEAK_ROOM) weak lists flagged: a word of the sync record
+  unsigned* weak_n;   // (list-building launch with GRADSLAM_HIP_ICP_WEAK_ROOM) weak lists flagged (IcpScratch::weak_n)
 };
 
-// flags of an entry of the block's list of left-over queries (hard_q)
-constexpr int FS_HQ_FAR = (int)0x80000000;   // the query has a far-candidate list (FAR variants)
+// An entry of the block's list of left-over queries (hard_q) is a slot; its two top bits were flags once and are still
+// masked off where it is read: without that one AND the compiler allocates the registers of the whole left-over pass anew
+// (profiles/retired_engines_isa.txt), and these kernels change only with a measurement.
 constexpr int FS_HQ_SLOT = 0x3fffffff;
 
 // index pairs (into [a0..a5, res]) of the 28 accumulated products: 21 upper-triangular a_i a_k, 6 a_i res, res res
@@ -310,7 +298,7 @@ GS_DEV int fs_pb(int i) { return i < 21 ? (int)((FS_PB_BITS >> (3 * i)) & 7ull) 
 //      critical path.  A list that gives no proof sends its point to the left-over pass, where a 16-lane group
 //      scans the 2x2x2 block and writes a new list.
 // Results do not depend on any of it: a proof is exact, everything else is the search that ran before.
-template <bool FULL, int G, bool FAR, int LMODE>
+template <bool FULL, int G, int LMODE>
 GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const IcpHalfWide& qw, const GsCount n_src_c, const float dist_thresh,
                           const gs_icp_params& prm, const int it, const int rows_in_reduced, const unsigned lb,
                           const int upb, unsigned long long* __restrict__ tl_arg = nullptr, const float weak_room = 0.0f) {
@@ -320,10 +308,8 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
 #else
   constexpr unsigned long long* tl = nullptr;  // per-block timeline stamps: debugging builds only (-DGS_ICP_TIMELINE)
 #endif
-  static_assert(!(FAR && LISTS), "the two kinds of candidate lists are not combined");
   constexpr int NQ = FS_BLOCK / G, NU = NQ / FS_QPB;
-  // (LMODE 3 = LMODE 1 with four entries per lane: the 8-entry lists the persistent solve reads, gs_icp_persist.h; 2 lanes only)
-  constexpr int LK = LMODE == 3 ? 4 : gl_k<G>(), LM = G * LK;   // list entries per lane / per source point
+  constexpr int LK = gl_k<G>(), LM = G * LK;   // list entries per lane / per source point
   static_assert(NQ % FS_QPB == 0 && 2 * NU <= FS_BLOCK / GS_WAVE && LM <= GL_SLOTS, "block shape");
   const float* __restrict__ src_in = q.src_in;
   float* __restrict__ src_out = q.src_out;
@@ -346,7 +332,7 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
   __shared__ float qs[NQ][3];
   __shared__ float qa_s[NQ][8];   // a0..a5, residual of every query of the block (zero when filtered out)
   __shared__ double sub_s[NU][FS_RG][LIN_NV];
-  __shared__ int unres_q[NQ], hard_q[NQ];   // (hard_q: slot | FS_HQ_* flags)
+  __shared__ int unres_q[NQ], hard_q[NQ];
   __shared__ int unres_n, hard_n;
   // (LMODE 2) points whose list gave no proof: re-searched after the check by 16-lane groups (the 2x2x2 block as one flat
   // candidate list, 4 candidates per lane at 65 per block in a mature map: two round trips instead of the eight a 2-lane
@@ -354,18 +340,11 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
   __shared__ int fail_q[LMODE == 2 ? NQ : 1];
   __shared__ int fail_n;
   __shared__ unsigned long long red[FS_BLOCK / GS_WAVE];
-  __shared__ uint8_t far_s[NQ];   // the query's candidate list proved this search (it keeps its flag)
   // (LMODE 2) source point and (list centre, radius) of every group, parked across the scalar stage of the prologue: its
   // one-lane float64 code needs the registers, the lanes that wait for it do not
   __shared__ float4 park_s[LMODE == 2 ? 2 * NQ : 1];
   __shared__ int lfail_s[3];   // (LMODE 2) lists of this block that gave no proof / were empty / points without a list
   __shared__ uint8_t rowdone_s[LMODE == 2 ? NQ : 1];   // (LMODE 2) the row of this slot was built by the lane that won its list check
-  float4* __restrict__ far_cq = q.far_cq;
-  uint32_t* __restrict__ far_c = q.far_c;
-  // (FAR is a template parameter: the kernels sit at their register limit, and the code of the lists costs the
-  // variant without them 0.5 us per launch when it is merely present)
-  const bool far_on = FAR && far_cq != nullptr && d2prev != nullptr;
-  const int far_pass = (FULL && FAR) ? fs_far_pass(it) : -1;
   float4* __restrict__ lq = LISTS ? ql.lq : nullptr;
   uint32_t* __restrict__ ls = LISTS ? ql.ls : nullptr;
 
@@ -378,7 +357,7 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
   // lists are read by blocks that serve ONE group of units (the host plans it so whenever it asks for them)
   // (LMODE is a template parameter: one kernel per mode keeps each of them within the register budget)
   constexpr bool verify = LMODE == 2;
-  constexpr bool build_all = LMODE == 1 || LMODE == 3;
+  constexpr bool build_all = LMODE == 1;
   constexpr bool NPREF = LMODE == 2;   // the list check also fetches the normal of the likely match
   // the source point of the first slot does not depend on the prologue: issue its load first so that
   // the global-memory latency hides behind the scalar stage
@@ -560,11 +539,8 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
         if (FULL) { src_out[3 * s] = p0; src_out[3 * s + 1] = p0; src_out[3 * s + 2] = p0; }
         qs[slot][0] = p0; qs[slot][1] = p0; qs[slot][2] = p0;
         keys_s[slot] = ~0ull;
-        if (FAR) far_s[slot] = 0;
       }
     } else if (live) {
-      const bool has_far = far_on && bounded && (__float_as_uint(dprev) >> 31) != 0u;
-      if (far_on) dprev = __builtin_fabsf(dprev);
       const float* T = FULL ? sm.T_step : sm.Tr;
       float qx, qy, qz;
       gs_rigid_fma(T, p0, p1, p2, qx, qy, qz);
@@ -665,10 +641,9 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
         }
         qs[slot][0] = qx; qs[slot][1] = qy; qs[slot][2] = qz;
         keys_s[slot] = key;
-        if (FAR) far_s[slot] = 0;
         if (!done || weak) {
           if (LMODE == 2 && refail) fail_q[atomicAdd(&fail_n, 1)] = slot;
-          else hard_q[atomicAdd(&hard_n, 1)] = slot | (has_far ? FS_HQ_FAR : 0);
+          else hard_q[atomicAdd(&hard_n, 1)] = slot;
         }
       }
     }
@@ -724,23 +699,17 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
     // (the first three launches of a solve) are at their scalar-register limit, where two more pointers spill scalars into
     // vector registers and those to memory; the pointers are read here, where the rare path starts, not at the top of the
     // kernel
-    constexpr bool WL = !FAR && LISTS;
+    constexpr bool WL = LISTS;
     float4* __restrict__ wl_cq = WL ? qw.cq : nullptr;
     uint32_t* __restrict__ wl_c = WL ? qw.c : nullptr;
     const bool wl_on = WL && wl_cq != nullptr;
     for (int i = threadIdx.x / FS_HG; i < nh; i += FS_BLOCK / FS_HG) {
-      const int e = hard_q[i], hs = e & FS_HQ_SLOT, l16 = threadIdx.x & (FS_HG - 1);
+      const int hs = hard_q[i] & FS_HQ_SLOT, l16 = threadIdx.x & (FS_HG - 1);
       const float hx = qs[hs][0], hy = qs[hs][1], hz = qs[hs][2];
       const int64_t sq = (int64_t)u0 * FS_QPB + hs;   // the query's source point
       bool done = false, listed = false;
       int win = -1;
       unsigned long long key = keys_s[hs];
-      if (FAR && e < 0) {   // (only with far_on) the list of an earlier search of this solve: exact while the query stays close
-        const float4 c0R = far_cq[sq];
-        const unsigned long long kl = far_list_search<FS_HG>(c0R, far_c + GS_FAR_SLOTS * sq, sorted, hx, hy, hz, l16, &done, &win);
-        if (done) { key = kl; listed = true; }
-        else win = -1;
-      }
       if (WL && wl_on) {   // the wide list an earlier launch of this solve left for the point, if any
         const float4 c0R = wl_cq[sq];
         if (c0R.w > 0.0f) {   // (group-uniform)
@@ -753,18 +722,8 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
       GlTop<KH> top;
       float rc2 = 0.0f;
       if (!done) {
-        int kdone = 0;
-        if (LISTS) {
-          key = grid_search_rings_top<FS_HG, KH>(g, cell_start, sorted, hx, hy, hz, l16, key, &done, &win, FS_HARD_RINGS, top, &rc2);
-        }
-        else key = grid_search_rings<FS_HG>(g, cell_start, sorted, hx, hy, hz, l16, key, &done, &win, FS_HARD_RINGS, &kdone);
-        // first halves with a list-building pass behind them (fs_far_pass): queries that needed a cube of radius >=
-        // FS_FAR_MIN_RING are handed to gs_icp_far_build_kernel together with what the search found (squared distance,
-        // radius of the last cube); the ones left to the brute-force pass follow below
-        if (FULL && FAR && far_pass >= 0 && far_on && l16 == 0 && done && kdone >= FS_FAR_MIN_RING) {
-          far_cq[sq] = make_float4(__uint_as_float((uint32_t)(key >> 32)), (float)kdone, 0.0f, 0.0f);
-          q.far_idx[(int64_t)far_pass * n_src + atomicAdd(q.far_n + far_pass, 1)] = (int)sq;
-        }
+        if (LISTS) key = grid_search_rings_top<FS_HG, KH>(g, cell_start, sorted, hx, hy, hz, l16, key, &done, &win, FS_HARD_RINGS, top, &rc2);
+        else key = grid_search_rings<FS_HG>(g, cell_start, sorted, hx, hy, hz, l16, key, &done, &win, FS_HARD_RINGS);
       }
       // (list variants) the scan that served the point leaves its list; what only the brute-force pass can serve keeps none
       if (LISTS && !(WL && listed)) {   // (a point its wide list served keeps what it has: no ordinary list, R < 0)
@@ -777,7 +736,6 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
       if (win >= 0) bslot_s[hs] = win;  // a candidate of the list / the cubes beat the 2x2x2 stage
       if (l16 == 0) {
         keys_s[hs] = key;
-        if (FAR && listed) far_s[hs] = 1;
         if (!done) unres_q[atomicAdd(&unres_n, 1)] = hs;
       }
     }
@@ -803,13 +761,7 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
     }
     if (nun) {
       __syncthreads();
-      if (FULL && FAR && far_pass >= 0 && far_on && (int)threadIdx.x < nun) {   // (see the cube searches above; -1: no cube)
-        const int hs = unres_q[threadIdx.x];
-        const int64_t sq = (int64_t)u0 * FS_QPB + hs;
-        far_cq[sq] = make_float4(__uint_as_float((uint32_t)(keys_s[hs] >> 32)), -1.0f, 0.0f, 0.0f);
-        q.far_idx[(int64_t)far_pass * n_src + atomicAdd(q.far_n + far_pass, 1)] = (int)sq;
-      }
-      __syncthreads();
+      __syncthreads();   // (a second barrier, from when a pass stood between the two: kept with the instruction text, as FS_HQ_SLOT)
       if (threadIdx.x == 0) unres_n = 0;
       __syncthreads();
     }
@@ -828,12 +780,7 @@ GS_DEV void icp_half_body(const IcpHalfSeq& q, const IcpHalfLists& ql, const Icp
         if (tape_idx) tape_idx[s] = -1;
       } else if (live) {
         const unsigned long long bb = keys_s[slot];
-        // NaN bits when nothing was found; with candidate lists the sign bit says "source point s has one"
-        if (d2prev) {
-          uint32_t db = (uint32_t)(bb >> 32);
-          if (far_on) db = (db & 0x7fffffffu) | (far_s[slot] ? 0x80000000u : 0u);
-          d2prev[s] = __uint_as_float(db);
-        }
+        if (d2prev) d2prev[s] = __uint_as_float((uint32_t)(bb >> 32));   // NaN bits when nothing was found
         int64_t j = (int64_t)(bb & 0xffffffffull);
         if (j >= n_tgt) j = 0;  // only when every distance was NaN
         const float d2 = __uint_as_float((uint32_t)(bb >> 32));
@@ -914,9 +861,9 @@ struct IcpHalfBatch {
   unsigned long long* timeline;  // debugging aid (GRADSLAM_HIP_ICP_TIMELINE): per block [start, end, hw id, xcc id]
   IcpHalfSeq s[GS_MAX_BATCH];
   IcpHalfLists l[GS_MAX_BATCH];   // (read by the list variants only)
-  IcpHalfWide w[GS_MAX_BATCH];    // (read in the left-over pass of the variants without far lists only)
+  IcpHalfWide w[GS_MAX_BATCH];    // (read in the left-over pass of the list variants only)
 };
-template <bool FULL, int G, bool FAR, int LMODE>
+template <bool FULL, int G, int LMODE>
 __global__ void __launch_bounds__(FS_BLOCK, 6) gs_icp_half_batch_kernel(const IcpHalfBatch hb, GsCount n_src_c,
                                                                         float dist_thresh, gs_icp_params prm, int it,
                                                                         int rows_in_reduced) {
@@ -926,9 +873,9 @@ __global__ void __launch_bounds__(FS_BLOCK, 6) gs_icp_half_batch_kernel(const Ic
   unsigned long long t0 = 0;
   if (hb.timeline && threadIdx.x == 0) t0 = wall_clock64();
 #endif
-  icp_half_body<FULL, G, FAR, LMODE>(hb.s[blockIdx.x % B], hb.l[blockIdx.x % B], hb.w[blockIdx.x % B], n_src_c, dist_thresh, prm, it, rows_in_reduced,
-                                     gs_xcd_block(blk, nblk, X), hb.upb,
-                                     hb.timeline ? hb.timeline + 72 * (size_t)blockIdx.x : nullptr, hb.weak_room);
+  icp_half_body<FULL, G, LMODE>(hb.s[blockIdx.x % B], hb.l[blockIdx.x % B], hb.w[blockIdx.x % B], n_src_c, dist_thresh, prm, it, rows_in_reduced,
+                                gs_xcd_block(blk, nblk, X), hb.upb,
+                                hb.timeline ? hb.timeline + 72 * (size_t)blockIdx.x : nullptr, hb.weak_room);
 #ifdef GS_ICP_TIMELINE
   if (hb.timeline && threadIdx.x == 0) {
     unsigned long long* r = hb.timeline + 72 * (size_t)blockIdx.x;
@@ -938,24 +885,18 @@ __global__ void __launch_bounds__(FS_BLOCK, 6) gs_icp_half_batch_kernel(const Ic
 #endif
 }
 
-#include "gs_icp_persist.h"
-
 static size_t icp_rows(int64_t n_src) { return (size_t)gs_ceil_div(n_src, FS_QPB); }  // >= ceil(n_src / LIN_BLOCK)
 
-// What the host asks of a device, once per device: its CU count, and whether the persistent solve fits it.  That solve
-// puts a sequence's blocks on ONE XCD of PS_CUS_PER_XCD CUs (gs_icp_persist.h): only a whole gfx950 device qualifies (a
-// partitioned one shows fewer CUs).
-struct IcpDevice { int cus = 256; bool ps_fits = false; };
+// What the host asks of a device, once per device: its CU count.
+struct IcpDevice { int cus = 256; };
 static IcpDevice icp_device() {
   constexpr int MAX_DEV = 64;
   static IcpDevice facts[MAX_DEV]; static std::once_flag asked[MAX_DEV];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return IcpDevice{};
   std::call_once(asked[dev], [dev] {
-    int v = 0; hipDeviceProp_t p;
+    int v = 0;
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) facts[dev].cus = v;
-    facts[dev].ps_fits = hipGetDeviceProperties(&p, dev) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0 &&
-                         p.multiProcessorCount == (int)(GS_XCDS * PS_CUS_PER_XCD);
   });
   return facts[dev];
 }
@@ -970,7 +911,8 @@ static IcpDevice icp_device() {
 // GRADSLAM_HIP_ICP_LANES = 2 | 4 | 8 forces G, GRADSLAM_HIP_ICP_BLOCKS_PER_CU the share (A/B runs: the results do not
 // depend on either).
 struct IcpHalfPlan { int G, nb, upb; };
-static IcpHalfPlan icp_half_plan(const GsEnv& env, int cus, int64_t n_src, int B, int g_max = 8) {
+static IcpHalfPlan icp_half_plan(const GsEnv& env, int cus, int64_t n_src, int B) {
+  constexpr int g_max = 8;   // the most lanes per query a variant exists for
   const int forced = env.icp_lanes;
   const int nunits = (int)icp_rows(n_src);
   int share = env.icp_blocks_per_cu;   // (not set: one block per CU if some G fits that, else two)
@@ -1002,22 +944,18 @@ static void icp_half_launch(const IcpHalfPlan& pl, IcpHalfBatch& hb, GsCount n_s
   hb.upb = pl.upb;
   hb.timeline = icp_tl_arm(FULL, hb.B * pl.nb, it, prm->numiters, st);
   const dim3 grid((unsigned)(hb.B * pl.nb)), block(FS_BLOCK);
-  const bool far = hb.s[0].far_cq != nullptr;   // candidate lists of far queries: the same for all sequences of a batch
-#define GS_HALF_LAUNCH(G_, FAR_, LMODE_)                                                                               \
-  hipLaunchKernelGGL((gs_icp_half_batch_kernel<FULL, G_, FAR_, LMODE_>), grid, block, 0, st, hb, n_src_c,              \
-                     prm->dist_thresh, *prm, it, rows_in_reduced)
+#define GS_HALF_LAUNCH(G_, LMODE_)                                                                                     \
+  hipLaunchKernelGGL((gs_icp_half_batch_kernel<FULL, G_, LMODE_>), grid, block, 0, st, hb, n_src_c, prm->dist_thresh,  \
+                     *prm, it, rows_in_reduced)
 #define GS_HALF_LAUNCH_L(G_)                                                 \
   do {                                                                       \
-    if (lmode == 2) GS_HALF_LAUNCH(G_, false, 2);                            \
-    else if (lmode == 1) GS_HALF_LAUNCH(G_, false, 1);                       \
-    else if (lmode == 3 && G_ == 2) GS_HALF_LAUNCH(2, false, 3);             \
-    else GS_HALF_LAUNCH(G_, false, 0);                                       \
+    if (lmode == 2) GS_HALF_LAUNCH(G_, 2);                                   \
+    else if (lmode == 1) GS_HALF_LAUNCH(G_, 1);                              \
+    else GS_HALF_LAUNCH(G_, 0);                                              \
   } while (0)
-  // (no 8-lane variant with far-candidate lists: its first half does not fit the register budget; icp_engine_plan plans
-  // solves with such lists for at most 4 lanes per query, and a list mode other than 0 only for solves without them)
   if (pl.G == 8) GS_HALF_LAUNCH_L(8);
-  else if (pl.G == 4) { if (far) GS_HALF_LAUNCH(4, true, 0); else GS_HALF_LAUNCH_L(4); }
-  else { if (far) GS_HALF_LAUNCH(2, true, 0); else GS_HALF_LAUNCH_L(2); }
+  else if (pl.G == 4) GS_HALF_LAUNCH_L(4);
+  else GS_HALF_LAUNCH_L(2);
 #undef GS_HALF_LAUNCH_L
 #undef GS_HALF_LAUNCH
   if (hb.timeline && !FULL) icp_tl_dump(hb, pl, lmode, st);   // (synchronous: both launches' block records)
@@ -1049,8 +987,6 @@ struct IcpFinishBatch {
   GsIcpState* st[GS_MAX_BATCH];
   const float* compose16[GS_MAX_BATCH];
   float* out_T16[GS_MAX_BATCH];
-  unsigned* sync[GS_MAX_BATCH];   // sync record of a persistent solve (NULL: none): anything but a complete run = NaN pose
-  int nb, h0;                     // (persistent solve) blocks per sequence, first half-iteration it served
 };
 __global__ void __launch_bounds__(FS_BLOCK) gs_icp_finish_batch_kernel(const IcpFinishBatch fb, GsCount n_src_c, int buf,
                                                                        gs_icp_params prm) {
@@ -1065,16 +1001,6 @@ __global__ void __launch_bounds__(FS_BLOCK) gs_icp_finish_batch_kernel(const Icp
   icp_update_math((float)e1, sm, prm, it < GS_ICP_MAX_ITERS ? st->trace + 12 * it : nullptr);
   st->s[buf ^ 1] = sm;
   icp_write_result(sm, fb.compose16[b], fb.out_T16[b]);
-  // The persistent solve (gs_icp_persist.h) counts as run only if no block gave up waiting (error word), every one of its
-  // nb blocks arrived at every half-iteration it served, and its XCD handed out at least nb tickets: an XCD that got no
-  // block at all raises no error, and its partial rows and state are those of the launch before -- fail loudly instead.
-  if (unsigned* sy = fb.sync[b]) {
-    const unsigned arrived = sy[PS_ARRIVED], want = (unsigned)fb.nb * (unsigned)(2 * prm.numiters - fb.h0);
-    if (!(sy[PS_ERROR] == 0u && arrived == want && sy[PS_TICKET] >= (unsigned)fb.nb))
-      for (int i = 0; i < 16; ++i) fb.out_T16[b][i] = __builtin_nanf("");
-    sy[PS_NB] = (unsigned)fb.nb;   // (diagnostics: gs_localize_solve_stats_i64)
-    sy[PS_H0] = (unsigned)fb.h0;
-  }
 }
 
 // ---------------------------------------------------------------- brute-force path ------
@@ -1202,15 +1128,15 @@ struct GsTake { size_t end = 0; size_t operator()(size_t n) { end += n; return e
 // Scratch of one solve as byte offsets from its start: state | rowred | best | srcA | srcB | partials[2] | grid | spare.
 // The ONE description of it: gs_icp_scratch_bytes returns its total, icp_carve applies it to a base pointer.
 constexpr int ICP_ROWRED_DOUBLES = 32;
-struct IcpLayout { size_t state, rowred, sync, best, srcA, srcB, partials[2], grid, total; };
+constexpr int ICP_WEAK_WORD = 3;   // the weak-list counter: this 32-bit word of the padding behind the one row of rowred
+struct IcpLayout { size_t state, rowred, weak_n, best, srcA, srcB, partials[2], grid, total; };
 static IcpLayout icp_layout(int64_t n_src, int64_t n_tgt) {
   GsTake take;
   IcpLayout L;
   L.state = take(gs_align(sizeof(GsIcpState)));
   L.rowred = take(gs_align(sizeof(double) * ICP_ROWRED_DOUBLES));
-  // the persistent solve's sync record (gs_icp_persist.h: PS_WORDS words) lives in the padding behind the one row
-  L.sync = L.rowred + sizeof(double) * LIN_NV;
-  static_assert(8 * ICP_ROWRED_DOUBLES >= 8 * LIN_NV + 4 * PS_WORDS, "the sync record does not fit behind rowred + LIN_NV");
+  L.weak_n = L.rowred + sizeof(double) * LIN_NV + 4 * ICP_WEAK_WORD;
+  static_assert(8 * ICP_ROWRED_DOUBLES >= 8 * LIN_NV + 4 * (ICP_WEAK_WORD + 1), "the weak-list counter does not fit behind rowred + LIN_NV");
   L.best = take(gs_align(8 * (size_t)n_src));
   L.srcA = take(gs_align(12 * (size_t)n_src)); L.srcB = take(gs_align(12 * (size_t)n_src));
   for (int k = 0; k < 2; ++k) L.partials[k] = take(gs_align(sizeof(double) * LIN_NV * icp_rows(n_src)));
@@ -1221,12 +1147,12 @@ static IcpLayout icp_layout(int64_t n_src, int64_t n_tgt) {
 struct IcpScratch {
   GsIcpState* state;
   double* rowred;  // one partial row (large solves: gs_icp_reduce_rows_batch_kernel)
-  unsigned* sync;  // [PS_WORDS] ticket / arrival / error words of the persistent solve
+  unsigned* weak_n;  // weak lists the list-building launch flagged (GRADSLAM_HIP_ICP_WEAK_ROOM; gs_localize_solve_stats_i64)
   unsigned long long* best; float *srcA, *srcB;
   double* partials[2]; void* grid;
 };
 static IcpScratch icp_carve(void* p, const IcpLayout& L) {
-  return IcpScratch{gs_at<GsIcpState>(p, L.state), gs_at<double>(p, L.rowred), gs_at<unsigned>(p, L.sync),
+  return IcpScratch{gs_at<GsIcpState>(p, L.state), gs_at<double>(p, L.rowred), gs_at<unsigned>(p, L.weak_n),
                     gs_at<unsigned long long>(p, L.best), gs_at<float>(p, L.srcA), gs_at<float>(p, L.srcB),
                     {gs_at<double>(p, L.partials[0]), gs_at<double>(p, L.partials[1])}, gs_at<void>(p, L.grid)};
 }
@@ -1267,10 +1193,9 @@ struct LocSeq {
   float* out_pose16;
   char* clear_ptr;       // grid scratch bytes that must be zero before the build
   int64_t* n_valid;      // number of lattice slots with depth (profiling / roofline accounting)
-  int* far_n;            // [FS_FAR_PASSES] counters of the far-query lists of the solve, zeroed here
   int* lstat;            // [3 * GL_STAT_LAUNCHES] failure counters of the ordinary candidate lists, zeroed here
   float4* wl_cq;         // [n_lat] wide lists of hard queries: every radius cleared here (NULL: none kept)
-  unsigned* sync;        // [PS_WORDS] ticket / arrival / error words of the persistent solve (gs_icp_persist.h), zeroed here
+  unsigned* weak_n;      // the weak-list counter of the solve (IcpScratch::weak_n), zeroed here
 };
 struct LocBatch {
   int B, W, ds, Wl;
@@ -1311,12 +1236,9 @@ GS_DEV void loc_prep_block(const LocBatch& lb, const unsigned bid, const unsigne
       const IcpSmall sm = icp_state_init(id, lb.damp);
       q.state->s[0] = sm;
       q.state->s[1] = sm;
-      if (q.far_n)
-        for (int i = 0; i < FS_FAR_PASSES; ++i) q.far_n[i] = 0;
       if (q.lstat)
         for (int i = 0; i < 3 * GL_STAT_LAUNCHES; ++i) q.lstat[i] = 0;
-      if (q.sync)
-        for (int i = 0; i < PS_WORDS; ++i) q.sync[i] = 0u;
+      if (q.weak_n) *q.weak_n = 0u;
       if (lb.numiters == 0) icp_write_result(sm, q.pose16, q.out_pose16);
     }
     return;
@@ -1355,109 +1277,24 @@ struct ListMem {
                    // is empty (nothing fitted), points the 2x2x2 stage cannot prove (no list)
 };
 
-// candidate lists of far queries (gs_knn.h), behind the lists of the ordinary ones
+// wide lists of hard queries (gs_knn.h), behind the lists of the ordinary ones
 struct FarMem {
   uint32_t* c;    // [n_lat][GS_FAR_SLOTS] slots of `sorted`
-  float4* cq;     // [n_lat] (position the list was built at, exactness radius)
-  int* idx;       // [FS_FAR_PASSES][n_lat] source points handed to the list builder
-  int* n;         // [FS_FAR_PASSES] how many
+  float4* cq;     // [n_lat] (position the list was made at, exactness radius; 0: no list)
 };
-
-// Lists for the source points a first half found far from every target (IcpHalfSeq::far_idx): one launch behind the
-// first halves of iterations 0, 1, 4, 8, ... (fs_far_pass; the step of iteration 0 is the large one of a solve: lists
-// built before it often do not survive it; solves that keep wandering by a millimetre per iteration lose lists later
-// too, and a point without a list pays a cube scan or a pass over all targets in EVERY launch until the next pass).
-// The half-iteration hands over what its search found (far_cq[s] = squared distance, radius of the proving cube or -1),
-// so a group of FS_HG lanes per point only collects everything within R of the point's position (the transformed cloud
-// of the iteration) from that cube; points only the brute-force pass served are finished by the block (one collecting
-// pass over the binned targets, FS_BQ points at a time).  The flag in the sign bit of d2prev[s] tells the following
-// searches that s has a list.
-struct FarBuildSeq {
-  const float* src;         // transformed cloud of the iteration
-  const int* idx;           // the pass's far source points, n[0] of them
-  const int* n;
-  const GsGrid* gp;
-  const int* cell_start;
-  const float4* sorted;
-  float* d2prev;
-  FarMem m;
-};
-struct FarBuildBatch {
-  int B;
-  FarBuildSeq s[GS_MAX_BATCH];
-};
-constexpr int FAR_BLOCK = 512;
-constexpr int FAR_BLOCKS_PER_SEQ = 64;
-__global__ void __launch_bounds__(FAR_BLOCK) gs_icp_far_build_kernel(const FarBuildBatch fb) {
-  const FarBuildSeq& q = fb.s[blockIdx.x % fb.B];
-  const int blk = (int)(blockIdx.x / fb.B);
-  const int n = *q.n;
-  if (blk >= n) return;   // (entry i is served by block i % FAR_BLOCKS_PER_SEQ)
-  constexpr int NG = FAR_BLOCK / FS_HG;
-  __shared__ float qs[NG][3];
-  __shared__ float d1_s[NG];
-  __shared__ uint8_t flag_s[NG];
-  __shared__ int unres_q[NG], sq_s[NG];
-  __shared__ int unres_n;
-  __shared__ uint32_t stage_s[NG][GS_FAR_SLOTS + 4];
-  const GsGrid g = *q.gp;
-  const int grp = threadIdx.x / FS_HG, l16 = threadIdx.x & (FS_HG - 1);
-  // entries of this block: blk, blk + FAR_BLOCKS_PER_SEQ, ...; NG of them per round
-  for (int base = blk; base < n; base += FAR_BLOCKS_PER_SEQ * NG) {   // block-uniform
-    if (threadIdx.x == 0) unres_n = 0;
-    __syncthreads();
-    const int e = base + grp * FAR_BLOCKS_PER_SEQ;
-    if (e < n) {
-      const int sq = q.idx[e];
-      const float hx = q.src[3 * (int64_t)sq], hy = q.src[3 * (int64_t)sq + 1], hz = q.src[3 * (int64_t)sq + 2];
-      // what the search of the half-iteration found for this point: squared distance of its neighbour, radius of the
-      // cube that proved it (-1: the brute-force pass did)
-      const float4 found = q.m.cq[sq];
-      const float d1 = sqrtf(found.x);
-      const int kdone = (int)found.y;
-      if (kdone >= 0) {
-        const float R = far_emit_cube<FS_HG>(g, q.cell_start, q.sorted, hx, hy, hz, l16, d1, kdone, stage_s[grp],
-                                             reinterpret_cast<int*>(&stage_s[grp][GS_FAR_SLOTS]));
-        for (int u = l16; u < GS_FAR_SLOTS; u += FS_HG) q.m.c[GS_FAR_SLOTS * (int64_t)sq + u] = stage_s[grp][u];
-        if (l16 == 0) {
-          q.m.cq[sq] = make_float4(hx, hy, hz, R);
-          if (R > 0.0f) q.d2prev[sq] = __uint_as_float(__float_as_uint(q.d2prev[sq]) | 0x80000000u);
-        }
-      } else if (l16 == 0) {
-        qs[grp][0] = hx; qs[grp][1] = hy; qs[grp][2] = hz;
-        d1_s[grp] = d1;
-        sq_s[grp] = sq;
-        unres_q[atomicAdd(&unres_n, 1)] = grp;
-      }
-    }
-    __syncthreads();
-    const int nun = unres_n;   // block-uniform
-    for (int u = 0; u < nun; u += FS_BQ) {
-      const int nq = nun - u < FS_BQ ? nun - u : FS_BQ;
-      block_brute_collect_multi<FAR_BLOCK, FS_BQ>(qs, unres_q + u, nq, q.sorted, q.cell_start[g.ncell], d1_s,
-                                                  GS_FAR_RADD * g.c, sq_s, q.m.cq, q.m.c, flag_s);
-      if ((int)threadIdx.x < nq) {
-        const int gq = unres_q[u + threadIdx.x];
-        const int s2 = sq_s[gq];
-        if (flag_s[gq]) q.d2prev[s2] = __uint_as_float(__float_as_uint(q.d2prev[s2]) | 0x80000000u);
-      }
-    }
-    __syncthreads();
-  }
-}
 
 static int64_t loc_rows(const gs_map_view& m) { return m.capacity > m.n_bound ? m.capacity : m.n_bound; }
 
 // Scratch of one sequence of the batched localisation as byte offsets from its start: lattice | n_valid | the solve's
-// scratch (IcpLayout sc, counted from `icp`; it holds the grid) | lists of ordinary queries (ListMem) | lists of far queries,
-// or the wide lists of hard ones (FarMem) + result words.  The ONE description of it: gs_localize_scratch_bytes returns its
+// scratch (IcpLayout sc, counted from `icp`; it holds the grid) | lists of ordinary queries (ListMem) | wide lists of hard
+// queries (FarMem).  The ONE description of it: gs_localize_scratch_bytes returns its
 // total, loc_carve applies it to a base pointer.  `rows` is the map's CAPACITY (what the scratch was sized for), not the count
 // bound of a frame: every pointer then stays where it is from frame to frame while the map grows (the fast path keeps one
 // scratch per sequence and checks buffer identity), and the stats exporters, given the capacity, find what the solve left.
 struct LocLayout {
   int64_t n_lat, rows;
   IcpLayout sc;
-  size_t lattice, n_valid, icp, lq, ls, lstat, far_c, far_cq, far_idx, far_n, far_out4, total;
+  size_t lattice, n_valid, icp, lq, ls, lstat, far_c, far_cq, total;
 };
 static LocLayout loc_layout(int64_t n_lat, int64_t rows) {
   GsTake take;
@@ -1472,10 +1309,6 @@ static LocLayout loc_layout(int64_t n_lat, int64_t rows) {
   L.lstat = take(gs_align(4 * 3 * GL_STAT_LAUNCHES));
   L.far_c = take(gs_align(4 * GS_FAR_SLOTS * (size_t)n_lat));
   L.far_cq = take(gs_align(16 * (size_t)n_lat));
-  L.far_idx = take(gs_align(4 * FS_FAR_PASSES * (size_t)n_lat));
-  L.far_n = take(256);   // the FS_FAR_PASSES counters and, behind them, the 4 result words of gs_localize_far_stats_i64
-  L.far_out4 = L.far_n + 4 * 8;
-  static_assert(FS_FAR_PASSES <= 8, "the far-list counters run into the result words");
   L.total = take.end;
   return L;
 }
@@ -1492,16 +1325,14 @@ extern "C" int64_t gs_localize_scratch_bytes(int H, int W, int ds, int64_t n_map
 
 struct LocCarve {
   float* lattice; int64_t* n_valid;
-  IcpScratch sc; GridMem gm; ListMem lm;
-  FarMem fm; int* far_out4;   // the far lists, or the wide lists whenever those are not in use; the stats result words
+  IcpScratch sc; GridMem gm; ListMem lm; FarMem fm;
 };
 static LocCarve loc_carve(void* p, const LocLayout& L) {
   const IcpScratch sc = icp_carve(gs_at<char>(p, L.icp), L.sc);
   return LocCarve{gs_at<float>(p, L.lattice), gs_at<int64_t>(p, L.n_valid), sc,
                   grid_carve(sc.grid, L.n_lat, L.rows),
                   ListMem{gs_at<float4>(p, L.lq), gs_at<uint32_t>(p, L.ls), gs_at<int>(p, L.lstat)},
-                  FarMem{gs_at<uint32_t>(p, L.far_c), gs_at<float4>(p, L.far_cq), gs_at<int>(p, L.far_idx), gs_at<int>(p, L.far_n)},
-                  gs_at<int>(p, L.far_out4)};
+                  FarMem{gs_at<uint32_t>(p, L.far_c), gs_at<float4>(p, L.far_cq)}};
 }
 // (the stats exporters and the one-call step: the scratch of a solve of HxW images at dsratio ds against map_rows rows)
 static LocCarve loc_carve_of(const void* scratch, int H, int W, int ds, int64_t map_rows) {
@@ -1510,22 +1341,17 @@ static LocCarve loc_carve_of(const void* scratch, int H, int W, int ds, int64_t 
 
 // Which engines a batched solve runs, decided ONCE, before its first launch (icp_engine_plan: no HIP call in there).
 struct IcpEnginePlan {
-  // candidate lists of far queries (opt-in; instead of the ordinary ones) / wide lists of hard queries, in the memory of the
-  // far lists / candidate lists of ordinary queries / the half-iterations from ps_it0 on as ONE launch (gs_icp_persist.h)
-  bool far_on, wide_on, lists_on, persist_on;
+  bool wide_on, lists_on;   // wide lists of hard queries / candidate lists of ordinary queries
   bool binned_normals;  // the matches' normals come from the binned copy, not from the map
   bool reduce_rows;     // large solves: one extra launch per iteration adds the rows up once (FS_REDUCE_ROWS)
   int lists_from;       // the lists are built behind the look-ahead search of this iteration, tried from the next on
   IcpHalfPlan half;     // geometry of the half-iteration launches
-  int ps_it0, ps_nb, ps_upb;   // persistent launch: first iteration it serves (numiters: none), blocks per sequence, units per block
   float weak_room;
-  // what a launch does with the ordinary lists (icp_half_body: LMODE): 0 nothing, 1 build 4-entry lists, 2 try them,
-  // 3 build the 8-entry lists the persistent kernel takes over (it keeps the four nearest of a list in registers and falls
-  // back on the other four, lane by lane, before anything is re-searched)
+  // what a launch does with the ordinary lists (icp_half_body: LMODE): 0 nothing, 1 build them, 2 try them
   int lmode(int it, bool look_ahead) const {
     if (!lists_on || it < lists_from) return 0;
     if (it > lists_from) return 2;
-    return look_ahead ? (persist_on ? 3 : 1) : 0;
+    return look_ahead ? 1 : 0;
   }
 };
 static IcpEnginePlan icp_engine_plan(const GsEnv& env, const IcpDevice& dev, int B, int64_t n_lat, int numiters,
@@ -1535,33 +1361,18 @@ static IcpEnginePlan icp_engine_plan(const GsEnv& env, const IcpDevice& dev, int
   p.binned_normals = env.icp_binned_normals; p.weak_room = env.icp_weak_room;
   p.lists_from = env.icp_lists_from >= 0 ? env.icp_lists_from : FS_LISTS_FROM;
   p.reduce_rows = rows > FS_REDUCE_ROWS;
-  p.far_on = env.icp_far && numiters > 0;
-  p.wide_on = env.icp_wide && !p.far_on && numiters > 0;
-  // The persistent solve: a sequence's source points must fit the 32 CUs of one XCD at 672 per block (640x480 at dsratio 4:
-  // 200 row units -> 29 blocks of 7, as few as the CUs allow, equally loaded), it reads the ordinary lists and the binned
-  // normals, and an iteration must be left for it behind the list-building look-ahead (the earliest start won: 4-entry lists
-  // and a start at 2 / 5 / 7 / 9 / 12 gave 7 924 / 7 857 / 7 872 / 7 816 / 7 763 frames/s against 7 623 without).
-  p.ps_upb = (int)gs_ceil_div(rows, PS_CUS_PER_XCD);
-  p.ps_nb = (int)gs_ceil_div(rows, p.ps_upb > 0 ? p.ps_upb : 1);
-  const bool persist_asked = env.icp_persist && env.icp_lists && !p.far_on && B <= (int)GS_XCDS && p.ps_upb <= PS_UPB &&
-                             numiters > p.lists_from + 1 && !env.icp_timeline && !env.icp_lanes_set && dev.ps_fits &&
-                             p.binned_normals;
-  // The launches in front of the persistent one run at 2 lanes per point (it reads the 4-entry lists two lanes write); far
-  // lists have no 8-lane variant.  QUIRK, kept: the cap of 2 follows what was ASKED for -- a solve whose persistent launch
-  // is ruled out below (no lists after all) still runs at 2 lanes.  Lifting it changes the speed of an opt-in path.
-  p.half = icp_half_plan(env, dev.cus, n_lat, B, p.far_on ? 4 : (persist_asked ? 2 : 8));
+  p.wide_on = env.icp_wide && numiters > 0;
+  p.half = icp_half_plan(env, dev.cus, n_lat, B);
   // (a block reads the lists of ONE group of row units: solves whose blocks walk several groups keep none)
-  p.lists_on = env.icp_lists && !p.far_on && p.half.upb * p.half.G * FS_QPB <= FS_BLOCK;
+  p.lists_on = env.icp_lists && p.half.upb * p.half.G * FS_QPB <= FS_BLOCK;
   for (int b = 0; b < B && p.lists_on; ++b) p.lists_on = loc_lists_fit(layouts[b]);
-  p.persist_on = persist_asked && p.half.G == 2 && p.lists_on;
-  p.ps_it0 = p.persist_on ? p.lists_from + 1 : numiters;
   return p;
 }
-// the plan of a solve with every engine off (the single solve): numiters iterations of two plain launches each
-static IcpEnginePlan icp_plain_plan(const IcpHalfPlan& half, int64_t n_src, int numiters) {
-  IcpEnginePlan p{};   // (no lists of any kind, no persistent launch, no weak room)
+// the plan of a solve with every engine off (the single solve): two plain launches per iteration
+static IcpEnginePlan icp_plain_plan(const IcpHalfPlan& half, int64_t n_src) {
+  IcpEnginePlan p{};   // (no lists of any kind, no weak room)
   p.binned_normals = true; p.reduce_rows = icp_rows(n_src) > FS_REDUCE_ROWS;
-  p.half = half; p.ps_it0 = numiters;
+  p.half = half;
   return p;
 }
 
@@ -1573,12 +1384,11 @@ struct IcpSolveView {
   IcpScratch sc; GridMem gm;
   int64_t* out_idx;                      // (optional) match of every source point in the last iteration
   TapePtrs tape;                         // (optional) forward tape
-  IcpHalfLists lists; IcpHalfWide wide; FarMem far;   // (optional) candidate lists: ordinary, wide, far
+  IcpHalfLists lists; IcpHalfWide wide;   // (optional) candidate lists: ordinary, wide
   const float* compose16; float* out_T16;
-  unsigned* sync;                        // (optional) sync record of a persistent solve, checked by the finish
 };
 
-// ---- the steps of a chunk: bind, prep + grid build, half-iterations, persistent launch, finish (c[b]: the carved scratch
+// ---- the steps of a chunk: bind, prep + grid build, half-iterations, finish (c[b]: the carved scratch
 // of sequence b, v[b]: the view of its solve)
 static void loc_bind(const gs_localize_seq* seqs, int B, int H, int W, int ds, const gs_icp_params* prm,
                      const IcpEnginePlan& plan, LocCarve* c, LocBatch& lb, GsGridBatch& gb, IcpSolveView* v) {
@@ -1589,19 +1399,18 @@ static void loc_bind(const gs_localize_seq* seqs, int B, int H, int W, int ds, c
   for (int b = 0; b < B; ++b) {
     const gs_localize_seq& q = seqs[b];
     if (!plan.binned_normals) c[b].gm.sorted_n = nullptr;
-    // (the prep launch zeroes the counters of the far and of the ordinary lists whether or not this solve keeps such lists)
+    // (the prep launch zeroes the counters of the ordinary lists whether or not this solve keeps such lists)
     lb.s[b] = LocSeq{q.vertex, q.depth, q.prev_pose16, c[b].lattice, c[b].sc.state, q.out_pose16,
-                     reinterpret_cast<char*>(c[b].gm.g), c[b].n_valid, c[b].fm.n, c[b].lm.stat,
-                     plan.wide_on ? c[b].fm.cq : nullptr, c[b].sc.sync};
+                     reinterpret_cast<char*>(c[b].gm.g), c[b].n_valid, c[b].lm.stat,
+                     plan.wide_on ? c[b].fm.cq : nullptr, c[b].sc.weak_n};
     gb.s[b] = GsGridSeq{q.map.points, GsCount{q.map.n_bound, q.map.n_dev}, nullptr, q.prev_pose16, q.K16,
                         plan.binned_normals ? q.map.normals : nullptr, c[b].gm};
     v[b] = IcpSolveView{c[b].lattice, q.map.points, q.map.normals, GsCount{q.map.n_bound, q.map.n_dev}, c[b].sc, c[b].gm,
                         nullptr, TapePtrs{nullptr, nullptr, nullptr},
-                        plan.lists_on ? IcpHalfLists{c[b].lm.lq, c[b].lm.ls, c[b].lm.stat, c[b].sc.sync + PS_WEAK}
+                        plan.lists_on ? IcpHalfLists{c[b].lm.lq, c[b].lm.ls, c[b].lm.stat, c[b].sc.weak_n}
                                       : IcpHalfLists{nullptr, nullptr, nullptr, nullptr},
                         plan.wide_on ? IcpHalfWide{c[b].fm.cq, c[b].fm.c} : IcpHalfWide{nullptr, nullptr},
-                        plan.far_on ? c[b].fm : FarMem{nullptr, nullptr, nullptr, nullptr},
-                        q.prev_pose16, q.out_pose16, plan.persist_on ? c[b].sc.sync : nullptr};
+                        q.prev_pose16, q.out_pose16};
   }
   lb.count_valid = g_gs_prof_on ? 1 : 0;
   lb.clear_bytes = gs_knn_grid_clear_bytes(c[0].gm, gb.cells_cap);  // same layout offsets for every sequence
@@ -1667,7 +1476,7 @@ static int32_t* icp_tape_idx(const IcpSolveView& v, int it, int look_ahead, int6
   return v.tape.idx ? v.tape.idx + ((size_t)it * 2 + look_ahead) * (size_t)n_src : nullptr;
 }
 
-// iterations [0, plan.ps_it0) of B solves: two launches each (+ the far-list builder, + the row sums of large solves)
+// every iteration of B solves: two launches each (+ the row sums of large solves)
 // prof_rows: the row sums get a profile record of their own (the single solve)
 static void loc_half_iterations(const IcpSolveView* v, int B, const IcpEnginePlan& plan, GsCount n_src_c,
                                 const gs_icp_params* prm, hipStream_t st, bool prof_rows) {
@@ -1675,7 +1484,7 @@ static void loc_half_iterations(const IcpSolveView* v, int B, const IcpEnginePla
   IcpHalfBatch hb;
   hb.B = B; hb.weak_room = plan.weak_room;
   for (int b = 0; b < B; ++b) { hb.w[b] = v[b].wide; hb.l[b] = v[b].lists; }
-  for (int it = 0; it < plan.ps_it0; ++it) {
+  for (int it = 0; it < prm->numiters; ++it) {
     int h = 2 * it;
     for (int b = 0; b < B; ++b) {
       const IcpSolveView& q = v[b];
@@ -1683,17 +1492,9 @@ static void loc_half_iterations(const IcpSolveView* v, int B, const IcpEnginePla
       hb.s[b] = IcpHalfSeq{it == 0 ? q.src0 : icp_cloud(q, it - 1, n_src), icp_cloud(q, it, n_src), q.tgt, q.tn, q.n_tgt, q.gm.g,
                            q.gm.cell_start, q.gm.sorted, q.gm.sorted_n, reinterpret_cast<float*>(q.sc.best),
                            io.rows_in, io.rows_out, io.st_in, io.st_out, q.sc.state->trace, q.out_idx,
-                           icp_tape_idx(q, it, 0, n_src), nullptr, q.far.cq, q.far.c, q.far.idx, q.far.n};
+                           icp_tape_idx(q, it, 0, n_src), nullptr};
     }
     icp_half_launch<true>(plan.half, hb, n_src_c, prm, it, 0, st, plan.lmode(it, false));
-    if (plan.far_on && fs_far_pass(it) >= 0) {   // lists for the far source points this search found
-      const int fp = fs_far_pass(it);
-      FarBuildBatch fbb; fbb.B = B;
-      for (int b = 0; b < B; ++b)
-        fbb.s[b] = FarBuildSeq{icp_cloud(v[b], it, n_src), v[b].far.idx + (int64_t)fp * n_src, v[b].far.n + fp,
-                               v[b].gm.g, v[b].gm.cell_start, v[b].gm.sorted, reinterpret_cast<float*>(v[b].sc.best), v[b].far};
-      hipLaunchKernelGGL(gs_icp_far_build_kernel, dim3((unsigned)B * FAR_BLOCKS_PER_SEQ), dim3(FAR_BLOCK), 0, st, fbb);
-    }
     ++h;
     if (plan.reduce_rows) {
       std::optional<GsProf> prof;
@@ -1715,37 +1516,15 @@ static void loc_half_iterations(const IcpSolveView* v, int B, const IcpEnginePla
   }
 }
 
-// iterations [plan.ps_it0, numiters) as ONE launch: it takes over behind the list-building look-ahead (LMODE 3)
-static void loc_persist(const IcpSolveView* v, int B, const IcpEnginePlan& plan, int64_t n_lat, const gs_icp_params* prm,
-                        hipStream_t st) {
-  IcpPersistBatch pb;
-  pb.B = B; pb.nb = plan.ps_nb; pb.upb = plan.ps_upb; pb.h0 = 2 * plan.ps_it0; pb.tl_h = 0; pb.timeline = nullptr;
-  for (int b = 0; b < B; ++b) {
-    const IcpSolveView& q = v[b];
-    const IcpScratch& sc = q.sc; const GridMem& gm = q.gm;
-    pb.s[b] = IcpPersistSeq{icp_cloud(q, plan.ps_it0 - 1, n_lat), q.n_tgt, gm.g, gm.cell_start,
-                            gm.sorted, gm.sorted_n, {sc.partials[0], sc.partials[1]}, sc.state, q.lists.lq, q.lists.ls,
-                            q.lists.lstat, q.wide.cq, q.wide.c, sc.sync};
-  }
-#ifdef GS_ICP_TIMELINE
-  ps_tl_arm(pb, prm->numiters, st);
-#endif
-  hipLaunchKernelGGL(gs_icp_persist_kernel, dim3(GS_XCDS * PS_CUS_PER_XCD), dim3(PS_BLOCK), 0, st, pb, n_lat, prm->dist_thresh, *prm);
-#ifdef GS_ICP_TIMELINE
-  ps_tl_dump(pb, st);
-#endif
-}
-
-// final LM / gradLM update and the composed result; a persistent solve that did not run completely leaves a NaN pose
-static void loc_finish(const IcpSolveView* v, int B, const IcpEnginePlan& plan, GsCount n_src_c, const gs_icp_params* prm,
-                       hipStream_t st) {
+// final LM / gradLM update and the composed result
+static void loc_finish(const IcpSolveView* v, int B, GsCount n_src_c, const gs_icp_params* prm, hipStream_t st) {
   const int h = 2 * prm->numiters;
   GsProf prof(GS_PROF_SOLVE, 1.0, st);
   IcpFinishBatch fb;
-  fb.B = B; fb.nb = plan.persist_on ? plan.ps_nb : 0; fb.h0 = plan.persist_on ? 2 * plan.ps_it0 : 0;
+  fb.B = B;
   for (int b = 0; b < B; ++b) {
     fb.partials_in[b] = icp_half_io(v[b].sc, h).rows_in;
-    fb.st[b] = v[b].sc.state; fb.compose16[b] = v[b].compose16; fb.out_T16[b] = v[b].out_T16; fb.sync[b] = v[b].sync;
+    fb.st[b] = v[b].sc.state; fb.compose16[b] = v[b].compose16; fb.out_T16[b] = v[b].out_T16;
   }
   hipLaunchKernelGGL(gs_icp_finish_batch_kernel, dim3((unsigned)B), dim3(FS_BLOCK), 0, st, fb, n_src_c, h & 1, *prm);   // (reads s[h & 1])
 }
@@ -1775,10 +1554,9 @@ static int icp_run(const float* src, int64_t n_src, const float* tgt, const floa
     GsIcpTape t = gs_icp_tape_carve(tape, n_src, prm->numiters);
     tp.src = t.src; tp.idx = t.idx; tp.sys = t.sys;
   }
-  // the solve as the shared driver sees it: one sequence, no candidate lists, no sync record
+  // the solve as the shared driver sees it: one sequence, no candidate lists
   const IcpSolveView v{src, tgt, tgt_normals, n_tgt_c, sc, grid_carve(sc.grid, n_src, n_tgt), out_idx, tp,
-                       IcpHalfLists{nullptr, nullptr, nullptr, nullptr}, IcpHalfWide{nullptr, nullptr},
-                       FarMem{nullptr, nullptr, nullptr, nullptr}, compose16, out_T16, nullptr};
+                       IcpHalfLists{nullptr, nullptr, nullptr, nullptr}, IcpHalfWide{nullptr, nullptr}, compose16, out_T16};
   auto cloud = [&](int it) { return icp_cloud(v, it, n_src); };
   auto tidx = [&](int it, int which) { return icp_tape_idx(v, it, which, n_src); };
 
@@ -1800,12 +1578,12 @@ static int icp_run(const float* src, int64_t n_src, const float* tgt, const floa
       prof_bytes = icp_alg_bytes(prm->numiters, n_src, n_src, n_binned);
     }
     // the B = 1, engines-off client of the batched driver
-    const IcpEnginePlan plan = icp_plain_plan(icp_half_plan(gs_env(), icp_device().cus, n_src, 1), n_src, prm->numiters);
+    const IcpEnginePlan plan = icp_plain_plan(icp_half_plan(gs_env(), icp_device().cus, n_src, 1), n_src);
     {
       GsProf prof(GS_PROF_ICP_FUSED, prof_bytes, st, 2 * prm->numiters);
       loc_half_iterations(&v, 1, plan, n_src_c, prm, st, true);
     }   // closing event right behind the last half-iteration kernel
-    loc_finish(&v, 1, plan, n_src_c, prm, st);
+    loc_finish(&v, 1, n_src_c, prm, st);
     GS_LAUNCH_CHECK();
     if (tape) return icp_tape_finish(tape, sc.state, n_src, prm->numiters, st);
     return GS_OK;
@@ -1894,9 +1672,8 @@ static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int 
   {
     GsProf prof(GS_PROF_ICP_FUSED, prof_bytes, st, 2 * prm->numiters);
     loc_half_iterations(v, B, plan, GsCount{n_lat, nullptr}, prm, st, false);
-    if (plan.persist_on) loc_persist(v, B, plan, n_lat, prm, st);
   }
-  loc_finish(v, B, plan, GsCount{n_lat, nullptr}, prm, st);
+  loc_finish(v, B, GsCount{n_lat, nullptr}, prm, st);
   GS_LAUNCH_CHECK();
   return GS_OK;
 }
@@ -1926,53 +1703,21 @@ extern "C" int gs_localize_batch_f32(const gs_localize_seq* seqs_host, int B, in
   return localize_batch(seqs_host, B, H, W, ds, prm, stream, false);
 }
 
-__global__ void __launch_bounds__(256) gs_far_stats_kernel(const int* __restrict__ far_idx, const int* __restrict__ far_n,
-                                                          const float* __restrict__ d2prev, const float4* __restrict__ far_cq,
-                                                          int64_t n_lat, int* __restrict__ out4) {
-  // (the first pass: what the first search of the solve found; clamped: a scratch no solve has used holds anything)
-  const int n0 = far_n[0], n = n0 < 0 ? 0 : (n0 > (int)n_lat ? (int)n_lat : n0);
-  if (blockIdx.x == 0 && threadIdx.x == 0) { out4[0] = n; out4[2] = far_n[1]; }
-  int c = 0, built = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const int s = far_idx[i];
-    if (s < 0 || s >= (int)n_lat) continue;
-    c += (__float_as_uint(d2prev[s]) >> 31) ? 1 : 0;
-    built += far_cq[s].w > 0.0f ? 1 : 0;
-  }
-  if (c) atomicAdd(&out4[1], c);
-  if (built) atomicAdd(&out4[3], built);
-}
-extern "C" int gs_localize_far_stats_i64(const void* scratch, int H, int W, int ds, int64_t map_rows, int64_t* out4_host,
-                                         void* stream) {
-  GS_REQUIRE(scratch && out4_host && H > 0 && W > 0 && ds > 0 && map_rows > 0, "bad arguments");
-  const int64_t n_lat = loc_lattice(H, W, ds);
-  const LocCarve cv = loc_carve_of(scratch, H, W, ds, map_rows);
-  const FarMem& fm = cv.fm; hipStream_t st = gs_stream(stream);
-  int* out4 = cv.far_out4;   // (behind the counters, in the 256 bytes reserved for them)
-  GS_HIP(hipMemsetAsync(out4, 0, 16, st));
-  hipLaunchKernelGGL(gs_far_stats_kernel, dim3(64), dim3(256), 0, st, fm.idx, fm.n, reinterpret_cast<const float*>(cv.sc.best),
-                     fm.cq, n_lat, out4);
-  int h[4] = {0, 0, 0, 0};
-  GsGrid g;
-  GS_HIP(hipMemcpyAsync(h, out4, 16, hipMemcpyDeviceToHost, st));
-  GS_HIP(hipMemcpyAsync(&g, cv.gm.g, sizeof(g), hipMemcpyDeviceToHost, st));
-  GS_HIP(hipStreamSynchronize(st));
-  for (int i = 0; i < 4; ++i) out4_host[i] = h[i];
-  if (gs_env().debug_grid)
-    fprintf(stderr, "grid: box (%.3f %.3f %.3f)-(%.3f %.3f %.3f) c %.4f cells %d x %d x %d = %d\n", g.ox, g.oy, g.oz, g.mx,
-            g.my, g.mz, g.c, g.nx, g.ny, g.nz, g.ncell);
-  return GS_OK;
-}
-
 extern "C" int gs_localize_list_stats_i64(const void* scratch, int H, int W, int ds, int64_t map_rows, int64_t* out192_host,
                                           void* stream) {
   GS_REQUIRE(scratch && out192_host && H > 0 && W > 0 && ds > 0 && map_rows > 0, "bad arguments");
-  const ListMem lm = loc_carve_of(scratch, H, W, ds, map_rows).lm;
+  const LocCarve cv = loc_carve_of(scratch, H, W, ds, map_rows);
   int h[3 * GL_STAT_LAUNCHES];
   hipStream_t st = gs_stream(stream);
-  GS_HIP(hipMemcpyAsync(h, lm.stat, sizeof(h), hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(h, cv.lm.stat, sizeof(h), hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   for (int i = 0; i < 3 * GL_STAT_LAUNCHES; ++i) out192_host[i] = h[i];
+  if (gs_env().debug_grid) {
+    GsGrid g;
+    GS_HIP(hipMemcpy(&g, cv.gm.g, sizeof(g), hipMemcpyDeviceToHost));
+    fprintf(stderr, "grid: box (%.3f %.3f %.3f)-(%.3f %.3f %.3f) c %.4f cells %d x %d x %d = %d\n", g.ox, g.oy, g.oz, g.mx,
+            g.my, g.mz, g.c, g.nx, g.ny, g.nz, g.ncell);
+  }
   return GS_OK;
 }
 
@@ -1980,12 +1725,11 @@ extern "C" int gs_localize_solve_stats_i64(const void* scratch, int H, int W, in
                                            void* stream) {
   GS_REQUIRE(scratch && out8_host && H > 0 && W > 0 && ds > 0 && map_rows > 0, "bad arguments");
   const LocCarve cv = loc_carve_of(scratch, H, W, ds, map_rows);
-  unsigned h[PS_WORDS];
+  unsigned weak = 0;
   hipStream_t st = gs_stream(stream);
-  GS_HIP(hipMemcpyAsync(h, cv.sc.sync, sizeof(h), hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(&weak, cv.sc.weak_n, sizeof(weak), hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
-  static_assert(PS_WORDS == 8, "out8");
-  for (int i = 0; i < PS_WORDS; ++i) out8_host[i] = h[i];
+  for (int i = 0; i < 8; ++i) out8_host[i] = i == ICP_WEAK_WORD ? (int64_t)weak : 0;
   return GS_OK;
 }
 

@@ -2,7 +2,7 @@
 // the per-block time stamps the kernels record in a library built with -DGS_ICP_TIMELINE.
 #pragma once
 
-// ---- the launch-per-half-iteration path (tools/icp_timeline.py): per-block time stamps of ONE iteration's two launches
+// tools/icp_timeline.py: per-block time stamps of ONE iteration's two launches
 // (GRADSLAM_HIP_ICP_TIMELINE_IT; default: the last), the first half into <path>, the look-ahead that follows it back to
 // back into <path>.next (their first block starts are one launch period apart); both are written after the second launch.
 constexpr size_t ICP_TL_HALF = 72 * 7000;   // words per launch: 72 per block
@@ -35,39 +35,3 @@ static void icp_tl_dump(const IcpHalfBatch& hb, const IcpHalfPlan& pl, int lmode
     fclose(f);
   }
 }
-
-#ifdef GS_ICP_TIMELINE
-// ---- the persistent solve (GRADSLAM_HIP_ICP_PERSIST_TIMELINE=<path>; tools/icp_persist_timeline.py): per block, the
-// phase stamps of ONE iteration's two half-iterations
-constexpr size_t PS_TL_WORDS = 72 * (size_t)GS_XCDS * PS_CUS_PER_XCD;
-static unsigned long long* g_ps_tl_buf = nullptr;
-// in front of the persistent launch: sets pb.timeline / pb.tl_h
-static void ps_tl_arm(IcpPersistBatch& pb, int numiters, hipStream_t st) {
-  if (!gs_env().icp_persist_timeline) return;
-  if (!g_ps_tl_buf && hipMalloc(&g_ps_tl_buf, 8 * PS_TL_WORDS) != hipSuccess) g_ps_tl_buf = nullptr;
-  if (!g_ps_tl_buf) return;
-  (void)hipMemsetAsync(g_ps_tl_buf, 0, 8 * PS_TL_WORDS, st);
-  pb.timeline = g_ps_tl_buf;
-  pb.tl_h = 2 * gs_env().timeline_it(numiters);
-}
-// behind it: synchronous dump
-static void ps_tl_dump(const IcpPersistBatch& pb, hipStream_t st) {
-  if (!pb.timeline) return;
-  std::unique_ptr<unsigned long long[]> hbuf(new unsigned long long[PS_TL_WORDS]);
-  if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(hbuf.get(), g_ps_tl_buf, 8 * PS_TL_WORDS, hipMemcpyDeviceToHost) != hipSuccess) return;
-  FILE* f = fopen(gs_env().icp_persist_timeline, "w");
-  if (!f) return;
-  fprintf(f, "# B=%d nb=%d upb=%d h0=%d tl_h=%d: per block: xcc lb end | first half: wait_done sums scalar check rare arrived at_barrier research hard brute - - | look-ahead: the same | start releases... (100 MHz ticks)\n",
-          pb.B, pb.nb, pb.upb, pb.h0, pb.tl_h);
-  for (size_t i = 0; i < PS_TL_WORDS / 72; ++i) {
-    const unsigned long long* r = hbuf.get() + 72 * i;
-    if (!r[0]) continue;
-    fprintf(f, "%llu %llu %llu |", r[1], r[2], r[3]);
-    for (int k = 8; k < 32; ++k) fprintf(f, " %llu%s", r[k], k == 19 ? " |" : "");
-    fprintf(f, " | %llu", r[4]);   // block start, then the release time of every half-iteration, then the end
-    for (int k = 32; k < 72; ++k) fprintf(f, " %llu", r[k]);
-    fprintf(f, "\n");
-  }
-  fclose(f);
-}
-#endif

@@ -751,19 +751,6 @@ def localize_batch(vertex, depth, K, prev_poses, maps, ds, mode=1, numiters=20, 
     return T
 
 
-def localize_far_stats(device, b, H, W, ds, capacity):
-    """Diagnostics of the last localisation of sequence b on `device` (gs_localize_far_stats_i64): (source points the
-    first search found far from every target, how many of them ended the solve with a proven candidate list, source
-    points of the second list-building pass, how many of the first have a list that fits)."""
-    L = lib()
-    scratch = Workspace.get(device).bytes("localize%d" % b, L.gs_localize_scratch_bytes(H, W, int(ds), int(capacity)))
-    import ctypes
-    out = (ctypes.c_int64 * 4)()
-    check(L.gs_localize_far_stats_i64(scratch.data_ptr(), H, W, int(ds), int(capacity), out, stream(device)),
-          "gs_localize_far_stats_i64")
-    return tuple(int(v) for v in out)
-
-
 def localize_list_stats(device, b, H, W, ds, capacity):
     """Diagnostics of the candidate lists of ordinary source points in the last localisation of sequence b on `device`
     (gs_localize_list_stats_i64): (failed[64], empty_list[64], without_list[64]) per launch of the solve (launch = 2 x
@@ -779,17 +766,15 @@ def localize_list_stats(device, b, H, W, ds, capacity):
 
 
 def localize_solve_stats(device, b, H, W, ds, capacity):
-    """Diagnostics of the sync record of the last localisation of sequence b on `device` (gs_localize_solve_stats_i64):
-    dict(ticket, arrived, error, weak, nb, h0).  ticket / arrived / error: the persistent solve's words (arrived =
-    nb x (2 numiters - h0) when it ran to its end); nb / h0: its blocks per sequence and first half-iteration (0 / 0: the
-    solve ran without it); weak: lists the list-building launch flagged as weak (GRADSLAM_HIP_ICP_WEAK_ROOM > 0)."""
+    """Diagnostics of the last localisation of sequence b on `device` (gs_localize_solve_stats_i64): {"weak": lists the
+    list-building launch flagged as weak (GRADSLAM_HIP_ICP_WEAK_ROOM > 0)}."""
     L = lib()
     scratch = Workspace.get(device).bytes("localize%d" % b, L.gs_localize_scratch_bytes(H, W, int(ds), int(capacity)))
     import ctypes
     out = (ctypes.c_int64 * 8)()
     check(L.gs_localize_solve_stats_i64(scratch.data_ptr(), H, W, int(ds), int(capacity), out, stream(device)),
           "gs_localize_solve_stats_i64")
-    return dict(zip(("ticket", "arrived", "error", "weak", "nb", "h0"), (int(x) for x in out[:6])))
+    return {"weak": int(out[3])}
 
 
 def update_map_fusion_batch_(maps, vertex, normal, depth, rgb, alpha, poses, K, dist_th, dot_th, renorm_all=True,

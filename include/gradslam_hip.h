@@ -460,7 +460,7 @@ GS_API int gs_frame_maps_batch_f32(const float* depth, int64_t depth_stride_seq,
  * (the transform gs_icp_map_dc_f32 returns).  scratch: gs_localize_scratch_bytes(H, W, ds, rows) bytes per sequence
  * with rows = max(map.capacity, map.n_bound): the layout follows the CAPACITY of the map buffers, so that it does not
  * move from frame to frame while the map grows inside them (after the call the scratch holds the solver state / trace
- * at the offset gs_icp_trace_f32 expects, the projection table and the candidate lists of far queries). */
+ * at the offset gs_icp_trace_f32 expects, the binned targets and the candidate lists of the solve). */
 typedef struct gs_localize_seq {
   const float* vertex;      /* live frame, LOCAL vertex map (H, W, 3) */
   const float* depth;       /* live frame depth (H, W) */
@@ -473,29 +473,21 @@ typedef struct gs_localize_seq {
 GS_API int64_t gs_localize_scratch_bytes(int H, int W, int ds, int64_t n_map_bound);
 GS_API int gs_localize_batch_f32(const gs_localize_seq* seqs_host, int B, int H, int W, int ds,
                                  const gs_icp_params* params_host, void* stream);
-/* Diagnostics of the last solve a scratch was used for (tests, tools; synchronises the stream): out4[0] = number of
- * source points the first search found far from every target and handed to the candidate-list builder (0 when the
- * lists are disabled), out4[1] = how many of them hold a proven list after the last search, out4[2] = source points
- * handed to the second builder pass, out4[3] = how many of out4[0] have a list that fits (exactness radius > 0).
- * H, W, ds and map_rows (= max(map.capacity, map.n_bound) of that call) locate the counters in the scratch. */
-GS_API int gs_localize_far_stats_i64(const void* scratch, int H, int W, int ds, int64_t map_rows, int64_t* out4_host,
-                                     void* stream);
 /* Diagnostics of the candidate lists of ordinary source points (round 4; tests, tools; synchronises the stream) for the
- * last solve a scratch was used for: out[h] = source points whose list gave no proof in launch h of the solve (h = 2 x
+ * last solve a scratch was used for; H, W, ds and map_rows (= max(map.capacity, map.n_bound) of that call) locate the
+ * counters in the scratch: out[h] = source points whose list gave no proof in launch h of the solve (h = 2 x
  * iteration + half; they were re-searched by the 2x2x2 scan and got a new list), out[64 + h] = source points whose list
  * was empty (no radius fitted the slots: re-searched as well), out[128 + h] = source points that had no list in launch h
  * because neither the 2x2x2 stage nor the cubes could prove them (as without lists).  All zero when the solve kept no
- * lists (GRADSLAM_HIP_ICP_LISTS=0, far-candidate lists in use, blocks walking several groups of row units) and for the
- * launches before the lists start (GRADSLAM_HIP_ICP_LISTS_FROM).  out_host holds 192 values. */
+ * lists (GRADSLAM_HIP_ICP_LISTS=0, blocks walking several groups of row units) and for the launches before the lists
+ * start (GRADSLAM_HIP_ICP_LISTS_FROM).  out_host holds 192 values.  With GRADSLAM_HIP_DEBUG_GRID set the call also
+ * prints the header of the solve's target grid to stderr. */
 GS_API int gs_localize_list_stats_i64(const void* scratch, int H, int W, int ds, int64_t map_rows, int64_t* out192_host,
                                       void* stream);
-/* Diagnostics of the sync record of the last solve a scratch was used for (ABI v3; tests, tools; synchronises the
- * stream; arguments as gs_localize_far_stats_i64): out8[0] = tickets the persistent solve's blocks took, out8[1] = their
- * arrivals (nb per half-iteration served: nb x (2 numiters - h0) for a complete run), out8[2] = its error word (a block
- * gave up waiting), out8[3] = source points whose list the list-building launch flagged as weak (counted only with
- * GRADSLAM_HIP_ICP_WEAK_ROOM > 0), out8[4] = nb, the persistent solve's blocks per sequence, out8[5] = h0, the first
- * half-iteration it served, out8[6..7] = 0.  out8[0], [1], [2], [4], [5] are 0 when the solve ran without the
- * persistent launch. */
+/* Diagnostics of the last solve a scratch was used for (ABI v3; tests, tools; synchronises the stream; arguments as
+ * gs_localize_list_stats_i64): out8[3] = source points whose list the list-building launch flagged as weak (counted only
+ * with GRADSLAM_HIP_ICP_WEAK_ROOM > 0); every other word of out8 is 0 (they reported an engine that has been retired;
+ * the signature stays). */
 GS_API int gs_localize_solve_stats_i64(const void* scratch, int H, int W, int ds, int64_t map_rows, int64_t* out8_host,
                                        void* stream);
 

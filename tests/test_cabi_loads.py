@@ -39,6 +39,23 @@ def test_host_argument_validation_without_gpu():
     assert lib.gs_solve_normal_eq_f32(None, None, None, 5, 9, 1e-8, None, None) == 1
 
 
+def test_retired_knobs_are_warned_about_at_import():
+    """The persistent solve and the far-query lists are gone; a process that still sets one of their
+    switches gets ONE RuntimeWarning that names what is set and says it is ignored -- not silence."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in _C.RETIRED_KNOBS}
+    code = "import sys; sys.path.insert(0, %r); import gradslam_amd._C" % REPO
+    r = subprocess.run([sys.executable, "-W", "always", "-c", code], capture_output=True, text=True, timeout=300,
+                       env=dict(env, GRADSLAM_HIP_ICP_PERSIST="1", GRADSLAM_HIP_ICP_FAR="0"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert ("RuntimeWarning: retired knobs are set and ignored: GRADSLAM_HIP_ICP_PERSIST, GRADSLAM_HIP_ICP_FAR ("
+            in r.stderr), r.stderr[-2000:]
+    assert r.stderr.count("RuntimeWarning: retired knobs") == 1 and "GRADSLAM_HIP_ICP_PERSIST_TIMELINE" not in r.stderr
+    quiet = subprocess.run([sys.executable, "-W", "always", "-c", code], capture_output=True, text=True, timeout=300, env=env)
+    assert quiet.returncode == 0 and "retired knobs" not in quiet.stderr, quiet.stderr[-2000:]
+
+
 def test_cpu_tensors_are_rejected_loudly():
     import torch
     from gradslam_amd import ops

@@ -664,60 +664,6 @@ def test_streamed_frames_give_the_resident_result(gs):
         FrameStreamer(d16.clone(), c8, K, P0, 5000.0)
 
 
-_FAR_SCRIPT = r"""
-import sys
-import numpy as np, torch
-sys.path.insert(0, %r)
-import gradslam_amd as gs
-from gradslam_amd import ops
-from gradslam_amd.datasets.synthetic import make_sequence
-L, H, W = 4, 240, 320
-s = make_sequence(L, H, W, seed=5)
-depths = s["depths"].copy()
-depths[0, :, int(0.62 * W):] = 0.0          # the map of frame 0 does not cover the right part of the view:
-T = torch.from_numpy                         # the source points there are far from every target
-poses = s["poses"].copy(); poses[1:] = poses[:1]
-frames = gs.RGBDImages(T(s["colors"][None]).cuda(), T(depths[None]).cuda(), T(s["intrinsics"][None]).cuda(), T(poses[None]).cuda())
-slam = gs.slam.PointFusion(odom="gradicp", device="cuda")
-pc, prev, rec, stats = gs.Pointclouds(device="cuda"), None, [], []
-for i in range(L):
-    live = frames[:, i]
-    pc, p = slam.step(pc, live, prev, inplace=True)
-    prev = live
-    rec.append(p[0, 0].cpu().numpy())
-    if i == 1:   # the first localisation: the map is frame 0 only
-        stats = ops.localize_far_stats(torch.device("cuda", 0), 0, H, W, 4, pc._buf["points"][0].shape[0])
-np.savez(sys.argv[1], poses=np.stack(rec), n=np.array([int(pc.points_list[0].shape[0])]), pts=pc.points_list[0].cpu().numpy(),
-         far=np.array(stats))
-"""
-
-
-def test_far_candidate_lists_leave_results_identical(tmp_path):
-    """Source points far from every target (here: 38 % of the view is missing from the map) get candidate lists after
-    the first search of a solve (gs_icp_far_build_kernel) and are then served by 16 gathers instead of a cube scan or
-    a pass over all targets (GRADSLAM_HIP_ICP_FAR=1 switches the lists on: opt-in since round 5, when ordinary + wide lists
-    became the faster choice at every size).  GRADSLAM_HIP_ICP_FAR=0 runs the same frames without lists: poses and the map must be
-    bit-identical, and the lists must actually have been in use.  (This scene is hostile on purpose: half of the far
-    points have more than 16 targets within reach or move out of their list's radius, and fall back to the scans.)"""
-    import os
-    import subprocess
-    import sys
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    outs = []
-    for far in ("1", "0"):
-        out = str(tmp_path / ("far%s.npz" % far))
-        subprocess.run([sys.executable, "-c", _FAR_SCRIPT % repo, out], check=True, timeout=600,
-                       env=dict(os.environ, GRADSLAM_HIP_ICP_FAR=far))
-        outs.append(np.load(out))
-    a, b = outs
-    assert a["far"][0] > 300, a["far"]                 # far source points found by the first search ...
-    assert a["far"][1] > 50, a["far"]                  # ... some of which still prove on their list at the last search
-    assert b["far"][0] == 0
-    assert np.array_equal(a["poses"].view(np.int32), b["poses"].view(np.int32))
-    assert a["n"][0] == b["n"][0]
-    assert np.array_equal(a["pts"].view(np.int32), b["pts"].view(np.int32))
-
-
 _LIST_SCRIPT = r"""
 import sys
 import numpy as np, torch
@@ -732,7 +678,7 @@ st = lambda k: torch.from_numpy(np.stack([s[k] for s in seqs])).cuda()
 poses = st("poses"); poses[:, 1:] = poses[:, :1]
 frames = gs.RGBDImages(st("colors"), st("depths"), st("intrinsics"), poses)
 slam = gs.slam.PointFusion(odom="gradicp", device="cuda")
-pc, prev, rec, stats, sstats = gs.Pointclouds(device="cuda"), None, [], [], []
+pc, prev, rec, stats = gs.Pointclouds(device="cuda"), None, [], []
 for i in range(L):
     live = frames[:, i]
     pc, p = slam.step(pc, live, prev, inplace=True)
@@ -740,11 +686,8 @@ for i in range(L):
     rec.append(p[:, 0].cpu().numpy())
     if i >= 1:
         stats.append([ops.localize_list_stats(torch.device("cuda", 0), b, H, W, 4, pc._buf["points"][b].shape[0]) for b in range(B)])
-        sstats.append([ops.localize_solve_stats(torch.device("cuda", 0), b, H, W, 4, pc._buf["points"][b].shape[0]) for b in range(B)])
 np.savez(sys.argv[1], poses=np.stack(rec), n=np.array([int(x.shape[0]) for x in pc.points_list]),
-         pts=np.concatenate([x.cpu().numpy() for x in pc.points_list]), stats=np.array(stats),
-         ps_nb=np.array([[d["nb"] for d in f] for f in sstats]), ps_h0=np.array([[d["h0"] for d in f] for f in sstats]),
-         ps_arrived=np.array([[d["arrived"] for d in f] for f in sstats]), ps_error=np.array([[d["error"] for d in f] for f in sstats]))
+         pts=np.concatenate([x.cpu().numpy() for x in pc.points_list]), stats=np.array(stats))
 """
 
 
@@ -835,40 +778,6 @@ def test_lanes_per_point_and_block_share_leave_results_identical(tmp_path):
         assert np.array_equal(a["poses"].view(np.int32), b["poses"].view(np.int32))
         assert np.array_equal(a["n"], b["n"])
         assert np.array_equal(a["pts"].view(np.int32), b["pts"].view(np.int32))
-
-
-@pytest.mark.parametrize("B,first", [(8, 0), (1, 0), (3, 85)])
-def test_persistent_xcd_solve_leaves_results_identical(tmp_path, B, first):
-    """Round 6 (opt-in, GRADSLAM_HIP_ICP_PERSIST=1): the list-checking half-iterations of a solve as ONE persistent launch per
-    sequence, resident on one XCD (csrc/gs_icp_persist.h: blocks find their XCD at run time, partial rows by plain stores +
-    one L2 atomic per half-iteration, readers bypass their L1; source points, lists and listed targets stay in registers /
-    LDS across the half-iterations).  Every sum keeps its order and every search its arithmetic, so the bits must be those
-    of the launch-per-half-iteration path: poses, surfel counts, points -- at 8 / 1 / 3 sequences per GPU, the last on
-    frames 85 .. 88 of the camera path, where points without a provable list (cube scans, wide lists, block passes) exist.
-    And the persistent kernel must really have run (it falls back to the launches without a word, e.g. under
-    GRADSLAM_HIP_ICP_LANES or GRADSLAM_HIP_ICP_TIMELINE, popped here): in every solve its nb blocks arrived at each of
-    the 2 numiters - h0 half-iterations it served (ops.localize_solve_stats)."""
-    import os
-    import subprocess
-    import sys
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    outs = []
-    for on in ("1", "0"):
-        out = str(tmp_path / ("persist%s.npz" % on))
-        env = dict(os.environ, GRADSLAM_HIP_ICP_PERSIST=on)
-        env.pop("GRADSLAM_HIP_ICP_LANES", None)
-        env.pop("GRADSLAM_HIP_ICP_TIMELINE", None)
-        subprocess.run([sys.executable, "-c", _LIST_SCRIPT % repo, out, str(B), "480", "640", str(first)], check=True, timeout=900,
-                       env=env)
-        outs.append(np.load(out))
-    a, b = outs
-    assert (a["ps_nb"] > 0).all() and not a["ps_error"].any(), (a["ps_nb"], a["ps_error"])   # (20 iterations per solve)
-    assert np.array_equal(a["ps_arrived"], a["ps_nb"] * (2 * 20 - a["ps_h0"])), (a["ps_arrived"], a["ps_nb"], a["ps_h0"])
-    assert not b["ps_nb"].any()
-    assert np.isfinite(a["poses"]).all()                         # (a block that gives up waiting leaves a NaN pose)
-    assert np.array_equal(a["poses"].view(np.int32), b["poses"].view(np.int32))
-    assert np.array_equal(a["n"], b["n"])
-    assert np.array_equal(a["pts"].view(np.int32), b["pts"].view(np.int32))
 
 
 def test_pointfusion_1296x968_vs_reference_golden(gs, golden):

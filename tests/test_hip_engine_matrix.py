@@ -1,7 +1,7 @@
 """GPU: every engine switch of the ICP solve against the ORACLE, not against another HIP run.
 
-The solve (csrc/gs_icp_loop.hip, gs_knn.h, gs_icp_persist.h) has runtime switches that pick other kernels or branches:
-candidate lists, wide lists, binned normals, weak-list room, the persistent solve, the brute-force search.  None may
+The solve (csrc/gs_icp_loop.hip, gs_knn.h) has runtime switches that pick other kernels or branches: candidate lists,
+wide lists, binned normals, weak-list room, the brute-force search.  None may
 change a result, and an A/B pair of two HIP runs cannot see a bug both of its sides share (a cube scan, the block-wide
 pass, the partial last row unit of 96 points).  So every (setting, scene) below runs in a fresh process -- the switches
 are read into statics once per process -- and is held to the oracle's record of the scene
@@ -63,14 +63,13 @@ for i in range(L):
     if i >= 1 and mode == "step":
         cap = [pc._buf["points"][b].shape[0] for b in range(B)]
         lstats.append([ops.localize_list_stats(torch.device("cuda", 0), b, H, W, 4, cap[b]) for b in range(B)])
-        sstats.append([[v for v in ops.localize_solve_stats(torch.device("cuda", 0), b, H, W, 4, cap[b]).values()]
-                       for b in range(B)])
+        sstats.append([[ops.localize_solve_stats(torch.device("cuda", 0), b, H, W, 4, cap[b])["weak"]] for b in range(B)])
 idx = torch.from_numpy(g["sample_idx"].astype(np.int64)).cuda()
 sample = np.stack([pc.points_list[b][idx[b]].cpu().numpy() for b in range(B)])
 np.savez(out, poses=np.stack(rec).transpose(1, 0, 2, 3), counts=np.array(counts).T, sums=np.stack([np.stack(s) for s in sums]).transpose(1, 0, 2),
          abs_sums=np.array(abss).T, sample=sample, lstats=np.array(lstats), sstats=np.array(sstats, np.int64))
 """
-SSTAT = ("ticket", "arrived", "error", "weak", "nb", "h0")   # (ops.localize_solve_stats, in order)
+SSTAT = ("weak",)   # (what the child records of ops.localize_solve_stats)
 
 SETTINGS = {
     "default": ({}, "step"),
@@ -78,8 +77,6 @@ SETTINGS = {
     "wide0": ({"GRADSLAM_HIP_ICP_WIDE": "0"}, "step"),
     "binned0": ({"GRADSLAM_HIP_ICP_BINNED_NORMALS": "0"}, "step"),
     "weak008": ({"GRADSLAM_HIP_ICP_WEAK_ROOM": "0.08"}, "step"),
-    "persist": ({"GRADSLAM_HIP_ICP_PERSIST": "1"}, "step"),
-    "persist_weak008": ({"GRADSLAM_HIP_ICP_PERSIST": "1", "GRADSLAM_HIP_ICP_WEAK_ROOM": "0.08"}, "step"),
     "brute": ({"GRADSLAM_HIP_KNN": "brute"}, "plugin"),
 }
 _cache = {}
@@ -126,7 +123,6 @@ def _assert_oracle(setting, scene, r):
                        "sample_rows_bit_exact": bool(np.array_equal(r["sample"].view(np.int32), g["sample_points"].view(np.int32))),
                        "sample_rows_max_abs_diff": float(np.abs(r["sample"] - g["sample_points"]).max()),
                        "point_sum_max_abs_diff": float(dsum.max()),
-                       "persistent_solve_ran_every_solve": bool(ss.size and (ss[..., SSTAT.index("nb")] > 0).all()),
                        "solve_stats": ss.tolist(),
                        "weak_lists": int(ss[..., SSTAT.index("weak")].sum()) if ss.size else 0}, fh)
     for b in range(B):
@@ -141,27 +137,12 @@ def _stat(r, name):
     return r["sstats"][..., SSTAT.index(name)]               # (frames - 1, B)
 
 
-def _assert_persistent_ran(r):
-    """every sequence, every frame >= 1: no error, nb blocks that each arrived at every half-iteration they served"""
-    nb, h0, arrived, err, ticket = (_stat(r, k) for k in ("nb", "h0", "arrived", "error", "ticket"))
-    assert (err == 0).all(), err
-    assert (nb > 0).all(), nb
-    assert (arrived == nb * (2 * NUMITERS - h0)).all(), (arrived, nb, h0)
-    assert (ticket >= nb).all(), (ticket, nb)
-
-
-def _assert_no_persistent(r):
-    for k in ("ticket", "arrived", "error", "nb", "h0"):
-        assert not _stat(r, k).any(), (k, _stat(r, k))
-
-
 @pytest.mark.parametrize("scene", ["bench8", "hard3", "ragged2", "weak1"])
 def test_default_engine_matches_oracle(tmp_path_factory, scene):
     """The anchor: the default engine (ordinary + wide candidate lists, binned normals, launch per half-iteration) on every
-    scene.  The persistent solve does not run, and no weak list is counted without GRADSLAM_HIP_ICP_WEAK_ROOM."""
+    scene.  No weak list is counted without GRADSLAM_HIP_ICP_WEAK_ROOM."""
     r = _run("default", scene, tmp_path_factory)
     _assert_oracle("default", scene, r)
-    _assert_no_persistent(r)
     assert not _stat(r, "weak").any()
     if scene == "hard3":   # the scene has points without an ordinary list (what the wide lists, cubes and block passes serve)
         assert r["lstats"][:, :, 2, 4:40].sum() > 0
@@ -189,8 +170,7 @@ def test_without_wide_lists_matches_oracle(tmp_path_factory):
 @pytest.mark.parametrize("scene", ["bench8", "ragged2"])
 def test_gathered_normals_match_oracle(tmp_path_factory, scene):
     """GRADSLAM_HIP_ICP_BINNED_NORMALS=0: the matches' normals gathered from the map instead of the binned copy.  No witness
-    needed: a host branch with no fallback (the grid build is given no normals).  It also keeps the persistent solve off
-    (which needs the binned normals), so it has no persistent row."""
+    needed: a host branch with no fallback (the grid build is given no normals)."""
     r = _run("binned0", scene, tmp_path_factory)
     _assert_oracle("binned0", scene, r)
 
@@ -201,25 +181,6 @@ def test_weak_list_room_matches_oracle(tmp_path_factory, scene):
     cube scans of the list-building launch.  Witness: some solve flagged weak lists."""
     r = _run("weak008", scene, tmp_path_factory)
     _assert_oracle("weak008", scene, r)
-    assert _stat(r, "weak").sum() > 0
-
-
-@pytest.mark.parametrize("scene", ["bench8", "hard3", "weak1"])
-def test_persistent_solve_matches_oracle(tmp_path_factory, scene):
-    """GRADSLAM_HIP_ICP_PERSIST=1: the list-checking half-iterations as one persistent launch per sequence.  Witness: in
-    every solve of every sequence it ran to its end (sync record: no error, nb > 0 blocks, nb x (2 numiters - h0)
-    arrivals, at least nb tickets).  It runs on all three scenes (B <= 8, 200 row units = 29 blocks of 7, 2 lanes)."""
-    r = _run("persist", scene, tmp_path_factory)
-    _assert_oracle("persist", scene, r)
-    _assert_persistent_ran(r)
-
-
-@pytest.mark.parametrize("scene", ["bench8", "weak1"])
-def test_persistent_solve_with_weak_room_matches_oracle(tmp_path_factory, scene):
-    """GRADSLAM_HIP_ICP_PERSIST=1 + GRADSLAM_HIP_ICP_WEAK_ROOM=0.08 (DESIGN.md's measured configuration): both witnesses."""
-    r = _run("persist_weak008", scene, tmp_path_factory)
-    _assert_oracle("persist_weak008", scene, r)
-    _assert_persistent_ran(r)
     assert _stat(r, "weak").sum() > 0
 
 

@@ -65,7 +65,7 @@ for lo, hi in bins:
         print("  %-52s %9.1f us per step" % (k, tot[k]))
     icp = sum(v for k, v in tot.items() if "gs_icp_half" in k)
     print("  ICP half-iteration launches together %.1f us; everything else %.1f us" % (icp, sum(tot.values()) - icp))
-    print("  launch h: variant <FULL, G, FAR, LMODE>: mean / max us")
+    print("  launch h: variant <FULL, G, LMODE>: mean / max us")
     for h in sorted(half):
         d = np.array([x[0] for x in half[h]])
         print("    %2d  %-22s %7.2f %7.2f" % (h, half[h][0][1], d.mean(), d.max()))

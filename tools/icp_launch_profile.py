@@ -11,7 +11,7 @@ skip = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 rows = []
 for r in csv.DictReader(open(path)):
     n = r["Kernel_Name"]
-    if "gs_icp_half_batch_kernel" in n or "gs_icp_finish_batch_kernel" in n or "gs_icp_far_build" in n:
+    if "gs_icp_half_batch_kernel" in n or "gs_icp_finish_batch_kernel" in n:
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), n))
 rows.sort()
 solves, cur = [], None
@@ -20,10 +20,8 @@ for s, e, n in rows:
         if cur is not None:
             cur.append((s, e, n)); solves.append(cur); cur = None
         continue
-    if "far_build" in n:
-        continue
-    m = re.search(r"<(true|false), (\d), (true|false)(?:, (\d))?>", n)
-    full, lm = m.group(1) == "true", int(m.group(4) or 0)
+    m = re.search(r"<(true|false), (\d), (\d)>", n)
+    full, lm = m.group(1) == "true", int(m.group(3))
     if cur is None:
         cur = []
     cur.append((s, e, n))

@@ -31,9 +31,9 @@ def load(d):
     return [(names[k], rows[k]) for k in order]
 
 
-def variant(name):   # <FULL, G, FAR, LMODE>
+def variant(name):   # <FULL, G, LMODE>
     a = name.split("<", 1)[1].split(">", 1)[0].replace(" ", "").split(",")
-    return ("first half" if a[0] == "true" else "look-ahead") + (", lists" if a[3] == "2" else ", mode " + a[3])
+    return ("first half" if a[0] == "true" else "look-ahead") + (", lists" if a[2] == "2" else ", mode " + a[2])
 
 
 per_solve = int(sys.argv[3]) if len(sys.argv) > 3 else 40

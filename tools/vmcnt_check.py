@@ -32,11 +32,11 @@ bad = 0
 i = 0
 print("# kernel: vector-memory instructions between the hand-issued state load and each hand-written `s_waitcnt vmcnt(N)` before the first barrier")
 while i < len(lines):
-    m = re.match(r"^(_Z24gs_icp_half_batch_kernelILb([01])ELi(\d)ELb0ELi2EE\w*):", lines[i])
+    m = re.match(r"^(_Z24gs_icp_half_batch_kernelILb([01])ELi(\d)ELi2EE\w*):", lines[i])
     if not m:
         i += 1
         continue
-    name = "gs_icp_half_batch_kernel<%s, %s, false, 2>" % ("true" if m.group(2) == "1" else "false", m.group(3))
+    name = "gs_icp_half_batch_kernel<%s, %s, 2>" % ("true" if m.group(2) == "1" else "false", m.group(3))
     j, in_app, issued, count, waits = i + 1, False, False, 0, []
     while j < len(lines) and not lines[j].startswith("\t.end_amdhsa_kernel") and "s_endpgm" not in lines[j]:
         ln = lines[j]
