@@ -94,13 +94,21 @@ GS_DEV bool gs_is_similar(const float* __restrict__ points, const float* __restr
   return (dist < dist_th) && (dot > dot_th);
 }
 
-// the same test on the pixel's global vertex f and normal g held in registers
-GS_DEV bool gs_is_similar_v(const float* __restrict__ points, const float* __restrict__ normals, const float* f,
-                            const float* g, int64_t n, float dist_th, float dot_th) {
+// the same test on the pixel's global vertex f and normal g held in registers, as its two halves: both are pure and the
+// test is their AND, so a pass may ask for the normal first and gather the vertex only for a row the normal lets through
+// (the key pass of the one-call map update: a row that projects onto a pixel without depth, or next to one, fails here)
+GS_DEV bool gs_is_similar_dot_v(const float* __restrict__ normals, const float* g, int64_t n, float dot_th) {
+  const float dot = gs_dot3_plain(g[0], g[1], g[2], normals[3 * n], normals[3 * n + 1], normals[3 * n + 2]);
+  return dot > dot_th;
+}
+GS_DEV bool gs_is_similar_dist_v(const float* __restrict__ points, const float* f, int64_t n, float dist_th) {
   const float q0 = points[3 * n], q1 = points[3 * n + 1], q2 = points[3 * n + 2];
   const float dist = gs_norm3(f[0] - q0, f[1] - q1, f[2] - q2);
-  const float dot = gs_dot3_plain(g[0], g[1], g[2], normals[3 * n], normals[3 * n + 1], normals[3 * n + 2]);
-  return (dist < dist_th) && (dot > dot_th);
+  return dist < dist_th;
+}
+GS_DEV bool gs_is_similar_v(const float* __restrict__ points, const float* __restrict__ normals, const float* f,
+                            const float* g, int64_t n, float dist_th, float dot_th) {
+  return gs_is_similar_dist_v(points, f, n, dist_th) && gs_is_similar_dot_v(normals, g, n, dot_th);
 }
 
 // slam/fusionutils.py:491-517: (1/(ccount+1e-20), |p - f|^2) packed so that unsigned order ==

@@ -42,9 +42,11 @@ int gs_frame_maps_batch_clear(const float* depth, int64_t depth_stride_seq, int6
                               float* normal, float* alpha, const GsClearJob* job, void* stream,
                               const GsPixelTables* tables = nullptr);
 
-// the batched map update behind gs_update_map_fusion_batch_f32 (gs_fuse.hip); tables_ready: see GsPixelTables
+// the batched map update behind gs_update_map_fusion_batch_f32 (gs_fuse.hip); tables_ready: see GsPixelTables.
+// two_sigma_sq: read only for sequences without global maps (gvertex == NULL, which needs tables_ready) -- the value the
+// caller's frame-map launch made their alpha maps with, from which the update computes a pixel's alpha again
 int gs_update_map_fusion_batch_impl(const gs_update_seq* seqs_host, int B, int H, int W, float dist_th, float dot_th,
-                                    int renorm_all, void* stream, bool tables_ready);
+                                    int renorm_all, void* stream, bool tables_ready, float two_sigma_sq);
 int32_t* gs_update_map_call_flag(void* scratch_of_first_sequence);
 void gs_update_map_tables(void* scratch, int32_t** any_flag, uint64_t** key_pix);
 
@@ -150,6 +152,9 @@ GS_DEV float gs_alpha_of(float vx, float vy, float vz, float two_sigma_sq, float
   a = a > 1.01f ? 1.01f : a;
   return a;
 }
+// the floor of a frame's alpha map (frame_maps_body, gs_frame.hip).  The one-call step's map update computes the alpha of
+// a pixel again from the local vertex it holds instead of gathering it (gs_fuse.hip, FrameLocalMaps): one constant for both
+constexpr float GS_FRAME_ALPHA_EPS = 1e-7f;
 
 struct GsKinv {
   float k00, k11, k02, k12;

@@ -169,7 +169,7 @@ GS_DEV void frame_maps_body(const float* __restrict__ depth, const float* __rest
     fm_vertex(d, h, w, k, vx, vy, vz);
     if (vertex) reinterpret_cast<GsRow3*>(vertex)[p] = GsRow3{vx, vy, vz};   // one 12-byte store per row (dwordx3)
     if (valid) valid[p] = d > 0.0f ? 1 : 0;
-    if (alpha) alpha[p] = gs_alpha_of(vx, vy, vz, two_sigma_sq, 1e-7f);
+    if (alpha) alpha[p] = gs_alpha_of(vx, vy, vz, two_sigma_sq, GS_FRAME_ALPHA_EPS);
     if (key_pix) { key_pix[p] = ~0ull; best_pix[p] = -1; }   // (GsPixelTables: the map update's per-pixel tables)
     if (normal) {
       // forward differences; the last column / row reuse the previous difference

@@ -35,6 +35,7 @@ __global__ void __launch_bounds__(256) gs_fuse_scatter_kernel(const int32_t* __r
 // `frame(p, fp, fn)` yields the global vertex and normal of pixel p: from the materialised global maps (FrameGlobalMaps)
 // or computed on the spot from the local maps and the pose (FrameLocalMaps: the same operations, so the same bits).
 struct FrameGlobalMaps {
+  static constexpr bool kAlphaFromVertex = false;   // the alpha map is the caller's: gathered
   const float* __restrict__ gvertex;
   const float* __restrict__ gnormal;
   __device__ void operator()(const int64_t p, float* fp, float* fn) const {
@@ -59,10 +60,15 @@ struct FrameGlobalMaps {
 // (A gather of depth[p] instead was measured: these passes are bound by the number of scattered accesses, and that
 // fifth one cost 15 us in the projection pass and 5 us in the merge at 8 x 640x480.)  Only the one-call step, which makes
 // the vertex map itself, uses this form.
+// The alpha of a pixel is not gathered either (kAlphaFromVertex): the step's frame-map launch wrote alpha[p] =
+// gs_alpha_of(local vertex of p, two_sigma_sq, GS_FRAME_ALPHA_EPS) in the same call, and whoever merges or appends pixel p
+// has just loaded that local vertex -- vertex_alpha_of applies the same function to the same bits.
 struct FrameLocalMaps {
+  static constexpr bool kAlphaFromVertex = true;
   const float* __restrict__ vertex;
   const float* __restrict__ normal;
   float T[12];
+  float two_sigma_sq;
   __device__ void operator()(const int64_t p, float* fp, float* fn) const {
     float v[3], n[3];
 #pragma unroll
@@ -78,14 +84,24 @@ struct FrameLocalMaps {
     fn[1] = gs_dot3_fma(T[4], T[5], T[6], n[0], n[1], n[2]);
     fn[2] = gs_dot3_fma(T[8], T[9], T[10], n[0], n[1], n[2]);
   }
-  __device__ void vertex_of(const int64_t p, float* fp) const {
-    float v[3];
+  // global vertex fp of pixel p, and the local vertex v it was made from
+  __device__ void vertex_of(const int64_t p, float* fp, float* v) const {
 #pragma unroll
     for (int k = 0; k < 3; ++k) v[k] = vertex[3 * p + k];
     const float validf = v[2] > 0.0f ? 1.0f : 0.0f;
     float g0, g1, g2;
     gs_rigid_fma(T, v[0], v[1], v[2], g0, g1, g2);
     fp[0] = g0 * validf; fp[1] = g1 * validf; fp[2] = g2 * validf;
+  }
+  __device__ void vertex_of(const int64_t p, float* fp) const {
+    float v[3];
+    vertex_of(p, fp, v);
+  }
+  // vertex_of, and the alpha the frame-map launch derived from the local vertex loaded here
+  __device__ float vertex_alpha_of(const int64_t p, float* fp) const {
+    float v[3];
+    vertex_of(p, fp, v);
+    return gs_alpha_of(v[0], v[1], v[2], two_sigma_sq, GS_FRAME_ALPHA_EPS);
   }
   __device__ void normal_of(const int64_t p, float* fn) const {
     float n[3];
@@ -96,24 +112,26 @@ struct FrameLocalMaps {
     fn[2] = gs_dot3_fma(T[8], T[9], T[10], n[0], n[1], n[2]);
   }
 };
-GS_DEV FrameLocalMaps frame_local_maps(const float* vertex, const float* normal, const float* pose16) {
+GS_DEV FrameLocalMaps frame_local_maps(const float* vertex, const float* normal, const float* pose16,
+                                       const float two_sigma_sq) {
   FrameLocalMaps f;
-  f.vertex = vertex; f.normal = normal;
+  f.vertex = vertex; f.normal = normal; f.two_sigma_sq = two_sigma_sq;
 #pragma unroll
   for (int i = 0; i < 12; ++i) f.T[i] = pose16[i];
   return f;
 }
 
 // `cc` = ccounts[n], loaded by the caller.  HAVE_VERTEX: the caller already holds the global vertex of pixel p in `fv` (the
-// one-call update's winner test gathers it to rebuild the row's key) and it is not gathered a second time.
+// one-call update's winner test gathers it to rebuild the row's key) and it is not gathered a second time.  HAVE_ALPHA: nor
+// is alpha[p] gathered, the caller hands it in as `av` (FrameLocalMaps::vertex_alpha_of).
 // (ccounts[n] is stored even where cc + 0.0f leaves its bits alone: a store only for the rows whose count changes was
 // measured and saves nothing)
-template <bool HAVE_VERTEX = false, class Frame>
+template <bool HAVE_VERTEX = false, bool HAVE_ALPHA = false, class Frame>
 GS_DEV void fuse_merge_row(float* __restrict__ points, float* __restrict__ normals, float* __restrict__ colors,
                            float* __restrict__ ccounts, const int64_t n, const int32_t p, const Frame& frame,
                            const float* __restrict__ rgb, const float* __restrict__ alpha, const float cc,
-                           const float* fv = nullptr) {
-  const float a = p >= 0 ? alpha[p] : 0.0f;
+                           const float* fv = nullptr, const float av = 0.0f) {
+  const float a = p >= 0 ? (HAVE_ALPHA ? av : alpha[p]) : 0.0f;
   float P[3], N[3], C[3], fp[3] = {0.0f, 0.0f, 0.0f}, fn[3] = {0.0f, 0.0f, 0.0f}, fc[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -187,13 +205,15 @@ struct EmitAppendT {
   __device__ void operator()(int64_t p, int64_t pos) const {
     const int64_t r = gs_count(n_map) + pos;
     float v[3], nn[3] = {0.0f, 0.0f, 0.0f}, c[3] = {0.0f, 0.0f, 0.0f};  // loads, then stores: 12-byte accesses
-    frame.vertex_of(p, v);
+    float a = 0.0f;
+    if constexpr (Frame::kAlphaFromVertex) a = frame.vertex_alpha_of(p, v);
+    else frame.vertex_of(p, v);
     if (normals) frame.normal_of(p, nn);
     if (colors) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) c[k] = rgb[3 * p + k];
     }
-    const float a = ccounts ? alpha[p] : 0.0f;
+    if constexpr (!Frame::kAlphaFromVertex) a = ccounts ? alpha[p] : 0.0f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) points[3 * r + k] = v[k];
     if (normals) {
@@ -421,7 +441,8 @@ extern "C" int gs_fuse_append_backward_f32(const float* points, const float* nor
 // launch (block b -> sequence b % B on its block b / B); every value is computed by the same arithmetic as in the
 // separate entry points:
 //   U1 per pixel : global vertex / normal under the new pose; clear the per-pixel key and winner tables
-//   U2 per surfel: project, similarity test, per-pixel atomicMin of the (1/ccount, ray) key
+//   U2 per surfel: project, similarity test (the pixel's normal first, its vertex only for a row that passes the dot test),
+//                  per-pixel atomicMin of the (1/ccount, ray) key
 //   U3 (round 5: no longer a pass over the map) the winner of a pixel is the row that attains its key; two rows with the SAME
 //      key (same confidence bits, same distance bits: the lower index wins, slam/fusionutils.py:491-536) are noticed by U2
 //      -- the atomicMin of the second one returns its own key -- which marks the pixel; the per-pixel pass U4 then settles the
@@ -459,6 +480,7 @@ struct MuBatch {
   int B, H, W, renorm_all;
   int64_t P, ntiles;
   float u_hi, v_hi, dist_th, dot_th;
+  float two_sigma_sq;   // of the frame-map launch that wrote MuSeq::alpha (the one-call step, gvertex == NULL; else unused)
   // "some sequence of the CALL has a match": batches beyond GS_MAX_BATCH sequences run in chunks, and the reference's
   // test (fusionutils.py:659) looks at the table of the whole batch.  One word shared by all chunks of a call (in the
   // first sequence's scratch), zeroed by the first chunk's pixel pass, set by every chunk's winner pass, read by the
@@ -503,11 +525,20 @@ __global__ void __launch_bounds__(256) gs_mu_project_key_kernel(const MuBatch mb
   int32_t pk = -1;
   if (p >= 0) {
     // the pixel's global vertex / normal: materialised by the pixel pass, or computed here (MuSeq::gvertex == NULL: the
-    // one-call step, whose frame-map launch initialised the tables -- there is no pixel pass then)
+    // one-call step, whose frame-map launch initialised the tables -- there is no pixel pass then).
+    // The normal first: on the benchmark scene half the rows in the frame fail its test (they project onto a pixel
+    // without depth, whose vertex and normal are zero, or belong to the rim of a hole and never match), and a row that
+    // fails gathers no vertex.  The two tests are pure and joined by AND: the same pk, keys and tie marks.
     float fp[3], fn[3];
-    if (q.gvertex) FrameGlobalMaps{q.gvertex, q.gnormal}((int64_t)p, fp, fn);
-    else frame_local_maps(q.vertex, q.normal, q.pose16)((int64_t)p, fp, fn);
-    if (gs_is_similar_v(q.points, q.normals, fp, fn, n, mb.dist_th, mb.dot_th)) {
+    if (q.gvertex) FrameGlobalMaps{q.gvertex, q.gnormal}.normal_of((int64_t)p, fn);
+    else frame_local_maps(q.vertex, q.normal, q.pose16, mb.two_sigma_sq).normal_of((int64_t)p, fn);
+    bool similar = gs_is_similar_dot_v(q.normals, fn, n, mb.dot_th);
+    if (similar) {
+      if (q.gvertex) FrameGlobalMaps{q.gvertex, q.gnormal}.vertex_of((int64_t)p, fp);
+      else frame_local_maps(q.vertex, q.normal, q.pose16, mb.two_sigma_sq).vertex_of((int64_t)p, fp);
+      similar = gs_is_similar_dist_v(q.points, fp, n, mb.dist_th);
+    }
+    if (similar) {
       const uint64_t k = gs_assoc_key_v(q.points, q.ccounts, fp, n);
       const unsigned long long old = atomicMin(reinterpret_cast<unsigned long long*>(&q.key_pix[p]), (unsigned long long)k);
       // Two rows with the same key at one pixel: whichever arrives second gets its own key back.  (If the key is beaten
@@ -527,7 +558,7 @@ __global__ void __launch_bounds__(256) gs_mu_project_key_kernel(const MuBatch mb
 // Settles the pixels U2 marked: the lowest-indexed row among those that attain the pixel's key.  Run by the blocks of the
 // per-pixel pass below (which comes between the key pass and the merge anyway) and skipped at once unless the frame has a
 // marked pixel (two surfels with bit-identical confidence and distance).
-GS_DEV void mu_settle_ties(const MuSeq& q, const unsigned blk, const unsigned nblk) {
+GS_DEV void mu_settle_ties(const MuBatch& mb, const MuSeq& q, const unsigned blk, const unsigned nblk) {
   if (q.any_flag[1] == 0) return;
   const int64_t n_map = gs_count(q.n_map);
   for (int64_t n = (int64_t)blk * GS_CP_BLOCK + threadIdx.x; n < n_map; n += (int64_t)nblk * GS_CP_BLOCK) {
@@ -535,7 +566,7 @@ GS_DEV void mu_settle_ties(const MuSeq& q, const unsigned blk, const unsigned nb
     if (p < 0 || q.best_pix[p] == -1) continue;   // (-1: unmarked pixel -- its key has one holder)
     float fp[3];
     if (q.gvertex) FrameGlobalMaps{q.gvertex, q.gnormal}.vertex_of((int64_t)p, fp);
-    else frame_local_maps(q.vertex, q.normal, q.pose16).vertex_of((int64_t)p, fp);
+    else frame_local_maps(q.vertex, q.normal, q.pose16, mb.two_sigma_sq).vertex_of((int64_t)p, fp);
     if (gs_assoc_key_v(q.points, q.ccounts, fp, n) == q.key_pix[p]) atomicMin(reinterpret_cast<unsigned*>(&q.best_pix[p]), (unsigned)n);
   }
 }
@@ -573,7 +604,7 @@ __global__ void __launch_bounds__(GS_CP_BLOCK) gs_mu_winner_count_kernel(const M
   int total;
   (void)gs_block_excl_scan<GS_CP_BLOCK>(c, smem, &total);
   if (threadIdx.x == 0) q.tile_counts[blk] = total;
-  mu_settle_ties(q, blk, gridDim.x / mb.B);
+  mu_settle_ties(mb, q, blk, gridDim.x / mb.B);
 }
 
 template <class Frame>
@@ -583,22 +614,28 @@ GS_DEV void mu_merge_row(const MuBatch& mb, const MuSeq& q, const int64_t n, con
   // (see U5 above), high word first: it needs nothing but ccounts[n], which the merge loads anyway, and almost every row
   // that lost its pixel lost it on confidence.  Only a row that ties the high word gathers the pixel's vertex for the low
   // word -- and, if it wins, hands that vertex on to the merge.
+  // best_pix[p] is read only in a frame with a tie mark (any_flag[1], raised by the key pass two launches ago): without
+  // one, every entry still holds the -1 the table was initialised with.  The alpha of the pixel comes with its vertex
+  // where the frame computes it (FrameLocalMaps::vertex_alpha_of), and is gathered by fuse_merge_row where it does not.
+  constexpr bool alpha_from_vertex = Frame::kAlphaFromVertex;
   int32_t p = q.pix[n];
   const float cc = q.ccounts[n];
-  float fp[3] = {0.0f, 0.0f, 0.0f};
+  const bool tie_marks = q.any_flag[1] != 0;
+  float fp[3] = {0.0f, 0.0f, 0.0f}, av = 0.0f;
   if (p >= 0) {
     const uint64_t kp = q.key_pix[p];
     bool win = (uint32_t)(kp >> 32) == gs_assoc_key_hi(cc);
     if (win) {   // (only the holders of the key act on the entry: an unmarked pixel's has one reader and writer)
-      frame.vertex_of((int64_t)p, fp);
-      const int32_t bp = q.best_pix[p];
+      if constexpr (alpha_from_vertex) av = frame.vertex_alpha_of((int64_t)p, fp);
+      else frame.vertex_of((int64_t)p, fp);
+      const int32_t bp = tie_marks ? q.best_pix[p] : -1;
       win = (uint32_t)kp == gs_assoc_key_lo_v(q.points, fp, n) && (bp == -1 || bp == (int32_t)n);
       if (win && bp == -1) q.best_pix[p] = (int32_t)n;
     }
     if (!win) p = -1;
   }
   if (p < 0 && !mb.renorm_all) return;
-  fuse_merge_row<true>(q.points, q.normals, q.colors, q.ccounts, n, p, frame, q.rgb, q.alpha, cc, fp);
+  fuse_merge_row<true, alpha_from_vertex>(q.points, q.normals, q.colors, q.ccounts, n, p, frame, q.rgb, q.alpha, cc, fp, av);
 }
 
 GS_DEV void mu_merge_body(const MuBatch& mb, const unsigned bid) {
@@ -610,7 +647,7 @@ GS_DEV void mu_merge_body(const MuBatch& mb, const unsigned bid) {
   // another sequence of the same call has some
   if (*mb.call_flag == 0) return;
   if (q.gvertex) mu_merge_row(mb, q, n, FrameGlobalMaps{q.gvertex, q.gnormal});
-  else mu_merge_row(mb, q, n, frame_local_maps(q.vertex, q.normal, q.pose16));
+  else mu_merge_row(mb, q, n, frame_local_maps(q.vertex, q.normal, q.pose16, mb.two_sigma_sq));
 }
 
 // ordered append without a scan launch: block b adds up the counts of the tiles before it (fixed order)
@@ -665,7 +702,7 @@ GS_DEV void mu_append_body(const MuBatch& mb, const unsigned bid) {
     }
   } else {
     const EmitAppendT<FrameLocalMaps> emit{q.points, q.normals, q.colors, q.ccounts, q.n_map,
-                                           frame_local_maps(q.vertex, q.normal, q.pose16), q.rgb, q.alpha};
+                                           frame_local_maps(q.vertex, q.normal, q.pose16, mb.two_sigma_sq), q.rgb, q.alpha};
     for (int r = threadIdx.x; r < tile_new; r += GS_CP_BLOCK) {
       const int64_t pos = (int64_t)tile_prefix + r;
       if (n_map + pos < q.capacity) emit(tile_base + loc_s[r], pos);
@@ -698,8 +735,10 @@ void gs_update_map_tables(void* scratch, int32_t** any_flag, uint64_t** key_pix)
 
 // phase 0: global maps, association, winner / tile counts; phase 1: merge + append (after phase 0 of every chunk)
 static int update_chunk(const gs_update_seq* seqs, int B, int H, int W, float dist_th, float dot_th, int renorm_all,
-                        hipStream_t st, int phase, int32_t* call_flag, bool first_chunk, bool tables_ready) {
+                        hipStream_t st, int phase, int32_t* call_flag, bool first_chunk, bool tables_ready,
+                        float two_sigma_sq) {
   MuBatch mb;
+  mb.two_sigma_sq = two_sigma_sq;
   mb.B = B; mb.H = H; mb.W = W; mb.renorm_all = renorm_all;
   mb.call_flag = call_flag; mb.zero_call_flag = first_chunk ? 1 : 0;
   mb.P = (int64_t)H * W;
@@ -725,11 +764,14 @@ static int update_chunk(const gs_update_seq* seqs, int B, int H, int W, float di
     m.tile_counts = reinterpret_cast<int32_t*>(q); q += gs_align(4 * (size_t)mb.ntiles);
     m.pix = reinterpret_cast<int32_t*>(q); q += gs_align(4 * (size_t)(n_map > 0 ? n_map : 1));
     m.pix_of = reinterpret_cast<int32_t*>(q);
-    // as built: projection 28 B read + 4 B written (+ 24 B frame gather and 8 B key per competing row); merge 4 + 80 B per
-    // row (+ 12 B of key / winner entry per competing row; the vertex gathered for the low word of the key is the one a
-    // winner gathers for the merge anyway), 49 B per pixel for the winner count and the append
-    bytes_assoc += 64.0 * (double)n_map;
-    bytes_fuse += 96.0 * (double)n_map + 49.0 * (double)mb.P;
+    // as built: projection 28 B read + 4 B written (+ 12 B of frame normal per row in the frame, 12 B of frame vertex per
+    // row that passes the dot test -- booked for half of them, the benchmark scene's share -- and 8 B key per competing
+    // row); merge 4 + 80 B per row (+ 8 B of key per competing row: the winner entry is read only in a frame with a tie
+    // mark, and the vertex gathered for the low word of the key is the one a winner gathers for the merge anyway, which
+    // with the global maps implicit also yields its alpha), 49 B per pixel for the winner count and the append (45 B with
+    // the global maps implicit: no alpha gather)
+    bytes_assoc += 58.0 * (double)n_map;
+    bytes_fuse += 92.0 * (double)n_map + (u.gvertex ? 49.0 : 45.0) * (double)mb.P;
   }
   const unsigned uB = (unsigned)B;
   const unsigned pb = uB * (unsigned)gs_ceil_div(mb.P, 256), nb = uB * (unsigned)gs_ceil_div(n_max > 0 ? n_max : 1, 256);
@@ -755,9 +797,11 @@ static int update_chunk(const gs_update_seq* seqs, int B, int H, int W, float di
 
 // tables_ready: the caller's frame-map launch has initialised key_pix / best_pix / the flags (gs_update_map_tables says
 // where they live); gvertex / gnormal may then be NULL -- the global vertex and normal of a pixel are computed where they
-// are used (the same operations as the pixel pass: the same bits) and never written to memory.
+// are used (the same operations as the pixel pass: the same bits) and never written to memory.  For such a sequence the
+// alpha map must be the one that launch made from u.vertex with `two_sigma_sq`: the merge and the append compute
+// alpha[p] again from the local vertex they load (FrameLocalMaps) and do not read u.alpha.
 int gs_update_map_fusion_batch_impl(const gs_update_seq* seqs_host, int B, int H, int W, float dist_th, float dot_th,
-                                    int renorm_all, void* stream, bool tables_ready) {
+                                    int renorm_all, void* stream, bool tables_ready, float two_sigma_sq) {
   GS_REQUIRE(seqs_host && B > 0 && H > 0 && W > 0, "bad arguments");
   GS_REQUIRE((int64_t)H * W < (1ll << 31), "too large for int32 indices");
   for (int b = 0; b < B; ++b) {
@@ -776,7 +820,7 @@ int gs_update_map_fusion_batch_impl(const gs_update_seq* seqs_host, int B, int H
     for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
       const int nb = B - c0 < GS_MAX_BATCH ? B - c0 : GS_MAX_BATCH;
       const int rc = update_chunk(seqs_host + c0, nb, H, W, dist_th, dot_th, renorm_all, st, phase, call_flag, c0 == 0,
-                                  tables_ready);
+                                  tables_ready, two_sigma_sq);
       if (rc != GS_OK) return rc;
     }
   }
@@ -785,7 +829,7 @@ int gs_update_map_fusion_batch_impl(const gs_update_seq* seqs_host, int B, int H
 
 extern "C" int gs_update_map_fusion_batch_f32(const gs_update_seq* seqs_host, int B, int H, int W, float dist_th,
                                               float dot_th, int renorm_all, void* stream) {
-  return gs_update_map_fusion_batch_impl(seqs_host, B, H, W, dist_th, dot_th, renorm_all, stream, false);
+  return gs_update_map_fusion_batch_impl(seqs_host, B, H, W, dist_th, dot_th, renorm_all, stream, false, 0.0f);
 }
 
 extern "C" int gs_update_map_fusion_dc_f32(float* points, float* normals, float* colors, float* ccounts,

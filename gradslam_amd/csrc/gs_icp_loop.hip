@@ -1796,7 +1796,10 @@ extern "C" int gs_pointfusion_step_batch_f32(const gs_step_seq* seqs_host, int B
     rc = localize_batch(ls, nb, H, W, ds, prm, stream, true);
     if (rc != GS_OK) return rc;
   }
-  return gs_update_map_fusion_batch_impl(us.get(), B, H, W, dist_th, dot_th, renorm_all, stream, implicit_global);
+  // (two_sigma_sq: with the global maps implicit the update computes the alpha of a pixel from the local vertex it holds,
+  // as the frame-map launch above did, instead of gathering alpha[p])
+  return gs_update_map_fusion_batch_impl(us.get(), B, H, W, dist_th, dot_th, renorm_all, stream, implicit_global,
+                                         two_sigma_sq);
 }
 
 extern "C" int64_t gs_icp_tape_bytes(int64_t n_src, int numiters) { return (int64_t)gs_icp_tape_size(n_src, numiters); }
