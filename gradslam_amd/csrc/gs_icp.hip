@@ -12,7 +12,9 @@ __global__ void __launch_bounds__(256) gs_gn_rows_kernel(
   if (s >= n_src) return;
   const unsigned long long bb = best[s];
   int64_t j = (int64_t)(bb & 0xffffffffull);
-  if (j >= n_tgt) j = 0;  // only when every distance was NaN
+  // (never taken: the brute-force kernel wrote (+inf, 0) where no distance was below +inf, see gs_knn_unpack_kernel; such a
+  // row is built from target 0 and kept only without a threshold)
+  if (j >= n_tgt) j = 0;
   const float d2 = __uint_as_float((uint32_t)(bb >> 32));
   float a[6], r;
   gn_row(src[3 * s], src[3 * s + 1], src[3 * s + 2], tgt, tn, j, a, r);

@@ -1024,7 +1024,7 @@ __global__ void __launch_bounds__(LIN_BLOCK) gs_icp_linearize_kernel(
     const unsigned long long bb = best[s];
     best[s] = ~0ull;
     int64_t j = (int64_t)(bb & 0xffffffffull);
-    if (j >= n_tgt) j = 0;  // only when every distance was NaN
+    if (j >= n_tgt) j = 0;  // (never taken behind the brute-force kernel: it wrote (+inf, 0), see gs_knn_unpack_kernel)
     const float d2 = __uint_as_float((uint32_t)(bb >> 32));
     const bool keep = (dist_thresh < 0.0f) || (d2 < dist_thresh);
     float p0 = src[3 * s], p1 = src[3 * s + 1], p2 = src[3 * s + 2];

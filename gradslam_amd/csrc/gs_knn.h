@@ -1,5 +1,24 @@
 // gs_knn.h — internal interface of the exact 1-NN engine (gs_knn.hip), shared with gs_icp.hip
 // (the fused search + linearise kernels of the ICP loop inline the device-side search).
+//
+// THE CONTRACT (tests/test_hip_knn_edges.py against oracle.knn1, tests/test_knn_cases_cpu.py for the oracle itself).
+// Every search returns what a sequential scan `best = +inf, idx = 0; for j: d = fma(dz, dz, fma(dy, dy, dx * dx));
+// if (d < best) { best = d; idx = j; }` in float32 returns: the same distance bit for bit, the lowest target index on a
+// tie.  From that scan follows what non-finite input gives, in the brute-force engine (gs_knn1_f32) and in the
+// stand-alone grid engine (gs_knn1_grid_f32) alike:
+//   * a target row with a NaN or +-inf component has a NaN or +inf distance to every query and never wins, whatever its
+//     index; the grid's bounding box is that of the finite coordinates;
+//   * a query with a NaN or +-inf component, or so far away that every distance overflows (1e20), gets (index 0, +inf);
+//   * a target set without a finite row gives (index 0, +inf) to every query; with one finite row, finite queries get
+//     that row.
+// Exactness is claimed, and tested, for finite coordinates up to about 1e4 in magnitude (any extent down to float32
+// denormals: the cell edge has a floor of 1e-6, smaller clouds share one cell), plus single queries at 1e20.  Target
+// sets whose squared CELL size overflows float32 (rb * rb = +inf in the bounds of stage 0 and of the cubes, extents
+// beyond ~1e19) are outside the claim.
+// The search inlined into the half-iteration kernels of the ICP solve is held to the same scan for finite queries with
+// at least one finite distance (every recorded search of a taped solve, per lane count); those kernels skip a source
+// point whose x is NaN (index -1, no row) instead of answering (0, +inf), and do not re-route a +inf best the way
+// gs_grid_query_kernel does.
 #pragma once
 #include "gs_common.h"
 
@@ -179,7 +198,9 @@ GS_DEV GsQueryCell grid_query_cell(const GsGrid& g, float qx, float qy, float qz
   // increases the distance to points inside it, so shell bounds around it stay valid)
   GsQueryCell c;
   // (compare + select rather than fminf / fmaxf: those canonicalise the block-uniform box corners into six VGPRs
-  // that stay live through the whole search; queries are never NaN here, the callers skip such points)
+  // that stay live through the whole search).  A NaN component fails both compares and stays NaN: grid_axis puts it in
+  // cell 0, every distance is NaN and no candidate wins, so the search ends unresolved with ~0ull.  The half-iteration
+  // kernels skip such source points; gs_grid_query_kernel does not, its brute-force pass then answers (+inf, 0).
   c.px = qx < g.ox ? g.ox : (qx > g.mx ? g.mx : qx);
   c.py = qy < g.oy ? g.oy : (qy > g.my ? g.my : qy);
   c.pz = qz < g.oz ? g.oz : (qz > g.mz ? g.mz : qz);

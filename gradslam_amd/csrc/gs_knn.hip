@@ -417,8 +417,13 @@ __global__ void __launch_bounds__(GQ_BLOCK) gs_grid_query_kernel(
   }
   bool done;
   const unsigned long long key = grid_search_group(g, cell_start, sorted, qx, qy, qz, lane, &done);
+  // A best distance of +inf is no answer: the sequential scan (`d < best`, best armed with +inf) never lets such a
+  // candidate win and returns (+inf, 0).  A grid with no cell behind any face of the 2x2x2 block (one or two cells per
+  // axis) calls whatever it found proven, +inf included, and would return the lowest index IN ITS CELLS -- not 0 when
+  // target 0 is not finite.  Such a query joins the unresolved ones; the brute-force pass writes (+inf, 0).
+  const bool found = done && __uint_as_float((uint32_t)(key >> 32)) < __builtin_inff();
   if (lane == 0) {
-    if (done) {
+    if (found) {
       best[s] = key;
     } else {
       best[s] = ~0ull;  // finished by the brute-force pass
@@ -455,7 +460,10 @@ __global__ void __launch_bounds__(256) gs_knn_unpack_kernel(const unsigned long 
   if (i >= n) return;
   const unsigned long long b = best[i];
   int64_t j = (int64_t)(b & 0xffffffffull);
-  if (j >= n_tgt) j = 0;  // only when every distance was NaN
+  // (never taken behind the brute-force kernel, which this unpacks: every chunk block writes a key for every query, (+inf,
+  // chunk base) when no distance was below +inf -- NaN or overflowing distances, non-finite targets -- so the minimum is
+  // (+inf, 0), the sequential scan's answer; the guard stands for a best[] that no search has written)
+  if (j >= n_tgt) j = 0;
   idx[i] = j;
   if (d2) d2[i] = __uint_as_float((uint32_t)(b >> 32));
 }

@@ -12,6 +12,7 @@ import torch
 
 from gradslam_amd.datasets.synthetic import make_sequence
 from oracle import oracle as o
+from tests.knn_cases import surface   # (the sheet the edge cases of tests/test_hip_knn_edges.py are built on)
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,13 +42,6 @@ def check_same(ops, src, tgt, max_unresolved_frac=None):
     if max_unresolved_frac is not None:
         assert unres <= max_unresolved_frac * src.shape[0], (unres, src.shape[0])
     return unres
-
-
-def surface(rng, n, noise=0.0):
-    u, v = rng.random(n) * 2.4 - 1.2, rng.random(n) * 1.8 - 0.9
-    z = 2.0 + 0.3 * np.sin(3 * u) * np.cos(2.5 * v)
-    p = np.stack([u, v, z], -1)
-    return (p + noise * rng.standard_normal(p.shape)).astype(np.float32)
 
 
 def test_surface_like_icp_case(ops):
