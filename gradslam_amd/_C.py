@@ -240,6 +240,13 @@ _PROTOS = {
                                                  C.POINTER(PicpParams), _f, _f, _f, _f, _vp],
     "gs_projective_icp_scaled_backward_batch_f32": [C.POINTER(PicpBackwardSeq), _i32, _i32, _i32, C.POINTER(PicpParams),
                                                     _vp],
+    "gs_projective_icp_color_joint_scaled_scratch_bytes": [_i32, _i32, _i32],
+    "gs_projective_icp_color_joint_scaled_batch_f32": [C.POINTER(PicpColorSeq), C.POINTER(C.c_void_p),
+                                                       C.POINTER(C.c_void_p), _i32, _i32, _i32, C.POINTER(PicpParams),
+                                                       _f, _f, _f, _f, _f, _vp],
+    "gs_projective_icp_color_joint_scaled_rows_f32": [C.POINTER(PicpColorSeq), _i32, _i32, _i32, _f, _f, _f, _f, _f, _f,
+                                                      _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                      _vp, _vp, _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,
             "gs_knn1_grid_scratch_bytes": _i64, "gs_update_map_scratch_bytes": _i64, "gs_global_maps_pose_backward_scratch_bytes": _i64, "gs_icp_tape_bytes": _i64, "gs_icp_backward_scratch_bytes": _i64,
@@ -248,7 +255,8 @@ _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scrat
             "gs_prune_scratch_bytes": _i64, "gs_projective_icp_scratch_bytes": _i64,
             "gs_projective_icp_tape_bytes": _i64, "gs_projective_icp_backward_scratch_bytes": _i64,
             "gs_projective_icp_color_scratch_bytes": _i64, "gs_projective_icp_scaled_scratch_bytes": _i64,
-            "gs_projective_icp_color_scaled_scratch_bytes": _i64}
+            "gs_projective_icp_color_scaled_scratch_bytes": _i64,
+            "gs_projective_icp_color_joint_scaled_scratch_bytes": _i64}
 EXPORTS = tuple(_PROTOS)
 
 

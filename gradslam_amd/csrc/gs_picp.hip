@@ -124,6 +124,7 @@ struct PiPlain {
   static void fill(Batch& pb, int b, const Seq& u, float) { picp_fill_seq(pb.s[b], u, pb.g.nchunks); }
   static size_t scratch_bytes(int64_t nchunks) { return picp_partials_bytes(nchunks) + picp_counts_bytes(nchunks); }
   static void color_outputs(Batch&, const PiRowsOut&) {}
+  static void color_scale(Batch&, int, PiScaleSeq& z, bool) { z.color = nullptr; z.model = nullptr; }
 };
 
 extern "C" int gs_projective_icp_batch_f32(const gs_picp_seq* seqs_host, int B, int H, int W,
@@ -165,7 +166,7 @@ extern "C" int gs_projective_icp_scaled_batch_f32(const gs_picp_seq* seqs_host, 
                                                   const gs_picp_params* params_host, float huber_k, float huber_floor,
                                                   void* stream) {
   PICP_CHECK_SCALE(__func__, huber_k, huber_floor);
-  const PiScale sc{picp_scale_c(huber_k), huber_floor, deltas_host, nullptr};
+  const PiScale sc = picp_scale_geo(huber_k, huber_floor, deltas_host, nullptr);
   return picp_solve<PiPlain>(__func__, seqs_host, tapes_host, B, H, W, params_host, 0.0f, 0.0f, 0.0f, &sc, stream);
 }
 
@@ -174,7 +175,7 @@ extern "C" int gs_projective_icp_scaled_rows_f32(const gs_picp_seq* seq_host, in
                                                  int64_t* row, float* a6, float* b, float* weight, double* sums28,
                                                  int64_t* count, float* delta_out, void* stream) {
   PICP_CHECK_SCALE(__func__, huber_k, huber_floor);
-  const PiScale sc{picp_scale_c(huber_k), huber_floor, nullptr, delta_out};
+  const PiScale sc = picp_scale_geo(huber_k, huber_floor, nullptr, delta_out);
   return picp_rows<PiPlain>(__func__, seq_host, H, W, stride, dist_th, dot_th, 0.0f,
                             PiRobust{0.0f, 0.0f, weight, nullptr},
                             PiRowsOut{code, row, a6, b, nullptr, nullptr, nullptr, sums28, count, nullptr}, &sc, stream);

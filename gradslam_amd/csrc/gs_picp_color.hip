@@ -41,12 +41,18 @@
 // w as in gs_picp.hip for b, wc = |r| > cdelta ? cdelta / |r| : 1 for the colour residual r BEFORE the weight w is applied
 // (a threshold of 0: that weight is 1), terms (double)w * (x_g y_g) + (double)wc * (x_c y_c), each product exact and
 // rounded once by its weight.  With both thresholds 0 they launch the plain kernel.
-#include "gs_picp_dev.h"
+// The colour row itself (pic_color_row) lives in gs_picp_color_dev.h: the residual pass of the median rule
+// (gs_picp_scale.hip) forms r with it too.  The joint scaled entries (gs_projective_icp_color_joint_scaled_*) estimate
+// cdelta per sequence and iteration from the lower median of |r| over the slots with a colour row; the ROBUST instance
+// then reads it from the sequence's device float (PicSeq::cdelta_dev) instead of the launch's constant.
+#include "gs_picp_color_dev.h"
 
 struct PicSeq {
   PiSeq g;
   const float* color;       // live frame (H, W, 3)
   const float4* model;      // model intensity (H, W)
+  const float* cdelta_dev;  // the sequence's colour Huber threshold of this iteration (gs_picp_scale.hip), or NULL:
+                            // PiRobust::cdelta
   int32_t* ccounts;         // (nchunks) colour rows per chunk
   int32_t* cflag_out;       // table-level outputs, any may be NULL: (nslots)
   float* ac_out;            // (nslots, 6)
@@ -58,27 +64,6 @@ struct PicBatch {
   PiGeom g;
   float weight;
 };
-
-GS_DEV float pic_luma(const float r, const float g, const float b) {
-  const float t = 0.299f * r + 0.587f * g;
-  return t + 0.114f * b;
-}
-
-// the continuous pixel (u, v) of the camera-frame point q: the operations of gs_project_point_hw_q
-GS_DEV void pic_project_uv(const GsCamera& c, const float* q, float& u, float& v) {
-  float r[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    float acc = c.K[4 * j] * q[0];
-    acc = acc + c.K[4 * j + 1] * q[1];
-    acc = acc + c.K[4 * j + 2] * q[2];
-    acc = acc + c.K[4 * j + 3] * 1.0f;
-    r[j] = acc;
-  }
-  const float zz = (r[2] != 0.0f) ? r[2] : 1.0f;
-  u = r[0] / zz;
-  v = r[1] / zz;
-}
 
 // ------------------------------------------------------------------ model intensity
 constexpr int PIC_TX = 32, PIC_TY = 8;   // 256 threads: a row of the tile is 32 pixels = 384 contiguous bytes of colour
@@ -157,6 +142,7 @@ GS_DEV void pic_linearize(const PicBatch& pb, const PiRobust& rb) {
   float z[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, zc[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   float w = 1.0f, wc = 1.0f;
   const float delta = ROBUST ? pi_huber_delta(q.delta_dev, rb) : 0.0f;
+  const float cdelta = ROBUST ? (qc.cdelta_dev ? *qc.cdelta_dev : rb.cdelta) : 0.0f;
   if (t.in_lattice) {
     float s[3];
     float4 d, m;
@@ -164,34 +150,9 @@ GS_DEV void pic_linearize(const PicBatch& pb, const PiRobust& rb) {
     if (code == 0) {
       gn_row_pn(s[0], s[1], s[2], d, m, z, z[6]);
       if (ROBUST) w = pi_huber_weight(pi_huber_clipped(z[6], delta), z[6], delta);
-      // the pixel the association read, again, with the camera-frame point (the same device function on the same
-      // operands: the same (h2, w2), inside the view -- the slot would be code 2 otherwise)
-      int h2 = 0, w2 = 0;
-      float cq[3];
-      gs_project_point_hw_q(cam, s[0], s[1], s[2], pb.g.H, pb.g.W, pb.g.u_hi, pb.g.v_hi, h2, w2, cq);
-      const float4 M = qc.model[(int64_t)h2 * pb.g.W + w2];   // (I, gx, gy, ok)
-      colored = M.w == 1.0f;
-      if (colored) {
-        float u, v;
-        pic_project_uv(cam, cq, u, v);
-        const float Il = pic_luma(qc.color[3 * t.p], qc.color[3 * t.p + 1], qc.color[3 * t.p + 2]);
-        const float lin = M.x + M.y * (u - (float)w2);
-        const float r = Il - (lin + M.z * (v - (float)h2));
-        const float ax = M.y * cam.K[0], ay = M.z * cam.K[5];
-        const float j0 = ax / cq[2], j1 = ay / cq[2];
-        const float j2 = (-(ax * cq[0] + ay * cq[1])) / (cq[2] * cq[2]);
-        // R_m[j][k] = cam.Ri[3 * k + j]
-        const float J0 = gs_dot3_plain(cam.Ri[0], cam.Ri[3], cam.Ri[6], j0, j1, j2);
-        const float J1 = gs_dot3_plain(cam.Ri[1], cam.Ri[4], cam.Ri[7], j0, j1, j2);
-        const float J2 = gs_dot3_plain(cam.Ri[2], cam.Ri[5], cam.Ri[8], j0, j1, j2);
-        const float wgt = pb.weight;
-        zc[0] = wgt * J0; zc[1] = wgt * J1; zc[2] = wgt * J2;
-        zc[3] = wgt * (J2 * s[1] - J1 * s[2]);
-        zc[4] = wgt * (J0 * s[2] - J2 * s[0]);
-        zc[5] = wgt * (J1 * s[0] - J0 * s[1]);
-        zc[6] = wgt * r;
-        if (ROBUST) wc = pi_huber_weight(pi_huber_clipped(r, rb.cdelta), r, rb.cdelta);
-      }
+      float r = 0.0f;
+      colored = pic_color_row(cam, pb.g, qc.color, qc.model, t.p, s, pb.weight, zc, r);
+      if (ROBUST && colored) wc = pi_huber_weight(pi_huber_clipped(r, cdelta), r, cdelta);
     }
     pi_table_out(q, t.k, code, row, z);
     if (qc.cflag_out) qc.cflag_out[t.k] = colored ? 1 : 0;
@@ -281,6 +242,7 @@ struct PiJoint {
     picp_fill_seq(s.g, u.base, nchunks);
     s.color = u.color;
     s.model = reinterpret_cast<const float4*>(u.model_intensity);
+    s.cdelta_dev = nullptr;
     s.ccounts = reinterpret_cast<int32_t*>(static_cast<char*>(u.base.scratch) + picp_partials_bytes(nchunks) +
                                            picp_counts_bytes(nchunks));
     s.cflag_out = nullptr; s.ac_out = nullptr; s.bc_out = nullptr; s.ccount_out = nullptr;
@@ -289,6 +251,14 @@ struct PiJoint {
   static void color_outputs(Batch& pb, const PiRowsOut& o) {
     PicSeq& s = pb.s[0];
     s.ac_out = o.ac6; s.bc_out = o.bc; s.cflag_out = o.colored; s.ccount_out = o.color_count;
+  }
+  // the colour side of the median rule: the residual pass reads the sequence's colour inputs, and with a colour
+  // threshold asked for the sequence reads it from the rule's device float
+  static void color_scale(Batch& pb, int b, PiScaleSeq& z, bool col) {
+    PicSeq& s = pb.s[b];
+    z.color = s.color;
+    z.model = s.model;
+    if (col) s.cdelta_dev = z.r[PS_COLOR].delta_dev;
   }
 };
 
@@ -311,9 +281,43 @@ extern "C" int gs_projective_icp_color_scaled_batch_f32(const gs_picp_color_seq*
                                                         float color_weight, float huber_k, float huber_floor,
                                                         float color_huber_delta, void* stream) {
   PICP_CHECK_SCALE(__func__, huber_k, huber_floor);
-  const PiScale sc{picp_scale_c(huber_k), huber_floor, deltas_host, nullptr};
+  const PiScale sc = picp_scale_geo(huber_k, huber_floor, deltas_host, nullptr);
   return picp_solve<PiJoint>(__func__, seqs_host, nullptr, B, H, W, params_host, color_weight, 0.0f, color_huber_delta,
                              &sc, stream);
+}
+
+// The joint solve with either threshold, or both, from its residuals' median (gs_picp_scale.hip): huber_k > 0: the
+// geometric one from |b| over the used slots, huber_floor its floor; color_huber_k > 0: the colour one from |r| (the
+// colour residual before color_weight is applied) over the slots with a colour row, color_huber_floor its floor.  A
+// constant of 0 leaves that threshold the constant its floor names (0: off).  The same two extra launches per iteration
+// whichever are asked for.  The scratch is gs_projective_icp_color_joint_scaled_scratch_bytes.
+static int pic_check_joint_scale(const char* who, float huber_k, float huber_floor, float color_huber_k,
+                                 float color_huber_floor) {
+  PICP_REQUIRE(who, huber_k >= 0.0f && huber_k < __builtin_inff(), "huber_k must be finite and not negative");
+  PICP_REQUIRE(who, huber_floor >= 0.0f && huber_floor < __builtin_inff(), "huber_floor must be finite and not negative");
+  PICP_REQUIRE(who, color_huber_k >= 0.0f && color_huber_k < __builtin_inff(),
+               "color_huber_k must be finite and not negative");
+  PICP_REQUIRE(who, color_huber_floor >= 0.0f && color_huber_floor < __builtin_inff(),
+               "color_huber_floor must be finite and not negative");
+  return GS_OK;
+}
+
+extern "C" int64_t gs_projective_icp_color_joint_scaled_scratch_bytes(int H, int W, int stride) {
+  const int64_t base = gs_projective_icp_color_scratch_bytes(H, W, stride);
+  return base > 0 ? (int64_t)picp_joint_scaled_bytes((size_t)base, picp_slots(H, W, stride)) : 0;
+}
+
+extern "C" int gs_projective_icp_color_joint_scaled_batch_f32(const gs_picp_color_seq* seqs_host,
+                                                              float* const* deltas_host, float* const* cdeltas_host,
+                                                              int B, int H, int W, const gs_picp_params* params_host,
+                                                              float color_weight, float huber_k, float huber_floor,
+                                                              float color_huber_k, float color_huber_floor,
+                                                              void* stream) {
+  if (const int err = pic_check_joint_scale(__func__, huber_k, huber_floor, color_huber_k, color_huber_floor)) return err;
+  const PiScale sc = picp_scale_joint(huber_k, huber_floor, color_huber_k, color_huber_floor, deltas_host, cdeltas_host,
+                                      nullptr, nullptr);
+  return picp_solve<PiJoint>(__func__, seqs_host, nullptr, B, H, W, params_host, color_weight, huber_floor,
+                             color_huber_floor, sc.on[PS_GEO] || sc.on[PS_COLOR] ? &sc : nullptr, stream);
 }
 
 extern "C" int gs_projective_icp_color_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
@@ -336,4 +340,23 @@ extern "C" int gs_projective_icp_color_robust_rows_f32(const gs_picp_color_seq* 
   return picp_rows<PiJoint>(__func__, seq_host, H, W, stride, dist_th, dot_th, color_weight,
                             PiRobust{huber_delta, color_huber_delta, weight, color_weight_out},
                             PiRowsOut{code, row, a6, b, ac6, bc, colored, sums28, count, color_count}, nullptr, stream);
+}
+
+// one joint linearisation with the thresholds derived at init_pose16 as in gs_projective_icp_color_joint_scaled_batch_f32;
+// delta_out / cdelta_out (one float each, may be NULL): the thresholds the weights were taken with
+extern "C" int gs_projective_icp_color_joint_scaled_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
+                                                             float dist_th, float dot_th, float color_weight,
+                                                             float huber_k, float huber_floor, float color_huber_k,
+                                                             float color_huber_floor, int32_t* code, int64_t* row,
+                                                             float* a6, float* b, float* ac6, float* bc,
+                                                             int32_t* colored, float* weight, float* color_weight_out,
+                                                             double* sums28, int64_t* count, int64_t* color_count,
+                                                             float* delta_out, float* cdelta_out, void* stream) {
+  if (const int err = pic_check_joint_scale(__func__, huber_k, huber_floor, color_huber_k, color_huber_floor)) return err;
+  const PiScale sc = picp_scale_joint(huber_k, huber_floor, color_huber_k, color_huber_floor, nullptr, nullptr, delta_out,
+                                      cdelta_out);
+  return picp_rows<PiJoint>(__func__, seq_host, H, W, stride, dist_th, dot_th, color_weight,
+                            PiRobust{huber_floor, color_huber_floor, weight, color_weight_out},
+                            PiRowsOut{code, row, a6, b, ac6, bc, colored, sums28, count, color_count},
+                            sc.on[PS_GEO] || sc.on[PS_COLOR] ? &sc : nullptr, stream);
 }

@@ -256,32 +256,48 @@ GS_DEV void pi_table_out(const PiSeq& q, const int k, const int code, const int6
 }
 
 // ------------------------------------------------------------------ the median rule (gs_picp_scale.hip)
-// What the two launches in front of a robust linearisation need of a sequence: they find the lower median of |b| over
-// the used slots at T_in and leave delta = max(c * median, floor) in *delta_dev (and in *delta_out when not NULL).
-struct PiScaleSeq {
-  PiInputs in;
-  const float* T_in;
-  uint32_t* keys;      // (nslots): bits(|b|) of a used slot, 0xFFFFFFFF elsewhere
-  uint32_t* hist;      // (GS_PS_BINS): used slots per value of the keys' top 11 bits; zero between the iterations (the
+// What the two launches in front of a robust linearisation need of a sequence.  The rule serves two residuals, each
+// with its own tables: the point-to-plane residual b over the used slots (PS_GEO) and, in the joint solve, the colour
+// residual r before color_weight is applied over the slots with a colour row (PS_COLOR).  For every residual asked for
+// they find the lower median of its absolute values at T_in and leave max(c * median, floor) in *delta_dev (and in
+// *delta_out when not NULL).
+constexpr int PS_GEO = 0, PS_COLOR = 1, PS_RESIDUALS = 2;
+struct PiScaleRes {
+  uint32_t* keys;      // (nslots): bits(|residual|) of a slot that has the row, 0xFFFFFFFF elsewhere
+  uint32_t* hist;      // (GS_PS_BINS): such slots per value of the keys' top 11 bits; zero between the iterations (the
                        // residual pass adds to it, the select block reads it and clears it; a call clears it first)
   float* delta_dev;
   float* delta_out;    // this iteration's entry of the caller's threshold table, or NULL
+};
+struct PiScaleSeq {
+  PiInputs in;
+  const float* T_in;
+  const float* color;     // the colour inputs of the joint solve (gs_picp_color.hip's PicSeq), read for PS_COLOR only
+  const float4* model;
+  PiScaleRes r[PS_RESIDUALS];
 };
 struct PiScaleBatch {
   PiScaleSeq s[GS_MAX_BATCH];
   PiGeom g;
 };
-// the caller's side of the rule: c = (float)huber_k * 1.4826f, the floor, and per sequence the device table of numiters
-// thresholds (deltas_host, or NULL; the rows entry: delta_out, one float)
+// what the launches take by value: the residuals asked for are first .. first + count - 1, each with its constant
+// c = (float)huber_k * 1.4826f and its floor
+struct PiScalePick {
+  float c[PS_RESIDUALS], floor[PS_RESIDUALS];
+  int first, count;
+};
+// the caller's side of the rule: which residuals (on), their constants and floors, and per sequence the device table of
+// numiters thresholds (deltas_host, or NULL; the rows entry: delta_out, one float)
 struct PiScale {
-  float c, floor;
-  float* const* deltas_host;
-  float* delta_out;
+  bool on[PS_RESIDUALS];
+  float c[PS_RESIDUALS], floor[PS_RESIDUALS];
+  float* const* deltas_host[PS_RESIDUALS];
+  float* delta_out[PS_RESIDUALS];
 };
 // the residual pass and the select, enqueued back to back (defined in gs_picp_scale.hip); first: the call's first use of
-// the descriptors: one more launch in front clears every sequence's counters (after it the select block leaves them
+// the descriptors: one more launch in front clears every sequence's counters (after it the select blocks leave them
 // cleared)
-void picp_scale_launch(const PiScaleBatch& sb, float c, float floor, bool first, hipStream_t st);
+void picp_scale_launch(const PiScaleBatch& sb, const PiScalePick& pk, bool first, hipStream_t st);
 
 constexpr int GS_PS_BINS = 2048;   // values of an 11-bit digit of a key
 static inline size_t picp_keys_bytes(int64_t nslots) { return gs_align((size_t)nslots * sizeof(uint32_t)); }
@@ -290,7 +306,31 @@ static inline size_t picp_hist_bytes() { return gs_align(GS_PS_BINS * sizeof(uin
 static inline size_t picp_scaled_bytes(size_t base, int64_t nslots) {
   return base + picp_keys_bytes(nslots) + picp_hist_bytes() + gs_align(sizeof(float));
 }
+// ... and with the colour residual's tables behind the geometric ones: the same three again
+static inline size_t picp_joint_scaled_bytes(size_t base, int64_t nslots) {
+  return picp_scaled_bytes(picp_scaled_bytes(base, nslots), nslots);
+}
 static inline float picp_scale_c(float huber_k) { return huber_k * 1.4826f; }
+static inline PiScale picp_scale_joint(float huber_k, float huber_floor, float color_huber_k, float color_huber_floor,
+                                       float* const* deltas_host, float* const* cdeltas_host, float* delta_out,
+                                       float* cdelta_out) {
+  return PiScale{{huber_k > 0.0f, color_huber_k > 0.0f},
+                 {picp_scale_c(huber_k), picp_scale_c(color_huber_k)},
+                 {huber_floor, color_huber_floor},
+                 {deltas_host, cdeltas_host},
+                 {delta_out, cdelta_out}};
+}
+// the geometric threshold alone (the scaled entries of the plain solve; the joint solve with a constant colour threshold)
+static inline PiScale picp_scale_geo(float huber_k, float huber_floor, float* const* deltas_host, float* delta_out) {
+  return picp_scale_joint(huber_k, huber_floor, 0.0f, 0.0f, deltas_host, nullptr, delta_out, nullptr);
+}
+static inline PiScalePick picp_scale_pick(const PiScale& sc) {
+  PiScalePick pk;
+  for (int i = 0; i < PS_RESIDUALS; ++i) { pk.c[i] = sc.c[i]; pk.floor[i] = sc.floor[i]; }
+  pk.first = sc.on[PS_GEO] ? PS_GEO : PS_COLOR;
+  pk.count = (sc.on[PS_GEO] ? 1 : 0) + (sc.on[PS_COLOR] ? 1 : 0);
+  return pk;
+}
 #define PICP_CHECK_SCALE(who, k, fl)                                                                    \
   do {                                                                                                  \
     PICP_REQUIRE(who, (k) > 0.0f && (k) < __builtin_inff(), "huber_k must be finite and positive");     \
@@ -443,6 +483,8 @@ static inline void picp_fill_seq(PiSeq& s, const gs_picp_seq& u, int nchunks) {
 //   X::check(who, u)      the checks of a Seq (GS_OK or the error)
 //   X::fill(pb, b, u, color_weight)      sequence b of the batch from u, the scratch carved, every output NULL
 //   X::color_outputs(pb, o)       the colour tables of o into sequence 0
+//   X::color_scale(pb, b, z, col) the colour inputs of sequence b into z, the descriptor of the median rule; col: the
+//                                 sequence reads its colour threshold from z's device float (the plain solve: nothing)
 //   X::scratch_bytes(nchunks)     bytes of a sequence's scratch (the median rule's keys and threshold lie behind them)
 // The plain entries pass color_weight = cdelta = 0 and no colour tables; the checks of these pass.
 
@@ -458,17 +500,23 @@ struct PiRowsOut {
 
 // a sequence's descriptor of the median rule: the inputs of s, the scratch behind the solve's own (16-byte aligned, which
 // the scaled entries check: the select block reads the keys four at a time); s then reads its threshold from the rule's
-// device float
+// device float.  The colour residual's tables lie behind the geometric ones (picp_joint_scaled_bytes) and are touched
+// only when the colour threshold is asked for
 template <typename X>
-static void picp_fill_scale(PiScaleSeq& z, PiSeq& s, const gs_picp_seq& u, const PiGeom& g) {
+static void picp_fill_scale(PiScaleSeq& z, typename X::Batch& pb, int b, const gs_picp_seq& u, const PiScale& sc) {
+  const PiGeom& g = pb.g;
+  PiSeq& s = X::seq(pb, b);
   char* p = static_cast<char*>(u.scratch) + X::scratch_bytes(g.nchunks);
   z.in = s.in;
   z.T_in = s.T_in;
-  z.keys = reinterpret_cast<uint32_t*>(p);
-  z.hist = reinterpret_cast<uint32_t*>(p + picp_keys_bytes(g.nslots));
-  z.delta_dev = reinterpret_cast<float*>(p + picp_keys_bytes(g.nslots) + picp_hist_bytes());
-  z.delta_out = nullptr;
-  s.delta_dev = z.delta_dev;
+  for (int i = 0; i < PS_RESIDUALS; ++i, p += picp_scaled_bytes(0, g.nslots)) {
+    z.r[i].keys = reinterpret_cast<uint32_t*>(p);
+    z.r[i].hist = reinterpret_cast<uint32_t*>(p + picp_keys_bytes(g.nslots));
+    z.r[i].delta_dev = reinterpret_cast<float*>(p + picp_keys_bytes(g.nslots) + picp_hist_bytes());
+    z.r[i].delta_out = nullptr;
+  }
+  if (sc.on[PS_GEO]) s.delta_dev = z.r[PS_GEO].delta_dev;
+  X::color_scale(pb, b, z, sc.on[PS_COLOR]);
 }
 
 // the solve behind the batch entries; tapes_host: per sequence the device buffer of numiters tape rows, or NULL
@@ -488,7 +536,8 @@ static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* c
   for (int b = 0; b < B; ++b) {
     if (const int err = X::check(who, seqs_host[b])) return err;
     PICP_REQUIRE(who, X::base(seqs_host[b]).out_pose16, "NULL pointer (out_pose16)");
-    PICP_REQUIRE(who, !sc || !sc->deltas_host || sc->deltas_host[b], "NULL pointer (deltas)");
+    for (int i = 0; sc && i < PS_RESIDUALS; ++i)
+      PICP_REQUIRE(who, !sc->on[i] || !sc->deltas_host[i] || sc->deltas_host[i][b], "NULL pointer (deltas)");
     PICP_REQUIRE(who, !sc || ((uintptr_t)X::base(seqs_host[b]).scratch & 15) == 0, "scratch must be 16-byte aligned");
     PICP_REQUIRE(who, !tapes_host || (tapes_host[b] && ((uintptr_t)tapes_host[b] & 7) == 0), "NULL or misaligned tape");
   }
@@ -504,7 +553,7 @@ static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* c
     for (int b = 0; b < nb; ++b) {
       X::fill(pb, b, seqs_host[c0 + b], color_weight);
       X::seq(pb, b).T_out = X::base(seqs_host[c0 + b]).out_pose16;
-      if (sc) picp_fill_scale<X>(sb.s[b], X::seq(pb, b), X::base(seqs_host[c0 + b]), pb.g);
+      if (sc) picp_fill_scale<X>(sb.s[b], pb, b, X::base(seqs_host[c0 + b]), *sc);
     }
     const unsigned blocks = (unsigned)nb * (unsigned)pb.g.nchunks;   // < 8 * 2^23
     for (int it = 0; it < prm.numiters; ++it) {
@@ -516,10 +565,11 @@ static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* c
         s.tape_row = tapes_host ? static_cast<PiTapeRow*>(tapes_host[c0 + b]) + it : nullptr;
         if (sc) {
           sb.s[b].T_in = s.T_in;
-          sb.s[b].delta_out = sc->deltas_host ? sc->deltas_host[c0 + b] + it : nullptr;
+          for (int i = 0; i < PS_RESIDUALS; ++i)
+            sb.s[b].r[i].delta_out = sc->on[i] && sc->deltas_host[i] ? sc->deltas_host[i][c0 + b] + it : nullptr;
         }
       }
-      if (sc) picp_scale_launch(sb, sc->c, sc->floor, it == 0, st);
+      if (sc) picp_scale_launch(sb, picp_scale_pick(*sc), it == 0, st);
       if (robust)
         hipLaunchKernelGGL(X::robust_linearize, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, rb);
       else
@@ -557,9 +607,9 @@ static int picp_rows(const char* who, const typename X::Seq* seq_host, int H, in
   if (sc) {   // the threshold at init_pose16 first: two launches in front of the robust linearisation
     PiScaleBatch sb;
     sb.g = pb.g;
-    picp_fill_scale<X>(sb.s[0], s, X::base(*seq_host), pb.g);
-    sb.s[0].delta_out = sc->delta_out;
-    picp_scale_launch(sb, sc->c, sc->floor, true, st);
+    picp_fill_scale<X>(sb.s[0], pb, 0, X::base(*seq_host), *sc);
+    for (int i = 0; i < PS_RESIDUALS; ++i) sb.s[0].r[i].delta_out = sc->on[i] ? sc->delta_out[i] : nullptr;
+    picp_scale_launch(sb, picp_scale_pick(*sc), true, st);
   }
   if (sc || rb.delta > 0.0f || rb.cdelta > 0.0f || rb.weight_out || rb.cweight_out)
     hipLaunchKernelGGL(X::robust_linearize, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb, rb);

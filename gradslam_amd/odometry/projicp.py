@@ -7,7 +7,8 @@ search.  The result is detached unless `differentiable` is set: the poses are th
 is the joint geometric + photometric one (gs_projective_icp_color_batch_f32): the view's colour image is rendered too and
 the live frame's colour is compared with it.  `huber_delta` / `color_huber_delta` > 0 switch on Huber weights
 (the *_robust_* entry points): rows with a large residual are down-weighted instead of pulling the pose at full weight.
-`huber_k` > 0 estimates the geometric threshold from the residuals in every iteration (the *_scaled_* entry points)."""
+`huber_k` > 0 estimates the geometric threshold from the residuals in every iteration (the *_scaled_* entry points),
+`color_huber_k` > 0 the colour threshold from the colour residuals (the *_joint_scaled_* entry points)."""
 from typing import Optional, Union
 
 import torch
@@ -49,8 +50,13 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
         huber_k: the geometric Huber threshold from the residuals themselves (0, the default: off): in every iteration
             delta = max(huber_k * 1.4826 * median|b|, huber_delta) over the used pairs, so `huber_delta` becomes a floor
             and no threshold has to be tuned per dataset; 1.345 is the usual constant.  Works with `differentiable=True`
-            (the thresholds are constants of the backward pass) and with `color_weight` (the colour threshold stays the
-            constant `color_huber_delta`).
+            (the thresholds are constants of the backward pass) and with `color_weight` (without `color_huber_k` the
+            colour threshold stays the constant `color_huber_delta`).
+        color_huber_k: the colour Huber threshold from the colour residuals themselves (0, the default: off): in every
+            iteration cdelta = max(color_huber_k * 1.4826 * median|r|, color_huber_delta) over the pairs with a colour
+            row, r the colour residual before `color_weight` is applied; `color_huber_delta` becomes a floor.  The
+            threshold is in the residuals' own units, so the same constant serves colours in 0 ... 1 and in 0 ... 255;
+            1.345 is the usual constant.  Needs `color_weight` > 0; combines with `huber_delta` and `huber_k`.
 
     Unlike the point-cloud-pair providers it needs the map and the live frame themselves: call
     `localize(pointclouds, live_frame, prev_poses)`."""
@@ -59,7 +65,8 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                  angle_thresh: Union[float, int] = 30, stride: Optional[int] = None,
                  min_confidence: Union[float, int] = 0.0, radius: int = 0, differentiable: bool = False,
                  color_weight: Union[float, int] = 0.0, huber_delta: Union[float, int] = 0.0,
-                 color_huber_delta: Union[float, int] = 0.0, huber_k: Union[float, int] = 0.0):
+                 color_huber_delta: Union[float, int] = 0.0, huber_k: Union[float, int] = 0.0,
+                 color_huber_k: Union[float, int] = 0.0):
         from .. import ops
         if not isinstance(differentiable, bool):
             raise TypeError("differentiable must be of type bool; but was of type {}.".format(type(differentiable)))
@@ -74,6 +81,11 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             raise ValueError("color_huber_delta > 0 needs color_weight > 0: it is the Huber threshold of the colour term")
         ops._picp_huber_k(huber_k, "ProjectiveICPOdometryProvider")
         self.huber_k = huber_k
+        ops._picp_color_huber_k(color_huber_k, "ProjectiveICPOdometryProvider")
+        if color_huber_k > 0 and not color_weight > 0:
+            raise ValueError("color_huber_k > 0 needs color_weight > 0: it estimates the Huber threshold of the colour "
+                             "term")
+        self.color_huber_k = color_huber_k
         self.color_weight = color_weight   # (carried next to _kwargs(): the plain solve does not take it)
         self.huber_delta = huber_delta     # (as are the Huber thresholds)
         self.color_huber_delta = color_huber_delta
@@ -154,7 +166,7 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                            view.index[:, 0], poses, maps, poses, fr.rgb_image[:, 0], model,
                                            color_weight=self.color_weight, out=out.view(B, 4, 4),
                                            huber_delta=self.huber_delta, color_huber_delta=self.color_huber_delta,
-                                           huber_k=self.huber_k, **self._kwargs())
+                                           huber_k=self.huber_k, color_huber_k=self.color_huber_k, **self._kwargs())
             return out
         view = ops.render_map_batch([(m[0], None) + m[2:] for m in maps], poses.view(B, 1, 4, 4), K, H, W,
                                     radius=self.radius, min_confidence=self.min_confidence)

@@ -963,6 +963,22 @@ def _picp_huber_k(huber_k, who="projective_icp"):
     return float(huber_k)
 
 
+def _picp_color_huber_k(color_huber_k, who, weight=None):
+    """the value check of the colour residual's median-rule constant (cdelta = color_huber_k * 1.4826 * median|r| per
+    iteration): a finite number >= 0, 0 = off (color_huber_delta is then the constant threshold it always was); weight:
+    the colour weight of the call, without which there is no colour residual to estimate from"""
+    import math
+    if isinstance(color_huber_k, bool) or not isinstance(color_huber_k, (float, int)):
+        raise TypeError("{}: color_huber_k must be of type float or int; but was of type {}.".format(
+            who, type(color_huber_k)))
+    if not (math.isfinite(color_huber_k) and color_huber_k >= 0):
+        raise ValueError("{}: color_huber_k ({}) must be finite and not negative.".format(who, color_huber_k))
+    if color_huber_k > 0 and weight is not None and not weight > 0:
+        raise ValueError("{}: color_huber_k > 0 needs color_weight > 0: it estimates the Huber threshold of the colour "
+                         "term".format(who))
+    return float(color_huber_k)
+
+
 def _picp_flag(who, name, val):
     if not isinstance(val, bool):
         raise TypeError("{}: {} must be of type bool; but was of type {}.".format(who, name, type(val)))
@@ -987,10 +1003,12 @@ def _picp_nslots(H, W, stride):
     return ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
 
 
-def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, color=False, scaled=False):
+def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, color=False, scaled=False,
+               color_scaled=False):
     """Shape / dtype / device checks shared by the batched solve and the table-level call; fills the descriptors.
     Returns (seqs, tensors kept alive, device, B, H, W).  color: the scratch is sized for the colour solve (the plain
-    layout plus the colour-row counts); scaled: ... plus the key table and the threshold of the median rule."""
+    layout plus the colour-row counts); scaled: ... plus the key table and the threshold of the median rule; color_scaled
+    (with color): ... plus the same again for the colour residual."""
     tensors = (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                ("model_pose", model_poses), ("init_pose", init_poses))
     _picp_tensors(who, tensors)
@@ -1028,6 +1046,8 @@ def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_pos
     sizer = {(False, False): L.gs_projective_icp_scratch_bytes, (True, False): L.gs_projective_icp_color_scratch_bytes,
              (False, True): L.gs_projective_icp_scaled_scratch_bytes,
              (True, True): L.gs_projective_icp_color_scaled_scratch_bytes}[(bool(color), bool(scaled))]
+    if color and color_scaled:
+        sizer = L.gs_projective_icp_color_joint_scaled_scratch_bytes
     nbytes = sizer(H, W, int(stride))
     seqs = (_C.PicpSeq * Bn)()
     P3, P1 = H * W * 12, H * W * 4
@@ -1415,7 +1435,8 @@ def _picp_color_seqs(who, seqs, held, Bn, H, W, color, model):
 def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, maps, init_poses, color, model, *,
                                color_weight, stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0,
                                return_trace=False, out=None, differentiable=False, huber_delta=0.0,
-                               color_huber_delta=0.0, huber_k=0.0, return_scale=False):
+                               color_huber_delta=0.0, huber_k=0.0, return_scale=False, color_huber_k=0.0,
+                               return_color_scale=False):
     """projective_icp_batch with a photometric term (gs_projective_icp_color_batch_f32: the same two launches per
     iteration for 8 sequences, nothing read back).  The arguments of projective_icp_batch, then color (B, H, W, 3): the
     live frames' colour, and model (B, H, W, 4): model_intensity of the views' rendered colour and index images.  A slot
@@ -1429,9 +1450,21 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
     on the colour residual before color_weight is applied (gs_projective_icp_color_robust_batch_f32); the trace's second
     column is then the weighted joint sum of squares.
     huber_k, return_scale: as in projective_icp_batch, for the GEOMETRIC threshold (gs_projective_icp_color_scaled_batch_f32:
-    the median of |b|, huber_delta its floor); color_huber_delta stays a constant."""
+    the median of |b|, huber_delta its floor); without color_huber_k, color_huber_delta stays a constant.
+    color_huber_k (0 = off; 1.345 is the usual constant): the COLOUR threshold is estimated from the colour residuals, per
+    sequence and per iteration: cdelta = max(color_huber_k * 1.4826 * median|r|, color_huber_delta), with the lower median
+    of |r| -- the colour residual before color_weight is applied -- over the slots that have a colour row at the pose the
+    iteration linearises at (gs_projective_icp_color_joint_scaled_batch_f32); color_huber_delta is then a floor.  The
+    threshold is in the units of the residuals, so colours in 0 ... 1 and in 0 ... 255 need no different constant.  It
+    needs color_weight > 0 and combines with huber_delta and huber_k freely: the same two extra launches per iteration
+    whichever of the two thresholds are estimated.  An iteration without a colour row, or whose median is 0, has
+    cdelta = color_huber_delta.
+    return_color_scale=True: the colour thresholds (B, numiters) float32 come after everything else in the returned
+    tuple (color_huber_k = 0: color_huber_delta in every entry)."""
     _picp_refuse_differentiable(differentiable)
     weight = _picp_color_weight(color_weight)
+    color_huber_k = _picp_color_huber_k(color_huber_k, "projective_icp_color", weight)
+    _picp_flag("projective_icp_color", "return_color_scale", return_color_scale)
     huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_color")
     huber_k = _picp_huber_k(huber_k, "projective_icp_color")
     _picp_flag("projective_icp_color", "return_scale", return_scale)
@@ -1439,12 +1472,19 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
     who = "projective_icp_color"
     seqs, held, dev, Bn, H, W = _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride,
-                                           color=True, scaled=huber_k > 0)
+                                           color=True, scaled=huber_k > 0, color_scaled=color_huber_k > 0)
     cseqs = _picp_color_seqs(who, seqs, held, Bn, H, W, color, model)
     T, trace, prm = _picp_outputs(who, [c.base for c in cseqs], dev, out, return_trace, PICP_COLOR_TRACE, stride,
                                   numiters, damp, dist_th, dot_th)
-    scale = None
-    if huber_k > 0:
+    scale = cscale = None
+    if color_huber_k > 0:
+        scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale and huber_k > 0 else (None, None)
+        cscale, cptrs = _picp_scale_table(Bn, numiters, dev) if return_color_scale else (None, None)
+        check(lib().gs_projective_icp_color_joint_scaled_batch_f32(cseqs, dptrs, cptrs, Bn, H, W, prm, weight, huber_k,
+                                                                   huber_delta, color_huber_k, color_huber_delta,
+                                                                   stream(dev)),
+              "gs_projective_icp_color_joint_scaled_batch_f32")
+    elif huber_k > 0:
         scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale else (None, None)
         check(lib().gs_projective_icp_color_scaled_batch_f32(cseqs, dptrs, Bn, H, W, prm, weight, huber_k, huber_delta,
                                                              color_huber_delta, stream(dev)),
@@ -1458,16 +1498,23 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
               "gs_projective_icp_color_batch_f32")
     if return_scale and scale is None:
         scale = torch.full((Bn, int(numiters)), huber_delta, dtype=f32, device=dev)
-    return _picp_pack(T, trace, scale, return_trace, return_scale)
+    if return_color_scale and cscale is None:
+        cscale = torch.full((Bn, int(numiters)), color_huber_delta, dtype=f32, device=dev)
+    res = _picp_pack(T, trace, scale, return_trace, return_scale)
+    if return_color_scale:
+        res = (res if isinstance(res, tuple) else (res,)) + (cscale,)
+    return res
 
 
 def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, color, model,
                          *, color_weight, n_dev=None, stride=1, numiters=10, damp=1e-8, dist_thresh=0.1,
                          angle_thresh=30.0, return_trace=False, differentiable=False, huber_delta=0.0,
-                         color_huber_delta=0.0, huber_k=0.0, return_scale=False):
+                         color_huber_delta=0.0, huber_k=0.0, return_scale=False, color_huber_k=0.0,
+                         return_color_scale=False):
     """projective_icp_color_batch for one sequence without the batch dimension (arguments as projective_icp, then color
     (H, W, 3) and model (H, W, 4)).  Returns the pose (4, 4) (and the trace (numiters, 9)).  huber_delta,
-    color_huber_delta, huber_k, return_scale: see projective_icp_color_batch."""
+    color_huber_delta, huber_k, return_scale, color_huber_k, return_color_scale (the thresholds (numiters,)): see
+    projective_icp_color_batch."""
     _picp_tensors("projective_icp_color", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K),
                                            ("index", index), ("model_pose", model_pose), ("init_pose", init_pose),
                                            ("color", color), ("model_intensity", model)))
@@ -1477,21 +1524,29 @@ def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points
                                    color.unsqueeze(0), model.unsqueeze(0), color_weight=color_weight, stride=stride,
                                    numiters=numiters, damp=damp, dist_thresh=dist_thresh, angle_thresh=angle_thresh,
                                    return_trace=return_trace, differentiable=differentiable, huber_delta=huber_delta,
-                                   color_huber_delta=color_huber_delta, huber_k=huber_k, return_scale=return_scale)
+                                   color_huber_delta=color_huber_delta, huber_k=huber_k, return_scale=return_scale,
+                                   color_huber_k=color_huber_k, return_color_scale=return_color_scale)
     return tuple(x[0] for x in r) if isinstance(r, tuple) else r[0]
 
 
 def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_points, map_normals, pose, color, model,
                               *, color_weight, n_dev=None, stride=1, dist_thresh=0.1, angle_thresh=30.0, huber_delta=0.0,
-                              color_huber_delta=0.0, return_weights=False):
+                              color_huber_delta=0.0, return_weights=False, huber_k=0.0, color_huber_k=0.0):
     """ONE joint linearisation at `pose` (gs_projective_icp_color_rows_f32), arguments as projective_icp_color.
     ProjectiveColorRows: code, row, a, b as projective_icp_rows; ac (nslots, 6), bc (nslots,): the colour row, zeros
     unless colored; colored int32 (nslots,): 1 where the slot is used and its model pixel has ok = 1; sums float64 (28,):
     the joint sums; count, color_count int64 (1,).
     huber_delta / color_huber_delta > 0 (gs_projective_icp_color_robust_rows_f32): sums are the Huber-weighted joint sums,
     the rows stay unweighted; return_weights=True returns (ProjectiveColorRows, weight, color_weight) float32 (nslots,):
-    the weight of a used slot and of a colour row, 0 elsewhere."""
+    the weight of a used slot and of a colour row, 0 elsewhere.
+    huber_k / color_huber_k > 0 (gs_projective_icp_color_joint_scaled_rows_f32): the geometric / the colour threshold is
+    derived at `pose` from the median of |b| over the used slots / of the colour residual |r| over the slots with a colour
+    row, huber_delta / color_huber_delta its floor (see projective_icp_color_batch); return_weights=True then returns
+    (ProjectiveColorRows, weight, color_weight, delta, cdelta): the two thresholds of this linearisation, float32 (1,)
+    each (the constant where its rule is off)."""
     weight = _picp_color_weight(color_weight)
+    huber_k = _picp_huber_k(huber_k, "projective_icp_color_rows")
+    color_huber_k = _picp_color_huber_k(color_huber_k, "projective_icp_color_rows", weight)
     huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_color_rows")
     color_huber_delta = _picp_huber("color_huber_delta", color_huber_delta, "projective_icp_color_rows")
     if not isinstance(return_weights, bool):
@@ -1504,12 +1559,25 @@ def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_p
     seqs, held, dev, _, H, W = _picp_seqs(who, vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0),
                                           K.reshape(1, 4, 4), index.unsqueeze(0), model_pose.reshape(1, 4, 4),
                                           [(map_points, map_normals, None, n_dev)], pose.reshape(1, 4, 4), stride,
-                                          color=True)
+                                          color=True, scaled=huber_k > 0 or color_huber_k > 0,
+                                          color_scaled=huber_k > 0 or color_huber_k > 0)
     cseqs = _picp_color_seqs(who, seqs, held, 1, H, W, color.unsqueeze(0), model.unsqueeze(0))
     ns = _picp_nslots(H, W, stride)
     e = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)   # noqa: E731
     res = ProjectiveColorRows(e(ns, torch.int32), e(ns, torch.int64), e((ns, 6), f32), e(ns, f32), e((ns, 6), f32),
                               e(ns, f32), e(ns, torch.int32), e(28, torch.float64), e(1, torch.int64), e(1, torch.int64))
+    if huber_k > 0 or color_huber_k > 0:
+        wt = (e(ns, f32), e(ns, f32)) if return_weights else (None, None)
+        # (a threshold whose rule is off is the constant: the library writes the estimated ones only)
+        th = (torch.full((1,), huber_delta, dtype=f32, device=dev),
+              torch.full((1,), color_huber_delta, dtype=f32, device=dev)) if return_weights else (None, None)
+        check(lib().gs_projective_icp_color_joint_scaled_rows_f32(cseqs, H, W, int(stride), dist_th, dot_th, weight,
+                                                                  huber_k, huber_delta, color_huber_k, color_huber_delta,
+                                                                  *[ptr(t) for t in res[:7]], ptr(wt[0]), ptr(wt[1]),
+                                                                  *[ptr(t) for t in res[7:]], ptr(th[0]), ptr(th[1]),
+                                                                  stream(dev)),
+              "gs_projective_icp_color_joint_scaled_rows_f32")
+        return (res,) + wt + th if return_weights else res
     if huber_delta > 0 or color_huber_delta > 0 or return_weights:
         wt = (e(ns, f32), e(ns, f32)) if return_weights else (None, None)
         check(lib().gs_projective_icp_color_robust_rows_f32(cseqs, H, W, int(stride), dist_th, dot_th, weight,

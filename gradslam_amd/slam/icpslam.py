@@ -42,7 +42,11 @@ class ICPSLAM(nn.Module):
     `ProjectiveICPOdometryProvider`.
 
     `huber_k` (0 by default, `odom="projicp"` only): the geometric Huber threshold from the residuals' median in every
-    iteration, `huber_delta` its floor (`ProjectiveICPOdometryProvider(huber_k=...)`)."""
+    iteration, `huber_delta` its floor (`ProjectiveICPOdometryProvider(huber_k=...)`).
+
+    `color_huber_k` (0 by default, `odom="projicp"` only; needs `color_weight`): the colour Huber threshold from the
+    colour residuals' median in every iteration, `color_huber_delta` its floor
+    (`ProjectiveICPOdometryProvider(color_huber_k=...)`)."""
 
     def __init__(self, *, odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0,
@@ -50,7 +54,7 @@ class ICPSLAM(nn.Module):
                  device: Union[torch.device, str, None] = None, depth_filter: Optional[dict] = None,
                  odom_differentiable: bool = False, color_weight: Union[float, int] = 0.0,
                  huber_delta: Union[float, int] = 0.0, color_huber_delta: Union[float, int] = 0.0,
-                 huber_k: Union[float, int] = 0.0):
+                 huber_k: Union[float, int] = 0.0, color_huber_k: Union[float, int] = 0.0):
         super().__init__()
         from .. import ops
         ops._picp_color_weight(color_weight)
@@ -67,6 +71,10 @@ class ICPSLAM(nn.Module):
         if huber_k > 0 and odom != "projicp":
             raise ValueError("huber_k is the Huber scale rule of odom='projicp' (got odom={!r})".format(odom))
         self.huber_k = huber_k
+        ops._picp_color_huber_k(color_huber_k, type(self).__name__)
+        if color_huber_k > 0 and odom != "projicp":
+            raise ValueError("color_huber_k is the colour Huber scale rule of odom='projicp' (got odom={!r})".format(odom))
+        self.color_huber_k = color_huber_k
         if not isinstance(odom_differentiable, bool):
             raise TypeError("odom_differentiable must be of type bool; but was of type {}.".format(
                 type(odom_differentiable)))
@@ -90,7 +98,8 @@ class ICPSLAM(nn.Module):
             odomprov = ProjectiveICPOdometryProvider(numiters, damp, 0.1 if dist_thresh is None else dist_thresh,
                                                      stride=dsratio, differentiable=odom_differentiable,
                                                      color_weight=color_weight, huber_delta=huber_delta,
-                                                     color_huber_delta=color_huber_delta, huber_k=huber_k)
+                                                     color_huber_delta=color_huber_delta, huber_k=huber_k,
+                                                     color_huber_k=color_huber_k)
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio

@@ -945,6 +945,40 @@ GS_API int gs_projective_icp_color_scaled_batch_f32(const gs_picp_color_seq* seq
 GS_API int gs_projective_icp_scaled_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
                                                        const gs_picp_params* params_host, void* stream);
 
+/* The rule for the COLOUR residual of the joint solve, next to (or without) the one for the geometric residual:
+ *   cdelta = max(c_c * med_c, color_huber_floor),  c_c = (float)color_huber_k * 1.4826f,
+ *   med_c  = the LOWER median (rank (n - 1) / 2) of |r| over the slots that have a colour row, r the colour residual
+ *            BEFORE color_weight is applied, with the bits the joint linearise kernel forms;
+ *   n == 0, a median of 0 or a product that is not above the floor (a NaN included): cdelta = color_huber_floor.
+ * A threshold in the units of the residuals themselves: the same scene in colours of 0 ... 1 and of 0 ... 255 gets
+ * thresholds a factor of 255 apart without a constant being retuned.  huber_k / color_huber_k: finite and >= 0, each
+ * switches its rule on when > 0; with 0 the floor of that residual is its constant threshold (0: off), as huber_delta /
+ * color_huber_delta are in gs_projective_icp_color_robust_batch_f32.  With both 0 the entries run the robust entries'
+ * launches.  The launches are those of the geometric rule, whichever thresholds are asked for: ONE residual pass (one
+ * association per slot, a key table and a first-digit histogram per residual asked for) and ONE select launch of
+ * B x (thresholds asked for) blocks; one clearing launch per call.  Nothing read back, integer atomics only.
+ * scratch: gs_projective_icp_color_joint_scaled_scratch_bytes (gs_projective_icp_color_scaled_scratch_bytes, then the
+ * colour residual's key table, 2048 counters and threshold), 16-byte aligned; 0 for bad sizes.
+ * gs_projective_icp_color_joint_scaled_batch_f32: deltas_host / cdeltas_host: NULL, or per sequence a device buffer of
+ * numiters floats that receives the geometric / the colour threshold of every iteration; a table is written only when
+ * its rule is on.
+ * gs_projective_icp_color_joint_scaled_rows_f32: gs_projective_icp_color_robust_rows_f32 with the thresholds derived at
+ * init_pose16; delta_out / cdelta_out (1 float each, or NULL) receive them, each only when its rule is on. */
+GS_API int64_t gs_projective_icp_color_joint_scaled_scratch_bytes(int H, int W, int stride);
+GS_API int gs_projective_icp_color_joint_scaled_batch_f32(const gs_picp_color_seq* seqs_host, float* const* deltas_host,
+                                                          float* const* cdeltas_host, int B, int H, int W,
+                                                          const gs_picp_params* params_host, float color_weight,
+                                                          float huber_k, float huber_floor, float color_huber_k,
+                                                          float color_huber_floor, void* stream);
+GS_API int gs_projective_icp_color_joint_scaled_rows_f32(const gs_picp_color_seq* seq_host, int H, int W, int stride,
+                                                         float dist_th, float dot_th, float color_weight, float huber_k,
+                                                         float huber_floor, float color_huber_k,
+                                                         float color_huber_floor, int32_t* code, int64_t* row, float* a6,
+                                                         float* b, float* ac6, float* bc, int32_t* colored,
+                                                         float* weight, float* color_weight_out, double* sums28,
+                                                         int64_t* count, int64_t* color_count, float* delta_out,
+                                                         float* cdelta_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

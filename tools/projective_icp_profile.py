@@ -2,7 +2,8 @@
 frame loop gains or loses with it, and what a launch of it costs (needs the MI355X; fails without one).
 
     python tools/projective_icp_profile.py [--out FILE] [--only localize|slam|launches] [--steps K] [--color-weight W]
-                                           [--huber-delta D] [--color-huber-delta C] [--huber-k K] [--parent-lib SO]
+                                           [--huber-delta D] [--color-huber-delta C] [--huber-k K] [--color-huber-k K]
+                                           [--parent-lib SO]
 
 1. One localisation.  640x480 frames of the benchmark's synthetic sequences, the map fused from the first 10 frames under
    the ground-truth poses, frame 10 localised from the pose of frame 9; B = 1 and B = 8.
@@ -40,6 +41,12 @@ median in every iteration (--huber-delta is then its floor) to all three parts, 
 constant-threshold solve in the same process: the provider with huber_k=K in part 1, the scaled solve alone in part 3
 (the slope is its four launches: residual pass, select, robust linearise, finish) and PointFusion(odom="projicp",
 huber_k=K) in part 2 (frames/s and ATE next to the plain projicp run).
+
+--color-huber-k K (K > 0, needs --color-weight) adds to part 3 the joint solve whose COLOUR threshold is estimated from the
+colour residuals' median in every iteration (--color-huber-delta is then its floor), alternating in the same process
+with the joint solve under a constant colour threshold (the one given, else 0.05) and, with --huber-k, with the joint
+solve under the geometric rule alone and under both rules: us_per_iteration_color_const / _cscaled / _gscaled /
+_bothscaled.  Every scaled variant has the same four launches per iteration.
 
 --parent-lib SO (needs --huber-delta): the libgradslam_hip.so of another build of this project, e.g. of the parent commit
 (same ABI version), loaded next to this tree's.  Part 3 then also times ITS gs_projective_icp_robust_batch_f32 on the
@@ -178,7 +185,7 @@ def load_parent(path):
 
 
 def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta=0.0, color_huber_delta=0.0,
-                 huber_k=0.0, parent=None):
+                 huber_k=0.0, parent=None, color_huber_k=0.0):
     out = []
     for B in (1, 8):
         pc, live, prev, _ = scene(torch, gs, B)
@@ -218,6 +225,22 @@ def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta
                 fns.update({"solve_color_robust_%dit" % n: (lambda n=n: ops.projective_icp_color_batch(
                     *cargs, numiters=n, huber_delta=huber_delta, color_huber_delta=color_huber_delta, **kw))
                     for n in (10, 40)})
+            # the colour threshold from the median of the colour residuals, next to what it is compared with in the same
+            # round robin: the joint solve with a constant colour threshold (the one given, else 0.05) and, with
+            # --huber-k, the joint solve with the geometric rule alone and with both rules
+            color_scaled = {}
+            if color_weight > 0 and color_huber_k > 0:
+                const = color_huber_delta if color_huber_delta > 0 else 0.05
+                color_scaled["color_const"] = dict(huber_delta=huber_delta, color_huber_delta=const)
+                color_scaled["color_cscaled"] = dict(huber_delta=huber_delta, color_huber_delta=color_huber_delta,
+                                                     color_huber_k=color_huber_k)
+                if huber_k > 0:
+                    color_scaled["color_gscaled"] = dict(huber_delta=huber_delta, color_huber_delta=const, huber_k=huber_k)
+                    color_scaled["color_bothscaled"] = dict(huber_delta=huber_delta, color_huber_delta=color_huber_delta,
+                                                            huber_k=huber_k, color_huber_k=color_huber_k)
+            for name, ckw in color_scaled.items():
+                fns.update({"solve_%s_%dit" % (name, n): (lambda n=n, ckw=ckw: ops.projective_icp_color_batch(
+                    *cargs, numiters=n, **ckw, **kw)) for n in (10, 40)})
             for fn in fns.values():
                 fn(), fn()
             t = time_round_robin(torch, fns, reps, rounds)
@@ -245,6 +268,10 @@ def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta
                 rec["color_huber_delta"] = color_huber_delta
                 rec["us_per_iteration_color_robust"] = \
                     (t["solve_color_robust_40it"]["median_ms"] - t["solve_color_robust_10it"]["median_ms"]) / 30 * 1e3
+            for name in color_scaled:
+                rec["color_huber_k"] = color_huber_k
+                rec["us_per_iteration_" + name] = \
+                    (t["solve_%s_40it" % name]["median_ms"] - t["solve_%s_10it" % name]["median_ms"]) / 30 * 1e3
             print(json.dumps(rec), flush=True)
             out.append(rec)
     return out
@@ -299,14 +326,20 @@ def main():
                     help="another build's libgradslam_hip.so (needs --huber-delta): part 3 also times its robust solve")
     ap.add_argument("--color-huber-delta", type=float, default=0.0,
                     help="> 0 (intensity units, needs --color-weight): Huber weights on the colour rows of the joint solve")
+    ap.add_argument("--color-huber-k", type=float, default=0.0,
+                    help="> 0 (needs --color-weight): part 3 also times the joint solve with the colour Huber threshold "
+                         "from the colour residuals' median (--color-huber-delta is then its floor), next to a constant "
+                         "colour threshold and, with --huber-k, next to the geometric rule alone and both rules")
     args = ap.parse_args()
     if not (args.color_weight >= 0 and args.color_weight < float("inf")):
         ap.error("--color-weight must be finite and not negative")
-    for name in ("huber_delta", "color_huber_delta", "huber_k"):
+    for name in ("huber_delta", "color_huber_delta", "huber_k", "color_huber_k"):
         if not (getattr(args, name) >= 0 and getattr(args, name) < float("inf")):
             ap.error("--%s must be finite and not negative" % name.replace("_", "-"))
     if args.color_huber_delta > 0 and not args.color_weight > 0:
         ap.error("--color-huber-delta needs --color-weight")
+    if args.color_huber_k > 0 and not args.color_weight > 0:
+        ap.error("--color-huber-k needs --color-weight")
     if args.parent_lib and not args.huber_delta > 0:
         ap.error("--parent-lib needs --huber-delta")
     import torch
@@ -324,7 +357,7 @@ def main():
     if args.only in (None, "launches"):
         out["launches"] = launch_times(torch, gs, ops, color_weight=args.color_weight, huber_delta=args.huber_delta,
                                        color_huber_delta=args.color_huber_delta, huber_k=args.huber_k,
-                                       parent=load_parent(args.parent_lib) if args.parent_lib else None)
+                                       color_huber_k=args.color_huber_k, parent=load_parent(args.parent_lib) if args.parent_lib else None)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
