@@ -72,13 +72,14 @@ class FrameStreamer(object):
         self.ready = [torch.cuda.Event() for _ in range(R)]     # copy + conversion of the slot's frame done
         self.done = {}                                            # frame t -> event: every step up to t has been enqueued
         self.in_slot = [-1] * R
+        self.last = -1                                            # the frame asked for last (frame(0) is its successor)
         self._prefetch(0)
 
     def __len__(self):
         return self.L
 
     def _prefetch(self, t):
-        if t >= self.L:
+        if not 0 <= t < self.L:
             return
         k = t % self.RING
         if self.in_slot[k] == t:
@@ -127,11 +128,24 @@ class FrameStreamer(object):
     def frame(self, t):
         """RGBDImages of frame t for all sequences (float32 on the device); starts the transfer of frame t + 1.
         The tensors of the returned frame live in a ring slot: they stay valid until frame t + RING - 2 is asked for
-        (a SLAM loop reads frame t in steps t and t + 1 only)."""
+        (a SLAM loop reads frame t in steps t and t + 1 only; work that reads them must be enqueued before the
+        next-but-one call of frame(): only that much is ordered before the slot's next transfer).  Frames may be asked
+        for in any order and more than once; only consecutive requests take the path that never waits.
+        IndexError for t outside [0, len(self))."""
+        if not 0 <= t < self.L:
+            raise IndexError("FrameStreamer.frame: frame %d of %d" % (t, self.L))
+        consecutive = t == self.last + 1
+        if not consecutive:
+            # A rewind, a skip or a repeat: the events on record say "every step up to j has been enqueued" of ANOTHER
+            # run of requests (a second pass would find the first pass's, fired long ago, under its own keys), and one
+            # recorded now would miss the step that is about to read the frame handed out last as its previous frame.
+            # Without a record _prefetch takes the conservative branch until the new run has events of its own.
+            self.done.clear()
+        self.last = t
         self._prefetch(t)
         k = t % self.RING
         cur = torch.cuda.current_stream(self.device)
-        if t > 0 and (t - 1) not in self.done:   # everything enqueued so far = the steps up to t - 1
+        if t > 0 and consecutive:   # everything enqueued so far = the steps up to t - 1
             ev = torch.cuda.Event()
             ev.record(cur)
             self.done[t - 1] = ev

@@ -411,7 +411,11 @@ def ingest_frames_native(depth_raw, color_raw, depth_out, color_out, scale_div, 
     None.  The raw tensors live on the device of the outputs -- or in PINNED host memory mapped into its address space
     (the kernel then reads them over PCIe: the streaming ingest).  `on_stream`: a torch stream to launch on (default:
     the current one)."""
-    ref = depth_raw if depth_raw is not None else color_raw
+    if (depth_raw is None) != (depth_out is None) or (color_raw is None) != (color_out is None) or \
+            (depth_raw is None and color_raw is None):
+        raise _C.HipExtensionError("ingest_frames_native: raw / out buffers must come in pairs (depth, colour or both)")
+    if (depth_raw is not None and depth_raw.ndim < 2) or (color_raw is not None and (color_raw.ndim < 3 or color_raw.shape[-1] != 3)):
+        raise _C.HipExtensionError("ingest_frames_native: raw / out buffers do not match")
     dev = require_device(depth_out if depth_raw is not None else color_out)
     H, W = (depth_raw.shape[-2:] if depth_raw is not None else color_raw.shape[-3:-1])
     n = (depth_raw.numel() if depth_raw is not None else color_raw.numel() // 3) // (H * W)
@@ -433,7 +437,6 @@ def ingest_frames_native(depth_raw, color_raw, depth_out, color_out, scale_div, 
                 raise _C.HipExtensionError("ingest_frames_native: host frames must be pinned and device-mapped "
                                            "(tensor.pin_memory()); there is no CPU path")
         ptrs += [_C.C.c_void_p(rp), ptr(out)]
-    del ref
     st = stream(dev) if on_stream is None else _C.C.c_void_p(on_stream.cuda_stream)
     check(lib().gs_ingest_frames_native_f32(ptrs[0], ptrs[2], n, int(H), int(W), float(scale_div), 1 if normalize else 0,
                                             ptrs[1], ptrs[3], st), "gs_ingest_frames_native_f32")
