@@ -94,6 +94,13 @@ class CarveSeq(C.Structure):
                 ("K16", C.c_void_p), ("violations", C.c_void_p), ("keep", C.c_void_p)]
 
 
+class VoxelKeepSeq(C.Structure):
+    """gs_voxel_keep_seq: one map's points and confidences, the outputs and the table scratch of gs_voxel_keep_dc_f32."""
+    _fields_ = [("points", C.c_void_p), ("confidence", C.c_void_p), ("n_bound", C.c_int64), ("n_dev", C.c_void_p),
+                ("keep", C.c_void_p), ("winner", C.c_void_p), ("unplaced", C.c_void_p), ("scratch", C.c_void_p),
+                ("scratch_bytes", C.c_int64)]
+
+
 class PicpSeq(C.Structure):
     """gs_picp_seq: one live frame, the model view's index image and the map for the projective ICP."""
     _fields_ = [("vertex", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("K16", C.c_void_p),
@@ -205,6 +212,8 @@ _PROTOS = {
     "gs_prune_scratch_bytes": [_i64],
     "gs_prune_map_dc_f32": [C.POINTER(PruneSeq), _i32, _f, _i32, _vp],
     "gs_free_space_dc_f32": [C.POINTER(CarveSeq), _i32, _i32, _i32, _i32, _f, _i32, _i32, _vp],
+    "gs_voxel_keep_scratch_bytes": [_i64],
+    "gs_voxel_keep_dc_f32": [C.POINTER(VoxelKeepSeq), _i32, _f, _vp],
     "gs_bilateral_depth_f32": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _f, _f, _vp, _vp, _vp],
     "gs_bilateral_depth_backward_f32": [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f, _f, _vp, _vp],
     "gs_projective_icp_scratch_bytes": [_i32, _i32, _i32],
@@ -256,7 +265,7 @@ _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scrat
             "gs_projective_icp_tape_bytes": _i64, "gs_projective_icp_backward_scratch_bytes": _i64,
             "gs_projective_icp_color_scratch_bytes": _i64, "gs_projective_icp_scaled_scratch_bytes": _i64,
             "gs_projective_icp_color_scaled_scratch_bytes": _i64,
-            "gs_projective_icp_color_joint_scaled_scratch_bytes": _i64}
+            "gs_projective_icp_color_joint_scaled_scratch_bytes": _i64, "gs_voxel_keep_scratch_bytes": _i64}
 EXPORTS = tuple(_PROTOS)
 
 

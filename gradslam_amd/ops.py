@@ -1820,6 +1820,115 @@ def free_space(points, depth, poses, K, *, n_dev=None, margin=0.05, window=1, mi
     return FreeSpace(r.violations[0], r.keep[0])
 
 
+# ----------------------------------------------------------------------------------- voxel thinning
+VoxelKeep = collections.namedtuple("VoxelKeep", ["keep", "winner", "unplaced"])
+VOXEL_MAX_ROWS = (1 << 31) - 1
+
+
+def _voxel_args(who, voxel_size):
+    """the check the C entry repeats, made before anything is allocated; names the argument.  Returns the float32 value
+    of the voxel size as a Python float: the number the kernel divides by"""
+    if isinstance(voxel_size, bool) or not isinstance(voxel_size, (float, int)):
+        raise TypeError("%s: voxel_size must be of type float or int; but was of type %s." % (who, type(voxel_size)))
+    v = float(voxel_size)
+    if not (v > 0.0 and v != float("inf")):
+        raise ValueError("%s: voxel_size must be finite and > 0; got %r" % (who, voxel_size))
+    v32 = float(torch.tensor(v, dtype=torch.float32))
+    if not (v32 > 0.0 and v32 != float("inf")):
+        raise ValueError("%s: voxel_size must be finite and > 0 as a float32; got %r" % (who, voxel_size))
+    return v32
+
+
+def voxel_keep_batch(maps, voxel_size, *, out=None):
+    """Which rows of B maps are the one surfel their voxel keeps (gs_voxel_keep_dc_f32: an elect and a resolve launch per
+    8 sequences over a hash table in scratch; nothing is read back).  maps: per sequence (points, normals, colors,
+    features, n_bound, n_dev) as in free_space_batch -- only the points, the confidence (features, when it has one
+    channel) and the counts are read.  With n = min(n_dev[0], n_bound): the voxel of a row is floor(p / voxel_size) per
+    component in float32; a row is griddable iff its point is finite and every voxel index lies in [-2^20, 2^20); among
+    the griddable rows < n of a voxel the winner has the largest confidence (its float32 bit pattern when >= +0.0, else
+    0: NaN and negative values score 0), ties go to the lowest row.  Returns VoxelKeep(keep, winner, unplaced): per
+    sequence an (n_bound,) uint8 tensor (1: the row is below the count and is not griddable or is its voxel's winner) and
+    an (n_bound,) int64 tensor (the winner of the row's voxel; the row itself when not griddable; -1 at or beyond the
+    count), and a (B,) int32 tensor on the device (rows the table could not place and that were kept: 0).  out: a pair
+    (keep, winner) of per-sequence lists to write into (a list, or an entry of it, may be None: that output is then not
+    produced).  The result is detached and never on the autograd tape: the mask is a constant, like the association."""
+    who = "voxel_keep"
+    voxel_size = _voxel_args(who, voxel_size)
+    if not isinstance(maps, (list, tuple)) or len(maps) == 0:
+        raise ValueError("%s: maps must be a non-empty list of (points, normals, colors, features, n_bound, n_dev)" % who)
+    Bn = len(maps)
+    if out is not None and (len(out) != 2 or any(o is not None and len(o) != Bn for o in out)):
+        raise ValueError("%s: out must be (keep, winner), each a list with one entry per map or None" % who)
+    for b, m in enumerate(maps):
+        if not isinstance(m, (list, tuple)) or len(m) != 6 or not torch.is_tensor(m[0]):
+            raise ValueError("%s: maps[%d] must be (points, normals, colors, features, n_bound, n_dev)" % (who, b))
+        if m[0].ndim != 2 or m[0].shape[1] != 3:
+            raise ValueError("%s: points must be (rows, 3); got %s for maps[%d]" % (who, tuple(m[0].shape), b))
+        if m[3] is not None and (not torch.is_tensor(m[3]) or m[3].ndim != 2 or m[3].shape[0] < m[0].shape[0]):
+            raise ValueError("%s: features must be (rows, F) with as many rows as points, for maps[%d]" % (who, b))
+    _warn_detached(who, *[t for m in maps for t in (m[0], m[3])])
+    # held: copies that _c had to make must outlive the loop (as in free_space_batch)
+    held = [(_c(m[0].detach()), None if m[3] is None or m[3].shape[1] != 1 else _c(m[3].detach())) for m in maps]
+    dev = require_device(*[t for h in held for t in h])
+    unplaced = torch.empty((Bn,), dtype=torch.int32, device=dev)
+    ws = Workspace.get(dev)
+    L = lib()
+    seqs = (_C.VoxelKeepSeq * Bn)()
+    keep, winner = [], []
+    for b in range(Bn):
+        P, Cf = held[b]
+        n_bound, n_dev = maps[b][4], maps[b][5]
+        require_device(P, Cf, n_dev)
+        n_bound = int(P.shape[0]) if n_bound is None else min(int(n_bound), int(P.shape[0]))
+        if n_bound < 0:
+            raise ValueError("%s: negative n_bound" % who)
+        if n_bound > VOXEL_MAX_ROWS:
+            raise ValueError("%s: maps of 2^31 rows or more are not supported" % who)
+        outs = []
+        for i, (name, dtype) in enumerate((("keep", torch.uint8), ("winner", torch.int64))):
+            if out is None:
+                t = torch.empty((n_bound,), dtype=dtype, device=dev)
+            else:
+                t = None if out[i] is None else out[i][b]
+                if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (n_bound,) or
+                                      not t.is_contiguous()):
+                    raise ValueError("%s: out.%s[%d] must be a contiguous %s tensor of shape (%d,)"
+                                     % (who, name, b, str(dtype).split(".")[-1], n_bound))
+            outs.append(t)
+        if outs[0] is None and outs[1] is None:
+            raise ValueError("%s: out must ask for keep or winner (or both) of every map" % who)
+        require_device(outs[0], outs[1], P)
+        nbytes = int(L.gs_voxel_keep_scratch_bytes(n_bound))
+        u = seqs[b]
+        u.points = P.data_ptr() if n_bound > 0 else 0
+        u.confidence = Cf.data_ptr() if Cf is not None and n_bound > 0 else 0
+        u.n_bound, u.n_dev = n_bound, (0 if n_dev is None else n_dev.data_ptr())
+        u.keep, u.winner = (0 if t is None else t.data_ptr() for t in outs)
+        u.unplaced = unplaced.data_ptr() + 4 * b
+        u.scratch, u.scratch_bytes = ws.bytes("voxel%d" % b, nbytes).data_ptr(), nbytes
+        keep.append(outs[0])
+        winner.append(outs[1])
+    check(L.gs_voxel_keep_dc_f32(seqs, Bn, voxel_size, stream(dev)), "gs_voxel_keep_dc_f32")
+    return VoxelKeep(keep, winner, unplaced)
+
+
+def voxel_keep(points, voxel_size, confidence=None, n_dev=None):
+    """One cloud: voxel_keep_batch for B = 1.  points (rows, 3); confidence (rows,) or (rows, 1) or None (every score is 0:
+    the first row of a voxel wins); n_dev: device int64[1] holding the actual row count (points.shape[0] is then an upper
+    bound).  Returns VoxelKeep(keep (rows,) uint8, winner (rows,) int64, unplaced int32[1])."""
+    _voxel_args("voxel_keep", voxel_size)
+    for name, val in (("points", points),) + ((("confidence", confidence),) if confidence is not None else ()):
+        if not torch.is_tensor(val):
+            raise TypeError("voxel_keep: expected %s to be of type tensor; got %s" % (name, type(val)))
+    if confidence is not None:
+        if confidence.ndim == 1:
+            confidence = confidence.unsqueeze(1)
+        if confidence.ndim != 2 or confidence.shape[1] != 1:
+            raise ValueError("voxel_keep: confidence must be (rows,) or (rows, 1); got %s" % (tuple(confidence.shape),))
+    r = voxel_keep_batch([(points, None, None, confidence, None, n_dev)], voxel_size)
+    return VoxelKeep(r.keep[0], r.winner[0], r.unplaced)
+
+
 # ----------------------------------------------------------------------------------- bilateral depth filter
 BILATERAL_MAX_RADIUS = 8
 

@@ -34,6 +34,12 @@ class PointFusion(ICPSLAM):
     violations).  It runs before the pruning schedule, on the fast path, the generic path and `forward` alike.  With
     `carve_margin=None` a step makes no such call.
 
+    Voxel thinning (off by default): with `voxel_size` set, every `voxel_every`-th `step` of a map follows its map
+    update (and its carve) with `pointclouds.voxel_downsample_(voxel_size)`: of the surfels that share a cube of side
+    `voxel_size` only the most confident stays (the oldest among equals); nothing is averaged.  It runs before the
+    pruning schedule, on the fast path, the generic path and `forward` alike.  With `voxel_size=None` a step makes no
+    such call.
+
     `odom_differentiable`: as in `ICPSLAM` (the projective ICP of `odom="projicp"` on the autograd tape).
     `color_weight`: as in `ICPSLAM` (the photometric term of `odom="projicp"`).
     `huber_delta`, `color_huber_delta`: as in `ICPSLAM` (the Huber thresholds of `odom="projicp"`).
@@ -49,7 +55,8 @@ class PointFusion(ICPSLAM):
                  odom_differentiable: bool = False, color_weight: Union[float, int] = 0.0,
                  huber_delta: Union[float, int] = 0.0, color_huber_delta: Union[float, int] = 0.0,
                  huber_k: Union[float, int] = 0.0, carve_margin: Union[float, int, None] = None,
-                 carve_window: int = 1, carve_every: int = 1, color_huber_k: Union[float, int] = 0.0):
+                 carve_window: int = 1, carve_every: int = 1, color_huber_k: Union[float, int] = 0.0,
+                 voxel_size: Union[float, int, None] = None, voxel_every: int = 1):
         super().__init__(odom=odom, dsratio=dsratio, numiters=numiters, damp=damp, dist_thresh=dist_thresh,
                          lambda_max=lambda_max, B=B, B2=B2, nu=nu, device=device, depth_filter=depth_filter,
                          odom_differentiable=odom_differentiable, color_weight=color_weight, huber_delta=huber_delta,
@@ -103,6 +110,17 @@ class PointFusion(ICPSLAM):
         self.carve_margin = carve_margin
         self.carve_window = carve_window
         self.carve_every = carve_every
+        if not (voxel_size is None or (isinstance(voxel_size, (float, int)) and not isinstance(voxel_size, bool))):
+            raise TypeError("Voxel size must be of type float or int or None; but was of type {}.".format(
+                type(voxel_size)))
+        if not isinstance(voxel_every, int) or isinstance(voxel_every, bool):
+            raise TypeError("voxel_every must be of type int; but was of type {}.".format(type(voxel_every)))
+        if voxel_size is not None and not (0 < voxel_size < math.inf):
+            raise ValueError("voxel_size ({}) must be finite and positive.".format(voxel_size))
+        if voxel_every < 1:
+            raise ValueError("voxel_every ({}) must be at least 1.".format(voxel_every))
+        self.voxel_size = voxel_size
+        self.voxel_every = voxel_every
 
     def step(self, pointclouds: Pointclouds, live_frame: RGBDImages, prev_frame=None, inplace: bool = False):
         # the plain SLAM loop (in place, nothing on the autograd tape, a map with surfels): one foreign call per frame
@@ -121,13 +139,15 @@ class PointFusion(ICPSLAM):
                 self._step(pointclouds, work, prev_frame, inplace)
         if work is not live_frame:
             live_frame.poses = work.poses
-        if self.carve_margin is not None or self.prune_min_confidence is not None:
+        if self.carve_margin is not None or self.voxel_size is not None or self.prune_min_confidence is not None:
             if res[0] is not pointclouds:
                 # an out-of-place step returns a new container: it takes the marks and the step counters once, before
                 # the carve, whose compaction rewrites the marks that the pruning schedule then reads
                 res[0]._carry_epochs(pointclouds)
             if self.carve_margin is not None:
                 self._carve_step(res[0], work)
+            if self.voxel_size is not None:
+                self._voxel_step(res[0])
             if self.prune_min_confidence is not None:
                 self._end_step(res[0])
         return res
@@ -139,6 +159,14 @@ class PointFusion(ICPSLAM):
         pointclouds._carve_steps += 1
         if pointclouds._carve_steps % self.carve_every == 0:
             pointclouds.carve_(frame, margin=self.carve_margin, window=self.carve_window, min_views=1)
+
+    def _voxel_step(self, pointclouds: Pointclouds):
+        """voxel thinning of a step (fast and generic path alike): on every voxel_every-th step of this map, keep one
+        surfel per voxel; after the carve (what the frame sees through does not compete) and before the pruning
+        schedule (which reads the marks this compaction rewrites)"""
+        pointclouds._voxel_steps += 1
+        if pointclouds._voxel_steps % self.voxel_every == 0:
+            pointclouds.voxel_downsample_(self.voxel_size)
 
     def _end_step(self, pointclouds: Pointclouds):
         """the pruning schedule of a step (fast and generic path alike): prune on every prune_every-th step of this map,

@@ -26,6 +26,37 @@ def _canon_device(device):
     return torch.Tensor().to(device).device
 
 
+def _voxel_keep_torch(points, confidence, voxel_size):
+    """The rule of gs_voxel.hip in torch, for maps the kernel does not serve (CPU maps): points (n, 3), confidence (n,) or
+    None, voxel_size a float that float32 holds.  Voxel q_c = floor(p_c / voxel_size) in float32; griddable iff p is
+    finite and -2^20 <= q_c < 2^20; score = the bit pattern of the confidence when >= +0.0 (else 0; -0.0 as +0.0); per
+    voxel the largest score wins, the lowest row among equals.  Returns (keep uint8 (n,), winner int64 (n,))."""
+    n = int(points.shape[0])
+    dev = points.device
+    rows = torch.arange(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return torch.zeros(0, dtype=torch.uint8, device=dev), rows
+    p = points.to(torch.float32)
+    q = torch.floor(p / torch.tensor(voxel_size, dtype=torch.float32, device=dev))
+    grid = (torch.isfinite(p) & (q >= -1048576.0) & (q < 1048576.0)).all(dim=1)
+    qi = torch.where(grid.unsqueeze(1), q, torch.zeros_like(q)).to(torch.int64) + (1 << 20)
+    key = (qi[:, 0] << 42) | (qi[:, 1] << 21) | qi[:, 2]
+    if confidence is None:
+        score = torch.zeros(n, dtype=torch.int64, device=dev)
+    else:
+        c = confidence.to(torch.float32).contiguous()
+        score = torch.where(c >= 0, c.view(torch.int32).to(torch.int64) & 0x7FFFFFFF, torch.zeros((), dtype=torch.int64,
+                                                                                                  device=dev))
+    winner = rows.clone()
+    g = torch.nonzero(grid).reshape(-1)
+    if g.numel():
+        _, inv = torch.unique(key[g], return_inverse=True)
+        word = (score[g] << 32) | (0xFFFFFFFF - g)          # larger: the larger score, then the lower row
+        best = torch.zeros(int(inv.max()) + 1, dtype=torch.int64, device=dev).scatter_reduce(0, inv, word, "amax")
+        winner[g] = 0xFFFFFFFF - (best[inv] & 0xFFFFFFFF)
+    return (winner == rows).to(torch.uint8), winner
+
+
 class _CountGroup(object):
     """Surfel counts of the sequences of a batch that live ON THE DEVICE (written by the fuse/append kernels).
 
@@ -155,6 +186,7 @@ class Pointclouds(object):
         self._n_marks = 0
         self._prune_steps = 0   # steps a pruning PointFusion has taken on this map (the step counter lives with the map)
         self._carve_steps = 0   # the same for a carving PointFusion (carve_margin)
+        self._voxel_steps = 0   # the same for a thinning PointFusion (voxel_size)
         self.last_pruned = None  # (B,) int64: rows the last prune_ removed per sequence (on the map's device, never synced)
         self.equisized = None
 
@@ -599,6 +631,7 @@ class Pointclouds(object):
         """takes the epoch marks and the step counter of `other` (of its sequences `ids`)"""
         self._prune_steps = other._prune_steps
         self._carve_steps = other._carve_steps
+        self._voxel_steps = other._voxel_steps
         self._n_marks = other._n_marks if other._marks is not None else 0
         if other._marks is None:
             self._marks = None
@@ -764,6 +797,65 @@ class Pointclouds(object):
     def carve(self, frames, *, margin: float = 0.05, window: int = 1, min_views: int = 1):
         r"""Out-of-place `carve_`: returns a carved copy (the copy resolves device-side counts, as `clone` does)."""
         return self.clone().carve_(frames, margin=margin, window=window, min_views=min_views)
+
+    # ------------------------------------------------------------------ voxel thinning
+    def _voxel_keep(self, who, voxel_size, want):
+        """the voxel rule on the map, read in place with its device-side counts; want: (keep, winner).  Returns the two
+        per-sequence lists (None where not wanted).  A float32 map on a HIP device goes through ops.voxel_keep_batch;
+        any other map (CPU, another dtype) through the same rule in torch (_voxel_keep_torch)."""
+        from .. import ops
+        voxel_size = ops._voxel_args(who, voxel_size)
+        B = len(self._n_host)
+        if B == 0 or self._buf["points"] is None:
+            raise ValueError("cannot voxel-downsample an empty pointclouds object")
+        # the confidence competes only on a surfel map's single count channel; any other feature layout scores 0
+        conf = self._buf["features"] if self._buf["features"] is not None and self.num_features == 1 else None
+        pts = self._buf["points"]
+        if self.device.type == "cuda" and all(t.dtype == torch.float32 for t in pts) and \
+                (conf is None or all(t.dtype == torch.float32 for t in conf)):
+            maps, out_k, out_w = [], [], []
+            for b in range(B):
+                bound, n_dev = self._count_of(b)   # (never forces a device-side count to the host)
+                maps.append((pts[b].detach(), None, None, None if conf is None else conf[b].detach(), bound, n_dev))
+                rows = min(bound, int(pts[b].shape[0]))
+                out_k.append(torch.empty(rows, dtype=torch.uint8, device=self.device) if want[0] else None)
+                out_w.append(torch.empty(rows, dtype=torch.int64, device=self.device) if want[1] else None)
+            r = ops.voxel_keep_batch(maps, voxel_size, out=(out_k, out_w))
+            return r.keep, r.winner
+        keep, winner = [], []
+        for b, nb in enumerate(self._n):
+            k, w = _voxel_keep_torch(pts[b][:nb].detach(), None if conf is None else conf[b][:nb, 0].detach(), voxel_size)
+            keep.append(k if want[0] else None)
+            winner.append(w if want[1] else None)
+        return keep, winner
+
+    def voxel_winners(self, voxel_size: float):
+        r"""Per sequence the (N_b,) int64 row of the surfel that the voxel of each point keeps: the most confident point
+        of the cube of side `voxel_size` that holds it (voxel index floor(p / voxel_size) per component, in float32),
+        the oldest among equals; the point itself where it cannot be put on the grid (a non-finite coordinate, a voxel
+        index outside [-2^20, 2^20)).  The confidence is the single feature channel of a surfel map; a map with another
+        feature layout scores every point 0 (the first point of a voxel wins).  `index_add` over it averages attributes
+        per voxel.  The map is only read, with its device-side counts: it can be called between steps; rows the
+        host-side bound holds beyond a device-side count read -1."""
+        return self._voxel_keep("voxel_winners", voxel_size, (False, True))[1]
+
+    def voxel_downsample_(self, voxel_size: float):
+        r"""Voxel thinning in place: keeps one point per cube of side `voxel_size` -- the winner of `voxel_winners` --
+        and every point that cannot be put on the grid, keeping the order of the rest.  Nothing is averaged or moved.
+        The removal is `prune_(keep=...)` with the mask of the voxel pass: counts stay on the device, the epoch marks
+        are rewritten, `last_pruned` holds the removed rows, and a differentiable render or projective-ICP solve taken
+        before it refuses a late backward, as for `prune_`.  A map on the CPU or on the autograd tape takes `prune_`'s
+        torch path with the (detached) mask: the kept rows stay on the tape.  A second call removes nothing.  Returns
+        self."""
+        keep = self._voxel_keep("voxel_downsample_", voxel_size, (True, False))[0]
+        return self.prune_(None, keep=keep)
+
+    def voxel_downsample(self, voxel_size: float):
+        r"""Out-of-place `voxel_downsample_`: returns a thinned copy (the copy resolves device-side counts, as `clone`
+        does)."""
+        from .. import ops
+        ops._voxel_args("voxel_downsample", voxel_size)
+        return self.clone().voxel_downsample_(voxel_size)
 
     def _prune_hip(self, conf, keep, young_mark):
         from .. import ops

@@ -691,6 +691,43 @@ typedef struct gs_carve_seq {
 GS_API int gs_free_space_dc_f32(const gs_carve_seq* seqs_host, int B, int L, int H, int W, float margin, int window,
                                 int min_views, void* stream);
 
+/* ------------------------------------------------------------------ voxel thinning ------
+ * Which rows of B maps are the one surfel their voxel keeps (the voxel_down_sample of point-cloud libraries, without
+ * averaging; the reference never removes a surfel)?  The pass only marks; the removal is gs_prune_map_dc_f32 with the
+ * keep mask written here.  Additions only: the ABI version stays.
+ * Per sequence, with n = min(*n_dev, n_bound) (n_bound when n_dev is NULL) and voxel_size a finite float32 > 0:
+ *   - voxel of a row: q_c = floorf(p_c / voxel_size) per component, the correctly rounded float32 division, then floorf;
+ *   - a row is GRIDDABLE iff all three p_c are finite and -2^20 <= q_c < 2^20 (tested on the float);
+ *   - key = ((q_x + 2^20) << 42) | ((q_y + 2^20) << 21) | (q_z + 2^20): 63 bits;
+ *   - score = the uint32 bit pattern of the confidence when confidence >= +0.0f holds in float32, else 0 (NaN and
+ *     negative values score 0, -0.0 scores as +0.0, +inf is the largest); without a confidence pointer every score is 0;
+ *   - among the griddable rows r < n of one voxel the WINNER has the largest score, ties go to the lowest row;
+ *   - keep[r] = 1 iff r < n and the row is not griddable or is its voxel's winner; rows in [n, n_bound) get 0 and never
+ *     compete; a non-griddable row is always kept and never competes;
+ *   - winner[r] (int64) = the winner of r's voxel, r itself for a non-griddable row, -1 for r >= n.
+ * Both outputs hold n_bound elements, every one is written (no clearing needed); either may be NULL, both only with
+ * n_bound == 0.  confidence: (n_bound) floats (feature channel 0 of a surfel map with F == 1) or NULL.  unplaced: device
+ * int32[1] or NULL; the call clears it and counts the rows for which the table ran out (they are kept, winner = r): it
+ * stays 0 at the table's load of at most one half.  scratch: gs_voxel_keep_scratch_bytes(n_bound) bytes per sequence,
+ * 16-byte aligned: an open-addressing table of the power of two >= max(2 n_bound, 1024) slots of 16 bytes (32 - 64
+ * bytes per row of the bound), cleared by the call.  n_bound < 2^31.  Every argument is checked before the first HIP
+ * call.  Two launches per 8 sequences (elect, resolve) after the clears; integer atomics only, no data-dependent loop
+ * without a bound, nothing is read back; the outputs are integers, a pure function of the inputs and bitwise
+ * reproducible; a second pass over the compacted map removes nothing. */
+typedef struct gs_voxel_keep_seq {
+  const float* points;       /* (n_bound, 3) */
+  const float* confidence;   /* (n_bound) or NULL */
+  int64_t n_bound;           /* host-side upper bound of the row count (launch geometry, table sizing) */
+  const int64_t* n_dev;      /* device int64[1]: the actual count, or NULL when n_bound is exact */
+  uint8_t* keep;             /* out (n_bound) or NULL */
+  int64_t* winner;           /* out (n_bound) or NULL */
+  int32_t* unplaced;         /* out: device int32[1] or NULL */
+  void* scratch;
+  int64_t scratch_bytes;
+} gs_voxel_keep_seq;
+GS_API int64_t gs_voxel_keep_scratch_bytes(int64_t n_bound);
+GS_API int gs_voxel_keep_dc_f32(const gs_voxel_keep_seq* seqs_host, int B, float voxel_size, void* stream);
+
 /* ------------------------------------------------------------------ bilateral depth filter ------
  * The edge-preserving pre-pass on the raw depth of Keller et al. and KinectFusion (no counterpart in the reference),
  * batched over n frames of H x W.  Frame f starts at depth + f * stride_frame and its row h at + h * stride_row (in
