@@ -129,17 +129,13 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                                                                          tuple(prev_poses.shape)))
         poses = prev_poses.reshape(B, 4, 4).contiguous().float()
         K = fr.intrinsics[:, 0].contiguous().float()
-        feats = pointclouds._buf["features"]
-        maps = []
-        for b in range(B):
-            bound, n_dev = pointclouds._count_of(b)   # (never forces a device-side count to the host)
-            # the index image is all the solve reads of the view: no colour, normal or confidence image is rendered
-            conf = feats[b] if feats is not None and self.min_confidence > 0 else None
-            maps.append((pointclouds._buf["points"][b], pointclouds._buf["normals"][b], None, conf, bound, n_dev))
+        # the index image is all the solve reads of the view: no colour, normal or confidence image is rendered
+        maps = pointclouds._map_rows(("points", "normals") + (("features",) if self.min_confidence > 0 else ()))
         if self.differentiable:
             # the render stays off the tape (the winners are constants): it sees detached tensors and does not warn
-            view = ops.render_map_batch([(m[0].detach(), None) + m[2:] for m in maps], poses.detach().view(B, 1, 4, 4), K,
-                                        H, W, radius=self.radius, min_confidence=self.min_confidence)
+            view = ops.render_map_batch([m._replace(points=m.points.detach(), normals=None) for m in maps],
+                                        poses.detach().view(B, 1, 4, 4), K, H, W, radius=self.radius,
+                                        min_confidence=self.min_confidence)
             key = pointclouds._rewrites()
 
             def guard():
@@ -158,7 +154,7 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             colors = pointclouds._buf["colors"]
             if colors is None or any(c is None for c in colors):
                 raise ValueError("color_weight > 0 needs a map with colours")
-            view = ops.render_map_batch([(m[0], None, colors[b]) + m[3:] for b, m in enumerate(maps)],
+            view = ops.render_map_batch([m._replace(normals=None, colors=colors[b]) for b, m in enumerate(maps)],
                                         poses.view(B, 1, 4, 4), K, H, W, radius=self.radius,
                                         min_confidence=self.min_confidence)
             model = ops.model_intensity(view.color[:, 0], view.index[:, 0])
@@ -168,7 +164,7 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                            huber_delta=self.huber_delta, color_huber_delta=self.color_huber_delta,
                                            huber_k=self.huber_k, color_huber_k=self.color_huber_k, **self._kwargs())
             return out
-        view = ops.render_map_batch([(m[0], None) + m[2:] for m in maps], poses.view(B, 1, 4, 4), K, H, W,
+        view = ops.render_map_batch([m._replace(normals=None) for m in maps], poses.view(B, 1, 4, 4), K, H, W,
                                     radius=self.radius, min_confidence=self.min_confidence)
         ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
                                  view.index[:, 0], poses, maps, poses, out=out.view(B, 4, 4),

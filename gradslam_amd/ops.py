@@ -710,17 +710,74 @@ def _batch_view(t, inner_ndim):
     return t, t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else acc) * 4
 
 
-def _map_view(bufs, cap, n_bound, n_dev):
-    P, N, Cc, F = bufs
-    return _C.MapView(P.data_ptr(), N.data_ptr(), 0 if Cc is None else Cc.data_ptr(), 0 if F is None else F.data_ptr(),
-                      int(cap), int(n_bound), 0 if n_dev is None else n_dev.data_ptr())
+MapRows = collections.namedtuple("MapRows", ["points", "normals", "colors", "features", "n_bound", "n_dev"])
+MapRows.__doc__ = """One sequence's map as every batched map pass takes it (`maps`: a list of these, or of tuples in this
+order).  points (rows, 3), normals (rows, 3), colors (rows, 3), features (rows, F; a surfel map's confidence count: F = 1):
+capacity-backed float32 buffers; an attribute the map lacks, or the pass does not read, may be None.  The first n_bound
+rows are the map (None: every row).  n_dev: a device int64[1] tensor with the exact count -- n_bound is then its upper
+bound on the host, a pass reads min(n_dev[0], n_bound) rows and nothing is read back -- or None when n_bound is exact.
+The passes that read points and normals only (localize_batch, render_map_backward_batch, the projective ICP) also take the
+short form (points, normals, n_bound, n_dev)."""
+_MAP_ATTRS = MapRows._fields[:4]
+
+
+def _map_rows(m, read=_MAP_ATTRS, four_ok=False):
+    """One entry of `maps` (with four_ok also in the short form) -> the MapRows to take pointers from: the attributes named
+    in `read` off the autograd tape and contiguous float32 (the tensor itself where it already is), the others None, and
+    n_bound resolved against the rows of points.  What differs between the passes (shape refusals, negative bounds, the
+    null pointers of empty maps) stays with them.  The result is also the keep-alive: a copy that had to be made lives
+    here only, so an entry keeps the MapRows of ALL its sequences referenced until its launch is enqueued -- freed earlier,
+    the caching allocator could hand the copy's block to a later sequence's output before the kernel has read it."""
+    short = four_ok and len(m) == 4
+    n_bound, n_dev = (m[2], m[3]) if short else (m[4], m[5])
+    bufs = [None if t is None or k not in read else _c(t.detach() if t.requires_grad else t)
+            for k, t in zip(_MAP_ATTRS, (m[0], m[1], None, None) if short else m[:4])]
+    rows = int(bufs[0].shape[0]) if bufs[0] is not None and bufs[0].ndim else 0   # (no (rows, 3) points: the pass refuses)
+    return MapRows(*bufs, rows if n_bound is None else min(int(n_bound), rows), n_dev)
+
+
+def _map_view(m, *explicit):
+    """the _C.MapView of a normalised MapRows (_map_rows): the only place one is built.  A caller that fills a descriptor
+    by hand may pass the four buffers and spell out (capacity, n_bound, n_dev) after them."""
+    cap, n_bound, n_dev = explicit or (m.points.shape[0], m.n_bound, m.n_dev)
+    return _C.MapView(*[0 if t is None else t.data_ptr() for t in m[:4]], int(cap), int(n_bound),
+                      0 if n_dev is None else n_dev.data_ptr())
+
+
+def _seq_outs(who, out, spec, b, n_bound, dev):
+    """The two per-sequence outputs of sequence b of a pass that marks rows; spec: their ((name, dtype), (name, dtype)).
+    out None: new (n_bound,) tensors; else out[i][b], checked -- a list, or an entry of it, may be None (that output is
+    then not produced), but not both of a sequence."""
+    outs = []
+    for i, (name, dtype) in enumerate(spec):
+        if out is None:
+            t = torch.empty((n_bound,), dtype=dtype, device=dev)
+        else:
+            t = None if out[i] is None else out[i][b]
+            if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (n_bound,) or
+                                  not t.is_contiguous()):
+                raise ValueError("%s: out.%s[%d] must be a contiguous %s tensor of shape (%d,)"
+                                 % (who, name, b, str(dtype).split(".")[-1], n_bound))
+        outs.append(t)
+    if outs[0] is None and outs[1] is None:
+        raise ValueError("%s: out must ask for %s or %s (or both) of every map" % (who, spec[0][0], spec[1][0]))
+    return outs
+
+
+def _rows_bar(rows, width, n_bound, dev):
+    """an uninitialised (rows, width) gradient buffer of a map attribute with the rows behind the bound zeroed: the
+    backward kernels write the first n_bound rows"""
+    g = torch.empty((rows, width), dtype=f32, device=dev)
+    if n_bound < rows:
+        g[n_bound:].zero_()
+    return g
 
 
 def localize_batch(vertex, depth, K, prev_poses, maps, ds, mode=1, numiters=20, damp=1e-8, dist_thresh=None,
                    lambda_max=2.0, B=1.0, B2=1.0, nu=200.0, out=None):
     """ICPSLAM._localize for all sequences of a batch in one chain of launches (gs_localize_batch_f32).
     vertex (B, H, W, 3) LOCAL vertex maps of the live frames, depth (B, H, W), K / prev_poses (B, 4, 4);
-    maps: per sequence (points, normals, n_bound, n_dev) with capacity-backed buffers (n_dev None: n_bound exact).
+    maps: per sequence a MapRows or its short form (points and normals are read).
     Returns the recovered poses (B, 4, 4) = T_icp @ prev_pose."""
     K, prev_poses = _c(K), _c(prev_poses)
     Bn, H, W = depth.shape
@@ -738,17 +795,16 @@ def localize_batch(vertex, depth, K, prev_poses, maps, ds, mode=1, numiters=20, 
     L = lib()
     k0, p0, t0 = K.data_ptr(), prev_poses.data_ptr(), T.data_ptr()
     for b in range(Bn):
-        P, N, n_bound, n_dev = maps[b]
-        require_device(P, N, n_dev)
+        P, N = maps[b][0], maps[b][1]
+        require_device(P, N, maps[b][-1])
         if P.dtype != f32 or N.dtype != f32 or N.shape[0] < P.shape[0]:
-            # (raw pointers go to the library: a float64 / float16 map would be read as float32 garbage)
             raise _C.HipExtensionError("localize_batch needs float32 map points / normals on buffers of equal capacity "
                                        "(got %s / %s, %d / %d rows)" % (P.dtype, N.dtype, P.shape[0], N.shape[0]))
-        cap = P.shape[0]
-        scratch = ws.bytes("localize%d" % b, L.gs_localize_scratch_bytes(H, W, int(ds), cap))
+        m = _map_rows(maps[b], read=("points", "normals"), four_ok=True)   # (no copies: `maps` holds what is read)
+        scratch = ws.bytes("localize%d" % b, L.gs_localize_scratch_bytes(H, W, int(ds), m.points.shape[0]))
         q = seqs[b]
         q.vertex, q.depth, q.K16, q.prev_pose16 = v0 + b * vs, d0 + b * dstr, k0 + b * 64, p0 + b * 64
-        q.map = _map_view((P, N, None, None), cap, n_bound, n_dev)
+        q.map = _map_view(m)
         q.out_pose16, q.scratch = t0 + b * 64, scratch.data_ptr()
     check(L.gs_localize_batch_f32(seqs, Bn, H, W, int(ds), prm, stream(dev)), "gs_localize_batch_f32")
     return T
@@ -783,8 +839,8 @@ def localize_solve_stats(device, b, H, W, ds, capacity):
 def update_map_fusion_batch_(maps, vertex, normal, depth, rgb, alpha, poses, K, dist_th, dot_th, renorm_all=True,
                              out=None):
     """update_map_fusion of all sequences of a batch, in place on their capacity-backed buffers
-    (gs_update_map_fusion_batch_f32: 4 launches for the whole batch).  maps: per sequence
-    (points, normals, colors, ccounts, n_bound, n_dev).  vertex / normal / rgb (B, H, W, 3), depth / alpha (B, H, W),
+    (gs_update_map_fusion_batch_f32: 4 launches for the whole batch).  maps: per sequence a MapRows with all four
+    attributes (features: the confidence count).  vertex / normal / rgb (B, H, W, 3), depth / alpha (B, H, W),
     poses / K (B, 4, 4).  Returns (counts int64 (B,) on the device, gvertex, gnormal, best_pix (B, H*W))."""
     poses, K = _c(poses), _c(K)
     dev = require_device(poses, K)
@@ -804,12 +860,12 @@ def update_map_fusion_batch_(maps, vertex, normal, depth, rgb, alpha, poses, K, 
     P1 = H * W * 4
     base = [t.data_ptr() for t in (poses, K, best, cnt)]
     for b in range(Bn):
-        P, N, Cc, F, n_bound, n_dev = maps[b]
-        require_device(P, N, Cc, F, n_dev)
-        cap = P.shape[0]
-        scratch = ws.bytes("map_update%d" % b, L.gs_update_map_scratch_bytes(cap, H, W))
+        P, N, Cc, F, _, n_dev = maps[b]
+        require_device(P, N, Cc, F, n_dev)   # (written in place: contiguous buffers, which _map_rows hands through)
+        m = _map_rows(maps[b])
+        scratch = ws.bytes("map_update%d" % b, L.gs_update_map_scratch_bytes(m.points.shape[0], H, W))
         u = seqs[b]
-        u.map = _map_view((P, N, Cc, F), cap, n_bound, n_dev)
+        u.map = _map_view(m)
         u.vertex, u.normal, u.depth, u.rgb, u.alpha = (v[1] + b * v[2] for v in views)
         u.pose16, u.K16 = base[0] + b * 64, base[1] + b * 64
         u.gvertex, u.gnormal = gviews[0][1] + b * gviews[0][2], gviews[1][1] + b * gviews[1][2]
@@ -826,12 +882,11 @@ RenderedViews = collections.namedtuple("RenderedViews", ["depth", "color", "norm
 def render_map_batch(maps, poses, K, H, W, radius=0, min_confidence=0.0, cull_backfaces=False, out=None,
                      differentiable=False, guard=None):
     """The maps of B sequences seen from L poses each (gs_render_map_dc_f32: a z-buffered point render, one key launch
-    and one resolve launch per 8 sequences x 4 views).  maps: per sequence (points, normals, colors,
-    ccounts, n_bound, n_dev) -- (rows, 3) / (rows, 1) float32 tensors of which the first n_bound rows (min(n_dev[0],
-    n_bound) when the device count n_dev is given) are the map; normals / colors / ccounts may be None, the images that
-    need them are then None.  poses (B, L, 4, 4) camera-to-world, K (B, 4, 4).  Returns RenderedViews(depth (B, L, H,
-    W, 1), color (B, L, H, W, 3), normal (B, L, H, W, 3), confidence (B, L, H, W, 1), index (B, L, H, W) int64);
-    pixels no row lands on hold 0 (index: -1).  out: a RenderedViews (or 5-tuple) of tensors to write into.
+    and one resolve launch per 8 sequences x 4 views).  maps: per sequence a MapRows (features: the (rows, 1) confidence
+    count); normals / colors / features may be None, the images that need them are then None.  poses (B, L, 4, 4)
+    camera-to-world, K (B, 4, 4).  Returns RenderedViews(depth (B, L, H, W, 1), color (B, L, H, W, 3), normal (B, L, H,
+    W, 3), confidence (B, L, H, W, 1), index (B, L, H, W) int64); pixels no row lands on hold 0 (index: -1).  out: a
+    RenderedViews (or 5-tuple) of tensors to write into.
     differentiable=False: the result is detached (with a warning when an input requires grad).  differentiable=True:
     the four float images are on the autograd tape (RenderMapFunction per sequence: gradients reach the map rows and
     the poses, not K; index stays a plain tensor); `out` is then refused.  guard: see RenderMapFunction."""
@@ -860,7 +915,7 @@ def render_map_batch(maps, poses, K, H, W, radius=0, min_confidence=0.0, cull_ba
                          % (len(maps), tuple(poses.shape), tuple(K.shape)))
     if Lv == 0 or H <= 0 or W <= 0:
         raise ValueError("render_map: needs at least one view and a positive image size")
-    held = [tuple(None if t is None else _c(t.detach()) for t in m[:4]) for m in maps]
+    held = [_map_rows(m) for m in maps]
     have = [all(h[i] is not None for h in held) for i in range(4)]
     if not have[0]:
         raise ValueError("render_map: a map without points")
@@ -884,16 +939,13 @@ def render_map_batch(maps, poses, K, H, W, radius=0, min_confidence=0.0, cull_ba
     seqs = (_C.RenderSeq * Bn)()
     nbytes = L.gs_render_scratch_bytes(Lv, H, W)
     per_seq = [0 if t is None else t[0].numel() * t.element_size() for t in imgs]
-    for b in range(Bn):
-        P, N, Cc, F = held[b]
-        n_bound, n_dev = maps[b][4], maps[b][5]
-        require_device(P, N, Cc, F, n_dev, poses)
-        if P.ndim != 2 or P.shape[1] != 3 or any(t is not None and t.shape[0] < P.shape[0] for t in (N, Cc, F)):
+    for b, m in enumerate(held):
+        P = m.points
+        require_device(*m[:4], m.n_dev, poses)
+        if P.ndim != 2 or P.shape[1] != 3 or any(t is not None and t.shape[0] < P.shape[0] for t in m[1:4]):
             raise ValueError("render_map: points must be (rows, 3) and every attribute must hold as many rows")
-        n_bound = P.shape[0] if n_bound is None else min(int(n_bound), int(P.shape[0]))
         u = seqs[b]
-        u.map = _C.MapView(*[0 if t is None else t.data_ptr() for t in (P, N, Cc, F)], int(P.shape[0]), n_bound,
-                           0 if n_dev is None else n_dev.data_ptr())
+        u.map = _map_view(m)
         u.poses16, u.K16 = poses.data_ptr() + b * Lv * 64, K.data_ptr() + b * 64
         u.depth, u.color, u.normal, u.confidence, u.index = (
             None if t is None else t.data_ptr() + b * sz for t, sz in zip(imgs, per_seq))
@@ -1055,19 +1107,17 @@ def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_pos
     seqs = (_C.PicpSeq * Bn)()
     P3, P1 = H * W * 12, H * W * 4
     for b in range(Bn):
-        P, N = maps[b][0], maps[b][1]
-        n_bound, n_dev = maps[b][-2], maps[b][-1]
-        require_device(P.detach(), N.detach(), n_dev, vertex)
-        if n_dev is not None and (n_dev.dtype != torch.int64 or n_dev.numel() < 1):
+        m = _map_rows(maps[b], read=("points", "normals"), four_ok=True)   # (refused above unless float32, contiguous)
+        require_device(m.points, m.normals, m.n_dev, vertex)
+        if m.n_dev is not None and (m.n_dev.dtype != torch.int64 or m.n_dev.numel() < 1):
             raise ValueError("{}: the device count must be an int64 tensor".format(who))
-        n_bound = P.shape[0] if n_bound is None else min(int(n_bound), int(P.shape[0]))
-        held += [P, N, n_dev]
+        m = m._replace(n_bound=max(m.n_bound, 0))
+        held.append(m)
         u = seqs[b]
         u.vertex, u.normal, u.depth = vertex.data_ptr() + b * P3, normal.data_ptr() + b * P3, depth.data_ptr() + b * P1
         u.K16, u.index, u.model_pose16 = K.data_ptr() + b * 64, index.data_ptr() + b * H * W * 8, \
             model_poses.data_ptr() + b * 64
-        u.map = _C.MapView(P.data_ptr(), N.data_ptr(), 0, 0, int(P.shape[0]), max(n_bound, 0),
-                           0 if n_dev is None else n_dev.data_ptr())
+        u.map = _map_view(m)
         u.init_pose16 = init_poses.data_ptr() + b * 64
         u.scratch = ws.bytes("picp%d" % b, nbytes).data_ptr()
     return seqs, held, dev, Bn, H, W
@@ -1079,12 +1129,12 @@ def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, ini
     """Frame-to-model tracking by projective data association for B sequences (gs_projective_icp_batch_f32: two launches
     per iteration for 8 sequences, nothing read back).  vertex / normal (B, H, W, 3): LOCAL maps of the live frames,
     depth (B, H, W), K (B, 4, 4); index (B, H, W) int64: the index image of render_map_batch at model_poses (B, 4, 4);
-    maps: per sequence the tuple render_map_batch takes, (points, normals, colors, ccounts, n_bound, n_dev), or the short
-    form (points, normals, n_bound, n_dev); init_poses (B, 4, 4).  Every lattice pixel [::stride, ::stride] with depth is
-    carried by the current estimate into the model view and paired with the map row that won the pixel it lands on, if
-    that row is within dist_thresh metres and angle_thresh degrees (normals); numiters point-to-plane Gauss-Newton steps
-    with constant damping follow.  Returns the poses (B, 4, 4), detached; with return_trace also (B, numiters, 8) rows
-    [inliers, sum of squared residuals, xi(6)].  An iteration without inliers leaves the pose as it is.
+    maps: per sequence a MapRows or its short form (points and normals are read); init_poses (B, 4, 4).  Every lattice
+    pixel [::stride, ::stride] with depth is carried by the current estimate into the model view and paired with the map
+    row that won the pixel it lands on, if that row is within dist_thresh metres and angle_thresh degrees (normals);
+    numiters point-to-plane Gauss-Newton steps with constant damping follow..  Returns the poses (B, 4, 4), detached; with
+    return_trace also (B, numiters, 8) rows [inliers, sum of squared residuals, xi(6)]..  An iteration without inliers
+    leaves the pose as it is.
     differentiable=True: the same pose bits, on the autograd tape (ProjectiveICPFunction: gradients reach vertex, the map
     points and normals and init_poses; the association, depth, K, model_poses and the live normals are constants);
     `out` is then refused.  guard: see ProjectiveICPFunction.
@@ -1216,14 +1266,7 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
         u.map = f.map
         P, N = maps[b][0], maps[b][1]
         n_bound = int(f.map.n_bound)
-        outs = []
-        for t, w in zip((P, N), want_maps[b]):
-            g = None
-            if w:
-                g = torch.empty((int(t.shape[0]), 3), dtype=f32, device=dev)
-                if n_bound < g.shape[0]:
-                    g[n_bound:].zero_()   # (rows of the buffer behind the bound: the kernel writes the first n_bound rows)
-            outs.append(g)
+        outs = [_rows_bar(int(t.shape[0]), 3, n_bound, dev) if w else None for t, w in zip((P, N), want_maps[b])]
         rows_out.append(tuple(outs))
         u.tape = tapes.data_ptr() + b * tapes.shape[1]
         u.pose_bar16 = pose_bar.data_ptr() + b * 64
@@ -1602,16 +1645,16 @@ PRUNE_MAX_MARKS = 64
 
 def prune_map_batch(maps, min_confidence=None, keep=None, marks=None, young_mark=-1, out=None):
     """Stable compaction of the maps of B sequences into NEW buffers (gs_prune_map_dc_f32: count, tile scan, scatter and
-    marks launch per 8 sequences; nothing is read back).  maps: per sequence (points, normals, colors, features,
-    n_bound, n_dev) as in render_map_batch -- normals / colors / features may be None, features is (rows, F).  With n =
-    min(n_dev[0], n_bound), row r < n survives iff (keep is None or keep[r] != 0) and (min_confidence is None or r >=
-    young_from or features[r, 0] >= min_confidence); min_confidence needs F == 1 (the confidence count).  keep: per
-    sequence a (rows,) bool / uint8 tensor or None.  marks: per sequence a device int64 tensor of at most 64 ascending row
-    indices or None; young_from = marks[b][young_mark] (young_mark, an int or one int per sequence; -1: every row is old
-    enough), and the call REWRITES each mark as the number of survivors in front of it.  out: per sequence the four
-    destination tensors (None where the source is None), at least n_bound rows each; default: new tensors of the sources'
-    shapes (same capacity).  Returns PrunedMaps(maps = per sequence (points, normals, colors, features), counts (B,) int64
-    on the device, removed (B,) int64 on the device); destination rows at or beyond the new count are not written."""
+    marks launch per 8 sequences; nothing is read back).  maps: per sequence a MapRows; normals / colors / features may
+    be None.  With n = min(n_dev[0], n_bound), row r < n survives iff (keep is None or keep[r] != 0) and
+    (min_confidence is None or r >= young_from or features[r, 0] >= min_confidence); min_confidence needs F == 1 (the
+    confidence count)..  keep: per sequence a (rows,) bool / uint8 tensor or None..  marks: per sequence a device int64
+    tensor of at most 64 ascending row indices or None; young_from = marks[b][young_mark] (young_mark, an int or one int
+    per sequence; -1: every row is old enough), and the call REWRITES each mark as the number of survivors in front of
+    it..  out: per sequence the four destination tensors (None where the source is None), at least n_bound rows each;
+    default: new tensors of the sources' shapes (same capacity)..  Returns PrunedMaps(maps = per sequence (points,
+    normals, colors, features), counts (B,) int64 on the device, removed (B,) int64 on the device); destination rows at
+    or beyond the new count are not written."""
     Bn = len(maps)
     if Bn == 0:
         raise ValueError("prune_map: no maps")
@@ -1622,8 +1665,8 @@ def prune_map_batch(maps, min_confidence=None, keep=None, marks=None, young_mark
     if len(young) != Bn:
         raise ValueError("prune_map: young_mark must be an int or one int per map")
     _warn_detached("prune_map", *[t for m in maps for t in m[:4]])
-    held = [tuple(None if t is None else _c(t.detach()) for t in m[:4]) for m in maps]
-    dev = require_device(*[t for h in held for t in h])
+    held = [_map_rows(m) for m in maps]
+    dev = require_device(*[t for h in held for t in h[:4]])
     if dev is None or held[0][0] is None:
         raise ValueError("prune_map: a map without points")
     ws = Workspace.get(dev)
@@ -1633,14 +1676,12 @@ def prune_map_batch(maps, min_confidence=None, keep=None, marks=None, young_mark
     c0 = cnt.data_ptr()
     res, alive = [], []
     for b in range(Bn):
-        P, N, Cc, F = held[b]
-        n_bound, n_dev = maps[b][4], maps[b][5]
+        P, N, Cc, F, n_bound, n_dev = held[b]
         if P is None or P.ndim != 2 or P.shape[1] != 3:
             raise ValueError("prune_map: points must be (rows, 3)")
         if any(t is not None and (t.ndim != 2 or t.shape[0] < P.shape[0]) for t in (N, Cc, F)) or \
                 any(t is not None and t.shape[1] != 3 for t in (N, Cc)):
             raise ValueError("prune_map: normals / colors must be (rows, 3), features (rows, F), with as many rows as points")
-        n_bound = P.shape[0] if n_bound is None else min(int(n_bound), int(P.shape[0]))
         if min_confidence is not None and (F is None or F.shape[1] != 1):
             raise ValueError("prune_map: min_confidence needs one feature channel (the confidence count)")
         if out is None:
@@ -1715,15 +1756,15 @@ def _carve_args(who, margin, window, min_views):
 
 def free_space_batch(maps, depth, poses, K, *, margin=0.05, window=1, min_views=1, out=None):
     """Which rows of B maps do L depth frames each see through (gs_free_space_dc_f32: one launch per 8 sequences,
-    whatever L is; nothing is read back).  maps: per sequence (points, normals, colors, ccounts, n_bound, n_dev) as in
-    render_map_batch -- only points and the counts are read.  depth (B, L, H, W) or (B, L, H, W, 1), poses (B, L, 4, 4)
-    camera-to-world, K (B, 4, 4).  A row violates a view iff it projects into the frame (the projection of the map update
-    and of render_map), its pixel has depth > 0 and every pixel with depth > 0 of the (2 window + 1)^2 square around it,
-    clipped to the image, has (depth - z) > margin in float32 (z: the row's camera-frame depth).  Returns
-    FreeSpace(violations, keep): per sequence an (n_bound,) int32 tensor (views the row violates) and an (n_bound,) uint8
-    tensor (violations < min_views); rows at or beyond the device count hold 0 in both.  out: a FreeSpace (or pair) of
-    per-sequence lists to write into (a list, or an entry of it, may be None: that output is then not produced).  The
-    result is detached and never on the autograd tape: the mask is a constant, like the association."""
+    whatever L is; nothing is read back).  maps: per sequence a MapRows, the full form only: points and the counts are
+    read.  depth (B, L, H, W) or (B, L, H, W, 1), poses (B, L, 4, 4) camera-to-world, K (B, 4, 4).  A row violates a
+    view iff it projects into the frame (the projection of the map update and of render_map), its pixel has depth > 0
+    and every pixel with depth > 0 of the (2 window + 1)^2 square around it, clipped to the image, has (depth - z) >
+    margin in float32 (z: the row's camera-frame depth)..  Returns FreeSpace(violations, keep): per sequence an (n_bound,)
+    int32 tensor (views the row violates) and an (n_bound,) uint8 tensor (violations < min_views); rows at or beyond the
+    device count hold 0 in both..  out: a FreeSpace (or pair) of per-sequence lists to write into (a list, or an entry of
+    it, may be None: that output is then not produced)..  The result is detached and never on the autograd tape: the mask
+    is a constant, like the association."""
     who = "free_space"
     margin, window, min_views = _carve_args(who, margin, window, min_views)
     for name, val in (("depth", depth), ("poses", poses), ("K", K)):
@@ -1758,40 +1799,23 @@ def free_space_batch(maps, depth, poses, K, *, margin=0.05, window=1, min_views=
         depth = depth.contiguous()
     dev = require_device(poses, K, depth[0, 0])
     seqs = (_C.CarveSeq * Bn)()
-    # held: where _c had to copy a sequence's points, the copy must outlive the loop -- freed at the next iteration, its
-    # block could be handed to a later sequence's output before the one launch below is enqueued
-    viol, keep, held = [], [], []
-    for b in range(Bn):
-        m = maps[b]
-        P, n_bound, n_dev = _c(m[0].detach()), m[4], m[5]
-        require_device(P, n_dev, poses)
-        n_bound = int(P.shape[0]) if n_bound is None else min(int(n_bound), int(P.shape[0]))
-        if n_bound < 0:
+    viol, keep, held = [], [], [_map_rows(m, read=("points",)) for m in maps]
+    for b, m in enumerate(held):
+        require_device(m.points, m.n_dev, poses)
+        if m.n_bound < 0:
             raise ValueError("%s: negative n_bound" % who)
-        outs = []
-        for i, (name, dtype) in enumerate((("violations", torch.int32), ("keep", torch.uint8))):
-            if out is None:
-                t = torch.empty((n_bound,), dtype=dtype, device=dev)
-            else:
-                t = None if out[i] is None else out[i][b]
-                if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (n_bound,) or
-                                      not t.is_contiguous()):
-                    raise ValueError("%s: out.%s[%d] must be a contiguous %s tensor of shape (%d,)"
-                                     % (who, name, b, str(dtype).split(".")[-1], n_bound))
-            outs.append(t)
-        if outs[0] is None and outs[1] is None:
-            raise ValueError("%s: out must ask for violations or keep (or both) of every map" % who)
+        outs = _seq_outs(who, out, (("violations", torch.int32), ("keep", torch.uint8)), b, m.n_bound, dev)
         require_device(outs[0], outs[1], poses)
         u = seqs[b]
-        u.map = _C.MapView(P.data_ptr() if n_bound > 0 else 0, 0, 0, 0, int(P.shape[0]), n_bound,
-                           0 if n_dev is None else n_dev.data_ptr())
+        u.map = _map_view(m)
+        if m.n_bound == 0:
+            u.map.points = None   # (an empty map: nothing to read)
         u.depth = depth.data_ptr() + b * int(depth.stride(0)) * 4
         u.depth_stride_view = int(depth.stride(1)) if Lv > 1 else H * W
         u.poses16, u.K16 = poses.data_ptr() + b * Lv * 64, K.data_ptr() + b * 64
         u.violations, u.keep = (0 if t is None else t.data_ptr() for t in outs)
         viol.append(outs[0])
         keep.append(outs[1])
-        held.append(P)
     check(lib().gs_free_space_dc_f32(seqs, Bn, Lv, H, W, margin, window, min_views, stream(dev)),
           "gs_free_space_dc_f32")
     return FreeSpace(viol, keep)
@@ -1841,17 +1865,17 @@ def _voxel_args(who, voxel_size):
 
 def voxel_keep_batch(maps, voxel_size, *, out=None):
     """Which rows of B maps are the one surfel their voxel keeps (gs_voxel_keep_dc_f32: an elect and a resolve launch per
-    8 sequences over a hash table in scratch; nothing is read back).  maps: per sequence (points, normals, colors,
-    features, n_bound, n_dev) as in free_space_batch -- only the points, the confidence (features, when it has one
-    channel) and the counts are read.  With n = min(n_dev[0], n_bound): the voxel of a row is floor(p / voxel_size) per
-    component in float32; a row is griddable iff its point is finite and every voxel index lies in [-2^20, 2^20); among
-    the griddable rows < n of a voxel the winner has the largest confidence (its float32 bit pattern when >= +0.0, else
-    0: NaN and negative values score 0), ties go to the lowest row.  Returns VoxelKeep(keep, winner, unplaced): per
-    sequence an (n_bound,) uint8 tensor (1: the row is below the count and is not griddable or is its voxel's winner) and
-    an (n_bound,) int64 tensor (the winner of the row's voxel; the row itself when not griddable; -1 at or beyond the
-    count), and a (B,) int32 tensor on the device (rows the table could not place and that were kept: 0).  out: a pair
-    (keep, winner) of per-sequence lists to write into (a list, or an entry of it, may be None: that output is then not
-    produced).  The result is detached and never on the autograd tape: the mask is a constant, like the association."""
+    8 sequences over a hash table in scratch; nothing is read back).  maps: per sequence a MapRows, the full form only:
+    the points, the confidence (features, when it has one channel) and the counts are read.  With n = min(n_dev[0],
+    n_bound): the voxel of a row is floor(p / voxel_size) per component in float32; a row is griddable iff its point is
+    finite and every voxel index lies in [-2^20, 2^20); among the griddable rows < n of a voxel the winner has the
+    largest confidence (its float32 bit pattern when >= +0.0, else 0: NaN and negative values score 0), ties go to the
+    lowest row..  Returns VoxelKeep(keep, winner, unplaced): per sequence an (n_bound,) uint8 tensor (1: the row is below
+    the count and is not griddable or is its voxel's winner) and an (n_bound,) int64 tensor (the winner of the row's
+    voxel; the row itself when not griddable; -1 at or beyond the count), and a (B,) int32 tensor on the device (rows
+    the table could not place and that were kept: 0)..  out: a pair (keep, winner) of per-sequence lists to write into (a
+    list, or an entry of it, may be None: that output is then not produced)..  The result is detached and never on the
+    autograd tape: the mask is a constant, like the association."""
     who = "voxel_keep"
     voxel_size = _voxel_args(who, voxel_size)
     if not isinstance(maps, (list, tuple)) or len(maps) == 0:
@@ -1867,36 +1891,23 @@ def voxel_keep_batch(maps, voxel_size, *, out=None):
         if m[3] is not None and (not torch.is_tensor(m[3]) or m[3].ndim != 2 or m[3].shape[0] < m[0].shape[0]):
             raise ValueError("%s: features must be (rows, F) with as many rows as points, for maps[%d]" % (who, b))
     _warn_detached(who, *[t for m in maps for t in (m[0], m[3])])
-    # held: copies that _c had to make must outlive the loop (as in free_space_batch)
-    held = [(_c(m[0].detach()), None if m[3] is None or m[3].shape[1] != 1 else _c(m[3].detach())) for m in maps]
-    dev = require_device(*[t for h in held for t in h])
+    # (the confidence competes only as a single channel: any other feature layout is not read)
+    held = [_map_rows(m, read=("points", "features") if m[3] is not None and m[3].shape[1] == 1 else ("points",))
+            for m in maps]
+    dev = require_device(*[t for h in held for t in h[:4]])
     unplaced = torch.empty((Bn,), dtype=torch.int32, device=dev)
     ws = Workspace.get(dev)
     L = lib()
     seqs = (_C.VoxelKeepSeq * Bn)()
     keep, winner = [], []
     for b in range(Bn):
-        P, Cf = held[b]
-        n_bound, n_dev = maps[b][4], maps[b][5]
+        P, _, _, Cf, n_bound, n_dev = held[b]
         require_device(P, Cf, n_dev)
-        n_bound = int(P.shape[0]) if n_bound is None else min(int(n_bound), int(P.shape[0]))
         if n_bound < 0:
             raise ValueError("%s: negative n_bound" % who)
         if n_bound > VOXEL_MAX_ROWS:
             raise ValueError("%s: maps of 2^31 rows or more are not supported" % who)
-        outs = []
-        for i, (name, dtype) in enumerate((("keep", torch.uint8), ("winner", torch.int64))):
-            if out is None:
-                t = torch.empty((n_bound,), dtype=dtype, device=dev)
-            else:
-                t = None if out[i] is None else out[i][b]
-                if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (n_bound,) or
-                                      not t.is_contiguous()):
-                    raise ValueError("%s: out.%s[%d] must be a contiguous %s tensor of shape (%d,)"
-                                     % (who, name, b, str(dtype).split(".")[-1], n_bound))
-            outs.append(t)
-        if outs[0] is None and outs[1] is None:
-            raise ValueError("%s: out must ask for keep or winner (or both) of every map" % who)
+        outs = _seq_outs(who, out, (("keep", torch.uint8), ("winner", torch.int64)), b, n_bound, dev)
         require_device(outs[0], outs[1], P)
         nbytes = int(L.gs_voxel_keep_scratch_bytes(n_bound))
         u = seqs[b]
@@ -2037,11 +2048,11 @@ def bilateral_depth(depth, radius=3, sigma_space=2.0, sigma_range=0.03, out=None
 
 def render_map_backward_batch(maps, poses, K, index, upstream, H, W, radius=0, want=(True, True, True, True, True)):
     """Reverse mode of render_map_batch for B sequences in ONE call of gs_render_map_backward_dc_f32 (8 sequences and 4
-    views per launch).  maps: per sequence (points, normals, n_bound, n_dev) as given to the forward (normals may be
-    None when upstream[2] is); poses (B, L, 4, 4), K (B, 4, 4), index (B, L, H, W) int64: the index image of the
-    forward; upstream: (depth_bar (B, L, H, W[, 1]), color_bar (B, L, H, W, 3), normal_bar (B, L, H, W, 3),
-    confidence_bar (B, L, H, W[, 1])), any of them None (its terms are skipped).  want: which of (points_bar,
-    normals_bar, colors_bar, ccounts_bar, poses_bar) to compute.  Returns (per-sequence list of (points_bar (rows, 3),
+    views per launch).  maps: per sequence a MapRows or its short form, as given to the forward (points and normals
+    are read; normals may be None when upstream[2] is); poses (B, L, 4, 4), K (B, 4, 4), index (B, L, H, W) int64: the
+    index image of the forward; upstream: (depth_bar (B, L, H, W[, 1]), color_bar (B, L, H, W, 3), normal_bar (B, L, H,
+    W, 3), confidence_bar (B, L, H, W[, 1])), any of them None (its terms are skipped)..  want: which of (points_bar,
+    normals_bar, colors_bar, ccounts_bar, poses_bar) to compute..  Returns (per-sequence list of (points_bar (rows, 3),
     normals_bar (rows, 3), colors_bar (rows, 3), ccounts_bar (rows, 1)) with None where not wanted, poses_bar (B, L, 4,
     4) or None); rows = points.shape[0], rows at or beyond the count hold zeros."""
     poses, K, index = _c(poses.detach()), _c(K.detach()), _c(index, torch.int64)
@@ -2061,31 +2072,19 @@ def render_map_backward_batch(maps, poses, K, index, upstream, H, W, radius=0, w
     ws = Workspace.get(dev)
     seqs = (_C.RenderBackwardSeq * Bn)()
     P1 = Lv * H * W
-    rows_out = []
-    held = []
-    for b in range(Bn):
-        P, N = _c(maps[b][0].detach()), (None if maps[b][1] is None else _c(maps[b][1].detach()))
-        n_bound, n_dev = maps[b][2], maps[b][3]
-        require_device(P, N, n_dev, poses)
+    rows_out, held = [], [_map_rows(m, read=("points", "normals"), four_ok=True) for m in maps]
+    for b, m in enumerate(held):
+        P, N, n_bound = m.points, m.normals, m.n_bound
+        require_device(P, N, m.n_dev, poses)
         rows = int(P.shape[0])
         if P.ndim != 2 or P.shape[1] != 3 or (N is not None and N.shape[0] < rows):
             raise ValueError("render_map_backward: points must be (rows, 3) and the normals must hold as many rows")
         if N is None and ups[2] is not None:
             raise ValueError("render_map_backward: normal_bar given but the map has no normals")
-        n_bound = rows if n_bound is None else min(int(n_bound), rows)
-        outs = []
-        for i, c in enumerate((3, 3, 3, 1)):
-            t = None
-            if want[i]:
-                t = torch.empty((rows, c), dtype=f32, device=dev)
-                if n_bound < rows:
-                    t[n_bound:].zero_()   # (rows of the buffer behind the bound: the kernel writes the first n_bound rows)
-            outs.append(t)
+        outs = [_rows_bar(rows, c, n_bound, dev) if want[i] else None for i, c in enumerate((3, 3, 3, 1))]
         rows_out.append(tuple(outs))
-        held.append((P, N))
         u = seqs[b]
-        u.map = _C.MapView(P.data_ptr(), 0 if N is None else N.data_ptr(), 0, 0, rows, n_bound,
-                           0 if n_dev is None else n_dev.data_ptr())
+        u.map = _map_view(m)
         u.poses16, u.K16, u.index = poses.data_ptr() + b * Lv * 64, K.data_ptr() + b * 64, index.data_ptr() + b * P1 * 8
         u.depth_bar, u.color_bar, u.normal_bar, u.confidence_bar = (
             None if t is None else t.data_ptr() + b * P1 * c * 4 for t, c in zip(ups, (1, 3, 3, 1)))

@@ -531,9 +531,8 @@ def _update_map_one_call(pointclouds, rgbdimages, dist_th, dot_th, sigma):
     gn = torch.empty_like(gv)
     maps = []
     for b in range(B):
-        P, N, C, F = pointclouds._reserve(b, H * W, pointclouds.RESERVE_FRAMES)   # before _count_of: see _fuse
-        n0, n_dev = pointclouds._count_of(b)
-        maps.append((P, N, C, F, n0, n_dev))
+        bufs = pointclouds._reserve(b, H * W, pointclouds.RESERVE_FRAMES)   # before _count_of: see _fuse
+        maps.append(ops.MapRows(*bufs, *pointclouds._count_of(b)))
     cnt, _, _, _ = ops.update_map_fusion_batch_(maps, vm[:, 0], nm[:, 0], depth[:, 0, ..., 0], rgb[:, 0],
                                                 alpha[:, 0, ..., 0], poses, K, dist_th, dot_th, RENORMALIZE_UNMATCHED,
                                                 out=(gv[:, 0], gn[:, 0]))

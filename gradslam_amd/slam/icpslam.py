@@ -197,11 +197,8 @@ class ICPSLAM(nn.Module):
                 # target set stays on the device.
                 # All sequences of the batch go through ONE chain of launches (gs_localize_batch_f32).
                 out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=fr.device)
-                maps = []
-                for b in range(B):
-                    n_b, n_dev = pointclouds._count_of(b)
-                    maps.append((pointclouds._buf["points"][b], pointclouds._buf["normals"][b], n_b, n_dev))
-                if all(m[2] > 0 for m in maps):
+                maps = pointclouds._map_rows(("points", "normals"))
+                if all(m.n_bound > 0 for m in maps):
                     ops.localize_batch(fr.vertex_map[:, 0], fr.depth_image[:, 0, ..., 0], K, prev_poses, maps,
                                        self.dsratio, mode=self.odomprov._mode, out=out.view(B, 4, 4),
                                        **self.odomprov._kwargs())

@@ -508,6 +508,19 @@ class Pointclouds(object):
         dc.poll()
         return dc.bound, dc.dev
 
+    def _map_rows(self, attrs=_ATTRS):
+        """The `maps` argument of the batched map passes of ops: one ops.MapRows per sequence over the buffers, read in
+        place; attributes not in `attrs`, or absent, are None.  The counts come from _count_of: a device-side count is
+        never forced to the host."""
+        from .. import ops
+        return [ops.MapRows(*[self._buf[k][b] if k in attrs and self._buf[k] is not None else None for k in _ATTRS],
+                            *self._count_of(b)) for b in range(len(self._n_host))]
+
+    def _row_outs(self, maps, dtype, want):
+        """per sequence an empty (bound,) output of a pass that marks rows (ops._seq_outs), None where not wanted"""
+        return [torch.empty(min(m.n_bound, int(m.points.shape[0])), dtype=dtype, device=self.device) if want else None
+                for m in maps]
+
     def _tighten_counts(self):
         """Reads the device-side counts back (one sync) and makes the host-side BOUNDS exact, keeping the device counts in
         charge: the next step takes the same path as without this call (used by profiling passes, whose byte counts come
@@ -599,10 +612,6 @@ class Pointclouds(object):
         if tuple(intrinsics.shape) != (B, 1, 4, 4):
             raise ValueError("intrinsics should have shape {}, but had shape {}".format((B, 1, 4, 4),
                                                                                      tuple(intrinsics.shape)))
-        maps = []
-        for b in range(B):
-            bound, n_dev = self._count_of(b)   # (never forces a device-side count to the host)
-            maps.append(tuple(self._buf[k][b] for k in _ATTRS) + (bound, n_dev))
         guard = None
         if differentiable:
             generation = self._generation
@@ -612,7 +621,7 @@ class Pointclouds(object):
                     raise RuntimeError("the map was changed in place after render(differentiable=True) and before its "
                                        "backward pass: the saved winners no longer belong to the map rows (run backward "
                                        "before the next PointFusion.step, or render again)")
-        out = ops.render_map_batch(maps, poses, intrinsics[:, 0], int(height), int(width), radius=radius,
+        out = ops.render_map_batch(self._map_rows(), poses, intrinsics[:, 0], int(height), int(width), radius=radius,
                                    min_confidence=min_confidence, cull_backfaces=cull_backfaces,
                                    differentiable=differentiable, guard=guard)
         frames = RGBDImages(out.color, out.depth, intrinsics.detach().to(torch.float32),
@@ -765,15 +774,10 @@ class Pointclouds(object):
             raise ValueError("frames must hold one sequence per pointcloud. Got {} != {}.".format(frames.shape[0], B))
         d = frames.depth_image
         d = d[:, :, 0] if frames.channels_first else d[..., 0]   # (B, L, H, W), a view: one channel either way
-        maps, out_v, out_k = [], [], []
-        for b in range(B):
-            bound, n_dev = self._count_of(b)   # (never forces a device-side count to the host)
-            maps.append((self._buf["points"][b], None, None, None, bound, n_dev))
-            rows = min(bound, int(self._buf["points"][b].shape[0]))
-            out_v.append(torch.empty(rows, dtype=torch.int32, device=self.device) if want[0] else None)
-            out_k.append(torch.empty(rows, dtype=torch.uint8, device=self.device) if want[1] else None)
+        maps = self._map_rows(("points",))
+        out = (self._row_outs(maps, torch.int32, want[0]), self._row_outs(maps, torch.uint8, want[1]))
         return ops.free_space_batch(maps, d, frames.poses, frames.intrinsics[:, 0], margin=margin, window=window,
-                                    min_views=min_views, out=(out_v, out_k))
+                                    min_views=min_views, out=out)
 
     def free_space_violations(self, frames, *, margin: float = 0.05, window: int = 1):
         r"""Per sequence the (N_b,) int32 number of frames of `frames` (an `RGBDImages` of shape (B, L, H, W) with poses)
@@ -813,14 +817,11 @@ class Pointclouds(object):
         pts = self._buf["points"]
         if self.device.type == "cuda" and all(t.dtype == torch.float32 for t in pts) and \
                 (conf is None or all(t.dtype == torch.float32 for t in conf)):
-            maps, out_k, out_w = [], [], []
-            for b in range(B):
-                bound, n_dev = self._count_of(b)   # (never forces a device-side count to the host)
-                maps.append((pts[b].detach(), None, None, None if conf is None else conf[b].detach(), bound, n_dev))
-                rows = min(bound, int(pts[b].shape[0]))
-                out_k.append(torch.empty(rows, dtype=torch.uint8, device=self.device) if want[0] else None)
-                out_w.append(torch.empty(rows, dtype=torch.int64, device=self.device) if want[1] else None)
-            r = ops.voxel_keep_batch(maps, voxel_size, out=(out_k, out_w))
+            # (detached: the mask is a constant, and the pass need not say so)
+            maps = [m._replace(points=m.points.detach(), features=None if conf is None else m.features.detach())
+                    for m in self._map_rows(("points", "features"))]
+            r = ops.voxel_keep_batch(maps, voxel_size, out=(self._row_outs(maps, torch.uint8, want[0]),
+                                                            self._row_outs(maps, torch.int64, want[1])))
             return r.keep, r.winner
         keep, winner = [], []
         for b, nb in enumerate(self._n):
@@ -860,10 +861,8 @@ class Pointclouds(object):
     def _prune_hip(self, conf, keep, young_mark):
         from .. import ops
         B = len(self._n_host)
-        maps, keeps = [], []
-        for b in range(B):
-            bound, n_dev = self._count_of(b)
-            maps.append(tuple(None if self._buf[k] is None else self._buf[k][b] for k in _ATTRS) + (bound, n_dev))
+        maps, keeps = self._map_rows(), []
+        for b, bound in enumerate(m.n_bound for m in maps):
             kp = keep[b]
             if kp is not None and kp.shape[0] < bound:   # (rows the caller's tensor does not cover are removed)
                 kp = torch.cat([kp.to(torch.uint8), torch.zeros(bound - kp.shape[0], dtype=torch.uint8, device=kp.device)])
