@@ -117,6 +117,11 @@ class PicpBackwardSeq(C.Structure):
                 ("scratch_bytes", C.c_int64)]
 
 
+class PicpOrderedBackwardSeq(C.Structure):
+    """gs_picp_ordered_backward_seq: gs_picp_backward_seq plus the optional copies of the record (keys, contributions)."""
+    _fields_ = [("base", PicpBackwardSeq), ("key_out", C.c_void_p), ("contrib_out", C.c_void_p)]
+
+
 class PicpColorSeq(C.Structure):
     """gs_picp_color_seq: gs_picp_seq plus the live colour image and the model intensity of the view."""
     _fields_ = [("base", PicpSeq), ("color", C.c_void_p), ("model_intensity", C.c_void_p)]
@@ -224,6 +229,10 @@ _PROTOS = {
                                          C.POINTER(PicpParams), _vp],
     "gs_projective_icp_backward_scratch_bytes": [_i32, _i32, _i32, _i64],
     "gs_projective_icp_backward_batch_f32": [C.POINTER(PicpBackwardSeq), _i32, _i32, _i32, C.POINTER(PicpParams), _vp],
+    "gs_projective_icp_ordered_backward_scratch_bytes": [_i32, _i32, _i32, _i64],
+    "gs_projective_icp_ordered_backward_sort_scratch_bytes": [_i32, _i32, _i32, _i32],
+    "gs_projective_icp_ordered_backward_batch_f32": [C.POINTER(PicpOrderedBackwardSeq), _i32, _i32, _i32,
+                                                     C.POINTER(PicpParams), _f, _i32, _vp, _i64, _vp],
     "gs_model_intensity_f32": [_vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "gs_projective_icp_color_scratch_bytes": [_i32, _i32, _i32],
     "gs_projective_icp_color_batch_f32": [C.POINTER(PicpColorSeq), _i32, _i32, _i32, C.POINTER(PicpParams), _f, _vp],
@@ -265,7 +274,9 @@ _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scrat
             "gs_projective_icp_tape_bytes": _i64, "gs_projective_icp_backward_scratch_bytes": _i64,
             "gs_projective_icp_color_scratch_bytes": _i64, "gs_projective_icp_scaled_scratch_bytes": _i64,
             "gs_projective_icp_color_scaled_scratch_bytes": _i64,
-            "gs_projective_icp_color_joint_scaled_scratch_bytes": _i64, "gs_voxel_keep_scratch_bytes": _i64}
+            "gs_projective_icp_color_joint_scaled_scratch_bytes": _i64, "gs_voxel_keep_scratch_bytes": _i64,
+            "gs_projective_icp_ordered_backward_scratch_bytes": _i64,
+            "gs_projective_icp_ordered_backward_sort_scratch_bytes": _i64}
 EXPORTS = tuple(_PROTOS)
 
 

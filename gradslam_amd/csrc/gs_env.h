@@ -1,8 +1,9 @@
 // gs_env.h — every GRADSLAM_HIP_* environment switch the library reads, in ONE place (README: the knob table).
 // gs_env() reads them once per process (a function-local static: thread-safe).  None of them changes a result (tests/
-// test_hip_engine_matrix.py, tests/test_hip_batch.py).  Not here: GRADSLAM_HIP_DETERMINISTIC_BACKWARD, read per call (gs_icp_bwd.hip);
-// it covers the ICP backward only -- the map scatter of the projective ICP's backward (gs_picp_bwd.hip) is float64 atomics in
-// every mode.
+// test_hip_engine_matrix.py, tests/test_hip_batch.py).  Not here: GRADSLAM_HIP_DETERMINISTIC_BACKWARD, read per call (on iff
+// atoi of the value is nonzero) in two places: gs_icp_backward_f32 (gs_icp_bwd.hip) reads it itself; for the projective
+// ICP's backward (gs_picp_bwd.hip) the Python layer reads it with the same rule (ops.deterministic_backward_env) and then
+// calls gs_projective_icp_ordered_backward_batch_f32 -- the C entries of that file never look at the environment.
 #pragma once
 #include <stdlib.h>
 #include <string.h>

@@ -29,8 +29,10 @@
 // tree per wave, (w0 + w1) + (w2 + w3), chunk partials in ascending order; no float atomics) and vertex_bar is
 // accumulated per slot by the slot's own thread across the serialised iterations (a slot is its own pixel): vertex_bar
 // and init_pose_bar are BITWISE REPRODUCIBLE.  Several slots can land on the same surfel, so points_bar and normals_bar
-// are float64 atomic adds into float64 (n_bound, 3) buffers, rounded once: reproducible up to the order of the float64
-// additions (GRADSLAM_HIP_DETERMINISTIC_BACKWARD does not apply here; a sorted scatter is not built).
+// are by default float64 atomic adds into float64 (n_bound, 3) buffers, rounded once: reproducible up to the order of the
+// float64 additions.  The ORDERED mode (gs_projective_icp_ordered_backward_batch_f32; the Python layer takes it under
+// GRADSLAM_HIP_DETERMINISTIC_BACKWARD or deterministic=True) makes them bitwise reproducible as well; see "ordered mode"
+// below.
 // Every output may be NULL: its work and its buffer are skipped; with both map outputs NULL nothing of map size is
 // touched.
 // gs_projective_icp_robust_backward_batch_f32 (a tape of the forward with Huber weights, the same huber_delta) launches
@@ -40,6 +42,28 @@
 // From gs_picp_dev.h, ONE definition with the forward: the inputs and the geometry of a launch (PiInputs, PiGeom), the
 // point stage's block prologue (pi_prologue), pi_associate, the chunk reduction (pi_chunk_reduce, here with 12 terms) and
 // the scalar stage's column sum of the chunk partials (pi_column_sums, here starting from 0.0).
+//
+// Ordered mode.  The RECORD instances of the point stage do not add a slot's two 3-vectors atomically: they record them,
+// contrib[k][0:6] (float64: the contribution to points_bar[row], then the one to normals_bar[row]) and key[k] = the
+// slot's row, or 0x7fffffff for a slot that contributes nothing.  A settle step follows each point stage: ONE stable
+// radix sort of the (sequence << 32 | key, slot) pairs of all sequences of the launch group (hipcub, 35 key bits), then
+// one thread per run of equal keys adds the run up and adds the sum to the row's float64 accumulator.  Two more launches
+// and a sort per iteration for up to 8 sequences; the record and the sort buffers are per-iteration scratch, reused.
+// The order contract (tests/picp_ordered_ref.py restates it, tests/test_hip_picp_ordered_backward.py pins the bits):
+//   * acc[row] starts at +0.0; a row that nobody touches ends as +0.0;
+//   * the iterations are processed in launch order, numiters - 1 down to 0;
+//   * in an iteration a row's run sum starts at 0.0 and adds the contributions of its slots in ascending slot id, then
+//     acc[row] = acc[row] + run_sum;
+//   * an iteration without inliers (state->active == 0) records no contribution: the point stage writes the key "none"
+//     for every slot of the lattice in every launch, so nothing of the iteration before is seen again;
+//   * slot ids at or beyond nslots in the tail of the last chunk write nothing; a stale index entry is rejected by
+//     pi_associate as ever and never recorded;
+//   * the accumulators are rounded to float32 once at the end;
+//   * vertex_bar, init_pose_bar, the scalar stage and the 12 sums are those of the atomic mode, bit for bit (the slot's
+//     arithmetic is ONE definition, pb_point).
+// With no map output asked for in a launch group the group runs the atomic mode's launches: nothing is recorded or sorted.
+#include <hipcub/hipcub.hpp>
+
 #include "gs_picp_dev.h"
 #include "gs_se3_f64.h"
 
@@ -68,6 +92,21 @@ struct PbSeq {
 struct PbBatch {
   PbSeq s[GS_MAX_BATCH];
   PiGeom g;
+};
+// ordered mode: what the RECORD instances of the point stage write, per launch group (slot k of sequence b is pair
+// b nslots + k of the sort)
+constexpr int32_t PB_NO_KEY = 0x7fffffff;
+struct PbRecord {
+  double* contrib[GS_MAX_BATCH];   // (nslots, 6): a used slot's contributions to points_bar[row] and normals_bar[row]
+  int32_t* key[GS_MAX_BATCH];      // (nslots): the slot's row, or PB_NO_KEY
+  uint64_t* sort_key;              // (B nslots): sequence << 32 | key
+};
+// ... and what the settle step needs of the group
+struct PbSettle {
+  const double* contrib[GS_MAX_BATCH];
+  double* pbar[GS_MAX_BATCH];
+  double* mbar[GS_MAX_BATCH];
+  int64_t nslots;
 };
 
 // Scalar stage in front of the point stage of iteration `it` (it == -1: the last one, which only hands out
@@ -154,14 +193,18 @@ __global__ void __launch_bounds__(GS_PI_FIN) gs_picp_bwd_scalar_kernel(const PbB
 // bb = e (w + w' (b - c)) takes the place of e in sb, points_bar and normals_bar.
 // taped (the scaled backward): the threshold is not the launch's but the one the forward derived for this iteration and
 // taped (PiTapeRow::pad[0], the median rule of gs_picp_scale.hip), a constant of the pass like the clip flags.
-template <bool ROBUST>
-GS_DEV void pb_point(const PbBatch& pb, const int it, const int first, const int last, const float delta_launch,
-                     const bool taped) {
+// RECORD (the ordered mode, rec != NULL): the two map contributions are not added atomically but stored in the slot's
+// record (zeros for a map output that is not asked for), and EVERY slot of the lattice writes its key, used or not,
+// active iteration or not.
+template <bool ROBUST, bool RECORD>
+GS_DEV void pb_point(const PbBatch& pb, const PbRecord* rec, const int it, const int first, const int last,
+                     const float delta_launch, const bool taped) {
   __shared__ GsCamera cam;
   __shared__ float Ts[12];
   __shared__ double ux[12];   // u(6), xi(6)
   __shared__ int active;
-  const PbSeq& q = pb.s[blockIdx.x % pb.g.B];
+  const int seq = blockIdx.x % pb.g.B;
+  const PbSeq& q = pb.s[seq];
   // (what this stage needs besides the camera and the pose, in front of the prologue's barrier)
   if (threadIdx.x == 0) active = q.state->active;
   if (threadIdx.x >= 2 * GS_WAVE && threadIdx.x < 2 * GS_WAVE + 12) {
@@ -173,6 +216,7 @@ GS_DEV void pb_point(const PbBatch& pb, const int it, const int first, const int
   const int64_t p = t.p;
   const int k = t.k;
   bool used = false;
+  int32_t key = PB_NO_KEY;   // (RECORD)
   double sb[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
   if (t.in_lattice) {
     if (active) {   // (block-uniform; an iteration without inliers has no used slot)
@@ -218,16 +262,41 @@ GS_DEV void pb_point(const PbBatch& pb, const int it, const int first, const int
         sb[0] = (m[1] * w[2] - m[2] * w[1]) - e * m[0];
         sb[1] = (m[2] * w[0] - m[0] * w[2]) - e * m[1];
         sb[2] = (m[0] * w[1] - m[1] * w[0]) - e * m[2];
+        double* cr = nullptr;
+        if constexpr (RECORD) {
+          if (q.pbar || q.mbar) {
+            cr = rec->contrib[seq] + 6 * (int64_t)k;
+            key = (int32_t)row;   // (row < n_bound < PB_NO_KEY: the entry checks it)
+          }
+        }
         if (q.pbar) {
 #pragma unroll
-          for (int c = 0; c < 3; ++c) atomicAdd(&q.pbar[3 * row + c], e * m[c]);
+          for (int c = 0; c < 3; ++c) {
+            const double x = e * m[c];
+            if constexpr (RECORD) cr[c] = x;
+            else atomicAdd(&q.pbar[3 * row + c], x);
+          }
+        } else if (RECORD && cr) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) cr[c] = 0.0;
         }
         if (q.mbar) {
           const double wxs[3] = {w[1] * s[2] - w[2] * s[1], w[2] * s[0] - w[0] * s[2], w[0] * s[1] - w[1] * s[0]};
 #pragma unroll
-          for (int c = 0; c < 3; ++c) atomicAdd(&q.mbar[3 * row + c], ab[c] + wxs[c] + e * r[c]);
+          for (int c = 0; c < 3; ++c) {
+            const double x = ab[c] + wxs[c] + e * r[c];
+            if constexpr (RECORD) cr[3 + c] = x;
+            else atomicAdd(&q.mbar[3 * row + c], x);
+          }
+        } else if (RECORD && cr) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) cr[3 + c] = 0.0;
         }
       }
+    }
+    if constexpr (RECORD) {   // every slot of the lattice, whatever the iteration: nothing of the launch before stays
+      rec->key[seq][k] = key;
+      rec->sort_key[(int64_t)seq * pb.g.nslots + k] = ((uint64_t)seq << 32) | (uint32_t)key;
     }
     if (q.vacc) {   // a slot is its own pixel and the iterations are serialised: no atomics
 #pragma unroll
@@ -246,13 +315,58 @@ GS_DEV void pb_point(const PbBatch& pb, const int it, const int first, const int
 
 __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_bwd_point_kernel(const PbBatch pb, const int it, const int first,
                                                                         const int last) {
-  pb_point<false>(pb, it, first, last, 0.0f, false);
+  pb_point<false, false>(pb, nullptr, it, first, last, 0.0f, false);
 }
 
 __global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_bwd_point_kernel(const PbBatch pb, const int it,
                                                                                const int first, const int last,
                                                                                const float delta, const int taped) {
-  pb_point<true>(pb, it, first, last, delta, taped != 0);
+  pb_point<true, false>(pb, nullptr, it, first, last, delta, taped != 0);
+}
+
+// ------------------------------------------------------------------ ordered mode: the RECORD point stages, the settle step
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_ordered_picp_bwd_point_kernel(const PbBatch pb, const PbRecord rec,
+                                                                                const int it, const int first,
+                                                                                const int last) {
+  pb_point<false, true>(pb, &rec, it, first, last, 0.0f, false);
+}
+
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_ordered_robust_picp_bwd_point_kernel(const PbBatch pb, const PbRecord rec,
+                                                                                       const int it, const int first,
+                                                                                       const int last, const float delta,
+                                                                                       const int taped) {
+  pb_point<true, true>(pb, &rec, it, first, last, delta, taped != 0);
+}
+
+// the values of the sort: 0, 1, 2, ... (pair b nslots + k is slot k of sequence b); written once per launch group
+__global__ void __launch_bounds__(256) gs_ordered_picp_bwd_iota_kernel(uint32_t* __restrict__ v, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) v[i] = (uint32_t)i;
+}
+
+// The pairs of a point stage sorted by (sequence, row), equal keys in ascending slot order (the sort is stable and its
+// input is in slot order).  The thread at the head of a run adds the run's contributions, one after the other from 0.0,
+// and then adds the sum to the row's accumulators: a fixed order, and no other thread of any launch touches the row
+// meanwhile (the launches of the backward are ordered).  The shape of bw_segment_add_kernel (gs_icp_bwd.hip).
+__global__ void __launch_bounds__(256) gs_ordered_picp_bwd_settle_kernel(const PbSettle z, const uint64_t* __restrict__ key,
+                                                                         const uint32_t* __restrict__ src, int64_t n) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n) return;
+  const uint64_t j = key[p];
+  const int64_t row = (int64_t)(uint32_t)j;
+  if (row == PB_NO_KEY || (p > 0 && key[p - 1] == j)) return;   // a slot without a row, or not the head of its run
+  const int b = (int)(j >> 32);
+  const double* contrib = z.contrib[b];
+  const int64_t slot0 = (int64_t)b * z.nslots;   // (the sequence's first pair)
+  double t[3] = {0.0, 0.0, 0.0}, m[3] = {0.0, 0.0, 0.0};
+  for (int64_t q = p; q < n && key[q] == j; ++q) {
+    const double* c = contrib + 6 * ((int64_t)src[q] - slot0);
+    for (int a = 0; a < 3; ++a) { t[a] += c[a]; m[a] += c[3 + a]; }
+  }
+  if (z.pbar[b])
+    for (int a = 0; a < 3; ++a) z.pbar[b][3 * row + a] = z.pbar[b][3 * row + a] + t[a];
+  if (z.mbar[b])
+    for (int a = 0; a < 3; ++a) z.mbar[b][3 * row + a] = z.mbar[b][3 * row + a] + m[a];
 }
 
 __global__ void __launch_bounds__(256) gs_picp_bwd_cast_kernel(const double* __restrict__ in, int64_t n,
@@ -272,18 +386,53 @@ extern "C" int64_t gs_projective_icp_backward_scratch_bytes(int H, int W, int st
                    2 * pb_rows_bytes(n_map));
 }
 
+// ordered mode: the record of a sequence lies behind its atomic-mode scratch, contrib (nslots, 6) | key (nslots); the
+// sort buffers of a launch group of g sequences, n = g nslots pairs, are one scratch of the call that its groups take
+// in turn: sort_key (n) | sorted keys (n) | values (n) | sorted values (n) | hipcub's temporary storage
+static size_t pb_contrib_bytes(int64_t nslots) { return gs_align((size_t)nslots * 6 * sizeof(double)); }
+static size_t pb_key_bytes(int64_t nslots) { return gs_align((size_t)nslots * sizeof(int32_t)); }
+static size_t pb_sort_temp_bytes(int64_t n) { return gs_align(64 * (size_t)n + (1u << 20)); }
+static int64_t pb_group(int B) { return B < GS_MAX_BATCH ? B : GS_MAX_BATCH; }
+
+extern "C" int64_t gs_projective_icp_ordered_backward_scratch_bytes(int H, int W, int stride, int64_t n_map) {
+  const int64_t base = gs_projective_icp_backward_scratch_bytes(H, W, stride, n_map);
+  if (base == 0) return 0;
+  const int64_t nslots = picp_slots(H, W, stride);
+  return base + (int64_t)(pb_contrib_bytes(nslots) + pb_key_bytes(nslots));
+}
+
+extern "C" int64_t gs_projective_icp_ordered_backward_sort_scratch_bytes(int B, int H, int W, int stride) {
+  if (B <= 0 || H <= 0 || W <= 0 || stride <= 0 || (int64_t)H * W >= (1ll << 31)) return 0;
+  const int64_t n = pb_group(B) * picp_slots(H, W, stride);
+  if (n >= (1ll << 31)) return 0;   // (hipcub counts the pairs in an int)
+  return (int64_t)(2 * gs_align((size_t)n * sizeof(uint64_t)) + 2 * gs_align((size_t)n * sizeof(uint32_t)) +
+                   pb_sort_temp_bytes(n));
+}
+
+// what the ordered entry adds to a call of pb_backward
+struct PbOrderedCall {
+  const gs_picp_ordered_backward_seq* seqs;
+  void* sort_scratch;
+  int64_t sort_scratch_bytes;
+};
+
 // the pass behind the entries; delta: the Huber threshold the forward ran with (0: the plain point kernel); taped: the
-// robust point kernel with every iteration's threshold from the tape (delta is then not read)
+// robust point kernel with every iteration's threshold from the tape (delta is then not read); oc: the ordered entry's
+// sequences and sort scratch (seqs_host is then NULL), or NULL: the atomic mode
 static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, int B, int H, int W,
-                       const gs_picp_params* params_host, float delta, bool taped, void* stream) {
-  PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
+                       const gs_picp_params* params_host, float delta, bool taped, const PbOrderedCall* oc,
+                       void* stream) {
+  PICP_REQUIRE(who, (oc ? oc->seqs != nullptr : seqs_host != nullptr) && params_host && B > 0 && H > 0 && W > 0,
+               "bad arguments");
   PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   const gs_picp_params& prm = *params_host;
   PICP_CHECK_PARAMS(who, prm);
   PICP_CHECK_DELTA(who, delta, "huber_delta");
   const int64_t nslots = picp_slots(H, W, prm.stride), nchunks = gs_ceil_div(nslots, GS_PI_CHUNK);
+  const auto seq = [&](int b) -> const gs_picp_backward_seq& { return oc ? oc->seqs[b].base : seqs_host[b]; };
+  bool any_map = false;
   for (int b = 0; b < B; ++b) {
-    const gs_picp_backward_seq& u = seqs_host[b];
+    const gs_picp_backward_seq& u = seq(b);
     PICP_REQUIRE(who, u.vertex && u.normal && u.depth && u.K16 && u.index && u.model_pose16 && u.tape && u.pose_bar16 &&
                    u.scratch,
                "NULL pointer");
@@ -291,16 +440,33 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
     PICP_REQUIRE(who, u.map.n_bound >= 0, "bad map size");
     PICP_REQUIRE(who, u.map.n_bound == 0 || (u.map.points && u.map.normals), "NULL pointer (map points / normals)");
     const bool want_map = u.points_bar || u.normals_bar;
-    PICP_REQUIRE(who, u.scratch_bytes >= gs_projective_icp_backward_scratch_bytes(H, W, prm.stride, want_map ? u.map.n_bound : 0),
-               "scratch too small");
+    any_map = any_map || (want_map && u.map.n_bound > 0);
+    if (oc) {
+      PICP_REQUIRE(who, u.map.n_bound < PB_NO_KEY, "map too large for int32 row keys (n_bound >= 0x7fffffff)");
+      PICP_REQUIRE(who, u.scratch_bytes >= gs_projective_icp_ordered_backward_scratch_bytes(H, W, prm.stride,
+                                                                                            want_map ? u.map.n_bound : 0),
+                   "scratch too small");
+    } else {
+      PICP_REQUIRE(who, u.scratch_bytes >= gs_projective_icp_backward_scratch_bytes(H, W, prm.stride, want_map ? u.map.n_bound : 0),
+                   "scratch too small");
+    }
+  }
+  if (oc && any_map) {
+    PICP_REQUIRE(who, pb_group(B) * nslots < (1ll << 31), "too many slots in a launch group for one sort (sequences x nslots >= 2^31)");
+    PICP_REQUIRE(who, oc->sort_scratch && ((uintptr_t)oc->sort_scratch & 7) == 0, "NULL or misaligned sort scratch");
+    PICP_REQUIRE(who, oc->sort_scratch_bytes >= gs_projective_icp_ordered_backward_sort_scratch_bytes(B, H, W, prm.stride),
+                 "sort scratch too small");
   }
   hipStream_t st = gs_stream(stream);
   for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
     const int nb = B - c0 < GS_MAX_BATCH ? B - c0 : GS_MAX_BATCH;
     PbBatch pb;
     picp_fill(pb.g, nb, H, W, prm.stride, prm.dist_th, prm.dot_th, prm.damp);
+    PbRecord rec{};
+    PbSettle sz{};
+    bool ordered = false;   // the group records and sorts: the ordered entry, and a map output asked for in the group
     for (int b = 0; b < nb; ++b) {
-      const gs_picp_backward_seq& u = seqs_host[c0 + b];
+      const gs_picp_backward_seq& u = seq(c0 + b);
       PbSeq& s = pb.s[b];
       picp_fill_inputs(s.in, u);
       s.tape = static_cast<const PiTapeRow*>(u.tape);
@@ -316,20 +482,74 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
       if (s.mbar) GS_HIP(hipMemsetAsync(s.mbar, 0, map_bytes, st));
       // pixels off the lattice get no gradient (the last point stage stores the lattice pixels)
       if (u.vertex_bar && prm.stride > 1) GS_HIP(hipMemsetAsync(u.vertex_bar, 0, (size_t)H * W * 3 * sizeof(float), st));
+      if (oc) {   // the sequence's record, behind the atomic mode's layout for the map size its scratch was checked for
+        char* r = static_cast<char*>(u.scratch) +
+                  gs_projective_icp_backward_scratch_bytes(H, W, prm.stride, (u.points_bar || u.normals_bar) ? u.map.n_bound : 0);
+        rec.contrib[b] = reinterpret_cast<double*>(r);
+        rec.key[b] = reinterpret_cast<int32_t*>(r + pb_contrib_bytes(nslots));
+        sz.contrib[b] = rec.contrib[b]; sz.pbar[b] = s.pbar; sz.mbar[b] = s.mbar;
+        ordered = ordered || s.pbar || s.mbar;
+      }
     }
     const unsigned blocks = (unsigned)nb * (unsigned)nchunks;
+    const int64_t npairs = (int64_t)nb * nslots;   // (ordered: < 2^31, checked above)
+    const unsigned pair_blocks = (unsigned)gs_ceil_div(npairs, 256);
+    uint64_t* keys_sorted = nullptr;
+    uint32_t *vals = nullptr, *vals_sorted = nullptr;
+    void* sort_temp = nullptr;
+    size_t sort_temp_bytes = 0;
+    if (ordered) {
+      char* p = static_cast<char*>(oc->sort_scratch);
+      rec.sort_key = reinterpret_cast<uint64_t*>(p); p += gs_align((size_t)npairs * sizeof(uint64_t));
+      keys_sorted = reinterpret_cast<uint64_t*>(p); p += gs_align((size_t)npairs * sizeof(uint64_t));
+      vals = reinterpret_cast<uint32_t*>(p); p += gs_align((size_t)npairs * sizeof(uint32_t));
+      vals_sorted = reinterpret_cast<uint32_t*>(p); p += gs_align((size_t)npairs * sizeof(uint32_t));
+      sort_temp = p;
+      sort_temp_bytes = pb_sort_temp_bytes(npairs);
+      sz.nslots = nslots;
+      size_t need = 0;   // (35 key bits: 3 of the sequence above the 32 of the row or PB_NO_KEY)
+      GS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, rec.sort_key, keys_sorted, vals, vals_sorted, (int)npairs, 0, 35, st));
+      if (need > sort_temp_bytes) {
+        gs_set_error("%s: %s", who, "sort scratch too small for hipcub's temporary storage");
+        return GS_ERR_INVALID;
+      }
+      hipLaunchKernelGGL(gs_ordered_picp_bwd_iota_kernel, dim3(pair_blocks), dim3(256), 0, st, vals, npairs);
+    }
     for (int it = prm.numiters - 1; it >= 0; --it) {
-      const int first = it == prm.numiters - 1;
+      const int first = it == prm.numiters - 1, last = it == 0 ? 1 : 0;
       hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb, it, first ? 0 : 1);
-      if (delta > 0.0f || taped)
-        hipLaunchKernelGGL(gs_robust_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first,
-                           it == 0 ? 1 : 0, delta, taped ? 1 : 0);
+      const bool robust = delta > 0.0f || taped;
+      if (!ordered) {
+        if (robust)
+          hipLaunchKernelGGL(gs_robust_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first, last,
+                             delta, taped ? 1 : 0);
+        else
+          hipLaunchKernelGGL(gs_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first, last);
+        continue;
+      }
+      if (robust)
+        hipLaunchKernelGGL(gs_ordered_robust_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, rec, it, first,
+                           last, delta, taped ? 1 : 0);
       else
-        hipLaunchKernelGGL(gs_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first, it == 0 ? 1 : 0);
+        hipLaunchKernelGGL(gs_ordered_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, rec, it, first, last);
+      for (int b = 0; b < nb; ++b) {   // the record as it stands, for the caller that asked (the tests)
+        const gs_picp_ordered_backward_seq& o = oc->seqs[c0 + b];
+        if (o.key_out)
+          GS_HIP(hipMemcpyAsync(o.key_out + (int64_t)it * nslots, rec.key[b], (size_t)nslots * sizeof(int32_t),
+                                hipMemcpyDeviceToDevice, st));
+        if (o.contrib_out && (pb.s[b].pbar || pb.s[b].mbar))
+          GS_HIP(hipMemcpyAsync(o.contrib_out + (int64_t)it * nslots * 6, rec.contrib[b], (size_t)nslots * 6 * sizeof(double),
+                                hipMemcpyDeviceToDevice, st));
+      }
+      // the settle step: ONE sort for the group, then one thread per run
+      size_t tb = sort_temp_bytes;
+      GS_HIP(hipcub::DeviceRadixSort::SortPairs(sort_temp, tb, rec.sort_key, keys_sorted, vals, vals_sorted, (int)npairs, 0, 35, st));
+      hipLaunchKernelGGL(gs_ordered_picp_bwd_settle_kernel, dim3(pair_blocks), dim3(256), 0, st, sz, keys_sorted, vals_sorted,
+                         npairs);
     }
     hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb, -1, 1);
     for (int b = 0; b < nb; ++b) {
-      const gs_picp_backward_seq& u = seqs_host[c0 + b];
+      const gs_picp_backward_seq& u = seq(c0 + b);
       const int64_t n3 = 3 * u.map.n_bound;
       if (pb.s[b].pbar)
         hipLaunchKernelGGL(gs_picp_bwd_cast_kernel, dim3((unsigned)gs_ceil_div(n3, 256)), dim3(256), 0, st, pb.s[b].pbar, n3,
@@ -345,16 +565,27 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
 
 extern "C" int gs_projective_icp_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
                                                     const gs_picp_params* params_host, void* stream) {
-  return pb_backward(__func__, seqs_host, B, H, W, params_host, 0.0f, false, stream);
+  return pb_backward(__func__, seqs_host, B, H, W, params_host, 0.0f, false, nullptr, stream);
 }
 
 extern "C" int gs_projective_icp_robust_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
                                                            const gs_picp_params* params_host, float huber_delta,
                                                            void* stream) {
-  return pb_backward(__func__, seqs_host, B, H, W, params_host, huber_delta, false, stream);
+  return pb_backward(__func__, seqs_host, B, H, W, params_host, huber_delta, false, nullptr, stream);
 }
 
 extern "C" int gs_projective_icp_scaled_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
                                                            const gs_picp_params* params_host, void* stream) {
-  return pb_backward(__func__, seqs_host, B, H, W, params_host, 0.0f, true, stream);
+  return pb_backward(__func__, seqs_host, B, H, W, params_host, 0.0f, true, nullptr, stream);
+}
+
+// the ordered mode of the three entries above in one: huber_delta as the robust entry's (0: the plain tape),
+// taped_scale != 0 as the scaled entry's (huber_delta is then not read)
+extern "C" int gs_projective_icp_ordered_backward_batch_f32(const gs_picp_ordered_backward_seq* seqs_host, int B, int H,
+                                                            int W, const gs_picp_params* params_host, float huber_delta,
+                                                            int taped_scale, void* sort_scratch,
+                                                            int64_t sort_scratch_bytes, void* stream) {
+  const PbOrderedCall oc{seqs_host, sort_scratch, sort_scratch_bytes};
+  return pb_backward(__func__, nullptr, B, H, W, params_host, taped_scale ? 0.0f : huber_delta, taped_scale != 0, &oc,
+                     stream);
 }

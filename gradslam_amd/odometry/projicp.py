@@ -57,6 +57,10 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             row, r the colour residual before `color_weight` is applied; `color_huber_delta` becomes a floor.  The
             threshold is in the residuals' own units, so the same constant serves colours in 0 ... 1 and in 0 ... 255;
             1.345 is the usual constant.  Needs `color_weight` > 0; combines with `huber_delta` and `huber_k`.
+        deterministic_backward: with `differentiable`, how the backward pass adds up the gradients of the map's points and
+            normals: True = in a fixed order (bitwise reproducible, slower: the ordered mode of
+            `ops.projective_icp_backward_batch`), False = float64 atomics, None (the default) = as
+            GRADSLAM_HIP_DETERMINISTIC_BACKWARD says when the backward runs.
 
     Unlike the point-cloud-pair providers it needs the map and the live frame themselves: call
     `localize(pointclouds, live_frame, prev_poses)`."""
@@ -66,10 +70,12 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                  min_confidence: Union[float, int] = 0.0, radius: int = 0, differentiable: bool = False,
                  color_weight: Union[float, int] = 0.0, huber_delta: Union[float, int] = 0.0,
                  color_huber_delta: Union[float, int] = 0.0, huber_k: Union[float, int] = 0.0,
-                 color_huber_k: Union[float, int] = 0.0):
+                 color_huber_k: Union[float, int] = 0.0, deterministic_backward: Optional[bool] = None):
         from .. import ops
         if not isinstance(differentiable, bool):
             raise TypeError("differentiable must be of type bool; but was of type {}.".format(type(differentiable)))
+        ops._picp_deterministic("ProjectiveICPOdometryProvider", "deterministic_backward", deterministic_backward)
+        self.deterministic_backward = deterministic_backward   # (carried next to _kwargs(), like color_weight)
         ops._picp_args(1 if stride is None else stride, numiters, damp, dist_thresh, angle_thresh)
         ops._picp_color_weight(color_weight)
         if color_weight > 0 and differentiable:
@@ -146,7 +152,8 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                        "update on the autograd tape)")
             T = ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
                                          view.index[:, 0], poses.detach(), maps, poses, differentiable=True, guard=guard,
-                                         huber_delta=self.huber_delta, huber_k=self.huber_k, **self._kwargs())
+                                         huber_delta=self.huber_delta, huber_k=self.huber_k,
+                                         deterministic=self.deterministic_backward, **self._kwargs())
             return T.unsqueeze(1)
         out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=poses.device)
         if self.color_weight > 0:

@@ -1040,6 +1040,26 @@ def _picp_flag(who, name, val):
     return val
 
 
+def _picp_deterministic(who, name, val):
+    """the type check of the ordered-backward switch: None (follow GRADSLAM_HIP_DETERMINISTIC_BACKWARD) or a bool"""
+    if val is not None and not isinstance(val, bool):
+        raise TypeError("{}: {} must be None or of type bool; but was of type {}.".format(who, name, type(val)))
+    return val
+
+
+def deterministic_backward_env():
+    """GRADSLAM_HIP_DETERMINISTIC_BACKWARD as the library reads it for the grid-search ICP backward (gs_icp_bwd.hip),
+    looked up on every call: on iff C atoi() of the value is nonzero (optional white space, an optional sign, then the
+    leading decimal digits; no digits: 0)."""
+    import os
+    import re
+    m = re.match(r"[ \t\n\v\f\r]*([+-]?[0-9]+)", os.environ.get("GRADSLAM_HIP_DETERMINISTIC_BACKWARD", ""))
+    return m is not None and int(m.group(1)) != 0
+
+
+PICP_NO_KEY = 0x7fffffff      # the key of a lattice slot that contributes nothing (the ordered backward's record)
+
+
 def _picp_scale_table(Bn, numiters, dev):
     """the (B, numiters) table of thresholds of a scaled solve and its per-sequence device pointers"""
     scale = torch.empty((Bn, int(numiters)), dtype=f32, device=dev)
@@ -1125,7 +1145,8 @@ def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_pos
 
 def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, init_poses, *, stride=1, numiters=10,
                          damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False, out=None,
-                         differentiable=False, guard=None, huber_delta=0.0, huber_k=0.0, return_scale=False):
+                         differentiable=False, guard=None, huber_delta=0.0, huber_k=0.0, return_scale=False,
+                         deterministic=None):
     """Frame-to-model tracking by projective data association for B sequences (gs_projective_icp_batch_f32: two launches
     per iteration for 8 sequences, nothing read back).  vertex / normal (B, H, W, 3): LOCAL maps of the live frames,
     depth (B, H, W), K (B, 4, 4); index (B, H, W) int64: the index image of render_map_batch at model_poses (B, 4, 4);
@@ -1148,10 +1169,14 @@ def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, ini
     read back, bit-exact); huber_delta is then a floor.  An iteration whose median is 0 has the plain solve's bits.  It
     works with differentiable=True (the thresholds are constants of the backward pass, like the clip flags).
     return_scale=True: the thresholds (B, numiters) float32 come last in the returned tuple (huber_k = 0: huber_delta in
-    every entry)."""
+    every entry).
+    deterministic (None | bool; it means something with differentiable=True only): True makes the backward's map
+    gradients bitwise reproducible (the ordered mode of projective_icp_backward_batch), False keeps the float64 atomics,
+    None follows GRADSLAM_HIP_DETERMINISTIC_BACKWARD as read when the backward runs."""
     if not isinstance(differentiable, bool):
         raise TypeError("projective_icp: differentiable must be of type bool; but was of type {}.".format(
             type(differentiable)))
+    _picp_deterministic("projective_icp", "deterministic", deterministic)
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
     huber_delta = _picp_huber("huber_delta", huber_delta)
     huber_k = _picp_huber_k(huber_k)
@@ -1161,7 +1186,8 @@ def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, ini
             raise ValueError("projective_icp: out= cannot be combined with differentiable=True (autograd owns the "
                              "outputs)")
         cfg = dict(stride=stride, numiters=numiters, damp=damp, dist_thresh=dist_thresh, angle_thresh=angle_thresh,
-                   guard=guard, counts=[(m[-2], m[-1]) for m in maps], huber_delta=huber_delta, huber_k=huber_k)
+                   guard=guard, counts=[(m[-2], m[-1]) for m in maps], huber_delta=huber_delta, huber_k=huber_k,
+                   deterministic=deterministic)
         flat = [t for m in maps for t in m[:2]]
         res = ProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses, cfg, *flat)
         scale = None
@@ -1229,7 +1255,8 @@ def projective_icp_tape_bytes(numiters):
 
 def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, maps, tapes, pose_bar, *, stride=1,
                                   numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, want_vertex=True,
-                                  want_init=True, want_maps=None, huber_delta=0.0, huber_k=0.0):
+                                  want_init=True, want_maps=None, huber_delta=0.0, huber_k=0.0, deterministic=None,
+                                  return_contributions=False):
     """Reverse mode of projective_icp_batch (gs_projective_icp_backward_batch_f32), arguments as the forward's; tapes:
     the (B, projective_icp_tape_bytes(numiters)) uint8 buffer the taped forward filled; pose_bar (B, 4, 4): the adjoint of
     the poses.  want_maps: per sequence (points, normals) flags, default all True.  Returns (vertex_bar (B, H, W, 3) or
@@ -1238,10 +1265,24 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
     additions.  An output that is not wanted costs nothing: without map outputs nothing of map size is allocated.
     huber_delta: the threshold the taped forward ran with (gs_projective_icp_robust_backward_batch_f32 when > 0).
     huber_k > 0: the taped forward ran with the median rule (gs_projective_icp_scaled_backward_batch_f32): every
-    iteration's threshold is read from the tape and is a constant of the pass; huber_delta is then not read."""
+    iteration's threshold is read from the tape and is a constant of the pass; huber_delta is then not read.
+    deterministic=True: the ordered mode (gs_projective_icp_ordered_backward_batch_f32, for all three tapes): the map
+    gradients are bitwise reproducible too -- every slot's contribution is recorded next to its row, the records are
+    stable-sorted by row and added per row in ascending slot order, iteration by iteration; vertex_bar and init_pose_bar
+    keep their bits.  False: the atomic mode.  None: GRADSLAM_HIP_DETERMINISTIC_BACKWARD decides, read at this call
+    (deterministic_backward_env).  return_contributions=True (ordered mode only): a fourth result, per sequence (keys
+    (numiters, nslots) int32, contrib (numiters, nslots, 6) float64): the record of every iteration as the kernel wrote it,
+    keys = the slot's row or PICP_NO_KEY, contrib = its contributions to points_bar[row] and normals_bar[row] (defined
+    where the key is a row)."""
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
     huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_backward")
     huber_k = _picp_huber_k(huber_k, "projective_icp_backward")
+    _picp_deterministic("projective_icp_backward", "deterministic", deterministic)
+    _picp_flag("projective_icp_backward", "return_contributions", return_contributions)
+    ordered = deterministic_backward_env() if deterministic is None else deterministic
+    if return_contributions and not ordered:
+        raise ValueError("projective_icp_backward: return_contributions=True needs the ordered mode (deterministic=True "
+                         "or GRADSLAM_HIP_DETERMINISTIC_BACKWARD=1)")
     with torch.no_grad():
         seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp_backward", vertex, normal, depth, K, index, model_poses,
                                                maps, pose_bar, stride)
@@ -1257,10 +1298,13 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
     init_bar = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if want_init else None
     ws = Workspace.get(dev)
     L = lib()
-    bseqs = (_C.PicpBackwardSeq * Bn)()
-    rows_out = []
+    oseqs = (_C.PicpOrderedBackwardSeq * Bn)() if ordered else None
+    bseqs = (_C.PicpBackwardSeq * Bn)() if not ordered else None
+    sizer = L.gs_projective_icp_ordered_backward_scratch_bytes if ordered else L.gs_projective_icp_backward_scratch_bytes
+    nslots = _picp_nslots(H, W, int(stride))
+    rows_out, record = [], []
     for b in range(Bn):
-        u, f = bseqs[b], seqs[b]
+        u, f = oseqs[b].base if ordered else bseqs[b], seqs[b]
         u.vertex, u.normal, u.depth, u.K16, u.index, u.model_pose16 = f.vertex, f.normal, f.depth, f.K16, f.index, \
             f.model_pose16
         u.map = f.map
@@ -1273,11 +1317,26 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
         u.vertex_bar = None if vertex_bar is None else vertex_bar.data_ptr() + b * H * W * 12
         u.points_bar, u.normals_bar = (None if g is None else g.data_ptr() for g in outs)
         u.init_pose_bar16 = None if init_bar is None else init_bar.data_ptr() + b * 64
-        nbytes = L.gs_projective_icp_backward_scratch_bytes(H, W, int(stride), n_bound if any(want_maps[b]) else 0)
+        nbytes = sizer(H, W, int(stride), n_bound if any(want_maps[b]) else 0)
         buf = ws.bytes("picp_bwd%d" % b, nbytes)
         u.scratch, u.scratch_bytes = buf.data_ptr(), int(buf.numel())
+        if return_contributions:   # (what the kernel does not write reads "none" / zero)
+            keys = torch.full((int(numiters), nslots), PICP_NO_KEY, dtype=torch.int32, device=dev)
+            contrib = torch.zeros((int(numiters), nslots, 6), dtype=torch.float64, device=dev)
+            oseqs[b].key_out, oseqs[b].contrib_out = keys.data_ptr(), contrib.data_ptr()
+            record.append((keys, contrib))
     prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
-    if huber_k > 0:
+    if ordered:
+        sort_bytes = L.gs_projective_icp_ordered_backward_sort_scratch_bytes(Bn, H, W, int(stride))
+        if sort_bytes <= 0:
+            raise ValueError("projective_icp_backward: the lattices of a launch group (%d x %d slots) are too many for "
+                             "one sort of the ordered mode" % (min(Bn, 8), nslots))
+        sort_buf = ws.bytes("picp_bwd_sort", sort_bytes) if any(any(w) for w in want_maps) else None
+        check(L.gs_projective_icp_ordered_backward_batch_f32(
+            oseqs, Bn, H, W, prm, 0.0 if huber_k > 0 else huber_delta, 1 if huber_k > 0 else 0,
+            None if sort_buf is None else sort_buf.data_ptr(), 0 if sort_buf is None else int(sort_buf.numel()),
+            stream(dev)), "gs_projective_icp_ordered_backward_batch_f32")
+    elif huber_k > 0:
         check(L.gs_projective_icp_scaled_backward_batch_f32(bseqs, Bn, H, W, prm, stream(dev)),
               "gs_projective_icp_scaled_backward_batch_f32")
     elif huber_delta > 0:
@@ -1286,6 +1345,8 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
     else:
         check(L.gs_projective_icp_backward_batch_f32(bseqs, Bn, H, W, prm, stream(dev)),
               "gs_projective_icp_backward_batch_f32")
+    if return_contributions:
+        return vertex_bar, rows_out, init_bar, record
     return vertex_bar, rows_out, init_bar
 
 
@@ -1294,7 +1355,8 @@ class ProjectiveICPFunction(torch.autograd.Function):
     and pose bits, plus the tape), backward = one call of gs_projective_icp_backward_batch_f32.  Inputs: vertex, normal,
     depth, K, index, model_poses, init_poses, cfg (the keyword arguments, `counts` = per sequence (n_bound, n_dev),
     `guard` and optionally `huber_delta`: both passes then run the robust entries, or `huber_k`: the scaled entries, and
-    the thresholds (B, numiters) are a third, non-differentiable output), then points and normals of every sequence's map.  Gradients reach vertex, init_poses and the map points /
+    the thresholds (B, numiters) are a third, non-differentiable output, or `deterministic`: handed to
+    projective_icp_backward_batch, None = the environment at backward time), then points and normals of every sequence's map.  Gradients reach vertex, init_poses and the map points /
     normals that require grad (needs_input_grad decides which outputs the kernel is asked for); the association is hard
     and a constant, as are depth, K, model_poses and the live normals.  The backward re-reads the map rows, so the map
     buffers must hold at backward time what they held at the forward; in-place steps write through raw pointers, which
@@ -1316,6 +1378,8 @@ class ProjectiveICPFunction(torch.autograd.Function):
                           kw["damp"], dist_th, dot_th, True, None, tapes, huber_delta, huber_k, huber_k > 0)
         T, trace = res[0], res[1]
         kw["huber_delta"], kw["huber_k"] = huber_delta, huber_k
+        # (None: the backward reads GRADSLAM_HIP_DETERMINISTIC_BACKWARD when it runs, not now)
+        kw["deterministic"] = _picp_deterministic("projective_icp", "deterministic", cfg.get("deterministic"))
         ctx.save_for_backward(vertex, normal, depth, K, index, model_poses, tapes, *flat,
                               *[c[1] for c in cfg["counts"]])
         ctx.kw, ctx.bounds, ctx.guard = kw, [c[0] for c in cfg["counts"]], cfg.get("guard")
@@ -1343,11 +1407,13 @@ class ProjectiveICPFunction(torch.autograd.Function):
 
 def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, *, n_dev=None,
                    stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False,
-                   differentiable=False, huber_delta=0.0, huber_k=0.0, return_scale=False):
+                   differentiable=False, huber_delta=0.0, huber_k=0.0, return_scale=False, deterministic=None):
     """projective_icp_batch for one sequence without the batch dimension: vertex / normal (H, W, 3), depth (H, W), K /
     model_pose / init_pose (4, 4), index (H, W) int64; n_dev: device int64[1] holding the actual row count of the map
     (map_points.shape[0] is then an upper bound).  Returns the pose (4, 4) (and the trace (numiters, 8)).
-    differentiable, huber_delta, huber_k, return_scale (the thresholds (numiters,)): see projective_icp_batch."""
+    differentiable, huber_delta, huber_k, return_scale (the thresholds (numiters,)), deterministic: see
+    projective_icp_batch."""
+    _picp_deterministic("projective_icp", "deterministic", deterministic)
     _picp_tensors("projective_icp", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                                      ("model_pose", model_pose), ("init_pose", init_pose)))
     r = projective_icp_batch(vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0), K.reshape(1, 4, 4),
@@ -1355,7 +1421,7 @@ def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_
                              init_pose.reshape(1, 4, 4), stride=stride, numiters=numiters, damp=damp,
                              dist_thresh=dist_thresh, angle_thresh=angle_thresh, return_trace=return_trace,
                              differentiable=differentiable, huber_delta=huber_delta, huber_k=huber_k,
-                             return_scale=return_scale)
+                             return_scale=return_scale, deterministic=deterministic)
     return tuple(x[0] for x in r) if isinstance(r, tuple) else r[0]
 
 

@@ -46,7 +46,12 @@ class ICPSLAM(nn.Module):
 
     `color_huber_k` (0 by default, `odom="projicp"` only; needs `color_weight`): the colour Huber threshold from the
     colour residuals' median in every iteration, `color_huber_delta` its floor
-    (`ProjectiveICPOdometryProvider(color_huber_k=...)`)."""
+    (`ProjectiveICPOdometryProvider(color_huber_k=...)`).
+
+    `odom_deterministic_backward` (None by default, `odom="projicp"` only; it matters with `odom_differentiable`): True
+    makes the map gradients of the projective ICP's backward bitwise reproducible, False keeps the float64 atomics, None
+    follows GRADSLAM_HIP_DETERMINISTIC_BACKWARD when the backward runs
+    (`ProjectiveICPOdometryProvider(deterministic_backward=...)`)."""
 
     def __init__(self, *, odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0,
@@ -54,9 +59,15 @@ class ICPSLAM(nn.Module):
                  device: Union[torch.device, str, None] = None, depth_filter: Optional[dict] = None,
                  odom_differentiable: bool = False, color_weight: Union[float, int] = 0.0,
                  huber_delta: Union[float, int] = 0.0, color_huber_delta: Union[float, int] = 0.0,
-                 huber_k: Union[float, int] = 0.0, color_huber_k: Union[float, int] = 0.0):
+                 huber_k: Union[float, int] = 0.0, color_huber_k: Union[float, int] = 0.0,
+                 odom_deterministic_backward: Optional[bool] = None):
         super().__init__()
         from .. import ops
+        ops._picp_deterministic(type(self).__name__, "odom_deterministic_backward", odom_deterministic_backward)
+        if odom_deterministic_backward is not None and odom != "projicp":
+            raise ValueError("odom_deterministic_backward is a switch of odom='projicp' (got odom={!r}): the backward of "
+                             "'icp' and 'gradicp' follows GRADSLAM_HIP_DETERMINISTIC_BACKWARD".format(odom))
+        self.odom_deterministic_backward = odom_deterministic_backward
         ops._picp_color_weight(color_weight)
         if color_weight > 0 and odom != "projicp":
             raise ValueError("color_weight is the photometric term of odom='projicp' (got odom={!r})".format(odom))
@@ -99,7 +110,8 @@ class ICPSLAM(nn.Module):
                                                      stride=dsratio, differentiable=odom_differentiable,
                                                      color_weight=color_weight, huber_delta=huber_delta,
                                                      color_huber_delta=color_huber_delta, huber_k=huber_k,
-                                                     color_huber_k=color_huber_k)
+                                                     color_huber_k=color_huber_k,
+                                                     deterministic_backward=odom_deterministic_backward)
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio

@@ -825,7 +825,8 @@ GS_API int gs_projective_icp_rows_f32(const gs_picp_seq* seq_host, int H, int W,
  * forward's device functions at the taped float32 pose, so the inputs (the map rows included) must hold what they held
  * at the forward; a stale index entry is never dereferenced.  float64 inside, rounded once.  vertex_bar and
  * init_pose_bar16 are bitwise reproducible (the forward's fixed reduction shape, no atomics); points_bar / normals_bar
- * are float64 atomic adds, reproducible up to the order of the float64 additions.  Any output may be NULL: its work and
+ * are float64 atomic adds, reproducible up to the order of the float64 additions (bitwise reproducible through
+ * gs_projective_icp_ordered_backward_batch_f32, below).  Any output may be NULL: its work and
  * its buffer are skipped (with both map outputs NULL nothing of map size is touched).  scratch:
  * gs_projective_icp_backward_scratch_bytes(H, W, stride, n_map) bytes per sequence, n_map = map.n_bound when a map output
  * is asked for, else 0; scratch_bytes is what the caller provides and is checked.  8 sequences per launch, 2 numiters + 1
@@ -853,6 +854,43 @@ GS_API int gs_projective_icp_tape_batch_f32(const gs_picp_seq* seqs_host, void* 
 GS_API int64_t gs_projective_icp_backward_scratch_bytes(int H, int W, int stride, int64_t n_map);
 GS_API int gs_projective_icp_backward_batch_f32(const gs_picp_backward_seq* seqs_host, int B, int H, int W,
                                                 const gs_picp_params* params_host, void* stream);
+
+/* ------------------------------------------------------------------ projective ICP backward: the ordered mode ------
+ * gs_projective_icp_ordered_backward_batch_f32 is the backward pass above -- of the plain tape (huber_delta = 0,
+ * taped_scale = 0), of the robust tape (huber_delta > 0: gs_projective_icp_robust_backward_batch_f32, further down) and
+ * of the scaled tape (taped_scale != 0: gs_projective_icp_scaled_backward_batch_f32; huber_delta is then not read) --
+ * with BITWISE REPRODUCIBLE points_bar / normals_bar.  The point stage of an iteration does not add a slot's two
+ * 3-vectors atomically; it records them, per slot k of the lattice:
+ *   contrib[k][0:3] the contribution to points_bar[row], contrib[k][3:6] the one to normals_bar[row] (float64; zeros for
+ *   a map output that is not asked for), key[k] = the slot's row, or 0x7fffffff for a slot that contributes nothing.
+ * A settle step follows: one stable radix sort of the pairs (sequence << 32 | key, slot) of all sequences of a launch
+ * group (up to 8), then one thread per run of equal keys.  The order contract: acc[row] starts at +0.0; the iterations
+ * are processed numiters - 1 down to 0; in an iteration a row's run sum starts at 0.0 and adds the contributions of its
+ * slots in ascending slot id, then acc[row] = acc[row] + run_sum; a row that nobody touches ends as +0.0; an iteration
+ * without inliers records nothing (every key reads "none"); acc is rounded to float32 once at the end.  vertex_bar and
+ * init_pose_bar16 have the bits of the other entries.  A launch group in which no map output is asked for runs the
+ * launches of the other entries: nothing is recorded or sorted.
+ * key_out (numiters, nslots) int32 / contrib_out (numiters, nslots, 6) float64, nslots = ceil(H / stride) ceil(W /
+ * stride), device, either may be NULL: the record as it stood after the point stage of iteration `it`, in slice `it`
+ * (a test's view of the pass).  They are written only for a sequence in a group that records (contrib_out only for a
+ * sequence with a map output; where a key is "none" the contribution is not defined): fill them beforehand.
+ * scratch per sequence: gs_projective_icp_ordered_backward_scratch_bytes(H, W, stride, n_map) bytes (n_map as above: the
+ * other entries' scratch plus the record, 48 + 4 bytes per slot); sort_scratch: one buffer for the call,
+ * gs_projective_icp_ordered_backward_sort_scratch_bytes(B, H, W, stride) bytes, 8-byte aligned (keys and values of
+ * min(B, 8) nslots pairs, in and out, and the sort's temporary storage; not read when no map output is asked for).
+ * Neither grows with numiters.  Both return 0 on bad arguments (the second also when min(B, 8) nslots >= 2^31).
+ * Refused, before the first HIP call like every other bad argument: map.n_bound >= 0x7fffffff, min(B, 8) nslots >= 2^31. */
+typedef struct gs_picp_ordered_backward_seq {
+  gs_picp_backward_seq base;
+  int32_t* key_out;           /* out (numiters, nslots), or NULL */
+  double* contrib_out;        /* out (numiters, nslots, 6), or NULL */
+} gs_picp_ordered_backward_seq;
+GS_API int64_t gs_projective_icp_ordered_backward_scratch_bytes(int H, int W, int stride, int64_t n_map);
+GS_API int64_t gs_projective_icp_ordered_backward_sort_scratch_bytes(int B, int H, int W, int stride);
+GS_API int gs_projective_icp_ordered_backward_batch_f32(const gs_picp_ordered_backward_seq* seqs_host, int B, int H,
+                                                        int W, const gs_picp_params* params_host, float huber_delta,
+                                                        int taped_scale, void* sort_scratch,
+                                                        int64_t sort_scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------ projective ICP with a colour term ------
  * The projective ICP above plus a photometric row per slot (Steinbruecker / Kerl; Kintinuous, ElasticFusion, Open3D's

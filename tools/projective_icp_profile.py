@@ -1,7 +1,7 @@
 """Projective-association ICP against the model view: what one localisation costs next to the grid-search ICP, what the
 frame loop gains or loses with it, and what a launch of it costs (needs the MI355X; fails without one).
 
-    python tools/projective_icp_profile.py [--out FILE] [--only localize|slam|launches] [--steps K] [--color-weight W]
+    python tools/projective_icp_profile.py [--out FILE] [--only localize|slam|launches|backward] [--steps K] [--color-weight W]
                                            [--huber-delta D] [--color-huber-delta C] [--huber-k K] [--color-huber-k K]
                                            [--parent-lib SO]
 
@@ -48,7 +48,15 @@ with the joint solve under a constant colour threshold (the one given, else 0.05
 solve under the geometric rule alone and under both rules: us_per_iteration_color_const / _cscaled / _gscaled /
 _bothscaled.  Every scaled variant has the same four launches per iteration.
 
---parent-lib SO (needs --huber-delta): the libgradslam_hip.so of another build of this project, e.g. of the parent commit
+4. The backward (--only backward; not part of a run without --only).  One call of ops.projective_icp_backward_batch on
+   the tape of the 10-iteration solve of part 3, all four outputs asked for (vertex_bar, points_bar, normals_bar,
+   init_pose_bar), strides 4 and 1, B = 1 and B = 8: the atomic mode (deterministic=False) and the ordered mode
+   (deterministic=True) alternating in the same process.  ordered_extra_ms is what the record, the sort and the settle
+   step add; at B = 8 it is set next to 8 x the B = 1 figure: one sort per launch group must cost less than the sorts of
+   8 separate sequences.  With --parent-lib the atomic mode of that build (its gs_projective_icp_backward_batch_f32
+   behind this tree's Python layer) alternates with this tree's: the default path must not have got slower.
+
+--parent-lib SO (needs --huber-delta, or --only backward): the libgradslam_hip.so of another build of this project, e.g. of the parent commit
 (same ABI version), loaded next to this tree's.  Part 3 then also times ITS gs_projective_icp_robust_batch_f32 on the
 same descriptors, alternating with this tree's solves in the same process: what a change to the robust kernels cost."""
 import argparse
@@ -176,8 +184,9 @@ def load_parent(path):
     import ctypes
     from gradslam_amd import _C
     parent = ctypes.CDLL(os.path.abspath(path))
-    fn = parent.gs_projective_icp_robust_batch_f32
-    fn.argtypes, fn.restype = _C._PROTOS["gs_projective_icp_robust_batch_f32"], ctypes.c_int
+    for name in ("gs_projective_icp_robust_batch_f32", "gs_projective_icp_backward_batch_f32"):
+        fn = getattr(parent, name)
+        fn.argtypes, fn.restype = _C._PROTOS[name], ctypes.c_int
     parent.gs_last_error.restype = ctypes.c_char_p
     if parent.gs_abi_version() != _C.ABI_VERSION:
         sys.exit("--parent-lib: ABI version %d, this tree has %d" % (parent.gs_abi_version(), _C.ABI_VERSION))
@@ -277,6 +286,86 @@ def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta
     return out
 
 
+class _BackwardOf:
+    """this tree's library with the atomic backward entry of another build in its place"""
+
+    def __init__(self, own, parent):
+        self._own, self._parent = own, parent
+
+    def __getattr__(self, name):
+        return getattr(self._parent if name == "gs_projective_icp_backward_batch_f32" else self._own, name)
+
+
+def backward_times(torch, gs, ops, reps=5, rounds=7, parent=None):
+    out = []
+    for B in (1, 8):
+        pc, live, prev, _ = scene(torch, gs, B)
+        fr = live.to_channels_last()
+        K = fr.intrinsics[:, 0].contiguous()
+        maps = [(pc._buf["points"][b], None, None, None) + tuple(pc._count_of(b)) for b in range(B)]
+        maps_n = [(pc._buf["points"][b], pc._buf["normals"][b]) + tuple(pc._count_of(b)) for b in range(B)]
+        index = ops.render_map_batch(maps, prev, K, H, W).index[:, 0]
+        args = (fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K, index, prev[:, 0], maps_n)
+        pose_bar = torch.randn((B, 4, 4), generator=torch.Generator().manual_seed(5)).cuda()
+        rows = pc._tighten_counts()
+        for stride in (4, 1):
+            numiters = 10
+            tapes = torch.empty((B, ops.projective_icp_tape_bytes(numiters)), dtype=torch.uint8, device="cuda")
+            dist_th, dot_th = ops._picp_args(stride, numiters, 1e-8, 0.1, 30.0)
+            _, trace = ops._picp_solve(*args, prev[:, 0], stride, numiters, 1e-8, dist_th, dot_th, True, None, tapes)
+
+            def call(deterministic):
+                return ops.projective_icp_backward_batch(*args, tapes, pose_bar, stride=stride, numiters=numiters,
+                                                         deterministic=deterministic)
+
+            def via(build, deterministic):
+                """a call with the atomic entry of `build` (None: this tree's); with --parent-lib every variant goes through
+                this detour, so that the host side (which is most of a call at stride 4) is the same code for all"""
+                def run():
+                    own = ops.lib
+                    ops.lib = lambda: _BackwardOf(own(), build if build is not None else own())
+                    try:
+                        return call(deterministic)
+                    finally:
+                        ops.lib = own
+                return run
+
+            fns = {"atomic": lambda: call(False), "ordered": lambda: call(True)}
+            if parent is not None:
+                fns = {"atomic": via(None, False), "ordered": via(None, True), "atomic_parent": via(parent, False)}
+            res = {k: fn() for k, fn in fns.items()}
+            torch.cuda.synchronize()
+            same = {k: all(torch.equal(a, b) for a, b in ((res[k][0], res["atomic"][0]), (res[k][2], res["atomic"][2])))
+                    for k in fns}                                  # vertex_bar and init_pose_bar: the same bits
+            again = call(True)
+            ordered_repeats = all(torch.equal(a, b) for x, y in zip(res["ordered"][1], again[1]) for a, b in zip(x, y))
+            del res, again
+            for fn in fns.values():
+                fn(), fn()
+            t = time_round_robin(torch, fns, reps, rounds)
+            nslots = -(-H // stride) * -(-W // stride)
+            rec = {"B": B, "stride": stride, "slots": nslots, "numiters": numiters, "map_rows": rows,
+                   "inliers_last_iteration": [int(x) for x in trace[:, -1, 0].cpu()], "times": t,
+                   "ordered_over_atomic": t["ordered"]["median_ms"] / t["atomic"]["median_ms"],
+                   "ordered_extra_ms": t["ordered"]["median_ms"] - t["atomic"]["median_ms"],
+                   "vertex_and_init_bits_equal_atomic": same, "ordered_map_gradients_repeat_bit_for_bit": ordered_repeats}
+            if parent is not None:
+                a, b = t["atomic"], t["atomic_parent"]
+                rec["atomic_over_parent"] = a["median_ms"] / b["median_ms"]
+                rec["medians_within_each_others_spread"] = \
+                    b["min_ms"] <= a["median_ms"] <= b["max_ms"] and a["min_ms"] <= b["median_ms"] <= a["max_ms"]
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+    for stride in (4, 1):      # one sort per launch group against the sorts of 8 separate sequences
+        one = next(r for r in out if r["B"] == 1 and r["stride"] == stride)
+        eight = next(r for r in out if r["B"] == 8 and r["stride"] == stride)
+        eight["ordered_extra_ms_of_8_single_calls"] = 8 * one["ordered_extra_ms"]
+        eight["one_sort_per_group_holds"] = eight["ordered_extra_ms"] <= 8 * one["ordered_extra_ms"]
+        print(json.dumps({"stride": stride, "ordered_extra_ms_B8": eight["ordered_extra_ms"],
+                          "ordered_extra_ms_8_x_B1": 8 * one["ordered_extra_ms"]}), flush=True)
+    return out
+
+
 def slam_runs(torch, gs, steps, warmup=10, huber_delta=0.0, huber_k=0.0):
     import bench
     B = 8
@@ -313,7 +402,7 @@ def slam_runs(torch, gs, steps, warmup=10, huber_delta=0.0, huber_k=0.0):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("localize", "slam", "launches"), default=None)
+    ap.add_argument("--only", choices=("localize", "slam", "launches", "backward"), default=None)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--color-weight", type=float, default=0.0,
                     help="> 0: also time the joint geometric + photometric solve (parts 1 and 3)")
@@ -340,8 +429,8 @@ def main():
         ap.error("--color-huber-delta needs --color-weight")
     if args.color_huber_k > 0 and not args.color_weight > 0:
         ap.error("--color-huber-k needs --color-weight")
-    if args.parent_lib and not args.huber_delta > 0:
-        ap.error("--parent-lib needs --huber-delta")
+    if args.parent_lib and not (args.huber_delta > 0 or args.only == "backward"):
+        ap.error("--parent-lib needs --huber-delta (or --only backward)")
     import torch
     if not torch.cuda.is_available():
         sys.exit("tools/projective_icp_profile.py measures on the GPU: no HIP device found (nothing is measured on the CPU)")
@@ -358,6 +447,8 @@ def main():
         out["launches"] = launch_times(torch, gs, ops, color_weight=args.color_weight, huber_delta=args.huber_delta,
                                        color_huber_delta=args.color_huber_delta, huber_k=args.huber_k,
                                        color_huber_k=args.color_huber_k, parent=load_parent(args.parent_lib) if args.parent_lib else None)
+    if args.only == "backward":
+        out["backward"] = backward_times(torch, gs, ops, parent=load_parent(args.parent_lib) if args.parent_lib else None)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
