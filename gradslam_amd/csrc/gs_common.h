@@ -40,7 +40,7 @@ struct GsPixelTables {
 int gs_frame_maps_batch_clear(const float* depth, int64_t depth_stride_seq, int64_t depth_stride_frame, const float* K16,
                               int n_frames, int frames_per_K, int H, int W, float two_sigma_sq, float* vertex,
                               float* normal, float* alpha, const GsClearJob* job, void* stream,
-                              const GsPixelTables* tables = nullptr);
+                              const GsPixelTables* tables = nullptr);   // (vertex, normal, alpha: each may be NULL)
 
 // the batched map update behind gs_update_map_fusion_batch_f32 (gs_fuse.hip); tables_ready: see GsPixelTables.
 // two_sigma_sq: read only for sequences without global maps (gvertex == NULL, which needs tables_ready) -- the value the
@@ -48,7 +48,8 @@ int gs_frame_maps_batch_clear(const float* depth, int64_t depth_stride_seq, int6
 int gs_update_map_fusion_batch_impl(const gs_update_seq* seqs_host, int B, int H, int W, float dist_th, float dot_th,
                                     int renorm_all, void* stream, bool tables_ready, float two_sigma_sq);
 int32_t* gs_update_map_call_flag(void* scratch_of_first_sequence);
-void gs_update_map_tables(void* scratch, int32_t** any_flag, uint64_t** key_pix);
+// (best_scratch: the tie-marker table of a call whose best_pix is NULL, H*W entries)
+void gs_update_map_tables(void* scratch, int64_t P, int32_t** any_flag, uint64_t** key_pix, int32_t** best_scratch);
 
 // ---------------------------------------------------------------- error plumbing -------
 void gs_set_error(const char* fmt, ...);
@@ -169,6 +170,27 @@ GS_DEV GsKinv gs_kinv(const float* __restrict__ K) {
   r.k02 = (-1.0f * cx) / (fx + eps);
   r.k12 = (-1.0f * cy) / (fy + eps);
   return r;
+}
+// local vertex of pixel (h, w) from its depth: einsum(Kinv, (u, v, 1)) as FMA chain, then
+// * depth, then * valid (structures/rgbdimages.py:662-679).  The ONE statement of it: the frame-map kernels
+// (gs_frame.hip) write it, and whoever runs without a materialised vertex map (the one-call step: the lattice source of
+// gs_icp_loop.hip, FrameDepthMaps of gs_fuse.hip) computes it again from depth[p] -- the same operations, the same bits.
+// z = (1.0f * d) * (d > 0 ? 1 : 0), so `z > 0` holds exactly when `d > 0` does (d <= 0 gives +-0, NaN gives NaN).
+GS_DEV void fm_vertex(float d, int h, int w, const GsKinv& k, float& x, float& y, float& z) {
+  float u = (float)w, v = (float)h;
+  float ax = k.k00 * u;
+  ax = gs_fma(0.0f, v, ax);
+  ax = gs_fma(k.k02, 1.0f, ax);
+  float ay = 0.0f * u;
+  ay = gs_fma(k.k11, v, ay);
+  ay = gs_fma(k.k12, 1.0f, ay);
+  float az = 0.0f * u;
+  az = gs_fma(0.0f, v, az);
+  az = gs_fma(1.0f, 1.0f, az);
+  float validf = d > 0.0f ? 1.0f : 0.0f;
+  x = (ax * d) * validf;
+  y = (ay * d) * validf;
+  z = (az * d) * validf;
 }
 
 // rigid transform of a point, sgemm-style FMA chain + t (geometryutils.py:781-794,

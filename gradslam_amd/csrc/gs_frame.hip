@@ -114,24 +114,7 @@ constexpr int FM_TH = 8;   // tile height (each of the 4 waves handles 2 rows)
 constexpr int FM_LW = FM_TW + 2;
 constexpr int FM_LH = FM_TH + 2;
 
-// local vertex of pixel (h, w) from its depth: einsum(Kinv, (u, v, 1)) as FMA chain, then
-// * depth, then * valid (structures/rgbdimages.py:662-679).
-GS_DEV void fm_vertex(float d, int h, int w, const GsKinv& k, float& x, float& y, float& z) {
-  float u = (float)w, v = (float)h;
-  float ax = k.k00 * u;
-  ax = gs_fma(0.0f, v, ax);
-  ax = gs_fma(k.k02, 1.0f, ax);
-  float ay = 0.0f * u;
-  ay = gs_fma(k.k11, v, ay);
-  ay = gs_fma(k.k12, 1.0f, ay);
-  float az = 0.0f * u;
-  az = gs_fma(0.0f, v, az);
-  az = gs_fma(1.0f, 1.0f, az);
-  float validf = d > 0.0f ? 1.0f : 0.0f;
-  x = (ax * d) * validf;
-  y = (ay * d) * validf;
-  z = (az * d) * validf;
-}
+// (the local vertex of a pixel from its depth: fm_vertex, gs_common.h)
 
 // a 12-byte row assembled in registers and stored by ONE instruction: three dword stores per row were the pattern that
 // cost the merge kernel 40 % before it was fixed
@@ -230,7 +213,8 @@ __global__ void __launch_bounds__(256) gs_frame_maps_batch_kernel(
     tabs.any_flag[f][1] = 0;   // ("some pixel has two rows with the same key", gs_fuse.hip)
     if (f == 0 && tabs.call_flag) *tabs.call_flag = 0;
   }
-  frame_maps_body(depth + b * stride_seq + l * stride_frame, K16 + 16 * b, H, W, two_sigma_sq, vertex + 3 * f * P,
+  frame_maps_body(depth + b * stride_seq + l * stride_frame, K16 + 16 * b, H, W, two_sigma_sq,
+                  vertex ? vertex + 3 * f * P : nullptr,
                   normal ? normal + 3 * f * P : nullptr, alpha ? alpha + f * P : nullptr, nullptr,
                   tb ? tabs.key_pix[f] : nullptr, tb ? tabs.best_pix[f] : nullptr);
 }
@@ -253,7 +237,7 @@ int gs_frame_maps_batch_clear(const float* depth, int64_t depth_stride_seq, int6
                               int n_frames, int frames_per_K, int H, int W, float two_sigma_sq, float* vertex,
                               float* normal, float* alpha, const GsClearJob* job, void* stream,
                               const GsPixelTables* tables) {
-  GS_REQUIRE(depth && K16 && vertex, "depth, K16 and vertex must not be NULL");
+  GS_REQUIRE(depth && K16, "depth and K16 must not be NULL");
   GsPixelTables tabs;
   tabs.n = 0; tabs.call_flag = nullptr;
   if (tables && tables->n > 0) {
@@ -275,7 +259,7 @@ int gs_frame_maps_batch_clear(const float* depth, int64_t depth_stride_seq, int6
   } else {
     job = &none;
   }
-  const double bytes = (double)n_frames * H * W * (4.0 + 12.0 + (normal ? 12 : 0) + (alpha ? 4 : 0)) +
+  const double bytes = (double)n_frames * H * W * (4.0 + (vertex ? 12 : 0) + (normal ? 12 : 0) + (alpha ? 4 : 0)) +
                        (double)tabs.n * H * W * 12.0;
   GsProf prof(GS_PROF_FRAME, bytes, gs_stream(stream));
   hipLaunchKernelGGL(gs_frame_maps_batch_kernel, grid, dim3(256), 0, gs_stream(stream), depth, depth_stride_seq,
@@ -287,6 +271,7 @@ int gs_frame_maps_batch_clear(const float* depth, int64_t depth_stride_seq, int6
 extern "C" int gs_frame_maps_batch_f32(const float* depth, int64_t depth_stride_seq, int64_t depth_stride_frame,
                                        const float* K16, int n_frames, int frames_per_K, int H, int W,
                                        float two_sigma_sq, float* vertex, float* normal, float* alpha, void* stream) {
+  GS_REQUIRE(vertex, "vertex must not be NULL");
   return gs_frame_maps_batch_clear(depth, depth_stride_seq, depth_stride_frame, K16, n_frames, frames_per_K, H, W,
                                    two_sigma_sq, vertex, normal, alpha, nullptr, stream);
 }

@@ -3,6 +3,8 @@
 // structures/pointclouds.py:1117-1237).  HBM-bound: 2 x 40 B per map row (parity mode rewrites
 // every row exactly like the reference, slam/fusionutils.py:678-699) + 40 B read + 40 B write
 // per appended pixel.
+#include <type_traits>
+
 #include "gs_assoc_dev.h"
 #include "gs_compact.h"
 
@@ -33,7 +35,8 @@ __global__ void __launch_bounds__(256) gs_fuse_scatter_kernel(const int32_t* __r
 // access (interleaved loads and stores compile to 21 + 10 single-dword accesses, and the scattered frame gathers of
 // the matched rows make the kernel address-rate bound).
 // `frame(p, fp, fn)` yields the global vertex and normal of pixel p: from the materialised global maps (FrameGlobalMaps)
-// or computed on the spot from the local maps and the pose (FrameLocalMaps: the same operations, so the same bits).
+// or computed on the spot from the local maps and the pose (FrameLocalMaps: the same operations, so the same bits), the
+// local vertex itself from the pixel's depth where no vertex map was written (FrameDepthMaps).
 struct FrameGlobalMaps {
   static constexpr bool kAlphaFromVertex = false;   // the alpha map is the caller's: gathered
   const float* __restrict__ gvertex;
@@ -120,6 +123,52 @@ GS_DEV FrameLocalMaps frame_local_maps(const float* vertex, const float* normal,
   for (int i = 0; i < 12; ++i) f.T[i] = pose16[i];
   return f;
 }
+// FrameLocalMaps without a vertex map in memory (the one-call step with gs_step_seq::vertex == NULL): the local vertex of
+// pixel p is computed from depth[p] by fm_vertex, the function the frame-map kernel would have written it with -- the same
+// bits -- and from there on every member does what FrameLocalMaps does.  The gather of depth[p] REPLACES the gather of
+// vertex[p] (4 B instead of 12 B, the same number of scattered accesses); the inverse intrinsics are formed only by a
+// thread that needs a vertex.
+struct FrameDepthMaps : FrameLocalMaps {
+  const float* __restrict__ depth;
+  const float* __restrict__ K16;
+  int W;
+  // the local vertex of pixel p whose depth d the caller holds
+  __device__ void local_vertex(const int64_t p, const float d, float* v) const {
+    const unsigned h = (unsigned)p / (unsigned)W, w = (unsigned)p - h * (unsigned)W;
+    fm_vertex(d, (int)h, (int)w, gs_kinv(K16), v[0], v[1], v[2]);
+  }
+  __device__ void global_of(const float* v, float* fp) const {   // (FrameLocalMaps::vertex_of on v)
+    const float validf = v[2] > 0.0f ? 1.0f : 0.0f;
+    float g0, g1, g2;
+    gs_rigid_fma(T, v[0], v[1], v[2], g0, g1, g2);
+    fp[0] = g0 * validf; fp[1] = g1 * validf; fp[2] = g2 * validf;
+  }
+  __device__ void vertex_of(const int64_t p, float* fp) const {
+    float v[3];
+    local_vertex(p, depth[p], v);
+    global_of(v, fp);
+  }
+  __device__ float vertex_alpha_of(const int64_t p, float* fp) const { return vertex_alpha_of(p, depth[p], fp); }
+  __device__ float vertex_alpha_of(const int64_t p, const float d, float* fp) const {
+    float v[3];
+    local_vertex(p, d, v);
+    global_of(v, fp);
+    return gs_alpha_of(v[0], v[1], v[2], two_sigma_sq, GS_FRAME_ALPHA_EPS);
+  }
+  __device__ void operator()(const int64_t p, float* fp, float* fn) const {
+    vertex_of(p, fp);
+    normal_of(p, fn);
+  }
+};
+GS_DEV FrameDepthMaps frame_depth_maps(const float* depth, const float* normal, const float* pose16, const float* K16,
+                                       const int W, const float two_sigma_sq) {
+  FrameDepthMaps f;
+  f.vertex = nullptr; f.normal = normal; f.two_sigma_sq = two_sigma_sq;
+  f.depth = depth; f.K16 = K16; f.W = W;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) f.T[i] = pose16[i];
+  return f;
+}
 
 // `cc` = ccounts[n], loaded by the caller.  HAVE_VERTEX: the caller already holds the global vertex of pixel p in `fv` (the
 // one-call update's winner test gathers it to rebuild the row's key) and it is not gathered a second time.  HAVE_ALPHA: nor
@@ -202,11 +251,13 @@ struct EmitAppendT {
   Frame frame;   // global vertex / normal of a pixel (FrameGlobalMaps | FrameLocalMaps)
   const float* rgb;
   const float* alpha;
-  __device__ void operator()(int64_t p, int64_t pos) const {
+  // d: the pixel's depth, read only by a frame that computes the vertex from it (FrameDepthMaps: the caller holds it)
+  __device__ void operator()(int64_t p, int64_t pos, const float d = 0.0f) const {
     const int64_t r = gs_count(n_map) + pos;
     float v[3], nn[3] = {0.0f, 0.0f, 0.0f}, c[3] = {0.0f, 0.0f, 0.0f};  // loads, then stores: 12-byte accesses
     float a = 0.0f;
-    if constexpr (Frame::kAlphaFromVertex) a = frame.vertex_alpha_of(p, v);
+    if constexpr (std::is_same<Frame, FrameDepthMaps>::value) a = frame.vertex_alpha_of(p, d, v);
+    else if constexpr (Frame::kAlphaFromVertex) a = frame.vertex_alpha_of(p, v);
     else frame.vertex_of(p, v);
     if (normals) frame.normal_of(p, nn);
     if (colors) {
@@ -449,7 +500,8 @@ extern "C" int gs_fuse_append_backward_f32(const float* points, const float* nor
 //      marked pixels by an atomicMin of the row index (skipped at once when no pixel of the frame is marked)
 //   U4 per pixel : "any match" flag, count of new pixels per tile (a pixel is matched iff its key was written)
 //   U5 per surfel: winner test (key attained, and no lower-indexed row holds the pixel) + confidence-weighted merge
-//                  (parity mode rewrites every row); the winner writes best_pix                } one launch
+//                  (parity mode rewrites every row); the winner writes best_pix (where the    } one launch
+//                  caller asked for the table: else it lives in the scratch, as the tie marker)
 //      The key of a row is never stored: whoever asks whether row n attains the key of its pixel (U5, and the tie
 //      settling of U4) computes it again -- gs_assoc_key_hi / gs_assoc_key_lo_v on points[n], ccounts[n] and the pixel's
 //      global vertex, the very functions and inputs of U2, hence the very bits.  Those inputs are still what U2 saw: the
@@ -467,20 +519,20 @@ struct MuSeq {
   const float* vertex; const float* normal; const float* depth; const float* rgb; const float* alpha;
   const float* pose16; const float* K16;
   float* gvertex; float* gnormal;
-  int32_t* best_pix;
+  int32_t* best_pix;   // the caller's table, or the one in the scratch (MuBatch::best_is_output == 0): the tie marker only
   int64_t* new_count_out;
   // scratch
   int32_t* any_flag;
   uint64_t* key_pix;
   int32_t* tile_counts;
   int32_t* pix;
-  int32_t* pix_of;
 };
 struct MuBatch {
   int B, H, W, renorm_all;
   int64_t P, ntiles;
   float u_hi, v_hi, dist_th, dot_th;
   float two_sigma_sq;   // of the frame-map launch that wrote MuSeq::alpha (the one-call step, gvertex == NULL; else unused)
+  int best_is_output;   // 0: nobody asked for the correspondence table -- the winners do not write it
   // "some sequence of the CALL has a match": batches beyond GS_MAX_BATCH sequences run in chunks, and the reference's
   // test (fusionutils.py:659) looks at the table of the whole batch.  One word shared by all chunks of a call (in the
   // first sequence's scratch), zeroed by the first chunk's pixel pass, set by every chunk's winner pass, read by the
@@ -513,6 +565,40 @@ __global__ void __launch_bounds__(256) gs_mu_pixel_init_kernel(const MuBatch mb)
   q.best_pix[p] = -1;
 }
 
+// The frame of a sequence as the update reads it: the materialised global maps, the local maps + the pose, or the depth
+// image + the normal map + the pose (the one-call step that wrote no vertex map).  One place for the choice; every pass
+// below is a template over it.
+#define MU_WITH_FRAME(mb, q, CALL)                                                                             \
+  do {                                                                                                         \
+    if ((q).gvertex) { const FrameGlobalMaps frame{(q).gvertex, (q).gnormal}; CALL; }                          \
+    else if ((q).vertex) { const FrameLocalMaps frame = frame_local_maps((q).vertex, (q).normal, (q).pose16, (mb).two_sigma_sq); CALL; } \
+    else { const FrameDepthMaps frame = frame_depth_maps((q).depth, (q).normal, (q).pose16, (q).K16, (mb).W, (mb).two_sigma_sq); CALL; } \
+  } while (0)
+
+// the key pass for row n that projects onto pixel p >= 0: the pixel it competes for, or -1 (not similar to the pixel)
+template <class Frame>
+GS_DEV int32_t mu_key_row(const MuBatch& mb, const MuSeq& q, const int64_t n, const int32_t p, const Frame& frame) {
+  // The normal first: on the benchmark scene half the rows in the frame fail its test (they project onto a pixel
+  // without depth, whose vertex and normal are zero, or belong to the rim of a hole and never match), and a row that
+  // fails gathers no vertex.  The two tests are pure and joined by AND: the same pk, keys and tie marks.
+  float fp[3], fn[3];
+  frame.normal_of((int64_t)p, fn);
+  if (!gs_is_similar_dot_v(q.normals, fn, n, mb.dot_th)) return -1;
+  frame.vertex_of((int64_t)p, fp);
+  if (!gs_is_similar_dist_v(q.points, fp, n, mb.dist_th)) return -1;
+  const uint64_t k = gs_assoc_key_v(q.points, q.ccounts, fp, n);
+  const unsigned long long old = atomicMin(reinterpret_cast<unsigned long long*>(&q.key_pix[p]), (unsigned long long)k);
+  // Two rows with the same key at one pixel: whichever arrives second gets its own key back.  (If the key is beaten
+  // later the mark is spurious and harmless; if it stays the minimum, every tie of the winning key has been seen:
+  // the first of the tied rows to arrive set it, every later one reads it back.)  The pixel is marked -- any value
+  // that is neither "no winner" (-1) nor a row index below it -- and settled by mu_settle_ties (in the per-pixel pass).
+  if (old == (unsigned long long)k) {
+    q.best_pix[p] = MU_TIE_MARK;
+    q.any_flag[1] = 1;   // benign race: every writer stores the same value
+  }
+  return p;
+}
+
 __global__ void __launch_bounds__(256) gs_mu_project_key_kernel(const MuBatch mb) {
   const MuSeq& q = mb.s[blockIdx.x % mb.B];
   const int64_t n = (int64_t)(blockIdx.x / mb.B) * 256 + threadIdx.x;
@@ -521,37 +607,11 @@ __global__ void __launch_bounds__(256) gs_mu_project_key_kernel(const MuBatch mb
   const int32_t p = gs_project_point(c, q.points[3 * n], q.points[3 * n + 1], q.points[3 * n + 2], mb.H, mb.W, mb.u_hi,
                                      mb.v_hi);
   // pix[n] = the pixel this row competes for, or -1 (not in the frame, or not similar to the pixel): all the merge needs
-  // to know of this pass (it rebuilds the key of a competing row from the row itself, see U5 above)
+  // to know of this pass (it rebuilds the key of a competing row from the row itself, see U5 above).
+  // The pixel's global vertex / normal: materialised by the pixel pass, or computed here (MuSeq::gvertex == NULL: the
+  // one-call step, whose frame-map launch initialised the tables -- there is no pixel pass then).
   int32_t pk = -1;
-  if (p >= 0) {
-    // the pixel's global vertex / normal: materialised by the pixel pass, or computed here (MuSeq::gvertex == NULL: the
-    // one-call step, whose frame-map launch initialised the tables -- there is no pixel pass then).
-    // The normal first: on the benchmark scene half the rows in the frame fail its test (they project onto a pixel
-    // without depth, whose vertex and normal are zero, or belong to the rim of a hole and never match), and a row that
-    // fails gathers no vertex.  The two tests are pure and joined by AND: the same pk, keys and tie marks.
-    float fp[3], fn[3];
-    if (q.gvertex) FrameGlobalMaps{q.gvertex, q.gnormal}.normal_of((int64_t)p, fn);
-    else frame_local_maps(q.vertex, q.normal, q.pose16, mb.two_sigma_sq).normal_of((int64_t)p, fn);
-    bool similar = gs_is_similar_dot_v(q.normals, fn, n, mb.dot_th);
-    if (similar) {
-      if (q.gvertex) FrameGlobalMaps{q.gvertex, q.gnormal}.vertex_of((int64_t)p, fp);
-      else frame_local_maps(q.vertex, q.normal, q.pose16, mb.two_sigma_sq).vertex_of((int64_t)p, fp);
-      similar = gs_is_similar_dist_v(q.points, fp, n, mb.dist_th);
-    }
-    if (similar) {
-      const uint64_t k = gs_assoc_key_v(q.points, q.ccounts, fp, n);
-      const unsigned long long old = atomicMin(reinterpret_cast<unsigned long long*>(&q.key_pix[p]), (unsigned long long)k);
-      // Two rows with the same key at one pixel: whichever arrives second gets its own key back.  (If the key is beaten
-      // later the mark is spurious and harmless; if it stays the minimum, every tie of the winning key has been seen:
-      // the first of the tied rows to arrive set it, every later one reads it back.)  The pixel is marked -- any value
-      // that is neither "no winner" (-1) nor a row index below it -- and settled by mu_settle_ties (in the per-pixel pass).
-      if (old == (unsigned long long)k) {
-        q.best_pix[p] = MU_TIE_MARK;
-        q.any_flag[1] = 1;   // benign race: every writer stores the same value
-      }
-      pk = p;
-    }
-  }
+  if (p >= 0) MU_WITH_FRAME(mb, q, pk = mu_key_row(mb, q, n, p, frame));
   q.pix[n] = pk;
 }
 
@@ -565,8 +625,7 @@ GS_DEV void mu_settle_ties(const MuBatch& mb, const MuSeq& q, const unsigned blk
     const int32_t p = q.pix[n];
     if (p < 0 || q.best_pix[p] == -1) continue;   // (-1: unmarked pixel -- its key has one holder)
     float fp[3];
-    if (q.gvertex) FrameGlobalMaps{q.gvertex, q.gnormal}.vertex_of((int64_t)p, fp);
-    else frame_local_maps(q.vertex, q.normal, q.pose16, mb.two_sigma_sq).vertex_of((int64_t)p, fp);
+    MU_WITH_FRAME(mb, q, frame.vertex_of((int64_t)p, fp));
     if (gs_assoc_key_v(q.points, q.ccounts, fp, n) == q.key_pix[p]) atomicMin(reinterpret_cast<unsigned*>(&q.best_pix[p]), (unsigned)n);
   }
 }
@@ -630,7 +689,7 @@ GS_DEV void mu_merge_row(const MuBatch& mb, const MuSeq& q, const int64_t n, con
       else frame.vertex_of((int64_t)p, fp);
       const int32_t bp = tie_marks ? q.best_pix[p] : -1;
       win = (uint32_t)kp == gs_assoc_key_lo_v(q.points, fp, n) && (bp == -1 || bp == (int32_t)n);
-      if (win && bp == -1) q.best_pix[p] = (int32_t)n;
+      if (win && bp == -1 && mb.best_is_output) q.best_pix[p] = (int32_t)n;   // (for a caller that wants the table)
     }
     if (!win) p = -1;
   }
@@ -646,8 +705,7 @@ GS_DEV void mu_merge_body(const MuBatch& mb, const unsigned bid) {
   // (pc2im_bnhw.shape[0] != 0 is a batch-level test): a sequence without matches is still renormalised when
   // another sequence of the same call has some
   if (*mb.call_flag == 0) return;
-  if (q.gvertex) mu_merge_row(mb, q, n, FrameGlobalMaps{q.gvertex, q.gnormal});
-  else mu_merge_row(mb, q, n, frame_local_maps(q.vertex, q.normal, q.pose16, mb.two_sigma_sq));
+  MU_WITH_FRAME(mb, q, mu_merge_row(mb, q, n, frame));
 }
 
 // ordered append without a scan launch: block b adds up the counts of the tiles before it (fixed order)
@@ -668,10 +726,10 @@ GS_DEV void mu_append_body(const MuBatch& mb, const unsigned bid) {
   if (blk == 0 && threadIdx.x == 0) q.new_count_out[0] = n_map + total_new;
   const int64_t base = (int64_t)blk * GS_CP_TILE + (int64_t)threadIdx.x * GS_CP_ITEMS;
   bool keep[GS_CP_ITEMS];
+  float dd[GS_CP_ITEMS];
   int c = 0;
   {
     uint64_t kk[GS_CP_ITEMS];  // loads first (see gs_mu_winner_count_kernel)
-    float dd[GS_CP_ITEMS];
 #pragma unroll
     for (int i = 0; i < GS_CP_ITEMS; ++i) {
       const int64_t pc = base + i < mb.P ? base + i : mb.P - 1;
@@ -688,13 +746,28 @@ GS_DEV void mu_append_body(const MuBatch& mb, const unsigned bid) {
   // new pixels of the tile listed in LDS (pixel order), then row r of the tile's output range is written by thread r
   // (see gs_cp_scatter_kernel: consecutive lanes -> consecutive rows)
   __shared__ unsigned short loc_s[GS_CP_TILE];
+  // without a vertex map (FrameDepthMaps) the depth of a new pixel, which this thread holds, travels with its list entry:
+  // the thread that writes the row computes the vertex from it and loads no depth a second time
+  __shared__ float dep_s[GS_CP_TILE];
+  const bool from_depth = !q.gvertex && !q.vertex;
 #pragma unroll
   for (int i = 0; i < GS_CP_ITEMS; ++i) {
-    if (keep[i]) loc_s[w++] = (unsigned short)(threadIdx.x * GS_CP_ITEMS + i);
+    if (keep[i]) {
+      if (from_depth) dep_s[w] = dd[i];
+      loc_s[w++] = (unsigned short)(threadIdx.x * GS_CP_ITEMS + i);
+    }
   }
   __syncthreads();
   const int64_t tile_base = (int64_t)blk * GS_CP_TILE;
-  if (q.gvertex) {
+  if (from_depth) {
+    const EmitAppendT<FrameDepthMaps> emit{q.points, q.normals, q.colors, q.ccounts, q.n_map,
+                                           frame_depth_maps(q.depth, q.normal, q.pose16, q.K16, mb.W, mb.two_sigma_sq), q.rgb,
+                                           q.alpha};
+    for (int r = threadIdx.x; r < tile_new; r += GS_CP_BLOCK) {
+      const int64_t pos = (int64_t)tile_prefix + r;
+      if (n_map + pos < q.capacity) emit(tile_base + loc_s[r], pos, dep_s[r]);
+    }
+  } else if (q.gvertex) {
     const EmitAppend emit{q.points, q.normals, q.colors, q.ccounts, q.n_map, FrameGlobalMaps{q.gvertex, q.gnormal}, q.rgb, q.alpha};
     for (int r = threadIdx.x; r < tile_new; r += GS_CP_BLOCK) {
       const int64_t pos = (int64_t)tile_prefix + r;
@@ -721,16 +794,19 @@ __global__ void __launch_bounds__(256) gs_mu_merge_append_kernel(const MuBatch m
 
 extern "C" int64_t gs_update_map_scratch_bytes(int64_t n_map_bound, int H, int W) {
   const int64_t P = (int64_t)H * W;
-  return (int64_t)(256 + gs_align(8 * (size_t)P) + gs_align(4 * (size_t)gs_cp_tiles(P)) +
-                   2 * gs_align(4 * (size_t)(n_map_bound > 0 ? n_map_bound : 1)) + 4096);
+  // flags | key_pix | the tie-marker table of a call that does not ask for best_pix | tile counts | pix[]
+  return (int64_t)(256 + gs_align(8 * (size_t)P) + gs_align(4 * (size_t)P) + gs_align(4 * (size_t)gs_cp_tiles(P)) +
+                   gs_align(4 * (size_t)(n_map_bound > 0 ? n_map_bound : 1)) + 4096);
 }
 
 // where the tables the frame-map launch of the one-call step initialises live inside an update scratch (as update_chunk
 // carves it); the call flag is the second flag word of the FIRST sequence of the call (see MuBatch::call_flag)
 int32_t* gs_update_map_call_flag(void* scratch0) { return reinterpret_cast<int32_t*>(scratch0) + 32; }
-void gs_update_map_tables(void* scratch, int32_t** any_flag, uint64_t** key_pix) {
-  *any_flag = reinterpret_cast<int32_t*>(scratch);
-  *key_pix = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(scratch) + 256);
+void gs_update_map_tables(void* scratch, int64_t P, int32_t** any_flag, uint64_t** key_pix, int32_t** best_scratch) {
+  char* q = reinterpret_cast<char*>(scratch);
+  *any_flag = reinterpret_cast<int32_t*>(q); q += 256;
+  *key_pix = reinterpret_cast<uint64_t*>(q); q += gs_align(8 * (size_t)P);
+  *best_scratch = reinterpret_cast<int32_t*>(q);
 }
 
 // phase 0: global maps, association, winner / tile counts; phase 1: merge + append (after phase 0 of every chunk)
@@ -741,6 +817,7 @@ static int update_chunk(const gs_update_seq* seqs, int B, int H, int W, float di
   mb.two_sigma_sq = two_sigma_sq;
   mb.B = B; mb.H = H; mb.W = W; mb.renorm_all = renorm_all;
   mb.call_flag = call_flag; mb.zero_call_flag = first_chunk ? 1 : 0;
+  mb.best_is_output = seqs[0].best_pix ? 1 : 0;   // (the same choice for every sequence of the call)
   mb.P = (int64_t)H * W;
   mb.ntiles = gs_cp_tiles(mb.P);
   mb.u_hi = (float)((double)W - 0.999); mb.v_hi = (float)((double)H - 0.999);
@@ -758,20 +835,24 @@ static int update_chunk(const gs_update_seq* seqs, int B, int H, int W, float di
     m.capacity = u.map.capacity;
     m.vertex = u.vertex; m.normal = u.normal; m.depth = u.depth; m.rgb = u.rgb; m.alpha = u.alpha;
     m.pose16 = u.pose16; m.K16 = u.K16;
-    m.gvertex = u.gvertex; m.gnormal = u.gnormal; m.best_pix = u.best_pix; m.new_count_out = u.new_count_out;
-    m.any_flag = reinterpret_cast<int32_t*>(q); q += 256;
-    m.key_pix = reinterpret_cast<uint64_t*>(q); q += gs_align(8 * (size_t)mb.P);
+    m.gvertex = u.gvertex; m.gnormal = u.gnormal; m.new_count_out = u.new_count_out;
+    int32_t* best_scratch;
+    gs_update_map_tables(u.scratch, mb.P, &m.any_flag, &m.key_pix, &best_scratch);
+    m.best_pix = u.best_pix ? u.best_pix : best_scratch;
+    q += 256 + gs_align(8 * (size_t)mb.P) + gs_align(4 * (size_t)mb.P);
     m.tile_counts = reinterpret_cast<int32_t*>(q); q += gs_align(4 * (size_t)mb.ntiles);
-    m.pix = reinterpret_cast<int32_t*>(q); q += gs_align(4 * (size_t)(n_map > 0 ? n_map : 1));
-    m.pix_of = reinterpret_cast<int32_t*>(q);
+    m.pix = reinterpret_cast<int32_t*>(q);
     // as built: projection 28 B read + 4 B written (+ 12 B of frame normal per row in the frame, 12 B of frame vertex per
     // row that passes the dot test -- booked for half of them, the benchmark scene's share -- and 8 B key per competing
     // row); merge 4 + 80 B per row (+ 8 B of key per competing row: the winner entry is read only in a frame with a tie
     // mark, and the vertex gathered for the low word of the key is the one a winner gathers for the merge anyway, which
     // with the global maps implicit also yields its alpha), 49 B per pixel for the winner count and the append (45 B with
-    // the global maps implicit: no alpha gather)
-    bytes_assoc += 58.0 * (double)n_map;
-    bytes_fuse += 92.0 * (double)n_map + (u.gvertex ? 49.0 : 45.0) * (double)mb.P;
+    // the global maps implicit: no alpha gather).  Without a vertex map (u.vertex == NULL) a vertex gather is the 4 B of the
+    // pixel's depth instead of 12 B -- 54 B per row in the projection -- and the append, which holds the depth, gathers
+    // nothing for the vertex: 33 B per pixel.  The winner's 4-byte store into best_pix was never booked.
+    const bool from_depth = !u.gvertex && !u.vertex;
+    bytes_assoc += (from_depth ? 54.0 : 58.0) * (double)n_map;
+    bytes_fuse += 92.0 * (double)n_map + (u.gvertex ? 49.0 : from_depth ? 33.0 : 45.0) * (double)mb.P;
   }
   const unsigned uB = (unsigned)B;
   const unsigned pb = uB * (unsigned)gs_ceil_div(mb.P, 256), nb = uB * (unsigned)gs_ceil_div(n_max > 0 ? n_max : 1, 256);
@@ -799,7 +880,10 @@ static int update_chunk(const gs_update_seq* seqs, int B, int H, int W, float di
 // where they live); gvertex / gnormal may then be NULL -- the global vertex and normal of a pixel are computed where they
 // are used (the same operations as the pixel pass: the same bits) and never written to memory.  For such a sequence the
 // alpha map must be the one that launch made from u.vertex with `two_sigma_sq`: the merge and the append compute
-// alpha[p] again from the local vertex they load (FrameLocalMaps) and do not read u.alpha.
+// alpha[p] again from the local vertex they load (FrameLocalMaps) and do not read u.alpha.  vertex and alpha may then be
+// NULL as well: the local vertex of a pixel is computed from its depth and K16 (FrameDepthMaps).
+// best_pix == NULL (any caller): the correspondence table is not an output; its tie-marker role is played by a table in
+// the scratch, which the winners do not write.
 int gs_update_map_fusion_batch_impl(const gs_update_seq* seqs_host, int B, int H, int W, float dist_th, float dot_th,
                                     int renorm_all, void* stream, bool tables_ready, float two_sigma_sq) {
   GS_REQUIRE(seqs_host && B > 0 && H > 0 && W > 0, "bad arguments");
@@ -808,10 +892,15 @@ int gs_update_map_fusion_batch_impl(const gs_update_seq* seqs_host, int B, int H
     const gs_update_seq& u = seqs_host[b];
     GS_REQUIRE(u.map.n_bound >= 0 && u.map.n_bound < 0x7fffffff, "bad map size");
     GS_REQUIRE(u.map.capacity >= u.map.n_bound + (int64_t)H * W, "capacity must cover n_bound + H*W rows");
-    GS_REQUIRE(u.map.points && u.map.normals && u.map.colors && u.map.ccounts && u.vertex && u.normal && u.depth && u.rgb &&
-                   u.alpha && u.pose16 && u.K16 && u.best_pix && u.new_count_out && u.scratch,
+    GS_REQUIRE(u.map.points && u.map.normals && u.map.colors && u.map.ccounts && u.normal && u.depth && u.rgb &&
+                   u.pose16 && u.K16 && u.new_count_out && u.scratch,
                "NULL pointer");
     GS_REQUIRE((u.gvertex && u.gnormal) || (tables_ready && !u.gvertex && !u.gnormal), "gvertex / gnormal: both or none");
+    // (without the global maps nothing reads the alpha map, and the local vertex of a pixel is fm_vertex of its depth)
+    GS_REQUIRE((u.vertex && u.alpha) || (tables_ready && !u.gvertex && !u.vertex && !u.alpha),
+               "vertex / alpha may be NULL only together, and only where the global maps are implicit");
+    GS_REQUIRE((u.vertex != nullptr) == (seqs_host[0].vertex != nullptr) && (u.best_pix != nullptr) == (seqs_host[0].best_pix != nullptr),
+               "vertex / alpha and best_pix: given or NULL, the same choice for every sequence");
     GS_REQUIRE(u.new_count_out != u.map.n_dev, "new_count_out must not alias the map's device count");
   }
   hipStream_t st = gs_stream(stream);

@@ -1185,7 +1185,8 @@ static double icp_alg_bytes(int numiters, int64_t n_slots, int64_t n_queries, in
 // is filled by B x the blocks.  Per sequence the arithmetic is that of gs_lattice_source_f32 + gs_project_map_dc_f32
 // + gs_icp_map_dc_f32, bit for bit (same device functions).
 struct LocSeq {
-  const float* vertex;
+  const float* vertex;   // may be NULL: the local vertex of a lattice pixel is fm_vertex of its depth (the same bits)
+  const float* K16;      // read only then
   const float* depth;
   const float* pose16;   // previous pose: lattice transform, projection and the composed result
   float* lattice;        // [n_lat][3] ICP source (NaN = no depth)
@@ -1218,11 +1219,18 @@ GS_DEV void loc_prep_block(const LocBatch& lb, const unsigned bid, const unsigne
     if (e < lb.n_lat) {
       const int64_t p = (e / lb.Wl) * lb.ds * (int64_t)lb.W + (e % lb.Wl) * lb.ds;
       float g0 = __builtin_nanf(""), g1 = g0, g2 = g0;
-      if (q.depth[p] > 0.0f) {
+      const float d = q.depth[p];
+      if (d > 0.0f) {
         float T[12];
 #pragma unroll
         for (int i = 0; i < 12; ++i) T[i] = q.pose16[i];
-        gs_rigid_fma(T, q.vertex[3 * p], q.vertex[3 * p + 1], q.vertex[3 * p + 2], g0, g1, g2);
+        float v0, v1, v2;
+        if (q.vertex) {
+          v0 = q.vertex[3 * p]; v1 = q.vertex[3 * p + 1]; v2 = q.vertex[3 * p + 2];
+        } else {
+          fm_vertex(d, (int)(e / lb.Wl) * lb.ds, (int)(e % lb.Wl) * lb.ds, gs_kinv(q.K16), v0, v1, v2);
+        }
+        gs_rigid_fma(T, v0, v1, v2, g0, g1, g2);
         valid = 1;
       }
       q.lattice[3 * e] = g0; q.lattice[3 * e + 1] = g1; q.lattice[3 * e + 2] = g2;
@@ -1400,7 +1408,7 @@ static void loc_bind(const gs_localize_seq* seqs, int B, int H, int W, int ds, c
     const gs_localize_seq& q = seqs[b];
     if (!plan.binned_normals) c[b].gm.sorted_n = nullptr;
     // (the prep launch zeroes the counters of the ordinary lists whether or not this solve keeps such lists)
-    lb.s[b] = LocSeq{q.vertex, q.depth, q.prev_pose16, c[b].lattice, c[b].sc.state, q.out_pose16,
+    lb.s[b] = LocSeq{q.vertex, q.K16, q.depth, q.prev_pose16, c[b].lattice, c[b].sc.state, q.out_pose16,
                      reinterpret_cast<char*>(c[b].gm.g), c[b].n_valid, c[b].lm.stat,
                      plan.wide_on ? c[b].fm.cq : nullptr, c[b].sc.weak_n};
     gb.s[b] = GsGridSeq{q.map.points, GsCount{q.map.n_bound, q.map.n_dev}, nullptr, q.prev_pose16, q.K16,
@@ -1679,13 +1687,13 @@ static int localize_chunk(const gs_localize_seq* seqs, int B, int H, int W, int 
 }
 
 static int localize_batch(const gs_localize_seq* seqs_host, int B, int H, int W, int ds, const gs_icp_params* prm,
-                          void* stream, bool grid_cleared) {
+                          void* stream, bool grid_cleared, bool vertex_optional = false) {
   GS_REQUIRE(seqs_host && prm && B > 0 && H > 0 && W > 0 && ds > 0, "bad arguments");
   GS_REQUIRE(!icp_params_error(prm), icp_params_error(prm));
   GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   for (int b = 0; b < B; ++b) {
     const gs_localize_seq& q = seqs_host[b];
-    GS_REQUIRE(q.vertex && q.depth && q.K16 && q.prev_pose16 && q.out_pose16 && q.scratch, "NULL pointer");
+    GS_REQUIRE((q.vertex || vertex_optional) && q.depth && q.K16 && q.prev_pose16 && q.out_pose16 && q.scratch, "NULL pointer");
     GS_REQUIRE(q.map.points && q.map.normals && q.map.n_bound > 0 && q.map.n_bound < 0x7fffffffll,
                "every sequence needs a non-empty map (points + normals)");
     GS_REQUIRE(q.map.capacity <= 0 || q.map.n_bound <= q.map.capacity, "map.n_bound exceeds map.capacity");
@@ -1742,12 +1750,16 @@ extern "C" int gs_pointfusion_step_batch_f32(const gs_step_seq* seqs_host, int B
   const int64_t dstride = B > 1 ? seqs_host[1].depth - s0.depth : P;
   for (int b = 0; b < B; ++b) {
     const gs_step_seq& q = seqs_host[b];
-    GS_REQUIRE(q.depth && q.rgb && q.K16 && q.prev_pose16 && q.out_pose16 && q.vertex && q.normal && q.alpha &&
-                   q.best_pix && q.new_count_out && q.loc_scratch && q.upd_scratch, "NULL pointer");
+    GS_REQUIRE(q.depth && q.rgb && q.K16 && q.prev_pose16 && q.out_pose16 && q.normal && q.new_count_out && q.loc_scratch &&
+                   q.upd_scratch, "NULL pointer");
     GS_REQUIRE((q.gvertex != nullptr) == (q.gnormal != nullptr) && (q.gvertex != nullptr) == (s0.gvertex != nullptr),
                "gvertex / gnormal: both or none, the same choice for every sequence");
+    GS_REQUIRE((q.vertex != nullptr) == (q.alpha != nullptr) && (q.vertex != nullptr) == (s0.vertex != nullptr),
+               "vertex / alpha: both or none, the same choice for every sequence");
+    GS_REQUIRE(q.vertex || !q.gvertex, "global maps are made from the vertex map: vertex / alpha must be given with them");
+    GS_REQUIRE((q.best_pix != nullptr) == (s0.best_pix != nullptr), "best_pix: the same choice for every sequence");
     GS_REQUIRE(q.out_pose16 != q.prev_pose16, "out_pose16 must not alias prev_pose16");
-    GS_REQUIRE(q.vertex == s0.vertex + 3 * P * b && q.normal == s0.normal + 3 * P * b && q.alpha == s0.alpha + P * b,
+    GS_REQUIRE(q.normal == s0.normal + 3 * P * b && (!q.vertex || (q.vertex == s0.vertex + 3 * P * b && q.alpha == s0.alpha + P * b)),
                "vertex / normal / alpha of the batch must be dense");
     GS_REQUIRE(q.depth == s0.depth + dstride * b && q.K16 == s0.K16 + 16 * (int64_t)b, "depth / K16 must be equally strided");
   }
@@ -1757,6 +1769,9 @@ extern "C" int gs_pointfusion_step_batch_f32(const gs_step_seq* seqs_host, int B
   // Global maps not asked for (gvertex == NULL): they are never written -- the update computes the global vertex / normal
   // of a pixel where it uses them -- and the frame-map launch initialises the update's per-pixel tables, so that the
   // update has no per-pixel pass at all (it was 26 us of a 1.05 ms frame at 8 x 640x480).
+  // Local vertex and alpha not asked for (vertex == alpha == NULL, which needs the global maps implicit): not written either
+  // -- the lattice source and the update compute the local vertex of a pixel from its depth (fm_vertex: the same bits) and
+  // its alpha from that.  best_pix == NULL: the table is no output; the update keeps its tie marks in its scratch.
   const bool implicit_global = s0.gvertex == nullptr;
   std::unique_ptr<gs_update_seq[]> us(new gs_update_seq[B]);
   for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
@@ -1787,13 +1802,14 @@ extern "C" int gs_pointfusion_step_batch_f32(const gs_step_seq* seqs_host, int B
     tabs.n = implicit_global ? nb : 0;
     tabs.call_flag = c0 == 0 ? gs_update_map_call_flag(seqs_host[0].upd_scratch) : nullptr;
     for (int b = 0; b < tabs.n; ++b) {
-      gs_update_map_tables(sq[b].upd_scratch, &tabs.any_flag[b], &tabs.key_pix[b]);
-      tabs.best_pix[b] = sq[b].best_pix;
+      int32_t* best_scratch;
+      gs_update_map_tables(sq[b].upd_scratch, P, &tabs.any_flag[b], &tabs.key_pix[b], &best_scratch);
+      tabs.best_pix[b] = sq[b].best_pix ? sq[b].best_pix : best_scratch;
     }
     int rc = gs_frame_maps_batch_clear(sq[0].depth, dstride, P, sq[0].K16, nb, 1, H, W, two_sigma_sq, sq[0].vertex,
                                        sq[0].normal, sq[0].alpha, &job, stream, &tabs);
     if (rc != GS_OK) return rc;
-    rc = localize_batch(ls, nb, H, W, ds, prm, stream, true);
+    rc = localize_batch(ls, nb, H, W, ds, prm, stream, true, true);
     if (rc != GS_OK) return rc;
   }
   // (two_sigma_sq: with the global maps implicit the update computes the alpha of a pixel from the local vertex it holds,

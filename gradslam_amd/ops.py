@@ -837,11 +837,13 @@ def localize_solve_stats(device, b, H, W, ds, capacity):
 
 
 def update_map_fusion_batch_(maps, vertex, normal, depth, rgb, alpha, poses, K, dist_th, dot_th, renorm_all=True,
-                             out=None):
+                             out=None, want_best_pix=True):
     """update_map_fusion of all sequences of a batch, in place on their capacity-backed buffers
     (gs_update_map_fusion_batch_f32: 4 launches for the whole batch).  maps: per sequence a MapRows with all four
     attributes (features: the confidence count).  vertex / normal / rgb (B, H, W, 3), depth / alpha (B, H, W),
-    poses / K (B, 4, 4).  Returns (counts int64 (B,) on the device, gvertex, gnormal, best_pix (B, H*W))."""
+    poses / K (B, 4, 4).  Returns (counts int64 (B,) on the device, gvertex, gnormal, best_pix (B, H*W)).
+    want_best_pix=False: the correspondence table is not written (the winners' scattered stores are saved) and the last
+    element of the result is None; maps and counts are the same."""
     poses, K = _c(poses), _c(K)
     dev = require_device(poses, K)
     Bn, H, W = depth.shape
@@ -852,13 +854,13 @@ def update_map_fusion_batch_(maps, vertex, normal, depth, rgb, alpha, poses, K, 
                                           torch.empty((Bn, H, W, 3), dtype=f32, device=dev))
     gviews = [_batch_view(t, 3) for t in (gv, gn)]
     assert gviews[0][0] is gv and gviews[1][0] is gn, "output global maps must have contiguous (H, W, 3) slices"
-    best = torch.empty((Bn, H * W), dtype=torch.int32, device=dev)
+    best = torch.empty((Bn, H * W), dtype=torch.int32, device=dev) if want_best_pix else None
     cnt = torch.empty(Bn, dtype=torch.int64, device=dev)
     ws = Workspace.get(dev)
     seqs = (_C.UpdateSeq * Bn)()
     L = lib()
     P1 = H * W * 4
-    base = [t.data_ptr() for t in (poses, K, best, cnt)]
+    base = [None if t is None else t.data_ptr() for t in (poses, K, best, cnt)]
     for b in range(Bn):
         P, N, Cc, F, _, n_dev = maps[b]
         require_device(P, N, Cc, F, n_dev)   # (written in place: contiguous buffers, which _map_rows hands through)
@@ -869,7 +871,8 @@ def update_map_fusion_batch_(maps, vertex, normal, depth, rgb, alpha, poses, K, 
         u.vertex, u.normal, u.depth, u.rgb, u.alpha = (v[1] + b * v[2] for v in views)
         u.pose16, u.K16 = base[0] + b * 64, base[1] + b * 64
         u.gvertex, u.gnormal = gviews[0][1] + b * gviews[0][2], gviews[1][1] + b * gviews[1][2]
-        u.best_pix, u.new_count_out, u.scratch = base[2] + b * P1, base[3] + b * 8, scratch.data_ptr()
+        u.best_pix = None if best is None else base[2] + b * P1
+        u.new_count_out, u.scratch = base[3] + b * 8, scratch.data_ptr()
     check(L.gs_update_map_fusion_batch_f32(seqs, Bn, H, W, float(dist_th), float(dot_th), 1 if renorm_all else 0,
                                            stream(dev)), "gs_update_map_fusion_batch_f32")
     return cnt, gv, gn, best

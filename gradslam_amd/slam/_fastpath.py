@@ -26,6 +26,13 @@ FASTPATH = os.environ.get("GRADSLAM_HIP_FASTPATH", "1") != "0"   # 0: always the
 # 1: the step also writes the live frame's GLOBAL vertex / normal maps (one more per-pixel pass per frame).  Default 0:
 # the update computes them where it uses them and the container computes them when somebody asks (the same bits).
 STEP_GLOBAL_MAPS = os.environ.get("GRADSLAM_HIP_STEP_GLOBAL_MAPS", "0") == "1"
+# 1: the step also writes the live frame's LOCAL vertex map and its alpha map (16 B per pixel).  Default 0: nothing in the
+# frame loop reads them -- the step computes the local vertex of a pixel from its depth where it uses it -- and the
+# container computes them when somebody asks (the same bits).  The global maps are made from the local ones:
+# STEP_GLOBAL_MAPS=1 implies this.
+STEP_LOCAL_MAPS = os.environ.get("GRADSLAM_HIP_STEP_LOCAL_MAPS", "0") == "1"
+# 1: the step also writes the correspondence table of the frame (H*W int32 per sequence; nothing keeps it: A/B runs)
+STEP_BEST_PIX = os.environ.get("GRADSLAM_HIP_STEP_BEST_PIX", "0") == "1"
 
 
 def _kwargs_key(kw):
@@ -125,16 +132,18 @@ class StepPlan(object):
         # (no global maps: the step computes them where the update uses them and never writes them; the container
         # computes them from the local maps and the pose when somebody asks -- the same bits)
         gm = STEP_GLOBAL_MAPS
-        out = torch.empty(B * (13 if gm else 7) * P, dtype=f32, device=dev)
+        lm = STEP_LOCAL_MAPS or gm
+        # layout: normal | vertex, alpha (lm) | global vertex, global normal (gm)
+        out = torch.empty(B * (13 if gm else 7 if lm else 3) * P, dtype=f32, device=dev)
         # The poses live in an allocation of their own (64 B per sequence): a caller that keeps the recovered poses of every
         # frame -- every SLAM loop does, slam/icpslam.py:134-137 -- would otherwise pin the 69 MB of maps they were carved
         # from (8 sequences of 640x480), the caching allocator could never hand a block back, and every step would pay a
         # fresh hipMalloc of that size on the host thread: usually ~0.1 ms, but 2 ms on a bad day of a shared host, which
         # made one bench run in six host-bound at half the rate (round 5, profiles/r05_bench_line_slow_host.json).
         poses_out = torch.empty(B * 16, dtype=f32, device=dev)
-        best = torch.empty((B, P), dtype=torch.int32, device=dev)
+        best = torch.empty((B, P), dtype=torch.int32, device=dev) if STEP_BEST_PIX else None
         o = out.data_ptr()
-        v0, n0, a0, po0 = o, o + 12 * P * B, o + 24 * P * B, poses_out.data_ptr()
+        n0, v0, a0, po0 = o, o + 12 * P * B, o + 24 * P * B, poses_out.data_ptr()
         gv0, gn0 = o + 28 * P * B, o + 28 * P * B + 12 * P * B
         # the new counts go to a buffer the MAP owns (two per count group, alternating): a plan serves whatever map it is
         # handed, and a map's live device count must not be a word some other map's next frame writes
@@ -144,15 +153,17 @@ class StepPlan(object):
         cnt_new = pair[0] if pair[0].data_ptr() != grp.dev.data_ptr() else pair[1]
         d0, ds_ = d
         r0, rs_ = r
-        k0, p0, c0, n_dev0, b0 = K.data_ptr(), pp.data_ptr(), cnt_new.data_ptr(), grp.dev.data_ptr(), best.data_ptr()
+        k0, p0, c0, n_dev0 = K.data_ptr(), pp.data_ptr(), cnt_new.data_ptr(), grp.dev.data_ptr()
+        b0 = None if best is None else best.data_ptr()
         seqs = self.seqs
         for b in range(B):
             q = seqs[b]
             q.depth, q.rgb = d0 + 4 * ds_ * b, r0 + 4 * rs_ * b
             q.K16, q.prev_pose16, q.out_pose16 = k0 + 64 * b, p0 + 64 * b, po0 + 64 * b
-            q.vertex, q.normal, q.alpha = v0 + 12 * P * b, n0 + 12 * P * b, a0 + 4 * P * b
+            q.normal = n0 + 12 * P * b
+            q.vertex, q.alpha = (v0 + 12 * P * b, a0 + 4 * P * b) if lm else (None, None)
             q.gvertex, q.gnormal = (gv0 + 12 * P * b, gn0 + 12 * P * b) if gm else (None, None)
-            q.best_pix = b0 + 4 * P * b
+            q.best_pix = None if b0 is None else b0 + 4 * P * b
             q.new_count_out = c0 + 8 * b
             q.map.n_bound = bounds[b]
             q.map.n_dev = n_dev0 + 8 * b
@@ -160,9 +171,12 @@ class StepPlan(object):
                                                         self.dot_th, 1 if RENORMALIZE_UNMATCHED else 0, self.stream), "gs_pointfusion_step_batch_f32")
         # hand the results to the containers (the caches the generic path fills)
         n3 = 3 * P * B
-        live._vertex_map = out[:n3].view(B, 1, H, W, 3)
-        live._normal_map = out[n3:2 * n3].view(B, 1, H, W, 3)
-        live._alpha_cache = (self.sigma, out[2 * n3:2 * n3 + P * B].view(B, 1, H, W, 1))
+        live._normal_map = out[:n3].view(B, 1, H, W, 3)
+        if lm:
+            live._vertex_map = out[n3:2 * n3].view(B, 1, H, W, 3)
+            live._alpha_cache = (self.sigma, out[2 * n3:2 * n3 + P * B].view(B, 1, H, W, 1))
+        else:
+            live._vertex_map = live._alpha_cache = None    # (computed on demand from the depth image)
         live._poses = poses_out.view(B, 1, 4, 4)
         if gm:
             g = 7 * P * B

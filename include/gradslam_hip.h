@@ -462,7 +462,8 @@ GS_API int gs_frame_maps_batch_f32(const float* depth, int64_t depth_stride_seq,
  * move from frame to frame while the map grows inside them (after the call the scratch holds the solver state / trace
  * at the offset gs_icp_trace_f32 expects, the binned targets and the candidate lists of the solve). */
 typedef struct gs_localize_seq {
-  const float* vertex;      /* live frame, LOCAL vertex map (H, W, 3) */
+  const float* vertex;      /* live frame, LOCAL vertex map (H, W, 3); gs_localize_batch_f32 needs it (inside the one-call
+                             * step it may be NULL: the local vertex of a lattice pixel is then computed from depth and K16) */
   const float* depth;       /* live frame depth (H, W) */
   const float* K16;         /* intrinsics of the previous frame */
   const float* prev_pose16; /* pose of the previous frame (initial guess and composition) */
@@ -504,7 +505,8 @@ typedef struct gs_update_seq {
   const float* K16;
   float* gvertex;           /* out: global maps (H, W, 3) */
   float* gnormal;
-  int32_t* best_pix;        /* out: correspondence table (H*W), -1 = none */
+  int32_t* best_pix;        /* out, optional: correspondence table (H*W), -1 = none.  NULL (for every sequence of the call): */
+                            /* not written -- maps and counts are the same, the winners' scattered stores are saved        */
   int64_t* new_count_out;   /* out: device int64[1]; must not alias map.n_dev */
   void* scratch;
 } gs_update_seq;
@@ -524,13 +526,15 @@ typedef struct gs_step_seq {
   const float* K16;          /* intrinsics (of the previous = live frame) */
   const float* prev_pose16;  /* pose of the previous frame */
   float* out_pose16;         /* out: recovered pose of the live frame (must not alias prev_pose16) */
-  float* vertex;             /* out: LOCAL vertex / normal maps (H, W, 3), sample confidences (H, W) */
-  float* normal;
-  float* alpha;
+  float* vertex;             /* out, optional (with alpha): LOCAL vertex map (H, W, 3) */
+  float* normal;             /* out: LOCAL normal map (H, W, 3) */
+  float* alpha;              /* out, optional (with vertex): sample confidences (H, W).  vertex and alpha both NULL (for every  */
+                             /* sequence of the call; needs gvertex == NULL): not written -- the step computes the local vertex */
+                             /* of a pixel from depth and K16 where it uses it (same bits); gs_frame_maps_batch_f32 on demand  */
   float* gvertex;            /* out, optional: global maps under the recovered pose.  Both NULL (for every sequence of the */
   float* gnormal;            /* call): not written -- the update computes the global vertex / normal of a pixel where it   */
                              /* uses them (same bits) and skips its per-pixel pass; gs_global_maps_f32 gives them on demand */
-  int32_t* best_pix;         /* out: correspondence table (H*W) */
+  int32_t* best_pix;         /* out, optional: correspondence table (H*W).  NULL (for every sequence of the call): not written */
   int64_t* new_count_out;    /* out: device int64[1], must not alias map.n_dev */
   gs_map_view map;           /* all four attributes; n_bound > 0; capacity >= n_bound + H*W */
   void* loc_scratch;         /* gs_localize_scratch_bytes(H, W, ds, map.capacity) */
