@@ -35,6 +35,23 @@
 // gs_picp_scale.hip in front of the robust linearisation: the kernel then reads its sequence's threshold of this iteration,
 // max(huber_k * 1.4826 * lower median |b|, huber_floor), from a device float (PiSeq::delta_dev; NULL: the constant above),
 // and the finish kernel tapes it in PiTapeRow::pad[0].
+// The weighted entries (gs_projective_icp_weighted_batch_f32 / _rows_f32): one optional float32 image of PIXEL WEIGHTS
+// per sequence, read at the pixel of each lattice slot.  The rule, per slot with pixel p and wp = weight[p]:
+//   1  depth[p] > 0, else code 1, as above
+//   6  wp > 0 && wp < +inf in float32, else code 6 ("masked"): zero, negative, NaN and +inf all mask; nothing is
+//      validated on the host, nothing is read back.  A masked slot is not associated, not counted as an inlier, not part
+//      of any median; it contributes +0.0 to every term and has no colour row
+//   2 .. 5 as above
+//   a used slot's total weight is wt = wp * h, ONE float32 product, h the Huber weight of its raw residual b
+//   (pi_huber_weight; 1.0f without a threshold; the clip flag is taken from the unweighted float32 b), and every one of
+//   its 28 terms is pi_term(wt, x, y); in the joint solve the colour products carry wp * wc in the same way.
+//   The inlier count stays the integer number of used slots, S[27] is the weighted sum of squares; with huber_k the
+//   median is that of the unweighted |b| of the used slots (masked slots excluded).  The reduction shape, the finish
+//   kernel, the solve, the update and "no inlier keeps the pose bits" are untouched.
+// They launch the WEIGHTED instance of the linearise body (and of the residual pass), one 4-byte load per slot more than
+// the robust one.  Two consequences, bit for bit: weights of all 1.0f give the unweighted entries' bits ((double)1.0f *
+// (x y) is the exact product), and weight 0 on a set of pixels gives the bits of depth 0 on those pixels (the code
+// tables differ in 6 against 1).  A sequence whose weights pointer is NULL has no weights.
 // What this file holds: the body of the linearise kernel with its two term expressions, the traits of the plain solve and
 // the entries.  The block prologue (pi_prologue), the association (pi_associate), the chunk reduction (pi_chunk_reduce,
 // PI_PAIRS), the column sum of the partials (pi_column_sums), the finish body (pi_finish) and the host drivers
@@ -44,8 +61,11 @@
 // The linearise kernel's body: prologue, association, the row z = (a0 .. a5, b), the table outputs, the chunk reduction.
 // ROBUST: every term of a used slot carries the Huber weight of its residual b (pi_huber_weight), which also goes to
 // rb.weight_out (nslots, 0 for a slot that is not used) when asked for; the colour half of rb is ignored.
-template <bool ROBUST>
+// WEIGHTED (with ROBUST): the weight of a used slot is wp * w, wp the slot's pixel weight (pi_associate<true>); a
+// masked slot has code 6.
+template <bool ROBUST, bool WEIGHTED = false>
 GS_DEV void pi_linearize(const PiBatch& pb, const PiRobust& rb) {
+  static_assert(ROBUST || !WEIGHTED, "the weighted instance carries its weight through the robust terms");
   __shared__ GsCamera cam;
   __shared__ float Ts[12];
   __shared__ int cnt[GS_PI_CHUNK / GS_WAVE];
@@ -59,11 +79,13 @@ GS_DEV void pi_linearize(const PiBatch& pb, const PiRobust& rb) {
   if (t.in_lattice) {
     float s[3];
     float4 d, m;
-    code = pi_associate(Ts, cam, q.in, pb.g, n_map, t.p, row, s, d, m);
+    float wp;
+    code = pi_associate<WEIGHTED>(Ts, cam, q.in, pb.g, n_map, t.p, row, s, d, m, wp);
     if (code == 0) gn_row_pn(s[0], s[1], s[2], d, m, z, z[6]);
     pi_table_out(q, t.k, code, row, z);
     if (ROBUST) {
       if (code == 0) w = pi_huber_weight(pi_huber_clipped(z[6], delta), z[6], delta);
+      if (WEIGHTED && code == 0) w = wp * w;
       if (rb.weight_out) rb.weight_out[t.k] = code == 0 ? w : 0.0f;
     }
   }
@@ -86,6 +108,10 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_linearize_kernel(const Pi
 
 __global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_linearize_kernel(const PiBatch pb, const PiRobust rb) {
   pi_linearize<true>(pb, rb);
+}
+
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_weighted_picp_linearize_kernel(const PiBatch pb, const PiRobust rb) {
+  pi_linearize<true, true>(pb, rb);
 }
 
 __global__ void __launch_bounds__(GS_PI_FIN) gs_picp_finish_kernel(const PiBatch pb) {
@@ -114,6 +140,7 @@ struct PiPlain {
   static constexpr int TRACE = GS_PI_TRACE;
   static constexpr auto linearize = gs_picp_linearize_kernel;
   static constexpr auto robust_linearize = gs_robust_picp_linearize_kernel;
+  static constexpr auto weighted_linearize = gs_weighted_picp_linearize_kernel;
   static constexpr auto finish = gs_picp_finish_kernel;
   static const gs_picp_seq& base(const Seq& u) { return u; }
   static PiSeq& seq(Batch& pb, int b) { return pb.s[b]; }
@@ -179,4 +206,36 @@ extern "C" int gs_projective_icp_scaled_rows_f32(const gs_picp_seq* seq_host, in
   return picp_rows<PiPlain>(__func__, seq_host, H, W, stride, dist_th, dot_th, 0.0f,
                             PiRobust{0.0f, 0.0f, weight, nullptr},
                             PiRowsOut{code, row, a6, b, nullptr, nullptr, nullptr, sums28, count, nullptr}, &sc, stream);
+}
+
+// The weighted entries: pixel weights next to any of the thresholds above.  huber_k > 0: the median rule, huber_delta its
+// floor (the scratch is then the scaled entries'); else huber_delta is the constant threshold (0: none).  tapes_host /
+// deltas_host as in the scaled entry (either may be NULL; deltas_host is read with huber_k > 0 only).
+static int pi_check_weighted(const char* who, float huber_delta, float huber_k) {
+  PICP_CHECK_DELTA(who, huber_delta, "huber_delta");
+  PICP_REQUIRE(who, huber_k >= 0.0f && huber_k < __builtin_inff(), "huber_k must be finite and not negative");
+  return GS_OK;
+}
+
+extern "C" int gs_projective_icp_weighted_batch_f32(const gs_picp_seq* seqs_host, const float* const* weights_host,
+                                                    void* const* tapes_host, float* const* deltas_host, int B, int H,
+                                                    int W, const gs_picp_params* params_host, float huber_delta,
+                                                    float huber_k, void* stream) {
+  if (const int err = pi_check_weighted(__func__, huber_delta, huber_k)) return err;
+  const PiScale sc = picp_scale_geo(huber_k, huber_delta, deltas_host, nullptr);
+  return picp_solve<PiPlain>(__func__, seqs_host, tapes_host, B, H, W, params_host, 0.0f, sc.on[PS_GEO] ? 0.0f : huber_delta,
+                             0.0f, sc.on[PS_GEO] ? &sc : nullptr, stream, weights_host, true);
+}
+
+extern "C" int gs_projective_icp_weighted_rows_f32(const gs_picp_seq* seq_host, const float* weights, int H, int W,
+                                                   int stride, float dist_th, float dot_th, float huber_delta,
+                                                   float huber_k, int32_t* code, int64_t* row, float* a6, float* b,
+                                                   float* weight, double* sums28, int64_t* count, float* delta_out,
+                                                   void* stream) {
+  if (const int err = pi_check_weighted(__func__, huber_delta, huber_k)) return err;
+  const PiScale sc = picp_scale_geo(huber_k, huber_delta, nullptr, delta_out);
+  return picp_rows<PiPlain>(__func__, seq_host, H, W, stride, dist_th, dot_th, 0.0f,
+                            PiRobust{sc.on[PS_GEO] ? 0.0f : huber_delta, 0.0f, weight, nullptr},
+                            PiRowsOut{code, row, a6, b, nullptr, nullptr, nullptr, sums28, count, nullptr},
+                            sc.on[PS_GEO] ? &sc : nullptr, stream, weights, true);
 }

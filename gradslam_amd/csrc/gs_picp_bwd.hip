@@ -62,7 +62,21 @@
 //   * vertex_bar, init_pose_bar, the scalar stage and the 12 sums are those of the atomic mode, bit for bit (the slot's
 //     arithmetic is ONE definition, pb_point).
 // With no map output asked for in a launch group the group runs the atomic mode's launches: nothing is recorded or sorted.
+//
+// Pixel weights (gs_projective_icp_weighted_backward_batch_f32, a tape of the weighted forward; the rule is in
+// gs_picp.hip's header).  With wp the slot's pixel weight and h the Huber weight of its residual (1 without a threshold)
+// the system is A = sum wp h a a^T, g = sum wp h a b.  The WEIGHTED instances of the point stage take, with the scalar
+// stage's u and xi unchanged, e = u . a and c = xi . a as above:
+//   pixel_weights_bar[p] += h e (b - c);   ab is multiplied by wp h;   the residual's adjoint is e wp (h + h' (b - c))
+// (h' as in the ROBUST instance, 0 without a threshold).  Which slots are masked (code 6 of pi_associate<true>) is a
+// constant of the pass like the association and the clip flags.  A slot is its own pixel and the iterations are
+// serialised, so pixel_weights_bar accumulates like vertex_bar: float64 per slot (wacc), no atomics, rounded once:
+// BITWISE REPRODUCIBLE in the atomic and in the ordered mode, and the same bits in both (ONE definition, pb_point; the
+// ordered mode's records are the weighted contributions).  Pixels off the lattice, masked slots and slots never used get
+// +0.0.  Not asked for (NULL): no work, no store, and the sequence's scratch is that of the unweighted entry.
 #include <hipcub/hipcub.hpp>
+
+#include <vector>
 
 #include "gs_picp_dev.h"
 #include "gs_se3_f64.h"
@@ -88,6 +102,8 @@ struct PbSeq {
   double* vacc;             // (nslots, 3) or NULL (no vertex_bar)
   double* pbar;             // (n_bound, 3) or NULL
   double* mbar;             // (n_bound, 3) or NULL
+  float* weights_bar;       // (H, W) or NULL (the weighted entry)
+  double* wacc;             // (nslots) or NULL (no weights_bar)
 };
 struct PbBatch {
   PbSeq s[GS_MAX_BATCH];
@@ -196,7 +212,9 @@ __global__ void __launch_bounds__(GS_PI_FIN) gs_picp_bwd_scalar_kernel(const PbB
 // RECORD (the ordered mode, rec != NULL): the two map contributions are not added atomically but stored in the slot's
 // record (zeros for a map output that is not asked for), and EVERY slot of the lattice writes its key, used or not,
 // active iteration or not.
-template <bool ROBUST, bool RECORD>
+// WEIGHTED (with ROBUST; the weighted entry): the slot's pixel weight wp enters as the header says, and the slot's
+// contribution to pixel_weights_bar is accumulated in wacc like vacc.
+template <bool ROBUST, bool RECORD, bool WEIGHTED = false>
 GS_DEV void pb_point(const PbBatch& pb, const PbRecord* rec, const int it, const int first, const int last,
                      const float delta_launch, const bool taped) {
   __shared__ GsCamera cam;
@@ -218,13 +236,16 @@ GS_DEV void pb_point(const PbBatch& pb, const PbRecord* rec, const int it, const
   bool used = false;
   int32_t key = PB_NO_KEY;   // (RECORD)
   double sb[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
+  double wbar = 0.0;   // (WEIGHTED) this iteration's contribution to the slot's pixel_weights_bar
+  static_assert(ROBUST || !WEIGHTED, "the weighted instance differentiates its weight next to the Huber weight");
   if (t.in_lattice) {
     if (active) {   // (block-uniform; an iteration without inliers has no used slot)
       const int64_t n_map = gs_count(q.in.n);
       int64_t row;
       float sf[3];
       float4 df, mf;
-      used = pi_associate(Ts, cam, q.in, pb.g, n_map, p, row, sf, df, mf) == 0;
+      float wp;
+      used = pi_associate<WEIGHTED>(Ts, cam, q.in, pb.g, n_map, p, row, sf, df, mf, wp) == 0;
       if (used) {
         double s[3], a[6];
         const double d[3] = {(double)df.x, (double)df.y, (double)df.z}, m[3] = {(double)mf.x, (double)mf.y, (double)mf.z};
@@ -254,9 +275,17 @@ GS_DEV void pb_point(const PbBatch& pb, const PbRecord* rec, const int it, const
           const bool clipped = pi_huber_clipped(bf, delta);
           const double hw = pi_huber_weight(clipped, b, (double)delta);
           const double hd = clipped ? -hw / b : 0.0;
+          if (WEIGHTED) {
+            wbar = hw * e * (b - cc);
+            const double wt = (double)wp * hw;
 #pragma unroll
-          for (int c = 0; c < 6; ++c) ab[c] = hw * ab[c];
-          e = e * (hw + hd * (b - cc));
+            for (int c = 0; c < 6; ++c) ab[c] = wt * ab[c];
+            e = e * ((double)wp * (hw + hd * (b - cc)));
+          } else {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) ab[c] = hw * ab[c];
+            e = e * (hw + hd * (b - cc));
+          }
         }
         const double* w = ab + 3;
         sb[0] = (m[1] * w[2] - m[2] * w[1]) - e * m[0];
@@ -307,6 +336,12 @@ GS_DEV void pb_point(const PbBatch& pb, const PbRecord* rec, const int it, const
         else q.vacc[3 * (int64_t)k + c] = acc;
       }
     }
+    if (WEIGHTED && q.wacc) {   // as vacc: the slot's own thread, float64 across the serialised iterations
+      double acc = first ? 0.0 : q.wacc[k];
+      if (used) acc += wbar;
+      if (last) q.weights_bar[p] = (float)acc;
+      else q.wacc[k] = acc;
+    }
   }
   // the 12 sums of sb [v^T 1] in the forward's reduction shape: terms 0 .. 8 the outer product, 9 .. 11 sb
   pi_chunk_reduce<PB_NV>([&](const int i) { return i < 9 ? sb[i / 3] * v[i % 3] : sb[i - 9]; }, __ballot(used) != 0ull,
@@ -324,6 +359,12 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_bwd_point_kernel(c
   pb_point<true, false>(pb, nullptr, it, first, last, delta, taped != 0);
 }
 
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_weighted_picp_bwd_point_kernel(const PbBatch pb, const int it,
+                                                                                 const int first, const int last,
+                                                                                 const float delta, const int taped) {
+  pb_point<true, false, true>(pb, nullptr, it, first, last, delta, taped != 0);
+}
+
 // ------------------------------------------------------------------ ordered mode: the RECORD point stages, the settle step
 __global__ void __launch_bounds__(GS_PI_CHUNK) gs_ordered_picp_bwd_point_kernel(const PbBatch pb, const PbRecord rec,
                                                                                 const int it, const int first,
@@ -336,6 +377,13 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_ordered_robust_picp_bwd_point_
                                                                                        const int last, const float delta,
                                                                                        const int taped) {
   pb_point<true, true>(pb, &rec, it, first, last, delta, taped != 0);
+}
+
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_ordered_weighted_picp_bwd_point_kernel(const PbBatch pb, const PbRecord rec,
+                                                                                         const int it, const int first,
+                                                                                         const int last, const float delta,
+                                                                                         const int taped) {
+  pb_point<true, true, true>(pb, &rec, it, first, last, delta, taped != 0);
 }
 
 // the values of the sort: 0, 1, 2, ... (pair b nslots + k is slot k of sequence b); written once per launch group
@@ -415,13 +463,28 @@ struct PbOrderedCall {
   void* sort_scratch;
   int64_t sort_scratch_bytes;
 };
+// what the weighted entry adds: per sequence the forward's pixel weights (a NULL entry: none) and the output (H, W) (a
+// NULL entry, or a NULL array: not asked for).  The float64 accumulator of the output (nslots) lies behind the
+// sequence's scratch of the mode.
+struct PbWeightedCall {
+  const float* const* weights;
+  float* const* weights_bar;
+};
+static size_t pb_wacc_bytes(int64_t nslots) { return gs_align((size_t)nslots * sizeof(double)); }
+
+extern "C" int64_t gs_projective_icp_weighted_backward_scratch_bytes(int H, int W, int stride, int64_t n_map, int ordered) {
+  const int64_t base = ordered ? gs_projective_icp_ordered_backward_scratch_bytes(H, W, stride, n_map)
+                               : gs_projective_icp_backward_scratch_bytes(H, W, stride, n_map);
+  return base > 0 ? base + (int64_t)pb_wacc_bytes(picp_slots(H, W, stride)) : 0;
+}
 
 // the pass behind the entries; delta: the Huber threshold the forward ran with (0: the plain point kernel); taped: the
 // robust point kernel with every iteration's threshold from the tape (delta is then not read); oc: the ordered entry's
 // sequences and sort scratch (seqs_host is then NULL), or NULL: the atomic mode
+// wc: the weighted entry's weights and output (the WEIGHTED point kernels run), or NULL
 static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, int B, int H, int W,
                        const gs_picp_params* params_host, float delta, bool taped, const PbOrderedCall* oc,
-                       void* stream) {
+                       void* stream, const PbWeightedCall* wc = nullptr) {
   PICP_REQUIRE(who, (oc ? oc->seqs != nullptr : seqs_host != nullptr) && params_host && B > 0 && H > 0 && W > 0,
                "bad arguments");
   PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
@@ -430,6 +493,16 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
   PICP_CHECK_DELTA(who, delta, "huber_delta");
   const int64_t nslots = picp_slots(H, W, prm.stride), nchunks = gs_ceil_div(nslots, GS_PI_CHUNK);
   const auto seq = [&](int b) -> const gs_picp_backward_seq& { return oc ? oc->seqs[b].base : seqs_host[b]; };
+  PICP_REQUIRE(who, !wc || wc->weights, "NULL pointer (weights)");
+  // (the scratch of sequence b in front of the weighted entry's accumulator, for the map size it is checked for)
+  const auto mode_bytes = [&](int64_t n_map) {
+    return oc ? gs_projective_icp_ordered_backward_scratch_bytes(H, W, prm.stride, n_map)
+              : gs_projective_icp_backward_scratch_bytes(H, W, prm.stride, n_map);
+  };
+  // (the accumulator is asked of a sequence only when its output is asked for)
+  const auto wacc_bytes = [&](int b) {
+    return wc && wc->weights_bar && wc->weights_bar[b] ? (int64_t)pb_wacc_bytes(nslots) : (int64_t)0;
+  };
   bool any_map = false;
   for (int b = 0; b < B; ++b) {
     const gs_picp_backward_seq& u = seq(b);
@@ -443,13 +516,8 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
     any_map = any_map || (want_map && u.map.n_bound > 0);
     if (oc) {
       PICP_REQUIRE(who, u.map.n_bound < PB_NO_KEY, "map too large for int32 row keys (n_bound >= 0x7fffffff)");
-      PICP_REQUIRE(who, u.scratch_bytes >= gs_projective_icp_ordered_backward_scratch_bytes(H, W, prm.stride,
-                                                                                            want_map ? u.map.n_bound : 0),
-                   "scratch too small");
-    } else {
-      PICP_REQUIRE(who, u.scratch_bytes >= gs_projective_icp_backward_scratch_bytes(H, W, prm.stride, want_map ? u.map.n_bound : 0),
-                   "scratch too small");
     }
+    PICP_REQUIRE(who, u.scratch_bytes >= mode_bytes(want_map ? u.map.n_bound : 0) + wacc_bytes(b), "scratch too small");
   }
   if (oc && any_map) {
     PICP_REQUIRE(who, pb_group(B) * nslots < (1ll << 31), "too many slots in a launch group for one sort (sequences x nslots >= 2^31)");
@@ -482,6 +550,16 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
       if (s.mbar) GS_HIP(hipMemsetAsync(s.mbar, 0, map_bytes, st));
       // pixels off the lattice get no gradient (the last point stage stores the lattice pixels)
       if (u.vertex_bar && prm.stride > 1) GS_HIP(hipMemsetAsync(u.vertex_bar, 0, (size_t)H * W * 3 * sizeof(float), st));
+      s.weights_bar = nullptr; s.wacc = nullptr;
+      if (wc) {
+        s.in.weight = wc->weights[c0 + b];
+        s.weights_bar = wc->weights_bar ? wc->weights_bar[c0 + b] : nullptr;
+        if (s.weights_bar) {
+          s.wacc = reinterpret_cast<double*>(static_cast<char*>(u.scratch) +
+                                             mode_bytes((u.points_bar || u.normals_bar) ? u.map.n_bound : 0));
+          if (prm.stride > 1) GS_HIP(hipMemsetAsync(s.weights_bar, 0, (size_t)H * W * sizeof(float), st));
+        }
+      }
       if (oc) {   // the sequence's record, behind the atomic mode's layout for the map size its scratch was checked for
         char* r = static_cast<char*>(u.scratch) +
                   gs_projective_icp_backward_scratch_bytes(H, W, prm.stride, (u.points_bar || u.normals_bar) ? u.map.n_bound : 0);
@@ -520,14 +598,20 @@ static int pb_backward(const char* who, const gs_picp_backward_seq* seqs_host, i
       hipLaunchKernelGGL(gs_picp_bwd_scalar_kernel, dim3(nb), dim3(GS_PI_FIN), 0, st, pb, it, first ? 0 : 1);
       const bool robust = delta > 0.0f || taped;
       if (!ordered) {
-        if (robust)
+        if (wc)
+          hipLaunchKernelGGL(gs_weighted_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first, last,
+                             delta, taped ? 1 : 0);
+        else if (robust)
           hipLaunchKernelGGL(gs_robust_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first, last,
                              delta, taped ? 1 : 0);
         else
           hipLaunchKernelGGL(gs_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, it, first, last);
         continue;
       }
-      if (robust)
+      if (wc)
+        hipLaunchKernelGGL(gs_ordered_weighted_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, rec, it,
+                           first, last, delta, taped ? 1 : 0);
+      else if (robust)
         hipLaunchKernelGGL(gs_ordered_robust_picp_bwd_point_kernel, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, rec, it, first,
                            last, delta, taped ? 1 : 0);
       else
@@ -588,4 +672,27 @@ extern "C" int gs_projective_icp_ordered_backward_batch_f32(const gs_picp_ordere
   const PbOrderedCall oc{seqs_host, sort_scratch, sort_scratch_bytes};
   return pb_backward(__func__, nullptr, B, H, W, params_host, taped_scale ? 0.0f : huber_delta, taped_scale != 0, &oc,
                      stream);
+}
+
+// the backward of the weighted forward (gs_projective_icp_weighted_batch_f32 with a tape): the three tapes as in the
+// ordered entry (huber_delta, taped_scale), atomic (ordered == 0: key_out / contrib_out and the sort scratch are not
+// read) or ordered; weights_host as at the forward; weights_bar_host: per sequence the output (H, W) or NULL, or NULL
+// for none at all.  scratch per sequence: gs_projective_icp_weighted_backward_scratch_bytes when its output is asked
+// for, else the scratch of the mode's unweighted entry.
+extern "C" int gs_projective_icp_weighted_backward_batch_f32(const gs_picp_ordered_backward_seq* seqs_host,
+                                                             const float* const* weights_host,
+                                                             float* const* weights_bar_host, int B, int H, int W,
+                                                             const gs_picp_params* params_host, float huber_delta,
+                                                             int taped_scale, int ordered, void* sort_scratch,
+                                                             int64_t sort_scratch_bytes, void* stream) {
+  GS_REQUIRE(seqs_host && B > 0, "bad arguments");
+  const PbWeightedCall wc{weights_host, weights_bar_host};
+  const float delta = taped_scale ? 0.0f : huber_delta;
+  if (ordered) {
+    const PbOrderedCall oc{seqs_host, sort_scratch, sort_scratch_bytes};
+    return pb_backward(__func__, nullptr, B, H, W, params_host, delta, taped_scale != 0, &oc, stream, &wc);
+  }
+  std::vector<gs_picp_backward_seq> base(B);
+  for (int b = 0; b < B; ++b) base[b] = seqs_host[b].base;
+  return pb_backward(__func__, base.data(), B, H, W, params_host, delta, taped_scale != 0, nullptr, stream, &wc);
 }

@@ -127,8 +127,11 @@ extern "C" int gs_model_intensity_f32(const float* color, const int64_t* index, 
 // The joint linearise kernel's body: prologue, association, the rows z = (a0 .. a5, b) and zc = (ac0 .. ac5, bc), the
 // table outputs, the chunk reduction.  ROBUST: the geometric product of every term carries the Huber weight w of the
 // slot's residual b, the colour product the weight wc of its colour residual r (pi_huber_weight, gs_picp_dev.h).
-template <bool ROBUST>
+// WEIGHTED (with ROBUST; the weighted entries, see gs_picp.hip): both weights carry the slot's pixel weight, wp * w and
+// wp * wc, one float32 product each; a masked slot has code 6 and no colour row.
+template <bool ROBUST, bool WEIGHTED = false>
 GS_DEV void pic_linearize(const PicBatch& pb, const PiRobust& rb) {
+  static_assert(ROBUST || !WEIGHTED, "the weighted instance carries its weight through the robust terms");
   __shared__ GsCamera cam;
   __shared__ float Ts[12];
   __shared__ int cnt[GS_PI_CHUNK / GS_WAVE], ccnt[GS_PI_CHUNK / GS_WAVE];
@@ -146,13 +149,16 @@ GS_DEV void pic_linearize(const PicBatch& pb, const PiRobust& rb) {
   if (t.in_lattice) {
     float s[3];
     float4 d, m;
-    code = pi_associate(Ts, cam, q.in, pb.g, n_map, t.p, row, s, d, m);
+    float wp;
+    code = pi_associate<WEIGHTED>(Ts, cam, q.in, pb.g, n_map, t.p, row, s, d, m, wp);
     if (code == 0) {
       gn_row_pn(s[0], s[1], s[2], d, m, z, z[6]);
       if (ROBUST) w = pi_huber_weight(pi_huber_clipped(z[6], delta), z[6], delta);
+      if (WEIGHTED) w = wp * w;
       float r = 0.0f;
       colored = pic_color_row(cam, pb.g, qc.color, qc.model, t.p, s, pb.weight, zc, r);
       if (ROBUST && colored) wc = pi_huber_weight(pi_huber_clipped(r, cdelta), r, cdelta);
+      if (WEIGHTED && colored) wc = wp * wc;
     }
     pi_table_out(q, t.k, code, row, z);
     if (qc.cflag_out) qc.cflag_out[t.k] = colored ? 1 : 0;
@@ -201,6 +207,11 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_robust_picp_color_linearize_ke
   pic_linearize<true>(pb, rb);
 }
 
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_weighted_picp_color_linearize_kernel(const PicBatch pb,
+                                                                                       const PiRobust rb) {
+  pic_linearize<true, true>(pb, rb);
+}
+
 __global__ void __launch_bounds__(GS_PI_FIN) gs_picp_color_finish_kernel(const PicBatch pb) {
   const PicSeq& qc = pb.s[blockIdx.x];
   pi_finish<true>(qc.g, pb.g.nchunks, pb.g.damp, qc.ccounts, qc.ccount_out);
@@ -226,6 +237,7 @@ struct PiJoint {
   static constexpr int TRACE = GS_PIC_TRACE;
   static constexpr auto linearize = gs_picp_color_linearize_kernel;
   static constexpr auto robust_linearize = gs_robust_picp_color_linearize_kernel;
+  static constexpr auto weighted_linearize = gs_weighted_picp_color_linearize_kernel;
   static constexpr auto finish = gs_picp_color_finish_kernel;
   static const gs_picp_seq& base(const Seq& u) { return u.base; }
   static PiSeq& seq(Batch& pb, int b) { return pb.s[b].g; }
@@ -359,4 +371,48 @@ extern "C" int gs_projective_icp_color_joint_scaled_rows_f32(const gs_picp_color
                             PiRobust{huber_floor, color_huber_floor, weight, color_weight_out},
                             PiRowsOut{code, row, a6, b, ac6, bc, colored, sums28, count, color_count},
                             sc.on[PS_GEO] || sc.on[PS_COLOR] ? &sc : nullptr, stream);
+}
+
+// The weighted joint entries (pixel weights: the rule is in gs_picp.hip's header): thresholds as in the joint scaled
+// entries with huber_delta / color_huber_delta for the floors -- a constant of 0 leaves that threshold the constant its
+// floor names --, the scratch gs_projective_icp_color_joint_scaled_scratch_bytes when a rule is on, else the colour one.
+static int pic_check_weighted(const char* who, float huber_delta, float huber_k, float color_huber_delta,
+                              float color_huber_k) {
+  PICP_CHECK_DELTA(who, huber_delta, "huber_delta");
+  PICP_CHECK_DELTA(who, color_huber_delta, "color_huber_delta");
+  PICP_REQUIRE(who, huber_k >= 0.0f && huber_k < __builtin_inff(), "huber_k must be finite and not negative");
+  PICP_REQUIRE(who, color_huber_k >= 0.0f && color_huber_k < __builtin_inff(),
+               "color_huber_k must be finite and not negative");
+  return GS_OK;
+}
+
+extern "C" int gs_projective_icp_color_weighted_batch_f32(const gs_picp_color_seq* seqs_host,
+                                                          const float* const* weights_host, float* const* deltas_host,
+                                                          float* const* cdeltas_host, int B, int H, int W,
+                                                          const gs_picp_params* params_host, float color_weight,
+                                                          float huber_delta, float huber_k, float color_huber_delta,
+                                                          float color_huber_k, void* stream) {
+  if (const int err = pic_check_weighted(__func__, huber_delta, huber_k, color_huber_delta, color_huber_k)) return err;
+  const PiScale sc = picp_scale_joint(huber_k, huber_delta, color_huber_k, color_huber_delta, deltas_host, cdeltas_host,
+                                      nullptr, nullptr);
+  return picp_solve<PiJoint>(__func__, seqs_host, nullptr, B, H, W, params_host, color_weight, huber_delta,
+                             color_huber_delta, sc.on[PS_GEO] || sc.on[PS_COLOR] ? &sc : nullptr, stream, weights_host,
+                             true);
+}
+
+extern "C" int gs_projective_icp_color_weighted_rows_f32(const gs_picp_color_seq* seq_host, const float* weights, int H,
+                                                         int W, int stride, float dist_th, float dot_th,
+                                                         float color_weight, float huber_delta, float huber_k,
+                                                         float color_huber_delta, float color_huber_k, int32_t* code,
+                                                         int64_t* row, float* a6, float* b, float* ac6, float* bc,
+                                                         int32_t* colored, float* weight, float* color_weight_out,
+                                                         double* sums28, int64_t* count, int64_t* color_count,
+                                                         float* delta_out, float* cdelta_out, void* stream) {
+  if (const int err = pic_check_weighted(__func__, huber_delta, huber_k, color_huber_delta, color_huber_k)) return err;
+  const PiScale sc = picp_scale_joint(huber_k, huber_delta, color_huber_k, color_huber_delta, nullptr, nullptr, delta_out,
+                                      cdelta_out);
+  return picp_rows<PiJoint>(__func__, seq_host, H, W, stride, dist_th, dot_th, color_weight,
+                            PiRobust{huber_delta, color_huber_delta, weight, color_weight_out},
+                            PiRowsOut{code, row, a6, b, ac6, bc, colored, sums28, count, color_count},
+                            sc.on[PS_GEO] || sc.on[PS_COLOR] ? &sc : nullptr, stream, weights, true);
 }

@@ -43,6 +43,7 @@ struct PiInputs {
   const float* points;
   const float* normals;
   GsCount n;
+  const float* weight;   // per-pixel weights (H, W) of the weighted entries, or NULL: none
 };
 struct PiGeom {
   int B, H, W, stride, Wl, nslots, nchunks;
@@ -105,10 +106,19 @@ GS_DEV PiSlot pi_prologue(const PiInputs& in, const PiGeom& g, const float* __re
 // The association of lattice pixel p at pose Ts (12 floats): the slot's code (0 used, 1 .. 5 the reject codes of the
 // header), the index image's entry where one was read (else -1), the live vertex under Ts and, for a row that was read
 // (codes 0, 4, 5), the map point d and normal m.  n_map = min(device count, bound): a stale index is never dereferenced.
+// WEIGHTED (the weighted entries; a sequence without weights has in.weight == NULL): behind the depth test the pixel's
+// weight wp = in.weight[p] is read, and a weight that is not a positive finite float32 (zero, negative, NaN, +inf) masks
+// the slot: code 6.  wp is handed out (1 where none is read).
+template <bool WEIGHTED>
 GS_DEV int pi_associate(const float* Ts, const GsCamera& cam, const PiInputs& in, const PiGeom& geom, const int64_t n_map,
-                        const int64_t p, int64_t& row, float* s, float4& d, float4& m) {
+                        const int64_t p, int64_t& row, float* s, float4& d, float4& m, float& wp) {
   row = -1;
+  wp = 1.0f;
   if (!(in.depth[p] > 0.0f)) return 1;
+  if (WEIGHTED && in.weight) {
+    wp = in.weight[p];
+    if (!(wp > 0.0f && wp < __builtin_inff())) return 6;
+  }
   float g[3];
   gs_rigid_fma(Ts, in.vertex[3 * p], in.vertex[3 * p + 1], in.vertex[3 * p + 2], s[0], s[1], s[2]);
   const float n0 = in.normal[3 * p], n1 = in.normal[3 * p + 1], n2 = in.normal[3 * p + 2];
@@ -297,7 +307,8 @@ struct PiScale {
 // the residual pass and the select, enqueued back to back (defined in gs_picp_scale.hip); first: the call's first use of
 // the descriptors: one more launch in front clears every sequence's counters (after it the select blocks leave them
 // cleared)
-void picp_scale_launch(const PiScaleBatch& sb, const PiScalePick& pk, bool first, hipStream_t st);
+// weighted: the WEIGHTED instances of the residual pass (a masked slot has no key: it is in no median)
+void picp_scale_launch(const PiScaleBatch& sb, const PiScalePick& pk, bool first, bool weighted, hipStream_t st);
 
 constexpr int GS_PS_BINS = 2048;   // values of an 11-bit digit of a key
 static inline size_t picp_keys_bytes(int64_t nslots) { return gs_align((size_t)nslots * sizeof(uint32_t)); }
@@ -463,6 +474,7 @@ static inline void picp_fill_inputs(PiInputs& in, const U& u) {
   in.model_pose16 = u.model_pose16;
   in.points = u.map.points; in.normals = u.map.normals;
   in.n = GsCount{u.map.n_bound, u.map.n_dev};
+  in.weight = nullptr;
 }
 
 static inline void picp_fill_seq(PiSeq& s, const gs_picp_seq& u, int nchunks) {
@@ -479,6 +491,7 @@ static inline void picp_fill_seq(PiSeq& s, const gs_picp_seq& u, int nchunks) {
 //   X::Seq, X::Batch      the caller's descriptor of a sequence and the kernels' argument
 //   X::TRACE              floats per trace row
 //   X::linearize, X::robust_linearize, X::finish     the kernels: (Batch), (Batch, PiRobust), (Batch)
+//   X::weighted_linearize  the WEIGHTED instance of the robust kernel: (Batch, PiRobust)
 //   X::base(u), X::seq(pb, b)      the gs_picp_seq inside a Seq, the PiSeq inside a Batch
 //   X::check(who, u)      the checks of a Seq (GS_OK or the error)
 //   X::fill(pb, b, u, color_weight)      sequence b of the batch from u, the scratch carved, every output NULL
@@ -521,12 +534,15 @@ static void picp_fill_scale(PiScaleSeq& z, typename X::Batch& pb, int b, const g
 
 // the solve behind the batch entries; tapes_host: per sequence the device buffer of numiters tape rows, or NULL
 // (untaped); delta / cdelta: the Huber thresholds of the robust entries (both 0: the plain kernel); sc: the median rule
-// of the scaled entries (delta is then not read: every sequence has its device threshold), or NULL
+// of the scaled entries (delta is then not read: every sequence has its device threshold), or NULL; weights_host: per
+// sequence the device image (H, W) of pixel weights or NULL (that sequence has none), weighted: the weighted entries
+// (weights_host must then be there; the WEIGHTED kernels run whatever the thresholds)
 template <typename X>
 static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* const* tapes_host, int B, int H, int W,
                       const gs_picp_params* params_host, float color_weight, float delta, float cdelta,
-                      const PiScale* sc, void* stream) {
+                      const PiScale* sc, void* stream, const float* const* weights_host = nullptr, bool weighted = false) {
   PICP_REQUIRE(who, seqs_host && params_host && B > 0 && H > 0 && W > 0, "bad arguments");
+  PICP_REQUIRE(who, !weighted || weights_host, "NULL pointer (weights)");
   PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   const gs_picp_params& prm = *params_host;
   PICP_CHECK_PARAMS(who, prm);
@@ -553,6 +569,7 @@ static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* c
     for (int b = 0; b < nb; ++b) {
       X::fill(pb, b, seqs_host[c0 + b], color_weight);
       X::seq(pb, b).T_out = X::base(seqs_host[c0 + b]).out_pose16;
+      if (weighted) X::seq(pb, b).in.weight = weights_host[c0 + b];
       if (sc) picp_fill_scale<X>(sb.s[b], pb, b, X::base(seqs_host[c0 + b]), *sc);
     }
     const unsigned blocks = (unsigned)nb * (unsigned)pb.g.nchunks;   // < 8 * 2^23
@@ -569,8 +586,10 @@ static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* c
             sb.s[b].r[i].delta_out = sc->on[i] && sc->deltas_host[i] ? sc->deltas_host[i][c0 + b] + it : nullptr;
         }
       }
-      if (sc) picp_scale_launch(sb, picp_scale_pick(*sc), it == 0, st);
-      if (robust)
+      if (sc) picp_scale_launch(sb, picp_scale_pick(*sc), it == 0, weighted, st);
+      if (weighted)
+        hipLaunchKernelGGL(X::weighted_linearize, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, rb);
+      else if (robust)
         hipLaunchKernelGGL(X::robust_linearize, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb, rb);
       else
         hipLaunchKernelGGL(X::linearize, dim3(blocks), dim3(GS_PI_CHUNK), 0, st, pb);
@@ -582,12 +601,14 @@ static int picp_solve(const char* who, const typename X::Seq* seqs_host, void* c
 }
 
 // the linearisation behind the table-level entries; rb: the thresholds and the weight tables of the robust entries (a
-// table with both thresholds 0: the robust kernel writes 1 for every row there is); sc: the median rule, or NULL
+// table with both thresholds 0: the robust kernel writes 1 for every row there is); sc: the median rule, or NULL;
+// weights / weighted: the weighted entries' image of pixel weights (the tables then hold the total weights)
 template <typename X>
 static int picp_rows(const char* who, const typename X::Seq* seq_host, int H, int W, int stride, float dist_th,
                      float dot_th, float color_weight, const PiRobust& rb, const PiRowsOut& o, const PiScale* sc,
-                     void* stream) {
+                     void* stream, const float* weights = nullptr, bool weighted = false) {
   PICP_REQUIRE(who, seq_host && H > 0 && W > 0, "bad arguments");
+  PICP_REQUIRE(who, !weighted || weights, "NULL pointer (weights)");
   PICP_REQUIRE(who, (int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
   PICP_REQUIRE(who, stride >= 1, "stride must be at least 1");
   PICP_REQUIRE(who, !(dist_th != dist_th) && !(dot_th != dot_th), "a threshold is NaN");
@@ -604,14 +625,17 @@ static int picp_rows(const char* who, const typename X::Seq* seq_host, int H, in
   s.code_out = o.code; s.row_out = o.row; s.a_out = o.a6; s.b_out = o.b;
   s.sums_out = o.sums28; s.count_out = o.count;
   X::color_outputs(pb, o);
+  if (weighted) s.in.weight = weights;
   if (sc) {   // the threshold at init_pose16 first: two launches in front of the robust linearisation
     PiScaleBatch sb;
     sb.g = pb.g;
     picp_fill_scale<X>(sb.s[0], pb, 0, X::base(*seq_host), *sc);
     for (int i = 0; i < PS_RESIDUALS; ++i) sb.s[0].r[i].delta_out = sc->on[i] ? sc->delta_out[i] : nullptr;
-    picp_scale_launch(sb, picp_scale_pick(*sc), true, st);
+    picp_scale_launch(sb, picp_scale_pick(*sc), true, weighted, st);
   }
-  if (sc || rb.delta > 0.0f || rb.cdelta > 0.0f || rb.weight_out || rb.cweight_out)
+  if (weighted)
+    hipLaunchKernelGGL(X::weighted_linearize, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb, rb);
+  else if (sc || rb.delta > 0.0f || rb.cdelta > 0.0f || rb.weight_out || rb.cweight_out)
     hipLaunchKernelGGL(X::robust_linearize, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb, rb);
   else
     hipLaunchKernelGGL(X::linearize, dim3((unsigned)pb.g.nchunks), dim3(GS_PI_CHUNK), 0, st, pb);

@@ -45,7 +45,9 @@ constexpr int GS_PS_TOP_SHIFT = 21;   // the first digit: the top 11 bits
 // The residual pass.  GEO / COL: the residuals asked for (at least one); for the other one nothing is computed, loaded
 // or stored.  One pi_associate per slot serves both.  Each residual has its own first-digit histogram in LDS (8 KB; both:
 // 16 KB a block, which at 256 threads still leaves room for the 8 waves a SIMD can hold).
-template <bool GEO, bool COL>
+// WEIGHTED (the weighted entries): pi_associate<true>, so a slot whose pixel weight masks it (code 6) has no key and is
+// in no median; the residuals themselves are the unweighted ones.
+template <bool GEO, bool COL, bool WEIGHTED = false>
 GS_DEV void ps_keys(const PiScaleBatch& sb) {
   static_assert(GEO || COL, "a residual pass without a residual");
   __shared__ GsCamera cam;
@@ -64,7 +66,8 @@ GS_DEV void ps_keys(const PiScaleBatch& sb) {
     int64_t row;
     float s[3];
     float4 d, m;
-    const bool used = pi_associate(Ts, cam, q.in, sb.g, n_map, t.p, row, s, d, m) == 0;
+    float wp;
+    const bool used = pi_associate<WEIGHTED>(Ts, cam, q.in, sb.g, n_map, t.p, row, s, d, m, wp) == 0;
     if (GEO) {
       float a[6], b = 0.0f;
       if (used) gn_row_pn(s[0], s[1], s[2], d, m, a, b);
@@ -103,6 +106,16 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_scale_color_keys_kernel(c
 }
 __global__ void __launch_bounds__(GS_PI_CHUNK) gs_picp_scale_joint_keys_kernel(const PiScaleBatch sb) {
   ps_keys<true, true>(sb);
+}
+
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_weighted_picp_scale_keys_kernel(const PiScaleBatch sb) {
+  ps_keys<true, false, true>(sb);
+}
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_weighted_picp_scale_color_keys_kernel(const PiScaleBatch sb) {
+  ps_keys<false, true, true>(sb);
+}
+__global__ void __launch_bounds__(GS_PI_CHUNK) gs_weighted_picp_scale_joint_keys_kernel(const PiScaleBatch sb) {
+  ps_keys<true, true, true>(sb);
 }
 
 // The bin of a 2048-bin histogram that holds `rank` (0-based, below the histogram's total) and the rank inside it, for
@@ -211,14 +224,14 @@ __global__ void __launch_bounds__(GS_PS_THREADS) gs_picp_scale_clear_kernel(cons
   hist[2 * threadIdx.x + 1] = 0u;
 }
 
-void picp_scale_launch(const PiScaleBatch& sb, const PiScalePick& pk, const bool first, hipStream_t st) {
+void picp_scale_launch(const PiScaleBatch& sb, const PiScalePick& pk, const bool first, const bool weighted,
+                       hipStream_t st) {
   const dim3 per_res((unsigned)sb.g.B * (unsigned)pk.count), chunks((unsigned)sb.g.B * (unsigned)sb.g.nchunks);
   if (first) hipLaunchKernelGGL(gs_picp_scale_clear_kernel, per_res, dim3(GS_PS_THREADS), 0, st, sb, pk);
-  if (pk.count == 2)
-    hipLaunchKernelGGL(gs_picp_scale_joint_keys_kernel, chunks, dim3(GS_PI_CHUNK), 0, st, sb);
-  else if (pk.first == PS_COLOR)
-    hipLaunchKernelGGL(gs_picp_scale_color_keys_kernel, chunks, dim3(GS_PI_CHUNK), 0, st, sb);
-  else
-    hipLaunchKernelGGL(gs_picp_scale_keys_kernel, chunks, dim3(GS_PI_CHUNK), 0, st, sb);
+  const auto keys = pk.count == 2 ? (weighted ? gs_weighted_picp_scale_joint_keys_kernel : gs_picp_scale_joint_keys_kernel)
+                    : pk.first == PS_COLOR
+                        ? (weighted ? gs_weighted_picp_scale_color_keys_kernel : gs_picp_scale_color_keys_kernel)
+                        : (weighted ? gs_weighted_picp_scale_keys_kernel : gs_picp_scale_keys_kernel);
+  hipLaunchKernelGGL(keys, chunks, dim3(GS_PI_CHUNK), 0, st, sb);
   hipLaunchKernelGGL(gs_picp_scale_select_kernel, per_res, dim3(GS_PS_THREADS), 0, st, sb, pk);
 }

@@ -8,8 +8,10 @@ is the joint geometric + photometric one (gs_projective_icp_color_batch_f32): th
 the live frame's colour is compared with it.  `huber_delta` / `color_huber_delta` > 0 switch on Huber weights
 (the *_robust_* entry points): rows with a large residual are down-weighted instead of pulling the pose at full weight.
 `huber_k` > 0 estimates the geometric threshold from the residuals in every iteration (the *_scaled_* entry points),
-`color_huber_k` > 0 the colour threshold from the colour residuals (the *_joint_scaled_* entry points)."""
-from typing import Optional, Union
+`color_huber_k` > 0 the colour threshold from the colour residuals (the *_joint_scaled_* entry points).  `pixel_weights`
+hands every solve a weight image made from the live frame (the *_weighted_* entry points); `axial_noise_weights` is a
+ready-made one."""
+from typing import Callable, Optional, Union
 
 import torch
 
@@ -17,7 +19,29 @@ from ..structures.pointclouds import Pointclouds
 from ..structures.rgbdimages import RGBDImages
 from .base import OdometryProvider
 
-__all__ = ["ProjectiveICPOdometryProvider"]
+__all__ = ["ProjectiveICPOdometryProvider", "axial_noise_weights"]
+
+
+def axial_noise_weights(frames: RGBDImages, sigma0: float = 0.0012, k: float = 0.0019, z0: float = 0.4) -> torch.Tensor:
+    r"""Per-pixel weights 1 / sigma^2(z) of a structured-light sensor's axial noise, normalised to 1 at z = z0:
+    (sigma0 / (sigma0 + k (z - z0)^2))^2 with z the depth in metres, and 0 where there is no depth.  Returns
+    (B, L, H, W) float32 for frames of shape (B, L, H, W): with one frame per sequence, what
+    `ProjectiveICPOdometryProvider(pixel_weights=...)` expects.  Plain torch, hence differentiable in the depth.
+
+    The defaults sigma(z) = 0.0012 + 0.0019 (z - 0.4)^2 are the published Kinect v1 axial-noise constants (Nguyen, Izadi
+    and Lovell, "Modeling Kinect Sensor Noise for Improved 3D Reconstruction and Tracking", 3DIMPVT 2012); they are not
+    tuned here."""
+    if not isinstance(frames, RGBDImages):
+        raise TypeError("Expected frames to be of type gradslam.RGBDImages. Got {0}.".format(type(frames)))
+    for name, val in (("sigma0", sigma0), ("k", k), ("z0", z0)):
+        if isinstance(val, bool) or not isinstance(val, (float, int)):
+            raise TypeError("axial_noise_weights: {} must be of type float or int; but was of type {}.".format(
+                name, type(val)))
+    if not sigma0 > 0 or not k >= 0:
+        raise ValueError("axial_noise_weights: sigma0 ({}) must be positive and k ({}) not negative.".format(sigma0, k))
+    z = frames.to_channels_last().depth_image[..., 0].float()
+    w = (sigma0 / (sigma0 + k * (z - z0) ** 2)) ** 2
+    return torch.where(z > 0, w, torch.zeros_like(w))
 
 
 class ProjectiveICPOdometryProvider(OdometryProvider):
@@ -61,6 +85,13 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             normals: True = in a fixed order (bitwise reproducible, slower: the ordered mode of
             `ops.projective_icp_backward_batch`), False = float64 atomics, None (the default) = as
             GRADSLAM_HIP_DETERMINISTIC_BACKWARD says when the backward runs.
+        pixel_weights: None (the default: no weights, the solves above bit for bit) or a callable that takes the live
+            `RGBDImages` the solve sees and returns the per-pixel weights of its frames as a float32 tensor (B, H, W) or
+            (B, 1, H, W) on the frames' device (`ops.projective_icp_batch(pixel_weights=...)`): a mask, a sensor model
+            (`axial_noise_weights`), a network's confidence.  A pixel whose weight is not a positive finite number is
+            masked for the solve (the map update still sees it).  It is called once per `localize`.  With
+            `differentiable=True` its output stays on the autograd tape: the parameters of a module get gradients.  Works
+            with every threshold and with `color_weight`.
 
     Unlike the point-cloud-pair providers it needs the map and the live frame themselves: call
     `localize(pointclouds, live_frame, prev_poses)`."""
@@ -70,8 +101,13 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                  min_confidence: Union[float, int] = 0.0, radius: int = 0, differentiable: bool = False,
                  color_weight: Union[float, int] = 0.0, huber_delta: Union[float, int] = 0.0,
                  color_huber_delta: Union[float, int] = 0.0, huber_k: Union[float, int] = 0.0,
-                 color_huber_k: Union[float, int] = 0.0, deterministic_backward: Optional[bool] = None):
+                 color_huber_k: Union[float, int] = 0.0, deterministic_backward: Optional[bool] = None,
+                 pixel_weights: Optional[Callable] = None):
         from .. import ops
+        if pixel_weights is not None and not callable(pixel_weights):
+            raise TypeError("pixel_weights must be None or a callable (live frame -> weights); but was of type "
+                            "{}.".format(type(pixel_weights)))
+        self.pixel_weights = pixel_weights   # (carried next to _kwargs(), like color_weight)
         if not isinstance(differentiable, bool):
             raise TypeError("differentiable must be of type bool; but was of type {}.".format(type(differentiable)))
         ops._picp_deterministic("ProjectiveICPOdometryProvider", "deterministic_backward", deterministic_backward)
@@ -108,6 +144,20 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
         return dict(stride=1 if self.stride is None else self.stride, numiters=self.numiters, damp=self.damp,
                     dist_thresh=self.dist_thresh, angle_thresh=self.angle_thresh)
 
+    def _weights(self, live_frame, B, H, W):
+        """the weight image of a localisation (B, H, W), or None: ONE call of the caller's function"""
+        if self.pixel_weights is None:
+            return None
+        w = self.pixel_weights(live_frame)
+        if not torch.is_tensor(w):
+            raise TypeError("pixel_weights must return a tensor; got {}.".format(type(w)))
+        if tuple(w.shape) not in ((B, H, W), (B, 1, H, W)):
+            raise ValueError("pixel_weights must return a tensor of shape {} or {}; got {}.".format(
+                (B, H, W), (B, 1, H, W), tuple(w.shape)))
+        if w.dtype != torch.float32:
+            raise TypeError("pixel_weights must return a float32 tensor; got {}.".format(w.dtype))
+        return w.reshape(B, H, W)
+
     def provide(self, *args, **kwargs):
         raise TypeError("ProjectiveICPOdometryProvider aligns a live frame with the rendered map, not two point clouds: "
                         "call localize(pointclouds, live_frame, prev_poses)")
@@ -137,6 +187,7 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
         K = fr.intrinsics[:, 0].contiguous().float()
         # the index image is all the solve reads of the view: no colour, normal or confidence image is rendered
         maps = pointclouds._map_rows(("points", "normals") + (("features",) if self.min_confidence > 0 else ()))
+        weights = self._weights(live_frame, B, H, W)
         if self.differentiable:
             # the render stays off the tape (the winners are constants): it sees detached tensors and does not warn
             view = ops.render_map_batch([m._replace(points=m.points.detach(), normals=None) for m in maps],
@@ -153,7 +204,8 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             T = ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
                                          view.index[:, 0], poses.detach(), maps, poses, differentiable=True, guard=guard,
                                          huber_delta=self.huber_delta, huber_k=self.huber_k,
-                                         deterministic=self.deterministic_backward, **self._kwargs())
+                                         deterministic=self.deterministic_backward, pixel_weights=weights,
+                                         **self._kwargs())
             return T.unsqueeze(1)
         out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=poses.device)
         if self.color_weight > 0:
@@ -169,11 +221,13 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                            view.index[:, 0], poses, maps, poses, fr.rgb_image[:, 0], model,
                                            color_weight=self.color_weight, out=out.view(B, 4, 4),
                                            huber_delta=self.huber_delta, color_huber_delta=self.color_huber_delta,
-                                           huber_k=self.huber_k, color_huber_k=self.color_huber_k, **self._kwargs())
+                                           huber_k=self.huber_k, color_huber_k=self.color_huber_k, pixel_weights=weights,
+                                           **self._kwargs())
             return out
         view = ops.render_map_batch([m._replace(normals=None) for m in maps], poses.view(B, 1, 4, 4), K, H, W,
                                     radius=self.radius, min_confidence=self.min_confidence)
         ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
                                  view.index[:, 0], poses, maps, poses, out=out.view(B, 4, 4),
-                                 huber_delta=self.huber_delta, huber_k=self.huber_k, **self._kwargs())
+                                 huber_delta=self.huber_delta, huber_k=self.huber_k, pixel_weights=weights,
+                                 **self._kwargs())
         return out

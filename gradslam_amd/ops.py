@@ -1081,6 +1081,53 @@ def _picp_nslots(H, W, stride):
     return ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
 
 
+def _picp_pixel_weights(who, pixel_weights, depth):
+    """The checks of the per-pixel weights of a batched call against depth (B, H, W): a float32 tensor (B, H, W) on
+    depth's device, or a list / tuple of B entries, each None (that sequence has no weights) or a float32 (H, W) tensor.
+    Returns None (no weights at all) or the list of B entries, detached and contiguous.  The values are not looked at:
+    a weight that is not a positive finite float32 masks its pixel on the device."""
+    if pixel_weights is None:
+        return None
+    if not torch.is_tensor(depth) or depth.ndim != 3:
+        return []   # (the checks of depth, which follow, refuse the call)
+    Bn, H, W = (int(x) for x in depth.shape)
+    if torch.is_tensor(pixel_weights):
+        if tuple(pixel_weights.shape) != (Bn, H, W):
+            raise ValueError("{}: expected pixel_weights of shape {} for depth {}; got {}".format(
+                who, (Bn, H, W), tuple(depth.shape), tuple(pixel_weights.shape)))
+        entries = [pixel_weights[b] for b in range(Bn)]
+    elif isinstance(pixel_weights, (list, tuple)):
+        if len(pixel_weights) != Bn:
+            raise ValueError("{}: expected one pixel_weights entry per sequence ({}); got {}".format(
+                who, Bn, len(pixel_weights)))
+        entries = list(pixel_weights)
+    else:
+        raise TypeError("{}: expected pixel_weights to be of type tensor (or a list of tensors / None); got {}".format(
+            who, type(pixel_weights)))
+    out = []
+    for t in entries:
+        if t is None:
+            out.append(None)
+            continue
+        if not torch.is_tensor(t):
+            raise TypeError("{}: expected pixel_weights to be of type tensor; got {}".format(who, type(t)))
+        if t.dtype != f32:
+            raise TypeError("{}: pixel_weights must be float32; got {}".format(who, t.dtype))
+        if tuple(t.shape) != (H, W):
+            raise ValueError("{}: expected pixel_weights of shape {} per sequence; got {}".format(who, (H, W),
+                                                                                                 tuple(t.shape)))
+        if t.device != depth.device:
+            raise ValueError("{}: pixel_weights must live on the inputs' device ({}); got {}".format(
+                who, depth.device, t.device))
+        out.append(t.detach().contiguous())
+    return out
+
+
+def _picp_weight_ptrs(entries):
+    """the host array of B device pointers of _picp_pixel_weights' entries (NULL: that sequence has no weights)"""
+    return (_C.C.c_void_p * len(entries))(*[None if t is None else t.data_ptr() for t in entries])
+
+
 def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, color=False, scaled=False,
                color_scaled=False):
     """Shape / dtype / device checks shared by the batched solve and the table-level call; fills the descriptors.
@@ -1149,7 +1196,7 @@ def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_pos
 def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, init_poses, *, stride=1, numiters=10,
                          damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False, out=None,
                          differentiable=False, guard=None, huber_delta=0.0, huber_k=0.0, return_scale=False,
-                         deterministic=None):
+                         deterministic=None, pixel_weights=None):
     """Frame-to-model tracking by projective data association for B sequences (gs_projective_icp_batch_f32: two launches
     per iteration for 8 sequences, nothing read back).  vertex / normal (B, H, W, 3): LOCAL maps of the live frames,
     depth (B, H, W), K (B, 4, 4); index (B, H, W) int64: the index image of render_map_batch at model_poses (B, 4, 4);
@@ -1175,10 +1222,21 @@ def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, ini
     every entry).
     deterministic (None | bool; it means something with differentiable=True only): True makes the backward's map
     gradients bitwise reproducible (the ordered mode of projective_icp_backward_batch), False keeps the float64 atomics,
-    None follows GRADSLAM_HIP_DETERMINISTIC_BACKWARD as read when the backward runs."""
+    None follows GRADSLAM_HIP_DETERMINISTIC_BACKWARD as read when the backward runs.
+    pixel_weights (None = none: the entry points above run, the same bits): a float32 tensor (B, H, W) on the inputs'
+    device, read at the pixel of each lattice slot (gs_projective_icp_weighted_batch_f32) -- a mask, a sensor model, a
+    learned confidence.  A pixel whose weight is not a positive finite float32 (0, negative, NaN, +inf) is masked: it is
+    not associated, not an inlier and in no median.  A used slot enters the normal equations with its pixel weight times
+    its Huber weight (one float32 product); the trace's second column is the weighted sum of squares, the inlier count
+    stays the number of used slots.  Weights of all ones give the bits of the call without weights; weight 0 on a set of
+    pixels gives the bits of depth 0 there.  Nothing is validated on the host.  A list of B entries, each None (that
+    sequence has no weights) or an (H, W) tensor, is taken as well.  With differentiable=True (the tensor form) the
+    gradient reaches the weights too (WeightedProjectiveICPFunction; which pixels are masked is a constant), bitwise
+    reproducible in both modes of the backward."""
     if not isinstance(differentiable, bool):
         raise TypeError("projective_icp: differentiable must be of type bool; but was of type {}.".format(
             type(differentiable)))
+    weights = _picp_pixel_weights("projective_icp", pixel_weights, depth)
     _picp_deterministic("projective_icp", "deterministic", deterministic)
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
     huber_delta = _picp_huber("huber_delta", huber_delta)
@@ -1192,13 +1250,19 @@ def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, ini
                    guard=guard, counts=[(m[-2], m[-1]) for m in maps], huber_delta=huber_delta, huber_k=huber_k,
                    deterministic=deterministic)
         flat = [t for m in maps for t in m[:2]]
-        res = ProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses, cfg, *flat)
+        if weights is not None and not torch.is_tensor(pixel_weights):
+            raise ValueError("projective_icp: differentiable=True takes pixel_weights as one (B, H, W) tensor")
+        if weights is not None:
+            res = WeightedProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses,
+                                                      pixel_weights, cfg, *flat)
+        else:
+            res = ProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses, cfg, *flat)
         scale = None
         if return_scale:
             scale = res[2] if huber_k > 0 else torch.full_like(res[1][..., 0], huber_delta)
         return _picp_pack(res[0], res[1], scale, return_trace, return_scale)
     return _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, numiters, damp, dist_th,
-                       dot_th, return_trace, out, None, huber_delta, huber_k, return_scale)
+                       dot_th, return_trace, out, None, huber_delta, huber_k, return_scale, weights)
 
 
 def _picp_pack(T, trace, scale, return_trace, return_scale):
@@ -1222,10 +1286,11 @@ def _picp_outputs(who, seqs, dev, out, return_trace, width, stride, numiters, da
 
 
 def _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, numiters, damp, dist_th, dot_th,
-                return_trace, out, tapes, huber_delta=0.0, huber_k=0.0, return_scale=False):
+                return_trace, out, tapes, huber_delta=0.0, huber_k=0.0, return_scale=False, weights=None):
     """the solve behind projective_icp_batch and ProjectiveICPFunction.forward; tapes: None, or the uint8 (B, tape bytes)
     buffer the taped entry fills (the same kernels and pose bits); huber_delta > 0: the robust entry; huber_k > 0: the
-    scaled entry (huber_delta its floor)"""
+    scaled entry (huber_delta its floor); weights: the entries of _picp_pixel_weights (the weighted entry, whatever the
+    thresholds) or None"""
     seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp", vertex, normal, depth, K, index, model_poses, maps,
                                            init_poses, stride, scaled=huber_k > 0)
     T, trace, prm = _picp_outputs("projective_icp", list(seqs), dev, out, return_trace, PICP_TRACE, stride, numiters,
@@ -1233,7 +1298,14 @@ def _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, 
     ptrs = None if tapes is None else \
         (_C.C.c_void_p * Bn)(*[tapes.data_ptr() + b * tapes.shape[1] for b in range(Bn)])
     scale = None
-    if huber_k > 0:
+    if weights is not None:
+        require_device(*weights, held[0])
+        held.append(weights)
+        scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale and huber_k > 0 else (None, None)
+        check(lib().gs_projective_icp_weighted_batch_f32(seqs, _picp_weight_ptrs(weights), ptrs, dptrs, Bn, H, W, prm,
+                                                         huber_delta, huber_k, stream(dev)),
+              "gs_projective_icp_weighted_batch_f32")
+    elif huber_k > 0:
         scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale else (None, None)
         check(lib().gs_projective_icp_scaled_batch_f32(seqs, ptrs, dptrs, Bn, H, W, prm, huber_k, huber_delta,
                                                        stream(dev)),
@@ -1259,7 +1331,7 @@ def projective_icp_tape_bytes(numiters):
 def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, maps, tapes, pose_bar, *, stride=1,
                                   numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, want_vertex=True,
                                   want_init=True, want_maps=None, huber_delta=0.0, huber_k=0.0, deterministic=None,
-                                  return_contributions=False):
+                                  return_contributions=False, pixel_weights=None, want_pixel_weights=False):
     """Reverse mode of projective_icp_batch (gs_projective_icp_backward_batch_f32), arguments as the forward's; tapes:
     the (B, projective_icp_tape_bytes(numiters)) uint8 buffer the taped forward filled; pose_bar (B, 4, 4): the adjoint of
     the poses.  want_maps: per sequence (points, normals) flags, default all True.  Returns (vertex_bar (B, H, W, 3) or
@@ -1276,8 +1348,17 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
     (deterministic_backward_env).  return_contributions=True (ordered mode only): a fourth result, per sequence (keys
     (numiters, nslots) int32, contrib (numiters, nslots, 6) float64): the record of every iteration as the kernel wrote it,
     keys = the slot's row or PICP_NO_KEY, contrib = its contributions to points_bar[row] and normals_bar[row] (defined
-    where the key is a row)."""
+    where the key is a row).
+    pixel_weights: the weights the taped forward ran with (as in projective_icp_batch; None: it ran without).  The
+    result then has one more entry, LAST: pixel_weights_bar (B, H, W) float32 with want_pixel_weights=True, else None
+    (nothing is allocated or computed for it).  It is accumulated per slot in float64 by the slot's own thread and rounded
+    once: bitwise reproducible, and the same bits in the atomic and the ordered mode; +0.0 off the lattice, at masked
+    pixels and at pixels never used (gs_projective_icp_weighted_backward_batch_f32)."""
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
+    _picp_flag("projective_icp_backward", "want_pixel_weights", want_pixel_weights)
+    weights = _picp_pixel_weights("projective_icp_backward", pixel_weights, depth)
+    if want_pixel_weights and weights is None:
+        raise ValueError("projective_icp_backward: want_pixel_weights=True needs the pixel_weights of the forward")
     huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_backward")
     huber_k = _picp_huber_k(huber_k, "projective_icp_backward")
     _picp_deterministic("projective_icp_backward", "deterministic", deterministic)
@@ -1301,13 +1382,19 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
     init_bar = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if want_init else None
     ws = Workspace.get(dev)
     L = lib()
-    oseqs = (_C.PicpOrderedBackwardSeq * Bn)() if ordered else None
-    bseqs = (_C.PicpBackwardSeq * Bn)() if not ordered else None
+    weighted = weights is not None
+    oseqs = (_C.PicpOrderedBackwardSeq * Bn)() if ordered or weighted else None   # (the weighted entry: both modes)
+    bseqs = (_C.PicpBackwardSeq * Bn)() if oseqs is None else None
     sizer = L.gs_projective_icp_ordered_backward_scratch_bytes if ordered else L.gs_projective_icp_backward_scratch_bytes
+    if weighted:
+        require_device(*weights, held[0])
+    if want_pixel_weights:   # (the float64 accumulator of pixel_weights_bar: 8 bytes per slot more)
+        sizer = lambda h, w, st, n: L.gs_projective_icp_weighted_backward_scratch_bytes(h, w, st, n, 1 if ordered else 0)  # noqa: E731
+    weights_bar = torch.empty((Bn, H, W), dtype=f32, device=dev) if want_pixel_weights else None
     nslots = _picp_nslots(H, W, int(stride))
     rows_out, record = [], []
     for b in range(Bn):
-        u, f = oseqs[b].base if ordered else bseqs[b], seqs[b]
+        u, f = oseqs[b].base if oseqs is not None else bseqs[b], seqs[b]
         u.vertex, u.normal, u.depth, u.K16, u.index, u.model_pose16 = f.vertex, f.normal, f.depth, f.K16, f.index, \
             f.model_pose16
         u.map = f.map
@@ -1329,12 +1416,22 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
             oseqs[b].key_out, oseqs[b].contrib_out = keys.data_ptr(), contrib.data_ptr()
             record.append((keys, contrib))
     prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
+    sort_buf = None
     if ordered:
         sort_bytes = L.gs_projective_icp_ordered_backward_sort_scratch_bytes(Bn, H, W, int(stride))
         if sort_bytes <= 0:
             raise ValueError("projective_icp_backward: the lattices of a launch group (%d x %d slots) are too many for "
                              "one sort of the ordered mode" % (min(Bn, 8), nslots))
         sort_buf = ws.bytes("picp_bwd_sort", sort_bytes) if any(any(w) for w in want_maps) else None
+    if weighted:
+        bar_ptrs = None if weights_bar is None else \
+            (_C.C.c_void_p * Bn)(*[weights_bar.data_ptr() + b * H * W * 4 for b in range(Bn)])
+        check(L.gs_projective_icp_weighted_backward_batch_f32(
+            oseqs, _picp_weight_ptrs(weights), bar_ptrs, Bn, H, W, prm, 0.0 if huber_k > 0 else huber_delta,
+            1 if huber_k > 0 else 0, 1 if ordered else 0, None if sort_buf is None else sort_buf.data_ptr(),
+            0 if sort_buf is None else int(sort_buf.numel()), stream(dev)),
+            "gs_projective_icp_weighted_backward_batch_f32")
+    elif ordered:
         check(L.gs_projective_icp_ordered_backward_batch_f32(
             oseqs, Bn, H, W, prm, 0.0 if huber_k > 0 else huber_delta, 1 if huber_k > 0 else 0,
             None if sort_buf is None else sort_buf.data_ptr(), 0 if sort_buf is None else int(sort_buf.numel()),
@@ -1348,9 +1445,8 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
     else:
         check(L.gs_projective_icp_backward_batch_f32(bseqs, Bn, H, W, prm, stream(dev)),
               "gs_projective_icp_backward_batch_f32")
-    if return_contributions:
-        return vertex_bar, rows_out, init_bar, record
-    return vertex_bar, rows_out, init_bar
+    res = (vertex_bar, rows_out, init_bar) + ((record,) if return_contributions else ())
+    return res + (weights_bar,) if weighted else res
 
 
 class ProjectiveICPFunction(torch.autograd.Function):
@@ -1408,15 +1504,68 @@ class ProjectiveICPFunction(torch.autograd.Function):
         return (vb, None, None, None, None, None, ib, None) + tuple(g for r in rows for g in r)
 
 
+class WeightedProjectiveICPFunction(torch.autograd.Function):
+    """ProjectiveICPFunction with per-pixel weights: forward = gs_projective_icp_weighted_batch_f32 with a tape, backward
+    = one call of gs_projective_icp_weighted_backward_batch_f32.  Inputs: vertex, normal, depth, K, index, model_poses,
+    init_poses, pixel_weights (B, H, W), cfg (as ProjectiveICPFunction's), then points and normals of every sequence's
+    map.  Gradients reach what ProjectiveICPFunction's reach and pixel_weights (needs_input_grad decides whether the
+    kernel is asked for it); which pixels are masked is a constant, like the association.  Returns as
+    ProjectiveICPFunction."""
+
+    @staticmethod
+    def forward(ctx, vertex, normal, depth, K, index, model_poses, init_poses, pixel_weights, cfg, *flat):
+        Bn = len(flat) // 2
+        kw = {k: cfg[k] for k in ("stride", "numiters", "damp", "dist_thresh", "angle_thresh")}
+        maps = [(flat[2 * b], flat[2 * b + 1]) + tuple(cfg["counts"][b]) for b in range(Bn)]
+        tapes = torch.empty((int(depth.shape[0]), projective_icp_tape_bytes(kw["numiters"])), dtype=torch.uint8,
+                            device=depth.device)
+        dist_th, dot_th = _picp_args(kw["stride"], kw["numiters"], kw["damp"], kw["dist_thresh"], kw["angle_thresh"])
+        huber_delta = _picp_huber("huber_delta", cfg.get("huber_delta", 0.0))
+        huber_k = _picp_huber_k(cfg.get("huber_k", 0.0))
+        weights = _picp_pixel_weights("projective_icp", pixel_weights, depth)
+        res = _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, kw["stride"], kw["numiters"],
+                          kw["damp"], dist_th, dot_th, True, None, tapes, huber_delta, huber_k, huber_k > 0, weights)
+        kw["huber_delta"], kw["huber_k"] = huber_delta, huber_k
+        kw["deterministic"] = _picp_deterministic("projective_icp", "deterministic", cfg.get("deterministic"))
+        ctx.save_for_backward(vertex, normal, depth, K, index, model_poses, tapes, pixel_weights, *flat,
+                              *[c[1] for c in cfg["counts"]])
+        ctx.kw, ctx.bounds, ctx.guard = kw, [c[0] for c in cfg["counts"]], cfg.get("guard")
+        ctx.mark_non_differentiable(*res[1:])
+        return res
+
+    @staticmethod
+    def backward(ctx, T_bar, *_constants_bar):
+        if ctx.guard is not None:
+            ctx.guard()
+        saved = ctx.saved_tensors
+        vertex, normal, depth, K, index, model_poses, tapes, pixel_weights = saved[:8]
+        Bn = len(ctx.bounds)
+        flat, n_devs = saved[8:8 + 2 * Bn], saved[8 + 2 * Bn:]
+        need = ctx.needs_input_grad
+        want_maps = [(bool(need[9 + 2 * b]), bool(need[10 + 2 * b])) for b in range(Bn)]
+        if T_bar is None or not (need[0] or need[6] or need[7] or any(any(w) for w in want_maps)):
+            return (None,) * (9 + 2 * Bn)
+        maps = [(flat[2 * b], flat[2 * b + 1], ctx.bounds[b], n_devs[b]) for b in range(Bn)]
+        vb, rows, ib, wb = projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, maps, tapes, T_bar,
+                                                         want_vertex=bool(need[0]), want_init=bool(need[6]),
+                                                         want_maps=want_maps, pixel_weights=pixel_weights,
+                                                         want_pixel_weights=bool(need[7]), **ctx.kw)
+        return (vb, None, None, None, None, None, ib, wb, None) + tuple(g for r in rows for g in r)
+
+
 def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, *, n_dev=None,
                    stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0, return_trace=False,
-                   differentiable=False, huber_delta=0.0, huber_k=0.0, return_scale=False, deterministic=None):
+                   differentiable=False, huber_delta=0.0, huber_k=0.0, return_scale=False, deterministic=None,
+                   pixel_weights=None):
     """projective_icp_batch for one sequence without the batch dimension: vertex / normal (H, W, 3), depth (H, W), K /
     model_pose / init_pose (4, 4), index (H, W) int64; n_dev: device int64[1] holding the actual row count of the map
     (map_points.shape[0] is then an upper bound).  Returns the pose (4, 4) (and the trace (numiters, 8)).
-    differentiable, huber_delta, huber_k, return_scale (the thresholds (numiters,)), deterministic: see
-    projective_icp_batch."""
+    differentiable, huber_delta, huber_k, return_scale (the thresholds (numiters,)), deterministic, pixel_weights
+    ((H, W) float32): see projective_icp_batch."""
     _picp_deterministic("projective_icp", "deterministic", deterministic)
+    if pixel_weights is not None:
+        _picp_tensors("projective_icp", (("pixel_weights", pixel_weights),))
+        pixel_weights = pixel_weights.unsqueeze(0)
     _picp_tensors("projective_icp", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                                      ("model_pose", model_pose), ("init_pose", init_pose)))
     r = projective_icp_batch(vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0), K.reshape(1, 4, 4),
@@ -1424,13 +1573,13 @@ def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_
                              init_pose.reshape(1, 4, 4), stride=stride, numiters=numiters, damp=damp,
                              dist_thresh=dist_thresh, angle_thresh=angle_thresh, return_trace=return_trace,
                              differentiable=differentiable, huber_delta=huber_delta, huber_k=huber_k,
-                             return_scale=return_scale, deterministic=deterministic)
+                             return_scale=return_scale, deterministic=deterministic, pixel_weights=pixel_weights)
     return tuple(x[0] for x in r) if isinstance(r, tuple) else r[0]
 
 
 def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points, map_normals, pose, *, n_dev=None,
                         stride=1, dist_thresh=0.1, angle_thresh=30.0, huber_delta=0.0, return_weights=False,
-                        huber_k=0.0):
+                        huber_k=0.0, pixel_weights=None):
     """ONE linearisation of the projective ICP at `pose` (gs_projective_icp_rows_f32), arguments as projective_icp.  With
     nslots = ceil(H / stride) * ceil(W / stride), slot i * ceil(W / stride) + j standing for pixel (i stride, j stride):
     ProjectiveRows(code int32 (nslots,): 0 used, 1 no depth, 2 outside the model view, 3 no (or a stale) winner, 4 too
@@ -1441,7 +1590,10 @@ def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points,
     return_weights=True returns (ProjectiveRows, weight float32 (nslots,): the weight of a used slot, 0 elsewhere).
     huber_k > 0 (gs_projective_icp_scaled_rows_f32): the threshold is max(huber_k * 1.4826 * the lower median of |b| over
     the used slots, huber_delta), derived at `pose`; return_weights=True then returns (ProjectiveRows, weight, threshold
-    float32 (1,))."""
+    float32 (1,)).
+    pixel_weights ((H, W) float32, see projective_icp_batch; gs_projective_icp_weighted_rows_f32): a masked slot has code
+    6 and row -1; sums are the weighted sums; `weight` is the total weight of a used slot, its pixel weight times its
+    Huber weight; the returned shapes are those of the call without pixel weights."""
     dist_th, dot_th = _picp_args(stride, 1, 1.0, dist_thresh, angle_thresh)
     huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_rows")
     huber_k = _picp_huber_k(huber_k, "projective_icp_rows")
@@ -1450,6 +1602,10 @@ def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points,
             type(return_weights)))
     _picp_tensors("projective_icp_rows", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K),
                                           ("index", index), ("model_pose", model_pose), ("pose", pose)))
+    if pixel_weights is not None:
+        _picp_tensors("projective_icp_rows", (("pixel_weights", pixel_weights),))
+    weights = _picp_pixel_weights("projective_icp_rows", None if pixel_weights is None else pixel_weights.unsqueeze(0),
+                                  depth.unsqueeze(0))
     seqs, held, dev, _, H, W = _picp_seqs("projective_icp_rows", vertex.unsqueeze(0), normal.unsqueeze(0),
                                           depth.unsqueeze(0), K.reshape(1, 4, 4), index.unsqueeze(0),
                                           model_pose.reshape(1, 4, 4), [(map_points, map_normals, None, n_dev)],
@@ -1458,6 +1614,17 @@ def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points,
     res = ProjectiveRows(torch.empty(ns, dtype=torch.int32, device=dev), torch.empty(ns, dtype=torch.int64, device=dev),
                          torch.empty((ns, 6), dtype=f32, device=dev), torch.empty(ns, dtype=f32, device=dev),
                          torch.empty(28, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.int64, device=dev))
+    if weights is not None:
+        require_device(*weights, held[0])
+        weight = torch.empty(ns, dtype=f32, device=dev) if return_weights else None
+        delta = torch.empty(1, dtype=f32, device=dev) if return_weights and huber_k > 0 else None
+        check(lib().gs_projective_icp_weighted_rows_f32(seqs, ptr(weights[0]), H, W, int(stride), dist_th, dot_th,
+                                                        huber_delta, huber_k, *[ptr(t) for t in res[:4]], ptr(weight),
+                                                        *[ptr(t) for t in res[4:]], ptr(delta), stream(dev)),
+              "gs_projective_icp_weighted_rows_f32")
+        if not return_weights:
+            return res
+        return (res, weight, delta) if huber_k > 0 else (res, weight)
     if huber_k > 0:
         weight, delta = (torch.empty(ns, dtype=f32, device=dev), torch.empty(1, dtype=f32, device=dev)) \
             if return_weights else (None, None)
@@ -1551,7 +1718,7 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
                                color_weight, stride=1, numiters=10, damp=1e-8, dist_thresh=0.1, angle_thresh=30.0,
                                return_trace=False, out=None, differentiable=False, huber_delta=0.0,
                                color_huber_delta=0.0, huber_k=0.0, return_scale=False, color_huber_k=0.0,
-                               return_color_scale=False):
+                               return_color_scale=False, pixel_weights=None):
     """projective_icp_batch with a photometric term (gs_projective_icp_color_batch_f32: the same two launches per
     iteration for 8 sequences, nothing read back).  The arguments of projective_icp_batch, then color (B, H, W, 3): the
     live frames' colour, and model (B, H, W, 4): model_intensity of the views' rendered colour and index images.  A slot
@@ -1575,8 +1742,11 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
     whichever of the two thresholds are estimated.  An iteration without a colour row, or whose median is 0, has
     cdelta = color_huber_delta.
     return_color_scale=True: the colour thresholds (B, numiters) float32 come after everything else in the returned
-    tuple (color_huber_k = 0: color_huber_delta in every entry)."""
+    tuple (color_huber_k = 0: color_huber_delta in every entry).
+    pixel_weights: as in projective_icp_batch (gs_projective_icp_color_weighted_batch_f32): a masked pixel has no colour
+    row either, and the colour products carry the pixel weight times the colour Huber weight."""
     _picp_refuse_differentiable(differentiable)
+    weights = _picp_pixel_weights("projective_icp_color", pixel_weights, depth)
     weight = _picp_color_weight(color_weight)
     color_huber_k = _picp_color_huber_k(color_huber_k, "projective_icp_color", weight)
     _picp_flag("projective_icp_color", "return_color_scale", return_color_scale)
@@ -1587,12 +1757,21 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
     dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
     who = "projective_icp_color"
     seqs, held, dev, Bn, H, W = _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride,
-                                           color=True, scaled=huber_k > 0, color_scaled=color_huber_k > 0)
+                                           color=True, scaled=huber_k > 0,
+                                           color_scaled=color_huber_k > 0 or (weights is not None and huber_k > 0))
     cseqs = _picp_color_seqs(who, seqs, held, Bn, H, W, color, model)
     T, trace, prm = _picp_outputs(who, [c.base for c in cseqs], dev, out, return_trace, PICP_COLOR_TRACE, stride,
                                   numiters, damp, dist_th, dot_th)
     scale = cscale = None
-    if color_huber_k > 0:
+    if weights is not None:
+        require_device(*weights, held[0])
+        scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale and huber_k > 0 else (None, None)
+        cscale, cptrs = _picp_scale_table(Bn, numiters, dev) if return_color_scale and color_huber_k > 0 else (None, None)
+        check(lib().gs_projective_icp_color_weighted_batch_f32(cseqs, _picp_weight_ptrs(weights), dptrs, cptrs, Bn, H, W,
+                                                               prm, weight, huber_delta, huber_k, color_huber_delta,
+                                                               color_huber_k, stream(dev)),
+              "gs_projective_icp_color_weighted_batch_f32")
+    elif color_huber_k > 0:
         scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale and huber_k > 0 else (None, None)
         cscale, cptrs = _picp_scale_table(Bn, numiters, dev) if return_color_scale else (None, None)
         check(lib().gs_projective_icp_color_joint_scaled_batch_f32(cseqs, dptrs, cptrs, Bn, H, W, prm, weight, huber_k,
@@ -1625,11 +1804,14 @@ def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points
                          *, color_weight, n_dev=None, stride=1, numiters=10, damp=1e-8, dist_thresh=0.1,
                          angle_thresh=30.0, return_trace=False, differentiable=False, huber_delta=0.0,
                          color_huber_delta=0.0, huber_k=0.0, return_scale=False, color_huber_k=0.0,
-                         return_color_scale=False):
+                         return_color_scale=False, pixel_weights=None):
     """projective_icp_color_batch for one sequence without the batch dimension (arguments as projective_icp, then color
     (H, W, 3) and model (H, W, 4)).  Returns the pose (4, 4) (and the trace (numiters, 9)).  huber_delta,
-    color_huber_delta, huber_k, return_scale, color_huber_k, return_color_scale (the thresholds (numiters,)): see
-    projective_icp_color_batch."""
+    color_huber_delta, huber_k, return_scale, color_huber_k, return_color_scale (the thresholds (numiters,)),
+    pixel_weights ((H, W) float32): see projective_icp_color_batch."""
+    if pixel_weights is not None:
+        _picp_tensors("projective_icp_color", (("pixel_weights", pixel_weights),))
+        pixel_weights = pixel_weights.unsqueeze(0)
     _picp_tensors("projective_icp_color", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K),
                                            ("index", index), ("model_pose", model_pose), ("init_pose", init_pose),
                                            ("color", color), ("model_intensity", model)))
@@ -1640,13 +1822,15 @@ def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points
                                    numiters=numiters, damp=damp, dist_thresh=dist_thresh, angle_thresh=angle_thresh,
                                    return_trace=return_trace, differentiable=differentiable, huber_delta=huber_delta,
                                    color_huber_delta=color_huber_delta, huber_k=huber_k, return_scale=return_scale,
-                                   color_huber_k=color_huber_k, return_color_scale=return_color_scale)
+                                   color_huber_k=color_huber_k, return_color_scale=return_color_scale,
+                                   pixel_weights=pixel_weights)
     return tuple(x[0] for x in r) if isinstance(r, tuple) else r[0]
 
 
 def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_points, map_normals, pose, color, model,
                               *, color_weight, n_dev=None, stride=1, dist_thresh=0.1, angle_thresh=30.0, huber_delta=0.0,
-                              color_huber_delta=0.0, return_weights=False, huber_k=0.0, color_huber_k=0.0):
+                              color_huber_delta=0.0, return_weights=False, huber_k=0.0, color_huber_k=0.0,
+                              pixel_weights=None):
     """ONE joint linearisation at `pose` (gs_projective_icp_color_rows_f32), arguments as projective_icp_color.
     ProjectiveColorRows: code, row, a, b as projective_icp_rows; ac (nslots, 6), bc (nslots,): the colour row, zeros
     unless colored; colored int32 (nslots,): 1 where the slot is used and its model pixel has ok = 1; sums float64 (28,):
@@ -1658,7 +1842,9 @@ def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_p
     derived at `pose` from the median of |b| over the used slots / of the colour residual |r| over the slots with a colour
     row, huber_delta / color_huber_delta its floor (see projective_icp_color_batch); return_weights=True then returns
     (ProjectiveColorRows, weight, color_weight, delta, cdelta): the two thresholds of this linearisation, float32 (1,)
-    each (the constant where its rule is off)."""
+    each (the constant where its rule is off).
+    pixel_weights ((H, W) float32, gs_projective_icp_color_weighted_rows_f32): as in projective_icp_rows; the two weight
+    tables hold the total weights (pixel weight times Huber weight); the returned shapes are those of the call without."""
     weight = _picp_color_weight(color_weight)
     huber_k = _picp_huber_k(huber_k, "projective_icp_color_rows")
     color_huber_k = _picp_color_huber_k(color_huber_k, "projective_icp_color_rows", weight)
@@ -1671,6 +1857,9 @@ def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_p
     who = "projective_icp_color_rows"
     _picp_tensors(who, (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                         ("model_pose", model_pose), ("pose", pose), ("color", color), ("model_intensity", model)))
+    if pixel_weights is not None:
+        _picp_tensors(who, (("pixel_weights", pixel_weights),))
+    weights = _picp_pixel_weights(who, None if pixel_weights is None else pixel_weights.unsqueeze(0), depth.unsqueeze(0))
     seqs, held, dev, _, H, W = _picp_seqs(who, vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0),
                                           K.reshape(1, 4, 4), index.unsqueeze(0), model_pose.reshape(1, 4, 4),
                                           [(map_points, map_normals, None, n_dev)], pose.reshape(1, 4, 4), stride,
@@ -1681,6 +1870,21 @@ def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_p
     e = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)   # noqa: E731
     res = ProjectiveColorRows(e(ns, torch.int32), e(ns, torch.int64), e((ns, 6), f32), e(ns, f32), e((ns, 6), f32),
                               e(ns, f32), e(ns, torch.int32), e(28, torch.float64), e(1, torch.int64), e(1, torch.int64))
+    if weights is not None:
+        require_device(*weights, held[0])
+        scaled = huber_k > 0 or color_huber_k > 0
+        wt = (e(ns, f32), e(ns, f32)) if return_weights else (None, None)
+        th = (torch.full((1,), huber_delta, dtype=f32, device=dev),
+              torch.full((1,), color_huber_delta, dtype=f32, device=dev)) if return_weights and scaled else (None, None)
+        check(lib().gs_projective_icp_color_weighted_rows_f32(cseqs, ptr(weights[0]), H, W, int(stride), dist_th, dot_th,
+                                                              weight, huber_delta, huber_k, color_huber_delta,
+                                                              color_huber_k, *[ptr(t) for t in res[:7]], ptr(wt[0]),
+                                                              ptr(wt[1]), *[ptr(t) for t in res[7:]], ptr(th[0]),
+                                                              ptr(th[1]), stream(dev)),
+              "gs_projective_icp_color_weighted_rows_f32")
+        if not return_weights:
+            return res
+        return (res,) + wt + th if scaled else (res,) + wt
     if huber_k > 0 or color_huber_k > 0:
         wt = (e(ns, f32), e(ns, f32)) if return_weights else (None, None)
         # (a threshold whose rule is off is the constant: the library writes the estimated ones only)

@@ -51,7 +51,13 @@ class ICPSLAM(nn.Module):
     `odom_deterministic_backward` (None by default, `odom="projicp"` only; it matters with `odom_differentiable`): True
     makes the map gradients of the projective ICP's backward bitwise reproducible, False keeps the float64 atomics, None
     follows GRADSLAM_HIP_DETERMINISTIC_BACKWARD when the backward runs
-    (`ProjectiveICPOdometryProvider(deterministic_backward=...)`)."""
+    (`ProjectiveICPOdometryProvider(deterministic_backward=...)`).
+
+    `odom_pixel_weights` (None by default, `odom="projicp"` only): a callable that takes the live `RGBDImages` the solve
+    sees (the filtered copy with `depth_filter`) and returns per-pixel weights (B, H, W) or (B, 1, H, W) for the
+    projective ICP (`ProjectiveICPOdometryProvider(pixel_weights=...)`): a mask, a sensor model
+    (`odometry.axial_noise_weights`), a learned confidence.  It is called once per localisation; the map update does not
+    see it.  With `odom_differentiable` its output stays on the autograd tape."""
 
     def __init__(self, *, odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0,
@@ -60,9 +66,15 @@ class ICPSLAM(nn.Module):
                  odom_differentiable: bool = False, color_weight: Union[float, int] = 0.0,
                  huber_delta: Union[float, int] = 0.0, color_huber_delta: Union[float, int] = 0.0,
                  huber_k: Union[float, int] = 0.0, color_huber_k: Union[float, int] = 0.0,
-                 odom_deterministic_backward: Optional[bool] = None):
+                 odom_deterministic_backward: Optional[bool] = None, odom_pixel_weights=None):
         super().__init__()
         from .. import ops
+        if odom_pixel_weights is not None and not callable(odom_pixel_weights):
+            raise TypeError("odom_pixel_weights must be None or a callable (live frame -> weights); but was of type "
+                            "{}.".format(type(odom_pixel_weights)))
+        if odom_pixel_weights is not None and odom != "projicp":
+            raise ValueError("odom_pixel_weights are the per-pixel weights of odom='projicp' (got odom={!r})".format(odom))
+        # (not an attribute of the module: a weight network is registered by whoever owns it, the provider holds it)
         ops._picp_deterministic(type(self).__name__, "odom_deterministic_backward", odom_deterministic_backward)
         if odom_deterministic_backward is not None and odom != "projicp":
             raise ValueError("odom_deterministic_backward is a switch of odom='projicp' (got odom={!r}): the backward of "
@@ -111,7 +123,8 @@ class ICPSLAM(nn.Module):
                                                      color_weight=color_weight, huber_delta=huber_delta,
                                                      color_huber_delta=color_huber_delta, huber_k=huber_k,
                                                      color_huber_k=color_huber_k,
-                                                     deterministic_backward=odom_deterministic_backward)
+                                                     deterministic_backward=odom_deterministic_backward,
+                                                     pixel_weights=odom_pixel_weights)
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio

@@ -45,7 +45,8 @@ class PointFusion(ICPSLAM):
     `huber_delta`, `color_huber_delta`: as in `ICPSLAM` (the Huber thresholds of `odom="projicp"`).
     `huber_k`: as in `ICPSLAM` (the Huber threshold of `odom="projicp"` from the residuals' median).
     `color_huber_k`: as in `ICPSLAM` (the colour Huber threshold of `odom="projicp"` from the colour residuals' median).
-    `odom_deterministic_backward`: as in `ICPSLAM` (bitwise reproducible map gradients of `odom="projicp"`'s backward)."""
+    `odom_deterministic_backward`: as in `ICPSLAM` (bitwise reproducible map gradients of `odom="projicp"`'s backward).
+    `odom_pixel_weights`: as in `ICPSLAM` (per-pixel weights of `odom="projicp"` from a callable on the live frame)."""
 
     def __init__(self, *, odom: str = "gradicp", dist_th: Union[float, int] = 0.05, angle_th: Union[float, int] = 20,
                  sigma: Union[float, int] = 0.6, dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
@@ -58,12 +59,13 @@ class PointFusion(ICPSLAM):
                  huber_k: Union[float, int] = 0.0, carve_margin: Union[float, int, None] = None,
                  carve_window: int = 1, carve_every: int = 1, color_huber_k: Union[float, int] = 0.0,
                  voxel_size: Union[float, int, None] = None, voxel_every: int = 1,
-                 odom_deterministic_backward: Optional[bool] = None):
+                 odom_deterministic_backward: Optional[bool] = None, odom_pixel_weights=None):
         super().__init__(odom=odom, dsratio=dsratio, numiters=numiters, damp=damp, dist_thresh=dist_thresh,
                          lambda_max=lambda_max, B=B, B2=B2, nu=nu, device=device, depth_filter=depth_filter,
                          odom_differentiable=odom_differentiable, color_weight=color_weight, huber_delta=huber_delta,
                          color_huber_delta=color_huber_delta, huber_k=huber_k, color_huber_k=color_huber_k,
-                         odom_deterministic_backward=odom_deterministic_backward)
+                         odom_deterministic_backward=odom_deterministic_backward,
+                         odom_pixel_weights=odom_pixel_weights)
         if not (isinstance(dist_th, float) or isinstance(dist_th, int)):
             raise TypeError("Distance threshold must be of type float or int; but was of type {}.".format(
                 type(dist_th)))

@@ -1058,6 +1058,73 @@ GS_API int gs_projective_icp_color_joint_scaled_rows_f32(const gs_picp_color_seq
                                                          int64_t* count, int64_t* color_count, float* delta_out,
                                                          float* cdelta_out, void* stream);
 
+/* ------------------------------------------------------------------ projective ICP: per-pixel weights ------
+ * Opt-in (additions only; the ABI version, every struct, every signature and every *_scratch_bytes function above stay):
+ * one float32 image of pixel weights (H, W) per sequence, read at the pixel p of each lattice slot: a mask, a sensor
+ * model (1 / sigma^2(z)), a learned confidence.  The weights travel as a host array of B device pointers next to the
+ * sequences; a NULL entry: that sequence has no weights (every wp = 1).  The rule, per slot with wp = weights[p]:
+ *   code 1  unless depth[p] > 0, as ever
+ *   code 6  ("masked") unless wp > 0 && wp < +inf in float32: zero, negative, NaN and +inf all mask.  Nothing is validated
+ *           on the host and nothing is read back.  A masked slot is not associated, not counted as an inlier and not part
+ *           of any median; it contributes +0.0 to every term and has no colour row
+ *   codes 2 .. 5 as ever
+ *   a used slot's total weight is wt = wp * h, ONE float32 product, h the Huber weight of its raw residual b (1.0f
+ *   without a threshold; the clip flag is taken from the unweighted float32 b); every one of its 28 terms is
+ *   (double)wt * ((double)x * (double)y); in the joint solve the colour products carry wp * wc in the same way.
+ * The inlier count stays the integer number of used slots; the sum of squares is the weighted one; with huber_k /
+ * color_huber_k the median is that of the unweighted |b| / |r| over the used / coloured slots, masked slots excluded.
+ * The reduction order, the finish, the solve, the update and "no inlier keeps the pose bits" are untouched.  Hence, bit
+ * for bit: weights of all 1.0f give the pose, trace, thresholds and tape of the unweighted entries, and weight 0 on a
+ * set of pixels gives what depth 0 on those pixels gives (the code tables differ in 6 against 1).
+ * Thresholds: huber_k > 0 switches the median rule on with huber_delta as its floor, else huber_delta is the constant
+ * threshold (0: none); color_huber_k / color_huber_delta alike.  scratch: that of the unweighted entry with the same
+ * thresholds (gs_projective_icp_scaled_scratch_bytes with huber_k > 0, else gs_projective_icp_scratch_bytes; the colour
+ * entries: gs_projective_icp_color_joint_scaled_scratch_bytes with either rule on, else
+ * gs_projective_icp_color_scratch_bytes).  One 4-byte load per slot on top of the robust kernels' work.
+ * gs_projective_icp_weighted_batch_f32: tapes_host / deltas_host as in gs_projective_icp_scaled_batch_f32 (either NULL).
+ * gs_projective_icp_weighted_rows_f32: `weight` (nslots) receives wt of a used slot, 0 elsewhere; delta_out is written
+ * with huber_k > 0 only.  gs_projective_icp_color_weighted_batch_f32 / _rows_f32: the joint solve; color_weight_out
+ * receives wp * wc.
+ * gs_projective_icp_weighted_backward_batch_f32: the reverse-mode pass for a tape of the weighted forward, atomic
+ * (ordered = 0: key_out / contrib_out and the sort scratch are not read) or ordered, for the three tapes as in
+ * gs_projective_icp_ordered_backward_batch_f32 (huber_delta, taped_scale).  With W = wp h: A = sum W a a^T, g = sum W a b;
+ * per used slot and iteration, e = u . a, c = xi . a:  weights_bar[p] += h e (b - c);  ab is multiplied by wp h;  the
+ * residual's adjoint is e wp (h + h' (b - c)).  Which slots are masked is a constant of the pass.  weights_bar_host: NULL,
+ * or per sequence a device image (H, W) or NULL; it is accumulated in float64 per slot by the slot's own thread and rounded
+ * once: bitwise reproducible, the same bits in both modes; +0.0 off the lattice, for masked slots and slots never used.
+ * scratch per sequence: gs_projective_icp_weighted_backward_scratch_bytes(H, W, stride, n_map, ordered) (the mode's
+ * scratch plus 8 bytes per slot) for a sequence whose weights_bar is asked for, else the mode's own scratch: an output
+ * that is not asked for costs nothing.  Every argument is checked before the first HIP call; a NULL weights array is refused. */
+GS_API int gs_projective_icp_weighted_batch_f32(const gs_picp_seq* seqs_host, const float* const* weights_host,
+                                                void* const* tapes_host, float* const* deltas_host, int B, int H, int W,
+                                                const gs_picp_params* params_host, float huber_delta, float huber_k,
+                                                void* stream);
+GS_API int gs_projective_icp_weighted_rows_f32(const gs_picp_seq* seq_host, const float* weights, int H, int W, int stride,
+                                               float dist_th, float dot_th, float huber_delta, float huber_k,
+                                               int32_t* code, int64_t* row, float* a6, float* b, float* weight,
+                                               double* sums28, int64_t* count, float* delta_out, void* stream);
+GS_API int gs_projective_icp_color_weighted_batch_f32(const gs_picp_color_seq* seqs_host,
+                                                      const float* const* weights_host, float* const* deltas_host,
+                                                      float* const* cdeltas_host, int B, int H, int W,
+                                                      const gs_picp_params* params_host, float color_weight,
+                                                      float huber_delta, float huber_k, float color_huber_delta,
+                                                      float color_huber_k, void* stream);
+GS_API int gs_projective_icp_color_weighted_rows_f32(const gs_picp_color_seq* seq_host, const float* weights, int H, int W,
+                                                     int stride, float dist_th, float dot_th, float color_weight,
+                                                     float huber_delta, float huber_k, float color_huber_delta,
+                                                     float color_huber_k, int32_t* code, int64_t* row, float* a6,
+                                                     float* b, float* ac6, float* bc, int32_t* colored, float* weight,
+                                                     float* color_weight_out, double* sums28, int64_t* count,
+                                                     int64_t* color_count, float* delta_out, float* cdelta_out,
+                                                     void* stream);
+GS_API int64_t gs_projective_icp_weighted_backward_scratch_bytes(int H, int W, int stride, int64_t n_map, int ordered);
+GS_API int gs_projective_icp_weighted_backward_batch_f32(const gs_picp_ordered_backward_seq* seqs_host,
+                                                         const float* const* weights_host,
+                                                         float* const* weights_bar_host, int B, int H, int W,
+                                                         const gs_picp_params* params_host, float huber_delta,
+                                                         int taped_scale, int ordered, void* sort_scratch,
+                                                         int64_t sort_scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

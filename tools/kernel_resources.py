@@ -2,6 +2,11 @@
 kernel.  Runs without a GPU (cross-compilation).
 
     python tools/kernel_resources.py gs_icp_loop.hip [substring of the kernel name ...]
+
+The per-pixel-weight instances of the projective ICP are the kernels named gs_weighted_* / gs_ordered_weighted_* of
+gs_picp.hip, gs_picp_color.hip, gs_picp_scale.hip and gs_picp_bwd.hip:
+
+    python tools/kernel_resources.py gs_picp_bwd.hip gs_weighted_ gs_ordered_weighted_
 """
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -3,7 +3,7 @@ frame loop gains or loses with it, and what a launch of it costs (needs the MI35
 
     python tools/projective_icp_profile.py [--out FILE] [--only localize|slam|launches|backward] [--steps K] [--color-weight W]
                                            [--huber-delta D] [--color-huber-delta C] [--huber-k K] [--color-huber-k K]
-                                           [--parent-lib SO]
+                                           [--parent-lib SO] [--pixel-weights ones|mask]
 
 1. One localisation.  640x480 frames of the benchmark's synthetic sequences, the map fused from the first 10 frames under
    the ground-truth poses, frame 10 localised from the pose of frame 9; B = 1 and B = 8.
@@ -55,6 +55,14 @@ _bothscaled.  Every scaled variant has the same four launches per iteration.
    step add; at B = 8 it is set next to 8 x the B = 1 figure: one sort per launch group must cost less than the sorts of
    8 separate sequences.  With --parent-lib the atomic mode of that build (its gs_projective_icp_backward_batch_f32
    behind this tree's Python layer) alternates with this tree's: the default path must not have got slower.
+
+--pixel-weights ones|mask adds the solve with per-pixel weights (ops.projective_icp_batch(pixel_weights=...), the
+gs_weighted_* kernels) to part 3 and to the backward, alternating in the same process with the unweighted solves of the
+same tree (and, with --parent-lib, with the parent's robust solve): solve_weighted_10it / _40it with the thresholds given
+(--huber-delta, and with --huber-k also solve_weighted_scaled_*), us_per_iteration_weighted next to
+us_per_iteration_robust, and in the backward weighted_atomic / weighted_ordered (pixel_weights_bar asked for) next to
+atomic / ordered.  ones: every weight 1.0 (the unweighted solve's bits); mask: 1.0 with the centre block of 15 % of the
+image 0 (those slots are masked: they stop at the weight).
 
 --parent-lib SO (needs --huber-delta, or --only backward): the libgradslam_hip.so of another build of this project, e.g. of the parent commit
 (same ABI version), loaded next to this tree's.  Part 3 then also times ITS gs_projective_icp_robust_batch_f32 on the
@@ -193,11 +201,20 @@ def load_parent(path):
     return parent
 
 
+def pixel_weights_of(torch, which, B):
+    """the weight images (B, H, W) of --pixel-weights"""
+    w = torch.ones((B, H, W), dtype=torch.float32, device="cuda")
+    if which == "mask":     # 186 x 248 of 480 x 640: 15 % of the image
+        w[:, 147:333, 196:444] = 0
+    return w
+
+
 def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta=0.0, color_huber_delta=0.0,
-                 huber_k=0.0, parent=None, color_huber_k=0.0):
+                 huber_k=0.0, parent=None, color_huber_k=0.0, pixel_weights=None):
     out = []
     for B in (1, 8):
         pc, live, prev, _ = scene(torch, gs, B)
+        wts = pixel_weights_of(torch, pixel_weights, B) if pixel_weights else None
         fr = live.to_channels_last()
         K = fr.intrinsics[:, 0].contiguous()
         maps = [(pc._buf["points"][b], None, None, None) + tuple(pc._count_of(b)) for b in range(B)]
@@ -229,6 +246,13 @@ def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta
             if huber_k > 0:
                 fns.update({"solve_scaled_%dit" % n: (lambda n=n: ops.projective_icp_batch(
                     *args, stride=stride, numiters=n, huber_delta=huber_delta, huber_k=huber_k)) for n in (10, 40)})
+            if wts is not None:
+                fns.update({"solve_weighted_%dit" % n: (lambda n=n: ops.projective_icp_batch(
+                    *args, stride=stride, numiters=n, huber_delta=huber_delta, pixel_weights=wts)) for n in (10, 40)})
+                if huber_k > 0:
+                    fns.update({"solve_weighted_scaled_%dit" % n: (lambda n=n: ops.projective_icp_batch(
+                        *args, stride=stride, numiters=n, huber_delta=huber_delta, huber_k=huber_k, pixel_weights=wts))
+                        for n in (10, 40)})
             robust_color = color_weight > 0 and (huber_delta > 0 or color_huber_delta > 0)
             if robust_color:
                 fns.update({"solve_color_robust_%dit" % n: (lambda n=n: ops.projective_icp_color_batch(
@@ -273,6 +297,16 @@ def launch_times(torch, gs, ops, reps=5, rounds=7, color_weight=0.0, huber_delta
                 rec["huber_k"] = huber_k
                 rec["us_per_iteration_scaled"] = \
                     (t["solve_scaled_40it"]["median_ms"] - t["solve_scaled_10it"]["median_ms"]) / 30 * 1e3
+            if wts is not None:
+                rec["pixel_weights"] = pixel_weights
+                rec["us_per_iteration_weighted"] = \
+                    (t["solve_weighted_40it"]["median_ms"] - t["solve_weighted_10it"]["median_ms"]) / 30 * 1e3
+                base = rec.get("us_per_iteration_robust_parent", rec.get("us_per_iteration_robust", rec["us_per_iteration"]))
+                rec["weighted_over_" + ("robust_parent" if parent is not None else "robust" if huber_delta > 0 else "plain")] = \
+                    rec["us_per_iteration_weighted"] / base
+                if huber_k > 0:
+                    rec["us_per_iteration_weighted_scaled"] = (t["solve_weighted_scaled_40it"]["median_ms"] -
+                                                               t["solve_weighted_scaled_10it"]["median_ms"]) / 30 * 1e3
             if robust_color:
                 rec["color_huber_delta"] = color_huber_delta
                 rec["us_per_iteration_color_robust"] = \
@@ -296,10 +330,11 @@ class _BackwardOf:
         return getattr(self._parent if name == "gs_projective_icp_backward_batch_f32" else self._own, name)
 
 
-def backward_times(torch, gs, ops, reps=5, rounds=7, parent=None):
+def backward_times(torch, gs, ops, reps=5, rounds=7, parent=None, pixel_weights=None):
     out = []
     for B in (1, 8):
         pc, live, prev, _ = scene(torch, gs, B)
+        wts = pixel_weights_of(torch, pixel_weights, B) if pixel_weights else None
         fr = live.to_channels_last()
         K = fr.intrinsics[:, 0].contiguous()
         maps = [(pc._buf["points"][b], None, None, None) + tuple(pc._count_of(b)) for b in range(B)]
@@ -333,10 +368,22 @@ def backward_times(torch, gs, ops, reps=5, rounds=7, parent=None):
             fns = {"atomic": lambda: call(False), "ordered": lambda: call(True)}
             if parent is not None:
                 fns = {"atomic": via(None, False), "ordered": via(None, True), "atomic_parent": via(parent, False)}
+            if wts is not None:   # the weighted backward on the weighted forward's tape, pixel_weights_bar asked for
+                wtapes = torch.empty_like(tapes)
+                ops._picp_solve(*args, prev[:, 0], stride, numiters, 1e-8, dist_th, dot_th, True, None, wtapes, 0.0, 0.0,
+                                False, list(wts))
+
+                def wcall(deterministic):
+                    return ops.projective_icp_backward_batch(*args, wtapes, pose_bar, stride=stride, numiters=numiters,
+                                                             deterministic=deterministic, pixel_weights=wts,
+                                                             want_pixel_weights=True)
+                fns["weighted_atomic"] = lambda: wcall(False)
+                fns["weighted_ordered"] = lambda: wcall(True)
             res = {k: fn() for k, fn in fns.items()}
             torch.cuda.synchronize()
             same = {k: all(torch.equal(a, b) for a, b in ((res[k][0], res["atomic"][0]), (res[k][2], res["atomic"][2])))
                     for k in fns}                                  # vertex_bar and init_pose_bar: the same bits
+            # (with --pixel-weights mask the weighted variants solve another problem: their entries then read False)
             again = call(True)
             ordered_repeats = all(torch.equal(a, b) for x, y in zip(res["ordered"][1], again[1]) for a, b in zip(x, y))
             del res, again
@@ -349,6 +396,10 @@ def backward_times(torch, gs, ops, reps=5, rounds=7, parent=None):
                    "ordered_over_atomic": t["ordered"]["median_ms"] / t["atomic"]["median_ms"],
                    "ordered_extra_ms": t["ordered"]["median_ms"] - t["atomic"]["median_ms"],
                    "vertex_and_init_bits_equal_atomic": same, "ordered_map_gradients_repeat_bit_for_bit": ordered_repeats}
+            if wts is not None:
+                rec["pixel_weights"] = pixel_weights
+                rec["weighted_atomic_over_atomic"] = t["weighted_atomic"]["median_ms"] / t["atomic"]["median_ms"]
+                rec["weighted_ordered_over_ordered"] = t["weighted_ordered"]["median_ms"] / t["ordered"]["median_ms"]
             if parent is not None:
                 a, b = t["atomic"], t["atomic_parent"]
                 rec["atomic_over_parent"] = a["median_ms"] / b["median_ms"]
@@ -419,6 +470,9 @@ def main():
                     help="> 0 (needs --color-weight): part 3 also times the joint solve with the colour Huber threshold "
                          "from the colour residuals' median (--color-huber-delta is then its floor), next to a constant "
                          "colour threshold and, with --huber-k, next to the geometric rule alone and both rules")
+    ap.add_argument("--pixel-weights", choices=("ones", "mask"), default=None,
+                    help="also time the solve with per-pixel weights and its backward (part 3 and --only backward), next "
+                         "to the unweighted ones of the same tree")
     args = ap.parse_args()
     if not (args.color_weight >= 0 and args.color_weight < float("inf")):
         ap.error("--color-weight must be finite and not negative")
@@ -446,9 +500,11 @@ def main():
     if args.only in (None, "launches"):
         out["launches"] = launch_times(torch, gs, ops, color_weight=args.color_weight, huber_delta=args.huber_delta,
                                        color_huber_delta=args.color_huber_delta, huber_k=args.huber_k,
-                                       color_huber_k=args.color_huber_k, parent=load_parent(args.parent_lib) if args.parent_lib else None)
+                                       color_huber_k=args.color_huber_k, parent=load_parent(args.parent_lib) if args.parent_lib else None,
+                                       pixel_weights=args.pixel_weights)
     if args.only == "backward":
-        out["backward"] = backward_times(torch, gs, ops, parent=load_parent(args.parent_lib) if args.parent_lib else None)
+        out["backward"] = backward_times(torch, gs, ops, parent=load_parent(args.parent_lib) if args.parent_lib else None,
+                                         pixel_weights=args.pixel_weights)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
