@@ -104,38 +104,41 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                  color_huber_k: Union[float, int] = 0.0, deterministic_backward: Optional[bool] = None,
                  pixel_weights: Optional[Callable] = None):
         from .. import ops
+        who = "ProjectiveICPOdometryProvider"
         if pixel_weights is not None and not callable(pixel_weights):
             raise TypeError("pixel_weights must be None or a callable (live frame -> weights); but was of type "
                             "{}.".format(type(pixel_weights)))
-        self.pixel_weights = pixel_weights   # (carried next to _kwargs(), like color_weight)
+        self.pixel_weights = pixel_weights
         if not isinstance(differentiable, bool):
             raise TypeError("differentiable must be of type bool; but was of type {}.".format(type(differentiable)))
-        ops._picp_deterministic("ProjectiveICPOdometryProvider", "deterministic_backward", deterministic_backward)
-        self.deterministic_backward = deterministic_backward   # (carried next to _kwargs(), like color_weight)
-        ops._picp_args(1 if stride is None else stride, numiters, damp, dist_thresh, angle_thresh)
-        ops._picp_color_weight(color_weight)
+        ops._picp_deterministic(who, "deterministic_backward", deterministic_backward)
+        opt = ops._picp_options(who, geometry=(1 if stride is None else stride, numiters, damp, dist_thresh, angle_thresh),
+                                color_weight=color_weight)
         if color_weight > 0 and differentiable:
             raise ValueError("color_weight > 0 cannot be combined with differentiable=True: the colour term has no "
                              "backward pass yet")
-        ops._picp_huber("huber_delta", huber_delta, "ProjectiveICPOdometryProvider")
-        ops._picp_huber("color_huber_delta", color_huber_delta, "ProjectiveICPOdometryProvider")
+        opt = ops._picp_options(who, opt, huber_delta=huber_delta, color_huber_delta=color_huber_delta)
         if color_huber_delta > 0 and not color_weight > 0:
             raise ValueError("color_huber_delta > 0 needs color_weight > 0: it is the Huber threshold of the colour term")
-        ops._picp_huber_k(huber_k, "ProjectiveICPOdometryProvider")
-        self.huber_k = huber_k
-        ops._picp_color_huber_k(color_huber_k, "ProjectiveICPOdometryProvider")
+        opt = ops._picp_options(who, opt, huber_k=huber_k, color_huber_k=color_huber_k)
         if color_huber_k > 0 and not color_weight > 0:
             raise ValueError("color_huber_k > 0 needs color_weight > 0: it estimates the Huber threshold of the colour "
                              "term")
-        self.color_huber_k = color_huber_k
-        self.color_weight = color_weight   # (carried next to _kwargs(): the plain solve does not take it)
-        self.huber_delta = huber_delta     # (as are the Huber thresholds)
-        self.color_huber_delta = color_huber_delta
+        # What every solve of localize runs with, fixed here: the validated record.  The attributes below are the values
+        # as they were given, for the SLAM drivers and callers to read (the first five make _kwargs()); assigning to
+        # one of them after construction does NOT reach localize -- build a new provider instead.
+        self.options = opt._replace(deterministic=deterministic_backward)
         self.numiters = numiters
         self.damp = damp
         self.dist_thresh = dist_thresh
         self.angle_thresh = angle_thresh
         self.stride = stride
+        self.color_weight = color_weight
+        self.huber_delta = huber_delta
+        self.color_huber_delta = color_huber_delta
+        self.huber_k = huber_k
+        self.color_huber_k = color_huber_k
+        self.deterministic_backward = deterministic_backward
         self.min_confidence = min_confidence
         self.radius = radius
         self.differentiable = differentiable
@@ -185,14 +188,20 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                                                                          tuple(prev_poses.shape)))
         poses = prev_poses.reshape(B, 4, 4).contiguous().float()
         K = fr.intrinsics[:, 0].contiguous().float()
-        # the index image is all the solve reads of the view: no colour, normal or confidence image is rendered
         maps = pointclouds._map_rows(("points", "normals") + (("features",) if self.min_confidence > 0 else ()))
         weights = self._weights(live_frame, B, H, W)
-        if self.differentiable:
-            # the render stays off the tape (the winners are constants): it sees detached tensors and does not warn
-            view = ops.render_map_batch([m._replace(points=m.points.detach(), normals=None) for m in maps],
-                                        poses.detach().view(B, 1, 4, 4), K, H, W, radius=self.radius,
-                                        min_confidence=self.min_confidence)
+        # The model view, rendered once.  The index image is all the geometric solve reads of it: no colour, normal or
+        # confidence image is rendered.  The joint solve reads the view's colour image too.  On the tape the render stays
+        # off it (the winners are constants): it sees detached tensors and does not warn
+        colour, taped = self.options.color_weight > 0, self.differentiable
+        view_maps, view_poses, guard = [m._replace(normals=None) for m in maps], poses, None
+        if colour:
+            colors = pointclouds._buf["colors"]
+            if colors is None or any(c is None for c in colors):
+                raise ValueError("color_weight > 0 needs a map with colours")
+            view_maps = [m._replace(colors=colors[b]) for b, m in enumerate(view_maps)]
+        elif taped:
+            view_maps, view_poses = [m._replace(points=m.points.detach()) for m in view_maps], poses.detach()
             key = pointclouds._rewrites()
 
             def guard():
@@ -201,33 +210,16 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                        "backward pass: the saved association no longer belongs to the map rows (run "
                                        "backward before the next in-place PointFusion.step or prune_, or keep the map "
                                        "update on the autograd tape)")
-            T = ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
-                                         view.index[:, 0], poses.detach(), maps, poses, differentiable=True, guard=guard,
-                                         huber_delta=self.huber_delta, huber_k=self.huber_k,
-                                         deterministic=self.deterministic_backward, pixel_weights=weights,
-                                         **self._kwargs())
-            return T.unsqueeze(1)
+        view = ops.render_map_batch(view_maps, view_poses.view(B, 1, 4, 4), K, H, W, radius=self.radius,
+                                    min_confidence=self.min_confidence)
+        # the joint solve: the view's intensity image and the live colour next to the geometric solve's inputs
+        color, model = (fr.rgb_image[:, 0], ops.model_intensity(view.color[:, 0], view.index[:, 0])) if colour \
+            else (None, None)
+        args = (fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K, view.index[:, 0], view_poses,
+                maps, poses)
+        entries = ops._picp_pixel_weights("projective_icp_color" if colour else "projective_icp", weights, args[2])
+        if taped:
+            return ops._picp_taped(self.options, *args, weights, entries, guard=guard).unsqueeze(1)
         out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=poses.device)
-        if self.color_weight > 0:
-            # the joint solve: the view's colour image next to the index image, their intensity image, the live colour
-            colors = pointclouds._buf["colors"]
-            if colors is None or any(c is None for c in colors):
-                raise ValueError("color_weight > 0 needs a map with colours")
-            view = ops.render_map_batch([m._replace(normals=None, colors=colors[b]) for b, m in enumerate(maps)],
-                                        poses.view(B, 1, 4, 4), K, H, W, radius=self.radius,
-                                        min_confidence=self.min_confidence)
-            model = ops.model_intensity(view.color[:, 0], view.index[:, 0])
-            ops.projective_icp_color_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
-                                           view.index[:, 0], poses, maps, poses, fr.rgb_image[:, 0], model,
-                                           color_weight=self.color_weight, out=out.view(B, 4, 4),
-                                           huber_delta=self.huber_delta, color_huber_delta=self.color_huber_delta,
-                                           huber_k=self.huber_k, color_huber_k=self.color_huber_k, pixel_weights=weights,
-                                           **self._kwargs())
-            return out
-        view = ops.render_map_batch([m._replace(normals=None) for m in maps], poses.view(B, 1, 4, 4), K, H, W,
-                                    radius=self.radius, min_confidence=self.min_confidence)
-        ops.projective_icp_batch(fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K,
-                                 view.index[:, 0], poses, maps, poses, out=out.view(B, 4, 4),
-                                 huber_delta=self.huber_delta, huber_k=self.huber_k, pixel_weights=weights,
-                                 **self._kwargs())
+        ops._picp_solve(self.options, *args, color=color, model=model, out=out.view(B, 4, 4), weights=entries)
         return out

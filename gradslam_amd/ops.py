@@ -2,6 +2,7 @@
 devices, allocates outputs with torch, and enqueues the HIP kernels on torch's current stream.
 Nothing here computes with torch: arithmetic happens in libgradslam_hip.so or not at all."""
 import collections
+import math
 import os
 
 import torch
@@ -981,7 +982,6 @@ PICP_TRACE = 8
 
 def _picp_args(stride, numiters, damp, dist_thresh, angle_thresh):
     """the value checks of the projective ICP; returns (dist_th, dot_th) as the Python doubles the library casts"""
-    import math
     for name, val in (("stride", stride), ("numiters", numiters)):
         if isinstance(val, bool) or not isinstance(val, int):
             raise TypeError("projective_icp: {} must be of type int; but was of type {}.".format(name, type(val)))
@@ -999,42 +999,38 @@ def _picp_args(stride, numiters, damp, dist_thresh, angle_thresh):
     return float(dist_thresh), math.cos((angle_thresh * math.pi) / 180)
 
 
+def _picp_number(who, name, val):
+    """the value check of a Huber threshold (huber_delta: metres, color_huber_delta: intensity units), of a median rule's
+    constant (huber_k, color_huber_k) and of the colour weight: a finite number >= 0, not a bool; 0 = off"""
+    if isinstance(val, bool) or not isinstance(val, (float, int)):
+        raise TypeError("{}: {} must be of type float or int; but was of type {}.".format(who, name, type(val)))
+    if not (math.isfinite(val) and val >= 0):
+        raise ValueError("{}: {} ({}) must be finite and not negative.".format(who, name, val))
+    return float(val)
+
+
 def _picp_huber(name, delta, who="projective_icp"):
-    """the value check of a Huber threshold (huber_delta: metres, color_huber_delta: intensity units): a finite number
-    >= 0, 0 = off"""
-    import math
-    if isinstance(delta, bool) or not isinstance(delta, (float, int)):
-        raise TypeError("{}: {} must be of type float or int; but was of type {}.".format(who, name, type(delta)))
-    if not (math.isfinite(delta) and delta >= 0):
-        raise ValueError("{}: {} ({}) must be finite and not negative.".format(who, name, delta))
-    return float(delta)
+    return _picp_number(who, name, delta)
 
 
 def _picp_huber_k(huber_k, who="projective_icp"):
-    """the value check of the median rule's constant (delta = huber_k * 1.4826 * median|b| per iteration): a finite
-    number >= 0, 0 = off (huber_delta is then the constant threshold it always was)"""
-    import math
-    if isinstance(huber_k, bool) or not isinstance(huber_k, (float, int)):
-        raise TypeError("{}: huber_k must be of type float or int; but was of type {}.".format(who, type(huber_k)))
-    if not (math.isfinite(huber_k) and huber_k >= 0):
-        raise ValueError("{}: huber_k ({}) must be finite and not negative.".format(who, huber_k))
-    return float(huber_k)
+    """delta = huber_k * 1.4826 * median|b| per iteration; 0: huber_delta is the constant threshold it always was"""
+    return _picp_number(who, "huber_k", huber_k)
 
 
 def _picp_color_huber_k(color_huber_k, who, weight=None):
-    """the value check of the colour residual's median-rule constant (cdelta = color_huber_k * 1.4826 * median|r| per
-    iteration): a finite number >= 0, 0 = off (color_huber_delta is then the constant threshold it always was); weight:
-    the colour weight of the call, without which there is no colour residual to estimate from"""
-    import math
-    if isinstance(color_huber_k, bool) or not isinstance(color_huber_k, (float, int)):
-        raise TypeError("{}: color_huber_k must be of type float or int; but was of type {}.".format(
-            who, type(color_huber_k)))
-    if not (math.isfinite(color_huber_k) and color_huber_k >= 0):
-        raise ValueError("{}: color_huber_k ({}) must be finite and not negative.".format(who, color_huber_k))
+    """cdelta = color_huber_k * 1.4826 * median|r| per iteration; 0: color_huber_delta is the constant threshold it always
+    was; weight: the colour weight of the call, without which there is no colour residual to estimate from"""
+    color_huber_k = _picp_number(who, "color_huber_k", color_huber_k)
     if color_huber_k > 0 and weight is not None and not weight > 0:
         raise ValueError("{}: color_huber_k > 0 needs color_weight > 0: it estimates the Huber threshold of the colour "
                          "term".format(who))
-    return float(color_huber_k)
+    return color_huber_k
+
+
+def _picp_color_weight(color_weight):
+    """the colour weight (metres per intensity unit)"""
+    return _picp_number("projective_icp_color", "color_weight", color_weight)
 
 
 def _picp_flag(who, name, val):
@@ -1048,6 +1044,92 @@ def _picp_deterministic(who, name, val):
     if val is not None and not isinstance(val, bool):
         raise TypeError("{}: {} must be None or of type bool; but was of type {}.".format(who, name, type(val)))
     return val
+
+
+PicpOptions = collections.namedtuple(
+    "PicpOptions", ["stride", "numiters", "damp", "dist_th", "dot_th", "huber_delta", "huber_k", "color_weight",
+                    "color_huber_delta", "color_huber_k", "deterministic"],
+    defaults=(1, 1, 1.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, None))
+PicpOptions.__doc__ = """The validated options of a projective ICP call, as every layer below the public functions
+carries them (_picp_solve, the autograd Functions, the backward, ProjectiveICPOdometryProvider): stride, numiters, damp
+and the two gates as the library takes them (dist_th metres, dot_th = cos(angle_thresh)); the thresholds and median-rule
+constants as floats, 0 = off; deterministic: None (the environment decides when the backward runs) or a bool."""
+
+
+def _picp_options(who, base=None, flags=(), **given):
+    """Validates into a PicpOptions on top of `base` (None: the defaults), IN THE ORDER THE KEYWORDS ARE WRITTEN: the order
+    in which a bad call is refused belongs to each public function.  The keywords: geometry=(stride, numiters, damp,
+    dist_thresh, angle_thresh), which goes through _picp_args; color_weight, huber_delta, huber_k, color_huber_delta,
+    color_huber_k, deterministic; and the names in `flags`, bool switches of the caller's that are checked in their
+    place and not kept.  Anything else is a mistake of the caller's.  color_huber_k > 0 needs color_weight > 0 where
+    color_weight was validated earlier in the same call."""
+    new = {}   # (one record is made, at the end: every _replace of a namedtuple is a microsecond of the call)
+    for name, val in given.items():
+        if name == "geometry":
+            dist_th, dot_th = _picp_args(*val)
+            new.update(stride=val[0], numiters=val[1], damp=float(val[2]), dist_th=dist_th, dot_th=dot_th)
+        elif name in ("huber_delta", "huber_k", "color_huber_delta"):
+            new[name] = _picp_number(who, name, val)
+        elif name == "deterministic":
+            new[name] = _picp_deterministic(who, name, val)
+        elif name == "color_weight":
+            new[name] = _picp_color_weight(val)
+        elif name == "color_huber_k":
+            new[name] = _picp_color_huber_k(val, who, new.get("color_weight"))
+        elif name in flags:
+            _picp_flag(who, name, val)
+        else:
+            raise TypeError("_picp_options: {!r} is neither an option nor one of the flags {}".format(name, flags))
+    return PicpOptions(**new) if base is None else base._replace(**new)
+
+
+def _picp_route(family, opt, weights=False, tape=False, ordered=False, tables=False):
+    """Which export serves a call, and which sizer its scratch: (export, sizer), the library's names being
+    gs_projective_icp_<export>_f32 and _PICP_SIZERS[sizer].  family: "batch", "rows", "color_batch", "color_rows" or
+    "backward"; weights: pixel weights are given; tape: the forward fills a tape (batch only); ordered: the backward's
+    ordered mode; tables: the optional per-slot output is asked for (rows: return_weights, backward:
+    want_pixel_weights, which needs weights).  Per family the rungs in order, the first that holds serves the call:
+    they are the features in the order they were added on top of each other -- the weighted entry serves every
+    threshold, the scaled entries take huber_delta as the floor, the robust entries serve a tape as well."""
+    k, ck = opt.huber_k > 0, opt.color_huber_k > 0
+    delta, cdelta = opt.huber_delta > 0, opt.color_huber_delta > 0
+    if (tape and family != "batch") or (ordered and family != "backward") or \
+            (tables and not (family in ("rows", "color_rows") or (family == "backward" and weights))):
+        raise ValueError("no projective ICP entry of family %r takes tape=%r, ordered=%r, tables=%r with weights=%r"
+                         % (family, tape, ordered, tables, weights))
+    if family == "batch":
+        rungs = ((weights, "weighted_batch"), (k, "scaled_batch"), (delta, "robust_batch"), (tape, "tape_batch"),
+                 (True, "batch"))
+        sizer = "scaled" if k else "plain"
+    elif family == "rows":
+        rungs = ((weights, "weighted_rows"), (k, "scaled_rows"), (delta or tables, "robust_rows"), (True, "rows"))
+        sizer = "scaled" if k else "plain"
+    elif family == "color_batch":
+        rungs = ((weights, "color_weighted_batch"), (ck, "color_joint_scaled_batch"), (k, "color_scaled_batch"),
+                 (delta or cdelta, "color_robust_batch"), (True, "color_batch"))
+        sizer = "joint_scaled" if ck or (weights and k) else "color_scaled" if k else "color"
+    elif family == "color_rows":
+        rungs = ((weights, "color_weighted_rows"), (k or ck, "color_joint_scaled_rows"),
+                 (delta or cdelta or tables, "color_robust_rows"), (True, "color_rows"))
+        sizer = "joint_scaled" if k or ck else "color"
+    elif family == "backward":
+        rungs = ((weights, "weighted_backward"), (ordered, "ordered_backward"), (k, "scaled_backward"),
+                 (delta, "robust_backward"), (True, "backward"))
+        sizer = "weighted_backward" if tables else "ordered_backward" if ordered else "backward"
+    else:
+        raise ValueError("no such family of projective ICP entries: %r" % (family,))
+    for holds, export in rungs:
+        if holds:
+            return export, sizer
+
+
+_PICP_SIZERS = {"plain": "gs_projective_icp_scratch_bytes", "scaled": "gs_projective_icp_scaled_scratch_bytes",
+                "color": "gs_projective_icp_color_scratch_bytes",
+                "color_scaled": "gs_projective_icp_color_scaled_scratch_bytes",
+                "joint_scaled": "gs_projective_icp_color_joint_scaled_scratch_bytes",
+                "backward": "gs_projective_icp_backward_scratch_bytes",
+                "ordered_backward": "gs_projective_icp_ordered_backward_scratch_bytes",
+                "weighted_backward": "gs_projective_icp_weighted_backward_scratch_bytes"}
 
 
 def deterministic_backward_env():
@@ -1128,12 +1210,9 @@ def _picp_weight_ptrs(entries):
     return (_C.C.c_void_p * len(entries))(*[None if t is None else t.data_ptr() for t in entries])
 
 
-def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, color=False, scaled=False,
-               color_scaled=False):
-    """Shape / dtype / device checks shared by the batched solve and the table-level call; fills the descriptors.
-    Returns (seqs, tensors kept alive, device, B, H, W).  color: the scratch is sized for the colour solve (the plain
-    layout plus the colour-row counts); scaled: ... plus the key table and the threshold of the median rule; color_scaled
-    (with color): ... plus the same again for the colour residual."""
+def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses):
+    """Shape / dtype / device checks shared by the batched solve, the table-level call and the backward; fills the input
+    fields of the descriptors (the scratch: _picp_scratch).  Returns (seqs, tensors kept alive, device, B, H, W)."""
     tensors = (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                ("model_pose", model_poses), ("init_pose", init_poses))
     _picp_tensors(who, tensors)
@@ -1166,14 +1245,6 @@ def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_pos
     index = index.contiguous()
     dev = require_device(vertex, normal, depth, K, index, model_poses, init_poses)
     held = [vertex, normal, depth, K, index, model_poses, init_poses]
-    ws = Workspace.get(dev)
-    L = lib()
-    sizer = {(False, False): L.gs_projective_icp_scratch_bytes, (True, False): L.gs_projective_icp_color_scratch_bytes,
-             (False, True): L.gs_projective_icp_scaled_scratch_bytes,
-             (True, True): L.gs_projective_icp_color_scaled_scratch_bytes}[(bool(color), bool(scaled))]
-    if color and color_scaled:
-        sizer = L.gs_projective_icp_color_joint_scaled_scratch_bytes
-    nbytes = sizer(H, W, int(stride))
     seqs = (_C.PicpSeq * Bn)()
     P3, P1 = H * W * 12, H * W * 4
     for b in range(Bn):
@@ -1189,8 +1260,17 @@ def _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_pos
             model_poses.data_ptr() + b * 64
         u.map = _map_view(m)
         u.init_pose16 = init_poses.data_ptr() + b * 64
-        u.scratch = ws.bytes("picp%d" % b, nbytes).data_ptr()
     return seqs, held, dev, Bn, H, W
+
+
+def _picp_scratch(seqs, dev, sizer, H, W, stride):
+    """the forward's scratch of every sequence, from the workspace of the current stream; sizer: _picp_route's (the plain
+    layout; "color": plus the colour-row counts; "scaled" / "color_scaled": plus the key table and the threshold of the
+    median rule; "joint_scaled": plus the same again for the colour residual)"""
+    ws = Workspace.get(dev)
+    nbytes = getattr(lib(), _PICP_SIZERS[sizer])(H, W, int(stride))
+    for b, u in enumerate(seqs):
+        u.scratch = ws.bytes("picp%d" % b, nbytes).data_ptr()
 
 
 def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, init_poses, *, stride=1, numiters=10,
@@ -1233,36 +1313,43 @@ def projective_icp_batch(vertex, normal, depth, K, index, model_poses, maps, ini
     sequence has no weights) or an (H, W) tensor, is taken as well.  With differentiable=True (the tensor form) the
     gradient reaches the weights too (WeightedProjectiveICPFunction; which pixels are masked is a constant), bitwise
     reproducible in both modes of the backward."""
-    if not isinstance(differentiable, bool):
-        raise TypeError("projective_icp: differentiable must be of type bool; but was of type {}.".format(
-            type(differentiable)))
+    _picp_flag("projective_icp", "differentiable", differentiable)
     weights = _picp_pixel_weights("projective_icp", pixel_weights, depth)
-    _picp_deterministic("projective_icp", "deterministic", deterministic)
-    dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
-    huber_delta = _picp_huber("huber_delta", huber_delta)
-    huber_k = _picp_huber_k(huber_k)
-    _picp_flag("projective_icp", "return_scale", return_scale)
-    if differentiable:
-        if out is not None:
-            raise ValueError("projective_icp: out= cannot be combined with differentiable=True (autograd owns the "
-                             "outputs)")
-        cfg = dict(stride=stride, numiters=numiters, damp=damp, dist_thresh=dist_thresh, angle_thresh=angle_thresh,
-                   guard=guard, counts=[(m[-2], m[-1]) for m in maps], huber_delta=huber_delta, huber_k=huber_k,
-                   deterministic=deterministic)
-        flat = [t for m in maps for t in m[:2]]
-        if weights is not None and not torch.is_tensor(pixel_weights):
-            raise ValueError("projective_icp: differentiable=True takes pixel_weights as one (B, H, W) tensor")
-        if weights is not None:
-            res = WeightedProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses,
-                                                      pixel_weights, cfg, *flat)
-        else:
-            res = ProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses, cfg, *flat)
-        scale = None
-        if return_scale:
-            scale = res[2] if huber_k > 0 else torch.full_like(res[1][..., 0], huber_delta)
-        return _picp_pack(res[0], res[1], scale, return_trace, return_scale)
-    return _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, numiters, damp, dist_th,
-                       dot_th, return_trace, out, None, huber_delta, huber_k, return_scale, weights)
+    opt = _picp_options("projective_icp", deterministic=deterministic,
+                        geometry=(stride, numiters, damp, dist_thresh, angle_thresh), huber_delta=huber_delta,
+                        huber_k=huber_k, flags=("return_scale",), return_scale=return_scale)
+    if not differentiable:
+        return _picp_solve(opt, vertex, normal, depth, K, index, model_poses, maps, init_poses, out=out, weights=weights,
+                           return_trace=return_trace, return_scale=return_scale)
+    if out is not None:
+        raise ValueError("projective_icp: out= cannot be combined with differentiable=True (autograd owns the "
+                         "outputs)")
+    return _picp_taped(opt, vertex, normal, depth, K, index, model_poses, maps, init_poses, pixel_weights, weights,
+                       return_trace=return_trace, return_scale=return_scale, guard=guard)
+
+
+PicpTapeConfig = collections.namedtuple("PicpTapeConfig", ["options", "counts", "guard"])
+PicpTapeConfig.__doc__ = """the `cfg` of ProjectiveICPFunction / WeightedProjectiveICPFunction: the PicpOptions, per
+sequence the map's (n_bound, n_dev), and the guard (a callable or None)"""
+
+
+def _picp_taped(opt, vertex, normal, depth, K, index, model_poses, maps, init_poses, pixel_weights, weights, *,
+                return_trace=False, return_scale=False, guard=None):
+    """projective_icp_batch(differentiable=True) behind its value checks: the solve on the autograd tape; opt: the
+    PicpOptions; weights: the entries of _picp_pixel_weights for pixel_weights"""
+    cfg = PicpTapeConfig(opt, [(m[-2], m[-1]) for m in maps], guard)
+    flat = [t for m in maps for t in m[:2]]
+    if weights is not None and not torch.is_tensor(pixel_weights):
+        raise ValueError("projective_icp: differentiable=True takes pixel_weights as one (B, H, W) tensor")
+    if weights is not None:
+        res = WeightedProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses,
+                                                  pixel_weights, cfg, *flat)
+    else:
+        res = ProjectiveICPFunction.apply(vertex, normal, depth, K, index, model_poses, init_poses, cfg, *flat)
+    scale = None
+    if return_scale:
+        scale = res[2] if opt.huber_k > 0 else torch.full_like(res[1][..., 0], opt.huber_delta)
+    return _picp_pack(res[0], res[1], scale, return_trace, return_scale)
 
 
 def _picp_pack(T, trace, scale, return_trace, return_scale):
@@ -1271,56 +1358,81 @@ def _picp_pack(T, trace, scale, return_trace, return_scale):
     return res if len(res) > 1 else T
 
 
-def _picp_outputs(who, seqs, dev, out, return_trace, width, stride, numiters, damp, dist_th, dot_th):
+def _picp_outputs(who, seqs, dev, out, return_trace, width, opt):
     """The outputs of a solve: `out` checked (or the poses allocated), the trace of `width` floats per iteration allocated
     when asked for, both wired into seqs (the PicpSeq of every sequence), and the PicpParams.  Returns (T, trace, prm)."""
     Bn = len(seqs)
     T = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if out is None else out
     if tuple(T.shape) != (Bn, 4, 4) or T.dtype != f32 or not T.is_contiguous() or T.device != dev:
         raise ValueError("%s: out must be a contiguous float32 tensor of shape %s on %s" % (who, (Bn, 4, 4), dev))
-    trace = torch.empty((Bn, int(numiters), width), dtype=f32, device=dev) if return_trace else None
+    trace = torch.empty((Bn, opt.numiters, width), dtype=f32, device=dev) if return_trace else None
     for b, u in enumerate(seqs):
         u.out_pose16 = T.data_ptr() + b * 64
-        u.trace = 0 if trace is None else trace.data_ptr() + b * int(numiters) * width * 4
-    return T, trace, _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
+        u.trace = 0 if trace is None else trace.data_ptr() + b * opt.numiters * width * 4
+    return T, trace, _C.PicpParams(*opt[:5])
 
 
-def _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, stride, numiters, damp, dist_th, dot_th,
-                return_trace, out, tapes, huber_delta=0.0, huber_k=0.0, return_scale=False, weights=None):
-    """the solve behind projective_icp_batch and ProjectiveICPFunction.forward; tapes: None, or the uint8 (B, tape bytes)
-    buffer the taped entry fills (the same kernels and pose bits); huber_delta > 0: the robust entry; huber_k > 0: the
-    scaled entry (huber_delta its floor); weights: the entries of _picp_pixel_weights (the weighted entry, whatever the
-    thresholds) or None"""
-    seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp", vertex, normal, depth, K, index, model_poses, maps,
-                                           init_poses, stride, scaled=huber_k > 0)
-    T, trace, prm = _picp_outputs("projective_icp", list(seqs), dev, out, return_trace, PICP_TRACE, stride, numiters,
-                                  damp, dist_th, dot_th)
-    ptrs = None if tapes is None else \
-        (_C.C.c_void_p * Bn)(*[tapes.data_ptr() + b * tapes.shape[1] for b in range(Bn)])
-    scale = None
+def _picp_solve(opt, vertex, normal, depth, K, index, model_poses, maps, init_poses, *, color=None, model=None, out=None,
+                tapes=None, weights=None, return_trace=False, return_scale=False, return_color_scale=False):
+    """The batched solve of both families, geometric and (color, model given) joint, behind projective_icp_batch,
+    projective_icp_color_batch and the autograd Functions' forward.  opt: the PicpOptions, which with `weights` (the
+    entries of _picp_pixel_weights, or None) and `tapes` (None, or the uint8 (B, tape bytes) buffer a taped entry fills:
+    the same kernels and pose bits) decides the entry (_picp_route).  Returns the poses, then the trace, the thresholds
+    and the colour thresholds where asked for."""
+    joint = color is not None
+    who = "projective_icp_color" if joint else "projective_icp"
+    export, sizer = _picp_route("color_batch" if joint else "batch", opt, weights=weights is not None,
+                                tape=tapes is not None)
+    seqs, held, dev, Bn, H, W = _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses)
+    _picp_scratch(seqs, dev, sizer, H, W, opt.stride)
+    if joint:
+        seqs = _picp_color_seqs(who, seqs, held, Bn, H, W, color, model)
+    T, trace, prm = _picp_outputs(who, [c.base for c in seqs] if joint else list(seqs), dev, out, return_trace,
+                                  PICP_COLOR_TRACE if joint else PICP_TRACE, opt)
     if weights is not None:
         require_device(*weights, held[0])
         held.append(weights)
-        scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale and huber_k > 0 else (None, None)
-        check(lib().gs_projective_icp_weighted_batch_f32(seqs, _picp_weight_ptrs(weights), ptrs, dptrs, Bn, H, W, prm,
-                                                         huber_delta, huber_k, stream(dev)),
-              "gs_projective_icp_weighted_batch_f32")
-    elif huber_k > 0:
-        scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale else (None, None)
-        check(lib().gs_projective_icp_scaled_batch_f32(seqs, ptrs, dptrs, Bn, H, W, prm, huber_k, huber_delta,
-                                                       stream(dev)),
-              "gs_projective_icp_scaled_batch_f32")
-    elif huber_delta > 0:
-        check(lib().gs_projective_icp_robust_batch_f32(seqs, ptrs, Bn, H, W, prm, huber_delta, stream(dev)),
-              "gs_projective_icp_robust_batch_f32")
-    elif tapes is not None:
-        check(lib().gs_projective_icp_tape_batch_f32(seqs, ptrs, Bn, H, W, prm, stream(dev)),
-              "gs_projective_icp_tape_batch_f32")
+        wptrs = _picp_weight_ptrs(weights)
+    ptrs = None if tapes is None else \
+        (_C.C.c_void_p * Bn)(*[tapes.data_ptr() + b * tapes.shape[1] for b in range(Bn)])
+    # a table of thresholds is written only where it is asked for AND its median rule runs; else it is the constant
+    scale, dptrs = _picp_scale_table(Bn, opt.numiters, dev) if return_scale and opt.huber_k > 0 else (None, None)
+    cscale, cptrs = _picp_scale_table(Bn, opt.numiters, dev) if return_color_scale and opt.color_huber_k > 0 \
+        else (None, None)
+    L, st = lib(), stream(dev)
+    delta, k, cw, cdelta, ck = opt.huber_delta, opt.huber_k, opt.color_weight, opt.color_huber_delta, opt.color_huber_k
+    # (the scaled entries take (k, floor), the weighted ones (delta, k))
+    if export == "weighted_batch":
+        status = L.gs_projective_icp_weighted_batch_f32(seqs, wptrs, ptrs, dptrs, Bn, H, W, prm, delta, k, st)
+    elif export == "scaled_batch":
+        status = L.gs_projective_icp_scaled_batch_f32(seqs, ptrs, dptrs, Bn, H, W, prm, k, delta, st)
+    elif export == "robust_batch":
+        status = L.gs_projective_icp_robust_batch_f32(seqs, ptrs, Bn, H, W, prm, delta, st)
+    elif export == "tape_batch":
+        status = L.gs_projective_icp_tape_batch_f32(seqs, ptrs, Bn, H, W, prm, st)
+    elif export == "batch":
+        status = L.gs_projective_icp_batch_f32(seqs, Bn, H, W, prm, st)
+    elif export == "color_weighted_batch":
+        status = L.gs_projective_icp_color_weighted_batch_f32(seqs, wptrs, dptrs, cptrs, Bn, H, W, prm, cw, delta, k,
+                                                              cdelta, ck, st)
+    elif export == "color_joint_scaled_batch":
+        status = L.gs_projective_icp_color_joint_scaled_batch_f32(seqs, dptrs, cptrs, Bn, H, W, prm, cw, k, delta, ck,
+                                                                  cdelta, st)
+    elif export == "color_scaled_batch":
+        status = L.gs_projective_icp_color_scaled_batch_f32(seqs, dptrs, Bn, H, W, prm, cw, k, delta, cdelta, st)
+    elif export == "color_robust_batch":
+        status = L.gs_projective_icp_color_robust_batch_f32(seqs, Bn, H, W, prm, cw, delta, cdelta, st)
     else:
-        check(lib().gs_projective_icp_batch_f32(seqs, Bn, H, W, prm, stream(dev)), "gs_projective_icp_batch_f32")
+        status = L.gs_projective_icp_color_batch_f32(seqs, Bn, H, W, prm, cw, st)
+    check(status, "gs_projective_icp_%s_f32" % export)
     if return_scale and scale is None:
-        scale = torch.full((Bn, int(numiters)), huber_delta, dtype=f32, device=dev)
-    return _picp_pack(T, trace, scale, return_trace, return_scale)
+        scale = torch.full((Bn, opt.numiters), delta, dtype=f32, device=dev)
+    if return_color_scale and cscale is None:
+        cscale = torch.full((Bn, opt.numiters), cdelta, dtype=f32, device=dev)
+    res = _picp_pack(T, trace, scale, return_trace, return_scale)
+    if return_color_scale:
+        res = (res if isinstance(res, tuple) else (res,)) + (cscale,)
+    return res
 
 
 def projective_icp_tape_bytes(numiters):
@@ -1354,22 +1466,34 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
     (nothing is allocated or computed for it).  It is accumulated per slot in float64 by the slot's own thread and rounded
     once: bitwise reproducible, and the same bits in the atomic and the ordered mode; +0.0 off the lattice, at masked
     pixels and at pixels never used (gs_projective_icp_weighted_backward_batch_f32)."""
-    dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
-    _picp_flag("projective_icp_backward", "want_pixel_weights", want_pixel_weights)
-    weights = _picp_pixel_weights("projective_icp_backward", pixel_weights, depth)
+    who = "projective_icp_backward"
+    flags = ("want_pixel_weights", "return_contributions")
+    opt = _picp_options(who, geometry=(stride, numiters, damp, dist_thresh, angle_thresh), flags=flags,
+                        want_pixel_weights=want_pixel_weights)
+    weights = _picp_pixel_weights(who, pixel_weights, depth)
     if want_pixel_weights and weights is None:
         raise ValueError("projective_icp_backward: want_pixel_weights=True needs the pixel_weights of the forward")
-    huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_backward")
-    huber_k = _picp_huber_k(huber_k, "projective_icp_backward")
-    _picp_deterministic("projective_icp_backward", "deterministic", deterministic)
-    _picp_flag("projective_icp_backward", "return_contributions", return_contributions)
-    ordered = deterministic_backward_env() if deterministic is None else deterministic
+    opt = _picp_options(who, opt, huber_delta=huber_delta, huber_k=huber_k, deterministic=deterministic, flags=flags,
+                        return_contributions=return_contributions)
+    return _picp_backward(opt, vertex, normal, depth, K, index, model_poses, maps, tapes, pose_bar,
+                          want_vertex=want_vertex, want_init=want_init, want_maps=want_maps, weights=weights,
+                          want_pixel_weights=want_pixel_weights, return_contributions=return_contributions)
+
+
+def _picp_backward(opt, vertex, normal, depth, K, index, model_poses, maps, tapes, pose_bar, *, want_vertex, want_init,
+                   want_maps, weights=None, want_pixel_weights=False, return_contributions=False):
+    """projective_icp_backward_batch behind its value checks; opt: the PicpOptions of the taped forward; weights: the
+    entries of _picp_pixel_weights (None: the forward ran without)"""
+    ordered = deterministic_backward_env() if opt.deterministic is None else opt.deterministic
     if return_contributions and not ordered:
         raise ValueError("projective_icp_backward: return_contributions=True needs the ordered mode (deterministic=True "
                          "or GRADSLAM_HIP_DETERMINISTIC_BACKWARD=1)")
+    weighted = weights is not None
+    export, sizer = _picp_route("backward", opt, weights=weighted, ordered=ordered, tables=want_pixel_weights)
     with torch.no_grad():
         seqs, held, dev, Bn, H, W = _picp_seqs("projective_icp_backward", vertex, normal, depth, K, index, model_poses,
-                                               maps, pose_bar, stride)
+                                               maps, pose_bar)
+    numiters, stride = opt.numiters, opt.stride
     if not torch.is_tensor(tapes) or tapes.dtype != torch.uint8 or tapes.ndim != 2 or not tapes.is_contiguous() or \
             tuple(tapes.shape) != (Bn, projective_icp_tape_bytes(numiters)) or tapes.device != dev:
         raise ValueError("projective_icp_backward: tapes must be the contiguous uint8 (B, %d) buffer of the taped forward"
@@ -1382,16 +1506,15 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
     init_bar = torch.empty((Bn, 4, 4), dtype=f32, device=dev) if want_init else None
     ws = Workspace.get(dev)
     L = lib()
-    weighted = weights is not None
-    oseqs = (_C.PicpOrderedBackwardSeq * Bn)() if ordered or weighted else None   # (the weighted entry: both modes)
+    # (the weighted entry takes the ordered descriptors in both modes)
+    oseqs = (_C.PicpOrderedBackwardSeq * Bn)() if export in ("weighted_backward", "ordered_backward") else None
     bseqs = (_C.PicpBackwardSeq * Bn)() if oseqs is None else None
-    sizer = L.gs_projective_icp_ordered_backward_scratch_bytes if ordered else L.gs_projective_icp_backward_scratch_bytes
+    # (the weighted sizer: the float64 accumulator of pixel_weights_bar, 8 bytes per slot more, in either mode)
+    size, mode = getattr(L, _PICP_SIZERS[sizer]), ((1 if ordered else 0,) if sizer == "weighted_backward" else ())
     if weighted:
         require_device(*weights, held[0])
-    if want_pixel_weights:   # (the float64 accumulator of pixel_weights_bar: 8 bytes per slot more)
-        sizer = lambda h, w, st, n: L.gs_projective_icp_weighted_backward_scratch_bytes(h, w, st, n, 1 if ordered else 0)  # noqa: E731
     weights_bar = torch.empty((Bn, H, W), dtype=f32, device=dev) if want_pixel_weights else None
-    nslots = _picp_nslots(H, W, int(stride))
+    nslots = _picp_nslots(H, W, stride)
     rows_out, record = [], []
     for b in range(Bn):
         u, f = oseqs[b].base if oseqs is not None else bseqs[b], seqs[b]
@@ -1407,46 +1530,78 @@ def projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, 
         u.vertex_bar = None if vertex_bar is None else vertex_bar.data_ptr() + b * H * W * 12
         u.points_bar, u.normals_bar = (None if g is None else g.data_ptr() for g in outs)
         u.init_pose_bar16 = None if init_bar is None else init_bar.data_ptr() + b * 64
-        nbytes = sizer(H, W, int(stride), n_bound if any(want_maps[b]) else 0)
-        buf = ws.bytes("picp_bwd%d" % b, nbytes)
+        buf = ws.bytes("picp_bwd%d" % b, size(H, W, stride, n_bound if any(want_maps[b]) else 0, *mode))
         u.scratch, u.scratch_bytes = buf.data_ptr(), int(buf.numel())
         if return_contributions:   # (what the kernel does not write reads "none" / zero)
-            keys = torch.full((int(numiters), nslots), PICP_NO_KEY, dtype=torch.int32, device=dev)
-            contrib = torch.zeros((int(numiters), nslots, 6), dtype=torch.float64, device=dev)
+            keys = torch.full((numiters, nslots), PICP_NO_KEY, dtype=torch.int32, device=dev)
+            contrib = torch.zeros((numiters, nslots, 6), dtype=torch.float64, device=dev)
             oseqs[b].key_out, oseqs[b].contrib_out = keys.data_ptr(), contrib.data_ptr()
             record.append((keys, contrib))
-    prm = _C.PicpParams(int(stride), int(numiters), float(damp), dist_th, dot_th)
+    prm = _C.PicpParams(stride, numiters, opt.damp, opt.dist_th, opt.dot_th)
     sort_buf = None
     if ordered:
-        sort_bytes = L.gs_projective_icp_ordered_backward_sort_scratch_bytes(Bn, H, W, int(stride))
+        sort_bytes = L.gs_projective_icp_ordered_backward_sort_scratch_bytes(Bn, H, W, stride)
         if sort_bytes <= 0:
             raise ValueError("projective_icp_backward: the lattices of a launch group (%d x %d slots) are too many for "
                              "one sort of the ordered mode" % (min(Bn, 8), nslots))
         sort_buf = ws.bytes("picp_bwd_sort", sort_bytes) if any(any(w) for w in want_maps) else None
-    if weighted:
+    sort_ptr, sort_len = (None, 0) if sort_buf is None else (sort_buf.data_ptr(), int(sort_buf.numel()))
+    # (a scaled tape holds every iteration's threshold: huber_delta is then not read)
+    delta, scaled = (0.0, 1) if opt.huber_k > 0 else (opt.huber_delta, 0)
+    st = stream(dev)
+    if export == "weighted_backward":
         bar_ptrs = None if weights_bar is None else \
             (_C.C.c_void_p * Bn)(*[weights_bar.data_ptr() + b * H * W * 4 for b in range(Bn)])
-        check(L.gs_projective_icp_weighted_backward_batch_f32(
-            oseqs, _picp_weight_ptrs(weights), bar_ptrs, Bn, H, W, prm, 0.0 if huber_k > 0 else huber_delta,
-            1 if huber_k > 0 else 0, 1 if ordered else 0, None if sort_buf is None else sort_buf.data_ptr(),
-            0 if sort_buf is None else int(sort_buf.numel()), stream(dev)),
-            "gs_projective_icp_weighted_backward_batch_f32")
-    elif ordered:
-        check(L.gs_projective_icp_ordered_backward_batch_f32(
-            oseqs, Bn, H, W, prm, 0.0 if huber_k > 0 else huber_delta, 1 if huber_k > 0 else 0,
-            None if sort_buf is None else sort_buf.data_ptr(), 0 if sort_buf is None else int(sort_buf.numel()),
-            stream(dev)), "gs_projective_icp_ordered_backward_batch_f32")
-    elif huber_k > 0:
-        check(L.gs_projective_icp_scaled_backward_batch_f32(bseqs, Bn, H, W, prm, stream(dev)),
-              "gs_projective_icp_scaled_backward_batch_f32")
-    elif huber_delta > 0:
-        check(L.gs_projective_icp_robust_backward_batch_f32(bseqs, Bn, H, W, prm, huber_delta, stream(dev)),
-              "gs_projective_icp_robust_backward_batch_f32")
+        status = L.gs_projective_icp_weighted_backward_batch_f32(oseqs, _picp_weight_ptrs(weights), bar_ptrs, Bn, H, W,
+                                                                 prm, delta, scaled, 1 if ordered else 0, sort_ptr,
+                                                                 sort_len, st)
+    elif export == "ordered_backward":
+        status = L.gs_projective_icp_ordered_backward_batch_f32(oseqs, Bn, H, W, prm, delta, scaled, sort_ptr, sort_len,
+                                                                st)
+    elif export == "scaled_backward":
+        status = L.gs_projective_icp_scaled_backward_batch_f32(bseqs, Bn, H, W, prm, st)
+    elif export == "robust_backward":
+        status = L.gs_projective_icp_robust_backward_batch_f32(bseqs, Bn, H, W, prm, opt.huber_delta, st)
     else:
-        check(L.gs_projective_icp_backward_batch_f32(bseqs, Bn, H, W, prm, stream(dev)),
-              "gs_projective_icp_backward_batch_f32")
+        status = L.gs_projective_icp_backward_batch_f32(bseqs, Bn, H, W, prm, st)
+    check(status, "gs_projective_icp_%s_batch_f32" % export)
     res = (vertex_bar, rows_out, init_bar) + ((record,) if return_contributions else ())
     return res + (weights_bar,) if weighted else res
+
+
+def _picp_taped_forward(ctx, tensors, cfg, flat):
+    """the forward of both autograd Functions; tensors: the inputs in front of cfg (vertex, normal, depth, K, index,
+    model_poses, init_poses, and the pixel weights of the weighted Function)"""
+    depth, opt = tensors[2], cfg.options
+    maps = [(flat[2 * b], flat[2 * b + 1]) + tuple(cfg.counts[b]) for b in range(len(flat) // 2)]
+    tapes = torch.empty((int(depth.shape[0]), projective_icp_tape_bytes(opt.numiters)), dtype=torch.uint8,
+                        device=depth.device)
+    weights = _picp_pixel_weights("projective_icp", tensors[7], depth) if len(tensors) > 7 else None
+    res = _picp_solve(opt, *tensors[:6], maps, tensors[6], tapes=tapes, weights=weights, return_trace=True,
+                      return_scale=opt.huber_k > 0)
+    ctx.save_for_backward(*tensors[:6], tapes, *tensors[7:], *flat, *[c[1] for c in cfg.counts])
+    # (opt.deterministic None: the backward reads GRADSLAM_HIP_DETERMINISTIC_BACKWARD when it runs, not now)
+    ctx.opt, ctx.bounds, ctx.guard = opt, [c[0] for c in cfg.counts], cfg.guard
+    ctx.mark_non_differentiable(*res[1:])
+    return res
+
+
+def _picp_taped_backward(ctx, T_bar, weighted):
+    """the backward of both autograd Functions; weighted: input 7 is the pixel weights (cfg and the maps follow it)"""
+    if ctx.guard is not None:
+        ctx.guard()
+    n_in = 9 if weighted else 8   # (the inputs in front of the maps' tensors, cfg among them)
+    saved, Bn, need = ctx.saved_tensors, len(ctx.bounds), ctx.needs_input_grad
+    flat, n_devs = saved[n_in - 1:n_in - 1 + 2 * Bn], saved[n_in - 1 + 2 * Bn:]
+    want_maps = [(bool(need[n_in + 2 * b]), bool(need[n_in + 1 + 2 * b])) for b in range(Bn)]
+    if T_bar is None or not (need[0] or need[6] or (weighted and need[7]) or any(any(w) for w in want_maps)):
+        return (None,) * (n_in + 2 * Bn)
+    maps = [(flat[2 * b], flat[2 * b + 1], ctx.bounds[b], n_devs[b]) for b in range(Bn)]
+    weights = _picp_pixel_weights("projective_icp_backward", saved[7], saved[2]) if weighted else None
+    res = _picp_backward(ctx.opt, *saved[:6], maps, saved[6], T_bar, want_vertex=bool(need[0]), want_init=bool(need[6]),
+                         want_maps=want_maps, weights=weights, want_pixel_weights=weighted and bool(need[7]))
+    return (res[0], None, None, None, None, None, res[2]) + ((res[3], None) if weighted else (None,)) + \
+        tuple(g for r in res[1] for g in r)
 
 
 class ProjectiveICPFunction(torch.autograd.Function):
@@ -1465,43 +1620,11 @@ class ProjectiveICPFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vertex, normal, depth, K, index, model_poses, init_poses, cfg, *flat):
-        Bn = len(flat) // 2
-        kw = {k: cfg[k] for k in ("stride", "numiters", "damp", "dist_thresh", "angle_thresh")}
-        maps = [(flat[2 * b], flat[2 * b + 1]) + tuple(cfg["counts"][b]) for b in range(Bn)]
-        tapes = torch.empty((int(depth.shape[0]), projective_icp_tape_bytes(kw["numiters"])), dtype=torch.uint8,
-                            device=depth.device)
-        dist_th, dot_th = _picp_args(kw["stride"], kw["numiters"], kw["damp"], kw["dist_thresh"], kw["angle_thresh"])
-        huber_delta = _picp_huber("huber_delta", cfg.get("huber_delta", 0.0))
-        huber_k = _picp_huber_k(cfg.get("huber_k", 0.0))
-        res = _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, kw["stride"], kw["numiters"],
-                          kw["damp"], dist_th, dot_th, True, None, tapes, huber_delta, huber_k, huber_k > 0)
-        T, trace = res[0], res[1]
-        kw["huber_delta"], kw["huber_k"] = huber_delta, huber_k
-        # (None: the backward reads GRADSLAM_HIP_DETERMINISTIC_BACKWARD when it runs, not now)
-        kw["deterministic"] = _picp_deterministic("projective_icp", "deterministic", cfg.get("deterministic"))
-        ctx.save_for_backward(vertex, normal, depth, K, index, model_poses, tapes, *flat,
-                              *[c[1] for c in cfg["counts"]])
-        ctx.kw, ctx.bounds, ctx.guard = kw, [c[0] for c in cfg["counts"]], cfg.get("guard")
-        ctx.mark_non_differentiable(*res[1:])
-        return res
+        return _picp_taped_forward(ctx, (vertex, normal, depth, K, index, model_poses, init_poses), cfg, flat)
 
     @staticmethod
     def backward(ctx, T_bar, *_constants_bar):
-        if ctx.guard is not None:
-            ctx.guard()
-        saved = ctx.saved_tensors
-        vertex, normal, depth, K, index, model_poses, tapes = saved[:7]
-        Bn = len(ctx.bounds)
-        flat, n_devs = saved[7:7 + 2 * Bn], saved[7 + 2 * Bn:]
-        need = ctx.needs_input_grad
-        want_maps = [(bool(need[8 + 2 * b]), bool(need[9 + 2 * b])) for b in range(Bn)]
-        if T_bar is None or not (need[0] or need[6] or any(any(w) for w in want_maps)):
-            return (None,) * (8 + 2 * Bn)
-        maps = [(flat[2 * b], flat[2 * b + 1], ctx.bounds[b], n_devs[b]) for b in range(Bn)]
-        vb, rows, ib = projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, maps, tapes, T_bar,
-                                                     want_vertex=bool(need[0]), want_init=bool(need[6]),
-                                                     want_maps=want_maps, **ctx.kw)
-        return (vb, None, None, None, None, None, ib, None) + tuple(g for r in rows for g in r)
+        return _picp_taped_backward(ctx, T_bar, weighted=False)
 
 
 class WeightedProjectiveICPFunction(torch.autograd.Function):
@@ -1514,43 +1637,12 @@ class WeightedProjectiveICPFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vertex, normal, depth, K, index, model_poses, init_poses, pixel_weights, cfg, *flat):
-        Bn = len(flat) // 2
-        kw = {k: cfg[k] for k in ("stride", "numiters", "damp", "dist_thresh", "angle_thresh")}
-        maps = [(flat[2 * b], flat[2 * b + 1]) + tuple(cfg["counts"][b]) for b in range(Bn)]
-        tapes = torch.empty((int(depth.shape[0]), projective_icp_tape_bytes(kw["numiters"])), dtype=torch.uint8,
-                            device=depth.device)
-        dist_th, dot_th = _picp_args(kw["stride"], kw["numiters"], kw["damp"], kw["dist_thresh"], kw["angle_thresh"])
-        huber_delta = _picp_huber("huber_delta", cfg.get("huber_delta", 0.0))
-        huber_k = _picp_huber_k(cfg.get("huber_k", 0.0))
-        weights = _picp_pixel_weights("projective_icp", pixel_weights, depth)
-        res = _picp_solve(vertex, normal, depth, K, index, model_poses, maps, init_poses, kw["stride"], kw["numiters"],
-                          kw["damp"], dist_th, dot_th, True, None, tapes, huber_delta, huber_k, huber_k > 0, weights)
-        kw["huber_delta"], kw["huber_k"] = huber_delta, huber_k
-        kw["deterministic"] = _picp_deterministic("projective_icp", "deterministic", cfg.get("deterministic"))
-        ctx.save_for_backward(vertex, normal, depth, K, index, model_poses, tapes, pixel_weights, *flat,
-                              *[c[1] for c in cfg["counts"]])
-        ctx.kw, ctx.bounds, ctx.guard = kw, [c[0] for c in cfg["counts"]], cfg.get("guard")
-        ctx.mark_non_differentiable(*res[1:])
-        return res
+        return _picp_taped_forward(ctx, (vertex, normal, depth, K, index, model_poses, init_poses, pixel_weights), cfg,
+                                   flat)
 
     @staticmethod
     def backward(ctx, T_bar, *_constants_bar):
-        if ctx.guard is not None:
-            ctx.guard()
-        saved = ctx.saved_tensors
-        vertex, normal, depth, K, index, model_poses, tapes, pixel_weights = saved[:8]
-        Bn = len(ctx.bounds)
-        flat, n_devs = saved[8:8 + 2 * Bn], saved[8 + 2 * Bn:]
-        need = ctx.needs_input_grad
-        want_maps = [(bool(need[9 + 2 * b]), bool(need[10 + 2 * b])) for b in range(Bn)]
-        if T_bar is None or not (need[0] or need[6] or need[7] or any(any(w) for w in want_maps)):
-            return (None,) * (9 + 2 * Bn)
-        maps = [(flat[2 * b], flat[2 * b + 1], ctx.bounds[b], n_devs[b]) for b in range(Bn)]
-        vb, rows, ib, wb = projective_icp_backward_batch(vertex, normal, depth, K, index, model_poses, maps, tapes, T_bar,
-                                                         want_vertex=bool(need[0]), want_init=bool(need[6]),
-                                                         want_maps=want_maps, pixel_weights=pixel_weights,
-                                                         want_pixel_weights=bool(need[7]), **ctx.kw)
-        return (vb, None, None, None, None, None, ib, wb, None) + tuple(g for r in rows for g in r)
+        return _picp_taped_backward(ctx, T_bar, weighted=True)
 
 
 def projective_icp(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, *, n_dev=None,
@@ -1594,72 +1686,51 @@ def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points,
     pixel_weights ((H, W) float32, see projective_icp_batch; gs_projective_icp_weighted_rows_f32): a masked slot has code
     6 and row -1; sums are the weighted sums; `weight` is the total weight of a used slot, its pixel weight times its
     Huber weight; the returned shapes are those of the call without pixel weights."""
-    dist_th, dot_th = _picp_args(stride, 1, 1.0, dist_thresh, angle_thresh)
-    huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_rows")
-    huber_k = _picp_huber_k(huber_k, "projective_icp_rows")
-    if not isinstance(return_weights, bool):
-        raise TypeError("projective_icp_rows: return_weights must be of type bool; but was of type {}.".format(
-            type(return_weights)))
-    _picp_tensors("projective_icp_rows", (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K),
-                                          ("index", index), ("model_pose", model_pose), ("pose", pose)))
+    who = "projective_icp_rows"
+    opt = _picp_options(who, geometry=(stride, 1, 1.0, dist_thresh, angle_thresh), huber_delta=huber_delta,
+                        huber_k=huber_k, flags=("return_weights",), return_weights=return_weights)
+    _picp_tensors(who, (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
+                        ("model_pose", model_pose), ("pose", pose)))
     if pixel_weights is not None:
-        _picp_tensors("projective_icp_rows", (("pixel_weights", pixel_weights),))
-    weights = _picp_pixel_weights("projective_icp_rows", None if pixel_weights is None else pixel_weights.unsqueeze(0),
-                                  depth.unsqueeze(0))
-    seqs, held, dev, _, H, W = _picp_seqs("projective_icp_rows", vertex.unsqueeze(0), normal.unsqueeze(0),
-                                          depth.unsqueeze(0), K.reshape(1, 4, 4), index.unsqueeze(0),
-                                          model_pose.reshape(1, 4, 4), [(map_points, map_normals, None, n_dev)],
-                                          pose.reshape(1, 4, 4), stride, scaled=huber_k > 0)
+        _picp_tensors(who, (("pixel_weights", pixel_weights),))
+    weights = _picp_pixel_weights(who, None if pixel_weights is None else pixel_weights.unsqueeze(0), depth.unsqueeze(0))
+    export, sizer = _picp_route("rows", opt, weights=weights is not None, tables=return_weights)
+    seqs, held, dev, _, H, W = _picp_seqs(who, vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0),
+                                          K.reshape(1, 4, 4), index.unsqueeze(0), model_pose.reshape(1, 4, 4),
+                                          [(map_points, map_normals, None, n_dev)], pose.reshape(1, 4, 4))
+    _picp_scratch(seqs, dev, sizer, H, W, stride)
     ns = _picp_nslots(H, W, stride)
     res = ProjectiveRows(torch.empty(ns, dtype=torch.int32, device=dev), torch.empty(ns, dtype=torch.int64, device=dev),
                          torch.empty((ns, 6), dtype=f32, device=dev), torch.empty(ns, dtype=f32, device=dev),
                          torch.empty(28, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.int64, device=dev))
     if weights is not None:
         require_device(*weights, held[0])
-        weight = torch.empty(ns, dtype=f32, device=dev) if return_weights else None
-        delta = torch.empty(1, dtype=f32, device=dev) if return_weights and huber_k > 0 else None
-        check(lib().gs_projective_icp_weighted_rows_f32(seqs, ptr(weights[0]), H, W, int(stride), dist_th, dot_th,
-                                                        huber_delta, huber_k, *[ptr(t) for t in res[:4]], ptr(weight),
-                                                        *[ptr(t) for t in res[4:]], ptr(delta), stream(dev)),
-              "gs_projective_icp_weighted_rows_f32")
-        if not return_weights:
-            return res
-        return (res, weight, delta) if huber_k > 0 else (res, weight)
-    if huber_k > 0:
-        weight, delta = (torch.empty(ns, dtype=f32, device=dev), torch.empty(1, dtype=f32, device=dev)) \
-            if return_weights else (None, None)
-        check(lib().gs_projective_icp_scaled_rows_f32(seqs, H, W, int(stride), dist_th, dot_th, huber_k, huber_delta,
-                                                      *[ptr(t) for t in res[:4]], ptr(weight),
-                                                      *[ptr(t) for t in res[4:]], ptr(delta), stream(dev)),
-              "gs_projective_icp_scaled_rows_f32")
-        return (res, weight, delta) if return_weights else res
-    if huber_delta > 0 or return_weights:
-        weight = torch.empty(ns, dtype=f32, device=dev) if return_weights else None
-        check(lib().gs_projective_icp_robust_rows_f32(seqs, H, W, int(stride), dist_th, dot_th, huber_delta,
-                                                      *[ptr(t) for t in res[:4]], ptr(weight),
-                                                      *[ptr(t) for t in res[4:]], stream(dev)),
-              "gs_projective_icp_robust_rows_f32")
-        return (res, weight) if return_weights else res
-    check(lib().gs_projective_icp_rows_f32(seqs, H, W, int(stride), dist_th, dot_th, *[ptr(t) for t in res], stream(dev)),
-          "gs_projective_icp_rows_f32")
-    return res
+    # the weights and, where the median rule runs, the threshold it derived follow the rows when asked for
+    extra = ()
+    if return_weights:
+        extra = (torch.empty(ns, dtype=f32, device=dev),) + \
+            ((torch.empty(1, dtype=f32, device=dev),) if opt.huber_k > 0 else ())
+    weight, th = (extra + (None, None))[:2]
+    L, st, gates = lib(), stream(dev), (H, W, int(stride), opt.dist_th, opt.dot_th)
+    rows, sums = [ptr(t) for t in res[:4]], [ptr(t) for t in res[4:]]
+    if export == "weighted_rows":
+        status = L.gs_projective_icp_weighted_rows_f32(seqs, ptr(weights[0]), *gates, opt.huber_delta, opt.huber_k,
+                                                       *rows, ptr(weight), *sums, ptr(th), st)
+    elif export == "scaled_rows":
+        status = L.gs_projective_icp_scaled_rows_f32(seqs, *gates, opt.huber_k, opt.huber_delta, *rows, ptr(weight),
+                                                     *sums, ptr(th), st)
+    elif export == "robust_rows":
+        status = L.gs_projective_icp_robust_rows_f32(seqs, *gates, opt.huber_delta, *rows, ptr(weight), *sums, st)
+    else:
+        status = L.gs_projective_icp_rows_f32(seqs, *gates, *rows, *sums, st)
+    check(status, "gs_projective_icp_%s_f32" % export)
+    return (res,) + extra if return_weights else res
 
 
 # ----------------------------------------------------------------------------------- projective ICP with a colour term
 ProjectiveColorRows = collections.namedtuple("ProjectiveColorRows", ["code", "row", "a", "b", "ac", "bc", "colored",
                                                                      "sums", "count", "color_count"])
 PICP_COLOR_TRACE = 9
-
-
-def _picp_color_weight(color_weight):
-    """the value check of the colour weight (metres per intensity unit): a finite number >= 0"""
-    import math
-    if isinstance(color_weight, bool) or not isinstance(color_weight, (float, int)):
-        raise TypeError("projective_icp_color: color_weight must be of type float or int; but was of type {}.".format(
-            type(color_weight)))
-    if not (math.isfinite(color_weight) and color_weight >= 0):
-        raise ValueError("projective_icp_color: color_weight ({}) must be finite and not negative.".format(color_weight))
-    return float(color_weight)
 
 
 def _picp_refuse_differentiable(differentiable):
@@ -1694,8 +1765,8 @@ def model_intensity(color, index):
 
 
 def _picp_color_seqs(who, seqs, held, Bn, H, W, color, model):
-    """the colour descriptors on top of the plain ones (_picp_seqs(..., color=True)): shape / dtype / device checks of the
-    live colour and the model intensity"""
+    """the colour descriptors on top of the plain ones (_picp_seqs; the scratch, sized for the colour solve, is in them):
+    shape / dtype / device checks of the live colour and the model intensity"""
     for name, t, shape in (("color", color, (Bn, H, W, 3)), ("model_intensity", model, (Bn, H, W, 4))):
         if not torch.is_tensor(t):
             raise TypeError("{}: expected {} to be of type tensor; got {}".format(who, name, type(t)))
@@ -1747,57 +1818,14 @@ def projective_icp_color_batch(vertex, normal, depth, K, index, model_poses, map
     row either, and the colour products carry the pixel weight times the colour Huber weight."""
     _picp_refuse_differentiable(differentiable)
     weights = _picp_pixel_weights("projective_icp_color", pixel_weights, depth)
-    weight = _picp_color_weight(color_weight)
-    color_huber_k = _picp_color_huber_k(color_huber_k, "projective_icp_color", weight)
-    _picp_flag("projective_icp_color", "return_color_scale", return_color_scale)
-    huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_color")
-    huber_k = _picp_huber_k(huber_k, "projective_icp_color")
-    _picp_flag("projective_icp_color", "return_scale", return_scale)
-    color_huber_delta = _picp_huber("color_huber_delta", color_huber_delta, "projective_icp_color")
-    dist_th, dot_th = _picp_args(stride, numiters, damp, dist_thresh, angle_thresh)
-    who = "projective_icp_color"
-    seqs, held, dev, Bn, H, W = _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, init_poses, stride,
-                                           color=True, scaled=huber_k > 0,
-                                           color_scaled=color_huber_k > 0 or (weights is not None and huber_k > 0))
-    cseqs = _picp_color_seqs(who, seqs, held, Bn, H, W, color, model)
-    T, trace, prm = _picp_outputs(who, [c.base for c in cseqs], dev, out, return_trace, PICP_COLOR_TRACE, stride,
-                                  numiters, damp, dist_th, dot_th)
-    scale = cscale = None
-    if weights is not None:
-        require_device(*weights, held[0])
-        scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale and huber_k > 0 else (None, None)
-        cscale, cptrs = _picp_scale_table(Bn, numiters, dev) if return_color_scale and color_huber_k > 0 else (None, None)
-        check(lib().gs_projective_icp_color_weighted_batch_f32(cseqs, _picp_weight_ptrs(weights), dptrs, cptrs, Bn, H, W,
-                                                               prm, weight, huber_delta, huber_k, color_huber_delta,
-                                                               color_huber_k, stream(dev)),
-              "gs_projective_icp_color_weighted_batch_f32")
-    elif color_huber_k > 0:
-        scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale and huber_k > 0 else (None, None)
-        cscale, cptrs = _picp_scale_table(Bn, numiters, dev) if return_color_scale else (None, None)
-        check(lib().gs_projective_icp_color_joint_scaled_batch_f32(cseqs, dptrs, cptrs, Bn, H, W, prm, weight, huber_k,
-                                                                   huber_delta, color_huber_k, color_huber_delta,
-                                                                   stream(dev)),
-              "gs_projective_icp_color_joint_scaled_batch_f32")
-    elif huber_k > 0:
-        scale, dptrs = _picp_scale_table(Bn, numiters, dev) if return_scale else (None, None)
-        check(lib().gs_projective_icp_color_scaled_batch_f32(cseqs, dptrs, Bn, H, W, prm, weight, huber_k, huber_delta,
-                                                             color_huber_delta, stream(dev)),
-              "gs_projective_icp_color_scaled_batch_f32")
-    elif huber_delta > 0 or color_huber_delta > 0:
-        check(lib().gs_projective_icp_color_robust_batch_f32(cseqs, Bn, H, W, prm, weight, huber_delta, color_huber_delta,
-                                                             stream(dev)),
-              "gs_projective_icp_color_robust_batch_f32")
-    else:
-        check(lib().gs_projective_icp_color_batch_f32(cseqs, Bn, H, W, prm, weight, stream(dev)),
-              "gs_projective_icp_color_batch_f32")
-    if return_scale and scale is None:
-        scale = torch.full((Bn, int(numiters)), huber_delta, dtype=f32, device=dev)
-    if return_color_scale and cscale is None:
-        cscale = torch.full((Bn, int(numiters)), color_huber_delta, dtype=f32, device=dev)
-    res = _picp_pack(T, trace, scale, return_trace, return_scale)
-    if return_color_scale:
-        res = (res if isinstance(res, tuple) else (res,)) + (cscale,)
-    return res
+    opt = _picp_options("projective_icp_color", flags=("return_scale", "return_color_scale"),
+                        color_weight=color_weight, color_huber_k=color_huber_k,
+                        return_color_scale=return_color_scale, huber_delta=huber_delta, huber_k=huber_k,
+                        return_scale=return_scale, color_huber_delta=color_huber_delta,
+                        geometry=(stride, numiters, damp, dist_thresh, angle_thresh))
+    return _picp_solve(opt, vertex, normal, depth, K, index, model_poses, maps, init_poses, color=color, model=model,
+                       out=out, weights=weights, return_trace=return_trace, return_scale=return_scale,
+                       return_color_scale=return_color_scale)
 
 
 def projective_icp_color(vertex, normal, depth, K, index, model_pose, map_points, map_normals, init_pose, color, model,
@@ -1845,26 +1873,21 @@ def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_p
     each (the constant where its rule is off).
     pixel_weights ((H, W) float32, gs_projective_icp_color_weighted_rows_f32): as in projective_icp_rows; the two weight
     tables hold the total weights (pixel weight times Huber weight); the returned shapes are those of the call without."""
-    weight = _picp_color_weight(color_weight)
-    huber_k = _picp_huber_k(huber_k, "projective_icp_color_rows")
-    color_huber_k = _picp_color_huber_k(color_huber_k, "projective_icp_color_rows", weight)
-    huber_delta = _picp_huber("huber_delta", huber_delta, "projective_icp_color_rows")
-    color_huber_delta = _picp_huber("color_huber_delta", color_huber_delta, "projective_icp_color_rows")
-    if not isinstance(return_weights, bool):
-        raise TypeError("projective_icp_color_rows: return_weights must be of type bool; but was of type {}.".format(
-            type(return_weights)))
-    dist_th, dot_th = _picp_args(stride, 1, 1.0, dist_thresh, angle_thresh)
     who = "projective_icp_color_rows"
+    opt = _picp_options(who, flags=("return_weights",), color_weight=color_weight, huber_k=huber_k,
+                        color_huber_k=color_huber_k, huber_delta=huber_delta, color_huber_delta=color_huber_delta,
+                        return_weights=return_weights,
+                        geometry=(stride, 1, 1.0, dist_thresh, angle_thresh))
     _picp_tensors(who, (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
                         ("model_pose", model_pose), ("pose", pose), ("color", color), ("model_intensity", model)))
     if pixel_weights is not None:
         _picp_tensors(who, (("pixel_weights", pixel_weights),))
     weights = _picp_pixel_weights(who, None if pixel_weights is None else pixel_weights.unsqueeze(0), depth.unsqueeze(0))
+    export, sizer = _picp_route("color_rows", opt, weights=weights is not None, tables=return_weights)
     seqs, held, dev, _, H, W = _picp_seqs(who, vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0),
                                           K.reshape(1, 4, 4), index.unsqueeze(0), model_pose.reshape(1, 4, 4),
-                                          [(map_points, map_normals, None, n_dev)], pose.reshape(1, 4, 4), stride,
-                                          color=True, scaled=huber_k > 0 or color_huber_k > 0,
-                                          color_scaled=huber_k > 0 or color_huber_k > 0)
+                                          [(map_points, map_normals, None, n_dev)], pose.reshape(1, 4, 4))
+    _picp_scratch(seqs, dev, sizer, H, W, stride)
     cseqs = _picp_color_seqs(who, seqs, held, 1, H, W, color.unsqueeze(0), model.unsqueeze(0))
     ns = _picp_nslots(H, W, stride)
     e = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)   # noqa: E731
@@ -1872,43 +1895,28 @@ def projective_icp_color_rows(vertex, normal, depth, K, index, model_pose, map_p
                               e(ns, f32), e(ns, torch.int32), e(28, torch.float64), e(1, torch.int64), e(1, torch.int64))
     if weights is not None:
         require_device(*weights, held[0])
-        scaled = huber_k > 0 or color_huber_k > 0
-        wt = (e(ns, f32), e(ns, f32)) if return_weights else (None, None)
-        th = (torch.full((1,), huber_delta, dtype=f32, device=dev),
-              torch.full((1,), color_huber_delta, dtype=f32, device=dev)) if return_weights and scaled else (None, None)
-        check(lib().gs_projective_icp_color_weighted_rows_f32(cseqs, ptr(weights[0]), H, W, int(stride), dist_th, dot_th,
-                                                              weight, huber_delta, huber_k, color_huber_delta,
-                                                              color_huber_k, *[ptr(t) for t in res[:7]], ptr(wt[0]),
-                                                              ptr(wt[1]), *[ptr(t) for t in res[7:]], ptr(th[0]),
-                                                              ptr(th[1]), stream(dev)),
-              "gs_projective_icp_color_weighted_rows_f32")
-        if not return_weights:
-            return res
-        return (res,) + wt + th if scaled else (res,) + wt
-    if huber_k > 0 or color_huber_k > 0:
-        wt = (e(ns, f32), e(ns, f32)) if return_weights else (None, None)
-        # (a threshold whose rule is off is the constant: the library writes the estimated ones only)
-        th = (torch.full((1,), huber_delta, dtype=f32, device=dev),
-              torch.full((1,), color_huber_delta, dtype=f32, device=dev)) if return_weights else (None, None)
-        check(lib().gs_projective_icp_color_joint_scaled_rows_f32(cseqs, H, W, int(stride), dist_th, dot_th, weight,
-                                                                  huber_k, huber_delta, color_huber_k, color_huber_delta,
-                                                                  *[ptr(t) for t in res[:7]], ptr(wt[0]), ptr(wt[1]),
-                                                                  *[ptr(t) for t in res[7:]], ptr(th[0]), ptr(th[1]),
-                                                                  stream(dev)),
-              "gs_projective_icp_color_joint_scaled_rows_f32")
-        return (res,) + wt + th if return_weights else res
-    if huber_delta > 0 or color_huber_delta > 0 or return_weights:
-        wt = (e(ns, f32), e(ns, f32)) if return_weights else (None, None)
-        check(lib().gs_projective_icp_color_robust_rows_f32(cseqs, H, W, int(stride), dist_th, dot_th, weight,
-                                                            huber_delta, color_huber_delta, *[ptr(t) for t in res[:7]],
-                                                            ptr(wt[0]), ptr(wt[1]), *[ptr(t) for t in res[7:]],
-                                                            stream(dev)),
-              "gs_projective_icp_color_robust_rows_f32")
-        return (res,) + wt if return_weights else res
-    check(lib().gs_projective_icp_color_rows_f32(cseqs, H, W, int(stride), dist_th, dot_th, weight,
-                                                 *[ptr(t) for t in res], stream(dev)),
-          "gs_projective_icp_color_rows_f32")
-    return res
+    delta, k, cdelta, ck = opt.huber_delta, opt.huber_k, opt.color_huber_delta, opt.color_huber_k
+    # the two weight tables and, where a median rule runs, the two thresholds follow the rows when asked for (a
+    # threshold whose rule is off is the constant: the library writes the estimated ones only)
+    extra = ()
+    if return_weights:
+        extra = (e(ns, f32), e(ns, f32)) + ((torch.full((1,), delta, dtype=f32, device=dev),
+                                             torch.full((1,), cdelta, dtype=f32, device=dev)) if k > 0 or ck > 0 else ())
+    wt, wtc, th, cth = (ptr(t) for t in (extra + (None,) * 4)[:4])
+    L, st, gates = lib(), stream(dev), (H, W, int(stride), opt.dist_th, opt.dot_th, opt.color_weight)
+    rows, sums = [ptr(t) for t in res[:7]], [ptr(t) for t in res[7:]]
+    if export == "color_weighted_rows":
+        status = L.gs_projective_icp_color_weighted_rows_f32(cseqs, ptr(weights[0]), *gates, delta, k, cdelta, ck, *rows,
+                                                             wt, wtc, *sums, th, cth, st)
+    elif export == "color_joint_scaled_rows":
+        status = L.gs_projective_icp_color_joint_scaled_rows_f32(cseqs, *gates, k, delta, ck, cdelta, *rows, wt, wtc,
+                                                                 *sums, th, cth, st)
+    elif export == "color_robust_rows":
+        status = L.gs_projective_icp_color_robust_rows_f32(cseqs, *gates, delta, cdelta, *rows, wt, wtc, *sums, st)
+    else:
+        status = L.gs_projective_icp_color_rows_f32(cseqs, *gates, *rows, *sums, st)
+    check(status, "gs_projective_icp_%s_f32" % export)
+    return (res,) + extra if return_weights else res
 
 
 # ----------------------------------------------------------------------------------- pruning the map

@@ -185,12 +185,11 @@ def joint_entry(ops, fx, stride, numiters, hk, hd, ck, cd, want_deltas=True):
     b = lambda x: x.unsqueeze(0)      # noqa: E731
     who = "projective_icp_color"
     seqs, held, device, Bn, H, W = ops._picp_seqs(who, b(t[0]), b(t[1]), b(t[2]), b(t[3]), b(t[4]), b(t[5]),
-                                                  [(t[6], t[7], None, n_dev)], b(dev(fx["T0"])), stride, color=True,
-                                                  scaled=True, color_scaled=True)
+                                                  [(t[6], t[7], None, n_dev)], b(dev(fx["T0"])))
+    ops._picp_scratch(seqs, device, "joint_scaled", H, W, stride)
     cseqs = ops._picp_color_seqs(who, seqs, held, Bn, H, W, b(dev(fx["color"])), b(dev(fx["model"])))
-    dist_th, dot_th = ops._picp_args(stride, numiters, 1e-8, 0.1, 30.0)
-    T, trace, prm = ops._picp_outputs(who, [c.base for c in cseqs], device, None, True, ops.PICP_COLOR_TRACE, stride,
-                                      numiters, 1e-8, dist_th, dot_th)
+    opt = ops._picp_options(who, geometry=(stride, numiters, 1e-8, 0.1, 30.0))
+    T, trace, prm = ops._picp_outputs(who, [c.base for c in cseqs], device, None, True, ops.PICP_COLOR_TRACE, opt)
     scale, dptrs = ops._picp_scale_table(Bn, numiters, device) if want_deltas else (None, None)
     _C.check(_C.lib().gs_projective_icp_color_joint_scaled_batch_f32(cseqs, dptrs, None, Bn, H, W, prm, WEIGHT, hk, hd, ck,
                                                                      cd, _C.stream(device)), "joint scaled")

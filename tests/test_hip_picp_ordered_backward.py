@@ -51,9 +51,9 @@ def tape_of(ops, fxs, counts, stride, numiters, kw, huber_delta=0.0, huber_k=0.0
                None if n is None else torch.tensor([n], dtype=torch.int64, device="cuda")) for q, n in zip(fxs, counts)]
     t.kw = dict(stride=stride, numiters=numiters, huber_delta=huber_delta, huber_k=huber_k, **kw)
     t.tapes = torch.empty((len(fxs), ops.projective_icp_tape_bytes(numiters)), dtype=torch.uint8, device="cuda")
-    dist_th, dot_th = ops._picp_args(stride, numiters, kw["damp"], kw["dist_thresh"], kw["angle_thresh"])
-    t.pose = ops._picp_solve(*t.args, t.maps, st("T0"), stride, numiters, kw["damp"], dist_th, dot_th, False, None, t.tapes,
-                             huber_delta, huber_k, False)
+    opt = ops._picp_options("projective_icp", geometry=(stride, numiters, kw["damp"], kw["dist_thresh"],
+                                                        kw["angle_thresh"]), huber_delta=huber_delta, huber_k=huber_k)
+    t.pose = ops._picp_solve(opt, *t.args, t.maps, st("T0"), tapes=t.tapes)
     return t
 
 

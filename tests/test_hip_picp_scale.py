@@ -326,10 +326,10 @@ def test_autograd_gives_the_gradients_of_the_tensor_level_call(ops):
     maps = [(t["points"], t["normals"], None, t["n_dev"])]
     kw = dict(stride=c.stride, numiters=c.numiters, **c.kw)
     tapes = torch.empty((1, ops.projective_icp_tape_bytes(c.numiters)), dtype=torch.uint8, device="cuda")
-    dist_th, dot_th = ops._picp_args(c.stride, c.numiters, c.kw["damp"], c.kw["dist_thresh"], c.kw["angle_thresh"])
-    T, _, scale = ops._picp_solve(b("vertex"), b("normal"), b("depth"), b("K"), b("index"), b("model_pose"), maps, b("T0"),
-                                  c.stride, c.numiters, c.kw["damp"], dist_th, dot_th, True, None, tapes, 0.0, c.huber_k,
-                                  True)
+    opt = ops._picp_options("projective_icp", geometry=(c.stride, c.numiters, c.kw["damp"], c.kw["dist_thresh"],
+                                                        c.kw["angle_thresh"]), huber_k=c.huber_k)
+    T, _, scale = ops._picp_solve(opt, b("vertex"), b("normal"), b("depth"), b("K"), b("index"), b("model_pose"), maps,
+                                  b("T0"), tapes=tapes, return_trace=True, return_scale=True)
     assert np.array_equal(bits(host(T[0])), bits(c.assoc.pose))
     # the tape row holds the iteration's threshold in pad[0] (byte 312 of 328)
     taped = host(tapes).reshape(c.numiters, 328)[:, 312:316].copy().view(F).reshape(-1)

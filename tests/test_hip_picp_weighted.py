@@ -149,11 +149,12 @@ def taped(ops, fx, stride, weights, huber_delta=0.0, huber_k=0.0):
     """(pose, trace, thresholds, tape bytes) of the taped solve, with pixel weights or through the unweighted entry"""
     b = lambda k: dev(fx[k]).unsqueeze(0)      # noqa: E731
     tapes = torch.zeros((1, ops.projective_icp_tape_bytes(NUMITERS)), dtype=torch.uint8, device="cuda")
-    dist_th, dot_th = ops._picp_args(stride, NUMITERS, 1e-8, 0.1, 30.0)
+    opt = ops._picp_options("projective_icp", geometry=(stride, NUMITERS, 1e-8, 0.1, 30.0), huber_delta=huber_delta,
+                            huber_k=huber_k)
     w = None if weights is None else [dev(weights)]
-    res = ops._picp_solve(b("vertex"), b("normal"), b("depth"), b("K"), b("index"), b("model_pose"),
-                          [(dev(fx["points"]), dev(fx["normals"]), None, None)], b("T0"), stride, NUMITERS, 1e-8, dist_th,
-                          dot_th, True, None, tapes, huber_delta, huber_k, True, w)
+    res = ops._picp_solve(opt, b("vertex"), b("normal"), b("depth"), b("K"), b("index"), b("model_pose"),
+                          [(dev(fx["points"]), dev(fx["normals"]), None, None)], b("T0"), tapes=tapes, weights=w,
+                          return_trace=True, return_scale=True)
     torch.cuda.synchronize()
     return [host(x) for x in res] + [host(tapes)]
 
@@ -368,9 +369,8 @@ def test_outputs_not_asked_for(ops):
     args = [b(k) for k in ("vertex", "normal", "depth", "K", "index", "model_pose")]
     maps = [(dev(fx["points"]), dev(fx["normals"]), None, None)]
     tapes = torch.empty((1, ops.projective_icp_tape_bytes(NUMITERS)), dtype=torch.uint8, device="cuda")
-    dist_th, dot_th = ops._picp_args(4, NUMITERS, 1e-8, 0.1, 30.0)
-    ops._picp_solve(*args, maps, b("T0"), 4, NUMITERS, 1e-8, dist_th, dot_th, False, None, tapes, DELTA, 0.0, False,
-                    [dev(wts)])
+    opt = ops._picp_options("projective_icp", geometry=(4, NUMITERS, 1e-8, 0.1, 30.0), huber_delta=DELTA)
+    ops._picp_solve(opt, *args, maps, b("T0"), tapes=tapes, weights=[dev(wts)])
     kw = dict(stride=4, numiters=NUMITERS, huber_delta=DELTA, pixel_weights=dev(wts)[None])
     res = ops.projective_icp_backward_batch(*args, maps, tapes, dev(T_BAR)[None], want_pixel_weights=False, **kw)
     assert len(res) == 4 and res[3] is None and same(res[0][0], full[0])
@@ -412,9 +412,8 @@ def test_backward_with_a_null_weights_entry(ops, deterministic):
              None if q["n_dev"] is None else torch.tensor([q["n_dev"]], dtype=torch.int64, device="cuda")) for q in seqs]
     given = [dev(wts[0]), None, dev(wts[2])]
     tapes = torch.empty((3, ops.projective_icp_tape_bytes(NUMITERS)), dtype=torch.uint8, device="cuda")
-    dist_th, dot_th = ops._picp_args(4, NUMITERS, 1e-8, 0.1, 30.0)
-    T = ops._picp_solve(*args, maps, st("T0"), 4, NUMITERS, 1e-8, dist_th, dot_th, False, None, tapes, DELTA, 0.0, False,
-                        given)
+    opt = ops._picp_options("projective_icp", geometry=(4, NUMITERS, 1e-8, 0.1, 30.0), huber_delta=DELTA)
+    T = ops._picp_solve(opt, *args, maps, st("T0"), tapes=tapes, weights=given)
     vb, rows_, ib, wb = ops.projective_icp_backward_batch(*args, maps, tapes, dev(T_BAR)[None].repeat(3, 1, 1), stride=4,
                                                           numiters=NUMITERS, huber_delta=DELTA, pixel_weights=given,
                                                           want_pixel_weights=True, deterministic=deterministic)

@@ -176,10 +176,10 @@ def parent_robust_solve(ops, parent, args, stride, numiters, huber_delta):
     """the constant-threshold robust solve of another build's library on descriptors filled by this tree's Python layer
     (the structs are part of the ABI, which both share)"""
     from gradslam_amd import _C
-    dist_th, dot_th = ops._picp_args(stride, numiters, 1e-8, 0.1, 30.0)
-    seqs, held, dev, Bn, Hh, Ww = ops._picp_seqs("projective_icp", *args, stride)
-    T, _, prm = ops._picp_outputs("projective_icp", list(seqs), dev, None, False, ops.PICP_TRACE, stride, numiters, 1e-8,
-                                  dist_th, dot_th)
+    opt = ops._picp_options("projective_icp", geometry=(stride, numiters, 1e-8, 0.1, 30.0))
+    seqs, held, dev, Bn, Hh, Ww = ops._picp_seqs("projective_icp", *args)
+    ops._picp_scratch(seqs, dev, "plain", Hh, Ww, stride)
+    T, _, prm = ops._picp_outputs("projective_icp", list(seqs), dev, None, False, ops.PICP_TRACE, opt)
     st = ops.stream(dev)
 
     def call():
@@ -346,8 +346,8 @@ def backward_times(torch, gs, ops, reps=5, rounds=7, parent=None, pixel_weights=
         for stride in (4, 1):
             numiters = 10
             tapes = torch.empty((B, ops.projective_icp_tape_bytes(numiters)), dtype=torch.uint8, device="cuda")
-            dist_th, dot_th = ops._picp_args(stride, numiters, 1e-8, 0.1, 30.0)
-            _, trace = ops._picp_solve(*args, prev[:, 0], stride, numiters, 1e-8, dist_th, dot_th, True, None, tapes)
+            opt = ops._picp_options("projective_icp", geometry=(stride, numiters, 1e-8, 0.1, 30.0))
+            _, trace = ops._picp_solve(opt, *args, prev[:, 0], tapes=tapes, return_trace=True)
 
             def call(deterministic):
                 return ops.projective_icp_backward_batch(*args, tapes, pose_bar, stride=stride, numiters=numiters,
@@ -370,8 +370,7 @@ def backward_times(torch, gs, ops, reps=5, rounds=7, parent=None, pixel_weights=
                 fns = {"atomic": via(None, False), "ordered": via(None, True), "atomic_parent": via(parent, False)}
             if wts is not None:   # the weighted backward on the weighted forward's tape, pixel_weights_bar asked for
                 wtapes = torch.empty_like(tapes)
-                ops._picp_solve(*args, prev[:, 0], stride, numiters, 1e-8, dist_th, dot_th, True, None, wtapes, 0.0, 0.0,
-                                False, list(wts))
+                ops._picp_solve(opt, *args, prev[:, 0], tapes=wtapes, weights=list(wts), return_trace=True)
 
                 def wcall(deterministic):
                     return ops.projective_icp_backward_batch(*args, wtapes, pose_bar, stride=stride, numiters=numiters,
