@@ -279,6 +279,10 @@ _PROTOS = {
     "gs_projective_icp_weighted_backward_batch_f32": [C.POINTER(PicpOrderedBackwardSeq), C.POINTER(C.c_void_p),
                                                       C.POINTER(C.c_void_p), _i32, _i32, _i32, C.POINTER(PicpParams),
                                                       _f, _i32, _i32, _vp, _i64, _vp],
+    "gs_picp_outlier_classes_scratch_bytes": [_i32, _i32],
+    "gs_picp_outlier_classes_batch_f32": [C.POINTER(PicpSeq), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_void_p), _i32, _i32, _i32, _f, _f, _f, _f, _f, _vp],
+    "gs_region_mask_u8": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f, _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,
             "gs_knn1_grid_scratch_bytes": _i64, "gs_update_map_scratch_bytes": _i64, "gs_global_maps_pose_backward_scratch_bytes": _i64, "gs_icp_tape_bytes": _i64, "gs_icp_backward_scratch_bytes": _i64,
@@ -291,7 +295,8 @@ _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scrat
             "gs_projective_icp_color_joint_scaled_scratch_bytes": _i64, "gs_voxel_keep_scratch_bytes": _i64,
             "gs_projective_icp_ordered_backward_scratch_bytes": _i64,
             "gs_projective_icp_ordered_backward_sort_scratch_bytes": _i64,
-            "gs_projective_icp_weighted_backward_scratch_bytes": _i64}
+            "gs_projective_icp_weighted_backward_scratch_bytes": _i64,
+            "gs_picp_outlier_classes_scratch_bytes": _i64}
 EXPORTS = tuple(_PROTOS)
 
 

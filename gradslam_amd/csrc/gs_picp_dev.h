@@ -309,6 +309,9 @@ struct PiScale {
 // cleared)
 // weighted: the WEIGHTED instances of the residual pass (a masked slot has no key: it is in no median)
 void picp_scale_launch(const PiScaleBatch& sb, const PiScalePick& pk, bool first, bool weighted, hipStream_t st);
+// ... and its first half alone, the clear (first) and the residual pass: the key tables and the first digit's counters
+// for a caller that selects with a kernel of its own (gs_picp_outliers.hip, through gs_picp_scale_dev.h)
+void picp_scale_keys_launch(const PiScaleBatch& sb, const PiScalePick& pk, bool first, bool weighted, hipStream_t st);
 
 constexpr int GS_PS_BINS = 2048;   // values of an 11-bit digit of a key
 static inline size_t picp_keys_bytes(int64_t nslots) { return gs_align((size_t)nslots * sizeof(uint32_t)); }

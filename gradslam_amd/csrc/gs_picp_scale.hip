@@ -34,13 +34,10 @@
 // The threshold goes to the sequence's device float, which the robust linearise kernels read (PiSeq::delta_dev; the
 // colour one: PicSeq::cdelta_dev of gs_picp_color.hip) and the
 // finish kernel copies to the tape row's pad[0], and to the caller's table of thresholds when there is one.
+// The selection itself (ps_pick, ps_select_median) is gs_picp_scale_dev.h's, shared with gs_picp_outliers.hip.
 #include "gs_picp_color_dev.h"
+#include "gs_picp_scale_dev.h"
 
-constexpr int GS_PS_THREADS = 1024;
-static_assert(GS_PS_BINS == 2 * GS_PS_THREADS, "two bins per thread of the select block");
-static_assert(GS_PS_BINS % GS_PI_CHUNK == 0, "the residual pass clears and flushes whole rounds of bins");
-constexpr uint32_t GS_PS_UNUSED = 0xFFFFFFFFu;
-constexpr int GS_PS_TOP_SHIFT = 21;   // the first digit: the top 11 bits
 
 // The residual pass.  GEO / COL: the residuals asked for (at least one); for the other one nothing is computed, loaded
 // or stored.  One pi_associate per slot serves both.  Each residual has its own first-digit histogram in LDS (8 KB; both:
@@ -118,97 +115,20 @@ __global__ void __launch_bounds__(GS_PI_CHUNK) gs_weighted_picp_scale_joint_keys
   ps_keys<true, true, true>(sb);
 }
 
-// The bin of a 2048-bin histogram that holds `rank` (0-based, below the histogram's total) and the rank inside it, for
-// every thread of the select block; h0, h1: the counts of the thread's bins 2 tid, 2 tid + 1.  total: the histogram's.
-GS_DEV void ps_pick(const uint32_t h0, const uint32_t h1, const uint32_t rank, const bool have_rank, uint32_t* wsum,
-                    uint32_t* sel, uint32_t& bin, uint32_t& inside, uint32_t& total) {
-  const int tid = threadIdx.x, lane = tid & (GS_WAVE - 1), wave = tid / GS_WAVE;
-  const uint32_t v = h0 + h1;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < GS_WAVE; d <<= 1) {
-    const uint32_t y = __shfl_up(inc, d, GS_WAVE);
-    if (lane >= d) inc += y;
-  }
-  if (lane == GS_WAVE - 1) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t excl = inc - v;
-  total = 0u;
-#pragma unroll
-  for (int w = 0; w < GS_PS_THREADS / GS_WAVE; ++w) {
-    if (w < wave) excl += wsum[w];
-    total += wsum[w];
-  }
-  // the rank of the first digit is known only with the total: (total - 1) / 2
-  const uint32_t want = have_rank ? rank : (total > 0u ? (total - 1u) / 2u : 0u);
-  // exactly one thread when total > 0: the bins are disjoint ranges of ranks
-  if (want >= excl && want - excl < v) {
-    const bool second = want - excl >= h0;
-    sel[0] = 2u * (uint32_t)tid + (second ? 1u : 0u);
-    sel[1] = want - excl - (second ? h0 : 0u);
-  }
-  __syncthreads();
-  bin = sel[0];
-  inside = sel[1];
-  __syncthreads();   // (wsum and sel are rewritten by the next call)
-}
-
 // A grid of B * pk.count blocks: block x selects residual pk.first + x / B of sequence x % B, with that residual's keys,
 // counters, constant, floor and destination.
 __global__ void __launch_bounds__(GS_PS_THREADS) gs_picp_scale_select_kernel(const PiScaleBatch sb,
                                                                              const PiScalePick pk) {
-  __shared__ uint32_t hist[GS_PS_BINS];
-  __shared__ uint32_t wsum[GS_PS_THREADS / GS_WAVE];
-  __shared__ uint32_t sel[2];
   const int which = pk.first + (int)blockIdx.x / sb.g.B;
   const PiScaleRes& q = sb.s[blockIdx.x % sb.g.B].r[which];
   const float c = pk.c[which], floor = pk.floor[which];
   const int tid = threadIdx.x;
-  const int nslots = sb.g.nslots;
-  if (tid == 0) { sel[0] = 0u; sel[1] = 0u; }
-  // the first digit: the counters of the residual pass, cleared for the next iteration
-  uint32_t h0 = q.hist[2 * tid], h1 = q.hist[2 * tid + 1];
-  q.hist[2 * tid] = 0u;
-  q.hist[2 * tid + 1] = 0u;
-  uint32_t bin, rank, n;
-  ps_pick(h0, h1, 0u, false, wsum, sel, bin, rank, n);
+  uint32_t n;
+  const uint32_t med = ps_select_median(q, sb.g.nslots, n);
   // no slot has the row: +0.0 for the geometric threshold, the floor for the colour one (no weight is read then)
   float delta = which == PS_COLOR ? floor : 0.0f;
   if (n > 0u) {   // (block-uniform)
-    uint32_t prefix = bin << GS_PS_TOP_SHIFT, known = (uint32_t)(GS_PS_BINS - 1) << GS_PS_TOP_SHIFT;
-    const uint4* keys4 = reinterpret_cast<const uint4*>(q.keys);   // (16-byte aligned: the entries check the scratch, the offsets are multiples of 256)
-    const int n4 = nslots / 4;
-    constexpr int DEPTH = 8;   // 16-byte loads in flight per thread
-#pragma unroll 1
-    for (int pass = 1; pass < 3; ++pass) {
-      const int shift = pass == 1 ? 10 : 0;
-      const uint32_t digit = pass == 1 ? 2047u : 1023u;
-      hist[tid] = 0u;
-      hist[tid + GS_PS_THREADS] = 0u;
-      __syncthreads();
-      const auto count = [&](const uint32_t k) {
-        if ((k & known) == prefix) atomicAdd(&hist[(k >> shift) & digit], 1u);
-      };
-      int i = tid;
-      for (; i + (DEPTH - 1) * GS_PS_THREADS < n4; i += DEPTH * GS_PS_THREADS) {
-        uint4 k[DEPTH];
-#pragma unroll
-        for (int r = 0; r < DEPTH; ++r) k[r] = keys4[i + r * GS_PS_THREADS];
-#pragma unroll
-        for (int r = 0; r < DEPTH; ++r) { count(k[r].x); count(k[r].y); count(k[r].z); count(k[r].w); }
-      }
-      for (; i < n4; i += GS_PS_THREADS) {
-        const uint4 k = keys4[i];
-        count(k.x); count(k.y); count(k.z); count(k.w);
-      }
-      for (int j = 4 * n4 + tid; j < nslots; j += GS_PS_THREADS) count(q.keys[j]);
-      __syncthreads();
-      uint32_t total;
-      ps_pick(hist[2 * tid], hist[2 * tid + 1], rank, true, wsum, sel, bin, rank, total);
-      prefix |= bin << shift;
-      known |= digit << shift;
-    }
-    delta = c * __uint_as_float(prefix);
+    delta = c * __uint_as_float(med);
     if (!(delta > floor)) delta = floor;
   }
   if (tid == 0) {
@@ -224,8 +144,8 @@ __global__ void __launch_bounds__(GS_PS_THREADS) gs_picp_scale_clear_kernel(cons
   hist[2 * threadIdx.x + 1] = 0u;
 }
 
-void picp_scale_launch(const PiScaleBatch& sb, const PiScalePick& pk, const bool first, const bool weighted,
-                       hipStream_t st) {
+void picp_scale_keys_launch(const PiScaleBatch& sb, const PiScalePick& pk, const bool first, const bool weighted,
+                             hipStream_t st) {
   const dim3 per_res((unsigned)sb.g.B * (unsigned)pk.count), chunks((unsigned)sb.g.B * (unsigned)sb.g.nchunks);
   if (first) hipLaunchKernelGGL(gs_picp_scale_clear_kernel, per_res, dim3(GS_PS_THREADS), 0, st, sb, pk);
   const auto keys = pk.count == 2 ? (weighted ? gs_weighted_picp_scale_joint_keys_kernel : gs_picp_scale_joint_keys_kernel)
@@ -233,5 +153,11 @@ void picp_scale_launch(const PiScaleBatch& sb, const PiScalePick& pk, const bool
                         ? (weighted ? gs_weighted_picp_scale_color_keys_kernel : gs_picp_scale_color_keys_kernel)
                         : (weighted ? gs_weighted_picp_scale_keys_kernel : gs_picp_scale_keys_kernel);
   hipLaunchKernelGGL(keys, chunks, dim3(GS_PI_CHUNK), 0, st, sb);
-  hipLaunchKernelGGL(gs_picp_scale_select_kernel, per_res, dim3(GS_PS_THREADS), 0, st, sb, pk);
+}
+
+void picp_scale_launch(const PiScaleBatch& sb, const PiScalePick& pk, const bool first, const bool weighted,
+                       hipStream_t st) {
+  picp_scale_keys_launch(sb, pk, first, weighted, st);
+  hipLaunchKernelGGL(gs_picp_scale_select_kernel, dim3((unsigned)sb.g.B * (unsigned)pk.count), dim3(GS_PS_THREADS), 0, st,
+                     sb, pk);
 }

@@ -10,7 +10,8 @@ the live frame's colour is compared with it.  `huber_delta` / `color_huber_delta
 `huber_k` > 0 estimates the geometric threshold from the residuals in every iteration (the *_scaled_* entry points),
 `color_huber_k` > 0 the colour threshold from the colour residuals (the *_joint_scaled_* entry points).  `pixel_weights`
 hands every solve a weight image made from the live frame (the *_weighted_* entry points); `axial_noise_weights` is a
-ready-made one."""
+ready-made one.  `outlier_mask` derives such a mask from the solve itself (gs_picp_outliers.hip): the outlier regions of
+the converged solve are masked and a few more iterations run without them."""
 from typing import Callable, Optional, Union
 
 import torch
@@ -92,6 +93,16 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             masked for the solve (the map update still sees it).  It is called once per `localize`.  With
             `differentiable=True` its output stays on the autograd tape: the parameters of a module get gradients.  Works
             with every threshold and with `color_weight`.
+        outlier_mask: None (the default: the calls and the pose bits above) or a dict with any of the keys hi, lo, floor,
+            min_support, grow, grow_depth (`ops.projective_icp_outliers_batch`; defaults 3.0, 1.5, 0.0, 6, 0, 0.02) and
+            refine_iters (default 5).  `localize` then runs the configured solve, builds the outlier mask at the poses it
+            reached (they stay on the device), and runs refine_iters more iterations of the same solve from those poses
+            with the masked pixels' weights set to 0 (the caller's `pixel_weights` elsewhere, or ones).  The mask of the
+            last call is kept in `last_outlier_mask` (B, H, W) bool.  Works with every threshold, `color_weight` and
+            `pixel_weights`; with `differentiable=True` the mask is a constant of the gradient like the association, the
+            two solves are two taped calls chained through the initial pose, and weights that require grad get their
+            gradient through the `torch.where` that applies the mask.  The parameters are starting points, not tuned to
+            any sensor.
 
     Unlike the point-cloud-pair providers it needs the map and the live frame themselves: call
     `localize(pointclouds, live_frame, prev_poses)`."""
@@ -102,7 +113,7 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                  color_weight: Union[float, int] = 0.0, huber_delta: Union[float, int] = 0.0,
                  color_huber_delta: Union[float, int] = 0.0, huber_k: Union[float, int] = 0.0,
                  color_huber_k: Union[float, int] = 0.0, deterministic_backward: Optional[bool] = None,
-                 pixel_weights: Optional[Callable] = None):
+                 pixel_weights: Optional[Callable] = None, outlier_mask: Optional[dict] = None):
         from .. import ops
         who = "ProjectiveICPOdometryProvider"
         if pixel_weights is not None and not callable(pixel_weights):
@@ -124,6 +135,10 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
         if color_huber_k > 0 and not color_weight > 0:
             raise ValueError("color_huber_k > 0 needs color_weight > 0: it estimates the Huber threshold of the colour "
                              "term")
+        # (validated after every other keyword: the refusals above and their order stay)
+        self.outlier_rule, self.refine_iters = self._outlier_mask(outlier_mask)
+        self.outlier_mask = None if outlier_mask is None else dict(outlier_mask)
+        self.last_outlier_mask = None
         # What every solve of localize runs with, fixed here: the validated record.  The attributes below are the values
         # as they were given, for the SLAM drivers and callers to read (the first five make _kwargs()); assigning to
         # one of them after construction does NOT reach localize -- build a new provider instead.
@@ -142,6 +157,28 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
         self.min_confidence = min_confidence
         self.radius = radius
         self.differentiable = differentiable
+
+    @staticmethod
+    def _outlier_mask(outlier_mask):
+        """(ops.OutlierRule, refine_iters) of the `outlier_mask` keyword, or (None, 0)"""
+        from .. import ops
+        if outlier_mask is None:
+            return None, 0
+        if not isinstance(outlier_mask, dict):
+            raise TypeError("outlier_mask must be None or a dict (hi, lo, floor, min_support, grow, grow_depth, "
+                            "refine_iters); but was of type {}.".format(type(outlier_mask)))
+        unknown = sorted(set(outlier_mask) - set(ops.OutlierRule._fields) - {"refine_iters"}, key=str)
+        if unknown:
+            raise TypeError("outlier_mask: unknown keys {}; it takes {} and refine_iters".format(
+                unknown, ", ".join(ops.OutlierRule._fields)))
+        rule = ops._outlier_rule("outlier_mask", **{k: v for k, v in outlier_mask.items() if k != "refine_iters"})
+        refine_iters = outlier_mask.get("refine_iters", 5)
+        if isinstance(refine_iters, bool) or not isinstance(refine_iters, int):
+            raise TypeError("outlier_mask: refine_iters must be of type int; but was of type {}.".format(
+                type(refine_iters)))
+        if refine_iters < 1:
+            raise ValueError("outlier_mask: refine_iters ({}) must be at least 1.".format(refine_iters))
+        return rule, refine_iters
 
     def _kwargs(self):
         return dict(stride=1 if self.stride is None else self.stride, numiters=self.numiters, damp=self.damp,
@@ -218,8 +255,27 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
         args = (fr.vertex_map[:, 0], fr.normal_map[:, 0], fr.depth_image[:, 0, ..., 0], K, view.index[:, 0], view_poses,
                 maps, poses)
         entries = ops._picp_pixel_weights("projective_icp_color" if colour else "projective_icp", weights, args[2])
-        if taped:
-            return ops._picp_taped(self.options, *args, weights, entries, guard=guard).unsqueeze(1)
-        out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=poses.device)
-        ops._picp_solve(self.options, *args, color=color, model=model, out=out.view(B, 4, 4), weights=entries)
-        return out
+        if self.outlier_rule is None:
+            if taped:
+                return ops._picp_taped(self.options, *args, weights, entries, guard=guard).unsqueeze(1)
+            out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=poses.device)
+            ops._picp_solve(self.options, *args, color=color, model=model, out=out.view(B, 4, 4), weights=entries)
+            return out
+        # The configured solve, the outlier mask at the poses it reached, then refine_iters more iterations of the same
+        # solve from those poses without the masked pixels.  Nothing is read back between the three.
+        who = "projective_icp_color" if colour else "projective_icp"
+
+        def solve(opt, init, w, w_entries):
+            if taped:
+                return ops._picp_taped(opt, *args[:7], init, w, w_entries, guard=guard)
+            return ops._picp_solve(opt, *args[:7], init, color=color, model=model, weights=w_entries)
+        first = solve(self.options, poses, weights, entries)
+        with torch.no_grad():   # (a constant of the gradient, like the association)
+            mask = ops.projective_icp_outliers_batch(*args[:7], first, dist_thresh=self.dist_thresh,
+                                                     angle_thresh=self.angle_thresh, pixel_weights=entries,
+                                                     **self.outlier_rule._asdict()).bool()
+        base = torch.ones((B, H, W), dtype=torch.float32, device=mask.device) if weights is None else weights
+        masked = torch.where(mask, torch.zeros((), dtype=torch.float32, device=mask.device), base)
+        self.last_outlier_mask = mask
+        return solve(self.options._replace(numiters=self.refine_iters), first, masked,
+                     ops._picp_pixel_weights(who, masked, args[2])).unsqueeze(1)

@@ -1727,8 +1727,131 @@ def projective_icp_rows(vertex, normal, depth, K, index, model_pose, map_points,
     return (res,) + extra if return_weights else res
 
 
+# ----------------------------------------------------------------------------------- projective ICP: the outlier mask
+OutlierRule = collections.namedtuple("OutlierRule", ["hi", "lo", "floor", "min_support", "grow", "grow_depth"],
+                                     defaults=(3.0, 1.5, 0.0, 6, 0, 0.02))
+OutlierRule.__doc__ = """The validated parameters of the outlier mask (gs_picp_outliers.hip): a pixel is strong when its
+residual exceeds hi * 1.4826 * median|b| (or the floor, metres) or one of the two gates rejected it, eligible from
+lo * 1.4826 * median|b|; a strong pixel with min_support strong pixels in its 3 x 3 window is a seed; the seeds grow for
+`grow` steps over eligible 4-neighbours whose depth differs by at most grow_depth metres.  The defaults are starting
+points, not tuned to any sensor."""
+OUTLIER_MAX_GROW = 16
+
+
+def _outlier_region_args(who, min_support, grow, grow_depth):
+    """the value checks of the region pass: (min_support, grow, grow_depth)"""
+    for name, val, lo, hi in (("min_support", min_support, 1, 9), ("grow", grow, 0, OUTLIER_MAX_GROW)):
+        if isinstance(val, bool) or not isinstance(val, int):
+            raise TypeError("{}: {} must be of type int; but was of type {}.".format(who, name, type(val)))
+        if not lo <= val <= hi:
+            raise ValueError("{}: {} ({}) must be within {} ... {}.".format(who, name, val, lo, hi))
+    return min_support, grow, _picp_number(who, "grow_depth", grow_depth)
+
+
+def _outlier_rule(who, hi=3.0, lo=1.5, floor=0.0, min_support=6, grow=0, grow_depth=0.02):
+    """Validates into an OutlierRule, in the order of its fields: hi >= lo > 0, floor >= 0 (all finite), min_support
+    within 1 ... 9, grow within 0 ... 16, grow_depth >= 0"""
+    hi, lo, floor = (_picp_number(who, name, val) for name, val in (("hi", hi), ("lo", lo), ("floor", floor)))
+    if not lo > 0:
+        raise ValueError("{}: lo ({}) must be positive.".format(who, lo))
+    if not hi >= lo:
+        raise ValueError("{}: hi ({}) must be at least lo ({}).".format(who, hi, lo))
+    return OutlierRule(hi, lo, floor, *_outlier_region_args(who, min_support, grow, grow_depth))
+
+
+def region_mask(classes, depth, *, min_support=6, grow=0, grow_depth=0.02):
+    """The region pass of the outlier mask (gs_region_mask_u8: one launch, tiles with a halo in LDS, bit-exact) for any
+    number of images: classes (..., H, W) uint8 (bit 0 strong, bit 1 eligible), depth (..., H, W) float32.  A strong
+    pixel with at least min_support strong pixels in its 3 x 3 window (itself included, pixels outside the image not) is
+    a seed; for `grow` steps the seeds spread to eligible 4-neighbours whose depth differs by at most grow_depth.
+    Returns the mask (..., H, W) uint8 of 0 / 1."""
+    who = "region_mask"
+    _picp_tensors(who, (("classes", classes), ("depth", depth)))
+    min_support, grow, grow_depth = _outlier_region_args(who, min_support, grow, grow_depth)
+    if classes.dtype != torch.uint8:
+        raise TypeError("{}: classes must be uint8; got {}".format(who, classes.dtype))
+    if depth.dtype != f32:
+        raise TypeError("{}: depth must be float32; got {}".format(who, depth.dtype))
+    if classes.ndim < 2 or tuple(classes.shape) != tuple(depth.shape) or classes.numel() == 0:
+        raise ValueError("{}: expected classes and depth of one shape (..., H, W) with at least one pixel; got {} and "
+                         "{}".format(who, tuple(classes.shape), tuple(depth.shape)))
+    H, W = (int(x) for x in classes.shape[-2:])
+    if H * W >= 1 << 31:
+        raise ValueError("{}: image too large ({} x {})".format(who, H, W))
+    _warn_detached(who, depth)
+    classes, depth = classes.contiguous(), depth.detach().contiguous()
+    dev = require_device(classes, depth)
+    mask = torch.empty(classes.shape, dtype=torch.uint8, device=dev)
+    check(lib().gs_region_mask_u8(ptr(classes), ptr(depth), ptr(mask), classes.numel() // (H * W), H, W, min_support, grow,
+                                  grow_depth, stream(dev)), "gs_region_mask_u8")
+    return mask
+
+
+def projective_icp_outliers_batch(vertex, normal, depth, K, index, model_poses, maps, poses, *, hi=3.0, lo=1.5, floor=0.0,
+                                  min_support=6, grow=0, grow_depth=0.02, dist_thresh=0.1, angle_thresh=30.0,
+                                  pixel_weights=None, return_classes=False, return_thresholds=False):
+    """The outlier mask of B sequences at `poses` (B, 4, 4), inputs as projective_icp_batch: which pixels of the live
+    frames the model view does not explain, as a (B, H, W) uint8 image of 0 / 1 -- at every pixel, whatever stride the
+    solve ran with.  The rule (gs_picp_outliers.hip, tests/outlier_mask_ref.py; everything on the device, nothing read
+    back, bit-exact): code and residual b of each pixel as projective_icp_rows(stride=1) gives them at the pose; med =
+    the lower median of |b| over the used pixels; a pixel is STRONG when it is used and |b| > max(hi * 1.4826 * med,
+    floor), or when a gate rejected it (too far, normals disagree), ELIGIBLE when strong or used with |b| > max(lo *
+    1.4826 * med, floor); a strong pixel with at least min_support strong pixels in its 3 x 3 window is a seed, and the
+    seeds grow for `grow` steps over eligible 4-neighbours whose depth differs by at most grow_depth metres (region_mask).
+    Pixels without depth, outside the model view, without a winner or masked by pixel_weights are never in the mask.
+    floor (metres) matters on data without noise, where the median is 0 and every residual would be an outlier.
+    return_classes: also the class bytes (B, H, W) uint8 (bit 0 strong, bit 1 eligible); return_thresholds: also the
+    two thresholds (B, 2) float32, last."""
+    who = "projective_icp_outliers"
+    weights = _picp_pixel_weights(who, pixel_weights, depth)
+    dist_th, dot_th = _picp_args(1, 1, 1.0, dist_thresh, angle_thresh)
+    rule = _outlier_rule(who, hi, lo, floor, min_support, grow, grow_depth)
+    _picp_flag(who, "return_classes", return_classes)
+    _picp_flag(who, "return_thresholds", return_thresholds)
+    seqs, held, dev, Bn, H, W = _picp_seqs(who, vertex, normal, depth, K, index, model_poses, maps, poses)
+    L, ws = lib(), Workspace.get(dev)
+    nbytes = L.gs_picp_outlier_classes_scratch_bytes(H, W)
+    for b, u in enumerate(seqs):
+        u.scratch = ws.bytes("picp_outliers%d" % b, nbytes).data_ptr()
+    wptrs = None
+    if weights is not None:
+        require_device(*weights, held[0])
+        wptrs = _picp_weight_ptrs(weights)
+    classes = torch.empty((Bn, H, W), dtype=torch.uint8, device=dev)
+    th = torch.empty((Bn, 2), dtype=f32, device=dev) if return_thresholds else None
+    cptrs = (_C.C.c_void_p * Bn)(*[classes.data_ptr() + b * H * W for b in range(Bn)])
+    tptrs = None if th is None else (_C.C.c_void_p * Bn)(*[th.data_ptr() + b * 8 for b in range(Bn)])
+    check(L.gs_picp_outlier_classes_batch_f32(seqs, wptrs, cptrs, tptrs, Bn, H, W, dist_th, dot_th, rule.hi, rule.lo,
+                                              rule.floor, stream(dev)), "gs_picp_outlier_classes_batch_f32")
+    mask = torch.empty((Bn, H, W), dtype=torch.uint8, device=dev)
+    check(L.gs_region_mask_u8(ptr(classes), ptr(held[2]), ptr(mask), Bn, H, W, rule.min_support, rule.grow,
+                              rule.grow_depth, stream(dev)), "gs_region_mask_u8")
+    res = (mask,) + ((classes,) if return_classes else ()) + ((th,) if return_thresholds else ())
+    return res if len(res) > 1 else mask
+
+
+def projective_icp_outliers(vertex, normal, depth, K, index, model_pose, map_points, map_normals, pose, *, n_dev=None,
+                            hi=3.0, lo=1.5, floor=0.0, min_support=6, grow=0, grow_depth=0.02, dist_thresh=0.1,
+                            angle_thresh=30.0, pixel_weights=None, return_classes=False, return_thresholds=False):
+    """projective_icp_outliers_batch for one sequence without the batch dimension (arguments as projective_icp_rows):
+    the mask (H, W) uint8 (and the classes (H, W), the thresholds (2,))."""
+    who = "projective_icp_outliers"
+    _picp_tensors(who, (("vertex", vertex), ("normal", normal), ("depth", depth), ("K", K), ("index", index),
+                        ("model_pose", model_pose), ("pose", pose)))
+    if pixel_weights is not None:
+        _picp_tensors(who, (("pixel_weights", pixel_weights),))
+        pixel_weights = pixel_weights.unsqueeze(0)
+    r = projective_icp_outliers_batch(vertex.unsqueeze(0), normal.unsqueeze(0), depth.unsqueeze(0), K.reshape(1, 4, 4),
+                                      index.unsqueeze(0), model_pose.reshape(1, 4, 4),
+                                      [(map_points, map_normals, None, n_dev)], pose.reshape(1, 4, 4), hi=hi, lo=lo,
+                                      floor=floor, min_support=min_support, grow=grow, grow_depth=grow_depth,
+                                      dist_thresh=dist_thresh, angle_thresh=angle_thresh, pixel_weights=pixel_weights,
+                                      return_classes=return_classes, return_thresholds=return_thresholds)
+    return tuple(x[0] for x in r) if isinstance(r, tuple) else r[0]
+
+
 # ----------------------------------------------------------------------------------- projective ICP with a colour term
-ProjectiveColorRows = collections.namedtuple("ProjectiveColorRows", ["code", "row", "a", "b", "ac", "bc", "colored",
+ProjectiveColorRows =collections.namedtuple("ProjectiveColorRows", ["code", "row", "a", "b", "ac", "bc", "colored",
                                                                      "sums", "count", "color_count"])
 PICP_COLOR_TRACE = 9
 

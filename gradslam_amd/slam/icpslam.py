@@ -57,7 +57,12 @@ class ICPSLAM(nn.Module):
     sees (the filtered copy with `depth_filter`) and returns per-pixel weights (B, H, W) or (B, 1, H, W) for the
     projective ICP (`ProjectiveICPOdometryProvider(pixel_weights=...)`): a mask, a sensor model
     (`odometry.axial_noise_weights`), a learned confidence.  It is called once per localisation; the map update does not
-    see it.  With `odom_differentiable` its output stays on the autograd tape."""
+    see it.  With `odom_differentiable` its output stays on the autograd tape.
+
+    `odom_outlier_mask` (None by default, `odom="projicp"` only): a dict of the outlier mask's parameters
+    (`ProjectiveICPOdometryProvider(outlier_mask=...)`: hi, lo, floor, min_support, grow, grow_depth, refine_iters, any
+    subset): after the configured solve the outlier regions of the live frame are masked and refine_iters more
+    iterations run without them.  The mask of the last localisation is `odomprov.last_outlier_mask`."""
 
     def __init__(self, *, odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0,
@@ -66,7 +71,8 @@ class ICPSLAM(nn.Module):
                  odom_differentiable: bool = False, color_weight: Union[float, int] = 0.0,
                  huber_delta: Union[float, int] = 0.0, color_huber_delta: Union[float, int] = 0.0,
                  huber_k: Union[float, int] = 0.0, color_huber_k: Union[float, int] = 0.0,
-                 odom_deterministic_backward: Optional[bool] = None, odom_pixel_weights=None):
+                 odom_deterministic_backward: Optional[bool] = None, odom_pixel_weights=None,
+                 odom_outlier_mask: Optional[dict] = None):
         super().__init__()
         from .. import ops
         if odom_pixel_weights is not None and not callable(odom_pixel_weights):
@@ -124,7 +130,13 @@ class ICPSLAM(nn.Module):
                                                      color_huber_delta=color_huber_delta, huber_k=huber_k,
                                                      color_huber_k=color_huber_k,
                                                      deterministic_backward=odom_deterministic_backward,
-                                                     pixel_weights=odom_pixel_weights)
+                                                     pixel_weights=odom_pixel_weights,
+                                                     outlier_mask=odom_outlier_mask)
+        if odom != "projicp":
+            # (checked after every other keyword, as the provider does: today's refusals and their order stay)
+            ProjectiveICPOdometryProvider._outlier_mask(odom_outlier_mask)
+            if odom_outlier_mask is not None:
+                raise ValueError("odom_outlier_mask is the outlier mask of odom='projicp' (got odom={!r})".format(odom))
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio

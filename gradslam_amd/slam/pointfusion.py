@@ -46,7 +46,12 @@ class PointFusion(ICPSLAM):
     `huber_k`: as in `ICPSLAM` (the Huber threshold of `odom="projicp"` from the residuals' median).
     `color_huber_k`: as in `ICPSLAM` (the colour Huber threshold of `odom="projicp"` from the colour residuals' median).
     `odom_deterministic_backward`: as in `ICPSLAM` (bitwise reproducible map gradients of `odom="projicp"`'s backward).
-    `odom_pixel_weights`: as in `ICPSLAM` (per-pixel weights of `odom="projicp"` from a callable on the live frame)."""
+    `odom_pixel_weights`: as in `ICPSLAM` (per-pixel weights of `odom="projicp"` from a callable on the live frame).
+    `odom_outlier_mask`: as in `ICPSLAM` (the outlier mask of `odom="projicp"` and the refinement without the masked
+    pixels).  `fuse_outliers` (True by default, `odom="projicp"` only): with False the pixels of that mask stay out of the
+    static map: the map update of the step, and its carve, see a copy of the frame with depth 0 at the masked pixels.
+    The caller's frame is untouched; the pose is written back to it as with `depth_filter`.  It needs
+    `odom_outlier_mask`."""
 
     def __init__(self, *, odom: str = "gradicp", dist_th: Union[float, int] = 0.05, angle_th: Union[float, int] = 20,
                  sigma: Union[float, int] = 0.6, dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
@@ -59,13 +64,22 @@ class PointFusion(ICPSLAM):
                  huber_k: Union[float, int] = 0.0, carve_margin: Union[float, int, None] = None,
                  carve_window: int = 1, carve_every: int = 1, color_huber_k: Union[float, int] = 0.0,
                  voxel_size: Union[float, int, None] = None, voxel_every: int = 1,
-                 odom_deterministic_backward: Optional[bool] = None, odom_pixel_weights=None):
+                 odom_deterministic_backward: Optional[bool] = None, odom_pixel_weights=None,
+                 odom_outlier_mask: Optional[dict] = None, fuse_outliers: bool = True):
         super().__init__(odom=odom, dsratio=dsratio, numiters=numiters, damp=damp, dist_thresh=dist_thresh,
                          lambda_max=lambda_max, B=B, B2=B2, nu=nu, device=device, depth_filter=depth_filter,
                          odom_differentiable=odom_differentiable, color_weight=color_weight, huber_delta=huber_delta,
                          color_huber_delta=color_huber_delta, huber_k=huber_k, color_huber_k=color_huber_k,
                          odom_deterministic_backward=odom_deterministic_backward,
-                         odom_pixel_weights=odom_pixel_weights)
+                         odom_pixel_weights=odom_pixel_weights, odom_outlier_mask=odom_outlier_mask)
+        if not isinstance(fuse_outliers, bool):
+            raise TypeError("fuse_outliers must be of type bool; but was of type {}.".format(type(fuse_outliers)))
+        if not fuse_outliers and odom != "projicp":
+            raise ValueError("fuse_outliers is a switch of odom='projicp' (got odom={!r})".format(odom))
+        if not fuse_outliers and odom_outlier_mask is None:
+            raise ValueError("fuse_outliers=False needs odom_outlier_mask: it keeps the pixels of that mask out of the map")
+        self.fuse_outliers = fuse_outliers
+        self._fused = None      # the frame the last step's map update saw, when it was not the frame of the step
         if not (isinstance(dist_th, float) or isinstance(dist_th, int)):
             raise TypeError("Distance threshold must be of type float or int; but was of type {}.".format(
                 type(dist_th)))
@@ -133,6 +147,7 @@ class PointFusion(ICPSLAM):
         # subclass that overrides _localize / _map, takes the generic path
         res = None
         work = live_frame
+        self._fused = None
         if self.depth_filter is not None and isinstance(live_frame, RGBDImages):
             work = self._filtered(live_frame)      # (filtered once, whichever path the step takes)
         if inplace and type(self) is PointFusion and isinstance(live_frame, RGBDImages) and \
@@ -150,12 +165,24 @@ class PointFusion(ICPSLAM):
                 # the carve, whose compaction rewrites the marks that the pruning schedule then reads
                 res[0]._carry_epochs(pointclouds)
             if self.carve_margin is not None:
-                self._carve_step(res[0], work)
+                self._carve_step(res[0], work if self._fused is None else self._fused)
             if self.voxel_size is not None:
                 self._voxel_step(res[0])
             if self.prune_min_confidence is not None:
                 self._end_step(res[0])
         return res
+
+    def _step(self, pointclouds: Pointclouds, live_frame: RGBDImages, prev_frame, inplace: bool):
+        if self.fuse_outliers:
+            return super()._step(pointclouds, live_frame, prev_frame, inplace)
+        # the outlier mask of this step's localisation (None when none ran: the first frame of a map) stays out of the
+        # map: the update sees a copy of the frame without depth there, which carries the recovered pose
+        self.odomprov.last_outlier_mask = None
+        live_frame.poses = self._localize(pointclouds, live_frame, prev_frame)
+        mask = self.odomprov.last_outlier_mask
+        fused = live_frame if mask is None else live_frame.masked_depth(mask)
+        self._fused = None if mask is None else fused
+        return self._map(pointclouds, fused, inplace), live_frame.poses
 
     def _carve_step(self, pointclouds: Pointclouds, frame: RGBDImages):
         """free-space carving of a step (fast and generic path alike): on every carve_every-th step of this map, remove

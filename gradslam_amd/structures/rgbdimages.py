@@ -305,6 +305,28 @@ class RGBDImages(object):
         other._drop_local()
         return other
 
+    def masked_depth(self, mask: torch.Tensor):
+        r"""A new `RGBDImages` whose depth is 0 where `mask` (bool, (B, L, H, W), or (B, H, W) for L = 1) is set and this
+        one's elsewhere: the frame a map update sees when a set of pixels must stay out of the map
+        (`PointFusion(fuse_outliers=False)`).  The result shares the colour, intrinsics and poses tensors with this
+        object, keeps its channel order and has no cached maps; this object is untouched."""
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool:
+            raise TypeError("mask must be a bool tensor. Got {}".format(mask.dtype if torch.is_tensor(mask) else type(mask)))
+        B, L = self.shape[:2]
+        H, W = self._depth_image.shape[3:5] if self.channels_first else self._depth_image.shape[2:4]
+        if tuple(mask.shape) == (B, H, W) and L == 1:
+            mask = mask.unsqueeze(1)
+        if tuple(mask.shape) != (B, L, H, W):
+            raise ValueError("mask must have shape {0}. Got {1} instead".format((B, L, H, W), tuple(mask.shape)))
+        other = object.__new__(type(self))
+        other.__dict__.update(self.__dict__)
+        other._depth_image = torch.where(mask.unsqueeze(self.cdim), torch.zeros((), dtype=self._depth_image.dtype,
+                                                                                 device=self._depth_image.device),
+                                         self._depth_image)
+        other._valid_depth_mask = None
+        other._drop_local()
+        return other
+
     # ------------------------------------------------------------------ setters (cache rules of
     # the reference: rgbdimages.py:399-463)
     @staticmethod

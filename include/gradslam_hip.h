@@ -1125,6 +1125,36 @@ GS_API int gs_projective_icp_weighted_backward_batch_f32(const gs_picp_ordered_b
                                                          int taped_scale, int ordered, void* sort_scratch,
                                                          int64_t sort_scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------ projective ICP: the outlier mask ------
+ * Opt-in (additions only; the ABI version, every struct and every signature above stay): from the residuals of a solve
+ * to the image of the pixels that moved.  Per sequence, at the float32 pose init_pose16, over EVERY pixel of the live
+ * frame (stride 1 whatever the solve's stride):
+ *   association  code, b of each pixel as gs_projective_icp_rows_f32 gives them at stride 1 (with weights: a masked
+ *                pixel has code 6, as in the weighted entries)
+ *   scale        med = the lower median of |b| over the code-0 pixels (the radix selection of the scaled entries);
+ *                hi_t = max(((float)hi * 1.4826f) * med, floor), lo_t alike: float32, one rounding per product; +0.0
+ *                without a code-0 pixel; a threshold of 0 makes no pixel strong or eligible by its residual
+ *   classes      strong = (code == 0 && |b| > hi_t && hi_t > 0) || code == 4 || code == 5;
+ *                eligible = strong || (code == 0 && |b| > lo_t && lo_t > 0); codes 1, 2, 3 and 6 have class 0
+ * gs_picp_outlier_classes_batch_f32 writes, per sequence, the class byte of every pixel (bit 0 strong, bit 1 eligible)
+ * to classes_host[b] (H, W) and, when thresholds_host is not NULL, (hi_t, lo_t) to thresholds_host[b].  weights_host:
+ * NULL (no weights) or per sequence a device image (H, W) or NULL.  seqs_host: out_pose16 and trace are not used;
+ * scratch: gs_picp_outlier_classes_scratch_bytes(H, W) bytes per sequence, 16-byte aligned.  hi >= lo > 0, floor >= 0,
+ * all finite.  8 sequences per launch; nothing is read back; no float atomics; bitwise reproducible.
+ * gs_region_mask_u8 maps B class images (B, H, W) and their depth to the mask (B, H, W) of 0 / 1:
+ *   seed(p) = strong(p) and at least min_support (1 .. 9) of the 3 x 3 window around p are strong (p counts, pixels
+ *   outside the image do not);  M_0 = seed;  M_{i+1}(p) = M_i(p) || (eligible(p) && some 4-neighbour q inside the image
+ *   has M_i(q) && fabsf(depth(p) - depth(q)) <= grow_depth), for exactly grow (0 .. 16) steps.
+ * One launch, tiles with a halo in LDS, integer outputs, bitwise reproducible.  Every argument of both entries is checked
+ * before the first HIP call. */
+GS_API int64_t gs_picp_outlier_classes_scratch_bytes(int H, int W);
+GS_API int gs_picp_outlier_classes_batch_f32(const gs_picp_seq* seqs_host, const float* const* weights_host,
+                                             uint8_t* const* classes_host, float* const* thresholds_host, int B, int H,
+                                             int W, float dist_th, float dot_th, float hi, float lo, float floor,
+                                             void* stream);
+GS_API int gs_region_mask_u8(const uint8_t* classes, const float* depth, uint8_t* mask, int64_t B, int H, int W,
+                             int min_support, int grow, float grow_depth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
