@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from gradslam_amd.datasets.synthetic import make_sequence
+from tests import scratch_guard
 
 pytestmark = pytest.mark.gpu
 
@@ -227,12 +228,12 @@ def _step_call(ops, duplicated, outputs, spoil=None):
     stores = [[t.clone() for t in m["bufs"]] for m in maps]
     n_dev = dev(np.array([m["n"] for m in maps], np.int64))
     seqs = (_C.StepSeq * B)()
-    keep = []
+    guards = scratch_guard.GuardLog(0xFF)
     for b, (m, bufs) in enumerate(zip(maps, stores)):
         cap = int(bufs[0].shape[0])
-        loc = torch.empty(L.gs_localize_scratch_bytes(H, W, DS, cap), dtype=torch.uint8, device="cuda")
-        upd = torch.empty(L.gs_update_map_scratch_bytes(cap, H, W), dtype=torch.uint8, device="cuda")
-        keep += [loc, upd]
+        # exactly what the sizers say, between guard bands, poisoned with 0xFF (tests/scratch_guard.py)
+        loc = scratch_guard.guarded_buffer(guards, "loc_scratch%d" % b, L.gs_localize_scratch_bytes(H, W, DS, cap), "cuda")
+        upd = scratch_guard.guarded_buffer(guards, "upd_scratch%d" % b, L.gs_update_map_scratch_bytes(cap, H, W), "cuda")
         q = seqs[b]
         q.depth, q.rgb, q.K16 = depth[b].data_ptr(), rgb[b].data_ptr(), K[b].data_ptr()
         q.prev_pose16, q.out_pose16 = prev[b].data_ptr(), out_pose[b].data_ptr()
@@ -248,6 +249,8 @@ def _step_call(ops, duplicated, outputs, spoil=None):
     status = L.gs_pointfusion_step_batch_f32(seqs, B, H, W, DS, prm, ops.two_sigma_sq(SIGMA), DIST_TH, DOT_TH, 1,
                                              _C.stream(depth.device))
     torch.cuda.synchronize()
+    ok, hits = scratch_guard.intact(guards)
+    assert ok, ("the step wrote outside a scratch of exactly the sizer's size", hits)
     return status, host(out_pose), host(cnt), [[host(t) for t in bufs] for bufs in stores]
 
 

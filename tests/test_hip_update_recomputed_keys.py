@@ -19,6 +19,7 @@ import torch
 
 from oracle import fusion_edges as fe
 from oracle import oracle as o
+from tests import scratch_guard
 
 gpu = pytest.mark.gpu
 SIGMA, DIST_TH, DOT_TH, DS = 0.6, 0.05, 0.9, 4
@@ -261,12 +262,12 @@ def run_step_entry(ops, sc, renorm, extra):
     stores = [store(s, extra, poison=True) for s in sc["seqs"]]
     n_dev = dev(np.array([s["P"].shape[0] for s in sc["seqs"]], np.int64))
     seqs = (_C.StepSeq * B)()
-    keep = []
+    guards = scratch_guard.GuardLog(0xFF)
     for b, (s, bufs) in enumerate(zip(sc["seqs"], stores)):
         cap = int(bufs[0].shape[0])
-        loc = torch.empty(L.gs_localize_scratch_bytes(H, W, DS, cap), dtype=torch.uint8, device="cuda")
-        upd = torch.empty(L.gs_update_map_scratch_bytes(cap, H, W), dtype=torch.uint8, device="cuda")
-        keep += [loc, upd]
+        # exactly what the sizers say, between guard bands, poisoned with 0xFF (tests/scratch_guard.py)
+        loc = scratch_guard.guarded_buffer(guards, "loc_scratch%d" % b, L.gs_localize_scratch_bytes(H, W, DS, cap), "cuda")
+        upd = scratch_guard.guarded_buffer(guards, "upd_scratch%d" % b, L.gs_update_map_scratch_bytes(cap, H, W), "cuda")
         q = seqs[b]
         q.depth, q.rgb, q.K16 = depth[b].data_ptr(), rgb[b].data_ptr(), K[b].data_ptr()
         q.prev_pose16, q.out_pose16 = prev[b].data_ptr(), out_pose[b].data_ptr()
@@ -280,6 +281,8 @@ def run_step_entry(ops, sc, renorm, extra):
                                              float(sc["dot_th"]), 1 if renorm else 0, _C.stream(depth.device)),
              "gs_pointfusion_step_batch_f32")
     torch.cuda.synchronize()
+    ok, hits = scratch_guard.intact(guards)
+    assert ok, ("the step wrote outside a scratch of exactly the sizer's size", hits)
     # the step made the frame maps itself and updated under the pose it wrote: they must be the scene's
     for b, s in enumerate(sc["seqs"]):
         fe.same_bits(host(out_pose[b]), s["pose"], "step pose", signed_zero=False)
