@@ -127,6 +127,24 @@ class PicpColorSeq(C.Structure):
     _fields_ = [("base", PicpSeq), ("color", C.c_void_p), ("model_intensity", C.c_void_p)]
 
 
+class FeatureFuseSeq(C.Structure):
+    """gs_feature_fuse_seq: one sequence's feature layer, the tables of its frame and the outputs of the fusion."""
+    _fields_ = [("emb", C.c_void_p), ("weight", C.c_void_p), ("capacity", C.c_int64), ("n_old_bound", C.c_int64),
+                ("n_old_dev", C.c_void_p), ("best_pix", C.c_void_p), ("depth", C.c_void_p), ("alpha", C.c_void_p),
+                ("feat", C.c_void_p), ("valid", C.c_void_p), ("row_of_pix", C.c_void_p), ("n_out", C.c_void_p),
+                ("scratch", C.c_void_p)]
+
+
+class FeatureCompactSeq(C.Structure):
+    """gs_feature_compact_seq: one sequence's feature layer, its keep mask and the destination buffers."""
+    _fields_ = [("emb", C.c_void_p), ("weight", C.c_void_p), ("n_bound", C.c_int64), ("n_dev", C.c_void_p),
+                ("keep", C.c_void_p), ("emb_out", C.c_void_p), ("weight_out", C.c_void_p), ("capacity_out", C.c_int64),
+                ("n_out", C.c_void_p), ("scratch", C.c_void_p)]
+
+
+FEATURE_F32, FEATURE_F16 = 0, 1
+
+
 class PicpParams(C.Structure):
     _fields_ = [("stride", C.c_int), ("numiters", C.c_int), ("damp", C.c_float), ("dist_th", C.c_float),
                 ("dot_th", C.c_float)]
@@ -283,6 +301,8 @@ _PROTOS = {
     "gs_picp_outlier_classes_batch_f32": [C.POINTER(PicpSeq), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                           C.POINTER(C.c_void_p), _i32, _i32, _i32, _f, _f, _f, _f, _f, _vp],
     "gs_region_mask_u8": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f, _vp],
+    "gs_fuse_features_batch": [C.POINTER(FeatureFuseSeq), _i32, _i32, _i32, _i32, _i32, _vp],
+    "gs_compact_features_batch": [C.POINTER(FeatureCompactSeq), _i32, _i32, _i32, _vp],
 }
 _RESTYPE = {"gs_last_error": C.c_char_p, "gs_scratch_bytes": _i64, "gs_icp_scratch_bytes": _i64,
             "gs_knn1_grid_scratch_bytes": _i64, "gs_update_map_scratch_bytes": _i64, "gs_global_maps_pose_backward_scratch_bytes": _i64, "gs_icp_tape_bytes": _i64, "gs_icp_backward_scratch_bytes": _i64,

@@ -13,7 +13,10 @@ and `Pointclouds.mark_epoch / prune_ / prune` with `PointFusion(prune_min_confid
 prune_every=...)` (off by default): a stable, batched compaction of the map that removes surfels whose confidence stays
 below a threshold after a number of steps, without a read-back and without a per-surfel age channel;
 `RGBDImages.bilateral_filter` with `ICPSLAM / PointFusion(depth_filter=...)` (off by default): the edge-preserving
-pre-pass on the raw depth in front of the vertex and normal maps, differentiable down to the sensor depth."""
+pre-pass on the raw depth in front of the vertex and normal maps, differentiable down to the sensor depth;
+`MapFeatures` with `Pointclouds.attach_features` and `PointFusion.step(..., features=...)` (off by default): a C-channel
+feature per surfel, fused from per-pixel feature images with the weights and the correspondences of the colour fusion
+and kept row-aligned with the map through pruning, carving and thinning."""
 from .version import __version__  # noqa: F401
 from .geometry import *  # noqa: F401,F403
 from . import odometry, slam, metrics  # noqa: F401

@@ -2344,6 +2344,160 @@ def voxel_keep(points, voxel_size, confidence=None, n_dev=None):
     return VoxelKeep(r.keep[0], r.winner[0], r.unplaced)
 
 
+# ----------------------------------------------------------------------------------- feature layers
+FEATURE_MAX_CHANNELS = 4096
+FEATURE_DTYPES = {torch.float32: _C.FEATURE_F32, torch.float16: _C.FEATURE_F16}
+FusedFeatures = collections.namedtuple("FusedFeatures", ["row_of_pix", "counts"])
+CompactedFeatures = collections.namedtuple("CompactedFeatures", ["layers", "counts"])
+
+
+def _feature_layers(who, layers):
+    """per sequence (emb (capacity, C), weight (capacity,)) -> (C, dtype) after the checks every layer pass makes"""
+    if len(layers) == 0:
+        raise ValueError("%s: no layers" % who)
+    C, dtype = None, None
+    for emb, weight in layers:
+        if not torch.is_tensor(emb) or not torch.is_tensor(weight):
+            raise TypeError("%s: a layer is (emb, weight), two tensors" % who)
+        if emb.dtype not in FEATURE_DTYPES:
+            raise ValueError("%s: emb must be float32 or float16; got %s" % (who, emb.dtype))
+        if emb.ndim != 2 or not 1 <= emb.shape[1] <= FEATURE_MAX_CHANNELS:
+            raise ValueError("%s: emb must be (capacity, C) with C in 1..%d; got %s"
+                             % (who, FEATURE_MAX_CHANNELS, tuple(emb.shape)))
+        if weight.dtype != f32 or weight.ndim != 1 or weight.shape[0] < emb.shape[0]:
+            raise ValueError("%s: weight must be a float32 (capacity,) tensor with as many rows as emb" % who)
+        if C is None:
+            C, dtype = int(emb.shape[1]), emb.dtype
+        elif (int(emb.shape[1]), emb.dtype) != (C, dtype):
+            raise ValueError("%s: every layer of a batch has the same channels and dtype" % who)
+    return C, dtype
+
+
+def _feature_scratch(ws, sizes):
+    """one region of gs_scratch_bytes(rows, pixels) bytes per sequence, carved from the workspace's "scratch" buffer"""
+    L = lib()
+    need = [int(L.gs_scratch_bytes(int(r), int(p))) for r, p in sizes]
+    base = ws.bytes("scratch", sum(need)).data_ptr()
+    offs, at = [], 0
+    for n in need:
+        offs.append(base + at)
+        at += n
+    return offs
+
+
+def fuse_features_batch(layers, n_old, best_pix, depth, alpha, feat=None, valid=None):
+    """Fuses per-pixel feature images into the feature layers of B sequences, in place, AFTER the map update of the
+    frame and on its tables (gs_fuse_features_batch: count, tile scan, rows and one wide fuse launch per 8 sequences;
+    nothing is read back).  layers: per sequence (emb (capacity, C) float32 | float16, weight (capacity,) float32).
+    n_old: per sequence (n_old_bound, n_old_dev): the map count BEFORE the update (n_old_dev: a device int64[1] tensor or
+    None when the bound is exact).  best_pix: (B, H * W) int32 as update_map_fusion_batch_ returns it, or None (every
+    pixel with depth is appended).  depth, alpha: (B, H, W) float32.  feat: (B, H, W, C) of the layers' dtype, or None
+    (no pixel is valid: the appended rows are created with zeros and weight 0).  valid: (B, H, W) or (B, H * W) bool /
+    uint8, or None (every pixel).  Pixel p goes to row best_pix[p] when 0 <= best_pix[p] < n_old (merged with the colour
+    fusion's weights: emb = (w emb + a feat) / (w + a), weight = w + a, a = alpha[p]), to row n_old + rank(p) when
+    best_pix[p] < 0 and depth[p] > 0 (emb = feat, weight = a), and nowhere otherwise.  Returns FusedFeatures(row_of_pix
+    (B, H * W) int32, -1 for none; counts (B,) int64 on the device, the map's own new counts)."""
+    who = "fuse_features"
+    C, dtype = _feature_layers(who, layers)
+    Bn = len(layers)
+    if not torch.is_tensor(depth) or depth.ndim != 3 or depth.shape[0] != Bn:
+        raise ValueError("%s: depth must be (%d, H, W)" % (who, Bn))
+    _, H, W = depth.shape
+    P = H * W
+    if not torch.is_tensor(alpha) or tuple(alpha.shape) != (Bn, H, W):
+        raise ValueError("%s: alpha must be (%d, %d, %d); got %s" % (who, Bn, H, W, tuple(alpha.shape)))
+    if len(n_old) != Bn:
+        raise ValueError("%s: n_old must have one (bound, device count) per layer" % who)
+    if best_pix is not None and (best_pix.dtype != torch.int32 or tuple(best_pix.shape) != (Bn, P)):
+        raise ValueError("%s: best_pix must be an int32 tensor of shape (%d, %d)" % (who, Bn, P))
+    if feat is not None:
+        if not torch.is_tensor(feat) or tuple(feat.shape) != (Bn, H, W, C):
+            raise ValueError("%s: feat must be (%d, %d, %d, %d); got %s"
+                             % (who, Bn, H, W, C, tuple(feat.shape) if torch.is_tensor(feat) else type(feat)))
+        if feat.dtype != dtype:
+            raise ValueError("%s: feat must have the layer's dtype %s; got %s" % (who, dtype, feat.dtype))
+        _warn_detached(who, feat)
+        feat = feat.detach().contiguous()
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or \
+                tuple(valid.shape) not in ((Bn, H, W), (Bn, P)):
+            raise ValueError("%s: valid must be a bool / uint8 tensor of shape (%d, %d, %d) or (%d, %d)"
+                             % (who, Bn, H, W, Bn, P))
+        valid = valid.contiguous()
+        valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+    best_pix = None if best_pix is None else best_pix.contiguous()
+    views = [_batch_view(depth, 2), _batch_view(alpha, 2)]
+    dev = require_device(best_pix, feat, valid, *[t for l in layers for t in l], *[n[1] for n in n_old])
+    if any(v[0].device != dev for v in views):   # (slices of a frame stack: contiguous per sequence, not as a whole)
+        raise _C.HipExtensionError("gradslam_amd kernels run on the GPU only; all tensors on one device")
+    rows = torch.empty((Bn, P), dtype=torch.int32, device=dev)
+    cnt = torch.empty(Bn, dtype=torch.int64, device=dev)
+    scratch = _feature_scratch(Workspace.get(dev), [(int(n[0]), P) for n in n_old])
+    seqs = (_C.FeatureFuseSeq * Bn)()
+    es = 4 if dtype == f32 else 2
+    for b in range(Bn):
+        emb, weight = layers[b]
+        bound, n_dev = n_old[b]
+        if n_dev is not None and (n_dev.dtype != torch.int64 or n_dev.numel() != 1):
+            raise ValueError("%s: a device count is an int64 tensor of one element" % who)
+        u = seqs[b]
+        u.emb, u.weight, u.capacity = emb.data_ptr(), weight.data_ptr(), int(emb.shape[0])
+        u.n_old_bound, u.n_old_dev = int(bound), (0 if n_dev is None else n_dev.data_ptr())
+        u.best_pix = 0 if best_pix is None else best_pix.data_ptr() + 4 * P * b
+        u.depth, u.alpha = (v[1] + b * v[2] for v in views)
+        u.feat = 0 if feat is None else feat.data_ptr() + es * P * C * b
+        u.valid = 0 if valid is None else valid.data_ptr() + P * b
+        u.row_of_pix, u.n_out, u.scratch = rows.data_ptr() + 4 * P * b, cnt.data_ptr() + 8 * b, scratch[b]
+    check(lib().gs_fuse_features_batch(seqs, Bn, H, W, C, FEATURE_DTYPES[dtype], stream(dev)), "gs_fuse_features_batch")
+    return FusedFeatures(rows, cnt)
+
+
+def compact_features_batch(layers, n, keep, out=None):
+    """Stable compaction of the feature layers of B sequences into NEW buffers by a keep mask
+    (gs_compact_features_batch: count, tile scan and scatter launch per 8 sequences; nothing is read back).  layers: per
+    sequence (emb (rows, C), weight (rows,)).  n: per sequence (n_bound, n_dev) as in MapRows.  keep: per sequence a
+    (rows,) bool / uint8 tensor of at least n_bound entries.  out: per sequence (emb_out, weight_out) with at least
+    n_bound rows; default: new tensors of the sources' shapes.  Survivor k of the first min(n_dev[0], n_bound) rows
+    becomes row k, bit for bit: with the same mask these are the rows prune_map_batch keeps.  Returns
+    CompactedFeatures(layers = per sequence (emb, weight), counts (B,) int64 on the device); destination rows at or
+    beyond the new count are not written."""
+    who = "compact_features"
+    C, dtype = _feature_layers(who, layers)
+    Bn = len(layers)
+    for name, val in (("n", n), ("keep", keep), ("out", out)):
+        if val is not None and len(val) != Bn:
+            raise ValueError("%s: %s must have one entry per layer (%d), got %d" % (who, name, Bn, len(val)))
+    if out is None:
+        out = [(torch.empty_like(e), torch.empty_like(w)) for e, w in layers]
+    else:
+        _feature_layers(who, out)
+        if any(o[0].shape[1] != C or o[0].dtype != dtype for o in out):
+            raise ValueError("%s: out must hold layers of the sources' channels and dtype" % who)
+    bounds = [min(int(layers[b][0].shape[0]), int(n[b][0])) for b in range(Bn)]
+    keeps = []
+    for b in range(Bn):
+        kp = keep[b]
+        if not torch.is_tensor(kp) or kp.dtype not in (torch.bool, torch.uint8) or kp.ndim != 1 or kp.shape[0] < bounds[b]:
+            raise ValueError("%s: keep must be a (rows,) bool / uint8 tensor of at least n_bound rows" % who)
+        kp = kp.contiguous()
+        keeps.append(kp.view(torch.uint8) if kp.dtype == torch.bool else kp)
+    dev = require_device(*[t for l in layers for t in l], *[t for l in out for t in l], *[x[1] for x in n], *keeps)
+    cnt = torch.empty(Bn, dtype=torch.int64, device=dev)
+    scratch = _feature_scratch(Workspace.get(dev), [(r, 0) for r in bounds])
+    seqs = (_C.FeatureCompactSeq * Bn)()
+    for b in range(Bn):
+        kp, n_dev = keeps[b], n[b][1]
+        u = seqs[b]
+        u.emb, u.weight = layers[b][0].data_ptr(), layers[b][1].data_ptr()
+        u.n_bound, u.n_dev = bounds[b], (0 if n_dev is None else n_dev.data_ptr())
+        u.keep = kp.data_ptr()
+        u.emb_out, u.weight_out = out[b][0].data_ptr(), out[b][1].data_ptr()
+        u.capacity_out = min(int(out[b][0].shape[0]), int(out[b][1].shape[0]))
+        u.n_out, u.scratch = cnt.data_ptr() + 8 * b, scratch[b]
+    check(lib().gs_compact_features_batch(seqs, Bn, C, FEATURE_DTYPES[dtype], stream(dev)), "gs_compact_features_batch")
+    return CompactedFeatures([tuple(o) for o in out], cnt)
+
+
 # ----------------------------------------------------------------------------------- bilateral depth filter
 BILATERAL_MAX_RADIUS = 8
 

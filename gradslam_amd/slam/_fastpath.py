@@ -141,7 +141,9 @@ class StepPlan(object):
         # fresh hipMalloc of that size on the host thread: usually ~0.1 ms, but 2 ms on a bad day of a shared host, which
         # made one bench run in six host-bound at half the rate (round 5, profiles/r05_bench_line_slow_host.json).
         poses_out = torch.empty(B * 16, dtype=f32, device=dev)
-        best = torch.empty((B, P), dtype=torch.int32, device=dev) if STEP_BEST_PIX else None
+        # (a map with a feature layer needs the table of this frame: the layer's pass runs on it after the step)
+        layer = pc._feature_layer
+        best = torch.empty((B, P), dtype=torch.int32, device=dev) if STEP_BEST_PIX or layer is not None else None
         o = out.data_ptr()
         n0, v0, a0, po0 = o, o + 12 * P * B, o + 24 * P * B, poses_out.data_ptr()
         gv0, gn0 = o + 28 * P * B, o + 28 * P * B + 12 * P * B
@@ -184,6 +186,10 @@ class StepPlan(object):
             live._global_normal_map = out[g + n3:g + 2 * n3].view(B, 1, H, W, 3)
         else:
             live._global_vertex_map = live._global_normal_map = None    # (computed on demand under the new pose)
+        if layer is not None:
+            # the old counts: the group's previous device buffer (the two alternate, so this step left it as it was)
+            old_dev = grp.dev
+            pc._fuse_record = (best, [(bounds[b], old_dev[b:b + 1]) for b in range(B)])
         grp.advance(cnt_new, P)
         pc._generation += 1
         pc._padded_cache.clear()

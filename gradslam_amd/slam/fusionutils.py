@@ -290,12 +290,16 @@ def _fuse(pointclouds, rgbdimages, best_pix, sigma, inplace):
     renorm = RENORMALIZE_UNMATCHED
     if renorm and B > 1 and bool(torch.stack([(bp >= 0).any() for bp in best_pix]).any()):   # (one read-back)
         renorm = 2
+    old = []    # (bound, device count) of every sequence before the update: what a feature layer's pass starts from
+    if inplace and pointclouds._feature_layer is not None:
+        pointclouds._fuse_record = (best_pix, old)
     for b in range(B):
         if inplace and ops.DEVICE_COUNTS:
             # the count stays on the device: no read-back, the host only tracks an upper bound.  Reserve FIRST:
             # the bound may tighten between two look-ups, and the capacity must cover the bound that is passed on
             P, N, C, F = pointclouds._reserve(b, H * W, pointclouds.RESERVE_FRAMES)
             n0, n_dev = pointclouds._count_of(b)
+            old.append((n0, n_dev))
             if P.dtype != torch.float32 or F.shape[-1] != 1:
                 raise ValueError("map fusion needs float32 surfels with one feature column (the confidence count)")
             cnt = ops.fuse_append_(P, N, C, F, n0, best_pix[b], gv[b, 0], gn[b, 0], rgb[b, 0], alpha[b, 0, ..., 0],
@@ -303,6 +307,7 @@ def _fuse(pointclouds, rgbdimages, best_pix, sigma, inplace):
             pointclouds._set_count_dev(b, cnt, H * W)
             continue
         n0 = pointclouds._n[b]
+        old.append((n0, None))
         P, N, C, F = pointclouds._reserve(b, H * W)
         if P.dtype != torch.float32 or F.shape[-1] != 1:
             raise ValueError("map fusion needs float32 surfels with one feature column (the confidence count)")
@@ -496,6 +501,8 @@ def _fuse_differentiable(pointclouds, rgbdimages, dist_th, dot_th, sigma, inplac
     out._n = [t.shape[0] for t in new["points"]]
     out._invalidate()
     out._taped_swaps += 1   # (new tensors, out of place: a backward that saved the old ones is still valid)
+    if inplace and out._feature_layer is not None:
+        out._fuse_record = (bests, [(int(o[0].shape[0]), None) for o in olds])
     return out
 
 
@@ -533,9 +540,12 @@ def _update_map_one_call(pointclouds, rgbdimages, dist_th, dot_th, sigma):
     for b in range(B):
         bufs = pointclouds._reserve(b, H * W, pointclouds.RESERVE_FRAMES)   # before _count_of: see _fuse
         maps.append(ops.MapRows(*bufs, *pointclouds._count_of(b)))
-    cnt, _, _, _ = ops.update_map_fusion_batch_(maps, vm[:, 0], nm[:, 0], depth[:, 0, ..., 0], rgb[:, 0],
-                                                alpha[:, 0, ..., 0], poses, K, dist_th, dot_th, RENORMALIZE_UNMATCHED,
-                                                out=(gv[:, 0], gn[:, 0]))
+    cnt, _, _, best = ops.update_map_fusion_batch_(maps, vm[:, 0], nm[:, 0], depth[:, 0, ..., 0], rgb[:, 0],
+                                                   alpha[:, 0, ..., 0], poses, K, dist_th, dot_th, RENORMALIZE_UNMATCHED,
+                                                   out=(gv[:, 0], gn[:, 0]))
+    if pointclouds._feature_layer is not None:
+        # (the old device counts stay as they are: the update wrote the new ones to a tensor of its own)
+        pointclouds._fuse_record = (best, [(m.n_bound, m.n_dev) for m in maps])
     pointclouds._set_counts_dev(cnt, H * W)
     fr._global_vertex_map, fr._global_normal_map = gv, gn
     return pointclouds

@@ -145,9 +145,12 @@ class ICPSLAM(nn.Module):
 
     def forward(self, frames: RGBDImages):
         r"""Returns (pointclouds: B global maps, poses (B, L, 4, 4))."""
+        return self._forward(frames, Pointclouds(device=self.device), lambda s: {})
+
+    def _forward(self, frames: RGBDImages, pointclouds: Pointclouds, step_kwargs):
+        """the frame loop of `forward` into the given (empty) map; step_kwargs(s): further keywords of step s"""
         if not isinstance(frames, RGBDImages):
             raise TypeError("Expected frames to be of type gradslam.RGBDImages. Got {0}.".format(type(frames)))
-        pointclouds = Pointclouds(device=self.device)
         batch_size, seq_len = frames.shape[:2]
         recovered_poses = torch.empty(batch_size, seq_len, 4, 4).to(self.device)
         prev_frame = None
@@ -156,7 +159,7 @@ class ICPSLAM(nn.Module):
             if s == 0 and live_frame.poses is None:
                 live_frame.poses = (torch.eye(4, dtype=torch.float, device=self.device).view(1, 1, 4, 4)
                                     .repeat(batch_size, 1, 1, 1))
-            pointclouds, live_frame.poses = self.step(pointclouds, live_frame, prev_frame, inplace=True)
+            pointclouds, live_frame.poses = self.step(pointclouds, live_frame, prev_frame, inplace=True, **step_kwargs(s))
             prev_frame = live_frame if self.odom != "gt" else None
             recovered_poses[:, s] = live_frame.poses[:, 0]
         return pointclouds, recovered_poses
@@ -166,12 +169,19 @@ class ICPSLAM(nn.Module):
         if not isinstance(live_frame, RGBDImages):
             raise TypeError("Expected live_frame to be of type gradslam.RGBDImages. Got {0}.".format(
                 type(live_frame)))
+        self._check_feature_layer(pointclouds)
         if self.depth_filter is None:
             return self._step(pointclouds, live_frame, prev_frame, inplace)
         work = self._filtered(live_frame)
         res = self._step(pointclouds, work, prev_frame, inplace)
         live_frame.poses = work.poses
         return res
+
+    def _check_feature_layer(self, pointclouds):
+        """the aggregate map update appends rows that no feature layer follows (PointFusion overrides this)"""
+        if isinstance(pointclouds, Pointclouds) and pointclouds.map_features is not None:
+            raise ValueError("ICPSLAM.step is not supported on a map with a feature layer attached: only PointFusion "
+                             "fuses features (detach_features() first)")
 
     def _step(self, pointclouds: Pointclouds, live_frame: RGBDImages, prev_frame: Optional[RGBDImages], inplace: bool):
         """localise and map on the frame as given (`step` hands over the filtered copy when `depth_filter` is set)"""

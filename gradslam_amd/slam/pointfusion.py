@@ -51,7 +51,17 @@ class PointFusion(ICPSLAM):
     pixels).  `fuse_outliers` (True by default, `odom="projicp"` only): with False the pixels of that mask stay out of the
     static map: the map update of the step, and its carve, see a copy of the frame with depth 0 at the masked pixels.
     The caller's frame is untouched; the pose is written back to it as with `depth_filter`.  It needs
-    `odom_outlier_mask`."""
+    `odom_outlier_mask`.
+
+    Feature layers: on a map with a `MapFeatures` layer (`Pointclouds.attach_features`) every in-place `step` follows
+    its map update with `ops.fuse_features_batch` on the update's own correspondences: `features` ((B, 1, H, W, C) or
+    (B, H, W, C), the layer's dtype) are merged into the matched surfels with the weights of the colour fusion and
+    copied to the appended ones; `features_valid` ((B, 1, H, W) or (B, H, W), bool / uint8) leaves pixels out.  A step
+    without `features` still runs the pass (the appended rows are created with weight 0), so the layer never falls out
+    of step with the map; it sees the frame the map update saw (`depth_filter`, `fuse_outliers=False`).  The carve, the
+    thinning and the pruning schedule compact the layer with the map.  `inplace=False` with a layer raises.  `forward`
+    with `features` (B, L, H, W, C) attaches a new layer (of `feature_dtype`, default: the dtype of `features`) to the
+    map it builds.  There is no backward pass: a feature image that requires grad warns and the layer is detached."""
 
     def __init__(self, *, odom: str = "gradicp", dist_th: Union[float, int] = 0.05, angle_th: Union[float, int] = 20,
                  sigma: Union[float, int] = 0.6, dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
@@ -141,7 +151,58 @@ class PointFusion(ICPSLAM):
         self.voxel_size = voxel_size
         self.voxel_every = voxel_every
 
-    def step(self, pointclouds: Pointclouds, live_frame: RGBDImages, prev_frame=None, inplace: bool = False):
+    def forward(self, frames: RGBDImages, *, features=None, features_valid=None, feature_dtype=None):
+        r"""Returns (pointclouds: B global maps, poses (B, L, 4, 4)).  With `features` the map carries a new
+        `MapFeatures` layer (`pointclouds.map_features`) fused from them frame by frame."""
+        if features is None:
+            if features_valid is not None or feature_dtype is not None:
+                raise ValueError("features_valid / feature_dtype were given without features")
+            return super().forward(frames)
+        from ..structures.mapfeatures import MapFeatures
+        if not isinstance(frames, RGBDImages):
+            raise TypeError("Expected frames to be of type gradslam.RGBDImages. Got {0}.".format(type(frames)))
+        B, L, H, W = frames.shape[:4]
+        if not torch.is_tensor(features) or features.ndim != 5 or tuple(features.shape[:4]) != (B, L, H, W):
+            raise ValueError("features must have shape ({}, {}, {}, {}, C); got {}".format(
+                B, L, H, W, tuple(features.shape) if torch.is_tensor(features) else type(features)))
+        if features_valid is not None and (not torch.is_tensor(features_valid) or
+                                           tuple(features_valid.shape) != (B, L, H, W)):
+            raise ValueError("features_valid must have shape ({}, {}, {}, {})".format(B, L, H, W))
+        dtype = features.dtype if feature_dtype is None else feature_dtype
+        pointclouds = Pointclouds(device=self.device).attach_features(MapFeatures(int(features.shape[-1]), dtype))
+        return self._forward(frames, pointclouds, lambda s: dict(
+            features=features[:, s].to(device=self.device, dtype=dtype),
+            features_valid=None if features_valid is None else features_valid[:, s].to(self.device)))
+
+    def _check_feature_layer(self, pointclouds):
+        pass    # (PointFusion is the driver that fuses features: see step)
+
+    def _fuse_features(self, pointclouds: Pointclouds, frame: RGBDImages, feat, valid):
+        """the feature pass of a step, on the tables its map update left with the map and on the frame that update saw"""
+        record, pointclouds._fuse_record = pointclouds._fuse_record, None
+        if record is None:
+            raise RuntimeError("the map update of this step left no correspondence table for the feature layer "
+                               "(a _map override that does not go through update_map_fusion?)")
+        fr = frame.to_channels_last()
+        depth = fr.depth_image[:, 0, ..., 0].detach()
+        alpha = fr._alpha_map(self.sigma)[:, 0, ..., 0].detach()
+        pointclouds.map_features._fuse(pointclouds, record, depth, alpha, feat, valid)
+
+    def step(self, pointclouds: Pointclouds, live_frame: RGBDImages, prev_frame=None, inplace: bool = False, *,
+             features=None, features_valid=None):
+        layer = pointclouds.map_features if isinstance(pointclouds, Pointclouds) else None
+        feat = valid = None
+        if layer is None:
+            if features is not None or features_valid is not None:
+                raise ValueError("features were given, but the map has no feature layer (Pointclouds.attach_features)")
+        else:
+            if not inplace:
+                raise ValueError("a map with a feature layer is updated in place: step(..., inplace=True) (an "
+                                 "out-of-place step returns a map without the layer)")
+            if isinstance(live_frame, RGBDImages):
+                B, L, H, W = live_frame.shape[:4]
+                feat, valid = layer._frame_features(features, features_valid, B, H, W)
+            pointclouds._fuse_record = None
         # the plain SLAM loop (in place, nothing on the autograd tape, a map with surfels): one foreign call per frame
         # (slam/_fastpath.py: same kernels in the same order as _localize + _map below); anything else, and every
         # subclass that overrides _localize / _map, takes the generic path
@@ -159,6 +220,9 @@ class PointFusion(ICPSLAM):
                 self._step(pointclouds, work, prev_frame, inplace)
         if work is not live_frame:
             live_frame.poses = work.poses
+        if layer is not None:
+            # before the carve, the thinning and the pruning schedule: they compact the layer with the map
+            self._fuse_features(res[0], work if self._fused is None else self._fused, feat, valid)
         if self.carve_margin is not None or self.voxel_size is not None or self.prune_min_confidence is not None:
             if res[0] is not pointclouds:
                 # an out-of-place step returns a new container: it takes the marks and the step counters once, before

@@ -188,6 +188,8 @@ class Pointclouds(object):
         self._carve_steps = 0   # the same for a carving PointFusion (carve_margin)
         self._voxel_steps = 0   # the same for a thinning PointFusion (voxel_size)
         self.last_pruned = None  # (B,) int64: rows the last prune_ removed per sequence (on the map's device, never synced)
+        self._feature_layer = None   # the MapFeatures attached to this object (attach_features); copies come without it
+        self._fuse_record = None     # with a layer: (best_pix, [(old bound, old device count)]) of the last map update
         self.equisized = None
 
         if isinstance(points, list):
@@ -342,6 +344,7 @@ class Pointclouds(object):
     # list representation: zero-copy views; the setters follow the reference (structures/pointclouds.py:824-878,
     # :1431-1467: same container type, length and per-sequence shapes, values are cloned)
     def _set_list(self, k, value, first_dim_only=False):
+        self._refuse_with_features("setting " + k)
         if not isinstance(value, list):
             raise TypeError("value must be list of torch.Tensors. Got {}".format(type(value)))
         if not self.has_points:
@@ -402,6 +405,7 @@ class Pointclouds(object):
         return ar < torch.tensor(self._n, device=self.device).unsqueeze(1)
 
     def _set_padded(self, k, value, channels=None):
+        self._refuse_with_features("setting " + k)
         if value is None:
             self._buf[k] = None
             return
@@ -561,6 +565,47 @@ class Pointclouds(object):
         self._generation += 1
         self._padded_cache.clear()
         self.equisized = True if B == 1 else None
+
+    # ------------------------------------------------------------------ feature layers
+    def attach_features(self, layer):
+        r"""Attaches a `MapFeatures` layer: from now on `PointFusion.step(..., inplace=True, features=...)` fuses
+        per-pixel feature images into it with the weights and the correspondences of the colour fusion, and `prune_`,
+        `carve_`, `voxel_downsample_` and the drivers' schedules keep it row-aligned with the map.  The rows a non-empty
+        map already holds get zeros with weight 0.  A layer belongs to one map object: `clone()`, indexing and the
+        out-of-place `prune` / `carve` / `voxel_downsample` return maps without it.  `append_points`, the attribute
+        setters and `ICPSLAM.step` refuse a map with a layer (they would change rows behind its back).  Returns self."""
+        from .mapfeatures import MapFeatures
+        if not isinstance(layer, MapFeatures):
+            raise TypeError("Expected layer to be of type gradslam.MapFeatures. Got {0}.".format(type(layer)))
+        if self._feature_layer is not None:
+            raise ValueError("this pointclouds object already has a feature layer (detach_features() first)")
+        if layer._map is not None:
+            raise ValueError("the feature layer is attached to another pointclouds object: a layer belongs to one map")
+        layer._emb = layer._weight = None
+        layer._map = self
+        self._feature_layer = layer
+        if len(self._n_host):
+            layer._bind(self)
+        return self
+
+    @property
+    def map_features(self):
+        """the attached `MapFeatures` layer, or None"""
+        return self._feature_layer
+
+    def detach_features(self):
+        """Takes the feature layer off the map and returns it (None when there is none).  The layer keeps its buffers,
+        but no longer follows the map: its list views are gone until it is attached again (which starts it afresh)."""
+        layer = self._feature_layer
+        if layer is not None:
+            layer._map = None
+        self._feature_layer = self._fuse_record = None
+        return layer
+
+    def _refuse_with_features(self, what):
+        if self._feature_layer is not None:
+            raise ValueError("{} is not supported on a map with a feature layer attached: the layer's rows would no "
+                             "longer belong to the map's (detach_features() first)".format(what))
 
     # ------------------------------------------------------------------ the model view
     def render(self, intrinsics: torch.Tensor, poses: torch.Tensor, height: int, width: int, *, radius: int = 0,
@@ -745,6 +790,9 @@ class Pointclouds(object):
         if conf is None and all(k is None for k in keep):
             self.last_pruned = torch.zeros(B, dtype=torch.int64, device=self.device)
         elif self.device.type == "cuda" and f32 and not taped:
+            if self._feature_layer is not None:
+                # the rule as an explicit mask, formed on the device: the map and the layer are compacted by the same one
+                keep, conf, young_mark = self._explicit_keep(conf, keep, young_mark), None, -1
             self._prune_hip(conf, keep, young_mark)
         else:
             self._prune_torch(conf, keep, young_mark)
@@ -858,6 +906,27 @@ class Pointclouds(object):
         ops._voxel_args("voxel_downsample", voxel_size)
         return self.clone().voxel_downsample_(voxel_size)
 
+    def _explicit_keep(self, conf, keep, young_mark):
+        """prune_'s rule over the host-side bound of every sequence as uint8 masks: (row >= marks[young_mark]) |
+        (confidence >= float32(min_confidence)), AND-ed with the caller's mask (rows it does not cover are removed).
+        Elementwise torch on the device, nothing is read back; a NaN confidence fails, as in the kernel."""
+        out = []
+        for b in range(len(self._n_host)):
+            bound = self._count_of(b)[0]
+            s = torch.ones(bound, dtype=torch.bool, device=self.device)
+            if keep[b] is not None:
+                kp = keep[b][:bound] != 0
+                s[: kp.shape[0]] &= kp
+                s[kp.shape[0]:] = False
+            if conf is not None:
+                cc = self._buf["features"][b][:bound, 0]
+                ok = cc >= torch.tensor(conf, dtype=torch.float32, device=self.device)
+                if young_mark >= 0:
+                    ok |= torch.arange(bound, device=self.device) >= self._marks[b, young_mark]
+                s &= ok
+            out.append(s.to(torch.uint8))
+        return out
+
     def _prune_hip(self, conf, keep, young_mark):
         from .. import ops
         B = len(self._n_host)
@@ -875,6 +944,9 @@ class Pointclouds(object):
             for i, k in enumerate(_ATTRS):
                 if self._buf[k] is not None:
                     self._buf[k][b] = r.maps[b][i]     # same capacity: nothing that follows the capacity is re-sized
+        if self._feature_layer is not None:
+            # (the counts of `maps` are those from before the prune: the layer's rows are the map's rows)
+            self._feature_layer._compact([(m.n_bound, m.n_dev) for m in maps], keeps)
         grp = self._count_group()
         if grp is not None:
             grp.shrink(r.counts)
@@ -904,6 +976,8 @@ class Pointclouds(object):
             for k in _ATTRS:
                 if self._buf[k] is not None:
                     self._buf[k][b] = self._buf[k][b][:nb][s]
+            if self._feature_layer is not None:
+                self._feature_layer._select(b, nb, s)
             if n_marks:
                 before = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(s, 0)])
                 self._marks[b, :n_marks] = before[self._marks[b, :n_marks].clamp(0, nb)]
@@ -963,6 +1037,7 @@ class Pointclouds(object):
         if not (pointclouds.device == self.device):
             raise ValueError("Device of pointclouds to append and to be appended must match: ({0} != {1})".format(
                 pointclouds.device, self.device))
+        self._refuse_with_features("append_points")
         if not pointclouds.has_points:
             return self
         if self.has_points:

@@ -1155,6 +1155,72 @@ GS_API int gs_picp_outlier_classes_batch_f32(const gs_picp_seq* seqs_host, const
 GS_API int gs_region_mask_u8(const uint8_t* classes, const float* depth, uint8_t* mask, int64_t B, int H, int W,
                              int min_support, int grow, float grow_depth, void* stream);
 
+/* ------------------------------------------------------------------ feature layers ------
+ * A C-channel feature per surfel (an embedding, class logits, any network output), fused from per-pixel feature images
+ * with the weights and the correspondences of the colour fusion.  A layer of one sequence is emb (capacity, C), float32
+ * (GS_FEATURE_F32) or float16 (GS_FEATURE_F16), and weight (capacity) float32; row r belongs to map row r.
+ *
+ * gs_fuse_features_batch runs AFTER the map update of the frame, on the update's correspondence table best_pix (H * W
+ * int32, as gs_update_map_fusion_batch_f32 / gs_pointfusion_step_batch_f32 write it; NULL: every pixel with depth is
+ * appended), the frame's depth and alpha, and the map count BEFORE the update, n_old = min(*n_old_dev, n_old_bound)
+ * (n_old_bound when n_old_dev is NULL).  In raster order,
+ *   row(p) = best_pix[p]         if 0 <= best_pix[p] < n_old                  (matched)
+ *            n_old + rank(p)     if best_pix[p] < 0 and depth[p] > 0          (appended: rank = such pixels before p)
+ *            none                otherwise (a stale entry >= n_old counts as none)
+ * and with valid(p) = feat != NULL && (valid == NULL || valid[p] != 0), a = alpha[p], w = weight[row]:
+ *   matched, valid      w2 = w + a; inv = 1.0f / (w2 == 0.0f ? 1.0f : w2);
+ *                       emb[row, c] = ((w * emb[row, c]) + (a * feat[p, c])) * inv; weight[row] = w2
+ *                       (float32, one rounding per operation, no FMA: the colour merge of the map update)
+ *   matched, not valid  untouched
+ *   appended, valid     emb[row] = feat[p] (the bits), weight[row] = a
+ *   appended, not valid emb[row] = +0, weight[row] = +0.0f
+ * A float16 layer is converted to float32, merged as above and stored round-to-nearest-even.  A map row is matched by
+ * at most one pixel, so every row has one writer: no atomics, bitwise reproducible.  row_of_pix (H * W int32) receives
+ * row(p), -1 for none; *n_out = n_old + appended pixels (the map's own new count).  feat (H, W, C) is of the layer's
+ * dtype.  Rows at or beyond *n_out are not written.
+ *
+ * gs_compact_features_batch: stable, out-of-place compaction by keep (uint8) over the first n = min(*n_dev, n_bound)
+ * rows: survivor k becomes row k of emb_out / weight_out, moved bit for bit; *n_out = survivors; destination rows at or
+ * beyond it are not written.  With the same keep it selects the rows gs_prune_map_dc_f32 selects.
+ *
+ * scratch: gs_scratch_bytes(rows, pixels) bytes per sequence (rows = n_old_bound and pixels = H * W for the fusion;
+ * rows = n_bound and pixels = 0 for the compaction).  Sequences are served 8 per group of launches; nothing is read
+ * back.  GS_ERR_INVALID, before the first HIP call: NULL pointers, C outside 1 .. 4096, an unknown dtype,
+ * capacity < n_old_bound + H * W, n_old_bound + H * W >= 2^31 (so H * W >= 2^31), capacity_out < n_bound, emb / emb_out
+ * not 16-byte aligned (feat too when C * sizeof(elem) is a multiple of 16), a destination equal to its source. */
+#define GS_FEATURE_F32 0
+#define GS_FEATURE_F16 1
+typedef struct gs_feature_fuse_seq {
+  void* emb;                 /* (capacity, C), 16-byte aligned */
+  float* weight;             /* (capacity) */
+  int64_t capacity;          /* >= n_old_bound + H * W */
+  int64_t n_old_bound;       /* host-side upper bound of the map count before the update */
+  const int64_t* n_old_dev;  /* device int64[1]: that count, or NULL when n_old_bound is exact */
+  const int32_t* best_pix;   /* (H * W) or NULL */
+  const float* depth;        /* (H, W) */
+  const float* alpha;        /* (H, W) */
+  const void* feat;          /* (H, W, C) or NULL: no pixel is valid */
+  const uint8_t* valid;      /* (H * W) or NULL: every pixel */
+  int32_t* row_of_pix;       /* (H * W) */
+  int64_t* n_out;            /* device int64[1] */
+  void* scratch;
+} gs_feature_fuse_seq;
+GS_API int gs_fuse_features_batch(const gs_feature_fuse_seq* seqs_host, int B, int H, int W, int C, int dtype,
+                                  void* stream);
+typedef struct gs_feature_compact_seq {
+  const void* emb;           /* (n_bound, C), 16-byte aligned */
+  const float* weight;       /* (n_bound) */
+  int64_t n_bound;
+  const int64_t* n_dev;      /* device int64[1], or NULL when n_bound is exact */
+  const uint8_t* keep;       /* (n_bound) */
+  void* emb_out;             /* (capacity_out, C), 16-byte aligned */
+  float* weight_out;         /* (capacity_out) */
+  int64_t capacity_out;      /* >= n_bound */
+  int64_t* n_out;            /* device int64[1] */
+  void* scratch;
+} gs_feature_compact_seq;
+GS_API int gs_compact_features_batch(const gs_feature_compact_seq* seqs_host, int B, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
