@@ -232,6 +232,11 @@ _PROTOS = {
     "gs_render_map_dc_f32": [C.POINTER(RenderSeq), _i32, _i32, _i32, _i32, _i32, _f, _i32, _vp],
     "gs_render_backward_scratch_bytes": [_i32, _i32, _i32, _i64],
     "gs_render_map_backward_dc_f32": [C.POINTER(RenderBackwardSeq), _i32, _i32, _i32, _i32, _i32, _vp],
+    "gs_surfel_radius_f32": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
+    "gs_render_map_radii_dc_f32": [C.POINTER(RenderSeq), C.POINTER(C.c_void_p), _i32, _i32, _i32, _i32, _i32, _f, _i32,
+                                   _vp],
+    "gs_render_map_radii_backward_dc_f32": [C.POINTER(RenderBackwardSeq), C.POINTER(C.c_void_p), _i32, _i32, _i32, _i32,
+                                            _i32, _vp],
     "gs_prune_scratch_bytes": [_i64],
     "gs_prune_map_dc_f32": [C.POINTER(PruneSeq), _i32, _f, _i32, _vp],
     "gs_free_space_dc_f32": [C.POINTER(CarveSeq), _i32, _i32, _i32, _i32, _f, _i32, _i32, _vp],

@@ -10,7 +10,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["gs_frame.hip", "gs_assoc.hip", "gs_fuse.hip", "gs_knn.hip", "gs_icp.hip", "gs_icp_loop.hip", "gs_icp_bwd.hip", "gs_ingest.hip", "gs_render.hip", "gs_prune.hip", "gs_carve.hip", "gs_voxel.hip", "gs_bilateral.hip", "gs_picp.hip", "gs_picp_bwd.hip", "gs_picp_color.hip", "gs_picp_scale.hip", "gs_picp_outliers.hip", "gs_features.hip"]
+SOURCES = ["gs_frame.hip", "gs_assoc.hip", "gs_fuse.hip", "gs_knn.hip", "gs_icp.hip", "gs_icp_loop.hip", "gs_icp_bwd.hip", "gs_ingest.hip", "gs_render.hip", "gs_prune.hip", "gs_carve.hip", "gs_voxel.hip", "gs_bilateral.hip", "gs_picp.hip", "gs_picp_bwd.hip", "gs_picp_color.hip", "gs_picp_scale.hip", "gs_picp_outliers.hip", "gs_features.hip", "gs_radii.hip"]
 HEADERS = ["gs_common.h", "gs_env.h", "gs_compact.h", "gs_assoc_dev.h", "gs_knn.h", "gs_knn_bbox.h", "gs_icp_math.h", "gs_icp_timeline.h", "gs_se3_f64.h", "gs_picp_dev.h", "gs_picp_color_dev.h", "gs_picp_scale_dev.h", os.path.join("..", "..", "include", "gradslam_hip.h")]
 LIB = os.path.join(HERE, "libgradslam_hip.so")
 # -fno-slp-vectorize: hipcc otherwise packs adjacent f32 ops into v_pk_* instructions, which issue at a

@@ -20,6 +20,14 @@
 //   back-face test (cull_backfaces): d = (nc0 * q0 + nc1 * q1) + nc2 * q2, one rounding per operation, left to right;
 //            the row is skipped when d >= 0 (it faces away from the camera or is seen edge-on)
 //   min_confidence: the row is skipped when ccount < min_confidence
+//
+// With per-surfel radii (gs_render_map_radii_dc_f32, gs_render_map_radii_backward_dc_f32) the half-width of the square
+// a row competes for is its own, from its radius rho (metres; a fused map attribute) and its depth in the view:
+//   fbar = 0.5f * (K[0][0] + K[1][1])
+//   x    = (rho * fbar) / q2                  float32, two operations
+//   r    = rho > 0 and 0 < x < inf ? min(max_radius, (int)floorf(x)) : 0        (max_radius 0 .. 8)
+// Everything else is the pass above: the same key, the same atomicMin, the same resolve pass.  With every r equal to
+// k <= 3 the key image, hence every output, is that of radius = k.
 #include "gs_assoc_dev.h"
 
 // Build-time switch for measurements (tools/render_profile.py): 0 = every candidate issues its atomic.
@@ -29,6 +37,7 @@
 
 constexpr int GS_RV_MAX_VIEWS = 4;   // views of one map served by one launch (one camera each in LDS); more views = more launches
 constexpr int GS_RV_MAX_RADIUS = 3;
+constexpr int GS_RV_MAX_SPLAT = 8;   // cap of a per-surfel radius in pixels (the radii entries)
 constexpr uint64_t GS_RV_EMPTY = ~0ull;
 
 struct RvSeq {
@@ -36,6 +45,7 @@ struct RvSeq {
   const float* normals;
   const float* colors;
   const float* ccounts;
+  const float* radii;     // (rows) metres, the radii entries only
   GsCount n;
   const float* poses16;   // first view of the launch
   const float* K16;
@@ -48,12 +58,32 @@ struct RvSeq {
 };
 struct RvBatch {
   RvSeq s[GS_MAX_BATCH];
-  int B, V, H, W, radius, cull, use_conf;
+  int B, V, H, W, radius, cull, use_conf;   // radius: the radii entries' max_radius
   int64_t P;
   float u_hi, v_hi, min_conf;
 };
 
-__global__ void __launch_bounds__(256) gs_render_key_kernel(const RvBatch rb) {
+// the half-width in pixels of the square of a row of radius rho (metres) at camera-frame depth q2 > 0 in view c
+GS_DEV int rv_splat_radius(const GsCamera& c, float rho, float q2, int max_radius) {
+  const float fbar = 0.5f * (c.K[0] + c.K[5]);
+  const float x = (rho * fbar) / q2;
+  if (!(rho > 0.0f && x > 0.0f && x < INFINITY)) return 0;
+  return x >= (float)max_radius ? max_radius : (int)x;   // x > 0: the cast is floorf
+}
+
+// one candidate pixel of a row: lower its key to the row's
+GS_DEV void rv_compete(unsigned long long* a, unsigned long long key) {
+#if GS_RENDER_PRECHECK
+  // Plain load first: a pixel's key only ever decreases during the pass, so a stale value (an older line in this
+  // CU's cache) is never below the current one -- it can let a redundant atomic through, never skip one that
+  // would have lowered the key.  Most rows of a dense map lose to a surfel in front of them and stop here.
+  if (*a <= key) return;
+#endif
+  atomicMin(a, key);
+}
+
+template <bool RADII>
+GS_DEV void rv_key_body(const RvBatch& rb) {
   __shared__ GsCamera cams[GS_RV_MAX_VIEWS];
   const RvSeq& q = rb.s[blockIdx.x % rb.B];
   if ((int)threadIdx.x < rb.V) cams[threadIdx.x] = gs_camera(q.poses16 + 16 * threadIdx.x, q.K16);
@@ -68,7 +98,8 @@ __global__ void __launch_bounds__(256) gs_render_key_kernel(const RvBatch rb) {
     n1 = q.normals[3 * n + 1];
     n2 = q.normals[3 * n + 2];
   }
-  const int r = rb.radius;
+  float rho = 0.0f;
+  if (RADII) rho = q.radii[n];
   for (int v = 0; v < rb.V; ++v) {
     const GsCamera& c = cams[v];
     int h, w;
@@ -80,24 +111,36 @@ __global__ void __launch_bounds__(256) gs_render_key_kernel(const RvBatch rb) {
       const float nc2 = gs_dot3_fma(n0, n1, n2, c.Ri[6], c.Ri[7], c.Ri[8]);
       if (gs_dot3_plain(nc0, nc1, nc2, cq[0], cq[1], cq[2]) >= 0.0f) continue;
     }
+    const int r = RADII ? rv_splat_radius(c, rho, cq[2], rb.radius) : rb.radius;
     const unsigned long long key = ((unsigned long long)__float_as_uint(cq[2]) << 32) | (unsigned long long)(uint32_t)n;
     unsigned long long* kv = reinterpret_cast<unsigned long long*>(q.keys) + (int64_t)v * rb.P;
+    if (RADII) {
+      // r differs from lane to lane.  The loops run over the offsets of the widest square among the wave's lanes that
+      // are still here -- bounds and counters the whole wave shares, in scalar registers -- and a lane sits out the
+      // offsets beyond its own r or outside the image: the trips a wave makes are those of its widest lane either way.
+      int rw = 0;
+      for (int k = 1; k <= rb.radius; ++k)
+        if (__ballot(r >= k) != 0ull) rw = k;
+      for (int dh = -rw; dh <= rw; ++dh)
+        for (int dw = -rw; dw <= rw; ++dw) {
+          const int reach = (dh < 0 ? -dh : dh) > (dw < 0 ? -dw : dw) ? (dh < 0 ? -dh : dh) : (dw < 0 ? -dw : dw);
+          const int hh = h + dh, ww = w + dw;
+          if (reach > r || hh < 0 || hh >= rb.H || ww < 0 || ww >= rb.W) continue;
+          rv_compete(kv + ((int64_t)hh * rb.W + ww), key);
+        }
+      continue;
+    }
     // the (2r+1)^2 square around (h, w), clipped to the image (h, w are inside it)
     const int h0 = h - r < 0 ? 0 : h - r, h1 = h + r > rb.H - 1 ? rb.H - 1 : h + r;
     const int w0 = w - r < 0 ? 0 : w - r, w1 = w + r > rb.W - 1 ? rb.W - 1 : w + r;
     for (int hh = h0; hh <= h1; ++hh)
-      for (int ww = w0; ww <= w1; ++ww) {
-        unsigned long long* a = kv + ((int64_t)hh * rb.W + ww);
-#if GS_RENDER_PRECHECK
-        // Plain load first: a pixel's key only ever decreases during the pass, so a stale value (an older line in this
-        // CU's cache) is never below the current one -- it can let a redundant atomic through, never skip one that
-        // would have lowered the key.  Most rows of a dense map lose to a surfel in front of them and stop here.
-        if (*a <= key) continue;
-#endif
-        atomicMin(a, key);
-      }
+      for (int ww = w0; ww <= w1; ++ww) rv_compete(kv + ((int64_t)hh * rb.W + ww), key);
   }
 }
+
+__global__ void __launch_bounds__(256) gs_render_key_kernel(const RvBatch rb) { rv_key_body<false>(rb); }
+// (named gs_rview_*: see the note on names in front of the reverse mode)
+__global__ void __launch_bounds__(256) gs_rview_radii_key_kernel(const RvBatch rb) { rv_key_body<true>(rb); }
 
 __global__ void __launch_bounds__(256) gs_render_resolve_kernel(const RvBatch rb) {
   const RvSeq& q = rb.s[blockIdx.x % rb.B];
@@ -146,25 +189,41 @@ extern "C" int64_t gs_render_scratch_bytes(int views, int H, int W) {
   return (int64_t)render_scratch_per_seq(views, H, W);
 }
 
-extern "C" int gs_render_map_dc_f32(const gs_render_seq* seqs_host, int B, int L, int H, int W, int radius,
-                                    float min_confidence, int cull_backfaces, void* stream) {
-  GS_REQUIRE(seqs_host && B > 0 && L > 0 && H > 0 && W > 0, "bad arguments");
-  GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
-  GS_REQUIRE(radius >= 0 && radius <= GS_RV_MAX_RADIUS, "radius must be 0, 1, 2 or 3");
-  GS_REQUIRE(!(min_confidence != min_confidence), "min_confidence is NaN");
+// what is wrong with the arguments of a forward entry, or NULL (radii_host: NULL for the plain entry)
+static const char* rv_check(const gs_render_seq* seqs_host, const float* const* radii_host, bool with_radii, int B, int L,
+                            int H, int W, int radius, float min_confidence, int cull_backfaces) {
+  if (!(seqs_host && B > 0 && L > 0 && H > 0 && W > 0)) return "bad arguments";
+  if (!((int64_t)H * W < (1ll << 31))) return "image too large for int32 pixel ids";
+  if (with_radii) {
+    if (!radii_host) return "NULL pointer (radii)";
+    if (!(radius >= 0 && radius <= GS_RV_MAX_SPLAT)) return "max_radius must be 0 ... 8";
+  } else if (!(radius >= 0 && radius <= GS_RV_MAX_RADIUS)) {
+    return "radius must be 0, 1, 2 or 3";
+  }
+  if (min_confidence != min_confidence) return "min_confidence is NaN";
   const bool use_conf = min_confidence > 0.0f;
   for (int b = 0; b < B; ++b) {
     const gs_render_seq& u = seqs_host[b];
-    GS_REQUIRE(u.map.n_bound >= 0, "bad map size");
-    GS_REQUIRE(u.map.n_bound < (1ll << 32), "maps of 2^32 rows or more are not supported (32-bit row index in the key)");
-    GS_REQUIRE(u.poses16 && u.K16 && u.scratch, "NULL pointer");
+    if (!(u.map.n_bound >= 0)) return "bad map size";
+    if (!(u.map.n_bound < (1ll << 32))) return "maps of 2^32 rows or more are not supported (32-bit row index in the key)";
+    if (!(u.poses16 && u.K16 && u.scratch)) return "NULL pointer";
     if (u.map.n_bound > 0) {
-      GS_REQUIRE(u.map.points, "NULL pointer (points)");
-      GS_REQUIRE(u.map.normals || !(u.normal || cull_backfaces), "NULL pointer (normals: needed by the normal image and by cull_backfaces)");
-      GS_REQUIRE(u.map.colors || !u.color, "NULL pointer (colors: needed by the colour image)");
-      GS_REQUIRE(u.map.ccounts || !(u.confidence || use_conf), "NULL pointer (ccounts: needed by the confidence image and by min_confidence)");
+      if (!u.map.points) return "NULL pointer (points)";
+      if (!(u.map.normals || !(u.normal || cull_backfaces)))
+        return "NULL pointer (normals: needed by the normal image and by cull_backfaces)";
+      if (!(u.map.colors || !u.color)) return "NULL pointer (colors: needed by the colour image)";
+      if (!(u.map.ccounts || !(u.confidence || use_conf)))
+        return "NULL pointer (ccounts: needed by the confidence image and by min_confidence)";
+      if (with_radii && !radii_host[b]) return "NULL pointer (radii of a sequence)";
     }
   }
+  return nullptr;
+}
+
+// the launches of a forward entry over checked arguments; radii_host NULL: the plain key pass, `radius` for every row
+static int gs_render_map_launch(const gs_render_seq* seqs_host, const float* const* radii_host, int B, int L, int H, int W,
+                                int radius, float min_confidence, int cull_backfaces, void* stream) {
+  const bool use_conf = min_confidence > 0.0f;
   hipStream_t st = gs_stream(stream);
   const int64_t P = (int64_t)H * W;
   for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
@@ -183,6 +242,7 @@ extern "C" int gs_render_map_dc_f32(const gs_render_seq* seqs_host, int B, int L
         const gs_render_seq& u = seqs_host[c0 + b];
         RvSeq& s = rb.s[b];
         s.points = u.map.points; s.normals = u.map.normals; s.colors = u.map.colors; s.ccounts = u.map.ccounts;
+        s.radii = radii_host ? radii_host[c0 + b] : nullptr;
         s.n = GsCount{u.map.n_bound, u.map.n_dev};
         s.poses16 = u.poses16 + 16 * (int64_t)v0;
         s.K16 = u.K16;
@@ -197,7 +257,10 @@ extern "C" int gs_render_map_dc_f32(const gs_render_seq* seqs_host, int B, int L
       }
       if (n_max > 0) {
         const unsigned blocks = (unsigned)nb * (unsigned)gs_ceil_div(n_max, 256);   // < 8 * 2^24
-        hipLaunchKernelGGL(gs_render_key_kernel, dim3(blocks), dim3(256), 0, st, rb);
+        if (radii_host)
+          hipLaunchKernelGGL(gs_rview_radii_key_kernel, dim3(blocks), dim3(256), 0, st, rb);
+        else
+          hipLaunchKernelGGL(gs_render_key_kernel, dim3(blocks), dim3(256), 0, st, rb);
       }
       const unsigned pblocks = (unsigned)nb * (unsigned)gs_ceil_div((int64_t)rb.V * P, 256);
       hipLaunchKernelGGL(gs_render_resolve_kernel, dim3(pblocks), dim3(256), 0, st, rb);
@@ -205,6 +268,22 @@ extern "C" int gs_render_map_dc_f32(const gs_render_seq* seqs_host, int B, int L
     }
   }
   return GS_OK;
+}
+
+extern "C" int gs_render_map_dc_f32(const gs_render_seq* seqs_host, int B, int L, int H, int W, int radius,
+                                    float min_confidence, int cull_backfaces, void* stream) {
+  const char* bad = rv_check(seqs_host, nullptr, false, B, L, H, W, radius, min_confidence, cull_backfaces);
+  GS_REQUIRE(!bad, bad);
+  return gs_render_map_launch(seqs_host, nullptr, B, L, H, W, radius, min_confidence, cull_backfaces, stream);
+}
+
+// The model view with per-surfel radii: radii_host[b] is a device array of map.n_bound floats (metres) for sequence b.
+extern "C" int gs_render_map_radii_dc_f32(const gs_render_seq* seqs_host, const float* const* radii_host, int B, int L,
+                                          int H, int W, int max_radius, float min_confidence, int cull_backfaces,
+                                          void* stream) {
+  const char* bad = rv_check(seqs_host, radii_host, true, B, L, H, W, max_radius, min_confidence, cull_backfaces);
+  GS_REQUIRE(!bad, bad);
+  return gs_render_map_launch(seqs_host, radii_host, B, L, H, W, max_radius, min_confidence, cull_backfaces, stream);
 }
 
 // ---------------------------------------------------------------- reverse mode of the model view ----
@@ -234,6 +313,7 @@ constexpr int GS_RB_NV = 12;
 struct RbSeq {
   const float* points;
   const float* normals;
+  const float* radii;     // (rows) metres, the radii entry only
   GsCount n;
   int64_t rows;           // rows of the four row outputs (= the host-side bound of the map)
   int nblk;               // blocks of 256 rows
@@ -253,12 +333,13 @@ struct RbSeq {
 };
 struct RbBatch {
   RbSeq s[GS_MAX_BATCH];
-  int B, V, H, W, radius, accumulate;
+  int B, V, H, W, radius, accumulate;   // radius: the radii entry's max_radius
   int64_t P;
   float u_hi, v_hi;
 };
 
-__global__ void __launch_bounds__(256) gs_rview_backward_rows_kernel(const RbBatch rb) {
+template <bool RADII>
+GS_DEV void rv_backward_rows_body(const RbBatch& rb) {
   __shared__ GsCamera cams[GS_RV_MAX_VIEWS];
   __shared__ float trans[GS_RV_MAX_VIEWS][3];
   __shared__ double red[GS_RV_MAX_VIEWS][256 / GS_WAVE][GS_RB_NV];
@@ -288,8 +369,9 @@ __global__ void __launch_bounds__(256) gs_rview_backward_rows_kernel(const RbBat
       n2 = q.normals[3 * n + 2];
     }
   }
+  float rho = 0.0f;
+  if (RADII && live) rho = q.radii[n];
   double aP[3] = {0.0, 0.0, 0.0}, aN[3] = {0.0, 0.0, 0.0}, aC[3] = {0.0, 0.0, 0.0}, aF = 0.0;
-  const int r = rb.radius;
   for (int v = 0; v < rb.V; ++v) {
     const GsCamera& c = cams[v];
     double Z = 0.0, O[3] = {0.0, 0.0, 0.0};
@@ -298,6 +380,7 @@ __global__ void __launch_bounds__(256) gs_rview_backward_rows_kernel(const RbBat
     float cq[3];
     if (live && gs_project_point_hw_q(c, p0, p1, p2, rb.H, rb.W, rb.u_hi, rb.v_hi, h, w, cq)) {
       const int64_t base = (int64_t)v * rb.P;
+      const int r = RADII ? rv_splat_radius(c, rho, cq[2], rb.radius) : rb.radius;   // (the forward's r)
       const int h0 = h - r < 0 ? 0 : h - r, h1 = h + r > rb.H - 1 ? rb.H - 1 : h + r;
       const int w0 = w - r < 0 ? 0 : w - r, w1 = w + r > rb.W - 1 ? rb.W - 1 : w + r;
       for (int hh = h0; hh <= h1; ++hh)
@@ -380,6 +463,11 @@ __global__ void __launch_bounds__(256) gs_rview_backward_rows_kernel(const RbBat
   if (q.ccounts_bar) q.ccounts_bar[n] = (float)aF;
 }
 
+__global__ void __launch_bounds__(256) gs_rview_backward_rows_kernel(const RbBatch rb) { rv_backward_rows_body<false>(rb); }
+__global__ void __launch_bounds__(256) gs_rview_radii_backward_rows_kernel(const RbBatch rb) {
+  rv_backward_rows_body<true>(rb);
+}
+
 // One wave per (sequence, view) adds the partial rows up (rows strided over the lanes, then across the lanes: a fixed
 // order) and writes the 4x4 pose adjoint, bottom row zero.
 __global__ void __launch_bounds__(GS_WAVE) gs_rview_backward_pose_kernel(const RbBatch rb) {
@@ -407,22 +495,33 @@ extern "C" int64_t gs_render_backward_scratch_bytes(int views, int H, int W, int
   return (int64_t)render_backward_scratch_per_seq(views, n_bound);
 }
 
-extern "C" int gs_render_map_backward_dc_f32(const gs_render_backward_seq* seqs_host, int B, int L, int H, int W,
-                                             int radius, void* stream) {
-  GS_REQUIRE(seqs_host && B > 0 && L > 0 && H > 0 && W > 0, "bad arguments");
-  GS_REQUIRE((int64_t)H * W < (1ll << 31), "image too large for int32 pixel ids");
-  GS_REQUIRE(radius >= 0 && radius <= GS_RV_MAX_RADIUS, "radius must be 0, 1, 2 or 3");
+static const char* rb_check(const gs_render_backward_seq* seqs_host, const float* const* radii_host, bool with_radii,
+                            int B, int L, int H, int W, int radius) {
+  if (!(seqs_host && B > 0 && L > 0 && H > 0 && W > 0)) return "bad arguments";
+  if (!((int64_t)H * W < (1ll << 31))) return "image too large for int32 pixel ids";
+  if (with_radii) {
+    if (!radii_host) return "NULL pointer (radii)";
+    if (!(radius >= 0 && radius <= GS_RV_MAX_SPLAT)) return "max_radius must be 0 ... 8";
+  } else if (!(radius >= 0 && radius <= GS_RV_MAX_RADIUS)) {
+    return "radius must be 0, 1, 2 or 3";
+  }
   for (int b = 0; b < B; ++b) {
     const gs_render_backward_seq& u = seqs_host[b];
-    GS_REQUIRE(u.map.n_bound >= 0, "bad map size");
-    GS_REQUIRE(u.map.n_bound < (1ll << 32), "maps of 2^32 rows or more are not supported (32-bit row index in the key)");
-    GS_REQUIRE(u.poses16 && u.K16 && u.index, "NULL pointer");
-    GS_REQUIRE(!u.poses_bar || u.scratch, "NULL pointer (scratch: needed by poses_bar)");
+    if (!(u.map.n_bound >= 0)) return "bad map size";
+    if (!(u.map.n_bound < (1ll << 32))) return "maps of 2^32 rows or more are not supported (32-bit row index in the key)";
+    if (!(u.poses16 && u.K16 && u.index)) return "NULL pointer";
+    if (!(!u.poses_bar || u.scratch)) return "NULL pointer (scratch: needed by poses_bar)";
     if (u.map.n_bound > 0) {
-      GS_REQUIRE(u.map.points, "NULL pointer (points)");
-      GS_REQUIRE(u.map.normals || !u.normal_bar, "NULL pointer (normals: needed by the terms of normal_bar)");
+      if (!u.map.points) return "NULL pointer (points)";
+      if (!(u.map.normals || !u.normal_bar)) return "NULL pointer (normals: needed by the terms of normal_bar)";
+      if (with_radii && !radii_host[b]) return "NULL pointer (radii of a sequence)";
     }
   }
+  return nullptr;
+}
+
+static int gs_render_map_backward_launch(const gs_render_backward_seq* seqs_host, const float* const* radii_host, int B,
+                                         int L, int H, int W, int radius, void* stream) {
   hipStream_t st = gs_stream(stream);
   const int64_t P = (int64_t)H * W;
   for (int c0 = 0; c0 < B; c0 += GS_MAX_BATCH) {
@@ -442,6 +541,7 @@ extern "C" int gs_render_map_backward_dc_f32(const gs_render_backward_seq* seqs_
         const gs_render_backward_seq& u = seqs_host[c0 + b];
         RbSeq& s = rb.s[b];
         s.points = u.map.points; s.normals = u.map.normals;
+        s.radii = radii_host ? radii_host[c0 + b] : nullptr;
         s.n = GsCount{u.map.n_bound, u.map.n_dev};
         s.rows = u.map.n_bound;
         s.nblk = (int)gs_ceil_div(u.map.n_bound, 256);   // < 2^24
@@ -461,11 +561,30 @@ extern "C" int gs_render_map_backward_dc_f32(const gs_render_backward_seq* seqs_
       }
       if (n_max > 0) {
         const unsigned blocks = (unsigned)nb * (unsigned)gs_ceil_div(n_max, 256);   // < 8 * 2^24
-        hipLaunchKernelGGL(gs_rview_backward_rows_kernel, dim3(blocks), dim3(256), 0, st, rb);
+        if (radii_host)
+          hipLaunchKernelGGL(gs_rview_radii_backward_rows_kernel, dim3(blocks), dim3(256), 0, st, rb);
+        else
+          hipLaunchKernelGGL(gs_rview_backward_rows_kernel, dim3(blocks), dim3(256), 0, st, rb);
       }
       if (any_pose) hipLaunchKernelGGL(gs_rview_backward_pose_kernel, dim3(rb.V, nb), dim3(GS_WAVE), 0, st, rb);
       GS_LAUNCH_CHECK();
     }
   }
   return GS_OK;
+}
+
+extern "C" int gs_render_map_backward_dc_f32(const gs_render_backward_seq* seqs_host, int B, int L, int H, int W,
+                                             int radius, void* stream) {
+  const char* bad = rb_check(seqs_host, nullptr, false, B, L, H, W, radius);
+  GS_REQUIRE(!bad, bad);
+  return gs_render_map_backward_launch(seqs_host, nullptr, B, L, H, W, radius, stream);
+}
+
+// Reverse mode of gs_render_map_radii_dc_f32: the radii are a constant of the gradient (they only say which pixels a
+// row could have won); radii_host and max_radius must be those of the forward call.
+extern "C" int gs_render_map_radii_backward_dc_f32(const gs_render_backward_seq* seqs_host, const float* const* radii_host,
+                                                   int B, int L, int H, int W, int max_radius, void* stream) {
+  const char* bad = rb_check(seqs_host, radii_host, true, B, L, H, W, max_radius);
+  GS_REQUIRE(!bad, bad);
+  return gs_render_map_backward_launch(seqs_host, radii_host, B, L, H, W, max_radius, stream);
 }

@@ -134,7 +134,7 @@ def count_drift(counts_a: Sequence[int], counts_b: Sequence[int]) -> Dict[str, o
 
 def depth_residual(pointclouds, rgbdimages, **render_kwargs) -> Dict[str, torch.Tensor]:
     """Depth residual of a surfel map against frames: the map is rendered from every frame's pose with the frames'
-    intrinsics and size (`Pointclouds.render`; render_kwargs: radius, min_confidence, cull_backfaces) and compared with
+    intrinsics and size (`Pointclouds.render`; render_kwargs: radius, min_confidence, cull_backfaces, radii, max_radius) and compared with
     the frame depth.  Per sequence and frame -- (B, L) float64 tensors on the host:
       coverage    pixels with a rendered depth among the pixels with a valid (> 0) frame depth
       mean_abs, median_abs, rmse   of (rendered - frame depth) over the pixels valid in both, in metres
@@ -167,7 +167,7 @@ def depth_residual(pointclouds, rgbdimages, **render_kwargs) -> Dict[str, torch.
 def render_loss(pointclouds, rgbdimages, *, depth_weight: float = 1.0, color_weight: float = 0.0,
                 **render_kwargs) -> torch.Tensor:
     """Photometric / geometric consistency of a surfel map with frames, ON THE AUTOGRAD TAPE: the map is rendered from
-    every frame's pose (`Pointclouds.render(differentiable=True)`; render_kwargs: radius, min_confidence,
+    every frame's pose (`Pointclouds.render(differentiable=True)`; render_kwargs: radius, radii, max_radius, min_confidence,
     cull_backfaces) and compared with the frame.  Per sequence and frame -- a (B, L) float32 tensor on the device:
       depth_weight * mean of 1/2 (rendered - frame depth)^2  +  color_weight * mean of 1/2 |rendered - frame colour|^2
     both means over the pixels valid in both (rendered depth > 0 and frame depth > 0: the mask of `depth_residual`, a

@@ -103,6 +103,13 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
             two solves are two taped calls chained through the initial pose, and weights that require grad get their
             gradient through the `torch.where` that applies the mask.  The parameters are starting points, not tuned to
             any sensor.
+        surfel_radii: False (the default: the calls and the pose bits above) or True: the model view is rendered with
+            the radii of the map's `SurfelRadii` layer (`Pointclouds.render(radii="layer")`), so a view nearer than the
+            capture keeps its pairs and a farther one does not fatten its edges.  `radius` must then be 0, and a map
+            without the layer raises.  Nothing else of the solve changes (it already accepts a surfel behind several
+            pixels): it works with every threshold, `color_weight`, `pixel_weights`, `outlier_mask` and
+            `differentiable=True` (the radii are constants of the gradient).
+        max_radius: 0..8, the cap of a surfel's square in pixels with `surfel_radii`
 
     Unlike the point-cloud-pair providers it needs the map and the live frame themselves: call
     `localize(pointclouds, live_frame, prev_poses)`."""
@@ -113,9 +120,17 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                  color_weight: Union[float, int] = 0.0, huber_delta: Union[float, int] = 0.0,
                  color_huber_delta: Union[float, int] = 0.0, huber_k: Union[float, int] = 0.0,
                  color_huber_k: Union[float, int] = 0.0, deterministic_backward: Optional[bool] = None,
-                 pixel_weights: Optional[Callable] = None, outlier_mask: Optional[dict] = None):
+                 pixel_weights: Optional[Callable] = None, outlier_mask: Optional[dict] = None,
+                 surfel_radii: bool = False, max_radius: int = 3):
         from .. import ops
         who = "ProjectiveICPOdometryProvider"
+        if not isinstance(surfel_radii, bool):
+            raise TypeError("surfel_radii must be of type bool; but was of type {}.".format(type(surfel_radii)))
+        ops._render_radii(who, (), None, 0, max_radius)
+        if surfel_radii and radius != 0:
+            raise ValueError("{}: radius ({}) must be 0 with surfel_radii: every surfel brings its own square (cap it "
+                             "with max_radius)".format(who, radius))
+        self.surfel_radii, self.max_radius = surfel_radii, max_radius
         if pixel_weights is not None and not callable(pixel_weights):
             raise TypeError("pixel_weights must be None or a callable (live frame -> weights); but was of type "
                             "{}.".format(type(pixel_weights)))
@@ -247,8 +262,17 @@ class ProjectiveICPOdometryProvider(OdometryProvider):
                                        "backward pass: the saved association no longer belongs to the map rows (run "
                                        "backward before the next in-place PointFusion.step or prune_, or keep the map "
                                        "update on the autograd tape)")
+        splat = {}
+        if self.surfel_radii:
+            from ..structures.mapfeatures import SurfelRadii
+            layer = pointclouds.map_features
+            if not isinstance(layer, SurfelRadii) or layer._emb is None:
+                raise ValueError("surfel_radii needs a SurfelRadii layer on the map (attach_features(SurfelRadii()), or "
+                                 "PointFusion(surfel_radii=True))")
+            splat = dict(radii=[layer._emb[b][:min(m.n_bound, int(m.points.shape[0])), 0] for b, m in enumerate(maps)],
+                         max_radius=self.max_radius)
         view = ops.render_map_batch(view_maps, view_poses.view(B, 1, 4, 4), K, H, W, radius=self.radius,
-                                    min_confidence=self.min_confidence)
+                                    min_confidence=self.min_confidence, **splat)
         # the joint solve: the view's intensity image and the live colour next to the geometric solve's inputs
         color, model = (fr.rgb_image[:, 0], ops.model_intensity(view.color[:, 0], view.index[:, 0])) if colour \
             else (None, None)

@@ -879,21 +879,112 @@ def update_map_fusion_batch_(maps, vertex, normal, depth, rgb, alpha, poses, K, 
     return cnt, gv, gn, best
 
 
+# ----------------------------------------------------------------------------------- surfel radii
+def surfel_radius(depth, normal, K):
+    """The radius of every depth sample as a surfel (gs_surfel_radius_f32; Keller et al.'s radius with ElasticFusion's
+    cap on oblique surfaces): depth (..., H, W), normal (..., H, W, 3) the frames' LOCAL normal maps, K (..., 4, 4) one
+    per image -> (radius (..., H, W) float32 in metres, valid (..., H, W) bool).  With fbar = (K[0,0] + K[1,1]) / 2:
+    r0 = 0.70710678 z / fbar, radius = min(r0 / |n_z|, 2 r0); valid = z > 0 and a finite, non-zero normal; radius is 0
+    where not valid.  A stack whose images are contiguous and evenly spaced (a slice frames[:, s] of a longer stack) is
+    read in place."""
+    who = "surfel_radius"
+    if not (torch.is_tensor(depth) and torch.is_tensor(normal) and torch.is_tensor(K)):
+        raise TypeError("%s: depth, normal and K must be tensors" % who)
+    if depth.ndim < 2 or tuple(normal.shape) != tuple(depth.shape) + (3,) or \
+            tuple(K.shape) != tuple(depth.shape[:-2]) + (4, 4):
+        raise ValueError("%s: expected depth (..., H, W), normal (..., H, W, 3) and K (..., 4, 4); got %s, %s and %s"
+                         % (who, tuple(depth.shape), tuple(normal.shape), tuple(K.shape)))
+    _warn_detached(who, depth, normal, K)
+    lead, (H, W) = tuple(depth.shape[:-2]), depth.shape[-2:]
+    n = 1
+    for d in lead:
+        n *= int(d)
+
+    def stack(t, inner):
+        """(n, *inner) view of t with contiguous images, in place where its images are evenly spaced"""
+        t = t.detach().to(f32)
+        if len(lead) != 1:
+            t = t.reshape((n,) + tuple(inner))   # (a view where the leading axes collapse to one stride, else a copy)
+        want, acc = [], 1
+        for d in reversed(inner):
+            want.append(acc)
+            acc *= int(d)
+        if tuple(t.stride()[1:]) != tuple(reversed(want)) or (n > 1 and t.stride(0) < acc):
+            t = t.contiguous()
+        return t
+
+    d2, n2, K2 = stack(depth, (H, W)), stack(normal, (H, W, 3)), _c(K.detach().reshape(n, 4, 4))
+    dev = require_device(K2)
+    if d2.device != dev or n2.device != dev:   # (strided stacks: contiguous per image, not as a whole)
+        raise _C.HipExtensionError("gradslam_amd kernels run on the GPU only; all tensors on one device")
+    radius = torch.empty(lead + (H, W), dtype=f32, device=dev)
+    valid = torch.empty(lead + (H, W), dtype=torch.uint8, device=dev)
+    if n:
+        check(lib().gs_surfel_radius_f32(d2.data_ptr(), d2.stride(0) if n > 1 else H * W, n2.data_ptr(),
+                                         n2.stride(0) if n > 1 else H * W * 3, ptr(K2), n, int(H), int(W), ptr(radius),
+                                         ptr(valid), stream(dev)), "gs_surfel_radius_f32")
+    return radius, valid.view(torch.bool)
+
+
 # ----------------------------------------------------------------------------------- the model view
 RenderedViews = collections.namedtuple("RenderedViews", ["depth", "color", "normal", "confidence", "index"])
 
 
+RENDER_MAX_SPLAT = 8
+
+
+def _render_radii(who, maps, radii, radius, max_radius):
+    """The checks of the radii= / max_radius= pair of the model view, before anything else of the call (they need no
+    GPU): radii None -> None; else the per-sequence (n_bound,) float32 tensors as given."""
+    if isinstance(max_radius, bool) or not isinstance(max_radius, int):
+        raise TypeError("%s: max_radius must be of type int; but was of type %s." % (who, type(max_radius)))
+    if not 0 <= max_radius <= RENDER_MAX_SPLAT:
+        raise ValueError("%s: max_radius (%d) must be 0 ... %d." % (who, max_radius, RENDER_MAX_SPLAT))
+    if radii is None:
+        return None
+    if int(radius) != 0:
+        raise ValueError("%s: radius (%d) must be 0 with radii: every row brings its own square (cap it with max_radius)"
+                         % (who, int(radius)))
+    if torch.is_tensor(radii) or len(radii) != len(maps):
+        raise ValueError("%s: radii must be a list of one (N_b,) float32 tensor per sequence (%d)" % (who, len(maps)))
+    for b, (r, m) in enumerate(zip(radii, maps)):
+        rows = int(m[0].shape[0])
+        bound = m[2] if len(m) == 4 else m[4]
+        bound = rows if bound is None else min(int(bound), rows)
+        if not torch.is_tensor(r) or r.dtype != f32:
+            raise ValueError("%s: radii[%d] must be a float32 tensor; got %s"
+                             % (who, b, r.dtype if torch.is_tensor(r) else type(r)))
+        if r.ndim != 1 or int(r.shape[0]) != bound:
+            raise ValueError("%s: radii[%d] must have shape (%d,), one radius per map row; got %s"
+                             % (who, b, bound, tuple(r.shape)))
+    return list(radii)
+
+
+def _radii_pointers(radii, dev):
+    """(host array of B device pointers, the tensors kept alive) of checked radii on `dev`"""
+    held = [_c(r.detach()) for r in radii]
+    if require_device(*held) not in (None, dev):
+        raise _C.HipExtensionError("tensors live on different devices: %s vs %s" % (dev, held[0].device))
+    import ctypes
+    return (ctypes.c_void_p * len(held))(*[t.data_ptr() for t in held]), held
+
+
 def render_map_batch(maps, poses, K, H, W, radius=0, min_confidence=0.0, cull_backfaces=False, out=None,
-                     differentiable=False, guard=None):
+                     differentiable=False, guard=None, radii=None, max_radius=3):
     """The maps of B sequences seen from L poses each (gs_render_map_dc_f32: a z-buffered point render, one key launch
     and one resolve launch per 8 sequences x 4 views).  maps: per sequence a MapRows (features: the (rows, 1) confidence
     count); normals / colors / features may be None, the images that need them are then None.  poses (B, L, 4, 4)
     camera-to-world, K (B, 4, 4).  Returns RenderedViews(depth (B, L, H, W, 1), color (B, L, H, W, 3), normal (B, L, H,
     W, 3), confidence (B, L, H, W, 1), index (B, L, H, W) int64); pixels no row lands on hold 0 (index: -1).  out: a
     RenderedViews (or 5-tuple) of tensors to write into.
+    radii: per sequence an (N_b,) float32 tensor of surfel radii in metres (ops.surfel_radius, a SurfelRadii layer): row n
+    then competes for the (2 r + 1)^2 square of its own r = min(max_radius, floor(radii[n] * fbar / z)) (0 for a radius
+    that is not positive and finite; fbar the mean focal length of K, z the row's depth in the view) through
+    gs_render_map_radii_dc_f32; `radius` must be 0 and max_radius 0 ... 8.  The radii are constants of the gradient.
     differentiable=False: the result is detached (with a warning when an input requires grad).  differentiable=True:
     the four float images are on the autograd tape (RenderMapFunction per sequence: gradients reach the map rows and
     the poses, not K; index stays a plain tensor); `out` is then refused.  guard: see RenderMapFunction."""
+    radii = _render_radii("render_map", maps, radii, radius, max_radius)
     if differentiable:
         if out is not None:
             raise ValueError("render_map: out= cannot be combined with differentiable=True (autograd owns the outputs)")
@@ -902,7 +993,8 @@ def render_map_batch(maps, poses, K, H, W, radius=0, min_confidence=0.0, cull_ba
                              % (len(maps), tuple(poses.shape), tuple(K.shape)))
         poses = poses.to(f32)
         per = [RenderMapFunction.apply(m[0], m[1], m[2], m[3], poses[b], K[b].detach(), m[4], m[5], int(H), int(W),
-                                       int(radius), float(min_confidence), bool(cull_backfaces), guard)
+                                       int(radius), float(min_confidence), bool(cull_backfaces), guard,
+                                       None if radii is None else radii[b], max_radius)
                for b, m in enumerate(maps)]
         if any((per[0][i] is None) != (r[i] is None) for r in per for i in range(5)):
             raise ValueError("render_map: every map of a batch must carry the same attributes")
@@ -954,24 +1046,29 @@ def render_map_batch(maps, poses, K, H, W, radius=0, min_confidence=0.0, cull_ba
         u.depth, u.color, u.normal, u.confidence, u.index = (
             None if t is None else t.data_ptr() + b * sz for t, sz in zip(imgs, per_seq))
         u.scratch = ws.bytes("render%d" % b, nbytes).data_ptr()
+    if radii is not None:
+        rptr, rheld = _radii_pointers(radii, dev)
+        check(L.gs_render_map_radii_dc_f32(seqs, rptr, Bn, Lv, H, W, max_radius, float(min_confidence),
+                                           1 if cull_backfaces else 0, stream(dev)), "gs_render_map_radii_dc_f32")
+        return RenderedViews(*imgs)
     check(L.gs_render_map_dc_f32(seqs, Bn, Lv, H, W, int(radius), float(min_confidence), 1 if cull_backfaces else 0,
                                  stream(dev)), "gs_render_map_dc_f32")
     return RenderedViews(*imgs)
 
 
 def render_map(points, normals, colors, ccounts, poses, K, H, W, n_dev=None, radius=0, min_confidence=0.0,
-               cull_backfaces=False, out=None, differentiable=False):
+               cull_backfaces=False, out=None, differentiable=False, radii=None, max_radius=3):
     """One map seen from L poses: render_map_batch for B = 1 without the batch dimension.  poses (L, 4, 4) or (4, 4),
     K (4, 4); n_dev: device int64[1] holding the actual row count (points.shape[0] is then an upper bound).  Returns
     RenderedViews(depth (L, H, W, 1), color (L, H, W, 3), normal (L, H, W, 3), confidence (L, H, W, 1), index (L, H, W)).
-    differentiable: see render_map_batch."""
+    radii: an (N,) float32 tensor, with max_radius; differentiable: see render_map_batch."""
     if poses.ndim == 2:
         poses = poses.unsqueeze(0)
     if out is not None:
         out = tuple(None if t is None else t.unsqueeze(0) for t in out)
     r = render_map_batch([(points, normals, colors, ccounts, None, n_dev)], poses.unsqueeze(0), K.reshape(1, 4, 4), H, W,
                          radius=radius, min_confidence=min_confidence, cull_backfaces=cull_backfaces, out=out,
-                         differentiable=differentiable)
+                         differentiable=differentiable, radii=None if radii is None else [radii], max_radius=max_radius)
     return RenderedViews(*[None if t is None else t[0] for t in r])
 
 
@@ -2604,7 +2701,8 @@ def bilateral_depth(depth, radius=3, sigma_space=2.0, sigma_range=0.03, out=None
     return (res, wsum) if return_wsum else res
 
 
-def render_map_backward_batch(maps, poses, K, index, upstream, H, W, radius=0, want=(True, True, True, True, True)):
+def render_map_backward_batch(maps, poses, K, index, upstream, H, W, radius=0, want=(True, True, True, True, True),
+                              radii=None, max_radius=3):
     """Reverse mode of render_map_batch for B sequences in ONE call of gs_render_map_backward_dc_f32 (8 sequences and 4
     views per launch).  maps: per sequence a MapRows or its short form, as given to the forward (points and normals
     are read; normals may be None when upstream[2] is); poses (B, L, 4, 4), K (B, 4, 4), index (B, L, H, W) int64: the
@@ -2612,7 +2710,9 @@ def render_map_backward_batch(maps, poses, K, index, upstream, H, W, radius=0, w
     W, 3), confidence_bar (B, L, H, W[, 1])), any of them None (its terms are skipped)..  want: which of (points_bar,
     normals_bar, colors_bar, ccounts_bar, poses_bar) to compute..  Returns (per-sequence list of (points_bar (rows, 3),
     normals_bar (rows, 3), colors_bar (rows, 3), ccounts_bar (rows, 1)) with None where not wanted, poses_bar (B, L, 4,
-    4) or None); rows = points.shape[0], rows at or beyond the count hold zeros."""
+    4) or None); rows = points.shape[0], rows at or beyond the count hold zeros.
+    radii, max_radius: those of the forward (gs_render_map_radii_backward_dc_f32; `radius` must then be 0)."""
+    radii = _render_radii("render_map_backward", maps, radii, radius, max_radius)
     poses, K, index = _c(poses.detach()), _c(K.detach()), _c(index, torch.int64)
     ups = [None if t is None else _c(t.detach()) for t in upstream]
     dev = require_device(poses, K, index, *ups)
@@ -2650,6 +2750,11 @@ def render_map_backward_batch(maps, poses, K, index, upstream, H, W, radius=0, w
         if T_bar is not None:
             u.poses_bar = T_bar.data_ptr() + b * Lv * 64
             u.scratch = ws.bytes("render_bwd%d" % b, L.gs_render_backward_scratch_bytes(Lv, H, W, n_bound)).data_ptr()
+    if radii is not None:
+        rptr, rheld = _radii_pointers(radii, dev)
+        check(L.gs_render_map_radii_backward_dc_f32(seqs, rptr, Bn, Lv, H, W, max_radius, stream(dev)),
+              "gs_render_map_radii_backward_dc_f32")
+        return rows_out, T_bar
     check(L.gs_render_map_backward_dc_f32(seqs, Bn, Lv, H, W, int(radius), stream(dev)), "gs_render_map_backward_dc_f32")
     return rows_out, T_bar
 
@@ -2663,19 +2768,21 @@ class RenderMapFunction(torch.autograd.Function):
     use reach the kernel as NULL (their terms are skipped; no zero images are made up).  The backward re-projects the
     map rows, so the map buffers must hold at backward time what they held at the forward (run backward before the next
     in-place step); in-place steps write through raw pointers, which torch's version counters do not see, so a caller
-    that can tell passes `guard`, a callable that raises when the map has changed (Pointclouds.render does)."""
+    that can tell passes `guard`, a callable that raises when the map has changed (Pointclouds.render does).  radii,
+    max_radius: the model view with per-surfel radii (the gs_render_map_radii_* entries); the radii get no gradient."""
 
     @staticmethod
     def forward(ctx, points, normals, colors, ccounts, poses, K, n_bound, n_dev, H, W, radius, min_confidence,
-                cull_backfaces, guard=None):
+                cull_backfaces, guard=None, radii=None, max_radius=3):
         if poses.ndim != 3 or tuple(poses.shape[1:]) != (4, 4) or tuple(K.shape) != (4, 4):
             raise ValueError("render_map: expected poses (L, 4, 4) and K (4, 4) per map; got %s and %s"
                              % (tuple(poses.shape), tuple(K.shape)))
         r = render_map_batch([(points, normals, colors, ccounts, n_bound, n_dev)], poses.unsqueeze(0), K.unsqueeze(0),
-                             H, W, radius=radius, min_confidence=min_confidence, cull_backfaces=cull_backfaces)
+                             H, W, radius=radius, min_confidence=min_confidence, cull_backfaces=cull_backfaces,
+                             radii=None if radii is None else [radii], max_radius=max_radius)
         r = RenderedViews(*[None if t is None else t[0] for t in r])
-        ctx.save_for_backward(points, normals, poses, K, r.index, n_dev)
-        ctx.geom = (H, W, radius, n_bound)
+        ctx.save_for_backward(points, normals, poses, K, r.index, n_dev, None if radii is None else radii.detach())
+        ctx.geom = (H, W, radius, n_bound, max_radius)
         ctx.shapes = tuple(None if t is None else tuple(t.shape) for t in (points, normals, colors, ccounts))
         ctx.guard = guard
         ctx.set_materialize_grads(False)   # an image the loss does not use arrives as None, not as a zero image
@@ -2686,19 +2793,20 @@ class RenderMapFunction(torch.autograd.Function):
     def backward(ctx, depth_bar, color_bar, normal_bar, conf_bar, _index_bar):
         if ctx.guard is not None:
             ctx.guard()
-        points, normals, poses, K, index, n_dev = ctx.saved_tensors
-        H, W, radius, n_bound = ctx.geom
+        points, normals, poses, K, index, n_dev, radii = ctx.saved_tensors
+        H, W, radius, n_bound, max_radius = ctx.geom
         need = ctx.needs_input_grad
         ups = (depth_bar, color_bar, normal_bar, conf_bar)
         if all(t is None for t in ups):
-            return (None,) * 14
+            return (None,) * 16
         want = tuple(bool(need[i]) and ctx.shapes[i] is not None for i in range(4)) + (bool(need[4]),)
         rows_out, T_bar = render_map_backward_batch([(points, normals, n_bound, n_dev)], poses.unsqueeze(0),
                                                     K.unsqueeze(0), index.unsqueeze(0),
                                                     [None if t is None else t.unsqueeze(0) for t in ups], H, W, radius,
-                                                    want=want)
+                                                    want=want, radii=None if radii is None else [radii],
+                                                    max_radius=max_radius)
         outs = [None if t is None else t.view(shape) for t, shape in zip(rows_out[0], ctx.shapes)]
-        return (outs[0], outs[1], outs[2], outs[3], None if T_bar is None else T_bar[0]) + (None,) * 9
+        return (outs[0], outs[1], outs[2], outs[3], None if T_bar is None else T_bar[0]) + (None,) * 11
 
 
 # ----------------------------------------------------------------------------------- K7 (autograd)

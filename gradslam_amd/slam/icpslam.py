@@ -62,7 +62,13 @@ class ICPSLAM(nn.Module):
     `odom_outlier_mask` (None by default, `odom="projicp"` only): a dict of the outlier mask's parameters
     (`ProjectiveICPOdometryProvider(outlier_mask=...)`: hi, lo, floor, min_support, grow, grow_depth, refine_iters, any
     subset): after the configured solve the outlier regions of the live frame are masked and refine_iters more
-    iterations run without them.  The mask of the last localisation is `odomprov.last_outlier_mask`."""
+    iterations run without them.  The mask of the last localisation is `odomprov.last_outlier_mask`.
+
+    `odom_surfel_radii` (False by default, `odom="projicp"` only): the model view of the projective ICP is rendered with
+    the radii of the map's `SurfelRadii` layer (`ProjectiveICPOdometryProvider(surfel_radii=True)`).  Only a driver that
+    fuses feature layers can keep such a map: `PointFusion` takes it, `ICPSLAM` itself raises at construction."""
+
+    _fuses_features = False   # (ICPSLAM.step refuses a map with a feature layer: see _check_feature_layer)
 
     def __init__(self, *, odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0,
@@ -72,9 +78,18 @@ class ICPSLAM(nn.Module):
                  huber_delta: Union[float, int] = 0.0, color_huber_delta: Union[float, int] = 0.0,
                  huber_k: Union[float, int] = 0.0, color_huber_k: Union[float, int] = 0.0,
                  odom_deterministic_backward: Optional[bool] = None, odom_pixel_weights=None,
-                 odom_outlier_mask: Optional[dict] = None):
+                 odom_outlier_mask: Optional[dict] = None, odom_surfel_radii: bool = False):
         super().__init__()
         from .. import ops
+        if not isinstance(odom_surfel_radii, bool):
+            raise TypeError("odom_surfel_radii must be of type bool; but was of type {}.".format(type(odom_surfel_radii)))
+        if odom_surfel_radii and odom != "projicp":
+            raise ValueError("odom_surfel_radii is a switch of odom='projicp' (got odom={!r})".format(odom))
+        if odom_surfel_radii and not self._fuses_features:
+            raise ValueError("odom_surfel_radii needs a map with a SurfelRadii layer, and {}.step is not supported on a "
+                             "map with a feature layer attached: only PointFusion fuses features".format(
+                                 type(self).__name__))
+        self.odom_surfel_radii = odom_surfel_radii
         if odom_pixel_weights is not None and not callable(odom_pixel_weights):
             raise TypeError("odom_pixel_weights must be None or a callable (live frame -> weights); but was of type "
                             "{}.".format(type(odom_pixel_weights)))
@@ -131,7 +146,8 @@ class ICPSLAM(nn.Module):
                                                      color_huber_k=color_huber_k,
                                                      deterministic_backward=odom_deterministic_backward,
                                                      pixel_weights=odom_pixel_weights,
-                                                     outlier_mask=odom_outlier_mask)
+                                                     outlier_mask=odom_outlier_mask,
+                                                     **(dict(surfel_radii=True) if odom_surfel_radii else {}))
         if odom != "projicp":
             # (checked after every other keyword, as the provider does: today's refusals and their order stay)
             ProjectiveICPOdometryProvider._outlier_mask(odom_outlier_mask)

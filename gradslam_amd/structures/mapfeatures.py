@@ -10,7 +10,7 @@ follows the map through `prune_`, `carve_`, `voxel_downsample_` and the drivers'
 (`ops.compact_features_batch` with the mask the map itself is compacted with)."""
 import torch
 
-__all__ = ["MapFeatures"]
+__all__ = ["MapFeatures", "SurfelRadii"]
 
 _DTYPES = (torch.float32, torch.float16)
 
@@ -172,3 +172,38 @@ class MapFeatures(object):
         """follows a prune of the map through boolean indexing (CPU maps, maps on the autograd tape)"""
         self._emb[b] = self._emb[b][:rows][selection]
         self._weight[b] = self._weight[b][:rows][selection]
+
+
+class SurfelRadii(MapFeatures):
+    r"""The radius of every surfel (Keller et al.), as a one-channel float32 layer that makes its own feature image:
+
+        pointclouds.attach_features(SurfelRadii())
+        slam.step(pointclouds, live, prev, inplace=True)                 # no features=: the layer samples the frame
+        view = pointclouds.render(K, poses, H, W, radii="layer")
+
+    On every in-place `PointFusion.step` the frame the map update saw yields a radius per pixel (`ops.surfel_radius` on
+    its depth, local normal map and intrinsics: 0.7071 z / f over |n_z|, at most twice the fronto-parallel value), which
+    is fused like any feature with the colours' weights: a matched surfel takes the confidence-weighted mean, an appended
+    one its sample's radius; a pixel without a usable normal leaves a matched surfel alone and appends radius 0, weight 0.
+    `features=` on such a map raises.  `radii_list` are the (N_b,) radii in metres."""
+
+    def __init__(self):
+        super().__init__(1, torch.float32)
+
+    @property
+    def radii_list(self):
+        """per sequence the (N_b,) radii of the map's rows: views of the live buffers"""
+        return [f[:, 0] for f in self.features_list]
+
+    def _frame_features(self, features, features_valid, B, H, W):
+        if features is not None or features_valid is not None:
+            raise ValueError("features were given, but the map's layer is a SurfelRadii: it makes its own feature image "
+                             "from the frame (a map has one layer; pass radii= to render explicitly to keep yours)")
+        return None, None
+
+    def _sample(self, frame):
+        """(feat (B, H, W, 1), valid (B, H, W)) of a channels-last frame of sequence length 1"""
+        from .. import ops
+        radius, valid = ops.surfel_radius(frame.depth_image[:, 0, ..., 0].detach(), frame.normal_map[:, 0].detach(),
+                                          frame.intrinsics[:, 0].detach())
+        return radius.unsqueeze(-1), valid

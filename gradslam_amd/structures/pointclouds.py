@@ -610,7 +610,7 @@ class Pointclouds(object):
     # ------------------------------------------------------------------ the model view
     def render(self, intrinsics: torch.Tensor, poses: torch.Tensor, height: int, width: int, *, radius: int = 0,
                min_confidence: float = 0.0, cull_backfaces: bool = False, return_extras: bool = False,
-               differentiable: bool = False):
+               differentiable: bool = False, radii=None, max_radius: int = 3):
         r"""The map seen from camera poses: a z-buffered point render (HIP; the result is detached unless
         `differentiable` is set).
 
@@ -623,6 +623,13 @@ class Pointclouds(object):
             poses: (B, L, 4, 4) camera-to-world
             radius: 0..3; a point competes for the (2 radius + 1)^2 pixel square around its pixel (closes the holes of
                 a view that is nearer than the capture)
+            radii: per-surfel splat sizes instead of one `radius` (which must then be 0).  "layer": the radii of the
+                attached `SurfelRadii` layer; or a list of B (N_b,) float32 tensors, radii in metres.  A point of
+                radius rho at depth z in a view competes for the square of half-width min(max_radius, floor(rho fbar /
+                z)), fbar the mean focal length of `intrinsics`: about one pixel-footprint of the sample it was fused
+                from, so a nearer view closes its holes and a farther one does not fatten.  A radius that is 0,
+                negative, NaN or inf splats one pixel.  Constants of the gradient.
+            max_radius: 0..8, the cap of that half-width
             min_confidence: points whose confidence count (the first and only feature channel) is below it are skipped
             cull_backfaces: points whose normal n has n.q >= 0 at their camera-frame position q (facing away from the
                 camera, or edge-on) are skipped.  Mind the orientation of the map's normals: the frame normals of
@@ -657,6 +664,10 @@ class Pointclouds(object):
         if tuple(intrinsics.shape) != (B, 1, 4, 4):
             raise ValueError("intrinsics should have shape {}, but had shape {}".format((B, 1, 4, 4),
                                                                                      tuple(intrinsics.shape)))
+        if radii is not None and not isinstance(radii, str):
+            # a caller's tensors are sized by the counts: make the host-side bounds exact (one read-back; the device
+            # counts stay in charge), before the guard below takes its snapshot of the map
+            self._tighten_counts()
         guard = None
         if differentiable:
             generation = self._generation
@@ -666,9 +677,19 @@ class Pointclouds(object):
                     raise RuntimeError("the map was changed in place after render(differentiable=True) and before its "
                                        "backward pass: the saved winners no longer belong to the map rows (run backward "
                                        "before the next PointFusion.step, or render again)")
-        out = ops.render_map_batch(self._map_rows(), poses, intrinsics[:, 0], int(height), int(width), radius=radius,
+        maps = self._map_rows()
+        if isinstance(radii, str):
+            from .mapfeatures import SurfelRadii
+            if radii != "layer":
+                raise ValueError("radii must be None, 'layer' or a list of (N_b,) float32 tensors; got {!r}".format(radii))
+            layer = self._feature_layer
+            if not isinstance(layer, SurfelRadii) or layer._emb is None:
+                raise ValueError("radii='layer' needs a SurfelRadii layer on the map (attach_features(SurfelRadii()), or "
+                                 "PointFusion(surfel_radii=True)); pass the radii as a list otherwise")
+            radii = [layer._emb[b][:min(m.n_bound, int(m.points.shape[0])), 0] for b, m in enumerate(maps)]
+        out = ops.render_map_batch(maps, poses, intrinsics[:, 0], int(height), int(width), radius=radius,
                                    min_confidence=min_confidence, cull_backfaces=cull_backfaces,
-                                   differentiable=differentiable, guard=guard)
+                                   differentiable=differentiable, guard=guard, radii=radii, max_radius=max_radius)
         frames = RGBDImages(out.color, out.depth, intrinsics.detach().to(torch.float32),
                             poses.to(torch.float32) if differentiable else poses.detach().to(torch.float32))
         if return_extras:

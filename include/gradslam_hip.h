@@ -623,6 +623,38 @@ GS_API int64_t gs_render_backward_scratch_bytes(int views, int H, int W, int64_t
 GS_API int gs_render_map_backward_dc_f32(const gs_render_backward_seq* seqs_host, int B, int L, int H, int W,
                                          int radius, void* stream);
 
+/* ------------------------------------------------------------------ surfel radii ------
+ * Keller et al. give every surfel a radius; the map fuses it like any per-surfel attribute (a one-channel float32
+ * feature layer, gs_fuse_features_batch with the colour fusion's weights) and the model view turns it into a splat size.
+ *
+ * gs_surfel_radius_f32: the radius of every depth sample of n images.  depth: image i starts at depth + i *
+ * depth_stride (H * W contiguous floats); normal: the frames' LOCAL normal maps, image i at normal + i * normal_stride
+ * (H * W * 3 contiguous floats); K16: n intrinsics matrices (n, 16).  float32, one rounding per operation, no FMA:
+ *   fbar = 0.5f * (K[0][0] + K[1][1]);  r0 = (0.70710678f * z) / fbar;  c = fabsf(n_z)
+ *   rho  = fminf(r0 / c, 2.0f * r0)   (c == 0: 2.0f * r0)      -- Keller's radius, ElasticFusion's cap on oblique surfaces
+ *   valid = z > 0 and n finite and not all zero;  rho = +0.0f where not valid
+ * radius (n, H, W) float32 and valid (n, H, W) uint8 (may be NULL) are contiguous outputs.
+ *
+ * gs_render_map_radii_dc_f32: gs_render_map_dc_f32 with a square per row.  radii_host: a host array of B device
+ * pointers, radii_host[b] = map.n_bound floats (metres) for sequence b.  Row n of radius rho whose camera-frame depth in a
+ * view is q2 > 0 competes for the (2 r + 1)^2 square around its pixel, clipped to the image, with
+ *   x = (rho * fbar) / q2   (float32, two operations, fbar of the view's K16 as above)
+ *   r = (rho > 0 and 0 < x < inf) ? min(max_radius, (int)floorf(x)) : 0          max_radius in 0..8
+ * (a radius that is 0, negative, NaN or +inf gives r = 0).  Keys, atomicMin, the resolve pass, the filters, the outputs
+ * and the scratch (gs_render_scratch_bytes) are those of gs_render_map_dc_f32: the images are a pure function of the
+ * inputs, and where every row of a view has r = k <= 3 they are bit for bit those of radius = k.
+ *
+ * gs_render_map_radii_backward_dc_f32: gs_render_map_backward_dc_f32 for that forward (radii_host and max_radius must be
+ * the forward's; scratch: gs_render_backward_scratch_bytes).  Each row is re-projected with its own r to find the pixels
+ * it could have won; the radii are a constant of the gradient, like the winners.  The same sums in the same order: no
+ * float atomics, bitwise reproducible. */
+GS_API int gs_surfel_radius_f32(const float* depth, int64_t depth_stride, const float* normal, int64_t normal_stride,
+                                const float* K16, int64_t n, int H, int W, float* radius, uint8_t* valid, void* stream);
+GS_API int gs_render_map_radii_dc_f32(const gs_render_seq* seqs_host, const float* const* radii_host, int B, int L, int H,
+                                      int W, int max_radius, float min_confidence, int cull_backfaces, void* stream);
+GS_API int gs_render_map_radii_backward_dc_f32(const gs_render_backward_seq* seqs_host, const float* const* radii_host,
+                                               int B, int L, int H, int W, int max_radius, void* stream);
+
 /* ------------------------------------------------------------------ pruning the map ------
  * A stable, out-of-place compaction of B maps (the reference never removes a surfel; Keller et al.'s point-based fusion
  * drops those that stay unstable).  With n = min(*n_dev, n_bound) (n_bound when n_dev is NULL), row r < n survives iff

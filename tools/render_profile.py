@@ -6,6 +6,10 @@
     python tools/render_profile.py --kernel-stats small=CSV large=CSV [--out FILE]
                                                                 algorithmic bytes over the kernel times of those runs
     python tools/render_profile.py --backward [--out FILE]      forward and backward of the differentiable render, timed
+    python tools/render_profile.py --projicp-window [--json FILE]  (also in a checkout of the parent commit: its side)
+    python tools/render_profile.py --radii [--steps 20 200] [--json FILE] [--parent-json FILE] [--out FILE]
+                                                                the view with per-surfel radii against radius 0, 1 and 3,
+                                                                and a projective-ICP window with and without them
 
 new       one Pointclouds.render call, one view, all five images.
 baseline  the same five images from ops.project_map + ops.transform_points + int64 key packing +
@@ -249,6 +253,125 @@ def backward_times(out):
             f.write(text)
 
 
+def projicp_window(layer_kw=None, runs=3):
+    """ms per step of 20 steps of PointFusion(odom="projicp") on one 640x480 sequence of the benchmark scene after 5
+    frames, `runs` times (wall time, device idle at both ends).  layer_kw None: no layer, calls that every version of the
+    package with odom="projicp" has -- `python tools/render_profile.py --projicp-window --json FILE` in a checkout of the
+    parent commit (with this file copied in) gives the other side of the comparison; else the map carries a SurfelRadii
+    layer and the driver takes layer_kw."""
+    import time
+    import torch
+    import gradslam_amd as gs
+    from gradslam_amd.datasets.synthetic import make_sequence
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    s = make_sequence(25, 480, 640, seed=0)
+    out = []
+    for _ in range(runs):
+        poses = T(s["poses"][None])
+        poses[:, 1:] = poses[:, :1]
+        frames = gs.RGBDImages(T(s["colors"][None]), T(s["depths"][None]), T(s["intrinsics"][None]), poses)
+        if layer_kw is None:
+            slam, pc = gs.slam.PointFusion(odom="projicp", device="cuda"), gs.Pointclouds(device="cuda")
+        else:
+            slam = gs.slam.PointFusion(odom="projicp", device="cuda", surfel_radii=True, **layer_kw)
+            pc = gs.Pointclouds(device="cuda").attach_features(gs.SurfelRadii())
+        prev = None
+        for f in range(25):
+            if f == 5:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            live = frames[:, f]
+            pc, _ = slam.step(pc, live, prev, inplace=True)
+            prev = live
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) / 20 * 1e3)
+    return out
+
+
+def radii_times(steps, out, json_out, parent_json=None):
+    """The model view with the radii of a SurfelRadii layer (Pointclouds.render(radii="layer"), max_radius 3) against the
+    constant radii 0, 1 and 3: one 640x480 view, index and depth image only (what the projective ICP renders: the key
+    pass dominates), of the map of one sequence of the benchmark scene after `steps` frames (PointFusion, gradICP
+    odometry, seed 0), seen from the last pose -- from where the map was built.  Then a window of 20 steps of
+    PointFusion(odom="projicp") on a map of 5 frames (projicp_window): without a layer, with the layer, and with the layer
+    and odom_surfel_radii, three runs each; parent_json: the figures of --projicp-window from a checkout of the parent
+    commit, which go into the report next to them."""
+    import json
+    import torch
+    import gradslam_amd as gs
+    from gradslam_amd import ops
+    from gradslam_amd.datasets.synthetic import make_sequence
+    assert torch.cuda.is_available(), "needs the MI355X"
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    H, W = 480, 640
+    report = {"tool": "tools/render_profile.py --radii", "size": [H, W], "views": []}
+    lines = ["# tools/render_profile.py --radii: ops.render_map_batch (one 640x480 view, depth and index) with radius 0 / 1 / 3",
+             "# and with the radii of the map's SurfelRadii layer (max_radius 3); microseconds per call, device events, the",
+             "# variants alternating"]
+    med = lambda x: float(np.median(x))  # noqa: E731
+    for n_steps in steps:
+        s = make_sequence(n_steps, H, W, seed=0)
+        poses = T(s["poses"][None])
+        poses[:, 1:] = poses[:, :1]
+        frames = gs.RGBDImages(T(s["colors"][None]), T(s["depths"][None]), T(s["intrinsics"][None]), poses)
+        pc, rec = gs.slam.PointFusion(odom="gradicp", device="cuda", surfel_radii=True)(frames)
+        n = int(pc.num_points_per_pointcloud[0])
+        maps = [m._replace(normals=None, colors=None, features=None) for m in pc._map_rows()]
+        radii = [t.contiguous() for t in pc.map_features.radii_list]
+        K, pose = frames.intrinsics[:, 0].contiguous(), rec[:, -1:].contiguous()
+        calls = {"radius=%d" % r: (lambda r=r: ops.render_map_batch(maps, pose, K, H, W, radius=r)) for r in (0, 1, 3)}
+        calls["radii"] = lambda: ops.render_map_batch(maps, pose, K, H, W, radii=radii, max_radius=3)
+        calls["radii, cap 8"] = lambda: ops.render_map_batch(maps, pose, K, H, W, radii=radii, max_radius=8)
+        # the same map from half the distance along the optical axis of the last pose: wider squares
+        near = pose.clone()
+        near[:, 0, :3, 3] += 1.0 * pose[:, 0, :3, 2]
+        calls["radius=1, 1 m nearer"] = lambda: ops.render_map_batch(maps, near, K, H, W, radius=1)
+        calls["radii, 1 m nearer"] = lambda: ops.render_map_batch(maps, near, K, H, W, radii=radii, max_radius=3)
+        calls["radii, cap 8, 1 m nearer"] = lambda: ops.render_map_batch(maps, near, K, H, W, radii=radii, max_radius=8)
+        view = {"steps": n_steps, "surfels": n, "us": {}, "covered": {}}
+        for k, fn in calls.items():
+            for _ in range(3):
+                fn()
+            view["covered"][k] = int((fn().index >= 0).sum())
+        torch.cuda.synchronize()
+        reps = {k: max(10, int(math.ceil(5000.0 / timed(torch, fn, 10)))) for k, fn in calls.items()}
+        t = {k: [] for k in calls}
+        for _ in range(9):
+            for k, fn in calls.items():
+                t[k].append(timed(torch, fn, reps[k]))
+        fb = float(K[0, 0, 0] + K[0, 1, 1]) / 2
+        lines += ["", "## after %d steps: %d surfels, mean radius %.2f mm (%.2f px at 2 m)"
+                  % (n_steps, n, 1e3 * float(radii[0].mean()), float(radii[0].mean()) * fb / 2.0)]
+        for k in calls:
+            view["us"][k] = {"median": med(t[k]), "min": min(t[k]), "max": max(t[k])}
+            lines.append("%-26s median %9.1f us   min %9.1f   max %9.1f   covered %d of %d"
+                         % (k, med(t[k]), min(t[k]), max(t[k]), view["covered"][k], H * W))
+        report["views"].append(view)
+        del pc, frames, maps, radii
+        torch.cuda.empty_cache()
+    # the tracking window
+    window = {"steps": 20, "ms_per_step": {}}
+    for name, kw in (("projicp", None), ("projicp, SurfelRadii layer", {}),
+                     ("projicp, SurfelRadii layer, odom_surfel_radii", dict(odom_surfel_radii=True))):
+        runs = projicp_window(kw)
+        window["ms_per_step"][name] = runs
+        lines.append("%-46s 20 steps after 5: %s ms per step (three runs)" % (name, ", ".join("%.3f" % x for x in runs)))
+    if parent_json:
+        window["ms_per_step"]["projicp, parent commit"] = runs = json.load(open(parent_json))["ms_per_step"]
+        lines.append("%-46s 20 steps after 5: %s ms per step (three runs)" % ("projicp, parent commit",
+                                                                              ", ".join("%.3f" % x for x in runs)))
+    report["projicp_window"] = window
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out:
+        with open(out, "a") as f:
+            f.write(text)
+    if json_out:
+        with open(json_out, "w") as f:
+            json.dump(report, f, indent=1, sort_keys=True)
+            f.write("\n")
+
+
 def trace_run(which, calls=30):
     import torch
     import gradslam_amd as gs
@@ -288,8 +411,22 @@ if __name__ == "__main__":
     ap.add_argument("--trace-run", choices=["small", "large"], default=None)
     ap.add_argument("--kernel-stats", nargs="+", metavar="NAME=CSV,n,H,W,hits", default=None)
     ap.add_argument("--backward", action="store_true", help="time forward and backward of the differentiable render")
+    ap.add_argument("--radii", action="store_true", help="time the view with per-surfel radii against radius 0, 1 and 3")
+    ap.add_argument("--steps", nargs="+", type=int, default=[20, 200], help="--radii: map sizes in frames")
+    ap.add_argument("--json", default=None, help="--radii / --projicp-window: write the figures to this file")
+    ap.add_argument("--projicp-window", action="store_true",
+                    help="only the plain odom='projicp' window of --radii (runs in a checkout of the parent commit too)")
+    ap.add_argument("--parent-json", default=None, help="--radii: the --projicp-window figures of the parent commit")
     a = ap.parse_args()
-    if a.backward:
+    if a.projicp_window:
+        import json
+        runs = projicp_window()
+        print("projicp, no layer: %s ms per step" % ", ".join("%.3f" % x for x in runs))
+        if a.json:
+            json.dump({"ms_per_step": runs}, open(a.json, "w"))
+    elif a.radii:
+        radii_times(a.steps, a.out, a.json, a.parent_json)
+    elif a.backward:
         backward_times(a.out)
     elif a.trace_run:
         trace_run(a.trace_run)
